@@ -19,6 +19,10 @@ thread legs) goes to stderr ("bench.py detail: ...") and to gpurun_out/bench_det
     python bench.py --gpus 1 --steps 200 --warmup 200
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 200 --warmup 200
+
+A plain run times the headline config alone (set up, settle, W warm-up steps, K timed steps, the line).  --full adds every
+other measurement (the other configs, the cold / paced / bus-form legs, the CPU baseline, the host path); --dump-outputs DIR
+writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -83,6 +87,13 @@ def parse():
     ap.add_argument("--tile", type=int, default=None,
                     help="channel-tiled HBM layout [N/W][B][W]; 0 = frame-major [B][N].  Default: the config's own `tile` entry, else 256 (the "
                          "engine-native tiling; tools/archive/r03_cfg2_layout_ab.sh, r03_cfg5_layout_ab.sh sweep it)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: configs 2 / 3 / 4 and config 4's other sweeps, the cold, "
+                         "paced and two-calls-late legs, the exchange forms of N > 1, the CPU baseline and the host path (--paced implies it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as float32 .npy files: DIR/out.npy = that block's "
+                         "samples [frames][channels] (every channel, or a fixed seeded sample of them: at most 32 MB), DIR/mix.npy = "
+                         "the Output node's bus of that block.  N > 1: one pair per rank (out_rank<r>.npy, mix_rank<r>.npy)")
     return ap.parse_args()
 
 
@@ -359,9 +370,29 @@ def paced_run(torch, eng, xs, y, mixes, B, total_channels, stream, seconds, pbus
             "deadline_misses": int((lat > period).sum())}
 
 
-def measure(ctx, args, cfg_name, steps, warmup, overrides=None, extras=False):
+DUMP_OUT_BYTES = 32 << 20     # --dump-outputs: out.npy's share (over all ranks) of the 64 MB a dump may take
+
+
+def dump_outputs(torch, out_dir, y, mix, N, B, tile, world, rank):
+    """--dump-outputs: the last timed block as its caller receives it, float32.  out.npy = the block's samples [B][S], frame-major,
+    of every channel if they fit DUMP_OUT_BYTES, else of S channels drawn once with SEED (sorted); mix.npy = its bus [B]."""
+    import numpy as np
+    S = min(N, DUMP_OUT_BYTES // world // (4 * B))
+    ch = np.arange(N) if S == N else np.sort(np.random.default_rng(SEED).choice(N, S, replace=False))
+    f, c = np.arange(B)[:, None], ch[None, :]
+    idx = (c // tile) * (B * tile) + f * tile + c % tile if tile else f * N + c      # pkg.from_layout, for S channels
+    out = y.index_select(0, torch.from_numpy(idx.reshape(-1)).to(y.device)).view(B, S)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "out%s.npy" % sfx), out.cpu().numpy())
+    if mix is not None:
+        np.save(os.path.join(out_dir, "mix%s.npy" % sfx), mix[:B].cpu().numpy())
+
+
+def measure(ctx, args, cfg_name, steps, warmup, overrides=None, extras=False, dump_dir=None):
     """One configuration: build the engine, settle, W warm-up steps, K timed steps.  Returns a dict.
-    extras: also the cold figure (first launches after an idle gap) and the paced real-time run (one block per block period)."""
+    extras: also the cold figure (first launches after an idle gap) and the paced real-time run (one block per block period).
+    dump_dir: write what the last timed step computed there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     pkg, P, dev, world = ctx.pkg, ctx.P, ctx.dev, ctx.world
@@ -546,6 +577,12 @@ def measure(ctx, args, cfg_name, steps, warmup, overrides=None, extras=False):
     for k in range(settle_steps):
         step(k)
     es1.record()
+    # settle_steps follows the clock, so the DSP state it leaves differs from run to run: start it again from zero (stream-ordered,
+    # no host pause) and refill the delay rings (one revolution) and a FIR's history, so that the same arguments always compute
+    # the same timed blocks
+    eng.reset()
+    for k in range(max(probe_steps, -(-int(cfg.get("taps") or 0) // B)) + 8):
+        step(k)
     for k in range(warmup):
         step(k)
     drain()
@@ -583,6 +620,11 @@ def measure(ctx, args, cfg_name, steps, warmup, overrides=None, extras=False):
 
     dt, t_submitted, t_event = timed_region(step, drain, ev0, ev1)
     region_ms = ev0.elapsed_time(ev1)
+    if dump_dir is not None:
+        # the bus of block K-1: in its own mix buffer (one rank), or in the pipelined bus' ring (drained in the timed region)
+        last_mix = (pbus.results().get(steps - 1) if pbus is not None else
+                    mixes[(steps - 1) & 3] if use_mix and mix_mode == "inline" and not dist_run else None)
+        dump_outputs(torch, dump_dir, y, last_mix, N, B, tile, world, ctx.rank)
     if region_timing:
         kern_ms_total, kern_launches = region_ms, steps
         kern_name = stage_lines[-1].split("kernel ")[1].split(" ")[0]
@@ -699,7 +741,7 @@ def measure(ctx, args, cfg_name, steps, warmup, overrides=None, extras=False):
     # ---- several ranks: what one exchange of the bus costs (the kernel of dspfx_mix_allreduce alone, ranks in step), and the
     # paced leg with the GLOBAL bus of every block
     exchange = None
-    if dist_run and use_mix and ctx.comm is not None:
+    if args.full and dist_run and use_mix and ctx.comm is not None:
         t = torch.zeros(B, dtype=torch.float32, device=dev)
         fence()
         xe = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
@@ -724,7 +766,7 @@ def measure(ctx, args, cfg_name, steps, warmup, overrides=None, extras=False):
     # (dspfx_process_mixpipe) and exchanges it on the second stream, under the next blocks' chain kernels: the weak-scaling ceiling
     # without the exchange on the critical path.  Same engine, same buffers, same K, same barrier + MAX-over-ranks clock.
     forms = None
-    if dist_run and use_mix and pbus is not None and pbus.inline and os.environ.get("DSPFX_BENCH_FORMS", "1") == "1":
+    if args.full and dist_run and use_mix and pbus is not None and pbus.inline and os.environ.get("DSPFX_BENCH_FORMS", "1") == "1":
         forms = {"inline": {"what": "same-block bus, exchange on the compute stream behind each chain kernel (= value)",
                             "value": value, "ms_per_step": dt * 1e3 / steps, "bus_delay_blocks": 0}}
         try:
@@ -1088,13 +1130,14 @@ def main():
 
     over = {k: getattr(args, k) for k in ("channels", "frames", "delay", "taps") if getattr(args, k) is not None}
     if args.paced:
+        args.full = True          # the paced run is one of --full's legs: --paced runs it alone
         args.no_others = True
         args.no_cpu_baseline = True
     # Config 2 is timed BEFORE the headline config.  After seconds of the large configs the chip runs this light, latency-
     # sensitive kernel 2-4 % slower for about three seconds (23.4-24.0 us against the 23.1 us it holds for as long as it runs
     # alone: profiles/r03_small_n.txt) -- the previous workload's power state, not config 2's.  DSPFX_BENCH_EARLY= (empty)
     # restores the old order (tools/archive/r03_cfg2_order.sh).
-    want_others = args.config == "cfg5" and world == 1 and not over and not args.no_others
+    want_others = args.full and args.config == "cfg5" and world == 1 and not over and not args.no_others
     other_names = [n for n in os.environ.get("DSPFX_BENCH_OTHERS", "cfg3,cfg2,cfg4").split(",") if n]
     early_names = [n for n in os.environ.get("DSPFX_BENCH_EARLY", "cfg2").split(",") if n and n in other_names] if want_others else []
     timed_order = []
@@ -1113,7 +1156,7 @@ def main():
             early[name] = other_entry(name)
         except Exception as ex:
             early[name] = {"error": str(ex)[:300]}
-    r = measure(ctx, args, args.config, args.steps, args.warmup, over, extras=(world == 1))
+    r = measure(ctx, args, args.config, args.steps, args.warmup, over, extras=(args.full and world == 1), dump_dir=args.dump_outputs)
     timed_order.append(args.config)
 
     # The other single-GPU BASELINE configs, timed in the same run with the same K / W (extra key; the line's
@@ -1192,7 +1235,7 @@ def main():
         line["bus_two_calls_late"] = r["alt_bus"]
     if others is not None:
         line["other_configs"] = others
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline(r["chain"], r["cfg"], args.link_flags, args.cpu_seconds)
             line["cpu_baseline"]["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
@@ -1200,7 +1243,7 @@ def main():
             line["cpu_baseline"] = {"value": None, "unit": "samples/s", "cores": os.cpu_count(), "kind": "port",
                                     "sample": f"failed: {ex}"}
     else:
-        line["cpu_baseline"] = None      # N > 1, or switched off with --no-cpu-baseline
+        line["cpu_baseline"] = None      # N > 1, a plain run (no --full), or switched off with --no-cpu-baseline
     if world == 1 and want_others and os.environ.get("DSPFX_BENCH_HOST_PATH", "1") == "1":
         try:
             line["host_path"] = host_path(ctx, args)

@@ -376,7 +376,7 @@ def test_bench_py_prints_one_compact_contract_line(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--channels", "65536", "--delay", "1024",
-                        "--cpu-seconds", "1", "--paced-seconds", "0.2"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--cpu-seconds", "1", "--paced-seconds", "0.2", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -395,6 +395,45 @@ def test_bench_py_prints_one_compact_contract_line(tmp_path):
     assert len(detail) == 1 and json.loads(detail[0][len("bench.py detail: "):])["value"] == d["value"]
 
 
+def test_plain_bench_run_times_the_headline_alone_and_dumps_the_same_outputs_twice(tmp_path, dspfx):
+    """bench.py without --full: the headline config and nothing else (no CPU baseline, other configs or extra legs) in one line that
+    states the K it was given; --dump-outputs writes the last timed block, and two runs with the same arguments write the same
+    bits.  That block is what the oracle computes for the run's input sequence: the state starts from zero after the settle,
+    then one ring revolution of refill (max(24, ceil(D / B)) + 8 blocks), W warm-up and K timed blocks, alternating between the
+    noise blocks 0 and 1."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    N, B, D, W, K = 65536, 128, 1024, 2, 5
+    outs = []
+    for run in range(2):
+        d_out = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--channels", str(N),
+                            "--delay", str(D), "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == K and d["warmup"] == W and d["cpu_baseline"] is None and d["unit"] == "samples/s" and d["dtype"] == "f32"
+        assert not {"other_configs", "paced", "cold", "host_path", "bus_two_calls_late"} & set(d), sorted(d)
+        assert abs(d["value"] - N * B / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+        assert sorted(os.listdir(d_out)) == ["mix.npy", "out.npy"]
+        outs.append((np.load(d_out / "out.npy"), np.load(d_out / "mix.npy")))
+    (y, mix), (y2, mix2) = outs
+    assert y.dtype == np.float32 and y.shape == (B, N) and mix.dtype == np.float32 and mix.shape == (B,)
+    assert np.array_equal(y.view(np.uint32), y2.view(np.uint32)) and np.array_equal(mix.view(np.uint32), mix2.view(np.uint32))
+    chans = sample_channels(N)
+    blocks = [O.noise(SEED, chans, np.arange(j * B, (j + 1) * B)) for j in (0, 1)]
+    n_refill = max(24, -(-D // B)) + 8
+    seq = list(range(n_refill)) + list(range(W)) + list(range(K))
+    x = np.concatenate([blocks[k % 2] for k in seq])
+    ref = O.run_channels([n.oracle_desc() for n in chain5(dspfx, D)], x, 3)[-B:]
+    assert ulp_diff(y[:, chans], ref).max() <= 1, ulp_diff(y[:, chans], ref).max()
+    assert np.allclose(mix, y.astype(np.float64).sum(axis=1) / float(dspfx.link_divisor(N)), rtol=1e-4, atol=1e-6)
+
+
 def test_bare_gpus_2_command_starts_its_own_ranks_and_reports_both_exchange_forms():
     """`python3 bench.py --gpus 2 ...` with NO torch.distributed.run in front of it and no launcher environment --
     the shape of the driver's recorded N = 1 command -- must start its own ranks (fresh children, before any GPU call of the
@@ -409,7 +448,8 @@ def test_bare_gpus_2_command_starts_its_own_ranks_and_reports_both_exchange_form
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                             "GROUP_RANK", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--channels", "65536", "--delay", "1024"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--channels", "65536", "--delay", "1024",
+           "--full"]
     import torch
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root, env=env)

@@ -193,7 +193,7 @@ def test_the_bare_bench_command_scales_itself_across_devices(world):
                                                             "GROUP_RANK", "ROLE_RANK", "TORCHELASTIC_RUN_ID", "DSPFX_BENCH_SHARE_GPU")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5", "--channels", "262144",
-                        "--delay", "1024"], capture_output=True, text=True, timeout=1800, cwd=root, env=env)
+                        "--delay", "1024", "--full"], capture_output=True, text=True, timeout=1800, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -2,18 +2,15 @@
 
 The Rust module cannot be compiled here; what runs on CPU: the case file is exactly what export_cases.py makes from the committed
 golden vectors; a Python walk of the case file in golden_dump.rs's order of operations over the oracle's nodes reproduces every
-expected vector and passes the comparator; the comparator notices a single flipped bit and a contradicting probe; and -- where the
-reference tree exists (the build container) -- tools/check_pin_kit.py: the module's crate:: paths, trait calls, third-party call
-spellings, the README's main.rs lines and every case's cfg against the real node.rs / nodes/*.rs / Cargo.toml."""
+expected vector and passes the comparator; the comparator notices a single flipped bit and a contradicting probe.  The check of the
+module and the case file against the reference's own sources (tools/check_pin_kit.py) needs a checkout of the reference, which
+this repository does not hold: it is run by hand, with DSPFX_REFERENCE naming that checkout."""
 import json
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("DSPFX_REFERENCE", "/root/reference")
 KIT = os.path.join(ROOT, "oracle", "pin_kit")
 
 
@@ -47,28 +44,3 @@ def test_emulated_harness_reproduces_every_vector_and_the_comparator_can_fail(tm
     json.dump(d, open(bad, "w"))
     r = _run(os.path.join(ROOT, "tools", "compare_pin.py"), str(bad))
     assert r.returncode == 1 and "NONE of the candidate orders" in r.stdout, r.stdout
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "dsp-stuff", "src", "nodes", "mod.rs")), reason="no reference tree here")
-def test_the_kit_fits_the_reference_tree(tmp_path):
-    r = _run(os.path.join(ROOT, "tools", "check_pin_kit.py"))
-    assert r.returncode == 0 and r.stdout.count("ok  ") == 4, r.stdout + r.stderr
-    # not vacuous: a case whose FIR cfg lacks `file_name` (Fir::restore would panic on it) is caught
-    import shutil
-    root = tmp_path / "repo"
-    shutil.copytree(KIT, root / "oracle" / "pin_kit")
-    os.makedirs(root / "tools")
-    for f in ("check_pin_kit.py", "check_rust_recipe.py"):
-        shutil.copy(os.path.join(ROOT, "tools", f), root / "tools" / f)
-    p = root / "oracle" / "pin_kit" / "cases.json"
-    d = json.load(open(p))
-    hit = 0
-    for c in d["cases"]:
-        for n in c["doc"]["nodes"]:
-            if n["typename"] == "fir":
-                n["cfg"].pop("file_name", None)
-                hit += 1
-    assert hit
-    json.dump(d, open(p, "w"))
-    r = subprocess.run([sys.executable, str(root / "tools" / "check_pin_kit.py")], capture_output=True, text=True, timeout=120)
-    assert r.returncode != 0 and "file_name" in r.stderr, r.stdout + r.stderr

@@ -12,8 +12,8 @@ for k,v in (d.get('other_configs') or {}).items():
 "; }
 for rep in 1 2; do
   echo "== default order (run $rep)" >> $out
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --paced-seconds 0 2>>$out.err | show >> $out
+  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --paced-seconds 0 --full 2>>$out.err | show >> $out
   echo "== config 2 after the headline config and config 3 (run $rep)" >> $out
-  DSPFX_BENCH_EARLY= python bench.py --steps 20 --warmup 5 --no-cpu-baseline --paced-seconds 0 2>>$out.err | show >> $out
+  DSPFX_BENCH_EARLY= python bench.py --steps 20 --warmup 5 --no-cpu-baseline --paced-seconds 0 --full 2>>$out.err | show >> $out
 done
 cat $out

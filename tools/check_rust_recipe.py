@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("DSPFX_REFERENCE", "/root/reference")
 SHIM = os.path.join(ROOT, "host", "rust", "src")
 
-# what host/rust/README.md tells the maintainer to add (kept in step with it by tests/test_rust_recipe_cpu.py)
+# what host/rust/README.md tells the maintainer to add (main() checks that the README shows these lines)
 RECIPE = {
     "main_mod": "mod gpu;",
     "use": "use crate::gpu::{gpu_bank::GpuBank, gpu_chain::GpuChain};",

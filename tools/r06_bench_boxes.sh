@@ -1,6 +1,6 @@
 #!/bin/bash
 # One more fresh box: the driver's command, one summary line appended to gpurun_out/r06_bench_boxes.txt (run it once per gpurun call).
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | python3 -c "
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']; o = d['other_configs']
 f = lambda v: '%s k %.4f s %.4f frac %.3f by_step %.3f' % (v['roofline']['kernel'], v['roofline']['kernel_ms_avg'], v['ms_per_step'], v['roofline']['frac'], v['roofline']['frac_by_step'])

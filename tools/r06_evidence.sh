@@ -8,9 +8,9 @@ ROOT=/root/repo
 export DSPFX_ROUND=r06
 OUT=$ROOT/gpurun_out/r06ev; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_run1.json 2>$OUT/bench_run1.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o drv -- python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_under_rocprof.json 2>$OUT/rocprof.err
-python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_run2.json 2>$OUT/bench_run2.err
+python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_run1.json 2>$OUT/bench_run1.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o drv -- python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_under_rocprof.json 2>$OUT/rocprof.err
+python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_run2.json 2>$OUT/bench_run2.err
 T=$(find $OUT/trace -name "*kernel_trace.csv" | head -1)
 python3 $ROOT/tools/trace_phases.py $T $OUT/bench_under_rocprof.json $OUT/timed_regions.json > $OUT/timed_regions.txt 2>&1
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
@@ -72,6 +72,6 @@ for f in ("bench_run1", "bench_under_rocprof", "bench_run2"):
 PY
 # the driver's N = 2 command shape WITHOUT a launcher in front of it (bench.py starts its own ranks), both ranks on this box's one GPU
 cd $ROOT
-DSPFX_BENCH_SHARE_GPU=1 DSPFX_BENCH_COMM=abi timeout 900 python3 bench.py --gpus 2 --steps 20 --warmup 5 > $OUT/two_ranks_self_launched.json 2> $OUT/two_ranks_self_launched.err
+DSPFX_BENCH_SHARE_GPU=1 DSPFX_BENCH_COMM=abi timeout 900 python3 bench.py --gpus 2 --steps 20 --warmup 5 --full > $OUT/two_ranks_self_launched.json 2> $OUT/two_ranks_self_launched.err
 echo "two ranks rc=$?"; python3 -c "
 import json; d = json.loads(open('$OUT/two_ranks_self_launched.json').read().strip().splitlines()[-1]); print(d['scaling_forms'], d['bus_exchange'])"
