@@ -43,6 +43,8 @@ GRAPH_MAX_IO = 16
 GRAPH_INPUTS = (GRAPH_INPUT, GRAPH_INPUT2) + tuple(-(2 + k) for k in range(2, GRAPH_MAX_IO))     # link source of input block k
 PORT_MAIN, PORT_SIDE, PORT_SLIDER = 0, 1, 2
 PORT_RAW = 256
+# dspfx_sample_format: device sample formats at the boundary (devices.rs:305-350)
+SAMPLE_F32, SAMPLE_I16, SAMPLE_U16, SAMPLE_I32 = range(4)
 
 # every symbol include/dspfx.h declares
 EXPORTS = [
@@ -56,7 +58,7 @@ EXPORTS = [
     "dspfx_process_io", "dspfx_comm_unique_id", "dspfx_comm_create", "dspfx_comm_destroy", "dspfx_comm_size", "dspfx_comm_rank",
     "dspfx_comm_last_error", "dspfx_mix_allreduce",
     "dspfx_set_param_seq", "dspfx_param_log", "dspfx_frames_submitted", "dspfx_process_bus", "dspfx_kernels_ready", "dspfx_comm_backend",
-    "dspfx_reserve_delay_len", "dspfx_ring_trim",
+    "dspfx_reserve_delay_len", "dspfx_ring_trim", "dspfx_process_pcm", "dspfx_process_host_pcm",
 ]
 COMM_ID_BYTES = 128
 
@@ -85,6 +87,10 @@ class _GraphLink(C.Structure):
 class _ParamEvent(C.Structure):
     _fields_ = [("seq", C.c_uint64), ("frame", C.c_uint64), ("node", C.c_int32), ("param", C.c_int32),
                 ("value", C.c_float), ("reserved", C.c_int32)]
+
+
+class _PcmIo(C.Structure):
+    _fields_ = [("in_format", C.c_int32), ("in_channels", C.c_int32), ("out_format", C.c_int32), ("out_channels", C.c_int32)]
 
 
 class _Ctl(C.Structure):
@@ -146,6 +152,8 @@ def lib():
     L.dspfx_reset.argtypes = [vp]
     L.dspfx_process.argtypes = [vp, f32p, f32p, f32p, f32p, C.c_uint32, vp]
     L.dspfx_process_host.argtypes = [vp, f32p, f32p, f32p, f32p, C.c_uint32]
+    L.dspfx_process_pcm.argtypes = [vp, C.POINTER(_PcmIo), vp, vp, vp, f32p, C.c_uint32, vp]
+    L.dspfx_process_host_pcm.argtypes = [vp, C.POINTER(_PcmIo), vp, vp, vp, f32p, C.c_uint32]
     L.dspfx_process_bus.argtypes = [vp, f32p, f32p, f32p, f32p, C.c_uint32, C.c_uint64, vp]
     L.dspfx_mix_finish.argtypes = [vp, f32p, C.c_uint32, C.c_uint64, vp]
     L.dspfx_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
@@ -205,15 +213,17 @@ def verify_fast_division(c: float, device: int = 0) -> int:
 
 
 class PinnedArray:
-    """A float32 numpy array over page-locked host memory from dspfx_host_alloc (`.array`); freed on close()/GC."""
+    """A numpy array (float32 unless `dtype` says otherwise) over page-locked host memory from dspfx_host_alloc (`.array`);
+    freed on close()/GC."""
 
-    def __init__(self, shape):
+    def __init__(self, shape, dtype=np.float32):
+        dt = np.dtype(dtype)
         n = int(np.prod(shape))
         self._p = C.c_void_p()
-        rc = lib().dspfx_host_alloc(n * 4, C.byref(self._p))
+        rc = lib().dspfx_host_alloc(max(1, n * dt.itemsize), C.byref(self._p))
         if rc != 0:
             raise DspfxError(rc, lib().dspfx_strerror(rc).decode())
-        self.array = np.ctypeslib.as_array((C.c_float * n).from_address(self._p.value)).reshape(shape)
+        self.array = np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(self._p.value), dtype=dt, count=n).reshape(shape)
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
@@ -354,6 +364,33 @@ def Envelope(attack: float = 0.0, release: float = 0.0) -> NodeSpec:
 
 
 # -------------------------------------------------------------------------- engine
+
+# numpy / torch dtype -> dspfx_sample_format (u16: torch.uint16 where torch has it, else fmt=SAMPLE_U16 over an int16 view)
+_NP_FORMATS = {np.dtype(np.float32): SAMPLE_F32, np.dtype(np.int16): SAMPLE_I16, np.dtype(np.uint16): SAMPLE_U16,
+               np.dtype(np.int32): SAMPLE_I32}
+_FORMAT_NP = {v: k for k, v in _NP_FORMATS.items()}
+
+
+def _np_format(a, fmt=None):
+    if fmt is not None:
+        return int(fmt)
+    if a.dtype not in _NP_FORMATS:
+        raise TypeError(f"no device sample format for dtype {a.dtype}: float32, int16, uint16 or int32")
+    return _NP_FORMATS[a.dtype]
+
+
+def _torch_format(t, fmt=None):
+    if fmt is not None:
+        return int(fmt)
+    import torch
+    m = {torch.float32: SAMPLE_F32, torch.int16: SAMPLE_I16, torch.int32: SAMPLE_I32}
+    if getattr(torch, "uint16", None) is not None:
+        m[torch.uint16] = SAMPLE_U16
+    if t.dtype not in m:
+        raise TypeError(f"no device sample format for dtype {t.dtype}: float32, int16, uint16 or int32 "
+                        "(or pass fmt= with a same-width view)")
+    return m[t.dtype]
+
 
 def _ptr(x):
     if x is None:
@@ -547,6 +584,36 @@ class Engine:
         mix = np.empty(x.shape[0], np.float32) if want_mix else None
         self._chk(self.L.dspfx_process_host(self.h, x.ctypes.data, s.ctypes.data if s is not None else None,
                                             out.ctypes.data, mix.ctypes.data if want_mix else None, x.shape[0]))
+        return (out, mix) if want_mix else out
+
+    def process_pcm(self, x, out, side=None, mix=None, in_channels: int = 1, out_channels: int = 1, stream: int = 0,
+                    n_frames: Optional[int] = None, in_fmt: Optional[int] = None, out_fmt: Optional[int] = None):
+        """Device path in device sample formats (dspfx_process_pcm): x / side / out are device tensors in the engine's sample
+        layout, [n_frames][channels * device channels]; the format is read from the dtype (float32, int16, int32, uint16 where
+        torch has it) unless in_fmt / out_fmt name it (SAMPLE_U16 over an int16 view).  `mix` stays an f32 device tensor."""
+        io = _PcmIo(_torch_format(x, in_fmt), int(in_channels), _torch_format(out, out_fmt), int(out_channels))
+        if n_frames is None:
+            n_frames = x.shape[0]
+        self._chk(self.L.dspfx_process_pcm(self.h, C.byref(io), _ptr(x), _ptr(side), _ptr(out), _ptr(mix), int(n_frames),
+                                           C.c_void_p(stream) if stream else None))
+        return out
+
+    def process_host_pcm(self, x: np.ndarray, out=None, side: Optional[np.ndarray] = None, want_mix: bool = False,
+                         in_channels: int = 1, out_channels: int = 1, out_dtype=None, in_fmt: Optional[int] = None,
+                         out_fmt: Optional[int] = None):
+        """Host path in device sample formats (dspfx_process_host_pcm): x [n_frames][channels * in_channels] numpy (float32,
+        int16, uint16, int32; the format from the dtype).  `out` may be a caller-provided (e.g. pinned) array; without one,
+        an array of `out_dtype` (default: x's dtype) is made.  Synchronous."""
+        x = np.ascontiguousarray(x)
+        assert x.ndim == 2 and x.shape[1] == self.channels * in_channels, x.shape
+        if out is None:
+            out = np.empty((x.shape[0], self.channels * out_channels), dtype=out_dtype or x.dtype)
+        assert out.shape == (x.shape[0], self.channels * out_channels) and out.flags.c_contiguous, out.shape
+        s = np.ascontiguousarray(side, dtype=x.dtype) if side is not None else None
+        io = _PcmIo(_np_format(x, in_fmt), int(in_channels), _np_format(out, out_fmt), int(out_channels))
+        mix = np.empty(x.shape[0], np.float32) if want_mix else None
+        self._chk(self.L.dspfx_process_host_pcm(self.h, C.byref(io), x.ctypes.data, s.ctypes.data if s is not None else None,
+                                                out.ctypes.data, mix.ctypes.data if want_mix else None, x.shape[0]))
         return (out, mix) if want_mix else out
 
     def mix_finish(self, mix, n_frames: int, n_connected: int, stream: int = 0):

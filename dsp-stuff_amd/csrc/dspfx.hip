@@ -924,6 +924,9 @@ extern "C" void dspfx_engine_destroy(dspfx_engine *e) {
     if (e->h_side) (void)hipFree(e->h_side);
     if (e->h_out) (void)hipFree(e->h_out);
     if (e->h_mix) (void)hipFree(e->h_mix);
+    if (e->p_in) (void)hipFree(e->p_in);
+    if (e->p_side) (void)hipFree(e->p_side);
+    if (e->p_out) (void)hipFree(e->p_out);
     for (auto &st : e->prof)
         for (auto &p : st) {
             (void)hipEventDestroy(p.first);
@@ -1359,6 +1362,53 @@ extern "C" int dspfx_process(dspfx_engine *e, const float *in, const float *side
         if (rc) return rc;
         e->frames_submitted += nf;
     }
+    return DSPFX_OK;
+}
+
+int dspfx_host::check_pcm_io(dspfx_engine *e, const dspfx_pcm_io *io) {
+    if (!io) return fail(e, DSPFX_ERR_INVALID, "io must not be null");
+    if (!pcm_format_ok(io->in_format) || !pcm_format_ok(io->out_format))
+        return fail(e, DSPFX_ERR_INVALID, "sample format in %d / out %d: not a dspfx_sample_format", io->in_format, io->out_format);
+    if (!pcm_channels_ok(io->in_channels) || !pcm_channels_ok(io->out_channels))
+        return fail(e, DSPFX_ERR_INVALID, "device channels in %d / out %d: 1 or 2", io->in_channels, io->out_channels);
+    return DSPFX_OK;
+}
+
+// devices.rs:227-260 / 394-498 around the block: widen into the f32 scratch, the block as dspfx_process runs it, narrow.  An f32
+// mono side is handed through as it is (the identity conversion), so {F32, 1, F32, 1} is dspfx_process itself.
+extern "C" int dspfx_process_pcm(dspfx_engine *e, const dspfx_pcm_io *io, const void *in, const void *side, void *out,
+                                 float *mix, uint32_t n_frames, void *stream) {
+    if (!e) return DSPFX_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    ApiScope api(e, true, s);            // the scratch is ordered behind whatever used it last, on any stream
+    if (api.rc) return api.rc;
+    if (const int rc = check_pcm_io(e, io)) return rc;
+    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
+    if (n_frames > e->desc.max_frames)
+        return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
+    if (n_frames == 0) return DSPFX_OK;
+    const uint32_t N = e->desc.channels;
+    const size_t cap = (size_t)e->desc.max_frames * N * sizeof(float);
+    const bool plain_in = io->in_format == DSPFX_SAMPLE_F32 && io->in_channels == 1;
+    const bool plain_out = io->out_format == DSPFX_SAMPLE_F32 && io->out_channels == 1;
+    const float *fin = (const float *)in, *fside = (const float *)side;
+    float *fout = (float *)out;
+    // a block in either layout is n_frames x N elements, contiguous: converted as n_frames rows of N
+    if (!plain_in) {
+        if (!e->h_in) HIPCHK(e, hipMalloc((void **)&e->h_in, cap));
+        if (side && !e->h_side) HIPCHK(e, hipMalloc((void **)&e->h_side, cap));
+        HIPCHK(e, launch_pcm_widen(io->in_format, io->in_channels, in, e->h_in, n_frames, N, N, 0, s));
+        if (side) HIPCHK(e, launch_pcm_widen(io->in_format, io->in_channels, side, e->h_side, n_frames, N, N, 0, s));
+        fin = e->h_in;
+        fside = side ? e->h_side : nullptr;
+    }
+    if (!plain_out) {
+        if (!e->h_out) HIPCHK(e, hipMalloc((void **)&e->h_out, cap));
+        fout = e->h_out;
+    }
+    const int rc = dspfx_process(e, fin, fside, fout, mix, n_frames, stream);
+    if (rc) return rc;
+    if (!plain_out) HIPCHK(e, launch_pcm_narrow(io->out_format, io->out_channels, e->h_out, out, n_frames, N, N, 0, s));
     return DSPFX_OK;
 }
 

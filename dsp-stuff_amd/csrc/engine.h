@@ -2,7 +2,9 @@
 // host-side functions that more than one of them calls.
 //   dspfx.hip      lifecycle, parameter stores, run_subblock and the process calls
 //   plan.hip       which kernels serve a chain: exact-division decision, variant selection, background specialisation, plan()
-//   host_pipe.hip  dspfx_process_host (pinned staging, overlapped upload / kernel / download) and its allocator
+//   host_pipe.hip  dspfx_process_host / dspfx_process_host_pcm (pinned staging, overlapped upload / kernel / download) and
+//                  its allocator
+//   pcm_kernels.hip device sample formats <-> f32 at the boundary (dspfx_process_pcm, dspfx_process_host_pcm)
 //   state_util.hip DSP state export / import, fan-in averaging, utilities (noise, checks, profiling read-out, dspfx_describe)
 //   jit.hip        run-time specialisation (hiprtc) of the chain kernels and the generator of whole-graph kernels
 //   placement.hip  delay-ring placement tuning (setup-time probe, dspfx_tune_placement)
@@ -38,6 +40,7 @@
 #include "aux_kernels.h"
 #include "fir_kernels.h"
 #include "variants.h"
+#include "pcm_kernels.h"
 #include "graph_kernel.hip.h"   // GraphArgs
 
 using namespace dspfx;
@@ -114,6 +117,8 @@ struct EnvSwitches {
     int fast_div = -1;           // DSPFX_FAST_DIV (0: IEEE division everywhere)
     int jit = -1, jit_async = -1;   // DSPFX_JIT, DSPFX_JIT_ASYNC
     int ts_tail = -1;            // DSPFX_TS_TAIL
+    int host_part = -1;          // DSPFX_HOST_PART (channels per part of the pipelined host path; unset: 65536)
+    int host_pipeline = -1;      // DSPFX_HOST_PIPELINE (0: the host path never pipelines)
     int menu_ring_reserve = -1;  // DSPFX_MENU_RING_RESERVE (0: never reserve a menu-fresh delay node's slider ring at chain set; 1: whenever it fits; unset: when cheap)
     bool has_variant = false;    // DSPFX_VARIANT set at all
     int variant_ts = -1;         // its ts= field
@@ -185,8 +190,12 @@ struct dspfx_engine {
     const float *io_in[GRAPH_IO] = {};
     float *io_out[GRAPH_IO] = {};
     size_t io_off = 0;
-    // staging for dspfx_process_host
+    // staging for dspfx_process_host; dspfx_process_pcm widens into h_in / h_side and narrows from h_out
     float *h_in = nullptr, *h_side = nullptr, *h_out = nullptr, *h_mix = nullptr;
+    // device staging of dspfx_process_host_pcm: blocks in device sample formats, sized max_frames x N elements of the
+    // widest format asked for so far (bytes)
+    void *p_in = nullptr, *p_side = nullptr, *p_out = nullptr;
+    size_t p_in_cap = 0, p_side_cap = 0, p_out_cap = 0;
     const Variant *tail = nullptr, *dyn = nullptr, *tail_mod = nullptr, *dyn_mod = nullptr, *dyn_mod2 = nullptr;
     bool has_fuzz = false;
     uint32_t min_delay = 0xffffffffu;
@@ -319,6 +328,7 @@ void recompute_min_delay(dspfx_engine *e);
 int run_subblock(dspfx_engine *e, const float *in, const float *side, float *out, float *mix, uint32_t nframes, uint32_t tile_frames,
                  hipStream_t stream);
 int bind_stream(dspfx_engine *e, hipStream_t s);
+int check_pcm_io(dspfx_engine *e, const dspfx_pcm_io *io);   // dspfx.hip: DSPFX_ERR_INVALID with a message, or DSPFX_OK
 int quiesce(dspfx_engine *e);
 int settle_null_stream(dspfx_engine *e);
 int drain_pending(dspfx_engine *e, hipStream_t s);

@@ -95,6 +95,8 @@ EnvSwitches read_env_switches() {
     s.jit_async = env_int("DSPFX_JIT_ASYNC");
     s.ts_tail = env_int("DSPFX_TS_TAIL");
     s.menu_ring_reserve = env_int("DSPFX_MENU_RING_RESERVE");
+    s.host_part = env_int("DSPFX_HOST_PART");
+    s.host_pipeline = env_int("DSPFX_HOST_PIPELINE");
     if (const char *v = getenv("DSPFX_VARIANT")) {
         s.has_variant = true;
         const char *q;

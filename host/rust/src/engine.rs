@@ -6,6 +6,23 @@ use std::ffi::CStr;
 use std::os::raw::c_int;
 use std::ptr;
 
+/// A sample type the engine takes at its boundary (`dspfx_sample_format`): cpal's i16 / u16 / i32 / f32.
+pub trait PcmSample: Copy {
+    const FORMAT: i32;
+}
+impl PcmSample for f32 {
+    const FORMAT: i32 = DSPFX_SAMPLE_F32;
+}
+impl PcmSample for i16 {
+    const FORMAT: i32 = DSPFX_SAMPLE_I16;
+}
+impl PcmSample for u16 {
+    const FORMAT: i32 = DSPFX_SAMPLE_U16;
+}
+impl PcmSample for i32 {
+    const FORMAT: i32 = DSPFX_SAMPLE_I32;
+}
+
 #[derive(Debug)]
 pub struct Error {
     pub status: c_int,
@@ -256,6 +273,40 @@ impl Engine {
         };
         let rc = unsafe {
             dspfx_process_host(self.h, input.as_ptr(), side.map_or(ptr::null(), |s| s.as_ptr()), out.as_mut_ptr(), mix_ptr, n_frames)
+        };
+        self.check(rc)
+    }
+
+    /// One block from host slices in the device's own sample type (i16 / u16 / i32 / f32, cpal's buffers as they come),
+    /// converted on the GPU by the reference's rules (devices.rs:227-260 in, 394-498 out).  `in_channels` / `out_channels`:
+    /// 1, or 2 for interleaved device frames -- a 2-channel input is folded to mono as a + b, a 2-channel output gets the
+    /// sample in both slots.  Frame-major `[n_frames][channels * device channels]`; `mix` stays f32.  Synchronous.
+    pub fn process_host_pcm<I: PcmSample, O: PcmSample>(&mut self, input: &[I], in_channels: u32, side: Option<&[I]>,
+                                                       out: &mut [O], out_channels: u32, mix: Option<&mut [f32]>,
+                                                       n_frames: u32) -> Result<(), Error> {
+        let frames = n_frames as usize * self.channels as usize;
+        assert!(input.len() == frames * in_channels as usize, "input must be [n_frames][channels * in_channels]");
+        assert!(out.len() == frames * out_channels as usize, "out must be [n_frames][channels * out_channels]");
+        if let Some(s) = side {
+            assert_eq!(s.len(), input.len());
+        }
+        let mix_ptr = match mix {
+            Some(m) => {
+                assert_eq!(m.len(), n_frames as usize);
+                m.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        let io = dspfx_pcm_io {
+            in_format: I::FORMAT,
+            in_channels: in_channels as i32,
+            out_format: O::FORMAT,
+            out_channels: out_channels as i32,
+        };
+        let rc = unsafe {
+            dspfx_process_host_pcm(self.h, &io, input.as_ptr() as *const std::os::raw::c_void,
+                                   side.map_or(ptr::null(), |s| s.as_ptr() as *const std::os::raw::c_void),
+                                   out.as_mut_ptr() as *mut std::os::raw::c_void, mix_ptr, n_frames)
         };
         self.check(rc)
     }

@@ -67,6 +67,16 @@ pub struct dspfx_param_event {
     pub reserved: i32,
 }
 
+/// Device sample formats at the process boundary (`dspfx_process_pcm` / `dspfx_process_host_pcm`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_pcm_io {
+    pub in_format: i32,
+    pub in_channels: i32,
+    pub out_format: i32,
+    pub out_channels: i32,
+}
+
 pub const DSPFX_ABI_VERSION: u32 = 2;
 pub const DSPFX_BUF_SIZE: u32 = 128; // dsp-stuff/src/node.rs:257
 pub const DSPFX_MAX_NODES: u32 = 32;
@@ -80,6 +90,12 @@ pub const DSPFX_ERR_HIP: c_int = -3;
 pub const DSPFX_ERR_OOM: c_int = -4;
 pub const DSPFX_ERR_UNSUPPORTED: c_int = -5;
 pub const DSPFX_ERR_STATE: c_int = -6;
+
+// dspfx_sample_format (devices.rs:305-350: cpal's SampleFormat, the four the engine converts)
+pub const DSPFX_SAMPLE_F32: i32 = 0;
+pub const DSPFX_SAMPLE_I16: i32 = 1;
+pub const DSPFX_SAMPLE_U16: i32 = 2;
+pub const DSPFX_SAMPLE_I32: i32 = 3;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -177,6 +193,8 @@ extern "C" {
     pub fn dspfx_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     pub fn dspfx_host_free(p: *mut c_void) -> c_int;
     pub fn dspfx_process_host(e: *mut dspfx_engine, input: *const f32, side: *const f32, out: *mut f32, mix: *mut f32, n_frames: u32) -> c_int;
+    pub fn dspfx_process_pcm(e: *mut dspfx_engine, io: *const dspfx_pcm_io, input: *const c_void, side: *const c_void, out: *mut c_void, mix: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_process_host_pcm(e: *mut dspfx_engine, io: *const dspfx_pcm_io, input: *const c_void, side: *const c_void, out: *mut c_void, mix: *mut f32, n_frames: u32) -> c_int;
     pub fn dspfx_process_partials(e: *mut dspfx_engine, input: *const f32, side: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
     pub fn dspfx_mix_collect(e: *mut dspfx_engine, mix: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
     pub fn dspfx_mix_finish(e: *mut dspfx_engine, mix: *mut f32, n_frames: u32, n_connected: u64, stream: *mut c_void) -> c_int;

@@ -369,6 +369,46 @@ int dspfx_host_free(void *p);
  * H2D copy, process, D2H copy, synchronous. */
 int dspfx_process_host(dspfx_engine *e, const float *in, const float *side, float *out, float *mix,
                        uint32_t n_frames);
+/* ---- device sample formats at the boundary -------------------------------------------------------------
+ * The reference's device boundary takes whatever sample type the sound card speaks (cpal's SampleFormat,
+ * devices.rs:305-350) and converts it at the edge with dasp_sample 0.11.0 (Cargo.lock:1267-1269):
+ *   input   do_read_1 / do_read_2 (devices.rs:227-260): to_sample into f32 (devices.rs:235, 253); a 2-channel device
+ *           is folded to mono as to_f32(a) + to_f32(b) -- one f32 add, no halving;
+ *   output  do_write_1 / do_write_2 (devices.rs:394-498): from_sample of each f32 (devices.rs:424, 432, 477, 488); a
+ *           2-channel device gets the same sample in both slots (o.fill(x), devices.rs:476-490).
+ * The rules, AS RECALLED (the crate is not vendored; they are restated once, in pcm_kernels.hip to_f32 / from_f32):
+ *   I16  to f32: s / 32768.0f                    from f32: x * 32768.0f, truncated toward zero, saturated, NaN -> 0
+ *   U16  to f32: (s - 32768) / 32768.0f          from f32: the I16 result + 32768 (bit pattern ^ 0x8000)
+ *   I32  to f32: (float)s / 2147483648.0f        from f32: x * 2147483648.0f, truncated toward zero, saturated, NaN -> 0
+ *   F32  identity                                identity
+ * (the float -> int rule is Rust's `as`: no dither, no rounding).
+ * Layout: every PCM buffer follows the engine's sample layout element by element (frame-major, or channel-tiled
+ * under tile_channels); with 2 device channels each element is an adjacent pair (a, b).  `mix` stays f32 and means
+ * what it means in dspfx_process: the Output node's f32 sum.  Any other format or channel count is DSPFX_ERR_INVALID.
+ * {F32, 1, F32, 1} gives the same bits as dspfx_process / dspfx_process_host. */
+typedef enum dspfx_sample_format {
+    DSPFX_SAMPLE_F32 = 0,
+    DSPFX_SAMPLE_I16 = 1,
+    DSPFX_SAMPLE_U16 = 2,
+    DSPFX_SAMPLE_I32 = 3
+} dspfx_sample_format;
+typedef struct dspfx_pcm_io {
+    int32_t in_format;     /* dspfx_sample_format of `in` AND `side` */
+    int32_t in_channels;   /* 1, or 2: interleaved device frames (a, b) -> to_f32(a) + to_f32(b)   devices.rs:244-258 */
+    int32_t out_format;    /* dspfx_sample_format of `out` */
+    int32_t out_channels;  /* 1, or 2: each output sample written to both slots                  devices.rs:476-490 */
+} dspfx_pcm_io;
+/* dspfx_process with device buffers in device sample formats; asynchronous on `stream`.  Widens `in` (and `side`)
+ * into engine-owned f32 scratch, runs the block as dspfx_process does, narrows into `out` (may alias `in`: the three
+ * steps are in stream order).  The scratch is shared with dspfx_process_host: calls on different streams are ordered
+ * like every other call on the engine (see "Threads and streams" above). */
+int dspfx_process_pcm(dspfx_engine *e, const dspfx_pcm_io *io, const void *in, const void *side, void *out,
+                      float *mix, uint32_t n_frames, void *stream);
+/* dspfx_process_host with host buffers in device sample formats; synchronous.  From page-locked buffers the block is
+ * pipelined in channel parts exactly when dspfx_process_host's would be; each part crosses the bus in its device format
+ * and is widened / narrowed on the GPU. */
+int dspfx_process_host_pcm(dspfx_engine *e, const dspfx_pcm_io *io, const void *in, const void *side, void *out,
+                           float *mix, uint32_t n_frames);
 /* Pipelined mix bus.  dspfx_process(mix != NULL) / dspfx_process_bus finish the bus inside the chain launch (a few
  * microseconds at its tail; a chain that ends in a FIR node, an odd block length or DSPFX_MIX_TAIL=0 take two small
  * kernels behind it instead).  The forms below move even that off the block's own launch, at the price of delivering

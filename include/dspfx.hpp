@@ -212,6 +212,16 @@ class Engine {
                       float *mix = nullptr) {
         chk(dspfx_process_host(e_, in, side, out, mix, n_frames));
     }
+    // device sample formats at the boundary (dspfx.h: dspfx_pcm_io); `mix` stays f32.  Device buffers, asynchronous on `stream`
+    void process_pcm(const dspfx_pcm_io &io, const void *in, void *out, std::uint32_t n_frames, const void *side = nullptr,
+                     float *mix = nullptr, void *stream = nullptr) {
+        chk(dspfx_process_pcm(e_, &io, in, side, out, mix, n_frames, stream));
+    }
+    // ... host buffers, synchronous
+    void process_host_pcm(const dspfx_pcm_io &io, const void *in, void *out, std::uint32_t n_frames, const void *side = nullptr,
+                          float *mix = nullptr) {
+        chk(dspfx_process_host_pcm(e_, &io, in, side, out, mix, n_frames));
+    }
     void mix_finish(float *mix, std::uint32_t n_frames, std::uint64_t n_connected, void *stream = nullptr) {
         chk(dspfx_mix_finish(e_, mix, n_frames, n_connected, stream));
     }
