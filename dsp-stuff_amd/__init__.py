@@ -45,6 +45,9 @@ PORT_MAIN, PORT_SIDE, PORT_SLIDER = 0, 1, 2
 PORT_RAW = 256
 # dspfx_sample_format: device sample formats at the boundary (devices.rs:305-350)
 SAMPLE_F32, SAMPLE_I16, SAMPLE_U16, SAMPLE_I32 = range(4)
+# dspfx_pitch_param: the Pitch Detector's sliders (nodes/pitch.rs:47-56), 0.5 each by default
+PITCH_POWER, PITCH_CLARITY, PITCH_PICK = range(3)
+PITCH_WINDOW = 1024
 
 # every symbol include/dspfx.h declares
 EXPORTS = [
@@ -59,6 +62,8 @@ EXPORTS = [
     "dspfx_comm_last_error", "dspfx_mix_allreduce",
     "dspfx_set_param_seq", "dspfx_param_log", "dspfx_frames_submitted", "dspfx_process_bus", "dspfx_kernels_ready", "dspfx_comm_backend",
     "dspfx_reserve_delay_len", "dspfx_ring_trim", "dspfx_process_pcm", "dspfx_process_host_pcm",
+    "dspfx_pitch_create", "dspfx_pitch_destroy", "dspfx_pitch_push", "dspfx_pitch_slot", "dspfx_pitch_set_param", "dspfx_pitch_read",
+    "dspfx_pitch_reset", "dspfx_pitch_windows",
 ]
 COMM_ID_BYTES = 128
 
@@ -91,6 +96,11 @@ class _ParamEvent(C.Structure):
 
 class _PcmIo(C.Structure):
     _fields_ = [("in_format", C.c_int32), ("in_channels", C.c_int32), ("out_format", C.c_int32), ("out_channels", C.c_int32)]
+
+
+class _PitchDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
+                ("power_thresh", C.c_float), ("clarity_thresh", C.c_float), ("pick_thresh", C.c_float)]
 
 
 class _Ctl(C.Structure):
@@ -190,6 +200,16 @@ def lib():
     L.dspfx_mix_allreduce.argtypes = [vp, vp, f32p, C.c_uint32, C.c_uint64, vp]
     L.dspfx_algorithmic_bytes_per_sample.restype = C.c_double
     L.dspfx_algorithmic_bytes_per_sample.argtypes = [vp, C.c_uint32]
+    L.dspfx_pitch_create.argtypes = [C.POINTER(_PitchDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_pitch_destroy.argtypes = [vp]
+    L.dspfx_pitch_push.argtypes = [vp, vp, C.c_uint32, vp]
+    L.dspfx_pitch_slot.restype = C.c_void_p
+    L.dspfx_pitch_slot.argtypes = [vp]
+    L.dspfx_pitch_set_param.argtypes = [vp, C.c_int, C.c_float]
+    L.dspfx_pitch_read.argtypes = [vp, vp, vp, vp]
+    L.dspfx_pitch_reset.argtypes = [vp]
+    L.dspfx_pitch_windows.restype = C.c_int64
+    L.dspfx_pitch_windows.argtypes = [vp]
     _lib = L
     return L
 
@@ -729,6 +749,83 @@ class Comm:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.L.dspfx_comm_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PitchBank:
+    """The Pitch Detector node (nodes/pitch.rs) for N channels (include/dspfx.h, dspfx_pitch_*): blocks pushed in the layout
+    of `tile_channels` (as Engine's), a McLeod pitch and clarity per channel for every 1024 frames, held until the next
+    window that gives one.  Device tensors in, device tensors out; asynchronous on `stream` like Engine.process."""
+
+    def __init__(self, channels: int, device: int = 0, tile_channels: int = 0, power_thresh: float = 0.5,
+                 clarity_thresh: float = 0.5, pick_thresh: float = 0.5):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.h = C.c_void_p()
+        d = _PitchDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, power_thresh, clarity_thresh, pick_thresh)
+        rc = self.L.dspfx_pitch_create(C.byref(d), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
+        """Append a device block [n_frames][N] (or the tiled form); runs the windows that fall due."""
+        if n_frames is None:
+            n_frames = block.numel() // self.channels if hasattr(block, "numel") else None
+        self._chk(self.L.dspfx_pitch_push(self.h, _ptr(block), int(n_frames), C.c_void_p(stream) if stream else None))
+
+    def slot(self) -> Optional[int]:
+        """Device address of the next 128-frame slot (None unless the frames pushed are a multiple of 128)."""
+        return self.L.dspfx_pitch_slot(self.h)
+
+    def slot_tensor(self):
+        """The next slot as a float32 device tensor of 128 * N elements over the bank's own memory (valid while the bank
+        lives; None when there is no slot): an Engine writes its block there, then push(slot, 128) copies nothing."""
+        import torch
+        addr = self.slot()
+        if addr is None:
+            return None
+
+        class _Slot:
+            __cuda_array_interface__ = {"shape": (BUF_SIZE * self.channels,), "typestr": "<f4", "data": (addr, False),
+                                        "version": 2}
+        return torch.as_tensor(_Slot(), device=torch.device("cuda", self.device))
+
+    def set_param(self, which: int, value: float):
+        self._chk(self.L.dspfx_pitch_set_param(self.h, int(which), float(value)))
+
+    def read(self, freq=None, clarity=None, stream: int = 0):
+        """-> (freq, clarity), float32 device tensors [N] (made when not given)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if freq is None:
+            freq = torch.empty(self.channels, dtype=torch.float32, device=dev)
+        if clarity is None:
+            clarity = torch.empty(self.channels, dtype=torch.float32, device=dev)
+        self._chk(self.L.dspfx_pitch_read(self.h, _ptr(freq), _ptr(clarity), C.c_void_p(stream) if stream else None))
+        return freq, clarity
+
+    def reset(self):
+        self._chk(self.L.dspfx_pitch_reset(self.h))
+
+    @property
+    def windows(self) -> int:
+        return int(self.L.dspfx_pitch_windows(self.h))
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_pitch_destroy(h)
             h.value = None
 
     def __del__(self):

@@ -1,0 +1,548 @@
+// pitch_kernels.hip -- the Pitch Detector bank (include/dspfx.h, dspfx_pitch_*): nodes/pitch.rs:120-146 for N channels.
+//   slot copy     a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store
+//   pitch_detect  one window of every channel: McLeod pitch and clarity, 8 bytes of result per channel that has one
+//   pitch_read    the held results into the caller's freq[N] / clarity[N]
+// The window store is a ring of 9 slots of 128 frames, each slot in the desc's layout for a 128-frame block, so an engine
+// can write its output straight into the next slot (dspfx_pitch_slot).  A window is 8 consecutive slots; the ninth is the
+// one being filled while the window before it has not been detected yet (it falls due only with its next frame).
+//
+// pitch_detect, one workgroup of 256 threads per PAIR of channels (c0, c0 + 1): the pair is one complex signal
+// z = x0 + i x1, zero-padded to 2048.  Z = FFT(z); X0 = (Z + conj Z(-k)) / 2, X1 = (Z - conj Z(-k)) / 2i;
+// IFFT(|X0|^2 + i |X1|^2) = r_lin0 + i r_lin1, the two linear autocorrelations, exact for every lag < 1024 (2048 >= 2 * 1024 - 1).
+// The crate's FFT is 1536 long, so its lags alias: r(tau) = r_lin(tau) + r_lin(1536 - tau) for tau > 512, added here.
+// The FFTs are radix-4 (x5) + radix-2 Stockham passes between two LDS buffers, twiddles from a table rounded once from f64.
+// m(tau) comes from prefix sums of x^2 (no running subtraction), then n, then the peak pick as six LDS reductions per
+// channel: lobe end, largest key maximum M, first tau >= pick * M, end of its run, the run's maximum, its first tau.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/dspfx.h"
+
+namespace {
+
+constexpr uint32_t SLOT = DSPFX_BUF_SIZE;          // frames per slot: one process block
+constexpr uint32_t WIN = DSPFX_PITCH_WINDOW;       // McLeodDetector::new(1024, 512): size
+constexpr uint32_t PAD = 512;                      //   padding: the crate's FFT is 1536 long
+constexpr uint32_t SLOTS_PER_WIN = WIN / SLOT;
+constexpr uint32_t RING = SLOTS_PER_WIN + 1;
+constexpr int FFT_N = 2048;
+constexpr int DT = 256;                            // threads of pitch_detect
+constexpr int CHUNK = WIN / DT;                    // frames each thread loads (both channels)
+constexpr int TPC = DT / 2;                        // threads per channel in the peak pick
+constexpr int PER = WIN / TPC;                     // lags each of them holds
+constexpr float RATE = 48000.0f;                   // pitch.rs:134 get_pitch(view, 48_000, ...)
+
+// element (f, c) of a block of nf frames in the desc's layout (dspfx_engine_desc.tile_channels)
+__host__ __device__ inline size_t lay(uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
+    return W ? ((size_t)(c / W) * nf + f) * W + (c % W) : (size_t)f * N + c;
+}
+
+// ---- slot copy: `rows` rows of `len` elements, row r at src + r * spitch / dst + r * dpitch (units of T) -------------
+template <typename T>
+__global__ void pitch_copy(const T *__restrict__ src, T *__restrict__ dst, size_t rows, size_t len, size_t spitch,
+                           size_t dpitch) {
+    const size_t total = rows * len;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = e / len, k = e - r * len;
+        dst[r * dpitch + k] = src[r * spitch + k];
+    }
+}
+
+hipError_t launch_copy(const float *src, float *dst, size_t rows, size_t len, size_t spitch, size_t dpitch, hipStream_t s) {
+    const bool v4 = len % 4 == 0 && spitch % 4 == 0 && dpitch % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0;
+    const size_t units = rows * (v4 ? len / 4 : len);
+    const unsigned blocks = (unsigned)std::min<size_t>((units + 255) / 256, 1u << 20);
+    if (v4)
+        pitch_copy<float4><<<blocks, 256, 0, s>>>((const float4 *)src, (float4 *)dst, rows, len / 4, spitch / 4, dpitch / 4);
+    else
+        pitch_copy<float><<<blocks, 256, 0, s>>>(src, dst, rows, len, spitch, dpitch);
+    return hipGetLastError();
+}
+
+// ---- detection ---------------------------------------------------------------------------------------------------------
+struct DetArgs {
+    const float *ring;
+    float2 *res;                 // [N] (frequency, clarity), written only where the window gives a result
+    const float2 *tw;            // [FFT_N] exp(-2 pi i t / FFT_N)
+    uint32_t N, W;
+    uint32_t slot0;              // ring slot of the window's first 128 frames
+    float P, C, K;               // power_thresh, clarity_thresh, pick_thresh
+};
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// one Stockham pass of radix R over FFT_N points, Ns = the product of the radices before it
+template <int R, bool INV>
+__device__ __forceinline__ void fft_pass(const float2 *src, float2 *dst, int Ns, const float2 *__restrict__ tw) {
+    constexpr int NR = FFT_N / R;
+    for (int j = threadIdx.x; j < NR; j += DT) {
+        const int k = j & (Ns - 1);
+        float2 v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = src[j + r * NR];
+#pragma unroll
+        for (int r = 1; r < R; ++r) {
+            float2 w = tw[k * r * (FFT_N / (Ns * R))];
+            if (INV) w.y = -w.y;
+            v[r] = cmul(v[r], w);
+        }
+        if (R == 2) {
+            const float2 a = v[0];
+            v[0] = cadd(a, v[1]);
+            v[1] = csub(a, v[1]);
+        } else {
+            const float2 a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]), a3 = csub(v[1], v[3]);
+            const float2 ja3 = INV ? make_float2(-a3.y, a3.x) : make_float2(a3.y, -a3.x);   // +-i * a3
+            v[0] = cadd(a0, a2);
+            v[1] = cadd(a1, ja3);
+            v[2] = csub(a0, a2);
+            v[3] = csub(a1, ja3);
+        }
+        const int d = (j - k) * R + k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) dst[d + r * Ns] = v[r];
+    }
+}
+
+// 2048 points: in a, out a (six passes, b in between)
+template <bool INV>
+__device__ void fft2048(float2 *a, float2 *b, const float2 *__restrict__ tw) {
+    fft_pass<4, INV>(a, b, 1, tw);
+    __syncthreads();
+    fft_pass<4, INV>(b, a, 4, tw);
+    __syncthreads();
+    fft_pass<4, INV>(a, b, 16, tw);
+    __syncthreads();
+    fft_pass<4, INV>(b, a, 64, tw);
+    __syncthreads();
+    fft_pass<4, INV>(a, b, 256, tw);
+    __syncthreads();
+    fft_pass<2, INV>(b, a, 1024, tw);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
+    __shared__ float2 A[FFT_N];
+    __shared__ float2 B[FFT_N];
+    __shared__ float wsum[2][DT / 64];
+    __shared__ int s_flag[2], s_lobe[2], s_M[2], s_t1[2], s_end[2], s_bmax[2], s_arg[2];
+    const int t = threadIdx.x;
+    // consecutive pairs on one XCD (workgroups are dealt round-robin over the 8), so their shared cache lines meet in one L2
+    uint32_t blk = blockIdx.x;
+    if (gridDim.x % 8 == 0) blk = (blk % 8) * (gridDim.x / 8) + blk / 8;
+    const uint32_t c0 = 2 * blk;
+    const bool has1 = c0 + 1 < a.N;
+    // c0 is even, so (c0, c0 + 1) share a tile when W >= 2, and every row starts 8-byte aligned when N is even
+    const bool pair2 = has1 && (a.W ? a.W >= 2 : a.N % 2 == 0);
+    if (t < 2) {
+        s_flag[t] = 0;
+        s_lobe[t] = WIN;
+        s_M[t] = 0;
+        s_t1[t] = WIN;
+        s_end[t] = WIN;
+        s_bmax[t] = 0;
+        s_arg[t] = WIN;
+    }
+
+    // ---- the window: frames [CHUNK t, CHUNK t + CHUNK) of both channels, kept in registers to the end
+    float x0[CHUNK], x1[CHUNK];
+    bool bad0 = false, bad1 = false, nz0 = false, nz1 = false;
+#pragma unroll
+    for (int i = 0; i < CHUNK; ++i) {
+        const uint32_t j = CHUNK * t + i;
+        uint32_t slot = a.slot0 + j / SLOT;
+        if (slot >= RING) slot -= RING;
+        const float *base = a.ring + (size_t)slot * SLOT * a.N;
+        const size_t e0 = lay(j % SLOT, c0, SLOT, a.N, a.W);
+        if (pair2) {                     // the pair is adjacent and 8-byte aligned: one load
+            const float2 v = *(const float2 *)(base + e0);
+            x0[i] = v.x;
+            x1[i] = v.y;
+        } else {
+            x0[i] = base[e0];
+            x1[i] = has1 ? base[lay(j % SLOT, c0 + 1, SLOT, a.N, a.W)] : 0.0f;
+        }
+        bad0 |= !isfinite(x0[i]);
+        bad1 |= !isfinite(x1[i]);
+        nz0 |= x0[i] != 0.0f;
+        nz1 |= x1[i] != 0.0f;
+        A[j] = make_float2(x0[i], x1[i]);
+        A[j + WIN] = make_float2(0.0f, 0.0f);
+    }
+    // prefix sums of x^2: P[k] = sum_{j<k} x_j^2 for this thread's k, from a scan of the per-thread sums
+    float q0 = 0.0f, q1 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < CHUNK; ++i) {
+        q0 += x0[i] * x0[i];
+        q1 += x1[i] * x1[i];
+    }
+    const int lane = t & 63, wv = t >> 6;
+    float i0 = q0, i1 = q1;
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+        const float u0 = __shfl_up(i0, d, 64), u1 = __shfl_up(i1, d, 64);
+        if (lane >= d) {
+            i0 += u0;
+            i1 += u1;
+        }
+    }
+    if (lane == 63) {
+        wsum[0][wv] = i0;
+        wsum[1][wv] = i1;
+    }
+    __syncthreads();
+    if (bad0) atomicOr(&s_flag[0], 1);
+    if (bad1) atomicOr(&s_flag[1], 1);
+    if (nz0) atomicOr(&s_flag[0], 2);
+    if (nz1) atomicOr(&s_flag[1], 2);
+    float e0 = i0 - q0, e1 = i1 - q1, tot0 = 0.0f, tot1 = 0.0f;
+    for (int w = 0; w < DT / 64; ++w) {
+        if (w < wv) {
+            e0 += wsum[0][w];
+            e1 += wsum[1][w];
+        }
+        tot0 += wsum[0][w];
+        tot1 += wsum[1][w];
+    }
+    float pre0[CHUNK], pre1[CHUNK];      // P[CHUNK t + i]
+#pragma unroll
+    for (int i = 0; i < CHUNK; ++i) {
+        pre0[i] = e0;
+        pre1[i] = e1;
+        e0 += x0[i] * x0[i];
+        e1 += x1[i] * x1[i];
+    }
+
+    // ---- r_lin of both channels
+    const float2 *tw = a.tw;
+    fft2048<false>(A, B, tw);
+    for (int k = t; k < FFT_N; k += DT) {
+        const float2 z = A[k], zm = A[(FFT_N - k) & (FFT_N - 1)];
+        const float ar = z.x + zm.x, ai = z.y - zm.y;    // 2 X0
+        const float br = z.x - zm.x, bi = z.y + zm.y;    // 2 i X1
+        B[k] = make_float2(ar * ar + ai * ai, br * br + bi * bi);
+    }
+    __syncthreads();
+    fft2048<true>(B, A, tw);             // B = 4 * 2048 * (r_lin0 + i r_lin1)
+
+    // P into A (free now): Pf[ch][k], k in [0, 1024]
+    float *Pf = (float *)A;
+#pragma unroll
+    for (int i = 0; i < CHUNK; ++i) {
+        Pf[CHUNK * t + i] = pre0[i];
+        Pf[(WIN + 1) + CHUNK * t + i] = pre1[i];
+    }
+    if (t == 0) {
+        Pf[WIN] = tot0;
+        Pf[(WIN + 1) + WIN] = tot1;
+    }
+    __syncthreads();
+
+    // ---- n(tau) for this thread's channel and lags
+    const int ch = t / TPC, lt = t % TPC;
+    const float *P = Pf + ch * (WIN + 1);
+    const float tot = P[WIN];
+    const float scale = 1.0f / (4.0f * FFT_N);
+    float n[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int tau = PER * lt + i;
+        const float2 rv = B[tau];
+        float r = ch ? rv.y : rv.x;
+        // m_lin(u) = sum_{j < 1024-u} x_j^2 + sum_{j >= u} x_j^2
+        float m = P[WIN - tau] + (tot - P[tau]);
+        if (tau > (int)PAD) {
+            const int u = (int)(WIN + PAD) - tau;
+            const float2 ra = B[u];
+            r += ch ? ra.y : ra.x;
+            m += P[WIN - u] + (tot - P[u]);
+        }
+        r *= scale;
+        n[i] = m > 0.0f ? 2.0f * r / m : 0.0f;
+    }
+    __syncthreads();
+    float *nb = (float *)B + ch * WIN;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) nb[PER * lt + i] = n[i];
+
+    // ---- the peak pick
+    int best = WIN;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int tau = PER * lt + i;
+        if (tau >= 1 && !(n[i] > 0.0f) && tau < best) best = tau;
+    }
+    if (best < (int)WIN) atomicMin(&s_lobe[ch], best);
+    __syncthreads();
+    const int lobe = s_lobe[ch];
+    float mx = 0.0f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i)
+        if (PER * lt + i > lobe && n[i] > mx) mx = n[i];
+    if (mx > 0.0f) atomicMax(&s_M[ch], __float_as_int(mx));     // positive floats order as their bits
+    __syncthreads();
+    const float M = __int_as_float(s_M[ch]);
+    const float thr = a.K * M;
+    best = WIN;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int tau = PER * lt + i;
+        if (tau > lobe && n[i] > 0.0f && n[i] >= thr && tau < best) best = tau;
+    }
+    if (best < (int)WIN) atomicMin(&s_t1[ch], best);
+    __syncthreads();
+    const int t1 = s_t1[ch];
+    best = WIN;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int tau = PER * lt + i;
+        if (tau > t1 && !(n[i] > 0.0f) && tau < best) best = tau;
+    }
+    if (best < (int)WIN) atomicMin(&s_end[ch], best);
+    __syncthreads();
+    const int e = s_end[ch];
+    mx = 0.0f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int tau = PER * lt + i;
+        if (tau >= t1 && tau < e && n[i] > mx) mx = n[i];
+    }
+    if (mx > 0.0f) atomicMax(&s_bmax[ch], __float_as_int(mx));
+    __syncthreads();
+    const float bmax = __int_as_float(s_bmax[ch]);
+    best = WIN;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int tau = PER * lt + i;
+        if (tau >= t1 && tau < e && n[i] == bmax && tau < best) best = tau;
+    }
+    if (best < (int)WIN) atomicMin(&s_arg[ch], best);
+    __syncthreads();
+
+    // ---- the result
+    if (lt != 0 || (ch == 1 && !has1)) return;
+    const int flag = s_flag[ch];
+    if ((flag & 1) || !(flag & 2) || tot < a.P) return;          // non-finite, all zero, power below the threshold
+    const int k = s_arg[ch];
+    if (s_M[ch] == 0 || t1 >= (int)WIN || k >= (int)WIN) return;
+    const float b = nb[k];
+    if (b < a.C) return;
+    const float av = nb[k - 1];
+    float delta = 0.0f, y = b;
+    if (k < (int)WIN - 1) {
+        const float c = nb[k + 1];
+        const float den = 2.0f * (2.0f * b - av - c);
+        if (den != 0.0f) delta = (c - av) / den;
+        y = b + (c - av) * delta / 4.0f;
+    }
+    a.res[c0 + ch] = make_float2(RATE / ((float)k + delta), y / nb[0]);
+}
+
+__global__ void pitch_read(const float2 *__restrict__ res, float *__restrict__ freq, float *__restrict__ clarity, uint32_t N) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const float2 v = res[c];
+    freq[c] = v.x;
+    clarity[c] = v.y;
+}
+
+}  // namespace
+
+struct dspfx_pitch {
+    dspfx_pitch_desc desc{};
+    std::mutex mu;                              // push / read / reset / destroy are serialised
+    float *ring = nullptr;                      // RING slots of 128 x N floats
+    float2 *res = nullptr;                      // [N]
+    float2 *tw = nullptr;                       // [FFT_N]
+    hipEvent_t ev = nullptr;
+    uint64_t frames = 0;                        // frames pushed since create / reset
+    std::atomic<int64_t> windows{0};
+    std::atomic<float> th[3];                   // dspfx_pitch_param
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+
+namespace {
+
+bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
+
+void release(dspfx_pitch *p) {
+    (void)hipSetDevice(p->desc.device);
+    if (p->ring) (void)hipFree(p->ring);
+    if (p->res) (void)hipFree(p->res);
+    if (p->tw) (void)hipFree(p->tw);
+    if (p->ev) (void)hipEventDestroy(p->ev);
+    delete p;
+}
+
+// a call on a stream other than the last one used waits (on the device) for that one
+hipError_t order(dspfx_pitch *p, hipStream_t s) {
+    hipError_t err = hipSuccess;
+    if (p->used && s != p->last) {
+        err = hipEventRecord(p->ev, p->last);
+        if (err == hipSuccess) err = hipStreamWaitEvent(s, p->ev, 0);
+    }
+    p->last = s;
+    p->used = true;
+    return err;
+}
+
+// frames [f, f + nf) of `block` (n_frames long, starting at stream frame f0) into the ring; nf stays within one slot
+hipError_t copy_in(dspfx_pitch *p, const float *block, uint32_t n_frames, uint64_t f0, uint64_t f, uint32_t nf, hipStream_t s) {
+    const uint32_t N = p->desc.channels, W = p->desc.tile_channels;
+    const uint32_t fa = (uint32_t)(f - f0), g0 = (uint32_t)(f % SLOT);
+    float *slot = p->ring + (size_t)((f / SLOT) % RING) * SLOT * N;
+    if (!W) return launch_copy(block + (size_t)fa * N, slot + (size_t)g0 * N, 1, (size_t)nf * N, 0, 0, s);
+    return launch_copy(block + (size_t)fa * W, slot + (size_t)g0 * W, N / W, (size_t)nf * W, (size_t)n_frames * W,
+                       (size_t)SLOT * W, s);
+}
+
+hipError_t detect(dspfx_pitch *p, uint64_t w, hipStream_t s) {
+    DetArgs a;
+    a.ring = p->ring;
+    a.res = p->res;
+    a.tw = p->tw;
+    a.N = p->desc.channels;
+    a.W = p->desc.tile_channels;
+    a.slot0 = (uint32_t)((w * SLOTS_PER_WIN) % RING);
+    a.P = p->th[DSPFX_PITCH_POWER].load();
+    a.C = p->th[DSPFX_PITCH_CLARITY].load();
+    a.K = p->th[DSPFX_PITCH_PICK].load();
+    pitch_detect<<<(a.N + 1) / 2, DT, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+#define PITCH_HIP(call)                              \
+    do {                                             \
+        if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
+    } while (0)
+
+extern "C" int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **out) {
+    if (!desc || !out) return DSPFX_ERR_INVALID;
+    *out = nullptr;
+    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
+    const uint32_t N = desc->channels, W = desc->tile_channels;
+    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
+    if (desc->device < 0 || desc->device >= count) return DSPFX_ERR_INVALID;
+    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    dspfx_pitch *p = new (std::nothrow) dspfx_pitch;
+    if (!p) return DSPFX_ERR_OOM;
+    p->desc = *desc;
+    p->th[DSPFX_PITCH_POWER] = desc->power_thresh;
+    p->th[DSPFX_PITCH_CLARITY] = desc->clarity_thresh;
+    p->th[DSPFX_PITCH_PICK] = desc->pick_thresh;
+    std::vector<float2> tw(FFT_N);
+    for (int k = 0; k < FFT_N; ++k) {
+        const double ang = -2.0 * M_PI * k / FFT_N;
+        tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+    }
+    if (hipMalloc((void **)&p->ring, (size_t)RING * SLOT * N * sizeof(float)) != hipSuccess ||
+        hipMalloc((void **)&p->res, (size_t)N * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&p->tw, FFT_N * sizeof(float2)) != hipSuccess) {
+        (void)hipGetLastError();
+        release(p);
+        return DSPFX_ERR_OOM;
+    }
+    if (hipMemcpy(p->tw, tw.data(), FFT_N * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(p->res, 0, (size_t)N * sizeof(float2)) != hipSuccess ||
+        hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess) {
+        release(p);
+        return DSPFX_ERR_HIP;
+    }
+    *out = p;
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_pitch_destroy(dspfx_pitch *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        (void)hipSetDevice(p->desc.device);
+        if (p->used) (void)hipStreamSynchronize(p->last);   // the bank's work is ordered on the last stream it used
+    }
+    release(p);
+    return DSPFX_OK;
+}
+
+extern "C" float *dspfx_pitch_slot(dspfx_pitch *p) {
+    if (!p) return nullptr;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->frames % SLOT) return nullptr;
+    return p->ring + (size_t)((p->frames / SLOT) % RING) * SLOT * p->desc.channels;
+}
+
+// pitch.rs:120-146 per frame position: window w runs once frame 1024 (w + 1) has been pushed too, and before the ring
+// slot that frame went to is overwritten (the 9th slot keeps the window whole up to then; see the top of this file)
+extern "C" int dspfx_pitch_push(dspfx_pitch *p, const float *block, uint32_t n_frames, void *stream) {
+    if (!p || !block || n_frames == 0) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const uint32_t N = p->desc.channels;
+    const float *slot = p->frames % SLOT ? nullptr : p->ring + (size_t)((p->frames / SLOT) % RING) * SLOT * N;
+    const bool in_place = block == slot;
+    if (in_place && n_frames != SLOT) return DSPFX_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    PITCH_HIP(hipSetDevice(p->desc.device));
+    PITCH_HIP(order(p, s));
+    const uint64_t f0 = p->frames, f1 = f0 + n_frames;
+    uint64_t f = f0;
+    for (;;) {
+        // window w falls due with frame 1024 (w + 1): F >= 1024 (w + 1) + 1.  It is launched before that frame is copied:
+        // the copy goes to the ring's ninth slot, never into the window.
+        if (f > 0 && f % WIN == 0 && f1 > f) {
+            PITCH_HIP(detect(p, f / WIN - 1, s));
+            p->windows.fetch_add(1);
+        }
+        if (f == f1) break;
+        const uint64_t end = std::min<uint64_t>(f1, (f / SLOT + 1) * SLOT);
+        if (!in_place) PITCH_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
+        f = end;
+        p->frames = f;                   // what has been launched so far: a failure part-way leaves a consistent state
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_pitch_set_param(dspfx_pitch *p, int which, float value) {
+    if (!p || which < DSPFX_PITCH_POWER || which > DSPFX_PITCH_PICK || !std::isfinite(value)) return DSPFX_ERR_INVALID;
+    p->th[which].store(value);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_pitch_read(dspfx_pitch *p, float *freq, float *clarity, void *stream) {
+    if (!p || !freq || !clarity) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    hipStream_t s = (hipStream_t)stream;
+    PITCH_HIP(hipSetDevice(p->desc.device));
+    PITCH_HIP(order(p, s));
+    const uint32_t N = p->desc.channels;
+    pitch_read<<<(N + 255) / 256, 256, 0, s>>>(p->res, freq, clarity, N);
+    PITCH_HIP(hipGetLastError());
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_pitch_reset(dspfx_pitch *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    PITCH_HIP(hipSetDevice(p->desc.device));
+    PITCH_HIP(hipMemsetAsync(p->res, 0, (size_t)p->desc.channels * sizeof(float2), p->last));
+    p->frames = 0;
+    p->windows = 0;
+    return DSPFX_OK;
+}
+
+extern "C" int64_t dspfx_pitch_windows(const dspfx_pitch *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    return p->windows.load();
+}

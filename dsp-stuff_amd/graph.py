@@ -24,7 +24,10 @@ Mux / Demux (nodes/mux.rs:42-55, nodes/demux.rs:42-58) are pure routing and cost
 the identity on its selected port (links into the other port are computed but unused, as in the reference), a
 demux is the identity whose unselected output port delivers zeros -- still a connected pipe for whoever averages it.
 
-The display-only nodes (pitch detector, wave view, spectrogram) produce no signal; they are dropped on import.
+The display-only nodes (pitch detector, wave view, spectrogram) produce no signal; they are dropped on import.  What feeds
+a pitch detector is kept in `Graph.pitch_taps` (node id -> PitchTap: the producers linked into its "in" port and its saved
+thresholds), for a PitchBank (dspfx_pitch_*) to evaluate (GraphEngine(pitch=True)); its threshold sliders are not ports (pitch.rs:47-56 has no
+`as_input`), so a link into one is rejected.
 
 Not expressible: cycles (the reference's scheduler would deadlock on them too), muff (GPL crate, source absent),
 slider ports with fan-in.
@@ -32,9 +35,9 @@ slider ports with fan-in.
 from __future__ import annotations
 
 import json
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
-from . import (ADD, DISTORT, ERR_UNSUPPORTED, FIR, FUZZ, GAIN, GRAPH_INPUT, GRAPH_INPUT2, GRAPH_INPUTS, GRAPH_MAX_IO, GRAPH_MAX_NODES, GRAPH_ZERO,
+from . import (ADD, DISTORT, PitchBank, ERR_UNSUPPORTED, FIR, FUZZ, GAIN, GRAPH_INPUT, GRAPH_INPUT2, GRAPH_INPUTS, GRAPH_MAX_IO, GRAPH_MAX_NODES, GRAPH_ZERO,
                LINK_INPUT, LINK_INTERNAL, LINK_SIDE_RAW, MIX, PORT_MAIN, PORT_RAW, PORT_SIDE, PORT_SLIDER, SIGNAL_GEN, DspfxError, Engine,
                NodeSpec)
 from .config import _TABLE, DspConfigError, _node_from_cfg
@@ -43,6 +46,7 @@ _UNSUPPORTED = {"muff"}                                # GPL crate, source not i
 _SINKS = {"pitch", "wave_view", "spectrogram"}          # display-only: `process` writes no output (pitch.rs:120-146,
                                                         # wave_view.rs:157-175), so they and the links into them are dropped
 _ROUTING = {"mux", "demux"}
+PITCH_SLIDERS = ("power_thresh", "clarity_thresh", "pick_thresh")   # pitch.rs:47-56, saved, 0.5 by default
 ZERO = -1          # pseudo producer: the unselected output port of a demux (a connected pipe that carries zeros)
 
 
@@ -58,6 +62,18 @@ class _GNode:
         self.outs: List[Tuple[int, str]] = []  # (consumer id, port name)
 
 
+class PitchTap:
+    """A Pitch Detector node of the document: `links` = producer ids linked into its "in" port, in link order (ZERO for a
+    demux's unselected port), `thresholds` = its saved (power_thresh, clarity_thresh, pick_thresh)."""
+    __slots__ = ("id", "links", "thresholds")
+
+    def __init__(self, nid, links, thresholds):
+        self.id, self.links, self.thresholds = nid, links, thresholds
+
+    def __repr__(self):
+        return f"PitchTap(id={self.id}, links={self.links}, thresholds={self.thresholds})"
+
+
 class Graph:
     """Parsed DSPConfig: nodes with their incoming links per port, in document order."""
 
@@ -70,10 +86,20 @@ class Graph:
             raise DspConfigError(f"not a DSPConfig document: {e}") from None
         self.nodes: Dict[int, _GNode] = {}
         self.dropped: List[int] = []
+        self.pitch_taps: Dict[int, PitchTap] = {}
+        pitch_cfg: Dict[int, dict] = {}
         for n in raw_nodes:
             tn = n["typename"]
             if tn in _SINKS:
                 self.dropped.append(int(n["id"]))
+                if tn == "pitch":
+                    cfg = n.get("cfg", {})
+                    try:
+                        th = tuple(float(cfg.get(f, 0.5)) for f in PITCH_SLIDERS)
+                    except (TypeError, ValueError):
+                        raise DspConfigError(f"pitch node {n['id']}: thresholds are not numbers") from None
+                    pitch_cfg[int(n["id"])] = cfg
+                    self.pitch_taps[int(n["id"])] = PitchTap(int(n["id"]), [], th)
                 continue
             if tn in _UNSUPPORTED:
                 raise DspConfigError(f"node type {tn!r} is outside the accelerated path")
@@ -100,6 +126,19 @@ class Graph:
             raise DspConfigError(f"link refers to unknown {which[:-1]} port {port_id} of node {node_id}")
 
         for (ln, lp), (rn, rp) in raw_links:
+            if rn in self.pitch_taps:
+                pname = next((name for name, pid in pitch_cfg[rn].get("inputs", {}).items() if int(pid) == rp), None)
+                if pname in PITCH_SLIDERS:
+                    raise DspConfigError(f"pitch node {rn}: slider {pname!r} is driven by a link (it is not an input port)")
+                if pname != "in":
+                    raise DspConfigError(f"link refers to unknown input port {rp} of node {rn}")
+                if ln not in self.nodes:
+                    raise DspConfigError("link refers to a missing node")
+                src = self.nodes[ln]
+                oname = port_name(ln, lp, "outputs")
+                sel = src.typename == "demux" and oname != src.cfg.get("out_port", "A").lower()
+                self.pitch_taps[rn].links.append(ZERO if sel else ln)
+                continue
             if rn in self.dropped:
                 continue
             if ln not in self.nodes or rn not in self.nodes:
@@ -172,9 +211,10 @@ class _Run:
         self.scratch_side = None
 
 
-def plan_runs(g: Graph):
+def plan_runs(g: Graph, keep=frozenset()):
     """Cut the graph into maximal linear runs (each becomes one fused engine).  A node joins its producer's run
-    when it is the producer's only consumer and is fed by nothing else on its main port."""
+    when it is the producer's only consumer and is fed by nothing else on its main port.  The nodes in `keep` (a pitch
+    tap reads them) always end their run, so that their block is in memory."""
     run_of: Dict[int, _Run] = {}
     runs: List[_Run] = []
     for nid in g.order:
@@ -183,7 +223,7 @@ def plan_runs(g: Graph):
             continue
         prev = g.nodes[n.main[0]] if len(n.main) == 1 and n.main[0] != ZERO else None
         joinable = (prev is not None and prev.spec is not None and len(prev.outs) == 1
-                    and n.spec.kind != SIGNAL_GEN)
+                    and n.spec.kind != SIGNAL_GEN and prev.id not in keep)
         if joinable:
             r = run_of[prev.id]
             # one side input per engine, shared by every Add/Mix of its chain: two of them may share a run
@@ -211,11 +251,12 @@ def run_link_flags(r: _Run) -> int:
     return flags
 
 
-def fused_plan(g: Graph):
+def fused_plan(g: Graph, taps: Sequence[Sequence[int]] = ()):
     """The graph as `dspfx_graph_set` takes it: (node specs in topological order, links), or None when it cannot
-    be one kernel (too many nodes, a FIR or Fuzz node)."""
+    be one kernel (too many nodes, a FIR or Fuzz node).  `taps`: producer lists (link order) of pitch taps, each an extra
+    output block 1, 2, ... averaged like the Output node's port."""
     order = [nid for nid in g.order if g.nodes[nid].spec is not None]
-    if len(order) > GRAPH_MAX_NODES:
+    if len(order) > GRAPH_MAX_NODES or 1 + len(taps) > GRAPH_MAX_IO:
         return None
     for nid in order:
         sp = g.nodes[nid].spec
@@ -236,6 +277,8 @@ def fused_plan(g: Graph):
         for k, srcs in sorted(n.ctl.items()):
             links += [(src(s), idx[nid], PORT_SLIDER + k) for s in srcs]
     links += [(src(s), len(order), PORT_MAIN) for s in g.nodes[g.outputs[0]].main]
+    for t, srcs in enumerate(taps):
+        links += [(src(s), len(order) + 1 + t, PORT_MAIN) for s in srcs]
     return [g.nodes[nid].spec for nid in order], links
 
 
@@ -408,7 +451,7 @@ def _late_source_order(g: Graph) -> List[int]:
     return order
 
 
-def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_MAX_IO):
+def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_MAX_IO, taps: Sequence[Sequence[int]] = ()):
     """ANY graph as a short series of generated kernels: the evaluation order is cut into REGIONS of at most `max_nodes`
     fusable nodes, each one kernel with up to `max_io` input blocks (signals from the Input node, from earlier regions,
     from FIR / Fuzz nodes -- read as main inputs, Add / Mix side inputs or control signals alike) and up to `max_io`
@@ -423,6 +466,9 @@ def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_
       ("output", refs)                             the Output node's average when no region is left to carry it
 
     A ref is -1 (the graph's Input block), (step index, output block) or None (a connected pipe of zeros).
+    `taps`: producer lists of pitch taps, read where the Output node is: the last region's output blocks 1 .. len(taps),
+    averaged like the Output node's port; when the graph ends in a FIR / Fuzz node the "output" step carries their refs
+    too: ("output", refs, tap_refs).
     None when some region would need more than `max_io` blocks either way."""
     order = _late_source_order(g)
     out_id = g.outputs[0]
@@ -432,6 +478,10 @@ def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_
     for nid in order + [out_id]:
         for p in g.producers(g.nodes[nid]):
             last_use[p] = max(last_use.get(p, -1), pos[nid])
+    tap_srcs = [[v for v in srcs if v != ZERO] for srcs in taps]
+    for srcs in tap_srcs:
+        for p in srcs:
+            last_use[p] = max(last_use.get(p, -1), len(order))
     loc: Dict[int, object] = {}
     if g.inputs:
         loc[g.inputs[0]] = -1
@@ -464,8 +514,13 @@ def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_
                 for v in g.producers(g.nodes[c]):
                     if v not in inside and v not in ext:
                         ext.append(v)
+            if final:
+                for srcs in tap_srcs:
+                    for v in srcs:
+                        if v not in inside and v not in ext:
+                            ext.append(v)
             outs = [] if final else [v for v in region if last_use.get(v, -1) >= end]      # read by a later step
-            n_out = (1 if final else 0) + len(outs)
+            n_out = (1 + len(taps) if final else 0) + len(outs)
             if len(ext) <= max_io and n_out <= max_io:
                 best = (end, region, ext, outs, final)
         if best is None:
@@ -489,9 +544,11 @@ def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_
         nn = len(region)
         if final:
             links += [(src(s), nn, PORT_MAIN) for s in g.nodes[out_id].main]
+            for t, srcs in enumerate(taps):
+                links += [(src(s), nn + 1 + t, PORT_MAIN) for s in srcs]
         if not final and not outs:
             outs = [region[-1]]                          # nothing of this region is read later (dead branch): still one block
-        base = 1 if final else 0
+        base = 1 + len(taps) if final else 0
         for m_, v in enumerate(outs):
             links.append((idx[v], nn + base + m_, PORT_MAIN | PORT_RAW))
         steps.append(("region", [g.nodes[v].spec for v in region], links, [loc[v] for v in ext], base + len(outs)))
@@ -499,7 +556,8 @@ def region_plan(g: Graph, max_nodes: int = GRAPH_MAX_NODES, max_io: int = GRAPH_
             loc[v] = (len(steps) - 1, base + m_)
         i = end
     if not steps or steps[-1][0] != "region":        # the graph ends in a FIR / Fuzz node (or has no effect node at all)
-        steps.append(("output", [ref(v) for v in g.nodes[out_id].main]))
+        steps.append(("output", [ref(v) for v in g.nodes[out_id].main]) +
+                     (([[ref(v) for v in srcs] for srcs in taps],) if taps else ()))
     return steps
 
 
@@ -512,16 +570,31 @@ class GraphEngine:
     """N independent copies of a saved graph.  `process(x)` takes the Input node's block [n_frames][N] (device
     tensor, the engine's layout) and returns the Output node's block.
     fused: None = one generated kernel for the whole graph when it can be had, else a series of them (segment_plan),
-    else run by run; True = insist on the one kernel; False = always run by run."""
+    else run by run; True = insist on the one kernel; False = always run by run.
+    pitch=True: every Pitch Detector node of the document gets a PitchBank, fed every block with its "in" port's value,
+    averaged over its links like any port (collect_and_average): an extra output block of the one kernel or of the last
+    region kernel, dspfx_link_average in the run-by-run plan (the series plan is not used then).  `pitch(node_id)` reads
+    its results, `set_pitch_param` stores its thresholds, `pitch_tap(node_id)` is the block it was fed last."""
 
     def __init__(self, text: str, channels: int, max_frames: int = 128, device: int = 0, tile_channels: int = 0,
                  page_round: bool = False, fused: Optional[bool] = None, max_nodes: Optional[int] = None,
-                 regions: Optional[bool] = None):
+                 regions: Optional[bool] = None, pitch: bool = False):
         import torch
         self.torch = torch
         self.g = Graph(text, page_round)
         self.N, self.B, self.tile = channels, max_frames, tile_channels
         self.dev = torch.device("cuda", device)
+        # pitch taps: banks, and the block each is fed (taps without a link read zeros: node.rs:288)
+        self.banks: Dict[int, PitchBank] = {}
+        self.tap_ids: List[int] = []                   # taps with links, in the order of their output blocks
+        self.tap_bufs: Dict[int, object] = {}
+        if pitch:
+            for nid, tap in self.g.pitch_taps.items():
+                self.banks[nid] = PitchBank(channels, device=device, tile_channels=tile_channels, power_thresh=tap.thresholds[0],
+                                            clarity_thresh=tap.thresholds[1], pick_thresh=tap.thresholds[2])
+                if tap.links:
+                    self.tap_ids.append(nid)
+        tap_links = [self.g.pitch_taps[t].links for t in self.tap_ids]
         self.fused: Optional[Engine] = None
         self.series, self.series_kind = [], []
         self.regions = []
@@ -529,12 +602,14 @@ class GraphEngine:
         self.zeros = torch.zeros(max_frames * channels, dtype=torch.float32, device=self.dev)
         self.final = self._buf()
         # regions=True (tests): go straight to the general region plan; False: never use it
+        for nid in self.tap_ids:
+            self.tap_bufs[nid] = self._buf()
         if regions:
-            if not self._build_regions(region_plan(self.g, max_nodes or GRAPH_MAX_NODES), device):
+            if not self._build_regions(region_plan(self.g, max_nodes or GRAPH_MAX_NODES, taps=tap_links), device):
                 raise DspConfigError("this graph has no region plan")
             return
         # max_nodes (tests): cut the graph as if a kernel held only that many nodes
-        plan = fused_plan(self.g) if fused is not False and max_nodes is None else None
+        plan = fused_plan(self.g, tap_links) if fused is not False and max_nodes is None else None
         if plan is not None:
             eng = Engine(channels, max_frames, device=device, tile_channels=tile_channels)
             try:
@@ -551,7 +626,8 @@ class GraphEngine:
             return
         # FIR / Fuzz nodes in series with fusable sub-graphs: one generated kernel per segment
         self.series = []                   # [(engine, out buffer)]
-        steps = (segment_plan(self.g, max_nodes) if max_nodes is not None else series_plan(self.g)) if fused is None else None
+        steps = (segment_plan(self.g, max_nodes) if max_nodes is not None else series_plan(self.g)) \
+            if fused is None and not self.tap_ids else None
         if steps is not None:
             try:
                 for kind, *what in steps:
@@ -576,9 +652,10 @@ class GraphEngine:
             self.util = self.series[0][0]
             return
         # anything else: regions with several input / output blocks each (region_plan), FIR / Fuzz nodes in between
-        if fused is None and regions is not False and self._build_regions(region_plan(self.g, max_nodes or GRAPH_MAX_NODES), device):
+        if fused is None and regions is not False and \
+                self._build_regions(region_plan(self.g, max_nodes or GRAPH_MAX_NODES, taps=tap_links), device):
             return
-        self.runs, self.run_of = plan_runs(self.g)
+        self.runs, self.run_of = plan_runs(self.g, keep={s for ls in tap_links for s in ls})
         for r in self.runs:
             head = r.nodes[0]
             side_node = next((m for m in r.nodes if m.side), None)
@@ -616,7 +693,8 @@ class GraphEngine:
                                       scratch=self._buf() if len(main_refs) > 1 else None))
                     eng.set_chain([spec])
                 else:
-                    built.append(dict(kind=kind, eng=None, refs=what[0], outs=[self.final]))
+                    built.append(dict(kind=kind, eng=None, refs=what[0], tap_refs=what[1] if len(what) > 1 else [],
+                                      outs=[self.final]))
         except DspfxError as e:
             for st in built:
                 if st["eng"] is not None:
@@ -624,6 +702,8 @@ class GraphEngine:
             if e.status != ERR_UNSUPPORTED:
                 raise
             return False
+        if self.tap_ids and built[-1]["kind"] == "region":           # its output blocks 1 .. k are the taps
+            built[-1]["outs"][1:1 + len(self.tap_ids)] = [self.tap_bufs[t] for t in self.tap_ids]
         self.regions = built
         self.util = next(st["eng"] for st in built if st["eng"] is not None) if any(st["eng"] for st in built) else \
             Engine(self.N, self.B, device=device, tile_channels=self.tile)
@@ -661,7 +741,12 @@ class GraphEngine:
     def process(self, x, n_frames: Optional[int] = None, stream: int = 0):
         nf = self.B if n_frames is None else int(n_frames)
         if self.fused is not None:
-            self.fused.process(self.zeros if x is None else x, out=self.final, n_frames=nf, stream=stream)
+            if self.tap_ids:
+                self.fused.process_io([self.zeros if x is None else x], [self.final] + [self.tap_bufs[t] for t in self.tap_ids], nf,
+                                      stream=stream)
+            else:
+                self.fused.process(self.zeros if x is None else x, out=self.final, n_frames=nf, stream=stream)
+            self._push_taps(nf, stream)
             return self.final
         if self.regions:
             x0 = self.zeros if x is None else x
@@ -685,6 +770,9 @@ class GraphEngine:
                     st["eng"].process(src, out=st["outs"][0], n_frames=nf, stream=stream, ctl=ctl or None)
                 else:
                     self.util.link_average([at(r) for r in st["refs"]], self.final, nf, stream)
+                    for t, refs in zip(self.tap_ids, st["tap_refs"]):
+                        self.util.link_average([at(r) for r in refs], self.tap_bufs[t], nf, stream)
+            self._push_taps(nf, stream)
             return self.regions[-1]["outs"][0]
         if self.series:
             x0 = self.zeros if x is None else x
@@ -729,7 +817,32 @@ class GraphEngine:
             r.engine.process(src, out=r.out, side=side, n_frames=nf, stream=stream, ctl=ctl or None)
         out_node = self.g.nodes[self.g.outputs[0]]
         self.util.link_average([self._source(s, x) for s in out_node.main], self.final, nf, stream)
+        for t in self.tap_ids:
+            self.util.link_average([self._source(s, x) for s in self.g.pitch_taps[t].links], self.tap_bufs[t], nf, stream)
+        self._push_taps(nf, stream)
         return self.final
+
+    def _push_taps(self, nf: int, stream: int):
+        for nid, bank in self.banks.items():
+            bank.push(self.tap_bufs.get(nid, self.zeros), nf, stream)
+
+    def _bank(self, node_id: int) -> PitchBank:
+        if node_id not in self.banks:
+            raise KeyError(f"node {node_id} is not a Pitch Detector of this graph, or the engine was made without pitch=True")
+        return self.banks[node_id]
+
+    def pitch(self, node_id: int, stream: int = 0):
+        """-> (freq, clarity): the held results of a Pitch node, float32 device tensors [N]."""
+        return self._bank(node_id).read(stream=stream)
+
+    def set_pitch_param(self, node_id: int, which: int, value: float):
+        """Store a threshold of a Pitch node (PITCH_POWER / PITCH_CLARITY / PITCH_PICK); later detections use it."""
+        self._bank(node_id).set_param(which, value)
+
+    def pitch_tap(self, node_id: int):
+        """The block a Pitch node was fed last (its "in" port's average; zeros for a node without links)."""
+        self._bank(node_id)
+        return self.tap_bufs.get(node_id, self.zeros)
 
     def tune_placement(self, x, n_frames: Optional[int] = None, stream: int = 0):
         """Re-tune the delay rings' placement of every generated kernel against the blocks it will really read and write
@@ -756,3 +869,5 @@ class GraphEngine:
             eng.close()
         for r in self.runs:
             r.engine.close()
+        for bank in self.banks.values():
+            bank.close()

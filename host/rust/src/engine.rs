@@ -415,3 +415,68 @@ impl ParamHandle {
         if rc == 0 { Ok(()) } else { Err(rc) }
     }
 }
+
+/// The Pitch Detector node (nodes/pitch.rs) for N channels (`dspfx_pitch_*`): device blocks in, one McLeod pitch and clarity
+/// per channel for every 1024 frames, held until the next window that gives one.  The sliders are `DSPFX_PITCH_*`.
+pub struct PitchBank {
+    h: *mut dspfx_pitch,
+    channels: u32,
+}
+unsafe impl Send for PitchBank {}
+// dspfx_pitch_set_param may be called from any thread; the other calls are serialised by the bank
+unsafe impl Sync for PitchBank {}
+
+impl PitchBank {
+    /// `tile_channels`: 0 (frame-major) or the engine's W; the thresholds are the node's saved sliders (0.5 by default).
+    pub fn new(device: i32, channels: u32, tile_channels: u32, power_thresh: f32, clarity_thresh: f32,
+               pick_thresh: f32) -> Result<Self, Error> {
+        let desc = dspfx_pitch_desc {
+            abi_version: DSPFX_ABI_VERSION,
+            device,
+            channels,
+            tile_channels,
+            power_thresh,
+            clarity_thresh,
+            pick_thresh,
+        };
+        let mut h = ptr::null_mut();
+        let rc = unsafe { dspfx_pitch_create(&desc, &mut h) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: "dspfx_pitch_create".into() });
+        }
+        Ok(PitchBank { h, channels })
+    }
+    fn check(&self, rc: c_int, what: &str) -> Result<(), Error> {
+        if rc == DSPFX_OK { Ok(()) } else { Err(Error { status: rc, message: what.into() }) }
+    }
+    pub fn channels(&self) -> u32 { self.channels }
+    /// Appends `n_frames` frames of a DEVICE block in the bank's layout; runs the windows that fall due.  Asynchronous on `stream`.
+    pub unsafe fn push(&self, block: *const f32, n_frames: u32, stream: *mut std::os::raw::c_void) -> Result<(), Error> {
+        let rc = dspfx_pitch_push(self.h, block, n_frames, stream);
+        self.check(rc, "dspfx_pitch_push")
+    }
+    /// Where an engine writes its next 128-frame block so that `push(slot, 128, ..)` copies nothing (null between slots).
+    pub fn slot(&self) -> *mut f32 { unsafe { dspfx_pitch_slot(self.h) } }
+    pub fn set_param(&self, which: i32, value: f32) -> Result<(), Error> {
+        let rc = unsafe { dspfx_pitch_set_param(self.h, which as c_int, value) };
+        self.check(rc, "dspfx_pitch_set_param")
+    }
+    /// The held results into DEVICE arrays `freq[N]`, `clarity[N]`; asynchronous on `stream`.
+    pub unsafe fn read(&self, freq: *mut f32, clarity: *mut f32, stream: *mut std::os::raw::c_void) -> Result<(), Error> {
+        let rc = dspfx_pitch_read(self.h, freq, clarity, stream);
+        self.check(rc, "dspfx_pitch_read")
+    }
+    pub fn reset(&self) -> Result<(), Error> {
+        let rc = unsafe { dspfx_pitch_reset(self.h) };
+        self.check(rc, "dspfx_pitch_reset")
+    }
+    pub fn windows(&self) -> i64 { unsafe { dspfx_pitch_windows(self.h) } }
+}
+
+impl Drop for PitchBank {
+    fn drop(&mut self) {
+        unsafe {
+            dspfx_pitch_destroy(self.h);
+        }
+    }
+}

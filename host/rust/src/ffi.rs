@@ -9,6 +9,12 @@ pub struct dspfx_engine {
     _private: [u8; 0],
 }
 
+/// Opaque pitch detector bank handle (`typedef struct dspfx_pitch dspfx_pitch`).
+#[repr(C)]
+pub struct dspfx_pitch {
+    _private: [u8; 0],
+}
+
 /// Opaque communicator handle (`typedef struct dspfx_comm dspfx_comm`).
 #[repr(C)]
 pub struct dspfx_comm {
@@ -77,6 +83,19 @@ pub struct dspfx_pcm_io {
     pub out_channels: i32,
 }
 
+/// The Pitch Detector bank's descriptor (`dspfx_pitch_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_pitch_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub channels: u32,
+    pub tile_channels: u32,
+    pub power_thresh: f32,
+    pub clarity_thresh: f32,
+    pub pick_thresh: f32,
+}
+
 pub const DSPFX_ABI_VERSION: u32 = 2;
 pub const DSPFX_BUF_SIZE: u32 = 128; // dsp-stuff/src/node.rs:257
 pub const DSPFX_MAX_NODES: u32 = 32;
@@ -96,6 +115,12 @@ pub const DSPFX_SAMPLE_F32: i32 = 0;
 pub const DSPFX_SAMPLE_I16: i32 = 1;
 pub const DSPFX_SAMPLE_U16: i32 = 2;
 pub const DSPFX_SAMPLE_I32: i32 = 3;
+
+// dspfx_pitch_param (nodes/pitch.rs:47-56 sliders)
+pub const DSPFX_PITCH_POWER: i32 = 0;
+pub const DSPFX_PITCH_CLARITY: i32 = 1;
+pub const DSPFX_PITCH_PICK: i32 = 2;
+pub const DSPFX_PITCH_WINDOW: u32 = 1024;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -228,4 +253,13 @@ extern "C" {
     pub fn dspfx_profile_enable(e: *mut dspfx_engine, enable: c_int) -> c_int;
     pub fn dspfx_profile_read(e: *mut dspfx_engine, total_ms: *mut f64, launches: *mut u32, kernel_name: *mut c_char, cap: usize, reset: c_int) -> c_int;
     pub fn dspfx_algorithmic_bytes_per_sample(e: *const dspfx_engine, n_frames: u32) -> f64;
+
+    pub fn dspfx_pitch_create(desc: *const dspfx_pitch_desc, out: *mut *mut dspfx_pitch) -> c_int;
+    pub fn dspfx_pitch_destroy(p: *mut dspfx_pitch) -> c_int;
+    pub fn dspfx_pitch_push(p: *mut dspfx_pitch, block: *const f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_pitch_slot(p: *mut dspfx_pitch) -> *mut f32;
+    pub fn dspfx_pitch_set_param(p: *mut dspfx_pitch, which: c_int, value: f32) -> c_int;
+    pub fn dspfx_pitch_read(p: *mut dspfx_pitch, freq: *mut f32, clarity: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_pitch_reset(p: *mut dspfx_pitch) -> c_int;
+    pub fn dspfx_pitch_windows(p: *const dspfx_pitch) -> i64;
 }

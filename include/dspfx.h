@@ -593,6 +593,68 @@ int dspfx_profile_read(dspfx_engine *e, double *total_ms, uint32_t *launches, ch
 /* Algorithmic HBM bytes per channel-sample of the current chain at n_frames. */
 double dspfx_algorithmic_bytes_per_sample(const dspfx_engine *e, uint32_t n_frames);
 
+/* ---- pitch detector bank ---------------------------------------------------------------------------------
+ * The Pitch Detector node (nodes/pitch.rs:120-146) for N independent channels: a McLeod pitch and clarity per
+ * channel.  A separate object, fed with blocks of samples; it is not a node kind of the chain.
+ * Per channel, pitch.rs keeps a FIFO of samples; at the start of every process call, if it holds 1024 samples, it
+ * runs McLeodDetector::new(1024, 512).get_pitch(oldest 1024, 48000, power, clarity, pick) on them and stores the
+ * result when there is one, then drops those 1024 samples, and then appends the call's block.  So the windows are
+ * samples [1024 w, 1024 w + 1024), consecutive, and window w has been detected once frames [0, F) have been pushed
+ * with F >= 1024 (w + 1) + 1.  (This holds for any FIFO capacity of at least 1024 samples; rivulet's page-rounded
+ * circular_buffer(128) of f32 holds 1024.)  A push of any length runs the windows that fall due, in order.
+ * The detector (the pitch-detection crate, magnetophon's fork, Cargo.lock:3092-3096: not vendored, restated from
+ * McLeod & Wyvill 2005 with pitch.rs's parameters, UNPINNED), for one window x[0..1024):
+ *   power = sum x^2; power < power_thresh, a non-finite or an all-zero window: no result;
+ *   r(tau), tau in [0, 1024): the circular autocorrelation of x zero-padded to 1536 (the crate's FFT length):
+ *       r_lin(tau) + r_lin(1536 - tau) for tau > 512;
+ *   m(tau): the energy of the same pairs, m_lin(tau) = sum_{j < 1024-tau} x_j^2 + sum_{j >= tau} x_j^2, plus
+ *       m_lin(1536 - tau) for tau > 512; n(tau) = 2 r(tau) / m(tau) (0 where m <= 0);
+ *   key maxima: after the positive lobe at tau = 0, the first largest n of every run with n > 0 (an open run counts);
+ *   pick: the first key maximum with n >= pick_thresh * (largest key maximum); none, or its n < clarity_thresh:
+ *       no result;
+ *   parabola through its neighbours a, b, c: delta = (c - a) / (2 (2b - a - c)) (0 if that is 0/0 or tau = 1023),
+ *       frequency = 48000 / (tau + delta), clarity = (b + (c - a) delta / 4) / n(0).
+ * The result is held per channel (0, 0 initially) and replaced only when a window gives one.
+ * Layout: every block pushed is in the layout of the desc, exactly as dspfx_engine_desc's channels / tile_channels
+ * (the tiled form for a block of n_frames).  The bank stores the samples in 128-frame slots, each in that layout. */
+typedef struct dspfx_pitch dspfx_pitch;
+typedef struct dspfx_pitch_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t channels;        /* N */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    float power_thresh;       /* pitch.rs sliders, default 0.5 each */
+    float clarity_thresh;
+    float pick_thresh;
+} dspfx_pitch_desc;
+/* which threshold dspfx_pitch_set_param stores */
+typedef enum dspfx_pitch_param {
+    DSPFX_PITCH_POWER = 0,
+    DSPFX_PITCH_CLARITY = 1,
+    DSPFX_PITCH_PICK = 2
+} dspfx_pitch_param;
+/* Samples per window (a slot holds DSPFX_BUF_SIZE = 128 frames; a window is 8 slots). */
+#define DSPFX_PITCH_WINDOW 1024
+int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **out);
+int dspfx_pitch_destroy(dspfx_pitch *p);
+/* Appends n_frames >= 1 frames (a device buffer in the desc's layout) and runs every detection that falls due, in
+ * order; asynchronous on `stream`, stream-ordered like the process calls.  When `block` is dspfx_pitch_slot(p) and
+ * n_frames is 128, the samples are already in place and nothing is copied. */
+int dspfx_pitch_push(dspfx_pitch *p, const float *block, uint32_t n_frames, void *stream);
+/* The device address where the next 128 frames belong (a 128-frame block in the desc's layout), so that an engine can
+ * write its output there and push it without a copy; NULL while the frames pushed are not a multiple of 128.
+ * The slot may still be read by the detection the previous push launched: a write into it must be stream-ordered
+ * after the previous dspfx_pitch_push (the same stream, or one that waits for it). */
+float *dspfx_pitch_slot(dspfx_pitch *p);
+/* Stores a threshold (dspfx_pitch_param); it applies to every detection a later push launches.  Any thread. */
+int dspfx_pitch_set_param(dspfx_pitch *p, int which, float value);
+/* Writes the held results into device arrays freq[N], clarity[N]; asynchronous on `stream`. */
+int dspfx_pitch_read(dspfx_pitch *p, float *freq, float *clarity, void *stream);
+/* Back to the state after create: no samples, results 0 (queued on the stream last used); the thresholds stay. */
+int dspfx_pitch_reset(dspfx_pitch *p);
+/* Windows detected so far (since create or reset). */
+int64_t dspfx_pitch_windows(const dspfx_pitch *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,4 +297,34 @@ class GpuChain {
     Engine eng_;
 };
 
+// The Pitch Detector node (nodes/pitch.rs) for N channels (include/dspfx.h, dspfx_pitch_*): device blocks in the layout of
+// tile_channels, a McLeod pitch and clarity per channel for every 1024 frames, held until the next window that gives one.
+class PitchBank {
+  public:
+    enum Param : int { Power = DSPFX_PITCH_POWER, Clarity = DSPFX_PITCH_CLARITY, Pick = DSPFX_PITCH_PICK };
+    explicit PitchBank(std::uint32_t channels, int device = 0, std::uint32_t tile_channels = 0, float power_thresh = 0.5f,
+                       float clarity_thresh = 0.5f, float pick_thresh = 0.5f) {
+        const dspfx_pitch_desc d{DSPFX_ABI_VERSION, device, channels, tile_channels, power_thresh, clarity_thresh, pick_thresh};
+        chk(dspfx_pitch_create(&d, &p_));
+    }
+    ~PitchBank() { dspfx_pitch_destroy(p_); }
+    PitchBank(const PitchBank &) = delete;
+    PitchBank &operator=(const PitchBank &) = delete;
+    // device block of n_frames; asynchronous on `stream`.  push(slot(), 128) copies nothing.
+    void push(const float *block, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_pitch_push(p_, block, n_frames, stream)); }
+    float *slot() { return dspfx_pitch_slot(p_); }
+    void set_param(Param which, float value) { chk(dspfx_pitch_set_param(p_, which, value)); }
+    // device arrays freq[N], clarity[N]
+    void read(float *freq, float *clarity, void *stream = nullptr) { chk(dspfx_pitch_read(p_, freq, clarity, stream)); }
+    void reset() { chk(dspfx_pitch_reset(p_)); }
+    std::int64_t windows() const { return dspfx_pitch_windows(p_); }
+    dspfx_pitch *raw() { return p_; }
+
+  private:
+    static void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    }
+    dspfx_pitch *p_ = nullptr;
+};
+
 }  // namespace dspfx
