@@ -48,6 +48,7 @@ SAMPLE_F32, SAMPLE_I16, SAMPLE_U16, SAMPLE_I32 = range(4)
 # dspfx_pitch_param: the Pitch Detector's sliders (nodes/pitch.rs:47-56), 0.5 each by default
 PITCH_POWER, PITCH_CLARITY, PITCH_PICK = range(3)
 PITCH_WINDOW = 1024
+RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
 EXPORTS = [
@@ -64,6 +65,8 @@ EXPORTS = [
     "dspfx_reserve_delay_len", "dspfx_ring_trim", "dspfx_process_pcm", "dspfx_process_host_pcm",
     "dspfx_pitch_create", "dspfx_pitch_destroy", "dspfx_pitch_push", "dspfx_pitch_slot", "dspfx_pitch_set_param", "dspfx_pitch_read",
     "dspfx_pitch_reset", "dspfx_pitch_windows",
+    "dspfx_resample_create", "dspfx_resample_destroy", "dspfx_resample_push", "dspfx_resample_slot", "dspfx_resample_pull",
+    "dspfx_resample_available", "dspfx_resample_skip", "dspfx_resample_reset", "dspfx_resample_plan",
 ]
 COMM_ID_BYTES = 128
 
@@ -101,6 +104,12 @@ class _PcmIo(C.Structure):
 class _PitchDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
                 ("power_thresh", C.c_float), ("clarity_thresh", C.c_float), ("pick_thresh", C.c_float)]
+
+
+class _ResampleDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
+                ("block_frames", C.c_uint32), ("slots", C.c_uint32), ("target_hz", C.c_uint32), ("out_format", C.c_int32),
+                ("out_channels", C.c_int32)]
 
 
 class _Ctl(C.Structure):
@@ -210,6 +219,18 @@ def lib():
     L.dspfx_pitch_reset.argtypes = [vp]
     L.dspfx_pitch_windows.restype = C.c_int64
     L.dspfx_pitch_windows.argtypes = [vp]
+    L.dspfx_resample_create.argtypes = [C.POINTER(_ResampleDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_resample_destroy.argtypes = [vp]
+    L.dspfx_resample_push.argtypes = [vp, vp, C.c_uint32, vp]
+    L.dspfx_resample_slot.restype = C.c_void_p
+    L.dspfx_resample_slot.argtypes = [vp]
+    L.dspfx_resample_pull.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
+    L.dspfx_resample_available.restype = C.c_int64
+    L.dspfx_resample_available.argtypes = [vp]
+    L.dspfx_resample_skip.argtypes = [vp, C.c_uint32]
+    L.dspfx_resample_reset.argtypes = [vp]
+    L.dspfx_resample_plan.argtypes = [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -826,6 +847,117 @@ class PitchBank:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.L.dspfx_pitch_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def resample_plan(target_hz: int, value: float, idx: int, n_out: int):
+    """dspfx_resample_plan, a pure host function (no GPU): the plan of the next n_out output frames of the 48 kHz -> target_hz
+    converter from the state (value, idx).  -> dict(advance uint32[n_out], depth uint32[n_out], coeff float64[n_out][16],
+    value, idx, input_len, pulled); coeff[o][2 n] / [2 n + 1] are the left / right coefficient of tap n."""
+    import numpy as np
+    L = lib()
+    adv = np.zeros(n_out, np.uint32)
+    dep = np.zeros(n_out, np.uint32)
+    coeff = np.zeros((n_out, 16), np.float64)
+    v, i, il, pl = C.c_double(value), C.c_uint32(idx), C.c_uint32(0), C.c_uint32(0)
+    rc = L.dspfx_resample_plan(int(target_hz), C.byref(v), C.byref(i), int(n_out), adv.ctypes.data_as(C.POINTER(C.c_uint32)),
+                               dep.ctypes.data_as(C.POINTER(C.c_uint32)), coeff.ctypes.data_as(C.POINTER(C.c_double)),
+                               C.byref(il), C.byref(pl))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    return {"advance": adv, "depth": dep, "coeff": coeff, "value": v.value, "idx": i.value, "input_len": il.value,
+            "pulled": pl.value}
+
+
+_PCM_TORCH = {SAMPLE_F32: "float32", SAMPLE_I16: "int16", SAMPLE_U16: "int16", SAMPLE_I32: "int32"}
+
+
+class Resampler:
+    """The output resampler bank (include/dspfx.h, dspfx_resample_*): the reference's output callback (devices.rs:394-498) for
+    N channels whose device runs at `target_hz`.  Blocks of engine output (48 kHz, the layout of `tile_channels`, as Engine's)
+    are pushed into a FIFO of `slots` slots of `block_frames` frames; pull(n_out) is one callback: n_out device frames of
+    every channel through dasp's Converter + 16-frame Sinc, in `out_format` with `out_channels` samples per frame.
+    Asynchronous on `stream` like Engine.process; the counters are host values."""
+
+    def __init__(self, channels: int, target_hz: int, device: int = 0, tile_channels: int = 0, block_frames: int = BUF_SIZE,
+                 slots: int = 4, out_format: int = SAMPLE_F32, out_channels: int = 1):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.block_frames, self.slots, self.target_hz = int(block_frames), int(slots), int(target_hz)
+        self.out_format, self.out_channels = int(out_format), int(out_channels)
+        self.h = C.c_void_p()
+        d = _ResampleDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, self.block_frames, self.slots,
+                          self.target_hz, self.out_format, self.out_channels)
+        rc = self.L.dspfx_resample_create(C.byref(d), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
+        """Append a device block [n_frames][N] (or the tiled form for n_frames).  slot_tensor() itself: nothing is copied.
+        A full FIFO raises DspfxError(ERR_STATE) and changes nothing."""
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        self._chk(self.L.dspfx_resample_push(self.h, _ptr(block), int(n_frames), C.c_void_p(stream) if stream else None))
+
+    def slot(self) -> Optional[int]:
+        """Device address of the next slot (None unless the frames pushed are a multiple of block_frames and a slot is free)."""
+        return self.L.dspfx_resample_slot(self.h)
+
+    def slot_tensor(self):
+        """The next slot as a float32 device tensor of block_frames * N elements over the bank's own memory (valid while the
+        bank lives; None when there is no slot): an Engine writes its block there, then push(slot) copies nothing."""
+        import torch
+        addr = self.slot()
+        if addr is None:
+            return None
+
+        class _Slot:
+            __cuda_array_interface__ = {"shape": (self.block_frames * self.channels,), "typestr": "<f4", "data": (addr, False),
+                                        "version": 2}
+        return torch.as_tensor(_Slot(), device=torch.device("cuda", self.device))
+
+    def pull(self, n_out: int, out=None, stream: int = 0):
+        """One output callback -> (out, consumed, underrun).  `out` (made when not given) holds n_out * N device frames of
+        out_channels samples in the bank's layout for a block of n_out frames: float32 / int16 / int32 (U16 as int16 bits)."""
+        import torch
+        if out is None:
+            out = torch.empty(int(n_out) * self.channels * self.out_channels, dtype=getattr(torch, _PCM_TORCH[self.out_format]),
+                              device=torch.device("cuda", self.device))
+        used, under = C.c_uint32(0), C.c_int32(0)
+        self._chk(self.L.dspfx_resample_pull(self.h, _ptr(out), int(n_out), C.byref(used), C.byref(under),
+                                             C.c_void_p(stream) if stream else None))
+        return out, int(used.value), bool(under.value)
+
+    @property
+    def available(self) -> int:
+        """Frames waiting in the FIFO (a host counter)."""
+        n = int(self.L.dspfx_resample_available(self.h))
+        if n < 0:
+            self._chk(n)
+        return n
+
+    def skip(self, n_frames: int):
+        """Drop the oldest n_frames waiting frames unseen by the converter (the catch-up of devices.rs:410-432)."""
+        self._chk(self.L.dspfx_resample_skip(self.h, int(n_frames)))
+
+    def reset(self):
+        self._chk(self.L.dspfx_resample_reset(self.h))
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_resample_destroy(h)
             h.value = None
 
     def __del__(self):

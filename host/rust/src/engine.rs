@@ -480,3 +480,74 @@ impl Drop for PitchBank {
         }
     }
 }
+
+/// The output resampler bank (`dspfx_resample_*`): the reference's output callback (devices.rs:394-498) for N channels whose
+/// device runs at `target_hz`.  Engine output goes into a FIFO of `block_frames`-frame slots; `pull` is one callback.
+pub struct Resampler {
+    h: *mut dspfx_resample,
+    channels: u32,
+}
+unsafe impl Send for Resampler {}
+// every call is serialised by the bank's own lock
+unsafe impl Sync for Resampler {}
+
+impl Resampler {
+    /// `tile_channels`: 0 (frame-major) or the engine's W; `out_format`: `DSPFX_SAMPLE_*`; `out_channels`: 1 or 2.
+    pub fn new(device: i32, channels: u32, tile_channels: u32, block_frames: u32, slots: u32, target_hz: u32, out_format: i32,
+               out_channels: i32) -> Result<Self, Error> {
+        let desc = dspfx_resample_desc {
+            abi_version: DSPFX_ABI_VERSION,
+            device,
+            channels,
+            tile_channels,
+            block_frames,
+            slots,
+            target_hz,
+            out_format,
+            out_channels,
+        };
+        let mut h = ptr::null_mut();
+        let rc = unsafe { dspfx_resample_create(&desc, &mut h) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: "dspfx_resample_create".into() });
+        }
+        Ok(Resampler { h, channels })
+    }
+    fn check(&self, rc: c_int, what: &str) -> Result<(), Error> {
+        if rc == DSPFX_OK { Ok(()) } else { Err(Error { status: rc, message: what.into() }) }
+    }
+    pub fn channels(&self) -> u32 { self.channels }
+    /// Appends `n_frames` frames of a DEVICE block in the bank's layout; a full FIFO is `DSPFX_ERR_STATE`.  Asynchronous on `stream`.
+    pub unsafe fn push(&self, block: *const f32, n_frames: u32, stream: *mut std::os::raw::c_void) -> Result<(), Error> {
+        let rc = dspfx_resample_push(self.h, block, n_frames, stream);
+        self.check(rc, "dspfx_resample_push")
+    }
+    /// Where an engine writes its next block so that `push(slot, block_frames, ..)` copies nothing (null when there is none).
+    pub fn slot(&self) -> *mut f32 { unsafe { dspfx_resample_slot(self.h) } }
+    /// One output callback: `n_out` device frames of every channel into the DEVICE buffer `out` -> (frames consumed, underrun).
+    pub unsafe fn pull(&self, out: *mut std::os::raw::c_void, n_out: u32, stream: *mut std::os::raw::c_void) -> Result<(u32, bool), Error> {
+        let mut consumed: u32 = 0;
+        let mut underrun: i32 = 0;
+        let rc = dspfx_resample_pull(self.h, out, n_out, &mut consumed, &mut underrun, stream);
+        self.check(rc, "dspfx_resample_pull")?;
+        Ok((consumed, underrun != 0))
+    }
+    pub fn available(&self) -> i64 { unsafe { dspfx_resample_available(self.h) } }
+    /// Drops the oldest `n_frames` waiting frames unseen by the converter (the catch-up of devices.rs:410-432).
+    pub fn skip(&self, n_frames: u32) -> Result<(), Error> {
+        let rc = unsafe { dspfx_resample_skip(self.h, n_frames) };
+        self.check(rc, "dspfx_resample_skip")
+    }
+    pub fn reset(&self) -> Result<(), Error> {
+        let rc = unsafe { dspfx_resample_reset(self.h) };
+        self.check(rc, "dspfx_resample_reset")
+    }
+}
+
+impl Drop for Resampler {
+    fn drop(&mut self) {
+        unsafe {
+            dspfx_resample_destroy(self.h);
+        }
+    }
+}

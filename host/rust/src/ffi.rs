@@ -83,6 +83,27 @@ pub struct dspfx_pcm_io {
     pub out_channels: i32,
 }
 
+/// Opaque output resampler bank handle (`typedef struct dspfx_resample dspfx_resample`).
+#[repr(C)]
+pub struct dspfx_resample {
+    _private: [u8; 0],
+}
+
+/// The output resampler bank's descriptor (`dspfx_resample_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_resample_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub channels: u32,
+    pub tile_channels: u32,
+    pub block_frames: u32,
+    pub slots: u32,
+    pub target_hz: u32,
+    pub out_format: i32,
+    pub out_channels: i32,
+}
+
 /// The Pitch Detector bank's descriptor (`dspfx_pitch_create`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -121,6 +142,8 @@ pub const DSPFX_PITCH_POWER: i32 = 0;
 pub const DSPFX_PITCH_CLARITY: i32 = 1;
 pub const DSPFX_PITCH_PICK: i32 = 2;
 pub const DSPFX_PITCH_WINDOW: u32 = 1024;
+// the most device frames one dspfx_resample_pull makes, and the most frames a FIFO slot holds
+pub const DSPFX_RESAMPLE_MAX_FRAMES: u32 = 4096;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -262,4 +285,13 @@ extern "C" {
     pub fn dspfx_pitch_read(p: *mut dspfx_pitch, freq: *mut f32, clarity: *mut f32, stream: *mut c_void) -> c_int;
     pub fn dspfx_pitch_reset(p: *mut dspfx_pitch) -> c_int;
     pub fn dspfx_pitch_windows(p: *const dspfx_pitch) -> i64;
+    pub fn dspfx_resample_create(desc: *const dspfx_resample_desc, out: *mut *mut dspfx_resample) -> c_int;
+    pub fn dspfx_resample_destroy(r: *mut dspfx_resample) -> c_int;
+    pub fn dspfx_resample_push(r: *mut dspfx_resample, block: *const f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_resample_slot(r: *mut dspfx_resample) -> *mut f32;
+    pub fn dspfx_resample_pull(r: *mut dspfx_resample, out: *mut c_void, n_out: u32, consumed: *mut u32, underrun: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_resample_available(r: *mut dspfx_resample) -> i64;
+    pub fn dspfx_resample_skip(r: *mut dspfx_resample, n_frames: u32) -> c_int;
+    pub fn dspfx_resample_reset(r: *mut dspfx_resample) -> c_int;
+    pub fn dspfx_resample_plan(target_hz: u32, value: *mut f64, idx: *mut u32, n_out: u32, advance: *mut u32, depth: *mut u32, coeff: *mut f64, input_len: *mut u32, pulled: *mut u32) -> c_int;
 }

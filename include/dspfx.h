@@ -376,7 +376,7 @@ int dspfx_process_host(dspfx_engine *e, const float *in, const float *side, floa
  *           is folded to mono as to_f32(a) + to_f32(b) -- one f32 add, no halving;
  *   output  do_write_1 / do_write_2 (devices.rs:394-498): from_sample of each f32 (devices.rs:424, 432, 477, 488); a
  *           2-channel device gets the same sample in both slots (o.fill(x), devices.rs:476-490).
- * The rules, AS RECALLED (the crate is not vendored; they are restated once, in pcm_kernels.hip to_f32 / from_f32):
+ * The rules, AS RECALLED (the crate is not vendored; they are restated once, in pcm_rules.h to_f32 / from_f32):
  *   I16  to f32: s / 32768.0f                    from f32: x * 32768.0f, truncated toward zero, saturated, NaN -> 0
  *   U16  to f32: (s - 32768) / 32768.0f          from f32: the I16 result + 32768 (bit pattern ^ 0x8000)
  *   I32  to f32: (float)s / 2147483648.0f        from f32: x * 2147483648.0f, truncated toward zero, saturated, NaN -> 0
@@ -654,6 +654,87 @@ int dspfx_pitch_read(dspfx_pitch *p, float *freq, float *clarity, void *stream);
 int dspfx_pitch_reset(dspfx_pitch *p);
 /* Windows detected so far (since create or reset). */
 int64_t dspfx_pitch_windows(const dspfx_pitch *p);
+
+/* ---- output resampler bank -----------------------------------------------------------------------------
+ * The reference's output stream runs at whatever rate the device offers closest to 48 kHz (devices.rs:513-527) and
+ * resamples every output callback from 48 kHz to it (devices.rs:394-498, 549-555) with dasp's Converter over a
+ * 16-frame Sinc.  This bank does that for N channels that share one device rate: blocks of engine output are pushed
+ * into a FIFO, and each pull is one output callback.  A separate object like the pitch bank; input streams are opened
+ * at 48 kHz by the reference and are never resampled, so there is no input direction.
+ * The rules (dasp_signal 0.11.0 interpolate::Converter, dasp_interpolate 0.11.0 sinc::Sinc over
+ * ring_buffer::Fixed<[f32; 16]>: not vendored, restated AS RECALLED, UNPINNED; include/dspfx_ir.hpp resample_dasp_sinc is
+ * the same state machine over f64 frames), per channel:
+ *   converter    ratio = 48000.0 / target_hz (f64); value = 0.0 at the start.  One output frame: while value >= 1.0
+ *                { pull one source frame into the interpolator; value -= 1.0 }; interpolate at value; value += ratio.
+ *   interpolator a ring of 16 frames, 0.0 at the start; a pulled frame enters at the back (ring[15]) and ring[0] drops
+ *                out; idx climbs by one per pulled frame up to 8.  At phase x: nl = idx, nr = idx + 1; depth = 8 once
+ *                idx >= 7, idx + 1 before.  v = 0.0f; for n in 0 .. depth, left tap then right tap:
+ *                    a = PI * (phase + n)            phase = x on the left, 1 - x on the right
+ *                    coeff = (a == 0 ? 1 : sin(a) / a) * (0.5 + 0.5 * cos(a / 8))                       (f64)
+ *                    v = v + (f32)(coeff * (f64)ring[k])      k = nl - n on the left, (nr + n) % 16 on the right
+ *                one f64 product rounded once to f32, f32 adds in that order, nothing contracted.  The % 16 is the
+ *                ring indexing modulo its length: in steady state the last right tap reads ring[0], the OLDEST frame.
+ *   callback     for n_out device frames: input_len = (size_t)((f32)n_out * (48000.0f / (f32)target_hz)), in f32.
+ *                Fewer than input_len frames waiting: every output slot is from_sample(0.0), nothing is consumed and the
+ *                converter is not touched (an underrun).  Otherwise the converter sees ALL waiting frames, makes
+ *                exactly n_out frames and pulls what its state needs (input_len - 1, input_len or input_len + 1 occur);
+ *                a pull past the last waiting frame yields 0.0 and is not counted (CountingSignal, devices.rs:376-388);
+ *                the frames pulled from the FIFO are released.  Each f32 goes through from_sample (the rules of the
+ *                "device sample formats" section); a 2-channel device gets it in both slots.
+ * The phases and coefficients depend on the call sequence only, never on samples: the host computes them
+ * (dspfx_resample_plan, f64, the C library's sin / cos) and the kernel multiplies and adds.
+ * Layout: the FIFO is `slots` slots of `block_frames` frames, each slot in the desc's layout for a block of block_frames
+ * frames (channels / tile_channels as dspfx_engine_desc), so an engine can write its output into dspfx_resample_slot
+ * and the push copies nothing.  A pull's `out` is in the same layout for a block of n_out frames, in the device format:
+ * element (f, c) is one device frame of out_channels samples. */
+typedef struct dspfx_resample dspfx_resample;
+typedef struct dspfx_resample_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t channels;        /* N */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t block_frames;    /* frames per FIFO slot, 1 ..= DSPFX_RESAMPLE_MAX_FRAMES (an engine's block: 128) */
+    uint32_t slots;           /* FIFO capacity = slots * block_frames frames; at least 3 */
+    uint32_t target_hz;       /* the device's rate, > 0; 48000 is NOT a bypass (the reference resamples then too) */
+    int32_t out_format;       /* dspfx_sample_format of a pull's `out` */
+    int32_t out_channels;     /* 1, or 2: each output sample written to both slots   devices.rs:476-490 */
+} dspfx_resample_desc;
+/* The most device frames one pull makes, and the most frames a slot holds. */
+#define DSPFX_RESAMPLE_MAX_FRAMES 4096
+/* A bad descriptor (no channels, a tile that is not a power of two dividing N, block_frames out of range, slots < 3,
+ * target_hz 0, an unknown format, a channel count other than 1 or 2) is DSPFX_ERR_INVALID. */
+int dspfx_resample_create(const dspfx_resample_desc *desc, dspfx_resample **out);
+int dspfx_resample_destroy(dspfx_resample *r);
+/* Appends n_frames >= 1 frames (a device buffer in the desc's layout for a block of n_frames); asynchronous on
+ * `stream`.  When `block` is dspfx_resample_slot(r), n_frames must be block_frames: the samples are in place and nothing
+ * is copied.  More frames than the FIFO has room for: DSPFX_ERR_STATE, nothing changed. */
+int dspfx_resample_push(dspfx_resample *r, const float *block, uint32_t n_frames, void *stream);
+/* The device address where the next block_frames frames belong, so that an engine can write its output there and push
+ * it without a copy; NULL while the frames pushed are not a multiple of block_frames, or the FIFO has no whole slot
+ * free.  A write into it must be stream-ordered after the pulls issued so far (the same stream, or one that waits). */
+float *dspfx_resample_slot(dspfx_resample *r);
+/* One output callback: n_out (1 ..= DSPFX_RESAMPLE_MAX_FRAMES) device frames of every channel into `out`;
+ * asynchronous on `stream`, stream-ordered.  *consumed = the frames released from the FIFO and *underrun = 1 when the
+ * callback found fewer than input_len frames (then *consumed = 0 and `out` is silence in the device format: 0x8000
+ * for U16); both are host values, known when the call returns (they depend on the counters only). */
+int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out, uint32_t *consumed, int32_t *underrun,
+                        void *stream);
+/* Frames waiting in the FIFO (a host counter: no device wait); negative: a dspfx_status. */
+int64_t dspfx_resample_available(dspfx_resample *r);
+/* Drops the oldest n_frames waiting frames unseen by the converter (the catch-up of devices.rs:410-432 is
+ * `skip(available - input_len)` before a pull; when to do it is the host's policy).  More than are waiting:
+ * DSPFX_ERR_INVALID, nothing changed. */
+int dspfx_resample_skip(dspfx_resample *r, uint32_t n_frames);
+/* Back to the state after create: ring 0.0 (queued on the stream last used), value = 0, idx = 0, FIFO empty. */
+int dspfx_resample_reset(dspfx_resample *r);
+/* PURE HOST function (no GPU, no bank): the plan of the next n_out output frames from the converter state (*value,
+ * *idx), which it updates.  For output frame o: advance[o] = source frames pulled first, depth[o] = the tap pairs
+ * summed, coeff[16 * o + 2 n] / [16 * o + 2 n + 1] = the left / right coefficient of tap n (0.0 from 2 * depth[o] on).
+ * advance, depth and coeff may be NULL (only the state is stepped).  *input_len = the callback's f32 figure above,
+ * *pulled = the sum of advance (what the converter asks for; a view shorter than that feeds 0.0).  Either may be NULL.
+ * dspfx_resample_pull runs exactly this plan. */
+int dspfx_resample_plan(uint32_t target_hz, double *value, uint32_t *idx, uint32_t n_out, uint32_t *advance,
+                        uint32_t *depth, double *coeff, uint32_t *input_len, uint32_t *pulled);
 
 #ifdef __cplusplus
 }

@@ -327,4 +327,59 @@ class PitchBank {
     dspfx_pitch *p_ = nullptr;
 };
 
+// The output resampler bank (include/dspfx.h, dspfx_resample_*): the reference's output callback (devices.rs:394-498) for N
+// channels whose device runs at target_hz.  Engine output goes into a FIFO of block_frames-frame slots; pull() is one callback.
+class Resampler {
+  public:
+    struct Pulled {
+        std::uint32_t consumed;   // frames released from the FIFO
+        bool underrun;            // fewer than input_len frames were waiting: `out` is silence, nothing was consumed
+    };
+    Resampler(std::uint32_t channels, std::uint32_t target_hz, int device = 0, std::uint32_t tile_channels = 0,
+              std::uint32_t block_frames = DSPFX_BUF_SIZE, std::uint32_t slots = 4, int out_format = DSPFX_SAMPLE_F32,
+              int out_channels = 1) {
+        const dspfx_resample_desc d{DSPFX_ABI_VERSION, device, channels, tile_channels, block_frames, slots, target_hz, out_format, out_channels};
+        chk(dspfx_resample_create(&d, &r_));
+    }
+    ~Resampler() { dspfx_resample_destroy(r_); }
+    Resampler(const Resampler &) = delete;
+    Resampler &operator=(const Resampler &) = delete;
+    // device block of n_frames; asynchronous on `stream`.  push(slot(), block_frames) copies nothing.  A full FIFO throws (DSPFX_ERR_STATE).
+    void push(const float *block, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_resample_push(r_, block, n_frames, stream)); }
+    float *slot() { return dspfx_resample_slot(r_); }
+    // n_out device frames of every channel into the device buffer `out`, in the bank's layout and format
+    Pulled pull(void *out, std::uint32_t n_out, void *stream = nullptr) {
+        std::uint32_t consumed = 0;
+        std::int32_t underrun = 0;
+        chk(dspfx_resample_pull(r_, out, n_out, &consumed, &underrun, stream));
+        return Pulled{consumed, underrun != 0};
+    }
+    std::int64_t available() { return dspfx_resample_available(r_); }
+    void skip(std::uint32_t n_frames) { chk(dspfx_resample_skip(r_, n_frames)); }
+    void reset() { chk(dspfx_resample_reset(r_)); }
+    dspfx_resample *raw() { return r_; }
+
+  private:
+    static void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    }
+    dspfx_resample *r_ = nullptr;
+};
+
+// The converter's plan for the next n_out output frames (dspfx_resample_plan: a pure host function, no GPU).
+struct ResamplePlan {
+    std::vector<std::uint32_t> advance, depth;
+    std::vector<double> coeff;                    // [n_out][16]
+    std::uint32_t input_len = 0, pulled = 0;
+};
+inline ResamplePlan resample_plan(std::uint32_t target_hz, double &value, std::uint32_t &idx, std::uint32_t n_out) {
+    ResamplePlan p;
+    p.advance.resize(n_out);
+    p.depth.resize(n_out);
+    p.coeff.resize((std::size_t)n_out * 16);
+    const int rc = dspfx_resample_plan(target_hz, &value, &idx, n_out, p.advance.data(), p.depth.data(), p.coeff.data(), &p.input_len, &p.pulled);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    return p;
+}
+
 }  // namespace dspfx
