@@ -430,14 +430,6 @@ extern "C" int dspfx_mix_allreduce(dspfx_engine *e, dspfx_comm *c, float *mix, u
             return fail(e, DSPFX_ERR_STATE, "mailbox all-reduce: %s", c->err.c_str());
         }
         if (n_frames > MBX_CAP) return fail(e, DSPFX_ERR_INVALID, "mailbox all-reduce: n_frames %u > %u", n_frames, MBX_CAP);
-        float div = 0.0f;
-        if (n_connected) {
-            if (e->div_n != n_connected || e->div_v == 0.0f) {
-                e->div_v = dspfx_link_divisor(n_connected);
-                e->div_n = n_connected;
-            }
-            div = e->div_v;
-        }
         MbxArgs a;
         memset(&a, 0, sizeof a);
         for (int p = 0; p < c->n_ranks; ++p) a.box[p] = m->peer[p];
@@ -449,7 +441,7 @@ extern "C" int dspfx_mix_allreduce(dspfx_engine *e, dspfx_comm *c, float *mix, u
         a.spin = m->spin;
         a.in = mix;
         a.out = mix;
-        a.div = div;
+        a.div = n_connected ? output_divisor(e, n_connected) : 0.0f;
         a.status = m->status;
         hipLaunchKernelGGL(mbx_allreduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
         HIPCHK(e, hipGetLastError());

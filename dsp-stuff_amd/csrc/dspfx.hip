@@ -117,8 +117,9 @@ int validate_node(dspfx_engine *e, const dspfx_node_desc &d) {
     return DSPFX_OK;
 }
 
-void fill_slot(const dspfx_engine *e, int idx, SlotArgs &s, uint32_t nframes) {
+void fill_slot(const dspfx_engine *e, const BlockCall &c, int idx, SlotArgs &s) {
     const Node &n = e->nodes[idx];
+    const uint32_t nframes = c.n_frames;
     memset(&s, 0, sizeof s);
     s.kind = n.d.kind;
     s.mode = n.d.mode;
@@ -146,7 +147,7 @@ void fill_slot(const dspfx_engine *e, int idx, SlotArgs &s, uint32_t nframes) {
     s.hop = node_hop(e, idx);
     s.rc = n.d.kind == DSPFX_DISTORT ? 1.0 / (double)n.d.params[0] : 0.0;
     for (int k = 0; k < 3; ++k) {
-        s.ctl[k] = n.ctl_now[k];
+        s.ctl[k] = c.signal(idx, k);
         s.latch[k] = n.latch[k];
     }
     s.latch_valid = n.latch_valid;
@@ -193,11 +194,64 @@ int ring_rows_copy(dspfx_engine *e, Node &n, uint32_t r0, uint32_t nrows, char *
 // rows of LDS the interpreter keeps per node (kind_nstate in chain_kernels.hip.h)
 int state_rows(const Node &n) { return kind_nstate(n.d.kind); }
 
-// One sub-block (nframes <= every delay length) through all stages.
-int run_subblock(dspfx_engine *e, const float *in, const float *side, float *out, float *mix,
-                 uint32_t nframes, uint32_t tile_frames, hipStream_t stream) {
-    const uint32_t N = e->desc.channels;
-    const float *src = in;
+// ---- the mix bus behind a block's launches ----------------------------------------------------------------------------
+
+// f32(0.0001 + n) by dspfx_link_divisor, whose literal f32 increment loop is O(n): the last one asked for is kept
+float output_divisor(dspfx_engine *e, uint64_t n_connected) {
+    if (e->div_n != n_connected || e->div_v == 0.0f) {
+        e->div_v = dspfx_link_divisor(n_connected);
+        e->div_n = n_connected;
+    }
+    return e->div_v;
+}
+
+// partials buffer b of the deferred / pipelined bus and its two events, on first use
+static int ensure_mixpart2(dspfx_engine *e, int b) {
+    if (e->mixpart2[b]) return DSPFX_OK;
+    HIPCHK(e, hipMalloc((void **)&e->mixpart2[b], e->mixpart_cols * e->desc.max_frames * sizeof(float)));
+    HIPCHK(e, hipEventCreateWithFlags(&e->ev_chain[b], hipEventDisableTiming));
+    HIPCHK(e, hipEventCreateWithFlags(&e->ev_red[b], hipEventDisableTiming));
+    return DSPFX_OK;
+}
+
+// A block whose last launch leaves `rows` rows of first-stage partial sums: *part = where they go.  Pipelined form: block k
+// (= mp_count) leaves them in mixpart2[k & 1], and *pipe is what its launch also carries -- stage 2 of block k-1 (its
+// partials -> slice sums in cur_b) and stage 3 of block k-2 (prev_b -> c.pipe_mix, divided by c.div).
+static int bus_begin(dspfx_engine *e, const BlockCall &c, uint32_t rows, float **part, FirMixPipe *pipe) {
+    if (rows > e->mixpart_cols) return fail(e, DSPFX_ERR_STATE, "mix partial buffer too small");
+    if (c.bus != BUS_PIPELINED) {
+        *part = c.bus == BUS_DEFERRED ? c.partials : e->mixpart;
+        return DSPFX_OK;
+    }
+    const int cur = (int)(e->mp_count & 1), prev = cur ^ 1;
+    *part = e->mixpart2[cur];
+    e->mp_rows[cur] = rows;
+    pipe->stage = (e->mp_count >= 1 ? 1 : 0) | (e->mp_count >= 2 ? 2 : 0);
+    pipe->rows_a = e->mp_rows[prev];
+    pipe->prev_a = e->mixpart2[prev];
+    pipe->cur_b = cur ? e->mixpart_b2 : e->mixpart_b;
+    pipe->prev_b = cur ? e->mixpart_b : e->mixpart_b2;
+    pipe->mix = c.pipe_mix;
+    pipe->div = c.div;
+    return DSPFX_OK;
+}
+
+// ... and what becomes of them behind that launch (unless the launch finished the bus in its own tail)
+static int bus_end(dspfx_engine *e, const BlockCall &c, uint32_t rows) {
+    if (c.bus == BUS_DEFERRED) {
+        e->part_stride[e->flip] = rows;
+        e->part_frames[e->flip] = c.n_frames;
+    } else if (c.bus == BUS_NOW) {
+        launch_mix_reduce(e->mixpart, e->mixpart_b, c.mix, c.n_frames, rows, c.stream);
+        if (c.div != 0.0f) launch_mix_finish(c.mix, c.n_frames, c.div, c.stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return DSPFX_OK;   // BUS_PIPELINED: the launches of the next two blocks go on with them
+}
+
+// ---- one sub-block, stage by stage --------------------------------------------------------------------------------------
+
+static Layout block_layout(const dspfx_engine *e, uint32_t tile_frames) {
     Layout lay{};
     if (e->desc.tile_channels) {
         const uint32_t W = e->desc.tile_channels;
@@ -208,266 +262,250 @@ int run_subblock(dspfx_engine *e, const float *in, const float *side, float *out
     } else {
         lay.w_shift = 31;
         lay.w_mask = 0x7fffffffu;
-        lay.ld = N;
+        lay.ld = e->desc.channels;
         lay.tile_stride = 0;
     }
-    bool bus_done = false;   // a FIR node that ends the chain left the mix bus' partial sums itself
+    return lay;
+}
+
+// graph engines: the blocks a generated kernel reads and writes beyond in / side / out, checked against the wiring
+static int graph_io_args(dspfx_engine *e, const BlockCall &c, GraphArgs &ga) {
+    const int n_nodes = (int)e->nodes.size();
+    for (const dspfx_graph_link &l : e->wiring) {
+        const int blk = graph_input_block(l.src);
+        if (blk == 1 && !c.side) return fail(e, DSPFX_ERR_INVALID, "this graph reads a second block (DSPFX_GRAPH_INPUT2): side must not be null");
+        if (blk >= 2 && !c.xin[blk]) return fail(e, DSPFX_ERR_INVALID, "this graph reads input block %d: pass it with dspfx_process_io", blk);
+        if (l.dst > n_nodes && !c.xout[l.dst - n_nodes]) return fail(e, DSPFX_ERR_INVALID, "this graph writes output block %d: pass it with dspfx_process_io", l.dst - n_nodes);   // (blocks are contiguous: validate_graph)
+    }
+    for (int k = 2; k < GRAPH_IO; ++k) ga.xin[k - 2] = c.xin[k];
+    for (int m = 1; m < GRAPH_IO; ++m) ga.xout[m - 1] = c.xout[m];
+    return DSPFX_OK;
+}
+
+// The stage's kernel for this call, *tail = the one for the channels a whole-wave launch leaves over.
+static const Variant *stage_kernel(dspfx_engine *e, const BlockCall &c, const Stage &st, const Variant **tail) {
+    const uint32_t N = e->desc.channels;
+    *tail = e->tail;
+    bool mod = false;   // modulated or latched sliders: only the kernels with control ports evaluate them
+    for (int k = 0; k < st.count; ++k)
+        mod = mod || e->nodes[st.first + k].latch_valid || c.signal(st.first + k, 0) || c.signal(st.first + k, 1) || c.signal(st.first + k, 2);
+    if (mod) {
+        // a run-time specialised kernel with control ports when one can be had (compiled on first use), else the
+        // control-port interpreter: two channels per lane above 131072 channels -- or, while the specialised kernel is on
+        // its way, the channels per lane of THAT kernel (the same rows of bus partials)
+        if (!st.var_mod_tried) request_mod_kernel(e, st);
+        // (fixed when the job was submitted and kept when it comes back empty-handed: the bus' rows must not change in mid-stream)
+        const bool two = st.mod_two >= 0 ? st.mod_two == 1 : N > 131072u;
+        *tail = e->tail_mod;
+        return st.var_mod ? st.var_mod : ((e->dyn_mod2 && two && N % 2u == 0) ? e->dyn_mod2 : e->dyn_mod);
+    }
+    return st.var;
+}
+
+// ST_FUSED: the chain (or graph) kernel over all channels -- or the call's channel window -- and, where N is not whole waves,
+// the guarded launch for the channels left over.  bus: this stage ends the chain and leaves the mix bus' partial sums.
+static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float *src, const Layout &lay, bool bus) {
+    const Stage &st = e->stages[si];
+    const uint32_t N = e->desc.channels, nframes = c.n_frames;
+    hipStream_t stream = c.stream;
+    GraphArgs ga;                   // a graph kernel reads the slots beyond ChainArgs from it
+    memset(&ga, 0, sizeof ga);
+    if (e->graph_mode)
+        if (const int rc = graph_io_args(e, c, ga)) return rc;
+    ChainArgs &a = ga.c;
+    a.in = src;
+    a.side = c.side;
+    a.out = c.out;
+    a.N = N;
+    a.nframes = nframes;
+    a.w_shift = lay.w_shift;
+    a.w_mask = lay.w_mask;
+    a.ld = lay.ld;
+    a.io_tile_stride = lay.tile_stride;
+    a.hop_div = e->hop_div;
+    a.hop_rc = 1.0 / (double)e->hop_div;
+    a.third_rc = 1.0 / 3.0;
+    a.fast_div = st.fast_div ? 1 : 0;
+    // DSPFX_XCD_REMAP=0 / 1 switches the XCD-contiguous block mapping off / on (A/B runs; EnvSwitches)
+    const bool xcd_env = e->env.xcd_remap >= 0;
+    a.xcd_remap = xcd_env ? e->env.xcd_remap : 1;
+    a.n_slots = st.count;
+    a.skip_store = (st.count == 0 && src == c.out) ? 1 : 0;   // an empty stage in place exists only for the mix bus
+    // hop flag of the side input and of control links (both are ordinary links between nodes);
+    // an unconnected side port reads zeros, for which the hop is a no-op
+    a.side_hop = 0;
+    if (e->desc.link_flags & DSPFX_LINK_INTERNAL) a.side_hop = (e->desc.link_flags & DSPFX_LINK_SIDE_RAW) ? 2 : 3;
+    int rows = 0;
+    for (int k = 0; k < st.count; ++k) {
+        const Node &nk = e->nodes[st.first + k];
+        if (nk.d.kind == DSPFX_REVERB && (!nk.d_groups || nk.groups.size() < ring_groups_for(nk.D) || !nk.D))
+            return fail(e, DSPFX_ERR_STATE, "REVERB node %d has no delay ring (an allocation failed earlier)", st.first + k);
+        fill_slot(e, c, st.first + k, k < MAX_SLOTS ? a.slot[k] : ga.more[k - MAX_SLOTS]);
+        rows += state_rows(nk);
+    }
+    if (st.async || st.async_mod) adopt_async_jit(e, st);      // kernels the background compiler has finished: from this block on
+    const Variant *tail = nullptr, *v = stage_kernel(e, c, st, &tail);
+    // few channels, a whole 128-frame block, no control ports in play: four time slices per channel group
+    if (st.var_ts && v == st.var && nframes == 4u * (uint32_t)st.var_ts->ts) {
+        v = st.var_ts;
+        // Its workgroups all issue their whole slices together; neighbouring channel groups on DIFFERENT XCDs (the
+        // dispatcher's round robin) serve the HBM better than an eighth of the channels per XCD: config 2 25.6 -> 23.3 us
+        // tiled, 24.2 -> 23.7 frame-major (profiles/r03_small_n.txt).  The large kernels keep the contiguous mapping.
+        if (!xcd_env) a.xcd_remap = 0;
+    }
+    const uint32_t per_wave = 64u * v->cpl;
+    // A few-channel engine (the time-sliced kernel is its main launch) whose N is not whole waves: two launches in a
+    // row would both be latency-bound (11 + 11 us), so the guarded time-sliced kernel takes ALL channels in one
+    // (N = 4099, 3-node chain: 61 us with the interpreter's one-wave launch behind the main one, 28 with the guarded
+    // time-sliced launch behind it, ~12 alone).  Engines in channel windows keep the two launches.
+    // Up to 32768 channels: one resident round of one-channel-per-lane workgroups, the same rows of bus partials.
+    const bool whole_guard = v->ts && v->cpl == 1 && N < 32768u && st.var_ts_tail && tail == e->tail && N % per_wave && !c.window_n &&
+                             nframes == 4u * (uint32_t)st.var_ts_tail->ts;
+    const uint32_t n_main = whole_guard ? 0u : N - N % per_wave;
+    const uint32_t waves_main = n_main / per_wave;
+    const unsigned grid_main = v->ts ? waves_main : (waves_main * 64 + WG - 1) / WG;   // time-sliced: one workgroup per channel group
+    // the bus' first stage leaves one row of partial sums per WORKGROUP (chain_kernels.hip.h, mixbus_flush); the
+    // guarded tail launch runs one-wave workgroups.  Engines up to TS_MAX_CHANNELS -- the ones a time-sliced kernel
+    // may serve -- leave one row per WAVE instead: one row per 64 x cpl channels in the interpreter, the specialised
+    // standard kernel and the time-sliced kernels alike.  An engine starts on the interpreter and adopts the kernels
+    // the background thread compiled at a block boundary nobody can predict (plan.hip): with the same rows before and
+    // after -- and, above this size, the interpreter instantiation of the coming kernel's channels per lane -- the
+    // bus' f32 summation order does not change at that switch (it used to).
+    const bool rows_per_wave = !v->ts && N <= TS_MAX_CHANNELS;
+    a.mix_per_wave = rows_per_wave ? 1 : 0;
+    const unsigned rows_main = (v->ts || rows_per_wave) ? waves_main : grid_main;
+    a.mix_stride = rows_main + (N - n_main + 63) / 64;
+    FirMixPipe mp;
+    if (bus)
+        if (const int rc = bus_begin(e, c, a.mix_stride, &a.mixpart, &mp)) return rc;
+    // Same-block bus: the slice and final stages ride in the tail of this very launch (mix_tail) instead of two more
+    // kernels behind it.  DSPFX_MIX_TAIL=0: the stand-alone kernels (A/B runs, tests: bit-identical).
+    // (even block lengths: the tail reads two frames per lane with one 8-byte load)
+    const bool tail_bus = bus && c.bus == BUS_NOW && e->mt_tickets && nframes % 2u == 0 && e->env.mix_tail != 0;
+    if (tail_bus) {
+        a.mt_tickets = e->mt_tickets;
+        a.mt_part2 = e->mixpart_b;
+        a.mt_mix = c.mix;
+        a.mt_div = c.div;
+    }
+    if (bus && c.bus == BUS_PIPELINED) {   // earlier blocks' reductions ride in this launch
+        if (grid_main > MIX_SLICES) {
+            a.mp_stage = mp.stage;
+            a.mp_rows_a = mp.rows_a;
+            a.mp_prev_a = mp.prev_a;
+            a.mp_cur_b = mp.cur_b;
+            a.mp_prev_b = mp.prev_b;
+            a.mp_mix = mp.mix;
+            a.mp_div = mp.div;
+        } else {                    // too few workgroups to host the prologue: same stages as stand-alone kernels
+            if (mp.stage & 2) {
+                launch_mix_reduce_final(mp.prev_b, mp.mix, nframes, stream);
+                if (mp.div != 0.0f) launch_mix_finish(mp.mix, nframes, mp.div, stream);
+            }
+            if (mp.stage & 1) launch_mix_reduce_slices(mp.prev_a, mp.cur_b, nframes, mp.rows_a, stream);
+        }
+    }
+    // the main launch: all whole waves, or those of the call's channel window (multiples of 1024 channels; the last one runs to N)
+    const uint32_t w0 = c.window_n ? c.window_c0 : 0u, w1 = c.window_n ? std::min(n_main, c.window_c0 + c.window_n) : n_main;
+    if (w1 > w0) {
+        a.c_base = w0;
+        a.n_launch = w1 - w0;
+        a.wave_base = (v->ts || rows_per_wave) ? w0 / per_wave : w0 / (per_wave * (WG / 64));   // rows of the windows before this one
+        ProfScope ps(e, si, stream);
+        if (launch_variant(v, a, v->ts ? (w1 - w0) / per_wave : ((w1 - w0) / v->cpl + WG - 1) / WG, WG, (unsigned)(rows * WG * v->cpl * sizeof(float)), stream)) {
+            if (tail_bus) (void)hipMemsetAsync(e->mt_tickets, 0, (MIX_SLICES + 1) * sizeof(unsigned), stream);
+            return fail(e, DSPFX_ERR_HIP, "kernel launch failed");
+        }
+    }
+    a.mp_stage = 0;   // the guarded tail launch never hosts the prologue
+    if ((N % per_wave || whole_guard) && (!c.window_n || c.window_c0 + c.window_n >= N)) {   // ragged tail: guarded one-wave blocks, lane per channel
+        const uint32_t n_tail = N - n_main;
+        a.c_base = n_main;
+        a.n_launch = n_tail;
+        a.wave_base = rows_main;
+        if (st.var_ts_tail && tail == e->tail && nframes == 4u * (uint32_t)st.var_ts_tail->ts) {
+            a.xcd_remap = 0;            // whole 128-frame blocks: four slices per 64 channels (pick_ts_tail_variant)
+            if (whole_guard) {          // the stage's only launch: it is the one dspfx_profile_read reports
+                ProfScope ps(e, si, stream);
+                (void)launch_variant(st.var_ts_tail, a, (n_tail + 63) / 64, WG, 0, stream);
+            } else {
+                (void)launch_variant(st.var_ts_tail, a, (n_tail + 63) / 64, WG, 0, stream);
+            }
+        } else {
+            (void)launch_variant(tail, a, (n_tail + 63) / 64, 64, (unsigned)(rows * WG * sizeof(float)), stream);
+        }
+    }
+    const hipError_t lerr = hipGetLastError();
+    if (lerr != hipSuccess) {
+        // one of the block's launches did not happen: the rows it would have ticketed never arrive, and the
+        // counters the other launch bumped would stay non-zero for ever -- every later bus silently stale
+        if (tail_bus) (void)hipMemsetAsync(e->mt_tickets, 0, (MIX_SLICES + 1) * sizeof(unsigned), stream);
+        return fail(e, DSPFX_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
+    }
+    return bus && !tail_bus ? bus_end(e, c, a.mix_stride) : DSPFX_OK;
+}
+
+static int run_fuzz(dspfx_engine *e, const BlockCall &c, size_t si, const float *src, const Layout &lay) {
+    const Stage &st = e->stages[si];
+    const Node &n = e->nodes[st.first];
+    FuzzArgs f{src, c.out, e->desc.channels, c.n_frames, n.d.params[0], e->hop_div, node_hop(e, st.first),
+               (e->desc.link_flags & DSPFX_LINK_INTERNAL) ? 1 : 0, c.signal(st.first, 0), n.latch[0], n.latch_valid & 1, 0, lay};
+    ProfScope ps(e, si, c.stream);
+    launch_fuzz(f, c.stream);
+    HIPCHK(e, hipGetLastError());
+    return DSPFX_OK;
+}
+
+// ST_FIR.  *bus_done: the node ended the chain and left the mix bus' partial sums itself.
+static int run_fir(dspfx_engine *e, const BlockCall &c, size_t si, const float *src, const Layout &lay, bool *bus_done) {
+    const Stage &st = e->stages[si];
+    Node &n = e->nodes[st.first];
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (e->profiling) {
+        ea = take_event(e);
+        eb = take_event(e);
+        if (e->prof.size() <= si) e->prof.resize(si + 1);
+        e->prof[si].emplace_back(ea, eb);
+    }
+    // The FIR node ends the chain and the Output node's mix bus is wanted: the sweep's epilogue leaves the bus'
+    // first-stage partials (one row per 32-channel tile) and the empty chain kernel that would otherwise read the
+    // whole FIR output again just to sum it is skipped.  Slice / final stages as after a chain kernel; in the
+    // pipelined form the sweep's first workgroups host them like a chain kernel's do (or fir_process launches them).
+    const bool ends_chain = si + 2 == e->stages.size() && e->stages[si + 1].type == ST_FUSED && e->stages[si + 1].count == 0 && !c.window_n;
+    const bool want_bus = ends_chain && c.wants_bus();
+    const uint32_t frows = (e->desc.channels + 31) / 32;
+    float *fpart = nullptr;
+    FirMixPipe fmp;
+    if (want_bus)
+        if (const int rc = bus_begin(e, c, frows, &fpart, &fmp)) return rc;
+    const int rc = fir_process(n.fir, src, c.out, c.n_frames, node_hop(e, st.first), e->hop_div, lay, c.stream, ea, eb, fpart, &fmp);
+    if (rc != 0) return fail(e, rc, "FIR: %s", fir_last_error());
+    *bus_done = want_bus;
+    return want_bus ? bus_end(e, c, frows) : DSPFX_OK;
+}
+
+// One sub-block (c.n_frames <= every delay length) through all stages.
+int run_subblock(dspfx_engine *e, const BlockCall &c) {
+    const Layout lay = block_layout(e, c.tile_frames);
+    const float *src = c.in;
+    bool bus_done = false;
     for (size_t si = 0; si < e->stages.size(); ++si) {
         const Stage &st = e->stages[si];
-        const bool last = si + 1 == e->stages.size();
-        if (st.type == ST_FUSED) {
-            if (st.count == 0 && (bus_done || !(last && (mix || e->partials_override || e->mp_building))) && src == out) continue;   // nothing to do
-            GraphArgs ga;                   // a graph kernel reads the slots beyond ChainArgs from it
-            memset(&ga, 0, sizeof ga);
-            if (e->graph_mode) {
-                const int n_nodes = (int)e->nodes.size();
-                for (const dspfx_graph_link &l : e->wiring) {
-                    const int blk = graph_input_block(l.src);
-                    if (blk == 1 && !side) return fail(e, DSPFX_ERR_INVALID, "this graph reads a second block (DSPFX_GRAPH_INPUT2): side must not be null");
-                    if (blk >= 2 && !e->io_in[blk]) return fail(e, DSPFX_ERR_INVALID, "this graph reads input block %d: pass it with dspfx_process_io", blk);
-                    if (l.dst > n_nodes && !e->io_out[l.dst - n_nodes]) return fail(e, DSPFX_ERR_INVALID, "this graph writes output block %d: pass it with dspfx_process_io", l.dst - n_nodes);   // (blocks are contiguous: validate_graph)
-                }
-                for (int k = 2; k < GRAPH_IO; ++k) ga.xin[k - 2] = e->io_in[k] ? e->io_in[k] + e->io_off : nullptr;
-                for (int m = 1; m < GRAPH_IO; ++m) ga.xout[m - 1] = e->io_out[m] ? e->io_out[m] + e->io_off : nullptr;
-            }
-            ChainArgs &a = ga.c;
-            a.in = src;
-            a.side = side;
-            a.out = out;
-            a.N = N;
-            a.nframes = nframes;
-            a.w_shift = lay.w_shift;
-            a.w_mask = lay.w_mask;
-            a.ld = lay.ld;
-            a.io_tile_stride = lay.tile_stride;
-            a.hop_div = e->hop_div;
-            a.hop_rc = 1.0 / (double)e->hop_div;
-            a.third_rc = 1.0 / 3.0;
-            a.fast_div = st.fast_div ? 1 : 0;
-            // DSPFX_XCD_REMAP=0 / 1 switches the XCD-contiguous block mapping off / on (A/B runs; EnvSwitches)
-            const bool xcd_env = e->env.xcd_remap >= 0;
-            a.xcd_remap = xcd_env ? e->env.xcd_remap : 1;
-            a.n_slots = st.count;
-            a.skip_store = (st.count == 0 && src == out) ? 1 : 0;   // an empty stage in place exists only for the mix bus
-            // hop flag of the side input and of control links (both are ordinary links between nodes);
-            // an unconnected side port reads zeros, for which the hop is a no-op
-            a.side_hop = 0;
-            if (e->desc.link_flags & DSPFX_LINK_INTERNAL) a.side_hop = (e->desc.link_flags & DSPFX_LINK_SIDE_RAW) ? 2 : 3;
-            int rows = 0;
-            for (int k = 0; k < st.count; ++k) {
-                const Node &nk = e->nodes[st.first + k];
-                if (nk.d.kind == DSPFX_REVERB && (!nk.d_groups || nk.groups.size() < ring_groups_for(nk.D) || !nk.D))
-                    return fail(e, DSPFX_ERR_STATE, "REVERB node %d has no delay ring (an allocation failed earlier)", st.first + k);
-                fill_slot(e, st.first + k, k < MAX_SLOTS ? a.slot[k] : ga.more[k - MAX_SLOTS], nframes);
-                rows += state_rows(nk);
-            }
-            if (st.async || st.async_mod) adopt_async_jit(e, st);      // kernels the background compiler has finished: from this block on
-            const Variant *v = st.var, *tail = e->tail;
-            for (int k = 0; k < st.count; ++k) {   // modulated or latched sliders: only the MOD interpreter evaluates them
-                const Node &nd = e->nodes[st.first + k];
-                if (nd.latch_valid || nd.ctl_now[0] || nd.ctl_now[1] || nd.ctl_now[2]) {
-                    // a run-time specialised kernel with control ports when one can be had (compiled on first use),
-                    // else the control-port interpreter: two channels per lane above 131072 channels
-                    // else the control-port interpreter: two channels per lane above 131072 channels -- or, while the
-                    // specialised kernel is on its way, the channels per lane of THAT kernel (the same rows of bus partials)
-                    if (!st.var_mod_tried) request_mod_kernel(e, st);
-                    // (fixed when the job was submitted and kept when it comes back empty-handed: the bus' rows must not change in mid-stream)
-                    const bool two = st.mod_two >= 0 ? st.mod_two == 1 : N > 131072u;
-                    v = st.var_mod ? st.var_mod : ((e->dyn_mod2 && two && N % 2u == 0) ? e->dyn_mod2 : e->dyn_mod);
-                    tail = e->tail_mod;
-                }
-            }
-            // few channels, a whole 128-frame block, no control ports in play: four time slices per channel group
-            if (st.var_ts && v == st.var && nframes == 4u * (uint32_t)st.var_ts->ts) {
-                v = st.var_ts;
-                // Its workgroups all issue their whole slices together; neighbouring channel groups on DIFFERENT XCDs (the
-                // dispatcher's round robin) serve the HBM better than an eighth of the channels per XCD: config 2 25.6 -> 23.3 us
-                // tiled, 24.2 -> 23.7 frame-major (profiles/r03_small_n.txt).  The large kernels keep the contiguous mapping.
-                if (!xcd_env) a.xcd_remap = 0;
-            }
-            const uint32_t per_wave = 64u * v->cpl;
-            // A few-channel engine (the time-sliced kernel is its main launch) whose N is not whole waves: two launches in a
-            // row would both be latency-bound (11 + 11 us), so the guarded time-sliced kernel takes ALL channels in one
-            // (N = 4099, 3-node chain: 61 us with the interpreter's one-wave launch behind the main one, 28 with the guarded
-            // time-sliced launch behind it, ~12 alone).  Engines in channel windows keep the two launches.
-            // Up to 32768 channels: one resident round of one-channel-per-lane workgroups, the same rows of bus partials.
-            const bool whole_guard = v->ts && v->cpl == 1 && N < 32768u && st.var_ts_tail && tail == e->tail && N % per_wave && !e->win_n &&
-                                     nframes == 4u * (uint32_t)st.var_ts_tail->ts;
-            const uint32_t n_main = whole_guard ? 0u : N - N % per_wave;
-            const uint32_t waves_main = n_main / per_wave;
-            const bool deferred = last && e->partials_override != nullptr;
-            a.mixpart = deferred ? e->partials_override : ((last && mix) ? e->mixpart : nullptr);
-            const unsigned grid_main = v->ts ? waves_main : (waves_main * 64 + WG - 1) / WG;   // time-sliced: one workgroup per channel group
-            // the bus' first stage leaves one row of partial sums per WORKGROUP (chain_kernels.hip.h, mixbus_flush); the
-            // guarded tail launch runs one-wave workgroups.  Engines up to TS_MAX_CHANNELS -- the ones a time-sliced kernel
-            // may serve -- leave one row per WAVE instead: one row per 64 x cpl channels in the interpreter, the specialised
-            // standard kernel and the time-sliced kernels alike.  An engine starts on the interpreter and adopts the kernels
-            // the background thread compiled at a block boundary nobody can predict (plan.hip): with the same rows before and
-            // after -- and, above this size, the interpreter instantiation of the coming kernel's channels per lane -- the
-            // bus' f32 summation order does not change at that switch (it used to).
-            const bool rows_per_wave = !v->ts && N <= TS_MAX_CHANNELS;
-            a.mix_per_wave = rows_per_wave ? 1 : 0;
-            const unsigned rows_main = (v->ts || rows_per_wave) ? waves_main : grid_main;
-            a.mix_stride = rows_main + (N - n_main + 63) / 64;
-            if (a.mixpart && a.mix_stride > e->mixpart_cols) return fail(e, DSPFX_ERR_STATE, "mix partial buffer too small");
-            // Same-block bus: the slice and final stages ride in the tail of this very launch (mix_tail) instead of two more
-            // kernels behind it.  DSPFX_MIX_TAIL=0: the stand-alone kernels (A/B runs, tests: bit-identical).
-            // (even block lengths: the tail reads two frames per lane with one 8-byte load)
-            const bool tail_bus = last && mix && !deferred && !e->mp_building && e->mt_tickets && nframes % 2u == 0 && e->env.mix_tail != 0;
-            if (tail_bus) {
-                a.mt_tickets = e->mt_tickets;
-                a.mt_part2 = e->mixpart_b;
-                a.mt_mix = mix;
-                a.mt_div = e->bus_div_now;
-            }
-            if (e->mp_building && last) {   // pipelined mix bus: earlier blocks' reductions ride in this launch
-                const int cur = (int)(e->mp_count & 1), prev = cur ^ 1;
-                a.mixpart = e->mixpart2[cur];
-                if (a.mix_stride > e->mixpart_cols) return fail(e, DSPFX_ERR_STATE, "mix partial buffer too small");
-                e->mp_rows[cur] = a.mix_stride;
-                const int stage = (e->mp_count >= 1 ? 1 : 0) | (e->mp_count >= 2 ? 2 : 0);
-                float *b_cur = cur ? e->mixpart_b2 : e->mixpart_b, *b_prev = cur ? e->mixpart_b : e->mixpart_b2;
-                if (grid_main > MIX_SLICES) {
-                    a.mp_stage = stage;
-                    a.mp_rows_a = e->mp_rows[prev];
-                    a.mp_prev_a = e->mixpart2[prev];
-                    a.mp_cur_b = b_cur;
-                    a.mp_prev_b = b_prev;
-                    a.mp_mix = e->mp_mix_now;
-                    a.mp_div = e->mp_div_now;
-                } else {                    // too few workgroups to host the prologue: same stages as stand-alone kernels
-                    if (stage & 2) {
-                        launch_mix_reduce_final(b_prev, e->mp_mix_now, nframes, stream);
-                        if (e->mp_div_now != 0.0f) launch_mix_finish(e->mp_mix_now, nframes, e->mp_div_now, stream);
-                    }
-                    if (stage & 1) launch_mix_reduce_slices(e->mixpart2[prev], b_cur, nframes, e->mp_rows[prev], stream);
-                }
-            }
-            if (e->win_n) {   // a channel window (multiples of 1024 channels; the last one runs to N)
-                const uint32_t w0 = e->win_c0, w1 = std::min(n_main, e->win_c0 + e->win_n);
-                if (w1 > w0) {
-                    a.c_base = w0;
-                    a.n_launch = w1 - w0;
-                    a.wave_base = (v->ts || rows_per_wave) ? w0 / per_wave : w0 / (per_wave * (WG / 64));   // rows of the windows before this one
-                    ProfScope ps(e, si, stream);
-                    if (launch_variant(v, a, v->ts ? (w1 - w0) / per_wave : ((w1 - w0) / v->cpl + WG - 1) / WG, WG, (unsigned)(rows * WG * v->cpl * sizeof(float)), stream)) {
-                        if (tail_bus) (void)hipMemsetAsync(e->mt_tickets, 0, (MIX_SLICES + 1) * sizeof(unsigned), stream);
-                        return fail(e, DSPFX_ERR_HIP, "kernel launch failed");
-                    }
-                }
-            } else if (n_main) {
-                a.c_base = 0;
-                a.n_launch = n_main;
-                a.wave_base = 0;
-                const unsigned grid = grid_main;
-                ProfScope ps(e, si, stream);
-                if (launch_variant(v, a, grid, WG, (unsigned)(rows * WG * v->cpl * sizeof(float)), stream))
-                    return fail(e, DSPFX_ERR_HIP, "kernel launch failed");
-            }
-            a.mp_stage = 0;   // the guarded tail launch never hosts the prologue
-            if ((N % per_wave || whole_guard) && (!e->win_n || e->win_c0 + e->win_n >= N)) {   // ragged tail: guarded one-wave blocks, lane per channel
-                const uint32_t n_tail = N - n_main;
-                a.c_base = n_main;
-                a.n_launch = n_tail;
-                a.wave_base = rows_main;
-                if (st.var_ts_tail && tail == e->tail && nframes == 4u * (uint32_t)st.var_ts_tail->ts) {
-                    a.xcd_remap = 0;            // whole 128-frame blocks: four slices per 64 channels (pick_ts_tail_variant)
-                    if (whole_guard) {          // the stage's only launch: it is the one dspfx_profile_read reports
-                        ProfScope ps(e, si, stream);
-                        (void)launch_variant(st.var_ts_tail, a, (n_tail + 63) / 64, WG, 0, stream);
-                    } else {
-                        (void)launch_variant(st.var_ts_tail, a, (n_tail + 63) / 64, WG, 0, stream);
-                    }
-                } else {
-                    (void)launch_variant(tail, a, (n_tail + 63) / 64, 64, (unsigned)(rows * WG * sizeof(float)), stream);
-                }
-            }
-            {
-                const hipError_t lerr = hipGetLastError();
-                if (lerr != hipSuccess) {
-                    // one of the block's launches did not happen: the rows it would have ticketed never arrive, and the
-                    // counters the other launch bumped would stay non-zero for ever -- every later bus silently stale
-                    if (tail_bus) (void)hipMemsetAsync(e->mt_tickets, 0, (MIX_SLICES + 1) * sizeof(unsigned), stream);
-                    return fail(e, DSPFX_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
-                }
-            }
-            if (deferred) {
-                e->part_stride[e->flip] = a.mix_stride;
-                e->part_frames[e->flip] = nframes;
-            } else if (a.mixpart && !e->mp_building && !tail_bus) {
-                launch_mix_reduce(e->mixpart, e->mixpart_b, mix, nframes, a.mix_stride, stream);
-                if (e->bus_div_now != 0.0f) launch_mix_finish(mix, nframes, e->bus_div_now, stream);
-                HIPCHK(e, hipGetLastError());
-            }
-        } else if (st.type == ST_FUZZ) {
-            const Node &n = e->nodes[st.first];
-            FuzzArgs f{src, out, N, nframes, n.d.params[0], e->hop_div, node_hop(e, st.first),
-                       (e->desc.link_flags & DSPFX_LINK_INTERNAL) ? 1 : 0, n.ctl_now[0], n.latch[0], n.latch_valid & 1, 0, lay};
-            ProfScope ps(e, si, stream);
-            launch_fuzz(f, stream);
-            HIPCHK(e, hipGetLastError());
-        } else {   // ST_FIR
-            Node &n = e->nodes[st.first];
-            hipEvent_t ea = nullptr, eb = nullptr;
-            if (e->profiling) {
-                ea = take_event(e);
-                eb = take_event(e);
-                if (e->prof.size() <= si) e->prof.resize(si + 1);
-                e->prof[si].emplace_back(ea, eb);
-            }
-            // The FIR node ends the chain and the Output node's mix bus is wanted: the sweep's epilogue leaves the bus'
-            // first-stage partials (one row per 32-channel tile) and the empty chain kernel that would otherwise read the
-            // whole FIR output again just to sum it is skipped.  Slice / final stages as after a chain kernel; in the
-            // pipelined form the sweep's first workgroups host them like a chain kernel's do.
-            const bool ends_chain = si + 2 == e->stages.size() && e->stages[si + 1].type == ST_FUSED && e->stages[si + 1].count == 0 && !e->win_n;
-            const bool want_bus = ends_chain && (mix || e->partials_override || e->mp_building);
-            const uint32_t frows = (N + 31) / 32;
-            const bool deferred = want_bus && e->partials_override != nullptr;
-            float *fpart = nullptr;
-            FirMixPipe fmp;      // the pipelined bus' stages of earlier blocks: hosted by the sweep or launched by fir_process
-            if (want_bus) {
-                if (frows > e->mixpart_cols) return fail(e, DSPFX_ERR_STATE, "mix partial buffer too small");
-                fpart = deferred ? e->partials_override : e->mixpart;
-                if (e->mp_building) {
-                    const int cur = (int)(e->mp_count & 1), prev = cur ^ 1;
-                    fpart = e->mixpart2[cur];
-                    e->mp_rows[cur] = frows;
-                    const int stage = (e->mp_count >= 1 ? 1 : 0) | (e->mp_count >= 2 ? 2 : 0);
-                    float *b_cur = cur ? e->mixpart_b2 : e->mixpart_b, *b_prev = cur ? e->mixpart_b : e->mixpart_b2;
-                    fmp.stage = stage;
-                    fmp.rows_a = e->mp_rows[prev];
-                    fmp.prev_a = e->mixpart2[prev];
-                    fmp.cur_b = b_cur;
-                    fmp.prev_b = b_prev;
-                    fmp.mix = e->mp_mix_now;
-                    fmp.div = e->mp_div_now;
-                }
-            }
-            const int rc = fir_process(n.fir, src, out, nframes, node_hop(e, st.first), e->hop_div, lay, stream, ea, eb, fpart, &fmp);
-            if (rc != 0) return fail(e, rc, "FIR: %s", fir_last_error());
-            if (want_bus) {
-                if (deferred) {
-                    e->part_stride[e->flip] = frows;
-                    e->part_frames[e->flip] = nframes;
-                } else if (!e->mp_building) {
-                    launch_mix_reduce(e->mixpart, e->mixpart_b, mix, nframes, frows, stream);
-                    if (e->bus_div_now != 0.0f) launch_mix_finish(mix, nframes, e->bus_div_now, stream);
-                    HIPCHK(e, hipGetLastError());
-                }
-                bus_done = true;
-            }
-        }
-        src = out;
+        const bool fused = st.type == ST_FUSED, bus = fused && !bus_done && si + 1 == e->stages.size() && c.wants_bus();
+        if (fused && st.count == 0 && !bus && src == c.out) continue;   // nothing to do
+        const int rc = fused ? run_fused(e, c, si, src, lay, bus)
+                             : st.type == ST_FUZZ ? run_fuzz(e, c, si, src, lay) : run_fir(e, c, si, src, lay, &bus_done);
+        if (rc) return rc;
+        src = c.out;
     }
-    if (!e->win_last) return DSPFX_OK;   // more channel windows of this block follow
-    for (Node &n : e->nodes)   // a connected control port leaves per-channel latched values behind
-        for (int k = 0; k < 3; ++k)
-            if (n.ctl_now[k]) n.latch_valid |= 1 << k;
+    if (!c.window_last) return DSPFX_OK;   // more channel windows of this block follow
+    for (int i = 0; i < c.n_ctl; ++i)   // a connected control port leaves per-channel latched values behind
+        e->nodes[(size_t)c.ctl[i].node].latch_valid |= 1 << c.ctl[i].param;
     // advance the delay rings (FIFO: the block's rows now hold the newest samples)
     for (Node &n : e->nodes)
         if (n.d.kind == DSPFX_REVERB) {
-            n.pos = (uint32_t)(((uint64_t)n.pos + nframes) % n.D);
-            n.zero_left -= std::min(n.zero_left, nframes);   // rows written since the ring's last clear are real samples
+            n.pos = (uint32_t)(((uint64_t)n.pos + c.n_frames) % n.D);
+            n.zero_left -= std::min(n.zero_left, c.n_frames);   // rows written since the ring's last clear are real samples
         }
     return DSPFX_OK;
 }
@@ -863,7 +901,7 @@ extern "C" int dspfx_engine_create(const dspfx_engine_desc *desc, dspfx_engine *
     e->env = read_env_switches();
     e->desc = *desc;
     e->device = desc->device;
-    e->hop_div = dspfx_link_divisor(1);
+    e->hop_div = output_divisor(e, 1);
     std::vector<const Variant *> all;
     collect_variants(all);
     for (const Variant *v : all) {
@@ -1320,17 +1358,75 @@ extern "C" int dspfx_reset(dspfx_engine *e) {
 // of the standard kernel at 4096 / 16384 / 32768 channels of the 3-node chain: 46.8 / 51.8 / 58.3 us; two time-sliced
 // launches: 21.2 / 22.7 / 28.5 (5-node chain: 52.0 / 53.7 / 55.7 against 31.7 / 34.1 / 44.6; profiles/r03_small_n.txt).
 // B = 256 IS two reference blocks back to back, so nothing changes but the launches.
-static uint32_t ts_sub_block(const dspfx_engine *e) {
-    if (e->win_n || e->mp_building || e->partials_override) return 0;     // channel windows, the pipelined / deferred bus: one launch per call
+static uint32_t ts_sub_block(const dspfx_engine *e, const BlockCall &c) {
+    if (c.window_n || c.bus != BUS_NOW) return 0;     // channel windows, the pipelined / deferred bus: one launch per call
     uint32_t b = 0;
     for (const Stage &st : e->stages)
         if (st.type == ST_FUSED && st.count > 0) {
             if (!st.var_ts) return 0;
             b = 4u * (uint32_t)st.var_ts->ts;
         }
+    if (c.n_ctl) return 0;                         // control ports, connected or latched: the interpreter serves
     for (const Node &nd : e->nodes)
-        if (nd.latch_valid || nd.ctl_now[0] || nd.ctl_now[1] || nd.ctl_now[2]) return 0;     // control ports: the interpreter serves
+        if (nd.latch_valid) return 0;
     return b;
+}
+
+// a block's delay taps must not depend on the same launch's outputs: a block (or piece of one) of n frames is cut at the
+// shortest delay line -- on 128-frame boundaries where Fuzz (block-global) or a signal generator (its clock wraps per
+// 128-frame block) is in the chain
+static uint32_t sub_block_frames(const dspfx_engine *e, uint32_t n) {
+    uint32_t sub = std::min(n, e->min_delay);
+    if (e->has_fuzz || e->has_siggen) sub = std::max<uint32_t>(DSPFX_BUF_SIZE, sub / DSPFX_BUF_SIZE * DSPFX_BUF_SIZE);
+    return sub;
+}
+
+// The call's sub-block [f0, f0 + nf): every per-call pointer moved there.  Frame f0 of a block starts f0 rows in: a row is N
+// floats (frame-major) or W floats (tiled).
+static BlockCall sub_block(const dspfx_engine *e, const BlockCall &c, uint32_t f0, uint32_t nf) {
+    const size_t off = (size_t)f0 * (e->desc.tile_channels ? e->desc.tile_channels : e->desc.channels);
+    BlockCall s = c;
+    s.n_frames = nf;
+    s.in = c.in + off;
+    s.side = c.side ? c.side + off : nullptr;
+    s.out = c.out + off;
+    s.mix = c.mix ? c.mix + f0 : nullptr;
+    for (int k = 0; k < GRAPH_IO; ++k) {
+        if (c.xin[k]) s.xin[k] = c.xin[k] + off;
+        if (c.xout[k]) s.xout[k] = c.xout[k] + off;
+    }
+    s.ctl_off = c.ctl_off + off;
+    return s;
+}
+
+// What every process call does once its arguments are checked and its BlockCall is built: the block, sub-block by sub-block.
+// pieces (dspfx_process_ctl): the block is first cut into pieces at the shortest delay line and each piece handled as a
+// block of its own was (its own Fuzz check, its own 128-frame slicing for the time-sliced kernels); the tile stride stays
+// that of the caller's whole block.
+static int process_block(dspfx_engine *e, const BlockCall &c, bool pieces = false) {
+    const uint32_t piece = pieces ? sub_block_frames(e, c.n_frames) : c.n_frames;
+    for (uint32_t p0 = 0; p0 < c.n_frames; p0 += piece) {
+        const uint32_t pn = std::min(piece, c.n_frames - p0);
+        if (e->has_fuzz && pn % DSPFX_BUF_SIZE)
+            return fail(e, DSPFX_ERR_INVALID, "Fuzz is block-global over 128 frames: n_frames %u %% 128 != 0", pn);
+        uint32_t sub = sub_block_frames(e, pn);
+        if (const uint32_t tsb = ts_sub_block(e, c))
+            if (pn > tsb && pn % tsb == 0 && sub >= tsb && sub % tsb == 0) sub = tsb;
+        for (uint32_t f0 = p0; f0 < p0 + pn; f0 += sub) {
+            const BlockCall s = sub_block(e, c, f0, std::min(sub, p0 + pn - f0));
+            if (const int rc = run_subblock(e, s)) return rc;
+            e->frames_submitted += s.n_frames;
+        }
+    }
+    return DSPFX_OK;
+}
+
+// the checks on a block's arguments that every process call makes
+int dspfx_host::check_block(dspfx_engine *e, const void *in, const void *out, uint32_t n_frames) {
+    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
+    if (n_frames > e->desc.max_frames)
+        return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
+    return DSPFX_OK;
 }
 
 extern "C" int dspfx_process(dspfx_engine *e, const float *in, const float *side, float *out, float *mix,
@@ -1339,30 +1435,9 @@ extern "C" int dspfx_process(dspfx_engine *e, const float *in, const float *side
     hipStream_t s = (hipStream_t)stream;
     ApiScope api(e, true, s);            // queued slider stores take effect here, at the block boundary
     if (api.rc) return api.rc;
-    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
     if (n_frames == 0) return DSPFX_OK;
-    if (n_frames > e->desc.max_frames)
-        return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
-    if (e->has_fuzz && n_frames % DSPFX_BUF_SIZE)
-        return fail(e, DSPFX_ERR_INVALID, "Fuzz is block-global over 128 frames: n_frames %u %% 128 != 0", n_frames);
-    // a block's delay taps must not depend on the same launch's outputs: split at min delay
-    uint32_t sub = std::min(n_frames, e->min_delay);
-    if (e->has_fuzz || e->has_siggen) sub = std::max<uint32_t>(DSPFX_BUF_SIZE, sub / DSPFX_BUF_SIZE * DSPFX_BUF_SIZE);
-    if (const uint32_t tsb = ts_sub_block(e))
-        if (n_frames > tsb && n_frames % tsb == 0 && sub >= tsb && sub % tsb == 0) sub = tsb;
-    const size_t N = e->desc.channels;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += sub) {
-        const uint32_t nf = std::min(sub, n_frames - f0);
-        // frame f0 of a block starts f0 rows in: a row is N floats (frame-major) or W floats (tiled)
-        const size_t off = (size_t)f0 * (e->desc.tile_channels ? e->desc.tile_channels : N);
-        e->io_off = off;
-        const int rc = run_subblock(e, in + off, side ? side + off : nullptr, out + off, mix ? mix + f0 : nullptr,
-                                    nf, e->ctl_tile_frames ? e->ctl_tile_frames : n_frames, s);
-        e->io_off = 0;
-        if (rc) return rc;
-        e->frames_submitted += nf;
-    }
-    return DSPFX_OK;
+    return process_block(e, BlockCall(in, side, out, mix, n_frames, s));
 }
 
 int dspfx_host::check_pcm_io(dspfx_engine *e, const dspfx_pcm_io *io) {
@@ -1383,9 +1458,7 @@ extern "C" int dspfx_process_pcm(dspfx_engine *e, const dspfx_pcm_io *io, const 
     ApiScope api(e, true, s);            // the scratch is ordered behind whatever used it last, on any stream
     if (api.rc) return api.rc;
     if (const int rc = check_pcm_io(e, io)) return rc;
-    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
-    if (n_frames > e->desc.max_frames)
-        return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
     if (n_frames == 0) return DSPFX_OK;
     const uint32_t N = e->desc.channels;
     const size_t cap = (size_t)e->desc.max_frames * N * sizeof(float);
@@ -1406,8 +1479,7 @@ extern "C" int dspfx_process_pcm(dspfx_engine *e, const dspfx_pcm_io *io, const 
         if (!e->h_out) HIPCHK(e, hipMalloc((void **)&e->h_out, cap));
         fout = e->h_out;
     }
-    const int rc = dspfx_process(e, fin, fside, fout, mix, n_frames, stream);
-    if (rc) return rc;
+    if (const int rc = process_block(e, BlockCall(fin, fside, fout, mix, n_frames, s))) return rc;
     if (!plain_out) HIPCHK(e, launch_pcm_narrow(io->out_format, io->out_channels, e->h_out, out, n_frames, N, N, 0, s));
     return DSPFX_OK;
 }
@@ -1420,18 +1492,11 @@ extern "C" int dspfx_process_bus(dspfx_engine *e, const float *in, const float *
     ApiScope api(e, true, (hipStream_t)stream);
     if (api.rc) return api.rc;
     if (!mix) return fail(e, DSPFX_ERR_INVALID, "mix must not be null");
-    float div = 0.0f;
-    if (n_connected) {
-        if (e->div_n != n_connected || e->div_v == 0.0f) {
-            e->div_v = dspfx_link_divisor(n_connected);
-            e->div_n = n_connected;
-        }
-        div = e->div_v;
-    }
-    e->bus_div_now = div;
-    const int rc = dspfx_process(e, in, side, out, mix, n_frames, stream);
-    e->bus_div_now = 0.0f;
-    return rc;
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
+    if (n_frames == 0) return DSPFX_OK;
+    BlockCall c(in, side, out, mix, n_frames, (hipStream_t)stream);
+    c.div = n_connected ? output_divisor(e, n_connected) : 0.0f;
+    return process_block(e, c);
 }
 
 extern "C" int dspfx_process_io(dspfx_engine *e, const float *const *ins, int n_ins, float *const *outs, int n_outs, float *mix,
@@ -1442,18 +1507,14 @@ extern "C" int dspfx_process_io(dspfx_engine *e, const float *const *ins, int n_
     if (n_ins < 0 || n_ins > DSPFX_GRAPH_MAX_IO || n_outs < 1 || n_outs > DSPFX_GRAPH_MAX_IO || (n_ins > 0 && !ins) || !outs || !outs[0])
         return fail(e, DSPFX_ERR_INVALID, "process_io: 0..%d input blocks, 1..%d output blocks (the first one non-null)", DSPFX_GRAPH_MAX_IO, DSPFX_GRAPH_MAX_IO);
     if (!e->graph_mode && (n_ins > 2 || n_outs > 1)) return fail(e, DSPFX_ERR_INVALID, "only a graph engine (dspfx_graph_set) takes extra blocks");
-    for (int k = 0; k < GRAPH_IO; ++k) {
-        e->io_in[k] = k < n_ins ? ins[k] : nullptr;
-        e->io_out[k] = k < n_outs ? outs[k] : nullptr;
-    }
     // a graph that never reads `in` still gets a valid pointer (the kernel does not touch it)
     const float *in0 = (n_ins > 0 && ins[0]) ? ins[0] : outs[0];
-    const int rc = dspfx_process(e, in0, n_ins > 1 ? ins[1] : nullptr, outs[0], mix, n_frames, stream);
-    for (int k = 0; k < GRAPH_IO; ++k) {
-        e->io_in[k] = nullptr;
-        e->io_out[k] = nullptr;
-    }
-    return rc;
+    if (const int rc = check_block(e, in0, outs[0], n_frames)) return rc;
+    if (n_frames == 0) return DSPFX_OK;
+    BlockCall c(in0, n_ins > 1 ? ins[1] : nullptr, outs[0], mix, n_frames, (hipStream_t)stream);
+    for (int k = 2; k < GRAPH_IO && k < n_ins; ++k) c.xin[k] = ins[k];
+    for (int k = 1; k < GRAPH_IO && k < n_outs; ++k) c.xout[k] = outs[k];
+    return process_block(e, c);
 }
 
 extern "C" int dspfx_process_ctl(dspfx_engine *e, const float *in, const float *side, float *out, float *mix,
@@ -1490,25 +1551,13 @@ extern "C" int dspfx_process_ctl(dspfx_engine *e, const float *in, const float *
             return fail(e, DSPFX_ERR_INVALID, "node %d has no `as_input` slider %d", c.node, c.param);
         if (!n.latch[c.param]) HIPCHK(e, hipMalloc((void **)&n.latch[c.param], (size_t)e->desc.channels * sizeof(float)));
     }
-    // split like dspfx_process does, offsetting the control signals with the samples
-    const size_t N = e->desc.channels;
-    const size_t rowlen = e->desc.tile_channels ? e->desc.tile_channels : N;
     if (n_frames > e->desc.max_frames) return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
-    uint32_t sub = std::min(n_frames, e->min_delay);
-    if (e->has_fuzz || e->has_siggen) sub = std::max<uint32_t>(DSPFX_BUF_SIZE, sub / DSPFX_BUF_SIZE * DSPFX_BUF_SIZE);
-    int rc = DSPFX_OK;
-    for (uint32_t f0 = 0; f0 < n_frames && rc == DSPFX_OK; f0 += sub) {
-        const uint32_t nf = std::min(sub, n_frames - f0);
-        const size_t off = (size_t)f0 * rowlen;
-        for (int i = 0; i < n_ctl; ++i) e->nodes[(size_t)ctl[i].node].ctl_now[ctl[i].param] = ctl[i].signal + off;
-        // one sub-block == one dspfx_process call of nf frames on offset pointers (tile stride stays n_frames)
-        e->ctl_tile_frames = n_frames;
-        rc = dspfx_process(e, in + off, side ? side + off : nullptr, out + off, mix ? mix + f0 : nullptr, nf, stream);
-        e->ctl_tile_frames = 0;
-    }
-    for (Node &n : e->nodes)
-        for (int k = 0; k < 3; ++k) n.ctl_now[k] = nullptr;
-    return rc;
+    if (n_frames == 0) return DSPFX_OK;
+    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
+    BlockCall c(in, side, out, mix, n_frames, (hipStream_t)stream);
+    c.ctl = ctl;
+    c.n_ctl = n_ctl;
+    return process_block(e, c, true);
 }
 
 extern "C" int dspfx_process_partials(dspfx_engine *e, const float *in, const float *side, float *out,
@@ -1522,20 +1571,17 @@ extern "C" int dspfx_process_partials(dspfx_engine *e, const float *in, const fl
     if (n_frames > e->min_delay)
         return fail(e, DSPFX_ERR_UNSUPPORTED, "deferred mix needs n_frames <= shortest delay line (%u)", e->min_delay);
     const int b = e->flip;
-    if (!e->mixpart2[b]) {
-        HIPCHK(e, hipMalloc((void **)&e->mixpart2[b], e->mixpart_cols * e->desc.max_frames * sizeof(float)));
-        HIPCHK(e, hipEventCreateWithFlags(&e->ev_chain[b], hipEventDisableTiming));
-        HIPCHK(e, hipEventCreateWithFlags(&e->ev_red[b], hipEventDisableTiming));
-    }
+    if (const int rc = ensure_mixpart2(e, b)) return rc;
     if (e->red_pending[b]) {   // the collect that read this buffer two blocks ago must be done
         if (hipEventQuery(e->ev_red[b]) != hipSuccess)      // normally long finished: no packet needed
             HIPCHK(e, hipStreamWaitEvent(s, e->ev_red[b], 0));
         e->red_pending[b] = false;
     }
-    e->partials_override = e->mixpart2[b];
-    const int rc = dspfx_process(e, in, side, out, nullptr, n_frames, stream);
-    e->partials_override = nullptr;
-    if (rc) return rc;
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
+    BlockCall c(in, side, out, nullptr, n_frames, s);
+    c.bus = BUS_DEFERRED;
+    c.partials = e->mixpart2[b];
+    if (const int rc = process_block(e, c)) return rc;
     HIPCHK(e, hipEventRecord(e->ev_chain[b], s));
     e->collect_due = true;
     return DSPFX_OK;
@@ -1574,26 +1620,14 @@ extern "C" int dspfx_process_mixpipe(dspfx_engine *e, const float *in, const flo
     if (e->mp_count >= 2 && !mix) return fail(e, DSPFX_ERR_INVALID, "mix must not be null from the third block on");
     HIPCHK(e, hipSetDevice(e->device));
     for (int b = 0; b < 2; ++b)
-        if (!e->mixpart2[b]) {
-            HIPCHK(e, hipMalloc((void **)&e->mixpart2[b], e->mixpart_cols * e->desc.max_frames * sizeof(float)));
-            HIPCHK(e, hipEventCreateWithFlags(&e->ev_chain[b], hipEventDisableTiming));
-            HIPCHK(e, hipEventCreateWithFlags(&e->ev_red[b], hipEventDisableTiming));
-        }
-    float div = 0.0f;
-    if (n_connected) {
-        if (e->div_n != n_connected || e->div_v == 0.0f) {
-            e->div_v = dspfx_link_divisor(n_connected);
-            e->div_n = n_connected;
-        }
-        div = e->div_v;
-    }
+        if (const int rc = ensure_mixpart2(e, b)) return rc;
     e->mp_frames = n_frames;
-    e->mp_mix_now = mix;
-    e->mp_div_now = div;
-    e->mp_building = true;
-    const int rc = dspfx_process(e, in, side, out, nullptr, n_frames, stream);
-    e->mp_building = false;
-    if (rc) return rc;
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
+    BlockCall c(in, side, out, nullptr, n_frames, (hipStream_t)stream);
+    c.bus = BUS_PIPELINED;
+    c.pipe_mix = mix;
+    c.div = n_connected ? output_divisor(e, n_connected) : 0.0f;
+    if (const int rc = process_block(e, c)) return rc;
     ++e->mp_count;
     return DSPFX_OK;
 }
@@ -1607,14 +1641,7 @@ extern "C" int dspfx_mixpipe_flush(dspfx_engine *e, float *mix_older, float *mix
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     const uint32_t nf = e->mp_frames;
-    float div = 0.0f;
-    if (n_connected) {
-        if (e->div_n != n_connected || e->div_v == 0.0f) {
-            e->div_v = dspfx_link_divisor(n_connected);
-            e->div_n = n_connected;
-        }
-        div = e->div_v;
-    }
+    const float div = n_connected ? output_divisor(e, n_connected) : 0.0f;
     const int last = (int)((e->mp_count - 1) & 1);          // buffers written by the last launch
     float *b_last = last ? e->mixpart_b2 : e->mixpart_b, *b_other = last ? e->mixpart_b : e->mixpart_b2;
     if (e->mp_count >= 2) {                                  // block n-2: its slices were reduced by the last launch
@@ -1634,11 +1661,7 @@ extern "C" int dspfx_mix_finish(dspfx_engine *e, float *mix, uint32_t n_frames, 
     ApiScope api(e);
     if (api.rc) return api.rc;
     HIPCHK(e, hipSetDevice(e->device));
-    if (e->div_n != n_connected || e->div_v == 0.0f) {   // the literal f32 increment loop is O(n): cache it
-        e->div_v = dspfx_link_divisor(n_connected);
-        e->div_n = n_connected;
-    }
-    launch_mix_finish(mix, n_frames, e->div_v, (hipStream_t)stream);
+    launch_mix_finish(mix, n_frames, output_divisor(e, n_connected), (hipStream_t)stream);
     HIPCHK(e, hipGetLastError());
     return DSPFX_OK;
 }

@@ -80,7 +80,6 @@ struct Node {
     // control ports: per-channel latched slider values (derive lib.rs:148)
     float *latch[3] = {nullptr, nullptr, nullptr};
     int latch_valid = 0;
-    const float *ctl_now[3] = {nullptr, nullptr, nullptr};   // signals of the call being launched
 };
 
 // A small engine's chain shape being specialised in the background (jit.hip: async_jit_submit).  The engine runs the
@@ -144,6 +143,47 @@ struct Stage {
     bool fast_div = false;          // all constant divisors of the stage verified (see divisor_is_fast)
 };
 
+// What ONE process call asks for: built on the entry point's stack and handed down to the launches by const reference.
+// Nothing about the block being launched lives in the engine, so no exit path has anything to put back.
+enum BusForm {
+    BUS_NOW = 0,        // `mix` (if any) is this block's bus, finished behind this block's launches and divided by `div` when != 0
+    BUS_DEFERRED = 1,   // the first-stage partial sums stay in `partials`; whoever reduces them reads part_stride / part_frames[flip]
+    BUS_PIPELINED = 2   // they stay in mixpart2[mp_count & 1]; this launch carries the later stages of the two blocks before it
+};
+struct BlockCall {
+    const float *in = nullptr, *side = nullptr;
+    float *out = nullptr, *mix = nullptr;
+    uint32_t n_frames = 0;            // of this (sub-)block
+    uint32_t tile_frames = 0;         // of the caller's whole block: the tile stride of the tiled layout
+    hipStream_t stream = nullptr;
+    // graph engines: input blocks 2.. and output blocks 1.. (dspfx_process_io; [0] / [1] are in / side / out above)
+    const float *xin[GRAPH_IO] = {};
+    float *xout[GRAPH_IO] = {};
+    // connected control ports: the caller's list; its signals start ctl_off floats in (the sub-block's offset)
+    const dspfx_ctl *ctl = nullptr;
+    int n_ctl = 0;
+    size_t ctl_off = 0;
+    BusForm bus = BUS_NOW;
+    float div = 0.0f;                 // Output-hop divisor, 0: none -- of this block (BUS_NOW) or of block k-2 (BUS_PIPELINED)
+    float *partials = nullptr;        // BUS_DEFERRED
+    float *pipe_mix = nullptr;        // BUS_PIPELINED: where block k-2's bus is delivered
+    // channel window (pipelined host path): channels [window_c0, window_c0 + window_n), window_n 0 = all; window_last marks the call that
+    // finishes the block (ring positions advance, sliders latch: once)
+    uint32_t window_c0 = 0, window_n = 0;
+    bool window_last = true;
+
+    BlockCall(const float *in_, const float *side_, float *out_, float *mix_, uint32_t n_frames_, hipStream_t s)
+        : in(in_), side(side_), out(out_), mix(mix_), n_frames(n_frames_), tile_frames(n_frames_), stream(s) {}
+    bool wants_bus() const { return mix || bus != BUS_NOW; }
+    // the signal connected to slider k of `node` in this call (the last entry that names it), or nullptr
+    const float *signal(int node, int k) const {
+        const float *s = nullptr;
+        for (int i = 0; i < n_ctl; ++i)
+            if (ctl[i].node == node && ctl[i].param == k) s = ctl[i].signal + ctl_off;
+        return s;
+    }
+};
+
 }  // namespace dspfx_host
 using namespace dspfx_host;
 
@@ -169,27 +209,12 @@ struct dspfx_engine {
     bool red_pending[2] = {false, false}, collect_due = false;
     int flip = 0;
     uint32_t part_stride[2] = {0, 0}, part_frames[2] = {0, 0};
-    float *partials_override = nullptr;   // set while a deferred-mix block is being launched
     // in-kernel pipelined mix bus (dspfx_process_mixpipe): block k's launch also runs stage 2 of block k-1 and
     // stage 3 of block k-2.  mp_count = blocks submitted since the last flush.
     uint64_t mp_count = 0;
     uint32_t mp_frames = 0, mp_rows[2] = {0, 0};
-    float *mp_mix_now = nullptr;          // where the launch being built delivers block k-2's bus
-    float mp_div_now = 0.0f;
-    bool mp_building = false;
-    float bus_div_now = 0.0f;             // dspfx_process_bus: the Output hop's divisor for the block being launched (0: none)
-    // channel window of the current run_subblock call (pipelined host path): channels [win_c0, win_c0 + win_n), 0 = all;
-    // win_last marks the call that finishes the block (ring positions advance once)
-    uint32_t win_c0 = 0, win_n = 0;
-    bool win_last = true;
     hipStream_t hs_in = nullptr, hs_out = nullptr, hs_run = nullptr;
     std::vector<hipEvent_t> hev;
-    uint32_t ctl_tile_frames = 0;         // dspfx_process_ctl: frames of the caller's whole block (tile stride)
-    // dspfx_process_io: input blocks 2.. and output blocks 1.. of the call being launched (graph engines), and the float
-    // offset of the sub-block being launched
-    const float *io_in[GRAPH_IO] = {};
-    float *io_out[GRAPH_IO] = {};
-    size_t io_off = 0;
     // staging for dspfx_process_host; dspfx_process_pcm widens into h_in / h_side and narrows from h_out
     float *h_in = nullptr, *h_side = nullptr, *h_out = nullptr, *h_mix = nullptr;
     // device staging of dspfx_process_host_pcm: blocks in device sample formats, sized max_frames x N elements of the
@@ -211,7 +236,7 @@ struct dspfx_engine {
     // api_mu serialises every entry point that touches the engine; a slider store from another thread never waits
     // for it: it is queued under pend_mu and applied by whoever holds api_mu next, at a block boundary.
     mutable std::recursive_mutex api_mu;
-    int api_depth = 0;                        // nesting of entry points (dspfx_process_ctl -> dspfx_process): only the outermost drains
+    int api_depth = 0;                        // nesting of entry points (dspfx_process_host -> dspfx_process_pcm, dspfx_mix_allreduce -> dspfx_mix_finish): only the outermost drains
     mutable std::mutex pend_mu;               // pending, pub_kinds, log, next_seq
     struct Store { uint64_t seq; int node, param; float value; };   // param -1: a mode store (value = the mode)
     std::deque<Store> pending;
@@ -325,10 +350,11 @@ inline size_t ring_groups_for(uint32_t D) { return ((size_t)D + RING_GROUP_ROWS 
 int ring_reserve(dspfx_engine *e, int node, uint64_t gen, size_t want_groups, size_t keep_free, bool quiet, size_t max_share);   // any thread, no api_mu
 int ring_resize(dspfx_engine *e, int node, uint32_t D, hipStream_t s);          // api_mu held
 void recompute_min_delay(dspfx_engine *e);
-int run_subblock(dspfx_engine *e, const float *in, const float *side, float *out, float *mix, uint32_t nframes, uint32_t tile_frames,
-                 hipStream_t stream);
+int run_subblock(dspfx_engine *e, const BlockCall &c);
+float output_divisor(dspfx_engine *e, uint64_t n_connected);   // dspfx_link_divisor, the last one cached (api_mu held)
 int bind_stream(dspfx_engine *e, hipStream_t s);
 int check_pcm_io(dspfx_engine *e, const dspfx_pcm_io *io);   // dspfx.hip: DSPFX_ERR_INVALID with a message, or DSPFX_OK
+int check_block(dspfx_engine *e, const void *in, const void *out, uint32_t n_frames);   // ... the same for a block's buffers and length
 int quiesce(dspfx_engine *e);
 int settle_null_stream(dspfx_engine *e);
 int drain_pending(dspfx_engine *e, hipStream_t s);

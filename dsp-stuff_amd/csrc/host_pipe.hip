@@ -114,15 +114,15 @@ static int host_block(dspfx_engine *e, const dspfx_pcm_io &io, const void *in, c
                 HIPCHK(e, launch_pcm_widen(io.in_format, io.in_channels, d_in, e->h_in, n_frames, cn, N, c0, e->hs_run));
                 if (side) HIPCHK(e, launch_pcm_widen(io.in_format, io.in_channels, d_side, e->h_side, n_frames, cn, N, c0, e->hs_run));
             }
-            e->win_c0 = c0;
-            e->win_n = cn;
-            e->win_last = p + 1 == n_parts;
-            if (mix) e->partials_override = e->mixpart;   // every part leaves its waves' partial sums; reduced once below
-            rc = run_subblock(e, e->h_in, side ? e->h_side : nullptr, e->h_out, nullptr, n_frames, n_frames, e->hs_run);
-            e->partials_override = nullptr;
-            e->win_c0 = 0;
-            e->win_n = 0;
-            e->win_last = true;
+            BlockCall c(e->h_in, side ? e->h_side : nullptr, e->h_out, nullptr, n_frames, e->hs_run);
+            c.window_c0 = c0;
+            c.window_n = cn;
+            c.window_last = p + 1 == n_parts;
+            if (mix) {   // every part leaves its waves' partial sums; reduced once below
+                c.bus = BUS_DEFERRED;
+                c.partials = e->mixpart;
+            }
+            rc = run_subblock(e, c);
             if (rc) break;
             if (!plain_out) HIPCHK(e, launch_pcm_narrow(io.out_format, io.out_channels, e->h_out, d_out, n_frames, cn, N, c0, e->hs_run));
             HIPCHK(e, hipEventRecord(e->hev[2 * p + 1], e->hs_run));
@@ -156,9 +156,7 @@ extern "C" int dspfx_process_host(dspfx_engine *e, const float *in, const float 
     if (!e) return DSPFX_ERR_INVALID;
     ApiScope api(e);
     if (api.rc) return api.rc;
-    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
-    if (n_frames > e->desc.max_frames)
-        return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
     const dspfx_pcm_io f32{DSPFX_SAMPLE_F32, 1, DSPFX_SAMPLE_F32, 1};
     return host_block(e, f32, in, side, out, mix, n_frames);
 }
@@ -169,8 +167,6 @@ extern "C" int dspfx_process_host_pcm(dspfx_engine *e, const dspfx_pcm_io *io, c
     ApiScope api(e);
     if (api.rc) return api.rc;
     if (const int rc = check_pcm_io(e, io)) return rc;
-    if (!in || !out) return fail(e, DSPFX_ERR_INVALID, "in/out must not be null");
-    if (n_frames > e->desc.max_frames)
-        return fail(e, DSPFX_ERR_INVALID, "n_frames %u > max_frames %u", n_frames, e->desc.max_frames);
+    if (const int rc = check_block(e, in, out, n_frames)) return rc;
     return host_block(e, *io, in, side, out, mix, n_frames);
 }

@@ -274,7 +274,8 @@ extern "C" int dspfx_tune_placement(dspfx_engine *e, const float *in, const floa
         }
     }
     int rc = DSPFX_OK;
-    const size_t tile_frames = e->desc.max_frames;   // the buffers are laid out like a full block of the engine
+    BlockCall call(in, side, out, nullptr, n_frames, s);
+    call.tile_frames = e->desc.max_frames;           // the buffers are laid out like a full block of the engine
     const auto tick = [] { return std::chrono::steady_clock::now(); };
     const auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     const bool debug = getenv("DSPFX_RING_TUNE_DEBUG") != nullptr;
@@ -302,7 +303,7 @@ extern "C" int dspfx_tune_placement(dspfx_engine *e, const float *in, const floa
             for (int rep = 0; rep < 3; ++rep) {
                 tg.rewind();
                 (void)hipEventRecord(tg.ea, s);
-                const int r = run_subblock(e, in, side, out, nullptr, n_frames, (uint32_t)tile_frames, s);
+                const int r = run_subblock(e, call);
                 (void)hipEventRecord(tg.eb, s);
                 if (r) return r;
                 if (hipEventSynchronize(tg.eb) != hipSuccess) return fail(e, DSPFX_ERR_HIP, "hipEventSynchronize failed");

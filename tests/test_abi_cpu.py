@@ -124,3 +124,32 @@ def test_no_getenv_on_the_per_block_path():
     # ... and the two functions every block goes through mention the snapshot, not the environment
     src = open(os.path.join(csrc, "dspfx.hip")).read()
     assert "e->env.mix_tail" in src and "e->env.xcd_remap" in src and "read_env_switches()" in src
+
+
+def test_block_context_travels_in_the_call_not_in_the_engine():
+    """What one process call means (bus form, control signals, extra graph blocks, channel window, tile stride) is a BlockCall on
+    the entry point's stack, handed down to run_subblock: the engine keeps no "for the block being launched" members, and no
+    entry point gets to the launches by calling the public dspfx_process* again.  Structural check on engine.h / dspfx.hip."""
+    csrc = os.path.join(ROOT, "dsp-stuff_amd", "csrc")
+
+    def code(name):      # the file without string literals and comments
+        lines = open(os.path.join(csrc, name), errors="ignore").read().splitlines()
+        return [re.sub(r'"(?:\\.|[^"\\])*"', '""', ln).split("//")[0] for ln in lines]
+
+    hdr = "\n".join(code("engine.h"))
+    for gone in ("bus_div_now", "partials_override", "mp_building", "mp_mix_now", "mp_div_now", "ctl_tile_frames", "ctl_now",
+                 "win_c0", "win_n", "win_last"):
+        assert not re.search(r"\b%s\b" % gone, hdr), f"engine.h still declares {gone}: per-call state belongs in BlockCall"
+    assert "struct BlockCall" in hdr
+    start = hdr.index("struct dspfx_engine {")
+    depth, end = 0, start
+    for end in range(start, len(hdr)):
+        depth += {"{": 1, "}": -1}.get(hdr[end], 0)
+        if depth == 0 and hdr[end] == "}":
+            break
+    engine = hdr[start:end]
+    assert "api_mu" in engine                                   # (the whole struct was found)
+    assert not re.search(r"\bio_(in|out|off)\b", engine), "dspfx_engine carries the extra graph blocks of a call"
+    for ln, line in enumerate(code("dspfx.hip"), 1):
+        if re.search(r"\bdspfx_process\w*\s*\(", line):
+            assert line.startswith('extern "" int dspfx_process'), f"dspfx.hip:{ln}: an entry point calls {line.strip()}"
