@@ -48,6 +48,8 @@ SAMPLE_F32, SAMPLE_I16, SAMPLE_U16, SAMPLE_I32 = range(4)
 # dspfx_pitch_param: the Pitch Detector's sliders (nodes/pitch.rs:47-56), 0.5 each by default
 PITCH_POWER, PITCH_CLARITY, PITCH_PICK = range(3)
 PITCH_WINDOW = 1024
+SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT = 128, 8192      # DSPFX_SPECTRUM_*: the Spectrogram node's fft_size slider (spectrogram.rs:142)
+SPECTRUM_RATE = 48000.0         # spectrogram.rs:238 sampling_rate: bin k of an n-point window is k * 48000 / n Hz
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -67,6 +69,8 @@ EXPORTS = [
     "dspfx_pitch_reset", "dspfx_pitch_windows",
     "dspfx_resample_create", "dspfx_resample_destroy", "dspfx_resample_push", "dspfx_resample_slot", "dspfx_resample_pull",
     "dspfx_resample_available", "dspfx_resample_skip", "dspfx_resample_reset", "dspfx_resample_plan",
+    "dspfx_spectrum_create", "dspfx_spectrum_destroy", "dspfx_spectrum_push", "dspfx_spectrum_slot", "dspfx_spectrum_column",
+    "dspfx_spectrum_reset", "dspfx_spectrum_windows", "dspfx_spectrum_plan",
 ]
 COMM_ID_BYTES = 128
 
@@ -110,6 +114,11 @@ class _ResampleDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
                 ("block_frames", C.c_uint32), ("slots", C.c_uint32), ("target_hz", C.c_uint32), ("out_format", C.c_int32),
                 ("out_channels", C.c_int32)]
+
+
+class _SpectrumDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
+                ("fft_size", C.c_uint32), ("columns", C.c_uint32), ("window", C.POINTER(C.c_float)), ("gain", C.POINTER(C.c_float))]
 
 
 class _Ctl(C.Structure):
@@ -231,6 +240,17 @@ def lib():
     L.dspfx_resample_reset.argtypes = [vp]
     L.dspfx_resample_plan.argtypes = [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.dspfx_spectrum_create.argtypes = [C.POINTER(_SpectrumDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_spectrum_destroy.argtypes = [vp]
+    L.dspfx_spectrum_push.argtypes = [vp, vp, C.c_uint32, vp]
+    L.dspfx_spectrum_slot.restype = C.c_void_p
+    L.dspfx_spectrum_slot.argtypes = [vp]
+    L.dspfx_spectrum_column.restype = C.c_void_p
+    L.dspfx_spectrum_column.argtypes = [vp, C.c_uint32]
+    L.dspfx_spectrum_reset.argtypes = [vp]
+    L.dspfx_spectrum_windows.restype = C.c_int64
+    L.dspfx_spectrum_windows.argtypes = [vp]
+    L.dspfx_spectrum_plan.argtypes = [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -976,3 +996,117 @@ def graph_source(nodes: Sequence[NodeSpec], links: Sequence[Tuple[int, int, int]
     if rc != 0:
         raise DspfxError(rc, L.dspfx_strerror(rc).decode())
     return buf.value.decode()
+
+
+def spectrum_plan(fft_size: int):
+    """dspfx_spectrum_plan, a pure host function (no GPU): -> (window float32[n], bin_hz float32[n/2]): the default (Hann)
+    window table and the physical frequency k * 48000 / n of every bin."""
+    L = lib()
+    n = int(fft_size)
+    ok = 0 < n <= SPECTRUM_MAX_FFT
+    win = np.zeros(n if ok else 1, np.float32)
+    hz = np.zeros(max(n // 2, 1) if ok else 1, np.float32)
+    rc = L.dspfx_spectrum_plan(n & 0xFFFFFFFF, win.ctypes.data_as(C.POINTER(C.c_float)), hz.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    return win, hz
+
+
+def spectrum_bins(fft_size: int, lower_hz: float, upper_hz: float):
+    """The Spectrogram node's frequency bounds as a bin range: -> (k_lo, k_hi, bin_hz[k_lo:k_hi]) with
+    lower_hz <= k * 48000 / n <= upper_hz exactly for k_lo <= k < k_hi (a slice of a column's bins; empty: k_lo == k_hi)."""
+    _, hz = spectrum_plan(fft_size)
+    inside = np.nonzero((hz >= lower_hz) & (hz <= upper_hz))[0]
+    if not len(inside):
+        return 0, 0, hz[:0]
+    k_lo, k_hi = int(inside[0]), int(inside[-1]) + 1
+    return k_lo, k_hi, hz[k_lo:k_hi]
+
+
+class SpectrumBank:
+    """The Spectrogram node (nodes/spectrogram.rs) for N channels (include/dspfx.h, dspfx_spectrum_*): blocks pushed in the
+    layout of `tile_channels` (as Engine's); every `fft_size` frames one column vol[k] = |FFT(window * x)[k]| * gain[k],
+    k in [0, fft_size/2), per channel, the newest `columns` of them kept on the device.  `window` (float32[fft_size]) and
+    `gain` (float32[fft_size/2]) are host tables: None = the Hann window of spectrum_plan / 1.0.  audioviz's volume
+    normalisation is not restated: a caller that wants it passes it as `gain`.  Asynchronous on `stream` like Engine.process."""
+
+    def __init__(self, channels: int, fft_size: int = 512, columns: int = 1, tile_channels: int = 0, window=None, gain=None,
+                 device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.fft_size, self.columns = int(fft_size), int(columns)
+        self.h = C.c_void_p()
+        fp = C.POINTER(C.c_float)
+        tables = []
+        for name, tab, length in (("window", window, self.fft_size), ("gain", gain, self.fft_size // 2)):
+            if tab is not None:
+                tab = np.ascontiguousarray(tab, np.float32)
+                if tab.shape != (length,):
+                    raise ValueError(f"{name} must hold {length} values, not {tab.shape}")
+            tables.append(tab)
+        d = _SpectrumDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, self.fft_size & 0xFFFFFFFF,
+                          self.columns & 0xFFFFFFFF, *(fp() if tab is None else tab.ctypes.data_as(fp) for tab in tables))
+        rc = self.L.dspfx_spectrum_create(C.byref(d), C.byref(self.h))         # the tables are copied before this returns
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    def _view(self, addr, elems):
+        import torch
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": (elems,), "typestr": "<f4", "data": (addr, False), "version": 2}
+        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+
+    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
+        """Append a device block [n_frames][N] (or the tiled form); computes the columns that fall due."""
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        self._chk(self.L.dspfx_spectrum_push(self.h, _ptr(block), int(n_frames), C.c_void_p(stream) if stream else None))
+
+    def slot(self) -> Optional[int]:
+        """Device address of the next 128-frame slot (None unless the frames pushed are a multiple of 128)."""
+        return self.L.dspfx_spectrum_slot(self.h)
+
+    def slot_tensor(self):
+        """The next slot as a float32 device tensor of 128 * N elements over the bank's own memory (valid while the bank
+        lives; None when there is no slot): an Engine writes its block there, then push(slot, 128) copies nothing."""
+        addr = self.slot()
+        return None if addr is None else self._view(addr, BUF_SIZE * self.channels)
+
+    def column(self, age: int = 0):
+        """The column `age` windows back (0 = the newest): a float32 device tensor of fft_size/2 * N elements over the bank's
+        own memory, no copy -- element (k, c) where frame k of channel c is in a block of fft_size/2 frames (frame-major:
+        [k][N]).  None when there is no such column (yet, or age >= columns).  It is overwritten `columns` windows later, and
+        a read must be ordered after the push that computed it."""
+        if age < 0:
+            return None
+        addr = self.L.dspfx_spectrum_column(self.h, int(age))
+        return None if addr is None else self._view(addr, self.fft_size // 2 * self.channels)
+
+    def bins(self, lower_hz: float = 20.0, upper_hz: float = 20000.0):
+        """spectrum_bins for this bank's fft_size (the defaults are the node's, spectrogram.rs:200-201)."""
+        return spectrum_bins(self.fft_size, lower_hz, upper_hz)
+
+    def reset(self):
+        self._chk(self.L.dspfx_spectrum_reset(self.h))
+
+    @property
+    def windows(self) -> int:
+        return int(self.L.dspfx_spectrum_windows(self.h))
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_spectrum_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -27,7 +27,9 @@ demux is the identity whose unselected output port delivers zeros -- still a con
 The display-only nodes (pitch detector, wave view, spectrogram) produce no signal; they are dropped on import.  What feeds
 a pitch detector is kept in `Graph.pitch_taps` (node id -> PitchTap: the producers linked into its "in" port and its saved
 thresholds), for a PitchBank (dspfx_pitch_*) to evaluate (GraphEngine(pitch=True)); its threshold sliders are not ports (pitch.rs:47-56 has no
-`as_input`), so a link into one is rejected.
+`as_input`), so a link into one is rejected.  What feeds a spectrogram is kept the same way in `Graph.spectrum_taps` (node
+id -> SpectrumTap: the producers linked into its "in" port and its saved fft_size / buffer_size / lower_bound / upper_bound),
+for a SpectrumBank (dspfx_spectrum_*) to evaluate (GraphEngine(spectrum=True)).  Wave views stay dropped: they are a copy.
 
 Not expressible: cycles (the reference's scheduler would deadlock on them too), muff (GPL crate, source absent),
 slider ports with fan-in.
@@ -37,7 +39,7 @@ from __future__ import annotations
 import json
 from typing import Dict, List, Optional, Sequence, Tuple
 
-from . import (ADD, DISTORT, PitchBank, ERR_UNSUPPORTED, FIR, FUZZ, GAIN, GRAPH_INPUT, GRAPH_INPUT2, GRAPH_INPUTS, GRAPH_MAX_IO, GRAPH_MAX_NODES, GRAPH_ZERO,
+from . import (ADD, DISTORT, PitchBank, SpectrumBank, SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT, ERR_UNSUPPORTED, FIR, FUZZ, GAIN, GRAPH_INPUT, GRAPH_INPUT2, GRAPH_INPUTS, GRAPH_MAX_IO, GRAPH_MAX_NODES, GRAPH_ZERO,
                LINK_INPUT, LINK_INTERNAL, LINK_SIDE_RAW, MIX, PORT_MAIN, PORT_RAW, PORT_SIDE, PORT_SLIDER, SIGNAL_GEN, DspfxError, Engine,
                NodeSpec)
 from .config import _TABLE, DspConfigError, _node_from_cfg
@@ -47,6 +49,7 @@ _SINKS = {"pitch", "wave_view", "spectrogram"}          # display-only: `process
                                                         # wave_view.rs:157-175), so they and the links into them are dropped
 _ROUTING = {"mux", "demux"}
 PITCH_SLIDERS = ("power_thresh", "clarity_thresh", "pick_thresh")   # pitch.rs:47-56, saved, 0.5 by default
+SPECTRUM_FIELDS = (("fft_size", 512), ("buffer_size", 250), ("lower_bound", 20), ("upper_bound", 20000))   # spectrogram.rs:198-201
 ZERO = -1          # pseudo producer: the unselected output port of a demux (a connected pipe that carries zeros)
 
 
@@ -74,6 +77,21 @@ class PitchTap:
         return f"PitchTap(id={self.id}, links={self.links}, thresholds={self.thresholds})"
 
 
+class SpectrumTap:
+    """A Spectrogram node of the document: `links` = producer ids linked into its "in" port, in link order (ZERO for a
+    demux's unselected port), and its saved sliders (spectrogram.rs:31-39).  fft_size is kept as saved: a SpectrumBank takes
+    powers of two only, which GraphEngine(spectrum=True) checks."""
+    __slots__ = ("id", "links", "fft_size", "buffer_size", "lower_bound", "upper_bound")
+
+    def __init__(self, nid, links, fft_size, buffer_size, lower_bound, upper_bound):
+        self.id, self.links = nid, links
+        self.fft_size, self.buffer_size, self.lower_bound, self.upper_bound = fft_size, buffer_size, lower_bound, upper_bound
+
+    def __repr__(self):
+        return (f"SpectrumTap(id={self.id}, links={self.links}, fft_size={self.fft_size}, buffer_size={self.buffer_size}, "
+                f"bounds=({self.lower_bound}, {self.upper_bound}))")
+
+
 class Graph:
     """Parsed DSPConfig: nodes with their incoming links per port, in document order."""
 
@@ -87,7 +105,9 @@ class Graph:
         self.nodes: Dict[int, _GNode] = {}
         self.dropped: List[int] = []
         self.pitch_taps: Dict[int, PitchTap] = {}
+        self.spectrum_taps: Dict[int, SpectrumTap] = {}
         pitch_cfg: Dict[int, dict] = {}
+        spectrum_cfg: Dict[int, dict] = {}
         for n in raw_nodes:
             tn = n["typename"]
             if tn in _SINKS:
@@ -100,6 +120,14 @@ class Graph:
                         raise DspConfigError(f"pitch node {n['id']}: thresholds are not numbers") from None
                     pitch_cfg[int(n["id"])] = cfg
                     self.pitch_taps[int(n["id"])] = PitchTap(int(n["id"]), [], th)
+                elif tn == "spectrogram":
+                    cfg = n.get("cfg", {})
+                    try:
+                        vals = [int(cfg.get(f, d)) for f, d in SPECTRUM_FIELDS]
+                    except (TypeError, ValueError):
+                        raise DspConfigError(f"spectrogram node {n['id']}: its sliders are not integers") from None
+                    spectrum_cfg[int(n["id"])] = cfg
+                    self.spectrum_taps[int(n["id"])] = SpectrumTap(int(n["id"]), [], *vals)
                 continue
             if tn in _UNSUPPORTED:
                 raise DspConfigError(f"node type {tn!r} is outside the accelerated path")
@@ -138,6 +166,17 @@ class Graph:
                 oname = port_name(ln, lp, "outputs")
                 sel = src.typename == "demux" and oname != src.cfg.get("out_port", "A").lower()
                 self.pitch_taps[rn].links.append(ZERO if sel else ln)
+                continue
+            if rn in self.spectrum_taps:
+                pname = next((name for name, pid in spectrum_cfg[rn].get("inputs", {}).items() if int(pid) == rp), None)
+                if pname != "in":
+                    raise DspConfigError(f"link refers to unknown input port {rp} of node {rn}")
+                if ln not in self.nodes:
+                    raise DspConfigError("link refers to a missing node")
+                src = self.nodes[ln]
+                oname = port_name(ln, lp, "outputs")
+                sel = src.typename == "demux" and oname != src.cfg.get("out_port", "A").lower()
+                self.spectrum_taps[rn].links.append(ZERO if sel else ln)
                 continue
             if rn in self.dropped:
                 continue
@@ -566,6 +605,16 @@ def series_plan(g: Graph):
     return None if fused_plan(g) is not None else segment_plan(g)
 
 
+def check_spectrum_sizes(g: Graph):
+    """What GraphEngine(spectrum=True) asks of the document: every Spectrogram node's saved fft_size is one a SpectrumBank
+    takes (the reference's slider stops anywhere in 128..=8192; rustfft takes any length, the bank powers of two)."""
+    for nid, tap in g.spectrum_taps.items():
+        n = tap.fft_size
+        if not (SPECTRUM_MIN_FFT <= n <= SPECTRUM_MAX_FFT) or n & (n - 1):
+            raise DspConfigError(f"spectrogram node {nid}: fft_size {n} is not a power of two in "
+                                 f"{SPECTRUM_MIN_FFT}..={SPECTRUM_MAX_FFT} (the spectrum bank takes no other size)")
+
+
 class GraphEngine:
     """N independent copies of a saved graph.  `process(x)` takes the Input node's block [n_frames][N] (device
     tensor, the engine's layout) and returns the Output node's block.
@@ -574,15 +623,21 @@ class GraphEngine:
     pitch=True: every Pitch Detector node of the document gets a PitchBank, fed every block with its "in" port's value,
     averaged over its links like any port (collect_and_average): an extra output block of the one kernel or of the last
     region kernel, dspfx_link_average in the run-by-run plan (the series plan is not used then).  `pitch(node_id)` reads
-    its results, `set_pitch_param` stores its thresholds, `pitch_tap(node_id)` is the block it was fed last."""
+    its results, `set_pitch_param` stores its thresholds, `pitch_tap(node_id)` is the block it was fed last.
+    spectrum=True: likewise every Spectrogram node gets a SpectrumBank of its saved fft_size that keeps `spectrum_columns`
+    columns, fed through the same tap path; `spectrum(node_id, age)` is a column, `spectrum_tap(node_id)` the block it was fed
+    last.  A saved fft_size that is not a power of two in 128..=8192 raises DspConfigError (only then: without spectrum=True
+    the node is dropped as before)."""
 
     def __init__(self, text: str, channels: int, max_frames: int = 128, device: int = 0, tile_channels: int = 0,
                  page_round: bool = False, fused: Optional[bool] = None, max_nodes: Optional[int] = None,
-                 regions: Optional[bool] = None, pitch: bool = False):
+                 regions: Optional[bool] = None, pitch: bool = False, spectrum: bool = False, spectrum_columns: int = 1):
         import torch
         self.torch = torch
         self.g = Graph(text, page_round)
         self.N, self.B, self.tile = channels, max_frames, tile_channels
+        if spectrum:
+            check_spectrum_sizes(self.g)
         self.dev = torch.device("cuda", device)
         # pitch taps: banks, and the block each is fed (taps without a link read zeros: node.rs:288)
         self.banks: Dict[int, PitchBank] = {}
@@ -594,7 +649,16 @@ class GraphEngine:
                                             clarity_thresh=tap.thresholds[1], pick_thresh=tap.thresholds[2])
                 if tap.links:
                     self.tap_ids.append(nid)
-        tap_links = [self.g.pitch_taps[t].links for t in self.tap_ids]
+        # spectrogram taps: the same path, after the pitch taps
+        self.spectra: Dict[int, SpectrumBank] = {}
+        if spectrum:
+            for nid, tap in self.g.spectrum_taps.items():
+                self.spectra[nid] = SpectrumBank(channels, fft_size=tap.fft_size, columns=spectrum_columns, tile_channels=tile_channels,
+                                                 device=device)
+                if tap.links:
+                    self.tap_ids.append(nid)
+        self.tap_links = {t: (self.g.pitch_taps[t] if t in self.g.pitch_taps else self.g.spectrum_taps[t]).links for t in self.tap_ids}
+        tap_links = [self.tap_links[t] for t in self.tap_ids]
         self.fused: Optional[Engine] = None
         self.series, self.series_kind = [], []
         self.regions = []
@@ -818,12 +882,14 @@ class GraphEngine:
         out_node = self.g.nodes[self.g.outputs[0]]
         self.util.link_average([self._source(s, x) for s in out_node.main], self.final, nf, stream)
         for t in self.tap_ids:
-            self.util.link_average([self._source(s, x) for s in self.g.pitch_taps[t].links], self.tap_bufs[t], nf, stream)
+            self.util.link_average([self._source(s, x) for s in self.tap_links[t]], self.tap_bufs[t], nf, stream)
         self._push_taps(nf, stream)
         return self.final
 
     def _push_taps(self, nf: int, stream: int):
         for nid, bank in self.banks.items():
+            bank.push(self.tap_bufs.get(nid, self.zeros), nf, stream)
+        for nid, bank in self.spectra.items():
             bank.push(self.tap_bufs.get(nid, self.zeros), nf, stream)
 
     def _bank(self, node_id: int) -> PitchBank:
@@ -842,6 +908,20 @@ class GraphEngine:
     def pitch_tap(self, node_id: int):
         """The block a Pitch node was fed last (its "in" port's average; zeros for a node without links)."""
         self._bank(node_id)
+        return self.tap_bufs.get(node_id, self.zeros)
+
+    def _spectrum_bank(self, node_id: int) -> SpectrumBank:
+        if node_id not in self.spectra:
+            raise KeyError(f"node {node_id} is not a Spectrogram of this graph, or the engine was made without spectrum=True")
+        return self.spectra[node_id]
+
+    def spectrum(self, node_id: int, age: int = 0):
+        """The column of a Spectrogram node `age` windows back (SpectrumBank.column: a view, None while there is none)."""
+        return self._spectrum_bank(node_id).column(age)
+
+    def spectrum_tap(self, node_id: int):
+        """The block a Spectrogram node was fed last (its "in" port's average; zeros for a node without links)."""
+        self._spectrum_bank(node_id)
         return self.tap_bufs.get(node_id, self.zeros)
 
     def tune_placement(self, x, n_frames: Optional[int] = None, stream: int = 0):
@@ -869,5 +949,5 @@ class GraphEngine:
             eng.close()
         for r in self.runs:
             r.engine.close()
-        for bank in self.banks.values():
+        for bank in list(self.banks.values()) + list(self.spectra.values()):
             bank.close()

@@ -551,3 +551,81 @@ impl Drop for Resampler {
         }
     }
 }
+
+/// The Spectrogram node (nodes/spectrogram.rs) for N channels (`dspfx_spectrum_*`): device blocks in, one column
+/// `vol[k] = |FFT(window * x)[k]| * gain[k]`, `k < fft_size / 2`, per channel for every `fft_size` frames; the newest `columns` stay
+/// on the device.  `window` / `gain`: host tables copied at construction, `None` = the Hann window / 1.0.
+pub struct SpectrumBank {
+    h: *mut dspfx_spectrum,
+    channels: u32,
+    fft_size: u32,
+}
+unsafe impl Send for SpectrumBank {}
+// every call is serialised by the bank's own lock
+unsafe impl Sync for SpectrumBank {}
+
+impl SpectrumBank {
+    /// `tile_channels`: 0 (frame-major) or the engine's W; `fft_size`: a power of two in 128..=8192; `columns`: the node's buffer_size.
+    pub fn new(device: i32, channels: u32, tile_channels: u32, fft_size: u32, columns: u32, window: Option<&[f32]>,
+               gain: Option<&[f32]>) -> Result<Self, Error> {
+        if window.map_or(false, |w| w.len() != fft_size as usize) || gain.map_or(false, |g| g.len() != (fft_size / 2) as usize) {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "SpectrumBank: table length".into() });
+        }
+        let desc = dspfx_spectrum_desc {
+            abi_version: DSPFX_ABI_VERSION,
+            device,
+            channels,
+            tile_channels,
+            fft_size,
+            columns,
+            window: window.map_or(ptr::null(), |w| w.as_ptr()),
+            gain: gain.map_or(ptr::null(), |g| g.as_ptr()),
+        };
+        let mut h = ptr::null_mut();
+        let rc = unsafe { dspfx_spectrum_create(&desc, &mut h) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: "dspfx_spectrum_create".into() });
+        }
+        Ok(SpectrumBank { h, channels, fft_size })
+    }
+    fn check(&self, rc: c_int, what: &str) -> Result<(), Error> {
+        if rc == DSPFX_OK { Ok(()) } else { Err(Error { status: rc, message: what.into() }) }
+    }
+    pub fn channels(&self) -> u32 { self.channels }
+    pub fn fft_size(&self) -> u32 { self.fft_size }
+    /// Appends `n_frames` frames of a DEVICE block in the bank's layout; computes the columns that fall due.  Asynchronous on `stream`.
+    pub unsafe fn push(&self, block: *const f32, n_frames: u32, stream: *mut std::os::raw::c_void) -> Result<(), Error> {
+        let rc = dspfx_spectrum_push(self.h, block, n_frames, stream);
+        self.check(rc, "dspfx_spectrum_push")
+    }
+    /// Where an engine writes its next 128-frame block so that `push(slot, 128, ..)` copies nothing (null between slots).
+    pub fn slot(&self) -> *mut f32 { unsafe { dspfx_spectrum_slot(self.h) } }
+    /// The DEVICE column `age` windows back (`fft_size / 2` frames of N channels in the bank's layout); null when there is none.
+    pub fn column(&self, age: u32) -> *const f32 { unsafe { dspfx_spectrum_column(self.h, age) } }
+    pub fn reset(&self) -> Result<(), Error> {
+        let rc = unsafe { dspfx_spectrum_reset(self.h) };
+        self.check(rc, "dspfx_spectrum_reset")
+    }
+    pub fn windows(&self) -> i64 { unsafe { dspfx_spectrum_windows(self.h) } }
+    /// The default window table and `k * 48000 / fft_size` per bin (a pure host function).
+    pub fn plan(fft_size: u32) -> Result<(Vec<f32>, Vec<f32>), Error> {
+        if fft_size > DSPFX_SPECTRUM_MAX_FFT {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "dspfx_spectrum_plan".into() });
+        }
+        let mut window = vec![0.0f32; fft_size as usize];
+        let mut bin_hz = vec![0.0f32; (fft_size / 2) as usize];
+        let rc = unsafe { dspfx_spectrum_plan(fft_size, window.as_mut_ptr(), bin_hz.as_mut_ptr()) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: "dspfx_spectrum_plan".into() });
+        }
+        Ok((window, bin_hz))
+    }
+}
+
+impl Drop for SpectrumBank {
+    fn drop(&mut self) {
+        unsafe {
+            dspfx_spectrum_destroy(self.h);
+        }
+    }
+}

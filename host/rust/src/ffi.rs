@@ -104,6 +104,26 @@ pub struct dspfx_resample_desc {
     pub out_channels: i32,
 }
 
+/// Opaque Spectrogram bank handle (`typedef struct dspfx_spectrum dspfx_spectrum`).
+#[repr(C)]
+pub struct dspfx_spectrum {
+    _private: [u8; 0],
+}
+
+/// The Spectrogram bank's descriptor (`dspfx_spectrum_create`); `window` / `gain` are host tables read at create, null = default.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_spectrum_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub channels: u32,
+    pub tile_channels: u32,
+    pub fft_size: u32,
+    pub columns: u32,
+    pub window: *const f32,
+    pub gain: *const f32,
+}
+
 /// The Pitch Detector bank's descriptor (`dspfx_pitch_create`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -142,6 +162,9 @@ pub const DSPFX_PITCH_POWER: i32 = 0;
 pub const DSPFX_PITCH_CLARITY: i32 = 1;
 pub const DSPFX_PITCH_PICK: i32 = 2;
 pub const DSPFX_PITCH_WINDOW: u32 = 1024;
+// the Spectrogram node's fft_size slider (spectrogram.rs:142); the bank takes the powers of two in it
+pub const DSPFX_SPECTRUM_MIN_FFT: u32 = 128;
+pub const DSPFX_SPECTRUM_MAX_FFT: u32 = 8192;
 // the most device frames one dspfx_resample_pull makes, and the most frames a FIFO slot holds
 pub const DSPFX_RESAMPLE_MAX_FRAMES: u32 = 4096;
 
@@ -294,4 +317,12 @@ extern "C" {
     pub fn dspfx_resample_skip(r: *mut dspfx_resample, n_frames: u32) -> c_int;
     pub fn dspfx_resample_reset(r: *mut dspfx_resample) -> c_int;
     pub fn dspfx_resample_plan(target_hz: u32, value: *mut f64, idx: *mut u32, n_out: u32, advance: *mut u32, depth: *mut u32, coeff: *mut f64, input_len: *mut u32, pulled: *mut u32) -> c_int;
+    pub fn dspfx_spectrum_create(desc: *const dspfx_spectrum_desc, out: *mut *mut dspfx_spectrum) -> c_int;
+    pub fn dspfx_spectrum_destroy(p: *mut dspfx_spectrum) -> c_int;
+    pub fn dspfx_spectrum_push(p: *mut dspfx_spectrum, block: *const f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_spectrum_slot(p: *mut dspfx_spectrum) -> *mut f32;
+    pub fn dspfx_spectrum_column(p: *mut dspfx_spectrum, age: u32) -> *const f32;
+    pub fn dspfx_spectrum_reset(p: *mut dspfx_spectrum) -> c_int;
+    pub fn dspfx_spectrum_windows(p: *const dspfx_spectrum) -> i64;
+    pub fn dspfx_spectrum_plan(fft_size: u32, window_out: *mut f32, bin_hz_out: *mut f32) -> c_int;
 }

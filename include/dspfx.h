@@ -736,6 +736,77 @@ int dspfx_resample_reset(dspfx_resample *r);
 int dspfx_resample_plan(uint32_t target_hz, double *value, uint32_t *idx, uint32_t n_out, uint32_t *advance,
                         uint32_t *depth, double *coeff, uint32_t *input_len, uint32_t *pulled);
 
+/* ---- spectrogram bank ------------------------------------------------------------------------------------
+ * The Spectrogram node (nodes/spectrogram.rs:225-268) for N independent channels: one column of per-bin volumes per
+ * channel for every fft_size frames.  A separate object like the pitch and resampler banks; it is not a node kind.
+ * Per call, spectrogram.rs gathers exactly fft_size frames of its "in" port (collect_and_average), hands them to
+ * audioviz's Processor::compute_all(), pushes the column onto a queue that keeps the newest buffer_size columns, and
+ * releases fft_size frames.  So the windows are frames [n w, n (w + 1)), back to back, no overlap, and window w is due
+ * as soon as n (w + 1) frames have been pushed (the Pitch node needs one frame more; this node does not).
+ * What compute_all() does (audioviz 0.6.0 with apodize 1.0.0 and rustfft 6.2.0, Cargo.lock:465-474: not vendored, restated
+ * AS RECALLED, UNPINNED): a window function over the buffer, a forward complex FFT, the norm of the first n/2 outputs, a
+ * per-bin volume normalisation, a frequency label per bin and a bound on those labels.  The only sample-dependent step is
+ * |FFT(window * x)[k]|, k in [0, n/2); everything else is a factor or a label that depends on the bin index alone.  So the
+ * GPU computes
+ *       vol[k] = |FFT(window * x)[k]| * gain[k]        k in [0, n/2)
+ * in f32 (window product rounded once, magnitude sqrtf(re * re + im * im), then the gain product), and window[n] and
+ * gain[n/2] are TABLES THE HOST SUPPLIES: what is not pinned is confined to them, and a maintainer who has the crates can
+ * replace them without a new kernel.  The defaults:
+ *   window = NULL   the symmetric Hann window 0.5 - 0.5 cos(2 pi i / (n - 1)), f64 rounded once to f32 (apodize's
+ *                   hanning_iter as recalled); entries n - 1 - i repeat entries i < n/2, so it is symmetric bit for bit
+ *   gain = NULL     1.0 for every bin.  audioviz's VolumeNormalisation::Mixture curve is not restated here: a caller
+ *                   that wants it passes it as `gain`.
+ * Frequency bounds (lower_bound ..= upper_bound) are not the bank's business: a column always holds all n/2 bins, and
+ * the host maps a bound to a bin range with the physical bin frequency k * 48000 / n (dspfx_spectrum_plan).
+ * Layout: every block pushed is in the layout of the desc (channels / tile_channels as dspfx_engine_desc, the tiled form
+ * for a block of n_frames).  The window store is fft_size / 128 + 1 slots of 128 frames, each in that layout.  A column
+ * is a block of fft_size / 2 "frames" in the same layout: element (k, c), bin k of channel c, is frame k of channel c
+ * (frame-major: [k][N]).
+ * Memory: the bank allocates columns * (fft_size / 2) * channels * 4 bytes of history plus
+ * (fft_size / 128 + 1) * 128 * channels * 4 bytes of window store (250 columns of 256 bins at 2^20 channels are 268 GB:
+ * the caller chooses `columns`).  An allocation that fails is DSPFX_ERR_OOM, never an abort. */
+typedef struct dspfx_spectrum dspfx_spectrum;
+typedef struct dspfx_spectrum_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t channels;        /* N */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t fft_size;        /* n: a power of two, DSPFX_SPECTRUM_MIN_FFT ..= DSPFX_SPECTRUM_MAX_FFT (the node's default: 512) */
+    uint32_t columns;         /* history depth >= 1: the node's buffer_size (its default: 250) */
+    const float *window;      /* host, [fft_size], read at create and copied; NULL = the Hann window above */
+    const float *gain;        /* host, [fft_size / 2], read at create and copied; NULL = 1.0 */
+} dspfx_spectrum_desc;
+/* The node's slider range for fft_size (spectrogram.rs:142). */
+#define DSPFX_SPECTRUM_MIN_FFT 128
+#define DSPFX_SPECTRUM_MAX_FFT 8192
+/* fft_size outside the slider range, columns 0, no channels, a tile that is not a power of two dividing N: DSPFX_ERR_INVALID.
+ * fft_size inside the range but not a power of two: DSPFX_ERR_UNSUPPORTED (rustfft takes any length; this bank does
+ * not).  All of that is checked before any device work. */
+int dspfx_spectrum_create(const dspfx_spectrum_desc *desc, dspfx_spectrum **out);
+int dspfx_spectrum_destroy(dspfx_spectrum *p);
+/* Appends n_frames >= 1 frames (a device buffer in the desc's layout) and computes the column of every window that
+ * falls due, in order; asynchronous on `stream`, stream-ordered like the process calls.  When `block` is
+ * dspfx_spectrum_slot(p) and n_frames is 128, the samples are already in place and nothing is copied. */
+int dspfx_spectrum_push(dspfx_spectrum *p, const float *block, uint32_t n_frames, void *stream);
+/* The device address where the next 128 frames belong (a 128-frame block in the desc's layout), so that an engine can
+ * write its output there and push it without a copy; NULL while the frames pushed are not a multiple of 128.
+ * The slot may still be read by the column the previous push launched: a write into it must be stream-ordered after
+ * the previous dspfx_spectrum_push (the same stream, or one that waits for it). */
+float *dspfx_spectrum_slot(dspfx_spectrum *p);
+/* The device address of the column `age` windows back (0 = the newest), fft_size / 2 * channels floats in the layout
+ * above; NULL when that column does not exist yet or age >= columns.  The column of window w is overwritten by the push
+ * that completes window w + columns; a read must be stream-ordered after the push that launched it (the same stream,
+ * or one that waits for it) and done before that later push. */
+const float *dspfx_spectrum_column(dspfx_spectrum *p, uint32_t age);
+/* Back to the state after create: no samples, no columns; the tables stay. */
+int dspfx_spectrum_reset(dspfx_spectrum *p);
+/* Windows computed so far (since create or reset). */
+int64_t dspfx_spectrum_windows(const dspfx_spectrum *p);
+/* PURE HOST function (no GPU, no bank): the default window table, window_out[fft_size], and the physical frequency of
+ * every bin, bin_hz_out[fft_size / 2] = k * 48000 / fft_size (exact in f32).  Either may be NULL.  The same size rules
+ * as dspfx_spectrum_create.  A host that wants a scaled Hann window scales this table and passes it as `window`. */
+int dspfx_spectrum_plan(uint32_t fft_size, float *window_out, float *bin_hz_out);
+
 #ifdef __cplusplus
 }
 #endif

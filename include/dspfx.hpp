@@ -366,6 +366,51 @@ class Resampler {
     dspfx_resample *r_ = nullptr;
 };
 
+// The Spectrogram node (nodes/spectrogram.rs) for N channels (include/dspfx.h, dspfx_spectrum_*): device blocks in the layout of
+// tile_channels; every fft_size frames one column vol[k] = |FFT(window * x)[k]| * gain[k], k < fft_size / 2, per channel, the
+// newest `columns` kept on the device.  window / gain: host tables copied at construction, nullptr = Hann / 1.0.
+class SpectrumBank {
+  public:
+    explicit SpectrumBank(std::uint32_t channels, std::uint32_t fft_size = 512, std::uint32_t columns = 1, int device = 0,
+                          std::uint32_t tile_channels = 0, const float *window = nullptr, const float *gain = nullptr) {
+        const dspfx_spectrum_desc d{DSPFX_ABI_VERSION, device, channels, tile_channels, fft_size, columns, window, gain};
+        chk(dspfx_spectrum_create(&d, &p_));
+    }
+    ~SpectrumBank() { dspfx_spectrum_destroy(p_); }
+    SpectrumBank(const SpectrumBank &) = delete;
+    SpectrumBank &operator=(const SpectrumBank &) = delete;
+    // device block of n_frames; asynchronous on `stream`.  push(slot(), 128) copies nothing.
+    void push(const float *block, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_spectrum_push(p_, block, n_frames, stream)); }
+    float *slot() { return dspfx_spectrum_slot(p_); }
+    // the device column `age` windows back (fft_size / 2 frames of N channels in the bank's layout), nullptr when there is none
+    const float *column(std::uint32_t age = 0) { return dspfx_spectrum_column(p_, age); }
+    void reset() { chk(dspfx_spectrum_reset(p_)); }
+    std::int64_t windows() const { return dspfx_spectrum_windows(p_); }
+    dspfx_spectrum *raw() { return p_; }
+
+  private:
+    static void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    }
+    dspfx_spectrum *p_ = nullptr;
+};
+
+// The default window table and the bin frequencies k * 48000 / fft_size (dspfx_spectrum_plan: a pure host function, no GPU).
+struct SpectrumPlan {
+    std::vector<float> window;                    // [fft_size]
+    std::vector<float> bin_hz;                    // [fft_size / 2]
+};
+inline SpectrumPlan spectrum_plan(std::uint32_t fft_size) {
+    SpectrumPlan p;
+    if (fft_size <= DSPFX_SPECTRUM_MAX_FFT) {
+        p.window.resize(fft_size);
+        p.bin_hz.resize(fft_size / 2);
+    }
+    const int rc = dspfx_spectrum_plan(fft_size, p.window.data(), p.bin_hz.data());
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    return p;
+}
+
 // The converter's plan for the next n_out output frames (dspfx_resample_plan: a pure host function, no GPU).
 struct ResamplePlan {
     std::vector<std::uint32_t> advance, depth;
