@@ -71,6 +71,8 @@ EXPORTS = [
     "dspfx_resample_available", "dspfx_resample_skip", "dspfx_resample_reset", "dspfx_resample_plan",
     "dspfx_spectrum_create", "dspfx_spectrum_destroy", "dspfx_spectrum_push", "dspfx_spectrum_slot", "dspfx_spectrum_column",
     "dspfx_spectrum_reset", "dspfx_spectrum_windows", "dspfx_spectrum_plan",
+    "dspfx_mixgroups_create", "dspfx_mixgroups_destroy", "dspfx_mixgroups_last_error", "dspfx_mixgroups_run",
+    "dspfx_mixgroups_set_gains", "dspfx_mixgroups_plan",
 ]
 COMM_ID_BYTES = 128
 
@@ -119,6 +121,12 @@ class _ResampleDesc(C.Structure):
 class _SpectrumDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
                 ("fft_size", C.c_uint32), ("columns", C.c_uint32), ("window", C.POINTER(C.c_float)), ("gain", C.POINTER(C.c_float))]
+
+
+class _MixGroupsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("n_groups", C.c_uint32), ("normalise", C.c_uint32),
+                ("group_start", C.POINTER(C.c_uint64))]
 
 
 class _Ctl(C.Structure):
@@ -251,6 +259,13 @@ def lib():
     L.dspfx_spectrum_windows.restype = C.c_int64
     L.dspfx_spectrum_windows.argtypes = [vp]
     L.dspfx_spectrum_plan.argtypes = [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.dspfx_mixgroups_create.argtypes = [C.POINTER(_MixGroupsDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_mixgroups_destroy.argtypes = [vp]
+    L.dspfx_mixgroups_last_error.restype = C.c_char_p
+    L.dspfx_mixgroups_last_error.argtypes = [vp]
+    L.dspfx_mixgroups_run.argtypes = [vp, f32p, C.c_uint32, f32p, vp]
+    L.dspfx_mixgroups_set_gains.argtypes = [vp, C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
+    L.dspfx_mixgroups_plan.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -1103,6 +1118,95 @@ class SpectrumBank:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.L.dspfx_spectrum_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _group_table(channels: int, group_start=None, group_size=None) -> np.ndarray:
+    if (group_start is None) == (group_size is None):
+        raise ValueError("give group_start (G + 1 channel indices) or group_size (uniform groups), one of them")
+    if group_size is not None:
+        if int(group_size) < 1 or channels % int(group_size):
+            raise ValueError(f"group_size {group_size} does not divide {channels} channels")
+        return np.arange(0, channels + 1, int(group_size), dtype=np.uint64)
+    t = np.ascontiguousarray(group_start, dtype=np.uint64)
+    if t.ndim != 1 or len(t) < 2:
+        raise ValueError("group_start holds G + 1 >= 2 channel indices")
+    return t
+
+
+def mixgroups_plan(channels: int, group_start=None, group_size=None, tile_channels: int = 0) -> np.ndarray:
+    """dspfx_mixgroups_plan, a pure host function (no GPU): checks the table (DspfxError with the reason when it is bad) and
+    -> depth uint32[G]: per group the longest chain of dependent f32 additions in its sum."""
+    L = lib()
+    t = _group_table(int(channels), group_start, group_size)
+    depth = np.zeros(len(t) - 1, np.uint32)
+    rc = L.dspfx_mixgroups_plan(t.ctypes.data_as(C.POINTER(C.c_uint64)), len(t) - 1, int(channels), int(tile_channels),
+                                depth.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_mixgroups_last_error(None).decode() or L.dspfx_strerror(rc).decode())
+    return depth
+
+
+class MixGroups:
+    """One Output bus per contiguous channel range, with a per-channel fader (include/dspfx.h, dspfx_mixgroups_*):
+    buses[f][g] = (sum over group g of fl32(x[f][c] * gain[c])) / link_divisor(n_g) for a device block in the layout of
+    `tile_channels` (as Engine's).  group_start: G + 1 channel indices, nondecreasing from 0 to N; or group_size for uniform
+    groups.  normalise=False leaves the raw sums.  run() returns [n_frames, G] float32 on the device: the frame-major block of a
+    G-channel Engine(G, tile_channels=0), Resampler(G, ..), PitchBank(G) or SpectrumBank(G).  Asynchronous on `stream`."""
+
+    def __init__(self, channels: int, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE,
+                 normalise: bool = True, device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.max_frames, self.normalise = int(max_frames), bool(normalise)
+        self.group_start = _group_table(self.channels, group_start, group_size)
+        self.groups = len(self.group_start) - 1
+        self.h = C.c_void_p()
+        d = _MixGroupsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
+                           self.groups, int(self.normalise), self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
+        rc = self.L.dspfx_mixgroups_create(C.byref(d), C.byref(self.h))        # the table is copied before this returns
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_mixgroups_last_error(None).decode() or self.L.dspfx_strerror(rc).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_mixgroups_last_error(self.h).decode() or self.L.dspfx_strerror(rc).decode())
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """The buses of one device block -> `out` [n_frames, G] float32 on the device (made when not given)."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty((int(n_frames), self.groups), dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_mixgroups_run(self.h, _ptr(block), int(n_frames), _ptr(out), C.c_void_p(stream) if stream else None))
+        return out
+
+    def set_gains(self, values, first_channel: int = 0, count: Optional[int] = None):
+        """Store the faders of channels [first_channel, first_channel + len(values)); values=None drops the faders of `count`
+        channels (default: all from first_channel) back to "not multiplied".  Any thread; applies to the runs submitted after it."""
+        if values is None:
+            n = self.channels - int(first_channel) if count is None else int(count)
+            self._chk(self.L.dspfx_mixgroups_set_gains(self.h, None, int(first_channel), n))
+            return
+        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        self._chk(self.L.dspfx_mixgroups_set_gains(self.h, v.ctypes.data_as(C.POINTER(C.c_float)), int(first_channel), len(v)))
+
+    def depth(self) -> np.ndarray:
+        """mixgroups_plan for this bank's table."""
+        return mixgroups_plan(self.channels, group_start=self.group_start, tile_channels=self.tile_channels)
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_mixgroups_destroy(h)
             h.value = None
 
     def __del__(self):

@@ -124,6 +124,26 @@ pub struct dspfx_spectrum_desc {
     pub gain: *const f32,
 }
 
+/// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
+#[repr(C)]
+pub struct dspfx_mixgroups {
+    _private: [u8; 0],
+}
+
+/// The mix-group bank's descriptor (`dspfx_mixgroups_create`); `group_start` is a host table of `n_groups + 1` entries read at create.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_mixgroups_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub n_groups: u32,
+    pub normalise: u32,
+    pub group_start: *const u64,
+}
+
 /// The Pitch Detector bank's descriptor (`dspfx_pitch_create`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -325,4 +345,10 @@ extern "C" {
     pub fn dspfx_spectrum_reset(p: *mut dspfx_spectrum) -> c_int;
     pub fn dspfx_spectrum_windows(p: *const dspfx_spectrum) -> i64;
     pub fn dspfx_spectrum_plan(fft_size: u32, window_out: *mut f32, bin_hz_out: *mut f32) -> c_int;
+    pub fn dspfx_mixgroups_create(desc: *const dspfx_mixgroups_desc, out: *mut *mut dspfx_mixgroups) -> c_int;
+    pub fn dspfx_mixgroups_destroy(m: *mut dspfx_mixgroups) -> c_int;
+    pub fn dspfx_mixgroups_last_error(m: *const dspfx_mixgroups) -> *const c_char;
+    pub fn dspfx_mixgroups_run(m: *mut dspfx_mixgroups, block: *const f32, n_frames: u32, buses: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_mixgroups_set_gains(m: *mut dspfx_mixgroups, host_values: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixgroups_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, depth_out: *mut u32) -> c_int;
 }

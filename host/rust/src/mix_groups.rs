@@ -1,0 +1,95 @@
+//! `MixGroups`: one Output bus per contiguous channel range of a bank, with a per-channel fader (`dspfx_mixgroups_*`).
+//!
+//! The reference allows any number of Output nodes, each averaging the pipes wired to it (nodes/output.rs:215-249 feeding
+//! collect_and_average, node.rs:162-194).  A host with R rooms of channels in one `GpuBank` binds one `MixGroups` over the bank's
+//! DEVICE output block: `buses[f][g] = (sum over room g of x[f][c] * gain[c]) / f32(0.0001 + n_g)`, `[n_frames][G]` on the
+//! device -- the frame-major block of a G-channel `Engine` (the master-bus chain), `Resampler`, `PitchBank` or `SpectrumBank`.
+//! The GUI thread stores faders through `set_gains`, which never waits for the device: the next `run` applies them in order.
+//! NOT compiled in the build container (no rustc).
+use super::engine::Error;
+use super::ffi::*;
+use std::ffi::CStr;
+use std::os::raw::{c_int, c_void};
+use std::ptr;
+
+pub struct MixGroups {
+    h: *mut dspfx_mixgroups,
+    channels: u32,
+    groups: u32,
+}
+unsafe impl Send for MixGroups {}
+// runs are serialised by the bank's own lock; fader stores only take the store queue's
+unsafe impl Sync for MixGroups {}
+
+fn reason(h: *const dspfx_mixgroups, what: &str) -> String {
+    let msg = unsafe { CStr::from_ptr(dspfx_mixgroups_last_error(h)) }.to_string_lossy().into_owned();
+    if msg.is_empty() { what.into() } else { msg }
+}
+
+impl MixGroups {
+    /// `group_start`: G + 1 channel indices, nondecreasing, from 0 to `channels`; `tile_channels`: 0 (frame-major) or the engine's W;
+    /// `normalise = false` leaves the raw sums (a group split over ranks).
+    pub fn new(device: i32, channels: u32, tile_channels: u32, max_frames: u32, group_start: &[u64], normalise: bool) -> Result<Self, Error> {
+        if group_start.len() < 2 {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "MixGroups: group_start holds G + 1 entries".into() });
+        }
+        let groups = (group_start.len() - 1) as u32;
+        let desc = dspfx_mixgroups_desc {
+            abi_version: DSPFX_ABI_VERSION,
+            device,
+            n_channels: channels,
+            max_frames,
+            tile_channels,
+            n_groups: groups,
+            normalise: normalise as u32,
+            group_start: group_start.as_ptr(),
+        };
+        let mut h = ptr::null_mut();
+        let rc = unsafe { dspfx_mixgroups_create(&desc, &mut h) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixgroups_create") });
+        }
+        Ok(MixGroups { h, channels, groups })
+    }
+    fn check(&self, rc: c_int, what: &str) -> Result<(), Error> {
+        if rc == DSPFX_OK { Ok(()) } else { Err(Error { status: rc, message: reason(self.h, what) }) }
+    }
+    pub fn channels(&self) -> u32 { self.channels }
+    pub fn groups(&self) -> u32 { self.groups }
+    /// The buses of a DEVICE block of `n_frames` frames in the bank's layout into the DEVICE array `buses`, `[n_frames][G]`.
+    /// Asynchronous on `stream`.
+    pub unsafe fn run(&self, block: *const f32, n_frames: u32, buses: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+        let rc = dspfx_mixgroups_run(self.h, block, n_frames, buses, stream);
+        self.check(rc, "dspfx_mixgroups_run")
+    }
+    /// Stores the faders of channels `first_channel ..` (any thread, never waits for the device); they govern the runs submitted later.
+    pub fn set_gains(&self, values: &[f32], first_channel: u64) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixgroups_set_gains(self.h, values.as_ptr(), first_channel, values.len() as u64) };
+        self.check(rc, "dspfx_mixgroups_set_gains")
+    }
+    /// Drops the faders of `count` channels from `first_channel`: back to "not multiplied".
+    pub fn clear_gains(&self, first_channel: u64, count: u64) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixgroups_set_gains(self.h, ptr::null(), first_channel, count) };
+        self.check(rc, "dspfx_mixgroups_set_gains")
+    }
+    /// Checks a table and gives, per group, the longest chain of dependent f32 additions in its sum (a pure host function).
+    pub fn plan(group_start: &[u64], channels: u64, tile_channels: u32) -> Result<Vec<u32>, Error> {
+        if group_start.len() < 2 {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "dspfx_mixgroups_plan".into() });
+        }
+        let mut depth = vec![0u32; group_start.len() - 1];
+        let rc = unsafe { dspfx_mixgroups_plan(group_start.as_ptr(), depth.len() as u32, channels, tile_channels, depth.as_mut_ptr()) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixgroups_plan") });
+        }
+        Ok(depth)
+    }
+}
+
+impl Drop for MixGroups {
+    fn drop(&mut self) {
+        unsafe {
+            dspfx_mixgroups_destroy(self.h);
+        }
+    }
+}

@@ -3,3 +3,4 @@ pub mod engine;
 pub mod ffi;
 pub mod gpu_bank;
 pub mod gpu_chain;
+pub mod mix_groups;

@@ -807,6 +807,63 @@ int64_t dspfx_spectrum_windows(const dspfx_spectrum *p);
  * as dspfx_spectrum_create.  A host that wants a scaled Hann window scales this table and passes it as `window`. */
 int dspfx_spectrum_plan(uint32_t fft_size, float *window_out, float *bin_hz_out);
 
+/* ---- mix groups: one Output bus per channel range ---------------------------------------------------------
+ * The reference allows any number of Output nodes, each averaging only the pipes wired to it (nodes/output.rs:215-249
+ * feeding collect_and_average, node.rs:162-194); the engine's own mix bus is ONE sum over all its channels.  This bank
+ * gives a host with many rooms of channels one bus per room, and every channel its own level in its room's mix: a table of
+ * G contiguous channel ranges ("groups") and an optional per-channel fader, over a device block in the engine's sample
+ * layout (channels / tile_channels as dspfx_engine_desc, the tiled form for a block of n_frames):
+ *       buses[f][g] = (sum over the channels c of group g of fl32(x[f][c] * gain[c])) / dspfx_link_divisor(n_g)
+ * n_g = the group's channel count.  The product is one f32 multiply, never contracted into the add: a Gain node in front
+ * of the Output node, x * level (gain.rs:25-38); a channel without a stored fader is not multiplied.  The division is an
+ * IEEE f32 division; normalise = 0 leaves the raw sums (a host that splits a group over ranks exchanges those and divides
+ * itself).  An empty group gives +0.0.  A separate object like the other banks; it reads the block once and changes nothing.
+ * `buses` is [n_frames][G] f32 on the device: the frame-major layout of a G-channel engine, so it can go straight into a second
+ * engine of G channels (tile_channels = 0) as a master-bus chain, or into a resampler, pitch or spectrogram bank of G channels.
+ * Summation order: fixed, and for one group a function of the group's first channel and length (and the layout) alone -- the
+ * bus of a group is the same bits whatever the rest of the table looks like, from run to run and on any stream; no atomics.
+ * Channels are cut into spans of 256 from channel 0.  A span wholly inside the group: a lane adds four adjacent channels
+ * (x0 + x1) + (x2 + x3), the 64 lanes are added pairwise across lane bits 32, 16, 8, 4, 2, 1.  A span the group shares: per
+ * 64 channels a segmented scan with steps 1, 2, .. 32, carried from one 64 to the next.  The spans' sums are added 64 at a
+ * time: four rows of up to 16 one after the other, then (r0 + r1) + (r2 + r3); more than 64 take further rounds of the same.
+ * The longest chain of dependent additions D(n) this makes for a group of n channels is at most 64 + ceil(log2(max(n, 1)))
+ * (47 at 2^24 channels); dspfx_mixgroups_plan reports it per group.  Not the reference's order (sequential): within
+ * (D + 1) 2^-24 sum|terms| / divisor of the exact sum. */
+typedef struct dspfx_mixgroups dspfx_mixgroups;
+typedef struct dspfx_mixgroups_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t n_groups;        /* G >= 1 */
+    uint32_t normalise;       /* 1: divide by the link divisor of the group's channel count; 0: the raw sums */
+    const uint64_t *group_start; /* host, [n_groups + 1], read at create and copied: group g is channels [group_start[g],
+                                 group_start[g + 1]); nondecreasing, [0] = 0, [G] = N; boundaries need not align with anything */
+} dspfx_mixgroups_desc;
+/* A bad descriptor or table is DSPFX_ERR_INVALID with the reason in dspfx_mixgroups_last_error of a NULL bank (kept per
+ * thread); all of that is checked before any device work. */
+int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mixgroups **out);
+int dspfx_mixgroups_destroy(dspfx_mixgroups *m);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_mixgroups_last_error(const dspfx_mixgroups *m);
+/* block: device, n_frames frames in the desc's layout (1 <= n_frames <= max_frames); buses: device, [n_frames][G] f32.
+ * Asynchronous on `stream`; a run on another stream than the one before first waits (on the device) for that one, since the
+ * partial sums are the bank's. */
+int dspfx_mixgroups_run(dspfx_mixgroups *m, const float *block, uint32_t n_frames, float *buses, void *stream);
+/* Stores the faders of channels [first_channel, first_channel + count) from a host array; host_values = NULL drops them for
+ * that range: back to "not multiplied".  Callable from any thread while runs are in flight, and never waits for the device or
+ * for a run: the values are copied into a page-locked staging buffer and queued; the next run puts the queued stores on its
+ * stream ahead of its kernels, in the order they were made.  So a run submitted after the call returns sees the new values,
+ * and the runs submitted before it see the old ones. */
+int dspfx_mixgroups_set_gains(dspfx_mixgroups *m, const float *host_values, uint64_t first_channel, uint64_t count);
+/* PURE HOST function (no GPU, no bank): checks a table as create does (DSPFX_ERR_INVALID and the reason for a table that
+ * decreases, does not start at 0 or end at n_channels, or a tile that is not a power of two dividing n_channels) and gives,
+ * per group, depth_out[g] = D: the longest chain of dependent f32 additions in the group's sum (an upper bound that counts
+ * every addition the kernels make on the path).  depth_out may be NULL. */
+int dspfx_mixgroups_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
+                         uint32_t *depth_out);
+
 #ifdef __cplusplus
 }
 #endif

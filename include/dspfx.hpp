@@ -427,4 +427,48 @@ inline ResamplePlan resample_plan(std::uint32_t target_hz, double &value, std::u
     return p;
 }
 
+// One Output bus per contiguous channel range, with a per-channel fader (include/dspfx.h, dspfx_mixgroups_*):
+// buses[f][g] = (sum over group g of fl32(x[f][c] * gain[c])) / link_divisor(n_g) for a device block in the layout of
+// tile_channels.  group_start: G + 1 channel indices, nondecreasing from 0 to N (copied).  The buses, [n_frames][G] on the device,
+// are the frame-major block of a G-channel Engine, Resampler, PitchBank or SpectrumBank.
+class MixGroups {
+  public:
+    MixGroups(std::uint32_t channels, const std::vector<std::uint64_t> &group_start, std::uint32_t tile_channels = 0,
+              std::uint32_t max_frames = DSPFX_BUF_SIZE, bool normalise = true, int device = 0)
+        : groups_(group_start.empty() ? 0 : (std::uint32_t)group_start.size() - 1) {
+        const dspfx_mixgroups_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, groups_, normalise ? 1u : 0u,
+                                     group_start.data()};
+        const int rc = dspfx_mixgroups_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_mixgroups_last_error(nullptr) ? dspfx_mixgroups_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~MixGroups() { dspfx_mixgroups_destroy(p_); }
+    MixGroups(const MixGroups &) = delete;
+    MixGroups &operator=(const MixGroups &) = delete;
+    std::uint32_t groups() const { return groups_; }
+    // device block of n_frames -> device buses [n_frames][G]; asynchronous on `stream`
+    void run(const float *block, std::uint32_t n_frames, float *buses, void *stream = nullptr) { chk(dspfx_mixgroups_run(p_, block, n_frames, buses, stream)); }
+    // faders of channels [first_channel, first_channel + count) from a host array; nullptr drops them.  Any thread; never waits.
+    void set_gains(const float *host_values, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_mixgroups_set_gains(p_, host_values, first_channel, count));
+    }
+    dspfx_mixgroups *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_mixgroups_last_error(p_) ? dspfx_mixgroups_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_mixgroups *p_ = nullptr;
+    std::uint32_t groups_;
+};
+
+// Checks a group table and gives, per group, the longest chain of dependent f32 additions in its sum (dspfx_mixgroups_plan: a
+// pure host function, no GPU).
+inline std::vector<std::uint32_t> mixgroups_plan(const std::vector<std::uint64_t> &group_start, std::uint64_t channels,
+                                                 std::uint32_t tile_channels = 0) {
+    std::vector<std::uint32_t> depth(group_start.empty() ? 0 : group_start.size() - 1);
+    const int rc = dspfx_mixgroups_plan(group_start.data(), (std::uint32_t)depth.size(), channels, tile_channels, depth.data());
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixgroups_last_error(nullptr));
+    return depth;
+}
+
 }  // namespace dspfx
