@@ -12,6 +12,16 @@ import numpy as np
 F = np.float32
 BUF_SIZE = 128  # dsp-stuff/src/node.rs:257
 
+# The reference's f32 math-library calls (Rust's f32::tanh / sin / atan / exp / powf go to the platform's libm).  By default
+# numpy's own float32 routines -- and, where this model always took the correctly rounded value, float64 rounded once
+# ("sin_cr", "powf").  A test that wants to compare everything AROUND these calls bit for bit with the C oracle swaps in the
+# platform's routines here (tests/test_edge_values_cpu.py).
+LIBM = {
+    "tanh": np.tanh, "sin": np.sin, "atan": np.arctan, "exp": np.exp,
+    "sin_cr": lambda v: np.sin(np.asarray(v, F).astype(np.float64)).astype(F),
+    "powf": lambda base, x: F(np.power(np.float64(base), np.float64(x))),
+}
+
 
 def link_scale(x):
     """node.rs:162-194 with ONE connected pipe: (0 + x) / f32(0.0001 + 1)."""
@@ -128,7 +138,7 @@ def distort(x, level, mode):
                          np.where((s >= F(-1)) & (s <= F(1)), mid, F(-2.0) / F(3.0))).astype(F)
             return (_clip(t) / L).astype(F)
         if mode == 2:
-            return np.tanh((x * L).astype(F)).astype(F)
+            return LIBM["tanh"]((x * L).astype(F)).astype(F)
         if mode == 3:
             den = ((np.abs(x) * L).astype(F) + F(1)).astype(F)
             return (_signum(x) * (F(1) - (F(1) / den).astype(F)).astype(F)).astype(F)
@@ -136,15 +146,15 @@ def distort(x, level, mode):
             lv = np.full(len(x), L, F)
             mx = np.abs(x).max() if not np.isnan(x).any() else F(np.nan)
             q = (_clip(x * lv) / mx).astype(F)
-            z = (-np.abs(F(1) - np.exp(-np.abs(q)).astype(F))).astype(F)
+            z = (-np.abs(F(1) - LIBM["exp"](-np.abs(q)).astype(F))).astype(F)
             mz = np.abs(z).max() if not np.isnan(z).any() else F(np.nan)
             y = (_clip((z * mx).astype(F)) / mz).astype(F)
             my = np.abs(y).max() if not np.isnan(y).any() else F(np.nan)
             return ((y * mx).astype(F) / my).astype(F)
         if mode == 5:
-            return np.sin((x * L).astype(F)).astype(F)
+            return LIBM["sin"]((x * L).astype(F)).astype(F)
         if mode == 6:
-            return np.arctan((x * L).astype(F)).astype(F)
+            return LIBM["atan"]((x * L).astype(F)).astype(F)
         if mode == 7:
             v = (x * L).astype(F)
             return ((v * v).astype(F) * _signum(v)).astype(F)
@@ -163,7 +173,7 @@ def overdrive(x, boost, drive, level):
         return x.copy()
     a = (x * F(boost)).astype(F)
     b = (F(np.pi / 4) * a).astype(F)
-    c = np.arctan(b).astype(F)
+    c = LIBM["atan"](b).astype(F)
     d = (F(2 / np.pi) * c).astype(F)
     mix = ((F(drive) * d).astype(F) + (F(F(1) - F(drive)) * x).astype(F)).astype(F)
     return (mix * F(level)).astype(F)
@@ -176,10 +186,10 @@ def chebyshev(x, level_pos, level_neg):
     lp, ln = F(level_pos), F(level_neg)
     pos = x >= F(0)
     if lp >= F(0.001):
-        out[pos] = (np.tanh((x[pos] * lp).astype(F)).astype(F) / np.tanh(lp)).astype(F)
+        out[pos] = (LIBM["tanh"]((x[pos] * lp).astype(F)).astype(F) / LIBM["tanh"](lp)).astype(F)
     neg = ~pos
     if ln >= F(0.001):
-        out[neg] = (np.tanh((x[neg] * ln).astype(F)).astype(F) / np.tanh(ln)).astype(F)
+        out[neg] = (LIBM["tanh"]((x[neg] * ln).astype(F)).astype(F) / LIBM["tanh"](ln)).astype(F)
     return out
 
 
@@ -299,7 +309,7 @@ class SignalGen:
             total[i] = acc
         ph = (self.clock + total).astype(F)
         if self.mode == 0:
-            out = (np.sin((ph * self.TAU).astype(F).astype(np.float64)).astype(F) * amp).astype(F)
+            out = (LIBM["sin_cr"]((ph * self.TAU).astype(F)) * amp).astype(F)
         elif self.mode == 1:
             out = ((F(2.0) * np.fmod(ph, F(1.0)).astype(F) - F(1.0)).astype(F) * amp).astype(F)
         else:
@@ -324,7 +334,7 @@ class Envelope:
         if n == F(0):
             return F(0.0)
         # powf(e_f32, x): evaluated in float64 and rounded once (glibc powf is within 1 ulp of that)
-        return F(np.power(np.float64(cls.E), np.float64(F(-1.0) / n)))
+        return F(LIBM["powf"](cls.E, F(-1.0) / n))
 
     def process(self, x):
         x = np.asarray(x, F)
@@ -373,7 +383,7 @@ def distort_per_sample(x, level, mode):
                 return F(np.nan) if np.isnan(v).any() else np.abs(v).max()       # max_by(total_cmp): NaN is largest
             mx = amax(x)
             q = (_clip((x * level).astype(F)) / mx).astype(F)
-            z = (-np.abs(F(1) - np.exp(-np.abs(q)).astype(F))).astype(F)
+            z = (-np.abs(F(1) - LIBM["exp"](-np.abs(q)).astype(F))).astype(F)
             mz = amax(z)
             y = (_clip((z * mx).astype(F)) / mz).astype(F)
             my = amax(y)
@@ -457,7 +467,7 @@ class NodeModel:
             if k == K_OVERDRIVE:                                  # overdrive.rs:58-72 (helpers in field order)
                 boost, drive, level = self._slider(0, ctl, n), self._slider(1, ctl, n), self._slider(2, ctl, n)
                 t = (F(np.pi / 4) * (a * boost).astype(F)).astype(F)
-                d = (F(2 / np.pi) * np.arctan(t).astype(F)).astype(F)
+                d = (F(2 / np.pi) * LIBM["atan"](t).astype(F)).astype(F)
                 m = ((drive * d).astype(F) + ((F(1) - drive).astype(F) * a).astype(F)).astype(F)
                 return np.where(level < F(0.001), a, (m * level).astype(F)).astype(F)
             if k == K_CHEBYSHEV:
