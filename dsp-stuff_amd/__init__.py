@@ -72,7 +72,7 @@ EXPORTS = [
     "dspfx_spectrum_create", "dspfx_spectrum_destroy", "dspfx_spectrum_push", "dspfx_spectrum_slot", "dspfx_spectrum_column",
     "dspfx_spectrum_reset", "dspfx_spectrum_windows", "dspfx_spectrum_plan",
     "dspfx_mixgroups_create", "dspfx_mixgroups_destroy", "dspfx_mixgroups_last_error", "dspfx_mixgroups_run",
-    "dspfx_mixgroups_set_gains", "dspfx_mixgroups_plan",
+    "dspfx_mixgroups_set_gains", "dspfx_mixgroups_plan", "dspfx_mixgroups_returns",
 ]
 COMM_ID_BYTES = 128
 
@@ -264,6 +264,7 @@ def lib():
     L.dspfx_mixgroups_last_error.restype = C.c_char_p
     L.dspfx_mixgroups_last_error.argtypes = [vp]
     L.dspfx_mixgroups_run.argtypes = [vp, f32p, C.c_uint32, f32p, vp]
+    L.dspfx_mixgroups_returns.argtypes = [vp, f32p, C.c_uint32, f32p, f32p, vp]
     L.dspfx_mixgroups_set_gains.argtypes = [vp, C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
     L.dspfx_mixgroups_plan.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]
     _lib = L
@@ -1187,6 +1188,19 @@ class MixGroups:
         if out is None:
             out = torch.empty((int(n_frames), self.groups), dtype=torch.float32, device=torch.device("cuda", self.device))
         self._chk(self.L.dspfx_mixgroups_run(self.h, _ptr(block), int(n_frames), _ptr(out), C.c_void_p(stream) if stream else None))
+        return out
+
+    def returns(self, block, n_frames: Optional[int] = None, out=None, buses=None, stream: int = 0):
+        """Every channel's room minus itself: out[f][c] = (S[f][g] - x[f][c] * gain[c]) / link_divisor(n_g - 1), S the group's raw
+        sum, +0.0 in a group of one; -> `out`, a device block in the layout of `block` (made when not given; out=block works in
+        place).  `buses` [n_frames, G], when given, receives what run() writes: the sums are paid for once."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_mixgroups_returns(self.h, _ptr(block), int(n_frames), _ptr(buses) if buses is not None else None,
+                                                 _ptr(out), C.c_void_p(stream) if stream else None))
         return out
 
     def set_gains(self, values, first_channel: int = 0, count: Optional[int] = None):

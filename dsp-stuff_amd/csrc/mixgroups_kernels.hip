@@ -18,6 +18,16 @@
 //             level of the same over the results.  The last level divides (IEEE) and writes the bus.
 // Which additions make a group's sum follows from the group's own first channel and length (and the layout) alone: no atomics,
 // nothing depends on the order waves run in or on the other groups.  dspfx_mixgroups_plan gives the depth of that tree.
+//
+// Per-channel returns (dspfx_mixgroups_returns): returns[f][c] = fl32(fl32(S[f][g] - t[f][c]) / link_divisor(n_g - 1)), every
+// channel hears its room minus itself.  The two kernels above, unchanged, are pointed at divisor tables of 1.0 and at the bank's
+// own [max_frames][G] buffer, which so holds the raw sums S; then
+//   divide    (only when the caller wants the buses too) buses = S / link_divisor(n_g), what `run` writes, the block not re-read;
+//   returns   one streaming pass, one wave per (span, chunk of 16 frames), a lane takes four adjacent channels with one 16-byte
+//             load and one 16-byte store per frame.  A span inside one group takes the group from a per-span table (sfirst, built
+//             when the first returns call is made) and S[f][g] is one wave-uniform load; a cut span looks its channels' groups up
+//             once per wave, between the first group of this span and the first group of the next, and gathers S per frame.
+//             A lane rewrites the elements it read, so returns may be the block itself.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -222,6 +232,128 @@ __global__ __launch_bounds__(RW * 64) void mixgroups_reduce(const Task *__restri
     else next[(size_t)t.dst * FS + f] = tot;
 }
 
+// ---- per-channel returns ---------------------------------------------------------------------------------------------------
+constexpr int RCHUNK = 16;                         // frames per wave of the returns kernel
+constexpr int RBATCH = 8;                          // ... of which so many are loaded before the first is written
+
+struct RetArgs {
+    const float *x;              // may be `out`: no __restrict__
+    float *out;
+    const float *gain;           // [N]
+    const float *S;              // [nf][G] raw sums
+    const uint32_t *gstart;      // [G + 1]
+    const float *rdiv;           // [G]: link_divisor(n_g - 1) (1.0 without normalise); 0.0 marks a group of one channel
+    const uint32_t *sfirst;      // [nspans + 1]: the group of the span's first channel; [nspans] = G - 1
+    const uint8_t *slow;         // [nspans]
+    uint32_t N, Wrow, nf, G, nspans, nchunks, norm;
+};
+
+// fl32(fl32(S - t) / div); div == 0 marks a group of one: no other pipe, +0.0 whatever the sample is
+__device__ __forceinline__ float mix_minus(float S, float x, float g, float div, bool gain, bool norm) {
+    const float t = gain ? __fmul_rn(x, g) : x;
+    const float d = __fsub_rn(S, t);
+    const float q = norm ? __fdiv_rn(d, div) : d;
+    return div == 0.0f ? 0.0f : q;
+}
+
+template <bool GAIN, bool VEC, bool CUT>
+__device__ __forceinline__ void returns_span(const RetArgs &a, uint32_t k, uint32_t f0, uint32_t lane) {
+    const uint32_t ch = k * SPAN + 4 * lane;
+    if (ch >= a.N) return;
+    uint32_t gi[4];
+    float dv[4], gn[4];
+    bool valid[4];
+    size_t b[4];
+    uint32_t lo = a.sfirst[k];
+    const uint32_t hi = a.sfirst[k + 1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t c = ch + i;
+        valid[i] = c < a.N;
+        if (CUT && valid[i]) {
+            // the first m in (lo, hi + 1] with gstart[m] > c: gstart[lo] <= c, and gstart[hi + 1] is past this span
+            uint32_t i0 = lo + 1, i1 = hi + 1;
+            while (i0 < i1) {
+                const uint32_t m = (i0 + i1) / 2;
+                if (a.gstart[m] > c) i1 = m;
+                else i0 = m + 1;
+            }
+            lo = i0 - 1;
+        }
+        gi[i] = lo;
+        dv[i] = a.rdiv[lo];
+        gn[i] = (GAIN && valid[i]) ? a.gain[c] : 1.0f;
+        b[i] = (valid[i] && (i == 0 || !VEC)) ? chan_base(c, a.Wrow, a.nf) : 0;
+    }
+    const bool norm = a.norm != 0;
+#pragma unroll
+    for (int i0 = 0; i0 < RCHUNK; i0 += RBATCH) {
+        float4 v[RBATCH], s[RBATCH];
+#pragma unroll
+        for (int j = 0; j < RBATCH; ++j) {
+            const uint32_t f = f0 + i0 + j;
+            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            s[j] = v[j];
+            if (f < a.nf) {
+                const size_t o = (size_t)f * a.Wrow;
+                if (VEC) {
+                    v[j] = *(const float4 *)(a.x + b[0] + o);
+                } else {
+                    v[j].x = a.x[b[0] + o];
+                    if (valid[1]) v[j].y = a.x[b[1] + o];
+                    if (valid[2]) v[j].z = a.x[b[2] + o];
+                    if (valid[3]) v[j].w = a.x[b[3] + o];
+                }
+                const float *row = a.S + (size_t)f * a.G;
+                s[j].x = row[gi[0]];
+                if (CUT) {
+                    s[j].y = row[gi[1]];
+                    s[j].z = row[gi[2]];
+                    s[j].w = row[gi[3]];
+                } else {
+                    s[j].y = s[j].z = s[j].w = s[j].x;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RBATCH; ++j) {
+            const uint32_t f = f0 + i0 + j;
+            if (f >= a.nf) continue;
+            const size_t o = (size_t)f * a.Wrow;
+            float4 r;
+            r.x = mix_minus(s[j].x, v[j].x, gn[0], dv[0], GAIN, norm);
+            r.y = mix_minus(s[j].y, v[j].y, gn[1], dv[1], GAIN, norm);
+            r.z = mix_minus(s[j].z, v[j].z, gn[2], dv[2], GAIN, norm);
+            r.w = mix_minus(s[j].w, v[j].w, gn[3], dv[3], GAIN, norm);
+            if (VEC) {
+                *(float4 *)(a.out + b[0] + o) = r;
+            } else {
+                a.out[b[0] + o] = r.x;
+                if (valid[1]) a.out[b[1] + o] = r.y;
+                if (valid[2]) a.out[b[2] + o] = r.z;
+                if (valid[3]) a.out[b[3] + o] = r.w;
+            }
+        }
+    }
+}
+
+template <bool GAIN, bool VEC>
+__global__ __launch_bounds__(P1_WG) void mixgroups_returns(RetArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t item = blockIdx.x * (P1_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (item >= a.nspans * a.nchunks) return;
+    const uint32_t k = item / a.nchunks, f0 = (item - k * a.nchunks) * RCHUNK;
+    if (a.slow[k]) returns_span<GAIN, VEC, true>(a, k, f0, lane);
+    else returns_span<GAIN, VEC, false>(a, k, f0, lane);
+}
+
+// buses[f][g] = S[f][g] / gdiv[g]: what the last reduce level (or a cut span) of `run` writes, from the raw sums
+__global__ __launch_bounds__(256) void mixgroups_divide(const float *__restrict__ S, const float *__restrict__ gdiv,
+                                                        float *__restrict__ bus, uint32_t G, uint64_t total) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) bus[i] = __fdiv_rn(S[i], gdiv[i % G]);
+}
+
 // ---- the plan: pure host -------------------------------------------------------------------------------------------------
 thread_local std::string g_err;        // the reason of the last failed call that had no bank to keep it
 
@@ -321,6 +453,7 @@ struct Level {
     std::vector<Task> tasks;
     uint32_t rows = 0;           // rows of partial sums it leaves for the next level
     Task *dtasks = nullptr;
+    Task *dtasks_raw = nullptr;  // the same tasks with div = 1.0 (returns; made at the first returns call of a normalising bank)
     float *out = nullptr;
 };
 
@@ -348,6 +481,13 @@ struct dspfx_mixgroups {
     uint32_t *gstart = nullptr;
     uint8_t *slow = nullptr;
     std::vector<Level> levels;
+    std::vector<uint32_t> hstart;                // the table, host copy (for the returns tables)
+    // per-channel returns: made at the first dspfx_mixgroups_returns call (mu)
+    bool ret_ready = false;
+    float *S = nullptr;                          // [max_frames][G] raw sums
+    float *gdiv_raw = nullptr;                   // [G] of 1.0 (a bank with normalise = 0 uses gdiv itself)
+    float *rdiv = nullptr;                       // [G]
+    uint32_t *sfirst = nullptr;                  // [nspans + 1]
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
@@ -358,10 +498,12 @@ namespace {
 
 void release(dspfx_mixgroups *p) {
     (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->gain, (void *)p->L, (void *)p->R, (void *)p->gdiv, (void *)p->gstart, (void *)p->slow})
+    for (void *d : {(void *)p->gain, (void *)p->L, (void *)p->R, (void *)p->gdiv, (void *)p->gstart, (void *)p->slow, (void *)p->S,
+                    (void *)p->gdiv_raw, (void *)p->rdiv, (void *)p->sfirst})
         if (d) (void)hipFree(d);
     for (Level &l : p->levels) {
         if (l.dtasks) (void)hipFree(l.dtasks);
+        if (l.dtasks_raw) (void)hipFree(l.dtasks_raw);
         if (l.out) (void)hipFree(l.out);
     }
     for (Store &s : p->queue)
@@ -585,6 +727,7 @@ extern "C" int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mi
         release(p);
         return DSPFX_ERR_HIP;
     }
+    p->hstart = std::move(gstart);
     *out = p;
     return DSPFX_OK;
 }
@@ -668,5 +811,153 @@ extern "C" int dspfx_mixgroups_run(dspfx_mixgroups *p, const float *block, uint3
         MG_HIP(hipGetLastError(), "mixgroups_reduce");
         src = l.out;
     }
+    return DSPFX_OK;
+}
+
+namespace {
+
+// The returns' buffers and tables, at the first call that asks for returns: a bank that never does keeps its footprint.
+int prepare_returns(dspfx_mixgroups *p) {
+    if (p->ret_ready) return DSPFX_OK;
+    const uint32_t G = p->desc.n_groups, N = p->desc.n_channels;
+    const std::vector<uint32_t> &gs = p->hstart;
+    std::vector<float> rdiv(G, 1.0f);
+    uint64_t last_n = ~0ull;
+    float last_div = 1.0f;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint64_t n = gs[g + 1] - gs[g];
+        if (n == 1) {
+            rdiv[g] = 0.0f;                      // no other pipe: the kernel writes +0.0
+        } else if (p->desc.normalise && n >= 2) {
+            if (n != last_n) {
+                last_n = n;
+                last_div = dspfx_link_divisor(n - 1);
+            }
+            rdiv[g] = last_div;
+        }
+    }
+    std::vector<uint32_t> sfirst(p->nspans + 1, G - 1);
+    uint32_t g = 0;
+    for (uint32_t k = 0; k < p->nspans; ++k) {
+        while (gs[g + 1] <= (uint64_t)k * SPAN) ++g;     // gs[G] = N > k * SPAN
+        sfirst[k] = g;
+    }
+    const bool raw = p->desc.normalise != 0;
+    bool ok = hipMalloc((void **)&p->S, (size_t)p->desc.max_frames * G * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&p->rdiv, (size_t)G * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&p->sfirst, sfirst.size() * sizeof(uint32_t)) == hipSuccess;
+    if (raw) {
+        ok = ok && hipMalloc((void **)&p->gdiv_raw, (size_t)G * sizeof(float)) == hipSuccess;
+        for (Level &l : p->levels) ok = ok && hipMalloc((void **)&l.dtasks_raw, l.tasks.size() * sizeof(Task)) == hipSuccess;
+    }
+    int rc = DSPFX_OK;
+    if (!ok) {
+        (void)hipGetLastError();
+        rc = fail(p, DSPFX_ERR_OOM, "mixgroups returns: no device memory for the raw sums [max_frames][G] and the returns tables");
+    } else {
+        ok = hipMemcpy(p->rdiv, rdiv.data(), (size_t)G * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(p->sfirst, sfirst.data(), sfirst.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+        if (raw) {
+            ok = ok && hipMemsetD32((hipDeviceptr_t)p->gdiv_raw, 0x3F800000, G) == hipSuccess;
+            for (Level &l : p->levels) {
+                std::vector<Task> t = l.tasks;
+                for (Task &q : t) q.div = 1.0f;
+                ok = ok && hipMemcpy(l.dtasks_raw, t.data(), t.size() * sizeof(Task), hipMemcpyHostToDevice) == hipSuccess;
+            }
+        }
+        if (!ok) rc = fail(p, DSPFX_ERR_HIP, "mixgroups returns: copying the returns tables");
+    }
+    if (rc != DSPFX_OK) {                        // all or nothing: the next call tries again
+        for (void **d : {(void **)&p->S, (void **)&p->rdiv, (void **)&p->sfirst, (void **)&p->gdiv_raw})
+            if (*d) {
+                (void)hipFree(*d);
+                *d = nullptr;
+            }
+        for (Level &l : p->levels)
+            if (l.dtasks_raw) {
+                (void)hipFree(l.dtasks_raw);
+                l.dtasks_raw = nullptr;
+            }
+        return rc;
+    }
+    p->ret_ready = true;
+    return DSPFX_OK;
+}
+
+hipError_t launch_returns(const RetArgs &a, bool gain, bool vec, hipStream_t s) {
+    const uint32_t items = a.nspans * a.nchunks, blocks = (items + P1_WG / 64 - 1) / (P1_WG / 64);
+    if (gain) {
+        if (vec) mixgroups_returns<true, true><<<blocks, P1_WG, 0, s>>>(a);
+        else mixgroups_returns<true, false><<<blocks, P1_WG, 0, s>>>(a);
+    } else {
+        if (vec) mixgroups_returns<false, true><<<blocks, P1_WG, 0, s>>>(a);
+        else mixgroups_returns<false, false><<<blocks, P1_WG, 0, s>>>(a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, uint32_t n_frames, float *buses, float *returns,
+                                       void *stream) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!block || !returns || n_frames == 0 || n_frames > p->desc.max_frames)
+        return fail(p, DSPFX_ERR_INVALID, "mixgroups returns: block, returns or n_frames");
+    hipStream_t s = (hipStream_t)stream;
+    MG_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
+    const int rc = prepare_returns(p);
+    if (rc != DSPFX_OK) return rc;
+    MG_HIP(order(p, s), "stream order");
+    MG_HIP(apply_stores(p, s), "fader store");       // once: the sums and the subtraction see the same table
+    const bool raw = p->desc.normalise != 0;
+    P1Args a;
+    a.x = block;
+    a.gain = p->gain;
+    a.L = p->L;
+    a.R = p->R;
+    a.bus = p->S;
+    a.gstart = p->gstart;
+    a.gdiv = raw ? p->gdiv_raw : p->gdiv;
+    a.slow = p->slow;
+    a.N = p->desc.n_channels;
+    a.Wrow = p->desc.tile_channels ? p->desc.tile_channels : a.N;
+    a.nf = n_frames;
+    a.G = p->desc.n_groups;
+    a.FS = p->FS;
+    a.nspans = p->nspans;
+    const bool gain = p->n_faded != 0;
+    a.nchunks = (n_frames + CHUNK - 1) / CHUNK;
+    MG_HIP(launch_partials<CHUNK>(a, gain, a.Wrow % 4 == 0 && ((uintptr_t)block & 15u) == 0, s), "mixgroups_partials");
+    const float *src = p->L;
+    for (Level &l : p->levels) {
+        const dim3 grid((unsigned)l.tasks.size(), (n_frames + 63) / 64);
+        mixgroups_reduce<<<grid, RW * 64, 0, s>>>(raw ? l.dtasks_raw : l.dtasks, src, p->R, l.out, p->S, n_frames, p->FS, a.G);
+        MG_HIP(hipGetLastError(), "mixgroups_reduce");
+        src = l.out;
+    }
+    if (buses) {
+        const uint64_t total = (uint64_t)n_frames * a.G;
+        mixgroups_divide<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(p->S, p->gdiv, buses, a.G, total);
+        MG_HIP(hipGetLastError(), "mixgroups_divide");
+    }
+    RetArgs r;
+    r.x = block;
+    r.out = returns;
+    r.gain = p->gain;
+    r.S = p->S;
+    r.gstart = p->gstart;
+    r.rdiv = p->rdiv;
+    r.sfirst = p->sfirst;
+    r.slow = p->slow;
+    r.N = a.N;
+    r.Wrow = a.Wrow;
+    r.nf = n_frames;
+    r.G = a.G;
+    r.nspans = p->nspans;
+    r.nchunks = (n_frames + RCHUNK - 1) / RCHUNK;
+    r.norm = raw ? 1u : 0u;
+    const bool vec = a.Wrow % 4 == 0 && (((uintptr_t)block | (uintptr_t)returns) & 15u) == 0;
+    MG_HIP(launch_returns(r, gain, vec, s), "mixgroups_returns");
     return DSPFX_OK;
 }

@@ -349,6 +349,7 @@ extern "C" {
     pub fn dspfx_mixgroups_destroy(m: *mut dspfx_mixgroups) -> c_int;
     pub fn dspfx_mixgroups_last_error(m: *const dspfx_mixgroups) -> *const c_char;
     pub fn dspfx_mixgroups_run(m: *mut dspfx_mixgroups, block: *const f32, n_frames: u32, buses: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_mixgroups_returns(m: *mut dspfx_mixgroups, block: *const f32, n_frames: u32, buses: *mut f32, returns: *mut f32, stream: *mut c_void) -> c_int;
     pub fn dspfx_mixgroups_set_gains(m: *mut dspfx_mixgroups, host_values: *const f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixgroups_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, depth_out: *mut u32) -> c_int;
 }

@@ -62,6 +62,13 @@ impl MixGroups {
         let rc = dspfx_mixgroups_run(self.h, block, n_frames, buses, stream);
         self.check(rc, "dspfx_mixgroups_run")
     }
+    /// Every channel's room minus itself (`dspfx_mixgroups_returns`): the DEVICE block `returns`, in the bank's layout, receives
+    /// `(S[f][g] - x[f][c] * gain[c]) / link_divisor(n_g - 1)`, +0.0 in a group of one.  `returns` may be `block` itself (in place);
+    /// any other overlap is undefined.  `buses` is null or a DEVICE array `[n_frames][G]` that receives what `run` writes.
+    pub unsafe fn returns(&self, block: *const f32, n_frames: u32, buses: *mut f32, returns: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+        let rc = dspfx_mixgroups_returns(self.h, block, n_frames, buses, returns, stream);
+        self.check(rc, "dspfx_mixgroups_returns")
+    }
     /// Stores the faders of channels `first_channel ..` (any thread, never waits for the device); they govern the runs submitted later.
     pub fn set_gains(&self, values: &[f32], first_channel: u64) -> Result<(), Error> {
         let rc = unsafe { dspfx_mixgroups_set_gains(self.h, values.as_ptr(), first_channel, values.len() as u64) };

@@ -851,6 +851,32 @@ const char *dspfx_mixgroups_last_error(const dspfx_mixgroups *m);
  * Asynchronous on `stream`; a run on another stream than the one before first waits (on the device) for that one, since the
  * partial sums are the bank's. */
 int dspfx_mixgroups_run(dspfx_mixgroups *m, const float *block, uint32_t n_frames, float *buses, void *stream);
+/* Per-channel returns: every participant of a room has an Output node of their own, wired to the OTHER n_g - 1 channels of
+ * the room, so that nobody hears themself.  With t[f][c] = fl32(x[f][c] * gain[c]) (x[f][c] itself for a channel without a
+ * stored fader: the terms dspfx_mixgroups_run sums), for channel c of group g:
+ *       returns[f][c] = fl32( fl32(S[f][g] - t[f][c]) / dspfx_link_divisor(n_g - 1) )      n_g >= 2
+ *       returns[f][c] = +0.0                                                               n_g == 1
+ * S[f][g] is the group's RAW sum exactly as this bank computes it: the bits a bank with the same table, layout and
+ * normalise = 0 writes as its bus.  One f32 subtraction, then one IEEE f32 division by the f32 divisor of n_g - 1 connected
+ * pipes (node.rs:166,179); nothing is contracted.  A group of one channel has no other pipe: the reference's unconnected
+ * port stays zeroed (node.rs:288), so the return is +0.0 whatever the sample is, NaN included.  normalise = 0 leaves the
+ * division out: returns = fl32(S - t).  Otherwise edge values are what that arithmetic gives: a channel carrying +inf gets
+ * inf - inf = NaN in its own return and +inf in the others', a NaN channel makes every return of its room NaN.
+ * Not the reference's order (which adds the other n_g - 1 pipes one after the other): within
+ *       (D + 2) 2^-24 (sum over the WHOLE group of |t|) / divisor + 2^-24 |ref| + 2^-149
+ * of the exact sum of the others, D = the group's depth from dspfx_mixgroups_plan; one rounding more than the bus, for the
+ * subtraction.  The bound is absolute and taken over the whole group's terms: a channel that dominates its room gets a
+ * return with a poor relative error, because of cancellation.  That is the known price of mix-minus, and it is what makes
+ * the cost O(n) instead of O(n^2).
+ * block, returns: device, n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  returns == block works in
+ * place (a thread rewrites the elements it read, after the sums in stream order); any other overlap is the caller's error.
+ * buses: NULL, or device [n_frames][G]: receives exactly what dspfx_mixgroups_run would have written, the same bits, and the
+ * sums are paid for once.  Stream rules as dspfx_mixgroups_run; queued fader stores are drained once, ahead of the first
+ * kernel, so the sums and the subtraction see the same table.  The first call allocates a [max_frames][G] f32 buffer for the
+ * raw sums (a bank that never asks for returns keeps its footprint); if that fails: DSPFX_ERR_OOM, the reason in
+ * dspfx_mixgroups_last_error, and a later call tries again.  NULL returns or block, n_frames of 0 or above max_frames:
+ * DSPFX_ERR_INVALID before any device work. */
+int dspfx_mixgroups_returns(dspfx_mixgroups *m, const float *block, uint32_t n_frames, float *buses, float *returns, void *stream);
 /* Stores the faders of channels [first_channel, first_channel + count) from a host array; host_values = NULL drops them for
  * that range: back to "not multiplied".  Callable from any thread while runs are in flight, and never waits for the device or
  * for a run: the values are copied into a page-locked staging buffer and queued; the next run puts the queued stores on its

@@ -447,6 +447,11 @@ class MixGroups {
     std::uint32_t groups() const { return groups_; }
     // device block of n_frames -> device buses [n_frames][G]; asynchronous on `stream`
     void run(const float *block, std::uint32_t n_frames, float *buses, void *stream = nullptr) { chk(dspfx_mixgroups_run(p_, block, n_frames, buses, stream)); }
+    // every channel's room minus itself: returns[f][c] = (S[f][g] - t[f][c]) / link_divisor(n_g - 1), in the block's layout
+    // (returns == block: in place); buses may be nullptr, else it receives what run() writes (dspfx_mixgroups_returns)
+    void returns(const float *block, std::uint32_t n_frames, float *buses, float *returns, void *stream = nullptr) {
+        chk(dspfx_mixgroups_returns(p_, block, n_frames, buses, returns, stream));
+    }
     // faders of channels [first_channel, first_channel + count) from a host array; nullptr drops them.  Any thread; never waits.
     void set_gains(const float *host_values, std::uint64_t first_channel, std::uint64_t count) {
         chk(dspfx_mixgroups_set_gains(p_, host_values, first_channel, count));

@@ -4,6 +4,8 @@ alternating input blocks filled with noise, every channel with a fader stored (t
   (b)      a ragged table drawn from a fixed seed, sizes 1 .. channels / 4 (mixgroups_ref.ragged_table's rule)
   nogain   (a) with no fader stored
   chain    Engine.process of [Gain(1.0)], which reads AND writes the block: twice the bank's bytes
+  returns  MixGroups.returns (every channel's room minus itself) into a third buffer: run's read, one more read and one write of
+           the block, three times the bank's bytes
 Device events around every call, --reps runs after 5 warm-ups, the median; the fraction of peak is block bytes / time / 8 TB/s.
 One JSON line per case, then a table.
 
@@ -65,7 +67,9 @@ def measure(torch, n, reps):
             mg.set_gains(np.random.default_rng(61).uniform(0.0, 4.0, n).astype(np.float32))
         buses = torch.empty((B, mg.groups), dtype=torch.float32, device=dev)
         ms = timed(torch, lambda i: mg.run(xs[i % 2], B, out=buses), reps)
+        ret = timed(torch, lambda i: mg.returns(xs[i % 2], B, out=y), reps)
         r = {"channels": n, "case": case, "groups": mg.groups, "ms": ms, "fraction_of_peak": B * n * 4 / (ms * 1e-3) / PEAK,
+             "returns_ms": ret, "returns_fraction_of_peak": 3 * B * n * 4 / (ret * 1e-3) / PEAK,
              "chain_ms": chain, "chain_fraction_of_peak": 2 * B * n * 4 / (chain * 1e-3) / PEAK, "depth_max": int(mg.depth().max())}
         print(json.dumps(r), flush=True)
         rows.append(r)
@@ -85,10 +89,12 @@ def main():
         rows += measure(torch, n, a.reps)
         torch.cuda.empty_cache()
     print(f"\ntimes in ms, median of {a.reps}; fractions of the 8 TB/s HBM peak")
-    print(f"{'channels':>9} {'case':>7} {'groups':>7} {'bank':>8} {'of peak':>8} {'chain':>8} {'of peak':>8} {'bank/chain':>10}")
+    print(f"{'channels':>9} {'case':>7} {'groups':>7} {'bank':>8} {'of peak':>8} {'chain':>8} {'of peak':>8} {'bank/chain':>10} "
+          f"{'returns':>8} {'of peak':>8}")
     for r in rows:
         print(f"{r['channels']:>9} {r['case']:>7} {r['groups']:>7} {r['ms']:>8.4f} {r['fraction_of_peak']:>8.3f} {r['chain_ms']:>8.4f} "
-              f"{r['chain_fraction_of_peak']:>8.3f} {r['ms'] / r['chain_ms']:>10.2f}")
+              f"{r['chain_fraction_of_peak']:>8.3f} {r['ms'] / r['chain_ms']:>10.2f} {r['returns_ms']:>8.4f} "
+              f"{r['returns_fraction_of_peak']:>8.3f}")
 
 
 if __name__ == "__main__":
