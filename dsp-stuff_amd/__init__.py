@@ -50,6 +50,7 @@ PITCH_POWER, PITCH_CLARITY, PITCH_PICK = range(3)
 PITCH_WINDOW = 1024
 SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT = 128, 8192      # DSPFX_SPECTRUM_*: the Spectrogram node's fft_size slider (spectrogram.rs:142)
 SPECTRUM_RATE = 48000.0         # spectrogram.rs:238 sampling_rate: bin k of an n-point window is k * 48000 / n Hz
+CONVOLVE_MAX_TAPS = 524288      # DSPFX_CONVOLVE_MAX_TAPS: the longest response a Convolver takes (4096 partitions of 128)
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -73,6 +74,8 @@ EXPORTS = [
     "dspfx_spectrum_reset", "dspfx_spectrum_windows", "dspfx_spectrum_plan",
     "dspfx_mixgroups_create", "dspfx_mixgroups_destroy", "dspfx_mixgroups_last_error", "dspfx_mixgroups_run",
     "dspfx_mixgroups_set_gains", "dspfx_mixgroups_plan", "dspfx_mixgroups_returns",
+    "dspfx_convolve_create", "dspfx_convolve_destroy", "dspfx_convolve_reset", "dspfx_convolve_run", "dspfx_convolve_set_taps",
+    "dspfx_convolve_plan",
 ]
 COMM_ID_BYTES = 128
 
@@ -127,6 +130,11 @@ class _MixGroupsDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("n_groups", C.c_uint32), ("normalise", C.c_uint32),
                 ("group_start", C.POINTER(C.c_uint64))]
+
+
+class _ConvolveDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
+                ("n_taps", C.c_uint32), ("max_taps", C.c_uint32), ("mode", C.c_int32), ("taps_reversed", C.POINTER(C.c_double))]
 
 
 class _Ctl(C.Structure):
@@ -267,6 +275,12 @@ def lib():
     L.dspfx_mixgroups_returns.argtypes = [vp, f32p, C.c_uint32, f32p, f32p, vp]
     L.dspfx_mixgroups_set_gains.argtypes = [vp, C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
     L.dspfx_mixgroups_plan.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.dspfx_convolve_create.argtypes = [C.POINTER(_ConvolveDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_convolve_destroy.argtypes = [vp]
+    L.dspfx_convolve_reset.argtypes = [vp]
+    L.dspfx_convolve_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_convolve_set_taps.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, C.c_int]
+    L.dspfx_convolve_plan.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1221,6 +1235,103 @@ class MixGroups:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.L.dspfx_mixgroups_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _taps_reversed(impulse_response) -> np.ndarray:
+    t = np.ascontiguousarray(np.asarray(impulse_response, np.float64).reshape(-1)[::-1])
+    if len(t) > CONVOLVE_MAX_TAPS:
+        raise DspfxError(-1, f"an impulse response of {len(t)} taps is longer than CONVOLVE_MAX_TAPS = {CONVOLVE_MAX_TAPS}")
+    return t
+
+
+def convolve_plan(impulse_response):
+    """dspfx_convolve_plan, a pure host function (no GPU): -> (P, table float32[128, P, 2]): the partitions of the response
+    h (in time order) and the f32 response table exactly as the device gets it -- table[k, p] = (re, im) of bin k of the
+    256-point FFT of h[128 p : 128 p + 128], zero-padded; table[0, p] = (DC, Nyquist)."""
+    L = lib()
+    t = _taps_reversed(impulse_response)
+    dp = C.POINTER(C.c_double)
+    parts = C.c_uint32()
+    rc = L.dspfx_convolve_plan(t.ctypes.data_as(dp), len(t), C.byref(parts), None)
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    table = np.zeros((128, int(parts.value), 2), np.float32)
+    rc = L.dspfx_convolve_plan(t.ctypes.data_as(dp), len(t), C.byref(parts), table.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    return int(parts.value), table
+
+
+class Convolver:
+    """One long impulse response over N channels by partitioned FFT (include/dspfx.h, dspfx_convolve_*): per 128-frame block
+    y[n] = fl32(sum_j h[j] x[n - j]) * divisor, divisor 1 (FIR_BALANCED) or 1 / T (FIR_AVERAGE), the FIR node's arithmetic for
+    responses too long for its tap table: a convolution reverb on the G buses of a MixGroups.  `impulse_response` is h in
+    time order (as Engine.set_taps takes it); `max_taps` reserves history for later set_taps of longer responses (0 = this
+    one's length).  Blocks are in the layout of `tile_channels` (as Engine's).  The history starts as silence.  Asynchronous on
+    `stream`."""
+
+    def __init__(self, channels: int, impulse_response, mode: int = FIR_BALANCED, max_taps: int = 0, tile_channels: int = 0,
+                 device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.max_taps = int(max_taps)
+        self.h = C.c_void_p()
+        t = _taps_reversed(impulse_response)
+        d = _ConvolveDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.tile_channels, len(t),
+                          self.max_taps & 0xFFFFFFFF, int(mode), t.ctypes.data_as(C.POINTER(C.c_double)))
+        rc = self.L.dspfx_convolve_create(C.byref(d), C.byref(self.h))         # the taps are copied before this returns
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+        self.n_taps, self.mode = len(t), int(mode)
+
+    @classmethod
+    def from_wav(cls, path: str, channels: int, resample: bool = True, **kw):
+        """The response from a WAV file exactly as the FIR node loads it (ir.load_impulse_response: channel 0, dasp sinc
+        resampling to 48 kHz)."""
+        from . import ir
+        return cls(channels, ir.load_impulse_response(path, resample=resample), **kw)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+
+    @property
+    def partitions(self) -> int:
+        """P = ceil(T / 128): the spectra of history one block reads per channel."""
+        return (self.n_taps + BUF_SIZE - 1) // BUF_SIZE
+
+    def run(self, block, n_frames: int = BUF_SIZE, out=None, stream: int = 0):
+        """One device block of n_frames (a multiple of 128) -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        import torch
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_convolve_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        return out
+
+    def set_taps(self, impulse_response, mode: Optional[int] = None):
+        """Replace the response (at most max_taps long) and keep the history: the reference's reload.  From the next run on."""
+        t = _taps_reversed(impulse_response)
+        m = self.mode if mode is None else int(mode)
+        self._chk(self.L.dspfx_convolve_set_taps(self.h, t.ctypes.data_as(C.POINTER(C.c_double)), len(t), m))
+        self.n_taps, self.mode = len(t), m
+
+    def reset(self):
+        """Back to silence (ahead of the next run)."""
+        self._chk(self.L.dspfx_convolve_reset(self.h))
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_convolve_destroy(h)
             h.value = None
 
     def __del__(self):

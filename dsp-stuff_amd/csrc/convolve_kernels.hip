@@ -1,0 +1,650 @@
+// convolve_kernels.hip -- the convolver bank (include/dspfx.h, dspfx_convolve_*): one long impulse response over N channels by
+// uniformly partitioned overlap-save, partition = the 128-frame block, P = ceil(T / 128) partitions.  Per block and channel:
+//   convolve_forward     the real 256-point FFT of (previous block, this block) into slot `head` of the spectral ring
+//   convolve_accumulate  Y[k] = sum_{p<P} H[p][k] * X[head - p][k]: the hot path, one read of the channel's spectral history
+//   convolve_inverse     the inverse FFT of Y, its last 128 samples times the divisor into `out`
+// A spectrum is 128 complex values: bins 1..127, and element 0 = (DC, Nyquist), both real, which multiplies component-wise.
+// The real transform of 256 samples is ONE complex transform of 128 points, z[j] = x[2j] + i x[2j + 1] (as spectrum_kernels.hip):
+// with Zc = conj Z[128 - k] and w = exp(-2 pi i k / 256)
+//       X[k] = ((Z[k] + Zc) - i w (Z[k] - Zc)) / 2            X[0] = Re Z[0] + Im Z[0], X[128] = Re Z[0] - Im Z[0]
+// and back, with Yc = conj Y[128 - k]:
+//       2 Z[k] = (Y[k] + Yc) + i conj(w) (Y[k] - Yc)          2 Z[0] = (Y[0] + Y[128]) + i (Y[0] - Y[128])
+// z = IFFT_128(Z) is done as conj(FFT_128(conj Z)) / 128; the factors 1/2 and 1/128 are one exact multiplication by 2^-8.
+// Ring layout [slot][k][N] complex, so in the accumulation consecutive lanes are consecutive channels and H is wave-uniform;
+// the response table is [k][P] complex, read with scalar loads through the constant address space.
+// The forward and inverse kernels give a workgroup of 256 threads a RUN of 32 adjacent channels (every global access a whole
+// segment in both layouts); the 32 transforms live in one LDS buffer A[point][q] and are done in place, radix 4, 4, 4, 2.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/dspfx.h"
+
+namespace {
+
+constexpr uint32_t L = DSPFX_BUF_SIZE;             // partition = block = 128 frames
+constexpr int M = 128;                             // complex points of a spectrum
+constexpr int Q = 32;                              // channels per workgroup of the forward / inverse kernels
+constexpr int ST = 256;                            // their threads
+constexpr int GROUP = 16;                          // partitions per partial sum, and loads in flight per lane
+constexpr int AW = 4;                              // waves (= values of k) per workgroup of the accumulation
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) float *TablePtr;   // wave-uniform index: scalar loads
+
+// element (f, c) of a block of nf frames in the desc's layout (dspfx_engine_desc.tile_channels)
+__host__ __device__ inline size_t lay(uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
+    return W ? ((size_t)(c / W) * nf + f) * W + (c % W) : (size_t)f * N + c;
+}
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// one in-place Stockham pass of radix R over the Q transforms of 128 points in A[point][q]; NS = the product of the radices
+// before it; tw[t] = exp(-2 pi i t / 256)
+template <int R, int NS>
+__device__ __forceinline__ void fft_pass(float2 *A, const float2 *__restrict__ tw) {
+    constexpr int NR = M / R, IT = NR * Q / ST;
+    static_assert(NR * Q % ST == 0, "every thread does the same number of butterflies");
+    float2 v[IT][R];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+        const int b = threadIdx.x + i * ST, q = b % Q, j = b / Q;
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[i][r] = A[(j + r * NR) * Q + q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+        const int b = threadIdx.x + i * ST, q = b % Q, j = b / Q;
+        const int k = j & (NS - 1);
+        float2 *u = v[i];
+        if (NS > 1) {
+#pragma unroll
+            for (int r = 1; r < R; ++r) u[r] = cmul(u[r], tw[2 * (k * r * (M / (NS * R)))]);
+        }
+        if (R == 2) {
+            const float2 a = u[0];
+            u[0] = cadd(a, u[1]);
+            u[1] = csub(a, u[1]);
+        } else {
+            const float2 a0 = cadd(u[0], u[2]), a1 = csub(u[0], u[2]), a2 = cadd(u[1], u[3]), a3 = csub(u[1], u[3]);
+            const float2 ja3 = make_float2(a3.y, -a3.x);                                   // -i * a3
+            u[0] = cadd(a0, a2);
+            u[1] = cadd(a1, ja3);
+            u[2] = csub(a0, a2);
+            u[3] = csub(a1, ja3);
+        }
+        const int d = (j - k) * R + k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) A[(d + r * NS) * Q + q] = u[r];
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void fft128(float2 *A, const float2 *__restrict__ tw) {
+    fft_pass<4, 1>(A, tw);
+    fft_pass<4, 4>(A, tw);
+    fft_pass<4, 16>(A, tw);
+    fft_pass<2, 64>(A, tw);
+}
+
+struct FftArgs {
+    const float *in;             // forward: the caller's block of nf frames
+    float *out;                  // inverse: the caller's block of nf frames
+    float *prev;                 // [128][N]: the bank's copy of the previous block, frame-major
+    float2 *spec;                // forward: the ring slot [128][N]; inverse: the accumulator [128][N]
+    const float2 *tw;            // [256] exp(-2 pi i t / 256)
+    uint32_t N, W, nf, f0;       // the block is frames [f0, f0 + 128) of nf
+    uint32_t vec;                // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N
+    float divisor;
+};
+
+// frame f of 4 channels from c (c a multiple of 4) of a block at `base`; channels outside N read 0
+__device__ __forceinline__ float4 load4(const float *base, uint32_t vec, uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (vec) {
+        if (c < N) v = *(const float4 *)(base + lay(f, c, nf, N, W));
+    } else {
+        if (c < N) v.x = base[lay(f, c, nf, N, W)];
+        if (c + 1 < N) v.y = base[lay(f, c + 1, nf, N, W)];
+        if (c + 2 < N) v.z = base[lay(f, c + 2, nf, N, W)];
+        if (c + 3 < N) v.w = base[lay(f, c + 3, nf, N, W)];
+    }
+    return v;
+}
+
+template <bool NT>
+__device__ __forceinline__ void store4(float *base, float4 v, uint32_t vec, uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
+    if (vec) {
+        if (c < N) {
+            f32x4 *p = (f32x4 *)(base + lay(f, c, nf, N, W));
+            const f32x4 t = {v.x, v.y, v.z, v.w};
+            if (NT) __builtin_nontemporal_store(t, p);
+            else *p = t;
+        }
+    } else {
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i)
+            if (c + i < N) {
+                float *p = base + lay(f, c + i, nf, N, W);
+                if (NT) __builtin_nontemporal_store(e[i], p);
+                else *p = e[i];
+            }
+    }
+}
+
+// the spectrum values of 4 channels at one k: element (k, c + i) of a [128][N] complex array
+__device__ __forceinline__ void load_spec4(const float2 *spec, uint32_t vec, uint32_t k, uint32_t c, uint32_t N, float4 &lo, float4 &hi) {
+    lo = hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float2 *p = spec + (size_t)k * N + c;
+    if (vec) {
+        if (c < N) {
+            lo = *(const float4 *)p;
+            hi = *(const float4 *)(p + 2);
+        }
+    } else {
+        if (c < N) { const float2 t = p[0]; lo.x = t.x; lo.y = t.y; }
+        if (c + 1 < N) { const float2 t = p[1]; lo.z = t.x; lo.w = t.y; }
+        if (c + 2 < N) { const float2 t = p[2]; hi.x = t.x; hi.y = t.y; }
+        if (c + 3 < N) { const float2 t = p[3]; hi.z = t.x; hi.w = t.y; }
+    }
+}
+
+__device__ __forceinline__ void store_spec4(float2 *spec, uint32_t vec, uint32_t k, uint32_t c, uint32_t N, float4 lo, float4 hi) {
+    float2 *p = spec + (size_t)k * N + c;
+    if (vec) {
+        if (c < N) {
+            *(float4 *)p = lo;
+            *(float4 *)(p + 2) = hi;
+        }
+    } else {
+        if (c < N) p[0] = make_float2(lo.x, lo.y);
+        if (c + 1 < N) p[1] = make_float2(lo.z, lo.w);
+        if (c + 2 < N) p[2] = make_float2(hi.x, hi.y);
+        if (c + 3 < N) p[3] = make_float2(hi.z, hi.w);
+    }
+}
+
+// X[k] of one channel from Z[k] and Z[(128 - k) & 127]; k = 0 gives the packed (DC, Nyquist)
+__device__ __forceinline__ float2 bin_of(float2 z, float2 zm, float2 w, uint32_t k) {
+    if (k == 0) return make_float2(z.x + z.y, z.x - z.y);
+    const float ar = z.x + zm.x, ai = z.y - zm.y;
+    const float2 t = cmul(w, make_float2(z.x - zm.x, z.y + zm.y));
+    return make_float2(0.5f * (ar + t.y), 0.5f * (ai - t.x));
+}
+
+// conj(2 Z[k]) of one channel from Y[k] and Y[(128 - k) & 127]; for k = 0 y is the packed (DC, Nyquist)
+__device__ __forceinline__ float2 point_of(float2 y, float2 ym, float2 w, uint32_t k) {
+    if (k == 0) return make_float2(y.x + y.y, -(y.x - y.y));
+    const float er = y.x + ym.x, ei = y.y - ym.y;
+    const float2 o = cmul(make_float2(w.x, -w.y), make_float2(y.x - ym.x, y.y + ym.y));
+    return make_float2(er - o.y, -(ei + o.x));
+}
+
+__global__ __launch_bounds__(ST) void convolve_forward(FftArgs a) {
+    __shared__ __attribute__((aligned(16))) float2 A[M * Q];
+    float4 *A4 = (float4 *)A;
+    const int t = threadIdx.x;
+    const uint32_t c0 = blockIdx.x * Q;
+    constexpr int UN = M * Q / 4 / ST;                   // units of 4 channels per thread
+
+    // ---- the window: unit u = frames (2j, 2j + 1) of 4 channels = point j of 4 transforms; points 0..63 are the previous block
+    float4 xe[UN], xo[UN];
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST, j = u / (Q / 4), c = c0 + 4 * (u % (Q / 4));
+        if (j < M / 2) {
+            xe[i] = load4(a.prev, a.vec, 2 * j, c, L, a.N, 0);
+            xo[i] = load4(a.prev, a.vec, 2 * j + 1, c, L, a.N, 0);
+        } else {
+            xe[i] = load4(a.in, a.vec, a.f0 + 2 * j - L, c, a.nf, a.N, a.W);
+            xo[i] = load4(a.in, a.vec, a.f0 + 2 * j - L + 1, c, a.nf, a.N, a.W);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST;
+        A4[2 * u] = make_float4(xe[i].x, xo[i].x, xe[i].y, xo[i].y);
+        A4[2 * u + 1] = make_float4(xe[i].z, xo[i].z, xe[i].w, xo[i].w);
+    }
+    __syncthreads();                                     // every read of the previous block is done: this block replaces it
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST, j = u / (Q / 4), c = c0 + 4 * (u % (Q / 4));
+        if (j >= M / 2) {
+            store4<false>(a.prev, xe[i], a.vec, 2 * j - L, c, L, a.N, 0);
+            store4<false>(a.prev, xo[i], a.vec, 2 * j - L + 1, c, L, a.N, 0);
+        }
+    }
+
+    fft128(A, a.tw);
+
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST, k = u / (Q / 4), h = u % (Q / 4), c = c0 + 4 * h;
+        const uint32_t km = (M - k) & (M - 1);
+        const float4 z0 = A4[(k * (Q / 4) + h) * 2], z1 = A4[(k * (Q / 4) + h) * 2 + 1];
+        const float4 y0 = A4[(km * (Q / 4) + h) * 2], y1 = A4[(km * (Q / 4) + h) * 2 + 1];
+        const float2 w = a.tw[k];
+        const float2 b0 = bin_of(make_float2(z0.x, z0.y), make_float2(y0.x, y0.y), w, k);
+        const float2 b1 = bin_of(make_float2(z0.z, z0.w), make_float2(y0.z, y0.w), w, k);
+        const float2 b2 = bin_of(make_float2(z1.x, z1.y), make_float2(y1.x, y1.y), w, k);
+        const float2 b3 = bin_of(make_float2(z1.z, z1.w), make_float2(y1.z, y1.w), w, k);
+        store_spec4(a.spec, a.vec, k, c, a.N, make_float4(b0.x, b0.y, b1.x, b1.y), make_float4(b2.x, b2.y, b3.x, b3.y));
+    }
+}
+
+__global__ __launch_bounds__(ST) void convolve_inverse(FftArgs a) {
+    __shared__ __attribute__((aligned(16))) float2 A[M * Q];
+    float4 *A4 = (float4 *)A;
+    const int t = threadIdx.x;
+    const uint32_t c0 = blockIdx.x * Q;
+    constexpr int UN = M * Q / 4 / ST;
+
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST, k = u / (Q / 4), c = c0 + 4 * (u % (Q / 4));
+        float4 lo, hi;
+        load_spec4(a.spec, a.vec, k, c, a.N, lo, hi);
+        A4[2 * u] = lo;
+        A4[2 * u + 1] = hi;
+    }
+    __syncthreads();
+    // ---- Y -> conj(2 Z), in place: read both partners, meet, write
+    float4 p0[UN], p1[UN];
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST, k = u / (Q / 4), h = u % (Q / 4);
+        const uint32_t km = (M - k) & (M - 1);
+        const float4 z0 = A4[2 * u], z1 = A4[2 * u + 1];
+        const float4 y0 = A4[(km * (Q / 4) + h) * 2], y1 = A4[(km * (Q / 4) + h) * 2 + 1];
+        const float2 w = a.tw[k];
+        const float2 b0 = point_of(make_float2(z0.x, z0.y), make_float2(y0.x, y0.y), w, k);
+        const float2 b1 = point_of(make_float2(z0.z, z0.w), make_float2(y0.z, y0.w), w, k);
+        const float2 b2 = point_of(make_float2(z1.x, z1.y), make_float2(y1.x, y1.y), w, k);
+        const float2 b3 = point_of(make_float2(z1.z, z1.w), make_float2(y1.z, y1.w), w, k);
+        p0[i] = make_float4(b0.x, b0.y, b1.x, b1.y);
+        p1[i] = make_float4(b2.x, b2.y, b3.x, b3.y);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const uint32_t u = t + i * ST;
+        A4[2 * u] = p0[i];
+        A4[2 * u + 1] = p1[i];
+    }
+    __syncthreads();
+
+    fft128(A, a.tw);
+
+    // ---- the last 128 samples: point j in [64, 128) holds 256 * (y[2j], -y[2j + 1])
+    constexpr float SCALE = 1.0f / 256.0f;
+#pragma unroll
+    for (int i = 0; i < UN / 2; ++i) {
+        const uint32_t u = t + i * ST, j = M / 2 + u / (Q / 4), h = u % (Q / 4), c = c0 + 4 * h;
+        const float4 z0 = A4[(j * (Q / 4) + h) * 2], z1 = A4[(j * (Q / 4) + h) * 2 + 1];
+        const float d = a.divisor;
+        const float4 e = make_float4(z0.x * SCALE * d, z0.z * SCALE * d, z1.x * SCALE * d, z1.z * SCALE * d);
+        const float4 o = make_float4(-z0.y * SCALE * d, -z0.w * SCALE * d, -z1.y * SCALE * d, -z1.w * SCALE * d);
+        store4<true>(a.out, e, a.vec, a.f0 + 2 * j - L, c, a.nf, a.N, a.W);
+        store4<true>(a.out, o, a.vec, a.f0 + 2 * j - L + 1, c, a.nf, a.N, a.W);
+    }
+}
+
+// ---- the accumulation -----------------------------------------------------------------------------------------------
+struct AccArgs {
+    const float2 *ring;          // [slots][128][N]
+    float2 *acc;                 // [128][N]
+    const float2 *table;         // [128][P]
+    uint32_t N, P, slots, head;  // head = the slot the forward kernel just wrote: partition p reads slot head - p (mod slots)
+};
+
+// V = complex values per lane: 2 (adjacent channels c, c + 1, one 16-byte load; N even) or 1 (8-byte loads)
+template <int V> struct Lane;
+template <> struct Lane<2> {
+    typedef f32x4 T;
+    static __device__ __forceinline__ T zero() { return T{0.0f, 0.0f, 0.0f, 0.0f}; }
+    // bins 1..127: s += h * x
+    static __device__ __forceinline__ void mac(T &s, float2 h, T x) {
+        s.x = fmaf(-h.y, x.y, fmaf(h.x, x.x, s.x));
+        s.y = fmaf(h.y, x.x, fmaf(h.x, x.y, s.y));
+        s.z = fmaf(-h.y, x.w, fmaf(h.x, x.z, s.z));
+        s.w = fmaf(h.y, x.z, fmaf(h.x, x.w, s.w));
+    }
+    // element 0: (DC, Nyquist), component-wise
+    static __device__ __forceinline__ void mac0(T &s, float2 h, T x) {
+        s.x = fmaf(h.x, x.x, s.x);
+        s.y = fmaf(h.y, x.y, s.y);
+        s.z = fmaf(h.x, x.z, s.z);
+        s.w = fmaf(h.y, x.w, s.w);
+    }
+};
+template <> struct Lane<1> {
+    typedef f32x2 T;
+    static __device__ __forceinline__ T zero() { return T{0.0f, 0.0f}; }
+    static __device__ __forceinline__ void mac(T &s, float2 h, T x) {
+        s.x = fmaf(-h.y, x.y, fmaf(h.x, x.x, s.x));
+        s.y = fmaf(h.y, x.x, fmaf(h.x, x.y, s.y));
+    }
+    static __device__ __forceinline__ void mac0(T &s, float2 h, T x) {
+        s.x = fmaf(h.x, x.x, s.x);
+        s.y = fmaf(h.y, x.y, s.y);
+    }
+};
+
+// One wave = one k and 64 * V adjacent channels.  The order of additions is a function of P alone: partitions in ascending
+// order into a partial sum per 16 consecutive partitions (the last group may be short), the partials added in ascending order.
+template <int V, bool DC>
+__device__ __forceinline__ void accumulate_wave(const AccArgs &a, uint32_t k, uint32_t c) {
+    typedef typename Lane<V>::T T;
+    const TablePtr h = (TablePtr)a.table + (size_t)k * a.P * 2;
+    const size_t slot_stride = (size_t)M * a.N;          // complex values per slot
+    const float2 *x0 = a.ring + (size_t)k * a.N + c;
+    T total = Lane<V>::zero();
+    uint32_t s = a.head;                                 // the slot of partition p
+    uint32_t p = 0;
+    for (; p + GROUP <= a.P; p += GROUP) {
+        T x[GROUP];
+#pragma unroll
+        for (int j = 0; j < GROUP; ++j) {
+            x[j] = __builtin_nontemporal_load((const T *)(x0 + (size_t)s * slot_stride));
+            s = s ? s - 1 : a.slots - 1;
+        }
+        T part = Lane<V>::zero();
+#pragma unroll
+        for (int j = 0; j < GROUP; ++j) {
+            const float2 hv = make_float2(h[2 * (p + j)], h[2 * (p + j) + 1]);
+            if (DC) Lane<V>::mac0(part, hv, x[j]);
+            else Lane<V>::mac(part, hv, x[j]);
+        }
+        total += part;
+    }
+    if (p < a.P) {                                       // the short last group: the same order, fewer terms
+        T part = Lane<V>::zero();
+        for (; p < a.P; ++p) {
+            const T x = __builtin_nontemporal_load((const T *)(x0 + (size_t)s * slot_stride));
+            s = s ? s - 1 : a.slots - 1;
+            const float2 hv = make_float2(h[2 * p], h[2 * p + 1]);
+            if (DC) Lane<V>::mac0(part, hv, x);
+            else Lane<V>::mac(part, hv, x);
+        }
+        total += part;
+    }
+    *(T *)(a.acc + (size_t)k * a.N + c) = total;
+}
+
+// One wave = one k and 64 * V adjacent channels.  The order of additions is a function of P alone: partitions in ascending
+// order into a partial sum per 16 consecutive partitions (the last group may be short), the partials added in ascending order.
+template <int V>
+__global__ __launch_bounds__(64 * AW) void convolve_accumulate(AccArgs a) {
+    const uint32_t k = __builtin_amdgcn_readfirstlane(blockIdx.y * AW + threadIdx.x / 64);
+    const uint32_t c = (blockIdx.x * 64 + (threadIdx.x & 63)) * V;
+    if (c >= a.N) return;                                // V = 2: N is even, so c + 1 < N as well
+    if (k == 0) accumulate_wave<V, true>(a, k, c);
+    else accumulate_wave<V, false>(a, k, c);
+}
+
+bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
+
+uint32_t partitions_of(uint32_t n_taps) { return (n_taps + L - 1) / L; }
+
+// DSPFX_OK for a response the bank takes
+int check_taps(const double *taps_reversed, uint32_t n_taps) {
+    if (!taps_reversed || n_taps == 0 || n_taps > DSPFX_CONVOLVE_MAX_TAPS) return DSPFX_ERR_INVALID;
+    for (uint32_t i = 0; i < n_taps; ++i)
+        if (!std::isfinite(taps_reversed[i])) return DSPFX_ERR_INVALID;
+    return DSPFX_OK;
+}
+
+// the table [128][P] complex: H[p] = the 256-point transform of taps h[128 p .. 128 p + 127] (zero-padded), in f64 with the
+// twiddle of every term looked up by its exact index (k n mod 256), rounded once to f32; element 0 is (DC, Nyquist)
+void make_table(const double *taps_reversed, uint32_t n_taps, float *table) {
+    const uint32_t P = partitions_of(n_taps);
+    double cs[256], sn[256];
+    for (int t = 0; t < 256; ++t) {
+        cs[t] = std::cos(2.0 * M_PI * t / 256.0);
+        sn[t] = -std::sin(2.0 * M_PI * t / 256.0);
+    }
+    for (int t = 0; t < 256; t += 64) {                  // the axes exactly
+        cs[t] = t == 0 ? 1.0 : t == 128 ? -1.0 : 0.0;
+        sn[t] = t == 64 ? -1.0 : t == 192 ? 1.0 : 0.0;
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t n = std::min<uint32_t>(L, n_taps - p * L);
+        double hp[L];
+        for (uint32_t i = 0; i < n; ++i) hp[i] = taps_reversed[n_taps - 1 - (p * L + i)];
+        for (uint32_t k = 0; k <= (uint32_t)M; ++k) {
+            double re = 0.0, im = 0.0;
+            for (uint32_t i = 0; i < n; ++i) {
+                re += hp[i] * cs[(k * i) & 255];
+                im += hp[i] * sn[(k * i) & 255];
+            }
+            if (k == 0) table[((size_t)0 * P + p) * 2] = (float)re;
+            else if (k == (uint32_t)M) table[((size_t)0 * P + p) * 2 + 1] = (float)re;
+            else {
+                table[((size_t)k * P + p) * 2] = (float)re;
+                table[((size_t)k * P + p) * 2 + 1] = (float)im;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+struct dspfx_convolve {
+    dspfx_convolve_desc desc{};
+    std::mutex mu;                              // run / set_taps / reset / destroy are serialised
+    uint32_t slots = 0;                         // P_max = partitions of max_taps
+    uint32_t P = 0;                             // partitions of the response in use
+    float divisor = 1.0f;
+    float2 *ring = nullptr;                     // [slots][128][N]
+    float *prev = nullptr;                      // [128][N]
+    float2 *acc = nullptr;                      // [128][N]
+    float2 *table = nullptr;                    // room for [128][slots]; in use: [128][P]
+    float2 *tw = nullptr;                       // [256]
+    hipEvent_t ev = nullptr;
+    uint64_t blocks = 0;                        // blocks run since create / reset
+    bool silence = false;                       // the next run clears the history first
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+
+namespace {
+
+void release(dspfx_convolve *p) {
+    (void)hipSetDevice(p->desc.device);
+    if (p->ring) (void)hipFree(p->ring);
+    if (p->prev) (void)hipFree(p->prev);
+    if (p->acc) (void)hipFree(p->acc);
+    if (p->table) (void)hipFree(p->table);
+    if (p->tw) (void)hipFree(p->tw);
+    if (p->ev) (void)hipEventDestroy(p->ev);
+    delete p;
+}
+
+// a call on a stream other than the last one used waits (on the device) for that one
+hipError_t order(dspfx_convolve *p, hipStream_t s) {
+    hipError_t err = hipSuccess;
+    if (p->used && s != p->last) {
+        err = hipEventRecord(p->ev, p->last);
+        if (err == hipSuccess) err = hipStreamWaitEvent(s, p->ev, 0);
+    }
+    p->last = s;
+    p->used = true;
+    return err;
+}
+
+size_t ring_bytes(const dspfx_convolve *p) { return (size_t)p->slots * M * p->desc.channels * sizeof(float2); }
+size_t prev_bytes(const dspfx_convolve *p) { return (size_t)L * p->desc.channels * sizeof(float); }
+
+float divisor_of(int mode, uint32_t n_taps) { return mode == DSPFX_FIR_AVERAGE ? 1.0f / (float)n_taps : 1.0f; }
+
+}  // namespace
+
+#define CONV_HIP(call)                               \
+    do {                                             \
+        if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
+    } while (0)
+
+extern "C" int dspfx_convolve_plan(const double *taps_reversed, uint32_t n_taps, uint32_t *partitions, float *table_out) {
+    const int rc = check_taps(taps_reversed, n_taps);
+    if (rc != DSPFX_OK) return rc;
+    if (partitions) *partitions = partitions_of(n_taps);
+    if (table_out) make_table(taps_reversed, n_taps, table_out);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_create(const dspfx_convolve_desc *desc, dspfx_convolve **out) {
+    if (!desc || !out) return DSPFX_ERR_INVALID;
+    *out = nullptr;
+    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
+    const uint32_t N = desc->channels, W = desc->tile_channels;
+    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
+    if (desc->mode != DSPFX_FIR_BALANCED && desc->mode != DSPFX_FIR_AVERAGE) return DSPFX_ERR_INVALID;
+    const int rc = check_taps(desc->taps_reversed, desc->n_taps);
+    if (rc != DSPFX_OK) return rc;
+    const uint32_t max_taps = desc->max_taps ? desc->max_taps : desc->n_taps;
+    if (max_taps < desc->n_taps || max_taps > DSPFX_CONVOLVE_MAX_TAPS) return DSPFX_ERR_INVALID;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
+    if (desc->device < 0 || desc->device >= count) return DSPFX_ERR_INVALID;
+    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    dspfx_convolve *p = new (std::nothrow) dspfx_convolve;
+    if (!p) return DSPFX_ERR_OOM;
+    p->desc = *desc;
+    p->desc.max_taps = max_taps;
+    p->desc.taps_reversed = nullptr;            // copied below: the caller's taps are not kept
+    p->slots = partitions_of(max_taps);
+    p->P = partitions_of(desc->n_taps);
+    p->divisor = divisor_of(desc->mode, desc->n_taps);
+    std::vector<float> table((size_t)M * p->P * 2);
+    make_table(desc->taps_reversed, desc->n_taps, table.data());
+    std::vector<float2> tw(256);
+    for (int t = 0; t < 256; ++t) {
+        const double ang = -2.0 * M_PI * t / 256.0;
+        tw[t] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+    }
+    tw[0] = make_float2(1.0f, 0.0f);            // the axes exactly: data whose spectrum lies on them goes through bit for bit
+    tw[64] = make_float2(0.0f, -1.0f);
+    tw[128] = make_float2(-1.0f, 0.0f);
+    tw[192] = make_float2(0.0f, 1.0f);
+    if (hipMalloc((void **)&p->ring, ring_bytes(p)) != hipSuccess ||
+        hipMalloc((void **)&p->prev, prev_bytes(p)) != hipSuccess ||
+        hipMalloc((void **)&p->acc, (size_t)M * N * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&p->table, (size_t)M * p->slots * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&p->tw, 256 * sizeof(float2)) != hipSuccess) {
+        (void)hipGetLastError();
+        release(p);
+        return DSPFX_ERR_OOM;
+    }
+    if (hipMemset(p->ring, 0, ring_bytes(p)) != hipSuccess || hipMemset(p->prev, 0, prev_bytes(p)) != hipSuccess ||
+        hipMemcpy(p->table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p->tw, tw.data(), 256 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
+        hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess) {
+        release(p);
+        return DSPFX_ERR_HIP;
+    }
+    *out = p;
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_destroy(dspfx_convolve *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        (void)hipSetDevice(p->desc.device);
+        if (p->used) (void)hipStreamSynchronize(p->last);   // the bank's work is ordered on the last stream it used
+    }
+    release(p);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_reset(dspfx_convolve *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->blocks = 0;
+    p->silence = true;
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_set_taps(dspfx_convolve *p, const double *taps_reversed, uint32_t n_taps, int mode) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (mode != DSPFX_FIR_BALANCED && mode != DSPFX_FIR_AVERAGE) return DSPFX_ERR_INVALID;
+    const int rc = check_taps(taps_reversed, n_taps);
+    if (rc != DSPFX_OK) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (n_taps > p->desc.max_taps) return DSPFX_ERR_INVALID;
+    const uint32_t P = partitions_of(n_taps);
+    std::vector<float> table((size_t)M * P * 2);
+    make_table(taps_reversed, n_taps, table.data());
+    CONV_HIP(hipSetDevice(p->desc.device));
+    // the runs already submitted read the table in place: they finish first, then it is replaced (a reload is a file load, not
+    // a per-block call); the ring holds input spectra, so the history stays
+    if (p->used) CONV_HIP(hipStreamSynchronize(p->last));
+    CONV_HIP(hipMemcpy(p->table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    p->P = P;
+    p->desc.n_taps = n_taps;
+    p->desc.mode = mode;
+    p->divisor = divisor_of(mode, n_taps);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out, uint32_t n_frames, void *stream) {
+    if (!p || !in || !out || n_frames == 0 || n_frames % L) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    hipStream_t s = (hipStream_t)stream;
+    CONV_HIP(hipSetDevice(p->desc.device));
+    CONV_HIP(order(p, s));
+    if (p->silence) {
+        CONV_HIP(hipMemsetAsync(p->ring, 0, ring_bytes(p), s));
+        CONV_HIP(hipMemsetAsync(p->prev, 0, prev_bytes(p), s));
+        p->silence = false;
+    }
+    const uint32_t N = p->desc.channels, W = p->desc.tile_channels;
+    FftArgs f;
+    f.in = in;
+    f.out = out;
+    f.prev = p->prev;
+    f.tw = p->tw;
+    f.N = N;
+    f.W = W;
+    f.nf = n_frames;
+    f.vec = (W ? W : N) % 4 == 0;               // the tile divides N; hipMalloc and every row offset are 16-byte aligned then
+    f.divisor = p->divisor;
+    if (f.vec && ((((uintptr_t)in) | ((uintptr_t)out)) & 15)) f.vec = 0;
+    AccArgs a;
+    a.ring = p->ring;
+    a.acc = p->acc;
+    a.table = p->table;
+    a.N = N;
+    a.P = p->P;
+    a.slots = p->slots;
+    const unsigned fft_blocks = (N + Q - 1) / Q;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += L) {
+        const uint32_t head = (uint32_t)(p->blocks % p->slots);
+        f.f0 = f0;
+        f.spec = p->ring + (size_t)head * M * N;
+        convolve_forward<<<fft_blocks, ST, 0, s>>>(f);
+        CONV_HIP(hipGetLastError());
+        p->blocks += 1;                          // the slot is written: a failure further on leaves a consistent history
+        a.head = head;
+        if (N % 2 == 0)
+            convolve_accumulate<2><<<dim3((N / 2 + 63) / 64, M / AW), 64 * AW, 0, s>>>(a);
+        else
+            convolve_accumulate<1><<<dim3((N + 63) / 64, M / AW), 64 * AW, 0, s>>>(a);
+        CONV_HIP(hipGetLastError());
+        f.spec = p->acc;
+        convolve_inverse<<<fft_blocks, ST, 0, s>>>(f);
+        CONV_HIP(hipGetLastError());
+    }
+    return DSPFX_OK;
+}

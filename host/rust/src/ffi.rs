@@ -157,6 +157,26 @@ pub struct dspfx_pitch_desc {
     pub pick_thresh: f32,
 }
 
+/// Opaque convolver bank handle (`typedef struct dspfx_convolve dspfx_convolve`).
+#[repr(C)]
+pub struct dspfx_convolve {
+    _private: [u8; 0],
+}
+
+/// The convolver bank's descriptor (`dspfx_convolve_create`); `taps_reversed` is a host array of `n_taps` f64 read at create.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_convolve_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub channels: u32,
+    pub tile_channels: u32,
+    pub n_taps: u32,
+    pub max_taps: u32,
+    pub mode: i32,
+    pub taps_reversed: *const f64,
+}
+
 pub const DSPFX_ABI_VERSION: u32 = 2;
 pub const DSPFX_BUF_SIZE: u32 = 128; // dsp-stuff/src/node.rs:257
 pub const DSPFX_MAX_NODES: u32 = 32;
@@ -187,6 +207,8 @@ pub const DSPFX_SPECTRUM_MIN_FFT: u32 = 128;
 pub const DSPFX_SPECTRUM_MAX_FFT: u32 = 8192;
 // the most device frames one dspfx_resample_pull makes, and the most frames a FIFO slot holds
 pub const DSPFX_RESAMPLE_MAX_FRAMES: u32 = 4096;
+// the longest response a convolver bank takes: 4096 partitions of 128 taps
+pub const DSPFX_CONVOLVE_MAX_TAPS: u32 = 524288;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -352,4 +374,10 @@ extern "C" {
     pub fn dspfx_mixgroups_returns(m: *mut dspfx_mixgroups, block: *const f32, n_frames: u32, buses: *mut f32, returns: *mut f32, stream: *mut c_void) -> c_int;
     pub fn dspfx_mixgroups_set_gains(m: *mut dspfx_mixgroups, host_values: *const f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixgroups_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, depth_out: *mut u32) -> c_int;
+    pub fn dspfx_convolve_create(desc: *const dspfx_convolve_desc, out: *mut *mut dspfx_convolve) -> c_int;
+    pub fn dspfx_convolve_destroy(p: *mut dspfx_convolve) -> c_int;
+    pub fn dspfx_convolve_reset(p: *mut dspfx_convolve) -> c_int;
+    pub fn dspfx_convolve_run(p: *mut dspfx_convolve, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_convolve_set_taps(p: *mut dspfx_convolve, taps_reversed: *const f64, n_taps: u32, mode: c_int) -> c_int;
+    pub fn dspfx_convolve_plan(taps_reversed: *const f64, n_taps: u32, partitions: *mut u32, table_out: *mut f32) -> c_int;
 }

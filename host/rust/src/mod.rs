@@ -4,3 +4,4 @@ pub mod ffi;
 pub mod gpu_bank;
 pub mod gpu_chain;
 pub mod mix_groups;
+pub mod convolver;

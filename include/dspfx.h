@@ -890,6 +890,63 @@ int dspfx_mixgroups_set_gains(dspfx_mixgroups *m, const float *host_values, uint
 int dspfx_mixgroups_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
                          uint32_t *depth_out);
 
+/* ---- convolver bank: one long impulse response by partitioned FFT ----------------------------------------------
+ * The FIR node takes any WAV file as its impulse response (nodes/fir.rs:86-173); the engine restates that arithmetic in the
+ * direct form, which is the wrong algorithm for a room response of 24 000 to 144 000 taps.  This bank is the same node for N
+ * channels and ONE response of T taps by uniformly partitioned overlap-save: per channel and 128-frame block
+ *       y[n] = fl32(sum_{j<T} h[j] x[n - j]) * divisor          h[j] = taps_reversed[T - 1 - j]
+ * taps arrive time-reversed in f64 exactly as dspfx_set_taps takes them (fir.rs:163,168); divisor is 1.0f for
+ * DSPFX_FIR_BALANCED and 1.0f / (float)T for DSPFX_FIR_AVERAGE (fir.rs:187-190,222), one f32 multiplication after the sum.
+ * The sum is NOT the reference's order of operations (no order is restated: the kernels use fmaf): it is a 256-point real FFT
+ * of (previous block, this block) per block, kept in a ring of P_max spectra, Y[k] = sum_{p<P} H[p][k] X[head - p][k] over the
+ * P = ceil(T / 128) partitions of the response, and the last 128 samples of the inverse FFT.  Relative RMS error against the
+ * exact convolution is about 2e-7 at any length; the additions are in a fixed order that depends on P
+ * alone (a partial sum per 16 consecutive partitions, the partials in ascending order; no atomics), so the output is the
+ * same bits from run to run, on any stream, in either layout, and whatever the other channels carry.
+ * History: starts as silence, and dspfx_convolve_reset returns to silence -- the reference node after T samples of silence.
+ * The reference's FILL PHASE (while its deque is shorter than the taps it pairs the oldest held sample with taps[0]) is
+ * deliberately NOT restated.  The ring holds input spectra, not products: dspfx_convolve_set_taps replaces the response and
+ * keeps the history, which is the reference's reload behaviour.
+ * A spectrum is 128 complex f32: bins 1..127, and element 0 = (DC, Nyquist), both real, which multiplies component-wise.
+ * The response table H[p] = the 256-point FFT of taps h[128 p .. 128 p + 127], zero-padded, is computed on the host in f64 and
+ * rounded once to f32 (dspfx_convolve_plan gives it exactly as the device gets it).
+ * Memory: (P_max + 1) * 1024 * channels bytes of ring and accumulator plus 512 * channels of previous block -- under
+ * (P_max + 2) * 1024 * channels bytes -- plus P_max * 1024 of table, P_max = ceil(max_taps / 128): 375 KiB per channel at
+ * 48 000 taps, so a tool for G buses, not for 2^20 channels.  An allocation that fails is DSPFX_ERR_OOM, never an abort. */
+typedef struct dspfx_convolve dspfx_convolve;
+typedef struct dspfx_convolve_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t channels;        /* N */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t n_taps;          /* T: 1 ..= DSPFX_CONVOLVE_MAX_TAPS */
+    uint32_t max_taps;        /* ring slots are reserved for reloads of up to this many taps; 0 = n_taps */
+    int32_t mode;             /* dspfx_fir_mode */
+    const double *taps_reversed; /* host, [n_taps], read at create and copied; every tap finite */
+} dspfx_convolve_desc;
+/* The longest response the bank takes (10.9 s at 48 kHz, 4096 partitions). */
+#define DSPFX_CONVOLVE_MAX_TAPS 524288
+/* n_taps 0 or above DSPFX_CONVOLVE_MAX_TAPS, max_taps below n_taps or above the maximum, NULL or non-finite taps, an unknown
+ * mode, no channels, a tile that is not a power of two dividing N, another ABI version: DSPFX_ERR_INVALID.  All of that is
+ * checked before any device work. */
+int dspfx_convolve_create(const dspfx_convolve_desc *desc, dspfx_convolve **out);
+int dspfx_convolve_destroy(dspfx_convolve *p);
+/* Back to silence; takes effect ahead of the next run, in that run's stream order.  The response stays. */
+int dspfx_convolve_reset(dspfx_convolve *p);
+/* in, out: device blocks of n_frames frames in the desc's layout (the tiled form for a block of n_frames); n_frames is a
+ * multiple of 128 and is taken 128 frames at a time (anything else: DSPFX_ERR_INVALID before any device work).  out == in
+ * works in place; any other overlap is the caller's error.  Asynchronous on `stream`; a run on another stream than the one
+ * before first waits (on the device) for that one, since the history is the bank's (the rules of dspfx_mixgroups_run). */
+int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Replaces the response (and the mode) and keeps the history; takes effect from the next run in stream order: the call waits
+ * for the runs already submitted, which read the table in place -- a reload is a file load, not a per-block call.  More
+ * than max_taps, or anything dspfx_convolve_create refuses in a response: DSPFX_ERR_INVALID, nothing changed. */
+int dspfx_convolve_set_taps(dspfx_convolve *p, const double *taps_reversed, uint32_t n_taps, int mode);
+/* PURE HOST function (no GPU, no bank): *partitions = P = ceil(n_taps / 128), and table_out (NULL, or room for
+ * 128 * P * 2 floats) = the f32 response table exactly as the device gets it: element (k, p) at table_out[(k * P + p) * 2]
+ * (re) and + 1 (im), k in [0, 128), with (DC, Nyquist) of partition p at k = 0.  The same rules for the taps as create. */
+int dspfx_convolve_plan(const double *taps_reversed, uint32_t n_taps, uint32_t *partitions, float *table_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -476,4 +476,47 @@ inline std::vector<std::uint32_t> mixgroups_plan(const std::vector<std::uint64_t
     return depth;
 }
 
+// One long impulse response over N channels by partitioned FFT (dspfx_convolve_*): the FIR node's arithmetic for responses too
+// long for its tap table, e.g. a convolution reverb on the G buses of a MixGroups.  `taps_reversed` as dspfx_set_taps takes them.
+class Convolver {
+  public:
+    Convolver(std::uint32_t channels, const std::vector<double> &taps_reversed, int mode = DSPFX_FIR_BALANCED,
+              std::uint32_t max_taps = 0, std::uint32_t tile_channels = 0, int device = 0) {
+        const dspfx_convolve_desc d{DSPFX_ABI_VERSION, device, channels, tile_channels, (std::uint32_t)taps_reversed.size(), max_taps,
+                                    mode, taps_reversed.data()};
+        const int rc = dspfx_convolve_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+        partitions_ = partitions_of(taps_reversed);
+    }
+    ~Convolver() { dspfx_convolve_destroy(p_); }
+    Convolver(const Convolver &) = delete;
+    Convolver &operator=(const Convolver &) = delete;
+    // P = ceil(T / 128): the spectra of history one block reads per channel
+    std::uint32_t partitions() const { return partitions_; }
+    // device block of n_frames (a multiple of 128) -> device block `out` in the same layout (out == in: in place); asynchronous
+    void run(const float *in, float *out, std::uint32_t n_frames = DSPFX_BUF_SIZE, void *stream = nullptr) {
+        chk(dspfx_convolve_run(p_, in, out, n_frames, stream));
+    }
+    // replaces the response (at most max_taps long) and keeps the history; from the next run on
+    void set_taps(const std::vector<double> &taps_reversed, int mode = DSPFX_FIR_BALANCED) {
+        chk(dspfx_convolve_set_taps(p_, taps_reversed.data(), (std::uint32_t)taps_reversed.size(), mode));
+        partitions_ = partitions_of(taps_reversed);
+    }
+    void reset() { chk(dspfx_convolve_reset(p_)); }
+    dspfx_convolve *raw() { return p_; }
+
+  private:
+    static std::uint32_t partitions_of(const std::vector<double> &taps_reversed) {
+        std::uint32_t parts = 0;
+        const int rc = dspfx_convolve_plan(taps_reversed.data(), (std::uint32_t)taps_reversed.size(), &parts, nullptr);
+        if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+        return parts;
+    }
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    }
+    dspfx_convolve *p_ = nullptr;
+    std::uint32_t partitions_ = 0;
+};
+
 }  // namespace dspfx
