@@ -51,6 +51,7 @@ PITCH_WINDOW = 1024
 SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT = 128, 8192      # DSPFX_SPECTRUM_*: the Spectrogram node's fft_size slider (spectrogram.rs:142)
 SPECTRUM_RATE = 48000.0         # spectrogram.rs:238 sampling_rate: bin k of an n-point window is k * 48000 / n Hz
 CONVOLVE_MAX_TAPS = 524288      # DSPFX_CONVOLVE_MAX_TAPS: the longest response a Convolver takes (4096 partitions of 128)
+CONVOLVE_MAX_RESPONSES = 256    # DSPFX_CONVOLVE_MAX_RESPONSES: the responses one Convolver holds
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -75,7 +76,8 @@ EXPORTS = [
     "dspfx_mixgroups_create", "dspfx_mixgroups_destroy", "dspfx_mixgroups_last_error", "dspfx_mixgroups_run",
     "dspfx_mixgroups_set_gains", "dspfx_mixgroups_plan", "dspfx_mixgroups_returns",
     "dspfx_convolve_create", "dspfx_convolve_destroy", "dspfx_convolve_reset", "dspfx_convolve_run", "dspfx_convolve_set_taps",
-    "dspfx_convolve_plan",
+    "dspfx_convolve_plan", "dspfx_convolve_response_add", "dspfx_convolve_response_set", "dspfx_convolve_assign",
+    "dspfx_convolve_response_count",
 ]
 COMM_ID_BYTES = 128
 
@@ -281,6 +283,10 @@ def lib():
     L.dspfx_convolve_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
     L.dspfx_convolve_set_taps.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, C.c_int]
     L.dspfx_convolve_plan.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.dspfx_convolve_response_add.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]
+    L.dspfx_convolve_response_set.argtypes = [vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_int]
+    L.dspfx_convolve_assign.argtypes = [vp, C.POINTER(C.c_uint16), C.c_uint64, C.c_uint64]
+    L.dspfx_convolve_response_count.argtypes = [vp]
     _lib = L
     return L
 
@@ -1275,7 +1281,10 @@ class Convolver:
     responses too long for its tap table: a convolution reverb on the G buses of a MixGroups.  `impulse_response` is h in
     time order (as Engine.set_taps takes it); `max_taps` reserves history for later set_taps of longer responses (0 = this
     one's length).  Blocks are in the layout of `tile_channels` (as Engine's).  The history starts as silence.  Asynchronous on
-    `stream`."""
+    `stream`.
+    A bank may hold up to CONVOLVE_MAX_RESPONSES responses and an id per channel: `add_response` / `add_wav` give the next id
+    (the one given here is 0, and every channel starts on it), `assign` points channels at an id and keeps their history.
+    Each channel gets the bits a Convolver of its response alone would give it."""
 
     def __init__(self, channels: int, impulse_response, mode: int = FIR_BALANCED, max_taps: int = 0, tile_channels: int = 0,
                  device: int = 0):
@@ -1291,6 +1300,8 @@ class Convolver:
             self.h = C.c_void_p()
             raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
         self.n_taps, self.mode = len(t), int(mode)
+        self._responses = [(self.n_taps, self.mode)]                           # (taps, mode) of every response, by id
+        self._ids = np.zeros(self.channels, np.uint16)
 
     @classmethod
     def from_wav(cls, path: str, channels: int, resample: bool = True, **kw):
@@ -1323,6 +1334,59 @@ class Convolver:
         m = self.mode if mode is None else int(mode)
         self._chk(self.L.dspfx_convolve_set_taps(self.h, t.ctypes.data_as(C.POINTER(C.c_double)), len(t), m))
         self.n_taps, self.mode = len(t), m
+        self._responses[0] = (len(t), m)
+
+    def add_response(self, impulse_response, mode: int = FIR_BALANCED) -> int:
+        """One more response (at most max_taps long, h in time order) -> its id: 1, 2, ...  No channel carries it until `assign`
+        says so.  A file load: it allocates the table and waits for the runs already submitted."""
+        t = _taps_reversed(impulse_response)
+        rid = C.c_uint32()
+        self._chk(self.L.dspfx_convolve_response_add(self.h, t.ctypes.data_as(C.POINTER(C.c_double)), len(t), int(mode), C.byref(rid)))
+        self._responses.append((len(t), int(mode)))
+        return int(rid.value)
+
+    def add_wav(self, path: str, resample: bool = True, mode: int = FIR_BALANCED) -> int:
+        """add_response of a WAV file, loaded as from_wav loads it."""
+        from . import ir
+        return self.add_response(ir.load_impulse_response(path, resample=resample), mode)
+
+    def set_response(self, id: int, impulse_response, mode: Optional[int] = None):
+        """Replace response `id` (mode=None keeps its mode) and leave the others, the ids and the history alone; id 0 is set_taps."""
+        rid = int(id)
+        if not 0 <= rid < len(self._responses):
+            raise DspfxError(-1, f"the bank holds {len(self._responses)} responses: no id {rid}")
+        t = _taps_reversed(impulse_response)
+        m = self._responses[rid][1] if mode is None else int(mode)
+        self._chk(self.L.dspfx_convolve_response_set(self.h, rid, t.ctypes.data_as(C.POINTER(C.c_double)), len(t), m))
+        self._responses[rid] = (len(t), m)
+        if rid == 0:
+            self.n_taps, self.mode = len(t), m
+
+    def assign(self, ids, first_channel: int = 0):
+        """Point channels [first_channel, first_channel + len(ids)) at the responses `ids` (an int for one channel, or any
+        integer sequence, numpy array or torch tensor) and keep their history: from the next run on a channel sounds as if its
+        new response had been there all along.  An id the bank does not hold, or a range past the channels, stores nothing."""
+        if hasattr(ids, "detach"):
+            ids = ids.detach().cpu().numpy()
+        v = np.atleast_1d(np.asarray(ids)).reshape(-1)
+        if v.size and (v.dtype.kind not in "iu" or v.min() < 0 or v.max() > 0xFFFF):
+            raise DspfxError(-1, "response ids are integers in [0, responses)")
+        v = np.ascontiguousarray(v, np.uint16)
+        self._chk(self.L.dspfx_convolve_assign(self.h, v.ctypes.data_as(C.POINTER(C.c_uint16)), int(first_channel), len(v)))
+        self._ids[int(first_channel):int(first_channel) + len(v)] = v
+
+    @property
+    def responses(self) -> int:
+        """How many responses the bank holds (dspfx_convolve_response_count)."""
+        n = self.L.dspfx_convolve_response_count(self.h)
+        if n < 0:
+            self._chk(n)
+        return int(n)
+
+    @property
+    def response_of(self) -> np.ndarray:
+        """uint16[channels]: the response id of every channel (a host copy)."""
+        return self._ids.copy()
 
     def reset(self):
         """Back to silence (ahead of the next run)."""

@@ -14,6 +14,10 @@
 // the response table is [k][P] complex, read with scalar loads through the constant address space.
 // The forward and inverse kernels give a workgroup of 256 threads a RUN of 32 adjacent channels (every global access a whole
 // segment in both layouts); the 32 transforms live in one LDS buffer A[point][q] and are done in place, radix 4, 4, 4, 2.
+// A bank may hold several responses and an id per channel (dspfx_convolve_response_add / _assign).  With one response nothing
+// changes: the same kernels, the same launches.  With more, convolve_accumulate_multi reads the ids: a wave whose channels
+// all carry one id takes accumulate_wave exactly as above with that response's table and P; a mixed wave runs it once per
+// distinct id with the other lanes masked off; convolve_inverse_multi takes the divisor per channel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -243,7 +247,17 @@ __global__ __launch_bounds__(ST) void convolve_forward(FftArgs a) {
     }
 }
 
-__global__ __launch_bounds__(ST) void convolve_inverse(FftArgs a) {
+// the responses of a bank that holds more than one, as the kernels read them (one device copy per bank)
+struct Responses {
+    const float2 *table[DSPFX_CONVOLVE_MAX_RESPONSES];   // [128][P] each
+    uint32_t P[DSPFX_CONVOLVE_MAX_RESPONSES];
+    float divisor[DSPFX_CONVOLVE_MAX_RESPONSES];
+};
+typedef const __attribute__((address_space(4))) Responses *ResponsesPtr;   // wave-uniform index: scalar loads
+
+// MULTI: the divisor is the one of each channel's response (ids [N], every id below the bank's response count)
+template <bool MULTI>
+__device__ __forceinline__ void inverse_block(FftArgs a, const uint16_t *ids, const Responses *resp) {
     __shared__ __attribute__((aligned(16))) float2 A[M * Q];
     float4 *A4 = (float4 *)A;
     const int t = threadIdx.x;
@@ -292,12 +306,26 @@ __global__ __launch_bounds__(ST) void convolve_inverse(FftArgs a) {
     for (int i = 0; i < UN / 2; ++i) {
         const uint32_t u = t + i * ST, j = M / 2 + u / (Q / 4), h = u % (Q / 4), c = c0 + 4 * h;
         const float4 z0 = A4[(j * (Q / 4) + h) * 2], z1 = A4[(j * (Q / 4) + h) * 2 + 1];
-        const float d = a.divisor;
-        const float4 e = make_float4(z0.x * SCALE * d, z0.z * SCALE * d, z1.x * SCALE * d, z1.z * SCALE * d);
-        const float4 o = make_float4(-z0.y * SCALE * d, -z0.w * SCALE * d, -z1.y * SCALE * d, -z1.w * SCALE * d);
+        float d0, d1, d2, d3;
+        if (MULTI) {                                     // channels outside N are not stored
+            d0 = c < a.N ? resp->divisor[ids[c]] : 1.0f;
+            d1 = c + 1 < a.N ? resp->divisor[ids[c + 1]] : 1.0f;
+            d2 = c + 2 < a.N ? resp->divisor[ids[c + 2]] : 1.0f;
+            d3 = c + 3 < a.N ? resp->divisor[ids[c + 3]] : 1.0f;
+        } else {
+            d0 = d1 = d2 = d3 = a.divisor;
+        }
+        const float4 e = make_float4(z0.x * SCALE * d0, z0.z * SCALE * d1, z1.x * SCALE * d2, z1.z * SCALE * d3);
+        const float4 o = make_float4(-z0.y * SCALE * d0, -z0.w * SCALE * d1, -z1.y * SCALE * d2, -z1.w * SCALE * d3);
         store4<true>(a.out, e, a.vec, a.f0 + 2 * j - L, c, a.nf, a.N, a.W);
         store4<true>(a.out, o, a.vec, a.f0 + 2 * j - L + 1, c, a.nf, a.N, a.W);
     }
+}
+
+__global__ __launch_bounds__(ST) void convolve_inverse(FftArgs a) { inverse_block<false>(a, nullptr, nullptr); }
+
+__global__ __launch_bounds__(ST) void convolve_inverse_multi(FftArgs a, const uint16_t *ids, const Responses *resp) {
+    inverse_block<true>(a, ids, resp);
 }
 
 // ---- the accumulation -----------------------------------------------------------------------------------------------
@@ -393,6 +421,69 @@ __global__ __launch_bounds__(64 * AW) void convolve_accumulate(AccArgs a) {
     else accumulate_wave<V, false>(a, k, c);
 }
 
+// ---- the accumulation of a bank with more than one response --------------------------------------------------------
+struct MultiArgs {
+    AccArgs a;                   // table and P are not used: they are the response's
+    const uint16_t *ids;         // [N]: the response of every channel, every id below the bank's response count
+    const Responses *resp;
+};
+
+// accumulate_wave for the active lanes with response r (wave-uniform): its table and its own P, so the order of additions of
+// a channel is the one of a single-response bank of that response
+template <int V, bool DC>
+__device__ __forceinline__ void accumulate_as(const MultiArgs &m, uint32_t r, uint32_t k, uint32_t c) {
+    const ResponsesPtr rp = (ResponsesPtr)m.resp;
+    AccArgs b = m.a;
+    b.table = rp->table[r];
+    b.P = rp->P[r];
+    accumulate_wave<V, DC>(b, k, c);
+}
+
+// the lanes of `todo`, one distinct id at a time: the id of the first lane left, the lanes that carry it, the rest masked off
+template <int V, bool DC>
+__device__ __forceinline__ void accumulate_by_id(const MultiArgs &m, bool todo, uint32_t id, uint32_t k, uint32_t c) {
+    for (uint64_t left = __builtin_amdgcn_ballot_w64(todo); left; left = __builtin_amdgcn_ballot_w64(todo)) {
+        const uint32_t r = __builtin_amdgcn_readlane(id, __builtin_ctzll(left));
+        if (todo && id == r) {                           // in here id IS r; read it back so that it stays a scalar: the compiler
+            accumulate_as<V, DC>(m, __builtin_amdgcn_readfirstlane(id), k, c);   // would put the lane's id in its place
+            todo = false;
+        }
+    }
+}
+
+// MIXED = false: the host saw that no wave of this launch carries two ids (wave_span), and only the single bank's path is
+// compiled in, at the single bank's registers
+template <int V, bool DC, bool MIXED>
+__device__ __forceinline__ void accumulate_multi(const MultiArgs &m, uint32_t k, uint32_t c) {
+    uint32_t i0, i1;                                     // the ids of the lane's channels (V = 1: one channel)
+    if (V == 2) {
+        const uint32_t w = *(const uint32_t *)(m.ids + c);   // c is even
+        i0 = w & 0xFFFFu;
+        i1 = w >> 16;
+    } else {
+        i0 = i1 = m.ids[c];
+    }
+    const uint32_t r = __builtin_amdgcn_readfirstlane(i0);
+    if (!MIXED || __builtin_amdgcn_ballot_w64(i0 != r || i1 != r) == 0) {   // one response for the whole wave: the single bank's path
+        accumulate_as<V, DC>(m, r, k, c);
+        return;
+    }
+    accumulate_by_id<V, DC>(m, i0 == i1, i0, k, c);
+    if (V == 2) {                                        // a lane whose two channels differ: one channel at a time
+        accumulate_by_id<1, DC>(m, i0 != i1, i0, k, c);
+        accumulate_by_id<1, DC>(m, i0 != i1, i1, k, c + 1);
+    }
+}
+
+template <int V, bool MIXED>
+__global__ __launch_bounds__(64 * AW) void convolve_accumulate_multi(MultiArgs m) {
+    const uint32_t k = __builtin_amdgcn_readfirstlane(blockIdx.y * AW + threadIdx.x / 64);
+    const uint32_t c = (blockIdx.x * 64 + (threadIdx.x & 63)) * V;
+    if (c >= m.a.N) return;
+    if (k == 0) accumulate_multi<V, true, MIXED>(m, k, c);
+    else accumulate_multi<V, false, MIXED>(m, k, c);
+}
+
 bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
 
 uint32_t partitions_of(uint32_t n_taps) { return (n_taps + L - 1) / L; }
@@ -440,9 +531,16 @@ void make_table(const double *taps_reversed, uint32_t n_taps, float *table) {
 
 }  // namespace
 
+// a response beyond the first: the first lives in the bank's own fields (P, divisor, table; desc.n_taps, desc.mode)
+struct Extra {
+    float2 *table = nullptr;                    // room for [128][slots]; in use: [128][P]
+    uint32_t P = 0;
+    float divisor = 1.0f;
+};
+
 struct dspfx_convolve {
     dspfx_convolve_desc desc{};
-    std::mutex mu;                              // run / set_taps / reset / destroy are serialised
+    std::mutex mu;                              // run / set_taps / response_* / assign / reset / destroy are serialised
     uint32_t slots = 0;                         // P_max = partitions of max_taps
     uint32_t P = 0;                             // partitions of the response in use
     float divisor = 1.0f;
@@ -456,6 +554,12 @@ struct dspfx_convolve {
     bool silence = false;                       // the next run clears the history first
     hipStream_t last = nullptr;
     bool used = false;
+    // more than one response (dspfx_convolve_response_add): made by the first add, absent before it
+    std::vector<Extra> extra;                   // responses 1, 2, ...
+    std::vector<uint16_t> ids_host;             // [N]: the map as the device has it
+    uint16_t *ids = nullptr;                    // [N]
+    Responses *resp = nullptr;                  // tables, P and divisors as the kernels read them
+    bool mixed = false;                         // some wave of the accumulation carries more than one id
 };
 
 namespace {
@@ -467,6 +571,10 @@ void release(dspfx_convolve *p) {
     if (p->acc) (void)hipFree(p->acc);
     if (p->table) (void)hipFree(p->table);
     if (p->tw) (void)hipFree(p->tw);
+    for (Extra &e : p->extra)
+        if (e.table) (void)hipFree(e.table);
+    if (p->ids) (void)hipFree(p->ids);
+    if (p->resp) (void)hipFree(p->resp);
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
 }
@@ -487,6 +595,64 @@ size_t ring_bytes(const dspfx_convolve *p) { return (size_t)p->slots * M * p->de
 size_t prev_bytes(const dspfx_convolve *p) { return (size_t)L * p->desc.channels * sizeof(float); }
 
 float divisor_of(int mode, uint32_t n_taps) { return mode == DSPFX_FIR_AVERAGE ? 1.0f / (float)n_taps : 1.0f; }
+
+// the channels of one wave of the accumulation
+uint32_t wave_span(uint32_t N) { return N % 2 == 0 ? 128 : 64; }
+
+bool any_mixed_wave(const std::vector<uint16_t> &ids) {
+    const size_t span = wave_span((uint32_t)ids.size());
+    for (size_t c = 0; c < ids.size(); ++c)
+        if (ids[c] != ids[c - c % span]) return true;
+    return false;
+}
+
+uint32_t response_count(const dspfx_convolve *p) { return 1 + (uint32_t)p->extra.size(); }
+
+// a host array to the device behind the runs already submitted (they are ordered on the last stream used); done on return
+hipError_t upload(dspfx_convolve *p, void *dst, const void *src, size_t bytes) {
+    const hipStream_t s = p->used ? p->last : nullptr;
+    const hipError_t err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    return err == hipSuccess ? hipStreamSynchronize(s) : err;
+}
+
+// the device's copy of what the kernels read per response, from the host's
+hipError_t upload_responses(dspfx_convolve *p) {
+    std::vector<Responses> r(1);
+    std::memset(r.data(), 0, sizeof(Responses));
+    r[0].table[0] = p->table;
+    r[0].P[0] = p->P;
+    r[0].divisor[0] = p->divisor;
+    for (size_t i = 0; i < p->extra.size(); ++i) {
+        r[0].table[i + 1] = p->extra[i].table;
+        r[0].P[i + 1] = p->extra[i].P;
+        r[0].divisor[i + 1] = p->extra[i].divisor;
+    }
+    return upload(p, p->resp, r.data(), sizeof(Responses));
+}
+
+// response `id` of the bank := these taps and this mode (checked by the caller, the lock held); the history stays
+int store_response(dspfx_convolve *p, uint32_t id, const double *taps_reversed, uint32_t n_taps, int mode) {
+    const uint32_t P = partitions_of(n_taps);
+    std::vector<float> table((size_t)M * P * 2);
+    make_table(taps_reversed, n_taps, table.data());
+    if (hipSetDevice(p->desc.device) != hipSuccess) return DSPFX_ERR_HIP;
+    // the runs already submitted read the table in place: they finish first, then it is replaced (a reload is a file load, not
+    // a per-block call); the ring holds input spectra, so the history stays
+    if (p->used && hipStreamSynchronize(p->last) != hipSuccess) return DSPFX_ERR_HIP;
+    float2 *dst = id ? p->extra[id - 1].table : p->table;
+    if (hipMemcpy(dst, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return DSPFX_ERR_HIP;
+    if (id) {
+        p->extra[id - 1].P = P;
+        p->extra[id - 1].divisor = divisor_of(mode, n_taps);
+    } else {
+        p->P = P;
+        p->desc.n_taps = n_taps;
+        p->desc.mode = mode;
+        p->divisor = divisor_of(mode, n_taps);
+    }
+    if (p->resp && upload_responses(p) != hipSuccess) return DSPFX_ERR_HIP;
+    return DSPFX_OK;
+}
 
 }  // namespace
 
@@ -577,25 +743,86 @@ extern "C" int dspfx_convolve_reset(dspfx_convolve *p) {
 }
 
 extern "C" int dspfx_convolve_set_taps(dspfx_convolve *p, const double *taps_reversed, uint32_t n_taps, int mode) {
+    return dspfx_convolve_response_set(p, 0, taps_reversed, n_taps, mode);
+}
+
+extern "C" int dspfx_convolve_response_set(dspfx_convolve *p, uint32_t id, const double *taps_reversed, uint32_t n_taps, int mode) {
     if (!p) return DSPFX_ERR_INVALID;
     if (mode != DSPFX_FIR_BALANCED && mode != DSPFX_FIR_AVERAGE) return DSPFX_ERR_INVALID;
     const int rc = check_taps(taps_reversed, n_taps);
     if (rc != DSPFX_OK) return rc;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (n_taps > p->desc.max_taps) return DSPFX_ERR_INVALID;
-    const uint32_t P = partitions_of(n_taps);
-    std::vector<float> table((size_t)M * P * 2);
-    make_table(taps_reversed, n_taps, table.data());
+    if (n_taps > p->desc.max_taps || id >= response_count(p)) return DSPFX_ERR_INVALID;
+    return store_response(p, id, taps_reversed, n_taps, mode);
+}
+
+extern "C" int dspfx_convolve_response_add(dspfx_convolve *p, const double *taps_reversed, uint32_t n_taps, int mode,
+                                           uint32_t *id_out) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (mode != DSPFX_FIR_BALANCED && mode != DSPFX_FIR_AVERAGE) return DSPFX_ERR_INVALID;
+    const int rc = check_taps(taps_reversed, n_taps);
+    if (rc != DSPFX_OK) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (n_taps > p->desc.max_taps || response_count(p) >= DSPFX_CONVOLVE_MAX_RESPONSES) return DSPFX_ERR_INVALID;
     CONV_HIP(hipSetDevice(p->desc.device));
-    // the runs already submitted read the table in place: they finish first, then it is replaced (a reload is a file load, not
-    // a per-block call); the ring holds input spectra, so the history stays
-    if (p->used) CONV_HIP(hipStreamSynchronize(p->last));
-    CONV_HIP(hipMemcpy(p->table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
-    p->P = P;
-    p->desc.n_taps = n_taps;
-    p->desc.mode = mode;
-    p->divisor = divisor_of(mode, n_taps);
+    const uint32_t N = p->desc.channels;
+    if (!p->resp) {                              // the first add: the map (every channel on response 0) and the kernels' view
+        uint16_t *ids = nullptr;
+        Responses *resp = nullptr;
+        if (hipMalloc((void **)&ids, (size_t)N * sizeof(uint16_t)) != hipSuccess ||
+            hipMalloc((void **)&resp, sizeof(Responses)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ids) (void)hipFree(ids);
+            return DSPFX_ERR_OOM;
+        }
+        if (hipMemset(ids, 0, (size_t)N * sizeof(uint16_t)) != hipSuccess || hipMemset(resp, 0, sizeof(Responses)) != hipSuccess) {
+            (void)hipFree(ids);
+            (void)hipFree(resp);
+            return DSPFX_ERR_HIP;
+        }
+        p->ids_host.assign(N, 0);
+        p->ids = ids;
+        p->resp = resp;
+    }
+    Extra e;
+    if (hipMalloc((void **)&e.table, (size_t)M * p->slots * sizeof(float2)) != hipSuccess) {
+        (void)hipGetLastError();
+        return DSPFX_ERR_OOM;                    // a bank of one response with a map of zeros runs as before
+    }
+    p->extra.push_back(e);
+    const uint32_t id = response_count(p) - 1;
+    const int st = store_response(p, id, taps_reversed, n_taps, mode);
+    if (st != DSPFX_OK) {
+        p->extra.pop_back();
+        (void)hipFree(e.table);
+        (void)upload_responses(p);
+        return st;
+    }
+    if (id_out) *id_out = id;
     return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_assign(dspfx_convolve *p, const uint16_t *host_ids, uint64_t first_channel, uint64_t count) {
+    if (!p || !host_ids || count == 0) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const uint64_t N = p->desc.channels;
+    if (first_channel >= N || count > N - first_channel) return DSPFX_ERR_INVALID;
+    const uint32_t R = response_count(p);
+    for (uint64_t i = 0; i < count; ++i)
+        if (host_ids[i] >= R) return DSPFX_ERR_INVALID;
+    if (!p->ids) return DSPFX_OK;                // one response: every id is 0, which is what a bank without a map runs
+    CONV_HIP(hipSetDevice(p->desc.device));
+    // in the order of the bank's last stream: behind every run submitted before, ahead of every run submitted after
+    CONV_HIP(upload(p, p->ids + first_channel, host_ids, (size_t)count * sizeof(uint16_t)));
+    std::copy(host_ids, host_ids + count, p->ids_host.begin() + (size_t)first_channel);
+    p->mixed = any_mixed_wave(p->ids_host);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_convolve_response_count(const dspfx_convolve *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<dspfx_convolve *>(p)->mu);
+    return (int)response_count(p);
 }
 
 extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out, uint32_t n_frames, void *stream) {
@@ -629,6 +856,7 @@ extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out
     a.P = p->P;
     a.slots = p->slots;
     const unsigned fft_blocks = (N + Q - 1) / Q;
+    const bool multi = !p->extra.empty();       // one response: the kernels and launches of a bank that never had more
     for (uint32_t f0 = 0; f0 < n_frames; f0 += L) {
         const uint32_t head = (uint32_t)(p->blocks % p->slots);
         f.f0 = f0;
@@ -637,13 +865,25 @@ extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out
         CONV_HIP(hipGetLastError());
         p->blocks += 1;                          // the slot is written: a failure further on leaves a consistent history
         a.head = head;
-        if (N % 2 == 0)
-            convolve_accumulate<2><<<dim3((N / 2 + 63) / 64, M / AW), 64 * AW, 0, s>>>(a);
-        else
-            convolve_accumulate<1><<<dim3((N + 63) / 64, M / AW), 64 * AW, 0, s>>>(a);
-        CONV_HIP(hipGetLastError());
+        const dim3 acc_grid(N % 2 == 0 ? (N / 2 + 63) / 64 : (N + 63) / 64, M / AW);
         f.spec = p->acc;
-        convolve_inverse<<<fft_blocks, ST, 0, s>>>(f);
+        if (!multi) {
+            if (N % 2 == 0) convolve_accumulate<2><<<acc_grid, 64 * AW, 0, s>>>(a);
+            else convolve_accumulate<1><<<acc_grid, 64 * AW, 0, s>>>(a);
+            CONV_HIP(hipGetLastError());
+            convolve_inverse<<<fft_blocks, ST, 0, s>>>(f);
+        } else {
+            const MultiArgs m{a, p->ids, p->resp};
+            if (N % 2 == 0) {
+                if (p->mixed) convolve_accumulate_multi<2, true><<<acc_grid, 64 * AW, 0, s>>>(m);
+                else convolve_accumulate_multi<2, false><<<acc_grid, 64 * AW, 0, s>>>(m);
+            } else {
+                if (p->mixed) convolve_accumulate_multi<1, true><<<acc_grid, 64 * AW, 0, s>>>(m);
+                else convolve_accumulate_multi<1, false><<<acc_grid, 64 * AW, 0, s>>>(m);
+            }
+            CONV_HIP(hipGetLastError());
+            convolve_inverse_multi<<<fft_blocks, ST, 0, s>>>(f, p->ids, p->resp);
+        }
         CONV_HIP(hipGetLastError());
     }
     return DSPFX_OK;

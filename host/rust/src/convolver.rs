@@ -49,6 +49,9 @@ impl Convolver {
         Ok(Convolver { h, channels, partitions })
     }
     pub fn channels(&self) -> u32 { self.channels }
+    /// The bank's handle, for the calls kept in `convolver_responses.rs`.
+    pub(super) fn handle(&self) -> *mut dspfx_convolve { self.h }
+    pub(super) fn set_partitions(&mut self, partitions: u32) { self.partitions = partitions; }
     /// P = ceil(T / 128): the spectra of history one block reads per channel.
     pub fn partitions(&self) -> u32 { self.partitions }
     /// A DEVICE block of `n_frames` frames (a multiple of 128) in the bank's layout into the DEVICE block `out` (which may be

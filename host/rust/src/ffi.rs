@@ -209,6 +209,8 @@ pub const DSPFX_SPECTRUM_MAX_FFT: u32 = 8192;
 pub const DSPFX_RESAMPLE_MAX_FRAMES: u32 = 4096;
 // the longest response a convolver bank takes: 4096 partitions of 128 taps
 pub const DSPFX_CONVOLVE_MAX_TAPS: u32 = 524288;
+// the responses one convolver bank holds
+pub const DSPFX_CONVOLVE_MAX_RESPONSES: u32 = 256;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -380,4 +382,8 @@ extern "C" {
     pub fn dspfx_convolve_run(p: *mut dspfx_convolve, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
     pub fn dspfx_convolve_set_taps(p: *mut dspfx_convolve, taps_reversed: *const f64, n_taps: u32, mode: c_int) -> c_int;
     pub fn dspfx_convolve_plan(taps_reversed: *const f64, n_taps: u32, partitions: *mut u32, table_out: *mut f32) -> c_int;
+    pub fn dspfx_convolve_response_add(p: *mut dspfx_convolve, taps_reversed: *const f64, n_taps: u32, mode: c_int, id_out: *mut u32) -> c_int;
+    pub fn dspfx_convolve_response_set(p: *mut dspfx_convolve, id: u32, taps_reversed: *const f64, n_taps: u32, mode: c_int) -> c_int;
+    pub fn dspfx_convolve_assign(p: *mut dspfx_convolve, host_ids: *const u16, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_convolve_response_count(p: *const dspfx_convolve) -> c_int;
 }

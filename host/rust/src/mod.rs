@@ -5,3 +5,4 @@ pub mod gpu_bank;
 pub mod gpu_chain;
 pub mod mix_groups;
 pub mod convolver;
+pub mod convolver_responses;

@@ -946,6 +946,39 @@ int dspfx_convolve_set_taps(dspfx_convolve *p, const double *taps_reversed, uint
  * 128 * P * 2 floats) = the f32 response table exactly as the device gets it: element (k, p) at table_out[(k * P + p) * 2]
  * (re) and + 1 (im), k in [0, 128), with (DC, Nyquist) of partition p at k = 0.  The same rules for the taps as create. */
 int dspfx_convolve_plan(const double *taps_reversed, uint32_t n_taps, uint32_t *partitions, float *table_out);
+/* Several responses, one per channel.  A bank holds up to DSPFX_CONVOLVE_MAX_RESPONSES responses and a response id for every
+ * channel: response 0 is the one given at create (the one dspfx_convolve_set_taps replaces) and every channel starts on it, so
+ * a bank on which none of the calls below is made runs, launches and costs what it did without them.  The use is a small set
+ * of halls shared by many buses -- this room a booth, that one a church -- not a table per channel.
+ * Contract: channel c carrying id r gets THE SAME BITS as the same channel of a bank created with response r alone (its taps,
+ * its mode) and fed the same input since the last reset -- in either layout, in place, 128 or 256 frames a call, after a reset,
+ * and whatever ids and data its neighbours carry.  The partitions read for c are the response's own P_r = ceil(n_taps_r / 128)
+ * (no padding to the longest response), so the order of additions stays a function of P_r alone and a NaN sample leaves the
+ * channel after P_r + 1 blocks; the Average divisor is the response's own 1.0f / (float)n_taps_r.  The ring holds input
+ * spectra, so pointing a channel at another response keeps its history: from the next run on its output is what a bank of the
+ * new response alone would give on the same input history.  The ids are a uint16_t per channel (256 halls fit four times
+ * over; the value is the cap on what one bank allocates).
+ * Memory: each response beyond the first adds P_max * 1024 bytes of table (375 KiB at 48 000 taps, 94 MiB for 256 of them),
+ * and the first one added 2 * channels + 4096 bytes of ids and per-response parameters. */
+#define DSPFX_CONVOLVE_MAX_RESPONSES 256
+/* Adds a response under dspfx_convolve_set_taps's rules (finite taps, 1 <= n_taps <= the bank's max_taps, a known mode) and
+ * gives its id -- 1, 2, ... -- in *id_out (which may be NULL).  No channel carries it until dspfx_convolve_assign says so.
+ * DSPFX_ERR_INVALID once the bank holds DSPFX_CONVOLVE_MAX_RESPONSES; DSPFX_ERR_OOM when the table cannot be allocated; either
+ * way nothing changed.  Allocates on the calling thread and waits for the runs already submitted: a file load, not a
+ * per-block call. */
+int dspfx_convolve_response_add(dspfx_convolve *p, const double *taps_reversed, uint32_t n_taps, int mode, uint32_t *id_out);
+/* Replaces response `id` (and its mode) and leaves the other responses, the ids and the history alone; id 0 is
+ * dspfx_convolve_set_taps, the same operation.  An id the bank does not hold: DSPFX_ERR_INVALID, nothing changed. */
+int dspfx_convolve_response_set(dspfx_convolve *p, uint32_t id, const double *taps_reversed, uint32_t n_taps, int mode);
+/* Stores the ids of channels [first_channel, first_channel + count) from a host array.  An id at or above
+ * dspfx_convolve_response_count, or a range past the bank's channels: DSPFX_ERR_INVALID and NOTHING is stored.  Serialised
+ * with dspfx_convolve_run under the bank's lock: it holds for every run submitted after it returns and for none submitted
+ * before (the copy travels in the order of the bank's last stream, and the call waits for it).  The history stays. */
+int dspfx_convolve_assign(dspfx_convolve *p, const uint16_t *host_ids, uint64_t first_channel, uint64_t count);
+/* The responses the bank holds (1 after create), or DSPFX_ERR_INVALID for a NULL bank. */
+int dspfx_convolve_response_count(const dspfx_convolve *p);
+/* In all four, the checks that need no device -- a NULL bank, NULL taps or ids, count == 0, the mode, the rules for the taps
+ * -- come first and return DSPFX_ERR_INVALID with or without a GPU. */
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ struct Error : std::runtime_error {
 };
 
 constexpr std::size_t BUF_SIZE = DSPFX_BUF_SIZE;   // node.rs:257
+constexpr std::uint32_t CONVOLVE_MAX_RESPONSES = DSPFX_CONVOLVE_MAX_RESPONSES;   // the responses one Convolver holds
 
 // nodes/distort.rs:18-28
 enum class Mode : int { HardClip = 0, SoftClip, Tanh, RecipSoftClip, Fuzz, Sin, Atan, Square, Chebyshev4 };
@@ -503,6 +504,28 @@ class Convolver {
         partitions_ = partitions_of(taps_reversed);
     }
     void reset() { chk(dspfx_convolve_reset(p_)); }
+    // one more response (at most max_taps long) -> its id: 1, 2, ...; no channel carries it until assign says so
+    std::uint32_t add_response(const std::vector<double> &taps_reversed, int mode = DSPFX_FIR_BALANCED) {
+        std::uint32_t id = 0;
+        chk(dspfx_convolve_response_add(p_, taps_reversed.data(), (std::uint32_t)taps_reversed.size(), mode, &id));
+        return id;
+    }
+    // replaces response `id` and leaves the others, the ids and the history alone; id 0 is set_taps
+    void set_response(std::uint32_t id, const std::vector<double> &taps_reversed, int mode = DSPFX_FIR_BALANCED) {
+        chk(dspfx_convolve_response_set(p_, id, taps_reversed.data(), (std::uint32_t)taps_reversed.size(), mode));
+        if (id == 0) partitions_ = partitions_of(taps_reversed);
+    }
+    // channels [first_channel, first_channel + ids.size()) carry these responses from the next run on; the history stays
+    void assign(const std::vector<std::uint16_t> &ids, std::uint64_t first_channel = 0) {
+        chk(dspfx_convolve_assign(p_, ids.data(), first_channel, ids.size()));
+    }
+    void assign(std::uint16_t id, std::uint64_t first_channel) { chk(dspfx_convolve_assign(p_, &id, first_channel, 1)); }
+    // how many responses the bank holds (at most CONVOLVE_MAX_RESPONSES)
+    std::uint32_t responses() const {
+        const int n = dspfx_convolve_response_count(p_);
+        if (n < 0) throw Error(n, dspfx_strerror(n));
+        return (std::uint32_t)n;
+    }
     dspfx_convolve *raw() { return p_; }
 
   private:
