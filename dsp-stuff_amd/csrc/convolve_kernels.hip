@@ -13,7 +13,7 @@
 // Ring layout [slot][k][N] complex, so in the accumulation consecutive lanes are consecutive channels and H is wave-uniform;
 // the response table is [k][P] complex, read with scalar loads through the constant address space.
 // The forward and inverse kernels give a workgroup of 256 threads a RUN of 32 adjacent channels (every global access a whole
-// segment in both layouts); the 32 transforms live in one LDS buffer A[point][q] and are done in place, radix 4, 4, 4, 2.
+// segment in both layouts); the 32 transforms are done in place in one LDS buffer A[point][q]: fft_core.hip.h.
 // A bank may hold several responses and an id per channel (dspfx_convolve_response_add / _assign).  With one response nothing
 // changes: the same kernels, the same launches.  With more, convolve_accumulate_multi reads the ids: a wave whose channels
 // all carry one id takes accumulate_wave exactly as above with that response's table and P; a mixed wave runs it once per
@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
+#include "bank_common.hip.h"
+#include "fft_core.hip.h"
 
 namespace {
 
@@ -39,66 +41,10 @@ constexpr int GROUP = 16;                          // partitions per partial sum
 constexpr int AW = 4;                              // waves (= values of k) per workgroup of the accumulation
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) float *TablePtr;   // wave-uniform index: scalar loads
 
-// element (f, c) of a block of nf frames in the desc's layout (dspfx_engine_desc.tile_channels)
-__host__ __device__ inline size_t lay(uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
-    return W ? ((size_t)(c / W) * nf + f) * W + (c % W) : (size_t)f * N + c;
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// one in-place Stockham pass of radix R over the Q transforms of 128 points in A[point][q]; NS = the product of the radices
-// before it; tw[t] = exp(-2 pi i t / 256)
-template <int R, int NS>
-__device__ __forceinline__ void fft_pass(float2 *A, const float2 *__restrict__ tw) {
-    constexpr int NR = M / R, IT = NR * Q / ST;
-    static_assert(NR * Q % ST == 0, "every thread does the same number of butterflies");
-    float2 v[IT][R];
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-        const int b = threadIdx.x + i * ST, q = b % Q, j = b / Q;
-#pragma unroll
-        for (int r = 0; r < R; ++r) v[i][r] = A[(j + r * NR) * Q + q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-        const int b = threadIdx.x + i * ST, q = b % Q, j = b / Q;
-        const int k = j & (NS - 1);
-        float2 *u = v[i];
-        if (NS > 1) {
-#pragma unroll
-            for (int r = 1; r < R; ++r) u[r] = cmul(u[r], tw[2 * (k * r * (M / (NS * R)))]);
-        }
-        if (R == 2) {
-            const float2 a = u[0];
-            u[0] = cadd(a, u[1]);
-            u[1] = csub(a, u[1]);
-        } else {
-            const float2 a0 = cadd(u[0], u[2]), a1 = csub(u[0], u[2]), a2 = cadd(u[1], u[3]), a3 = csub(u[1], u[3]);
-            const float2 ja3 = make_float2(a3.y, -a3.x);                                   // -i * a3
-            u[0] = cadd(a0, a2);
-            u[1] = cadd(a1, ja3);
-            u[2] = csub(a0, a2);
-            u[3] = csub(a1, ja3);
-        }
-        const int d = (j - k) * R + k;
-#pragma unroll
-        for (int r = 0; r < R; ++r) A[(d + r * NS) * Q + q] = u[r];
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void fft128(float2 *A, const float2 *__restrict__ tw) {
-    fft_pass<4, 1>(A, tw);
-    fft_pass<4, 4>(A, tw);
-    fft_pass<4, 16>(A, tw);
-    fft_pass<2, 64>(A, tw);
-}
+// the 128-point transform of the workgroup's 32 channels, radix 4, 4, 4, 2; tw[t] = exp(-2 pi i t / 256)
+__device__ __forceinline__ void fft128(float2 *A, const float2 *__restrict__ tw) { fft_all<7, Q, ST, 1>(A, tw); }
 
 struct FftArgs {
     const float *in;             // forward: the caller's block of nf frames
@@ -110,41 +56,6 @@ struct FftArgs {
     uint32_t vec;                // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N
     float divisor;
 };
-
-// frame f of 4 channels from c (c a multiple of 4) of a block at `base`; channels outside N read 0
-__device__ __forceinline__ float4 load4(const float *base, uint32_t vec, uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (vec) {
-        if (c < N) v = *(const float4 *)(base + lay(f, c, nf, N, W));
-    } else {
-        if (c < N) v.x = base[lay(f, c, nf, N, W)];
-        if (c + 1 < N) v.y = base[lay(f, c + 1, nf, N, W)];
-        if (c + 2 < N) v.z = base[lay(f, c + 2, nf, N, W)];
-        if (c + 3 < N) v.w = base[lay(f, c + 3, nf, N, W)];
-    }
-    return v;
-}
-
-template <bool NT>
-__device__ __forceinline__ void store4(float *base, float4 v, uint32_t vec, uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
-    if (vec) {
-        if (c < N) {
-            f32x4 *p = (f32x4 *)(base + lay(f, c, nf, N, W));
-            const f32x4 t = {v.x, v.y, v.z, v.w};
-            if (NT) __builtin_nontemporal_store(t, p);
-            else *p = t;
-        }
-    } else {
-        const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i)
-            if (c + i < N) {
-                float *p = base + lay(f, c + i, nf, N, W);
-                if (NT) __builtin_nontemporal_store(e[i], p);
-                else *p = e[i];
-            }
-    }
-}
 
 // the spectrum values of 4 channels at one k: element (k, c + i) of a [128][N] complex array
 __device__ __forceinline__ void load_spec4(const float2 *spec, uint32_t vec, uint32_t k, uint32_t c, uint32_t N, float4 &lo, float4 &hi) {
@@ -178,7 +89,8 @@ __device__ __forceinline__ void store_spec4(float2 *spec, uint32_t vec, uint32_t
     }
 }
 
-// X[k] of one channel from Z[k] and Z[(128 - k) & 127]; k = 0 gives the packed (DC, Nyquist)
+// X[k] of one channel from Z[k] and Z[(128 - k) & 127]; k = 0 gives the packed (DC, Nyquist).  Not spectrum_kernels.hip's
+// bin_norm: here the 0.5 is applied per component, there once after the square root, and the two round differently
 __device__ __forceinline__ float2 bin_of(float2 z, float2 zm, float2 w, uint32_t k) {
     if (k == 0) return make_float2(z.x + z.y, z.x - z.y);
     const float ar = z.x + zm.x, ai = z.y - zm.y;
@@ -484,8 +396,6 @@ __global__ __launch_bounds__(64 * AW) void convolve_accumulate_multi(MultiArgs m
     else accumulate_multi<V, false, MIXED>(m, k, c);
 }
 
-bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
-
 uint32_t partitions_of(uint32_t n_taps) { return (n_taps + L - 1) / L; }
 
 // DSPFX_OK for a response the bank takes
@@ -579,18 +489,6 @@ void release(dspfx_convolve *p) {
     delete p;
 }
 
-// a call on a stream other than the last one used waits (on the device) for that one
-hipError_t order(dspfx_convolve *p, hipStream_t s) {
-    hipError_t err = hipSuccess;
-    if (p->used && s != p->last) {
-        err = hipEventRecord(p->ev, p->last);
-        if (err == hipSuccess) err = hipStreamWaitEvent(s, p->ev, 0);
-    }
-    p->last = s;
-    p->used = true;
-    return err;
-}
-
 size_t ring_bytes(const dspfx_convolve *p) { return (size_t)p->slots * M * p->desc.channels * sizeof(float2); }
 size_t prev_bytes(const dspfx_convolve *p) { return (size_t)L * p->desc.channels * sizeof(float); }
 
@@ -656,11 +554,6 @@ int store_response(dspfx_convolve *p, uint32_t id, const double *taps_reversed, 
 
 }  // namespace
 
-#define CONV_HIP(call)                               \
-    do {                                             \
-        if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
-    } while (0)
-
 extern "C" int dspfx_convolve_plan(const double *taps_reversed, uint32_t n_taps, uint32_t *partitions, float *table_out) {
     const int rc = check_taps(taps_reversed, n_taps);
     if (rc != DSPFX_OK) return rc;
@@ -695,14 +588,11 @@ extern "C" int dspfx_convolve_create(const dspfx_convolve_desc *desc, dspfx_conv
     std::vector<float> table((size_t)M * p->P * 2);
     make_table(desc->taps_reversed, desc->n_taps, table.data());
     std::vector<float2> tw(256);
-    for (int t = 0; t < 256; ++t) {
-        const double ang = -2.0 * M_PI * t / 256.0;
-        tw[t] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
+    twiddles(256, tw.data());
     tw[0] = make_float2(1.0f, 0.0f);            // the axes exactly: data whose spectrum lies on them goes through bit for bit
     tw[64] = make_float2(0.0f, -1.0f);
     tw[128] = make_float2(-1.0f, 0.0f);
-    tw[192] = make_float2(0.0f, 1.0f);
+    tw[192] = make_float2(0.0f, 1.0f);           // (this bank's only: its unit-impulse tests are bit-exact; the others are not held to that)
     if (hipMalloc((void **)&p->ring, ring_bytes(p)) != hipSuccess ||
         hipMalloc((void **)&p->prev, prev_bytes(p)) != hipSuccess ||
         hipMalloc((void **)&p->acc, (size_t)M * N * sizeof(float2)) != hipSuccess ||
@@ -764,7 +654,7 @@ extern "C" int dspfx_convolve_response_add(dspfx_convolve *p, const double *taps
     if (rc != DSPFX_OK) return rc;
     std::lock_guard<std::mutex> lk(p->mu);
     if (n_taps > p->desc.max_taps || response_count(p) >= DSPFX_CONVOLVE_MAX_RESPONSES) return DSPFX_ERR_INVALID;
-    CONV_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(hipSetDevice(p->desc.device));
     const uint32_t N = p->desc.channels;
     if (!p->resp) {                              // the first add: the map (every channel on response 0) and the kernels' view
         uint16_t *ids = nullptr;
@@ -811,9 +701,9 @@ extern "C" int dspfx_convolve_assign(dspfx_convolve *p, const uint16_t *host_ids
     for (uint64_t i = 0; i < count; ++i)
         if (host_ids[i] >= R) return DSPFX_ERR_INVALID;
     if (!p->ids) return DSPFX_OK;                // one response: every id is 0, which is what a bank without a map runs
-    CONV_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(hipSetDevice(p->desc.device));
     // in the order of the bank's last stream: behind every run submitted before, ahead of every run submitted after
-    CONV_HIP(upload(p, p->ids + first_channel, host_ids, (size_t)count * sizeof(uint16_t)));
+    BANK_HIP(upload(p, p->ids + first_channel, host_ids, (size_t)count * sizeof(uint16_t)));
     std::copy(host_ids, host_ids + count, p->ids_host.begin() + (size_t)first_channel);
     p->mixed = any_mixed_wave(p->ids_host);
     return DSPFX_OK;
@@ -829,11 +719,11 @@ extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out
     if (!p || !in || !out || n_frames == 0 || n_frames % L) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     hipStream_t s = (hipStream_t)stream;
-    CONV_HIP(hipSetDevice(p->desc.device));
-    CONV_HIP(order(p, s));
+    BANK_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(order(p, s));
     if (p->silence) {
-        CONV_HIP(hipMemsetAsync(p->ring, 0, ring_bytes(p), s));
-        CONV_HIP(hipMemsetAsync(p->prev, 0, prev_bytes(p), s));
+        BANK_HIP(hipMemsetAsync(p->ring, 0, ring_bytes(p), s));
+        BANK_HIP(hipMemsetAsync(p->prev, 0, prev_bytes(p), s));
         p->silence = false;
     }
     const uint32_t N = p->desc.channels, W = p->desc.tile_channels;
@@ -862,7 +752,7 @@ extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out
         f.f0 = f0;
         f.spec = p->ring + (size_t)head * M * N;
         convolve_forward<<<fft_blocks, ST, 0, s>>>(f);
-        CONV_HIP(hipGetLastError());
+        BANK_HIP(hipGetLastError());
         p->blocks += 1;                          // the slot is written: a failure further on leaves a consistent history
         a.head = head;
         const dim3 acc_grid(N % 2 == 0 ? (N / 2 + 63) / 64 : (N + 63) / 64, M / AW);
@@ -870,7 +760,7 @@ extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out
         if (!multi) {
             if (N % 2 == 0) convolve_accumulate<2><<<acc_grid, 64 * AW, 0, s>>>(a);
             else convolve_accumulate<1><<<acc_grid, 64 * AW, 0, s>>>(a);
-            CONV_HIP(hipGetLastError());
+            BANK_HIP(hipGetLastError());
             convolve_inverse<<<fft_blocks, ST, 0, s>>>(f);
         } else {
             const MultiArgs m{a, p->ids, p->resp};
@@ -881,10 +771,10 @@ extern "C" int dspfx_convolve_run(dspfx_convolve *p, const float *in, float *out
                 if (p->mixed) convolve_accumulate_multi<1, true><<<acc_grid, 64 * AW, 0, s>>>(m);
                 else convolve_accumulate_multi<1, false><<<acc_grid, 64 * AW, 0, s>>>(m);
             }
-            CONV_HIP(hipGetLastError());
+            BANK_HIP(hipGetLastError());
             convolve_inverse_multi<<<fft_blocks, ST, 0, s>>>(f, p->ids, p->resp);
         }
-        CONV_HIP(hipGetLastError());
+        BANK_HIP(hipGetLastError());
     }
     return DSPFX_OK;
 }

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
+#include "bank_common.hip.h"
 #include "chain_kernels.hip.h"
 
 namespace {
@@ -357,8 +358,6 @@ __global__ __launch_bounds__(256) void mixgroups_divide(const float *__restrict_
 // ---- the plan: pure host -------------------------------------------------------------------------------------------------
 thread_local std::string g_err;        // the reason of the last failed call that had no bank to keep it
 
-bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
-
 uint32_t ceil_log2(uint64_t n) {
     uint32_t b = 0;
     while (((uint64_t)1 << b) < n) ++b;
@@ -519,18 +518,6 @@ void release(dspfx_mixgroups *p) {
     delete p;
 }
 
-// a call on a stream other than the last one used waits (on the device) for that one: the partial sums are the bank's
-hipError_t order(dspfx_mixgroups *p, hipStream_t s) {
-    hipError_t err = hipSuccess;
-    if (p->used && s != p->last) {
-        err = hipEventRecord(p->ev, p->last);
-        if (err == hipSuccess) err = hipStreamWaitEvent(s, p->ev, 0);
-    }
-    p->last = s;
-    p->used = true;
-    return err;
-}
-
 int fail(dspfx_mixgroups *p, int rc, const char *what) {
     p->err = what;
     return rc;
@@ -605,6 +592,7 @@ hipError_t launch_partials(const P1Args &a, bool gain, bool vec, hipStream_t s) 
 
 }  // namespace
 
+// (not BANK_HIP: this bank keeps the reason of a failure for dspfx_mixgroups_last_error)
 #define MG_HIP(call, what)                                         \
     do {                                                           \
         if ((call) != hipSuccess) return fail(p, DSPFX_ERR_HIP, what); \

@@ -1,5 +1,5 @@
 // pitch_kernels.hip -- the Pitch Detector bank (include/dspfx.h, dspfx_pitch_*): nodes/pitch.rs:120-146 for N channels.
-//   slot copy     a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store
+//   slot copy     a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store (bank_common.hip.h)
 //   pitch_detect  one window of every channel: McLeod pitch and clarity, 8 bytes of result per channel that has one
 //   pitch_read    the held results into the caller's freq[N] / clarity[N]
 // The window store is a ring of 9 slots of 128 frames, each slot in the desc's layout for a 128-frame block, so an engine
@@ -11,6 +11,8 @@
 // IFFT(|X0|^2 + i |X1|^2) = r_lin0 + i r_lin1, the two linear autocorrelations, exact for every lag < 1024 (2048 >= 2 * 1024 - 1).
 // The crate's FFT is 1536 long, so its lags alias: r(tau) = r_lin(tau) + r_lin(1536 - tau) for tau > 512, added here.
 // The FFTs are radix-4 (x5) + radix-2 Stockham passes between two LDS buffers, twiddles from a table rounded once from f64.
+// (Not fft_core.hip.h's transform: that one is in place over a run of channels, forward only; this one is one transform per
+// workgroup between two buffers, forward and inverse.  Only cmul / cadd / csub are shared.)
 // m(tau) comes from prefix sums of x^2 (no running subtraction), then n, then the peak pick as six LDS reductions per
 // channel: lobe end, largest key maximum M, first tau >= pick * M, end of its run, the run's maximum, its first tau.
 #include <hip/hip_runtime.h>
@@ -24,6 +26,8 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
+#include "bank_common.hip.h"
+#include "fft_core.hip.h"
 
 namespace {
 
@@ -39,33 +43,6 @@ constexpr int TPC = DT / 2;                        // threads per channel in the
 constexpr int PER = WIN / TPC;                     // lags each of them holds
 constexpr float RATE = 48000.0f;                   // pitch.rs:134 get_pitch(view, 48_000, ...)
 
-// element (f, c) of a block of nf frames in the desc's layout (dspfx_engine_desc.tile_channels)
-__host__ __device__ inline size_t lay(uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
-    return W ? ((size_t)(c / W) * nf + f) * W + (c % W) : (size_t)f * N + c;
-}
-
-// ---- slot copy: `rows` rows of `len` elements, row r at src + r * spitch / dst + r * dpitch (units of T) -------------
-template <typename T>
-__global__ void pitch_copy(const T *__restrict__ src, T *__restrict__ dst, size_t rows, size_t len, size_t spitch,
-                           size_t dpitch) {
-    const size_t total = rows * len;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = e / len, k = e - r * len;
-        dst[r * dpitch + k] = src[r * spitch + k];
-    }
-}
-
-hipError_t launch_copy(const float *src, float *dst, size_t rows, size_t len, size_t spitch, size_t dpitch, hipStream_t s) {
-    const bool v4 = len % 4 == 0 && spitch % 4 == 0 && dpitch % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0;
-    const size_t units = rows * (v4 ? len / 4 : len);
-    const unsigned blocks = (unsigned)std::min<size_t>((units + 255) / 256, 1u << 20);
-    if (v4)
-        pitch_copy<float4><<<blocks, 256, 0, s>>>((const float4 *)src, (float4 *)dst, rows, len / 4, spitch / 4, dpitch / 4);
-    else
-        pitch_copy<float><<<blocks, 256, 0, s>>>(src, dst, rows, len, spitch, dpitch);
-    return hipGetLastError();
-}
-
 // ---- detection ---------------------------------------------------------------------------------------------------------
 struct DetArgs {
     const float *ring;
@@ -76,11 +53,7 @@ struct DetArgs {
     float P, C, K;               // power_thresh, clarity_thresh, pick_thresh
 };
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// one Stockham pass of radix R over FFT_N points, Ns = the product of the radices before it
+// one ping-pong Stockham pass of radix R over FFT_N points, src -> dst, Ns = the product of the radices before it
 template <int R, bool INV>
 __device__ __forceinline__ void fft_pass(const float2 *src, float2 *dst, int Ns, const float2 *__restrict__ tw) {
     constexpr int NR = FFT_N / R;
@@ -373,8 +346,6 @@ struct dspfx_pitch {
 
 namespace {
 
-bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
-
 void release(dspfx_pitch *p) {
     (void)hipSetDevice(p->desc.device);
     if (p->ring) (void)hipFree(p->ring);
@@ -382,18 +353,6 @@ void release(dspfx_pitch *p) {
     if (p->tw) (void)hipFree(p->tw);
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
-}
-
-// a call on a stream other than the last one used waits (on the device) for that one
-hipError_t order(dspfx_pitch *p, hipStream_t s) {
-    hipError_t err = hipSuccess;
-    if (p->used && s != p->last) {
-        err = hipEventRecord(p->ev, p->last);
-        if (err == hipSuccess) err = hipStreamWaitEvent(s, p->ev, 0);
-    }
-    p->last = s;
-    p->used = true;
-    return err;
 }
 
 // frames [f, f + nf) of `block` (n_frames long, starting at stream frame f0) into the ring; nf stays within one slot
@@ -423,11 +382,6 @@ hipError_t detect(dspfx_pitch *p, uint64_t w, hipStream_t s) {
 
 }  // namespace
 
-#define PITCH_HIP(call)                              \
-    do {                                             \
-        if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
-    } while (0)
-
 extern "C" int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **out) {
     if (!desc || !out) return DSPFX_ERR_INVALID;
     *out = nullptr;
@@ -445,10 +399,7 @@ extern "C" int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **ou
     p->th[DSPFX_PITCH_CLARITY] = desc->clarity_thresh;
     p->th[DSPFX_PITCH_PICK] = desc->pick_thresh;
     std::vector<float2> tw(FFT_N);
-    for (int k = 0; k < FFT_N; ++k) {
-        const double ang = -2.0 * M_PI * k / FFT_N;
-        tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
+    twiddles(FFT_N, tw.data());
     if (hipMalloc((void **)&p->ring, (size_t)RING * SLOT * N * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->res, (size_t)N * sizeof(float2)) != hipSuccess ||
         hipMalloc((void **)&p->tw, FFT_N * sizeof(float2)) != hipSuccess) {
@@ -494,20 +445,20 @@ extern "C" int dspfx_pitch_push(dspfx_pitch *p, const float *block, uint32_t n_f
     const bool in_place = block == slot;
     if (in_place && n_frames != SLOT) return DSPFX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    PITCH_HIP(hipSetDevice(p->desc.device));
-    PITCH_HIP(order(p, s));
+    BANK_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(order(p, s));
     const uint64_t f0 = p->frames, f1 = f0 + n_frames;
     uint64_t f = f0;
     for (;;) {
         // window w falls due with frame 1024 (w + 1): F >= 1024 (w + 1) + 1.  It is launched before that frame is copied:
         // the copy goes to the ring's ninth slot, never into the window.
         if (f > 0 && f % WIN == 0 && f1 > f) {
-            PITCH_HIP(detect(p, f / WIN - 1, s));
+            BANK_HIP(detect(p, f / WIN - 1, s));
             p->windows.fetch_add(1);
         }
         if (f == f1) break;
         const uint64_t end = std::min<uint64_t>(f1, (f / SLOT + 1) * SLOT);
-        if (!in_place) PITCH_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
+        if (!in_place) BANK_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
         f = end;
         p->frames = f;                   // what has been launched so far: a failure part-way leaves a consistent state
     }
@@ -524,19 +475,19 @@ extern "C" int dspfx_pitch_read(dspfx_pitch *p, float *freq, float *clarity, voi
     if (!p || !freq || !clarity) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     hipStream_t s = (hipStream_t)stream;
-    PITCH_HIP(hipSetDevice(p->desc.device));
-    PITCH_HIP(order(p, s));
+    BANK_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(order(p, s));
     const uint32_t N = p->desc.channels;
     pitch_read<<<(N + 255) / 256, 256, 0, s>>>(p->res, freq, clarity, N);
-    PITCH_HIP(hipGetLastError());
+    BANK_HIP(hipGetLastError());
     return DSPFX_OK;
 }
 
 extern "C" int dspfx_pitch_reset(dspfx_pitch *p) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    PITCH_HIP(hipSetDevice(p->desc.device));
-    PITCH_HIP(hipMemsetAsync(p->res, 0, (size_t)p->desc.channels * sizeof(float2), p->last));
+    BANK_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(hipMemsetAsync(p->res, 0, (size_t)p->desc.channels * sizeof(float2), p->last));
     p->frames = 0;
     p->windows = 0;
     return DSPFX_OK;

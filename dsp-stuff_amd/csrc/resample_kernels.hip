@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
+#include "bank_common.hip.h"
 #include "pcm_kernels.h"
 #include "pcm_rules.h"
 
@@ -308,8 +309,6 @@ struct dspfx_resample {
 
 namespace {
 
-bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
-
 void release(dspfx_resample *r) {
     (void)hipSetDevice(r->desc.device);
     if (r->fifo) (void)hipFree(r->fifo);
@@ -321,18 +320,6 @@ void release(dspfx_resample *r) {
     }
     if (r->ev) (void)hipEventDestroy(r->ev);
     delete r;
-}
-
-// a call on a stream other than the last one used waits (on the device) for that one
-hipError_t order(dspfx_resample *r, hipStream_t s) {
-    hipError_t err = hipSuccess;
-    if (r->used && s != r->last) {
-        err = hipEventRecord(r->ev, r->last);
-        if (err == hipSuccess) err = hipStreamWaitEvent(s, r->ev, 0);
-    }
-    r->last = s;
-    r->used = true;
-    return err;
 }
 
 uint64_t capacity(const dspfx_resample *r) { return (uint64_t)r->desc.slots * r->desc.block_frames; }
@@ -354,11 +341,6 @@ hipError_t copy_in(dspfx_resample *r, const float *block, uint32_t n_frames, uin
 }
 
 }  // namespace
-
-#define RS_HIP(call)                                    \
-    do {                                                \
-        if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
-    } while (0)
 
 extern "C" int dspfx_resample_plan(uint32_t target_hz, double *value, uint32_t *idx, uint32_t n_out, uint32_t *advance,
                                    uint32_t *depth, double *coeff, uint32_t *input_len, uint32_t *pulled) {
@@ -483,12 +465,12 @@ extern "C" int dspfx_resample_push(dspfx_resample *r, const float *block, uint32
         return DSPFX_OK;
     }
     hipStream_t s = (hipStream_t)stream;
-    RS_HIP(hipSetDevice(r->desc.device));
-    RS_HIP(order(r, s));
+    BANK_HIP(hipSetDevice(r->desc.device));
+    BANK_HIP(order(r, s));
     const uint64_t f0 = r->tail, f1 = f0 + n_frames;
     for (uint64_t f = f0; f < f1;) {
         const uint64_t end = std::min<uint64_t>(f1, (f / BF + 1) * BF);
-        RS_HIP(copy_in(r, block, n_frames, (uint32_t)(f - f0), f, (uint32_t)(end - f), s));
+        BANK_HIP(copy_in(r, block, n_frames, (uint32_t)(f - f0), f, (uint32_t)(end - f), s));
         f = end;
         r->tail = f;                     // what has been launched so far: a failure part-way leaves a consistent state
     }
@@ -501,13 +483,13 @@ extern "C" int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out,
     std::lock_guard<std::mutex> lk(r->mu);
     const dspfx_resample_desc &d = r->desc;
     hipStream_t s = (hipStream_t)stream;
-    RS_HIP(hipSetDevice(d.device));
+    BANK_HIP(hipSetDevice(d.device));
     const uint64_t avail = r->tail - r->head;
     if (consumed) *consumed = 0;
     if (underrun) *underrun = 0;
     if (avail < input_len_of(n_out, d.target_hz)) {              // try_grant failed: silence, nothing touched
-        RS_HIP(order(r, s));
-        RS_HIP(launch_silence(d.out_format, out, (size_t)n_out * d.channels * d.out_channels, s));
+        BANK_HIP(order(r, s));
+        BANK_HIP(launch_silence(d.out_format, out, (size_t)n_out * d.channels * d.out_channels, s));
         if (underrun) *underrun = 1;
         return DSPFX_OK;
     }
@@ -518,7 +500,7 @@ extern "C" int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out,
     if (dspfx_resample_plan(d.target_hz, &value, &idx, n_out, r->adv.data(), r->depth.data(), r->coeff.data(), nullptr, &pulled) != DSPFX_OK)
         return DSPFX_ERR_INVALID;
     const uint32_t h = r->hnext;
-    if (r->hbusy[h]) RS_HIP(hipEventSynchronize(r->hev[h]));     // PLAN_RING pulls ago: long done unless the device is far behind
+    if (r->hbusy[h]) BANK_HIP(hipEventSynchronize(r->hev[h]));     // PLAN_RING pulls ago: long done unless the device is far behind
     PlanRow *rows = r->hplan[h];
     uint32_t nl = idx0;
     for (uint32_t o = 0; o < n_out; ++o) {
@@ -529,9 +511,9 @@ extern "C" int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out,
         rows[o].nl = nl;
         rows[o].pad = 0;
     }
-    RS_HIP(order(r, s));
-    RS_HIP(hipMemcpyAsync(r->dplan, rows, (size_t)n_out * sizeof(PlanRow), hipMemcpyHostToDevice, s));
-    RS_HIP(hipEventRecord(r->hev[h], s));
+    BANK_HIP(order(r, s));
+    BANK_HIP(hipMemcpyAsync(r->dplan, rows, (size_t)n_out * sizeof(PlanRow), hipMemcpyHostToDevice, s));
+    BANK_HIP(hipEventRecord(r->hev[h], s));
     r->hbusy[h] = true;
     r->hnext = (h + 1) % PLAN_RING;
 
@@ -554,7 +536,7 @@ extern "C" int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out,
     const bool want4 = r->vec >= 0 ? r->vec != 0 : a.N / 4 >= 256u * RS_WG;
     const Path path = idx0 < DEPTH ? WARM : (can4 && want4 ? FAST4 : FAST1);
     const hipError_t err = d.out_channels == 2 ? launch_pull_ch<2>(d.out_format, path, a, s) : launch_pull_ch<1>(d.out_format, path, a, s);
-    RS_HIP(err);
+    BANK_HIP(err);
     const uint32_t used = (uint32_t)std::min<uint64_t>(pulled, avail);      // CountingSignal: pulls past the view do not count
     r->head += used;
     r->value = value;
@@ -580,8 +562,8 @@ extern "C" int dspfx_resample_skip(dspfx_resample *r, uint32_t n_frames) {
 extern "C" int dspfx_resample_reset(dspfx_resample *r) {
     if (!r) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(r->mu);
-    RS_HIP(hipSetDevice(r->desc.device));
-    RS_HIP(hipMemsetAsync(r->state, 0, (size_t)TAPS * r->desc.channels * sizeof(float), r->last));
+    BANK_HIP(hipSetDevice(r->desc.device));
+    BANK_HIP(hipMemsetAsync(r->state, 0, (size_t)TAPS * r->desc.channels * sizeof(float), r->last));
     r->head = r->tail = 0;
     r->value = 0.0;
     r->idx = 0;

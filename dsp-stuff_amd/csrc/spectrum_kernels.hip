@@ -1,5 +1,5 @@
 // spectrum_kernels.hip -- the Spectrogram bank (include/dspfx.h, dspfx_spectrum_*): nodes/spectrogram.rs:225-268 for N channels.
-//   slot copy        a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store
+//   slot copy        a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store (bank_common.hip.h)
 //   spectrum_column  one window of every channel: vol[k] = |FFT(window * x)[k]| * gain[k], k in [0, n/2), into the history
 // The window store is a ring of n/128 + 1 slots of 128 frames, each slot in the desc's layout for a 128-frame block, so an
 // engine can write its output straight into the next slot (dspfx_spectrum_slot).  A window is n/128 consecutive slots and is
@@ -12,10 +12,7 @@
 //       X[k] = ((Z[k] + Zc) - i w (Z[k] - Zc)) / 2          k in [0, n/2)
 // Every channel is transformed on its own: its rounding error is relative to its own level.  (Packing two CHANNELS into one
 // complex FFT costs the same, but each channel then carries the other's rounding error, which fails a quiet channel beside
-// a loud one.)  The Q transforms live in ONE LDS buffer A[point][q] (q fastest, as in memory) and are done in place: a pass
-// reads all its points into registers, the workgroup meets, then it writes them in Stockham order, so the output is in
-// natural order with no second buffer and the run is twice as wide as two buffers would allow.  Radix-4 passes and one
-// radix-2 pass when log2 m is odd; twiddles from a table rounded once from f64 (none in the first pass, where they are all 1).
+// a loud one.)  The Q transforms are done in place in ONE LDS buffer A[point][q]: fft_core.hip.h.
 //   n       128   256   512  1024  2048  4096  8192
 //   Q       128    64    32    16     8     4     4      channels per workgroup
 //   LDS     64 KiB everywhere, 128 KiB at 8192 (one workgroup per CU there, two elsewhere)
@@ -30,39 +27,14 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
+#include "bank_common.hip.h"
+#include "fft_core.hip.h"
 
 namespace {
 
 constexpr uint32_t SLOT = DSPFX_BUF_SIZE;          // frames per slot: one process block
 constexpr int ST = 512;                            // threads of spectrum_column
 constexpr double RATE = 48000.0;                   // spectrogram.rs:238 sampling_rate
-
-// element (f, c) of a block of nf frames in the desc's layout (dspfx_engine_desc.tile_channels)
-__host__ __device__ inline size_t lay(uint32_t f, uint32_t c, uint32_t nf, uint32_t N, uint32_t W) {
-    return W ? ((size_t)(c / W) * nf + f) * W + (c % W) : (size_t)f * N + c;
-}
-
-// ---- slot copy: `rows` rows of `len` elements, row r at src + r * spitch / dst + r * dpitch (units of T) -------------
-template <typename T>
-__global__ void spectrum_copy(const T *__restrict__ src, T *__restrict__ dst, size_t rows, size_t len, size_t spitch,
-                              size_t dpitch) {
-    const size_t total = rows * len;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = e / len, k = e - r * len;
-        dst[r * dpitch + k] = src[r * spitch + k];
-    }
-}
-
-hipError_t launch_copy(const float *src, float *dst, size_t rows, size_t len, size_t spitch, size_t dpitch, hipStream_t s) {
-    const bool v4 = len % 4 == 0 && spitch % 4 == 0 && dpitch % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0;
-    const size_t units = rows * (v4 ? len / 4 : len);
-    const unsigned blocks = (unsigned)std::min<size_t>((units + 255) / 256, 1u << 20);
-    if (v4)
-        spectrum_copy<float4><<<blocks, 256, 0, s>>>((const float4 *)src, (float4 *)dst, rows, len / 4, spitch / 4, dpitch / 4);
-    else
-        spectrum_copy<float><<<blocks, 256, 0, s>>>(src, dst, rows, len, spitch, dpitch);
-    return hipGetLastError();
-}
 
 // ---- the column -----------------------------------------------------------------------------------------------------
 struct ColArgs {
@@ -76,78 +48,8 @@ struct ColArgs {
     uint32_t vec;                // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N
 };
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// one in-place Stockham pass of radix R over the Q transforms of m = 2^LOGM points in A[point][q]; NS = the product of the
-// radices before it; tw is the table of 2m points, so exp(-2 pi i t / m) = tw[2t]
-template <int LOGM, int Q, int R, int NS>
-__device__ __forceinline__ void fft_pass(float2 *A, const float2 *__restrict__ tw) {
-    constexpr int n = 1 << LOGM, NR = n / R, IT = NR * Q / ST;
-    static_assert(NR * Q % ST == 0, "every thread does the same number of butterflies");
-    float2 v[IT][R];
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-        const int b = threadIdx.x + i * ST, q = b % Q, j = b / Q;
-#pragma unroll
-        for (int r = 0; r < R; ++r) v[i][r] = A[(j + r * NR) * Q + q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-        const int b = threadIdx.x + i * ST, q = b % Q, j = b / Q;
-        const int k = j & (NS - 1);
-        float2 *u = v[i];
-        if (NS > 1) {
-#pragma unroll
-            for (int r = 1; r < R; ++r) u[r] = cmul(u[r], tw[2 * (k * r * (n / (NS * R)))]);
-        }
-        if (R == 2) {
-            const float2 a = u[0];
-            u[0] = cadd(a, u[1]);
-            u[1] = csub(a, u[1]);
-        } else {
-            const float2 a0 = cadd(u[0], u[2]), a1 = csub(u[0], u[2]), a2 = cadd(u[1], u[3]), a3 = csub(u[1], u[3]);
-            const float2 ja3 = make_float2(a3.y, -a3.x);                                   // -i * a3
-            u[0] = cadd(a0, a2);
-            u[1] = cadd(a1, ja3);
-            u[2] = csub(a0, a2);
-            u[3] = csub(a1, ja3);
-        }
-        const int d = (j - k) * R + k;
-#pragma unroll
-        for (int r = 0; r < R; ++r) A[(d + r * NS) * Q + q] = u[r];
-    }
-    __syncthreads();
-}
-
-template <int LOGM, int Q, int NS>
-__device__ __forceinline__ void fft_all(float2 *A, const float2 *__restrict__ tw) {
-    constexpr int m = 1 << LOGM;
-    if constexpr (NS * 4 <= m) {
-        fft_pass<LOGM, Q, 4, NS>(A, tw);
-        fft_all<LOGM, Q, NS * 4>(A, tw);
-    } else if constexpr (NS * 2 <= m) {
-        fft_pass<LOGM, Q, 2, NS>(A, tw);
-    }
-}
-
-// frame f of 4 channels from c (c a multiple of 4); channels outside N read 0
-__device__ __forceinline__ float4 load4(const ColArgs &a, const float *base, uint32_t f, uint32_t c) {
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (a.vec) {
-        if (c < a.N) v = *(const float4 *)(base + lay(f, c, SLOT, a.N, a.W));
-    } else {
-        if (c < a.N) v.x = base[lay(f, c, SLOT, a.N, a.W)];
-        if (c + 1 < a.N) v.y = base[lay(f, c + 1, SLOT, a.N, a.W)];
-        if (c + 2 < a.N) v.z = base[lay(f, c + 2, SLOT, a.N, a.W)];
-        if (c + 3 < a.N) v.w = base[lay(f, c + 3, SLOT, a.N, a.W)];
-    }
-    return v;
-}
-
-// |((z + conj zm) - i w (z - conj zm)) / 2|
+// |((z + conj zm) - i w (z - conj zm)) / 2|.  Not convolve_kernels.hip's bin_of: there the 0.5 is applied per component, here
+// once after the square root, and the two round differently
 __device__ __forceinline__ float bin_norm(float2 z, float2 zm, float2 w) {
     const float ar = z.x + zm.x, ai = z.y - zm.y;
     const float2 t = cmul(w, make_float2(z.x - zm.x, z.y + zm.y));
@@ -177,8 +79,9 @@ __global__ __launch_bounds__(ST) void spectrum_column(ColArgs a) {
         uint32_t slot = a.slot0 + f / SLOT;
         if (slot >= RING) slot -= RING;
         const float *base = a.ring + (size_t)slot * SLOT * a.N;
-        xe[i] = load4(a, base, f % SLOT, c);             // 2j and 2j + 1 are in one slot: a slot holds an even number of frames
-        xo[i] = load4(a, base, f % SLOT + 1, c);
+        // 2j and 2j + 1 are in one slot: a slot holds an even number of frames
+        xe[i] = load4(base, a.vec, f % SLOT, c, SLOT, a.N, a.W);
+        xo[i] = load4(base, a.vec, f % SLOT + 1, c, SLOT, a.N, a.W);
     }
 #pragma unroll
     for (int i = 0; i < UN; ++i) {
@@ -189,7 +92,7 @@ __global__ __launch_bounds__(ST) void spectrum_column(ColArgs a) {
     }
     __syncthreads();
 
-    fft_all<LOGN - 1, Q, 1>(A, a.tw);
+    fft_all<LOGN - 1, Q, ST, 1>(A, a.tw);
 
     // ---- the column: bins [0, n/2) of 4 channels per unit, times the gain table
 #pragma unroll
@@ -205,6 +108,8 @@ __global__ __launch_bounds__(ST) void spectrum_column(ColArgs a) {
         o.y = bin_norm(make_float2(z0.z, z0.w), make_float2(y0.z, y0.w), w) * g;
         o.z = bin_norm(make_float2(z1.x, z1.y), make_float2(y1.x, y1.y), w) * g;
         o.w = bin_norm(make_float2(z1.z, z1.w), make_float2(y1.z, y1.w), w) * g;
+        // not store4<false> (bank_common.hip.h): its scalar tail is a loop over an array, from which the compiler makes other code
+        // for this kernel (fewer instructions, other registers); this form keeps the kernel as it was measured
         if (a.vec) {
             if (c < a.N) *(float4 *)(a.col + lay(k, c, m, a.N, a.W)) = o;
         } else {
@@ -221,8 +126,6 @@ hipError_t launch_column(const ColArgs &a, hipStream_t s) {
     spectrum_column<LOGN, Q><<<(a.N + Q - 1) / Q, ST, 0, s>>>(a);
     return hipGetLastError();
 }
-
-bool pow2(uint32_t w) { return w && !(w & (w - 1)); }
 
 // DSPFX_OK for a size the bank takes
 int check_size(uint32_t n) {
@@ -270,18 +173,6 @@ void release(dspfx_spectrum *p) {
     delete p;
 }
 
-// a call on a stream other than the last one used waits (on the device) for that one
-hipError_t order(dspfx_spectrum *p, hipStream_t s) {
-    hipError_t err = hipSuccess;
-    if (p->used && s != p->last) {
-        err = hipEventRecord(p->ev, p->last);
-        if (err == hipSuccess) err = hipStreamWaitEvent(s, p->ev, 0);
-    }
-    p->last = s;
-    p->used = true;
-    return err;
-}
-
 size_t column_elems(const dspfx_spectrum *p) { return (size_t)(p->desc.fft_size / 2) * p->desc.channels; }
 
 // frames [f, f + nf) of `block` (n_frames long, starting at stream frame f0) into the ring; nf stays within one slot
@@ -320,11 +211,6 @@ hipError_t column(dspfx_spectrum *p, uint64_t w, hipStream_t s) {
 
 }  // namespace
 
-#define SPEC_HIP(call)                               \
-    do {                                             \
-        if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
-    } while (0)
-
 extern "C" int dspfx_spectrum_plan(uint32_t fft_size, float *window_out, float *bin_hz_out) {
     const int rc = check_size(fft_size);
     if (rc != DSPFX_OK) return rc;
@@ -359,10 +245,7 @@ extern "C" int dspfx_spectrum_create(const dspfx_spectrum_desc *desc, dspfx_spec
     else
         default_window(n, win.data());
     if (desc->gain) std::memcpy(gain.data(), desc->gain, (n / 2) * sizeof(float));
-    for (uint32_t k = 0; k < n; ++k) {
-        const double ang = -2.0 * M_PI * k / n;
-        tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
+    twiddles(n, tw.data());
     if (hipMalloc((void **)&p->ring, (size_t)p->ring_slots * SLOT * N * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->cols, (size_t)desc->columns * column_elems(p) * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->win, n * sizeof(float)) != hipSuccess ||
@@ -410,16 +293,16 @@ extern "C" int dspfx_spectrum_push(dspfx_spectrum *p, const float *block, uint32
     const bool in_place = block == slot;
     if (in_place && n_frames != SLOT) return DSPFX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    SPEC_HIP(hipSetDevice(p->desc.device));
-    SPEC_HIP(order(p, s));
+    BANK_HIP(hipSetDevice(p->desc.device));
+    BANK_HIP(order(p, s));
     const uint64_t f0 = p->frames, f1 = f0 + n_frames;
     for (uint64_t f = f0; f < f1;) {
         const uint64_t end = std::min<uint64_t>(f1, (f / SLOT + 1) * SLOT);
-        if (!in_place) SPEC_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
+        if (!in_place) BANK_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
         f = end;
         p->frames = f;                   // what has been launched so far: a failure part-way leaves a consistent state
         if (f % n == 0) {                // a window ends on a slot boundary (n is a multiple of 128)
-            SPEC_HIP(column(p, f / n - 1, s));
+            BANK_HIP(column(p, f / n - 1, s));
             p->windows.fetch_add(1);
         }
     }
