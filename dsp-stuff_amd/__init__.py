@@ -51,6 +51,7 @@ PITCH_WINDOW = 1024
 SPECTRUM_MIN_FFT, SPECTRUM_MAX_FFT = 128, 8192      # DSPFX_SPECTRUM_*: the Spectrogram node's fft_size slider (spectrogram.rs:142)
 SPECTRUM_RATE = 48000.0         # spectrogram.rs:238 sampling_rate: bin k of an n-point window is k * 48000 / n Hz
 CONVOLVE_MAX_TAPS = 524288      # DSPFX_CONVOLVE_MAX_TAPS: the longest response a Convolver takes (4096 partitions of 128)
+NO_ROOM = 0xFFFFFFFF            # DSPFX_MIXGROUPS_NO_ROOM: MixGroups.assign, the channel sits in no room
 CONVOLVE_MAX_RESPONSES = 256    # DSPFX_CONVOLVE_MAX_RESPONSES: the responses one Convolver holds
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
@@ -75,6 +76,7 @@ EXPORTS = [
     "dspfx_spectrum_reset", "dspfx_spectrum_windows", "dspfx_spectrum_plan",
     "dspfx_mixgroups_create", "dspfx_mixgroups_destroy", "dspfx_mixgroups_last_error", "dspfx_mixgroups_run",
     "dspfx_mixgroups_set_gains", "dspfx_mixgroups_plan", "dspfx_mixgroups_returns",
+    "dspfx_mixgroups_assign", "dspfx_mixgroups_rooms", "dspfx_mixgroups_room_plan",
     "dspfx_convolve_create", "dspfx_convolve_destroy", "dspfx_convolve_reset", "dspfx_convolve_run", "dspfx_convolve_set_taps",
     "dspfx_convolve_plan", "dspfx_convolve_response_add", "dspfx_convolve_response_set", "dspfx_convolve_assign",
     "dspfx_convolve_response_count",
@@ -277,6 +279,10 @@ def lib():
     L.dspfx_mixgroups_returns.argtypes = [vp, f32p, C.c_uint32, f32p, f32p, vp]
     L.dspfx_mixgroups_set_gains.argtypes = [vp, C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
     L.dspfx_mixgroups_plan.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.dspfx_mixgroups_assign.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
+    L.dspfx_mixgroups_rooms.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
+    L.dspfx_mixgroups_room_plan.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.dspfx_convolve_create.argtypes = [C.POINTER(_ConvolveDesc), C.POINTER(C.c_void_p)]
     L.dspfx_convolve_destroy.argtypes = [vp]
     L.dspfx_convolve_reset.argtypes = [vp]
@@ -1174,12 +1180,40 @@ def mixgroups_plan(channels: int, group_start=None, group_size=None, tile_channe
     return depth
 
 
+def _room_ids(ids) -> np.ndarray:
+    if hasattr(ids, "detach"):
+        ids = ids.detach().cpu().numpy()
+    v = np.atleast_1d(np.asarray(ids)).reshape(-1)
+    if v.size and (v.dtype.kind not in "iu" or v.min() < 0 or v.max() > NO_ROOM):
+        raise DspfxError(-1, "room ids are integers in [0, groups), or NO_ROOM")
+    return np.ascontiguousarray(v, np.uint32)
+
+
+def mixgroups_room_plan(room_of, groups: int, tile_channels: int = 0):
+    """dspfx_mixgroups_room_plan, a pure host function (no GPU): checks a map -- a room id in [0, groups) or NO_ROOM per channel
+    -- (DspfxError with the reason when it is bad) and -> (count uint64[G], depth uint32[G], pieces uint64[G]): per room its
+    members, the longest chain of dependent f32 additions in its sum in mapped mode, and its pieces (one per span it has members
+    in; their sum sizes the seating's piece buffer).  A room's depth and pieces depend on its own members alone."""
+    L = lib()
+    v = _room_ids(room_of)
+    G = int(groups)
+    count, depth, pieces = np.zeros(max(G, 0), np.uint64), np.zeros(max(G, 0), np.uint32), np.zeros(max(G, 0), np.uint64)
+    u64 = C.POINTER(C.c_uint64)
+    rc = L.dspfx_mixgroups_room_plan(v.ctypes.data_as(C.POINTER(C.c_uint32)), len(v), G & 0xFFFFFFFF, int(tile_channels),
+                                     count.ctypes.data_as(u64), depth.ctypes.data_as(C.POINTER(C.c_uint32)), pieces.ctypes.data_as(u64))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_mixgroups_last_error(None).decode() or L.dspfx_strerror(rc).decode())
+    return count, depth, pieces
+
+
 class MixGroups:
     """One Output bus per contiguous channel range, with a per-channel fader (include/dspfx.h, dspfx_mixgroups_*):
     buses[f][g] = (sum over group g of fl32(x[f][c] * gain[c])) / link_divisor(n_g) for a device block in the layout of
     `tile_channels` (as Engine's).  group_start: G + 1 channel indices, nondecreasing from 0 to N; or group_size for uniform
     groups.  normalise=False leaves the raw sums.  run() returns [n_frames, G] float32 on the device: the frame-major block of a
-    G-channel Engine(G, tile_channels=0), Resampler(G, ..), PitchBank(G) or SpectrumBank(G).  Asynchronous on `stream`."""
+    G-channel Engine(G, tile_channels=0), Resampler(G, ..), PitchBank(G) or SpectrumBank(G).  Asynchronous on `stream`.
+    Every channel starts in the room its range puts it in; `assign` reseats channels live among the G rooms (or in none,
+    NO_ROOM): run and returns then read "group g" as the channels whose room is g.  A bank that never calls it runs as before."""
 
     def __init__(self, channels: int, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE,
                  normalise: bool = True, device: int = 0):
@@ -1233,8 +1267,37 @@ class MixGroups:
         v = np.ascontiguousarray(values, np.float32).reshape(-1)
         self._chk(self.L.dspfx_mixgroups_set_gains(self.h, v.ctypes.data_as(C.POINTER(C.c_float)), int(first_channel), len(v)))
 
+    def assign(self, ids, first_channel: int = 0):
+        """Seat channels [first_channel, first_channel + len(ids)) in the rooms `ids` (an int for one channel, or any integer
+        sequence, numpy array or torch tensor; each in [0, groups) or NO_ROOM).  A bad id, or a range past the channels, stores
+        nothing.  Any thread, while runs are in flight: it holds for the runs submitted after it returns.  The channel's fader,
+        and its state in the engine, stay where they are."""
+        v = _room_ids(ids)
+        self._chk(self.L.dspfx_mixgroups_assign(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), len(v)))
+        self._mapped = True
+
+    def room_of(self) -> np.ndarray:
+        """uint32[channels]: the room of every channel (NO_ROOM: none) as the next run sees it."""
+        v = np.zeros(self.channels, np.uint32)
+        self._chk(self.L.dspfx_mixgroups_rooms(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), 0, len(v)))
+        return v
+
+    def counts(self) -> np.ndarray:
+        """uint64[G]: the members of every room."""
+        r = self.room_of()
+        return np.bincount(r[r != NO_ROOM], minlength=self.groups).astype(np.uint64)
+
+    def pieces(self) -> int:
+        """The piece rows of the current seating ([pieces][max_frames] f32 on the device); 0 on a bank without a map."""
+        if not getattr(self, "_mapped", False):
+            return 0
+        return int(mixgroups_room_plan(self.room_of(), self.groups, self.tile_channels)[2].sum())
+
     def depth(self) -> np.ndarray:
-        """mixgroups_plan for this bank's table."""
+        """Per room the longest chain of dependent f32 additions in its sum, for the current seating: mixgroups_plan of the
+        table on a bank without a map, mixgroups_room_plan of room_of() once assign has been called."""
+        if getattr(self, "_mapped", False):
+            return mixgroups_room_plan(self.room_of(), self.groups, self.tile_channels)[1]
         return mixgroups_plan(self.channels, group_start=self.group_start, tile_channels=self.tile_channels)
 
     def close(self):

@@ -79,8 +79,9 @@ __device__ __forceinline__ size_t chan_base(uint32_t ch, uint32_t Wrow, uint32_t
     return (size_t)t * nf * Wrow + (ch - t * Wrow);
 }
 
-template <int F, bool GAIN, bool VEC>
-__device__ __forceinline__ void whole_span(const P1Args &a, uint32_t k, uint32_t f0, uint32_t lane) {
+// (A: P1Args or MapArgs; the piece is row `row` of a.L: the span itself without a map)
+template <int F, bool GAIN, bool VEC, class A>
+__device__ __forceinline__ void whole_span(const A &a, uint32_t k, uint32_t row, uint32_t f0, uint32_t lane) {
     const uint32_t ch = k * SPAN + 4 * lane;
     size_t b[4];
     b[0] = chan_base(ch, a.Wrow, a.nf);
@@ -119,7 +120,7 @@ __device__ __forceinline__ void whole_span(const P1Args &a, uint32_t k, uint32_t
     }
     dspfx::wave_reduce_scatter<F>(r, (int)lane);
     const uint32_t f = f0 + (uint32_t)dspfx::mixbus_frame_of_lane<F>((int)lane);
-    if (dspfx::mixbus_lane_writes<F>((int)lane) && f < a.nf) a.L[(size_t)k * a.FS + f] = r[0];
+    if (dspfx::mixbus_lane_writes<F>((int)lane) && f < a.nf) a.L[(size_t)row * a.FS + f] = r[0];
 }
 
 template <int F, bool GAIN>
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(P1_WG) void mixgroups_partials(P1Args a) {
     if (item >= a.nspans * a.nchunks) return;
     const uint32_t k = item / a.nchunks, f0 = (item - k * a.nchunks) * F;
     if (a.slow[k]) cut_span<F, GAIN>(a, k, f0, lane);
-    else whole_span<F, GAIN, VEC>(a, k, f0, lane);
+    else whole_span<F, GAIN, VEC>(a, k, k, f0, lane);
 }
 
 __global__ __launch_bounds__(RW * 64) void mixgroups_reduce(const Task *__restrict__ tasks, const float *__restrict__ src,
@@ -257,6 +258,62 @@ __device__ __forceinline__ float mix_minus(float S, float x, float g, float div,
     return div == 0.0f ? 0.0f : q;
 }
 
+// the frames [f0, f0 + RCHUNK) of a lane's four channels; CUT: the four may be in different groups
+template <bool GAIN, bool VEC, bool CUT>
+__device__ __forceinline__ void returns_rows(const float *x, float *out, const float *S, uint32_t Wrow, uint32_t nf, uint32_t G,
+                                             bool norm, uint32_t f0, const uint32_t (&gi)[4], const float (&dv)[4],
+                                             const float (&gn)[4], const bool (&valid)[4], const size_t (&b)[4]) {
+#pragma unroll
+    for (int i0 = 0; i0 < RCHUNK; i0 += RBATCH) {
+        float4 v[RBATCH], s[RBATCH];
+#pragma unroll
+        for (int j = 0; j < RBATCH; ++j) {
+            const uint32_t f = f0 + i0 + j;
+            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            s[j] = v[j];
+            if (f < nf) {
+                const size_t o = (size_t)f * Wrow;
+                if (VEC) {
+                    v[j] = *(const float4 *)(x + b[0] + o);
+                } else {
+                    v[j].x = x[b[0] + o];
+                    if (valid[1]) v[j].y = x[b[1] + o];
+                    if (valid[2]) v[j].z = x[b[2] + o];
+                    if (valid[3]) v[j].w = x[b[3] + o];
+                }
+                const float *row = S + (size_t)f * G;
+                s[j].x = row[gi[0]];
+                if (CUT) {
+                    s[j].y = row[gi[1]];
+                    s[j].z = row[gi[2]];
+                    s[j].w = row[gi[3]];
+                } else {
+                    s[j].y = s[j].z = s[j].w = s[j].x;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RBATCH; ++j) {
+            const uint32_t f = f0 + i0 + j;
+            if (f >= nf) continue;
+            const size_t o = (size_t)f * Wrow;
+            float4 r;
+            r.x = mix_minus(s[j].x, v[j].x, gn[0], dv[0], GAIN, norm);
+            r.y = mix_minus(s[j].y, v[j].y, gn[1], dv[1], GAIN, norm);
+            r.z = mix_minus(s[j].z, v[j].z, gn[2], dv[2], GAIN, norm);
+            r.w = mix_minus(s[j].w, v[j].w, gn[3], dv[3], GAIN, norm);
+            if (VEC) {
+                *(float4 *)(out + b[0] + o) = r;
+            } else {
+                out[b[0] + o] = r.x;
+                if (valid[1]) out[b[1] + o] = r.y;
+                if (valid[2]) out[b[2] + o] = r.z;
+                if (valid[3]) out[b[3] + o] = r.w;
+            }
+        }
+    }
+}
+
 template <bool GAIN, bool VEC, bool CUT>
 __device__ __forceinline__ void returns_span(const RetArgs &a, uint32_t k, uint32_t f0, uint32_t lane) {
     const uint32_t ch = k * SPAN + 4 * lane;
@@ -286,56 +343,7 @@ __device__ __forceinline__ void returns_span(const RetArgs &a, uint32_t k, uint3
         gn[i] = (GAIN && valid[i]) ? a.gain[c] : 1.0f;
         b[i] = (valid[i] && (i == 0 || !VEC)) ? chan_base(c, a.Wrow, a.nf) : 0;
     }
-    const bool norm = a.norm != 0;
-#pragma unroll
-    for (int i0 = 0; i0 < RCHUNK; i0 += RBATCH) {
-        float4 v[RBATCH], s[RBATCH];
-#pragma unroll
-        for (int j = 0; j < RBATCH; ++j) {
-            const uint32_t f = f0 + i0 + j;
-            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            s[j] = v[j];
-            if (f < a.nf) {
-                const size_t o = (size_t)f * a.Wrow;
-                if (VEC) {
-                    v[j] = *(const float4 *)(a.x + b[0] + o);
-                } else {
-                    v[j].x = a.x[b[0] + o];
-                    if (valid[1]) v[j].y = a.x[b[1] + o];
-                    if (valid[2]) v[j].z = a.x[b[2] + o];
-                    if (valid[3]) v[j].w = a.x[b[3] + o];
-                }
-                const float *row = a.S + (size_t)f * a.G;
-                s[j].x = row[gi[0]];
-                if (CUT) {
-                    s[j].y = row[gi[1]];
-                    s[j].z = row[gi[2]];
-                    s[j].w = row[gi[3]];
-                } else {
-                    s[j].y = s[j].z = s[j].w = s[j].x;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RBATCH; ++j) {
-            const uint32_t f = f0 + i0 + j;
-            if (f >= a.nf) continue;
-            const size_t o = (size_t)f * a.Wrow;
-            float4 r;
-            r.x = mix_minus(s[j].x, v[j].x, gn[0], dv[0], GAIN, norm);
-            r.y = mix_minus(s[j].y, v[j].y, gn[1], dv[1], GAIN, norm);
-            r.z = mix_minus(s[j].z, v[j].z, gn[2], dv[2], GAIN, norm);
-            r.w = mix_minus(s[j].w, v[j].w, gn[3], dv[3], GAIN, norm);
-            if (VEC) {
-                *(float4 *)(a.out + b[0] + o) = r;
-            } else {
-                a.out[b[0] + o] = r.x;
-                if (valid[1]) a.out[b[1] + o] = r.y;
-                if (valid[2]) a.out[b[2] + o] = r.z;
-                if (valid[3]) a.out[b[3] + o] = r.w;
-            }
-        }
-    }
+    returns_rows<GAIN, VEC, CUT>(a.x, a.out, a.S, a.Wrow, a.nf, a.G, a.norm != 0, f0, gi, dv, gn, valid, b);
 }
 
 template <bool GAIN, bool VEC>
@@ -353,6 +361,200 @@ __global__ __launch_bounds__(256) void mixgroups_divide(const float *__restrict_
                                                         float *__restrict__ bus, uint32_t G, uint64_t total) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < total) bus[i] = __fdiv_rn(S[i], gdiv[i % G]);
+}
+
+// ---- mapped mode: a room id per channel (dspfx_mixgroups_assign) ----------------------------------------------------------------
+// A room's members may lie anywhere.  Per span the host sorts the channels by (room, channel): a room's members of the span
+// become one SEGMENT of adjacent sorted positions, and every segment of a seated room has a piece row; one room's pieces are
+// adjacent rows, in ascending span order, so the reduce kernel above adds them as it adds a range's.
+//   partials  one wave per (span, chunk of 16 frames), the same single 16-byte load per lane and frame.
+//             A span whose 256 channels all sit in one room: whole_span, unchanged, into the room's piece row.
+//             Any other span: the terms go through LDS into sorted order (four frames at a time; a row of 256 is padded by one
+//             word per 64 so that neither the scattered write of a near-identity order nor the read conflicts), lane l then
+//             holds sorted positions 4 l .. 4 l + 3, and a Hillis-Steele scan with steps 1, 2, .. 128 runs over the 256
+//             positions in which the element of rank r IN ITS OWN SEGMENT adds the element `step` below it when r >= step.
+//             The last element of a segment of n members then holds their sum, put together by a tree that n alone decides:
+//             where the segment lies in the span, and what lies around it, changes nothing.  Unseated channels (and the
+//             channels past N of the last span) sort last as a segment of their own that is written nowhere: left out, not
+//             multiplied by zero.
+//   returns   the streaming pass above with the room of each of a lane's four channels from the map, S gathered per frame;
+//             an unseated channel and a room of one carry the divisor 0.0, which writes +0.0.
+constexpr uint32_t SKIP = 0xFFFFFFFEu;             // swhole: nobody of the span is seated
+constexpr int MB = 4;                              // frames that go through LDS together
+constexpr uint32_t MROW = SPAN + SPAN / 64;        // floats of one frame's row in LDS: position p at p + p / 64
+
+struct MapArgs {
+    const float *x;
+    const float *gain;           // [N]
+    float *L;                    // [pieces][FS]
+    const uint8_t *pos;          // [nspans * SPAN]: the sorted position of a channel in its span
+    const uint8_t *rank;         // [nspans * SPAN], by sorted position: the rank in its segment
+    const uint32_t *slot;        // [nspans * SPAN], by sorted position: the piece row, at the last element of a seated room's segment; else NONE
+    const uint32_t *swhole;      // [nspans]: the piece row of a span that one room holds wholly; SKIP; NONE: sorted and scanned
+    uint32_t N, Wrow, nf, FS, nspans, nchunks;
+};
+
+// the wave's own LDS writes before its reads, and its reads before the next writes (one wave: the LDS takes them in order)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the value the lane below holds (DPP wave_shr:1, no LDS round trip); lane 0 gets 0.0
+__device__ __forceinline__ float lane_below(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
+
+template <int F, bool GAIN, bool VEC>
+__device__ __forceinline__ void mapped_span(const MapArgs &a, float *lds, uint32_t k, uint32_t f0, uint32_t lane) {
+    const uint32_t c0 = k * SPAN, ch = c0 + 4 * lane;
+    const uint32_t pp = *(const uint32_t *)(a.pos + ch);         // the tables are padded to whole spans
+    const uint32_t rr = *(const uint32_t *)(a.rank + ch);
+    const uint4 ss = *(const uint4 *)(a.slot + ch);
+    const uint32_t sl[4] = {ss.x, ss.y, ss.z, ss.w};
+    bool valid[4];
+    size_t b[4];
+    float gn[4];
+    uint32_t ph[4], rk[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t c = ch + i, p = (pp >> (8 * i)) & 255u;
+        valid[i] = c < a.N;
+        ph[i] = p + (p >> 6);
+        gn[i] = (GAIN && valid[i]) ? a.gain[c] : 1.0f;
+        b[i] = (valid[i] && (i == 0 || !VEC)) ? chan_base(c, a.Wrow, a.nf) : 0;
+        rk[i] = (rr >> (8 * i)) & 255u;
+    }
+    const uint32_t rd = 4 * lane + (lane >> 4);                  // where sorted position 4 * lane lies in a row
+#pragma unroll
+    for (int i0 = 0; i0 < F; i0 += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t f = f0 + i0 + j;
+            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (f < a.nf && valid[0]) {
+                const size_t o = (size_t)f * a.Wrow;
+                if (VEC) {
+                    v[j] = *(const float4 *)(a.x + b[0] + o);
+                } else {
+                    v[j].x = a.x[b[0] + o];
+                    if (valid[1]) v[j].y = a.x[b[1] + o];
+                    if (valid[2]) v[j].z = a.x[b[2] + o];
+                    if (valid[3]) v[j].w = a.x[b[3] + o];
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 8; h += MB) {
+            if (f0 + i0 + h >= a.nf) break;                      // wave-uniform
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                float4 t = v[h + m];
+                if (GAIN) t = make_float4(__fmul_rn(t.x, gn[0]), __fmul_rn(t.y, gn[1]), __fmul_rn(t.z, gn[2]), __fmul_rn(t.w, gn[3]));
+                float *row = lds + m * MROW;
+                row[ph[0]] = t.x;
+                row[ph[1]] = t.y;
+                row[ph[2]] = t.z;
+                row[ph[3]] = t.w;
+            }
+            wave_lds_sync();
+            float s[MB][4];
+#pragma unroll
+            for (int m = 0; m < MB; ++m)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[m][j] = lds[m * MROW + rd + j];
+            wave_lds_sync();
+            // sorted position 4 * lane + j is s[.][j]: steps 1 and 2 stay inside the lane but for the lane below's last elements,
+            // a step of 4 k takes the same register k lanes below.  A position below `step` has a rank below it: no lane reads
+            // past lane 0
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                float (&e)[4] = s[m];
+                const float u3 = lane_below(e[3]);
+                if (rk[3] >= 1u) e[3] = e[3] + e[2];
+                if (rk[2] >= 1u) e[2] = e[2] + e[1];
+                if (rk[1] >= 1u) e[1] = e[1] + e[0];
+                if (rk[0] >= 1u) e[0] = e[0] + u3;
+                const float w2 = lane_below(e[2]), w3 = lane_below(e[3]);
+                if (rk[3] >= 2u) e[3] = e[3] + e[1];
+                if (rk[2] >= 2u) e[2] = e[2] + e[0];
+                if (rk[1] >= 2u) e[1] = e[1] + w3;
+                if (rk[0] >= 2u) e[0] = e[0] + w2;
+            }
+#pragma unroll
+            for (uint32_t k = 1; k < 64; k *= 2) {
+                const int from = (int)((lane - k) & 63u);
+#pragma unroll
+                for (int m = 0; m < MB; ++m)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float u = k == 1 ? lane_below(s[m][j]) : __shfl(s[m][j], from, 64);
+                        if (rk[j] >= 4 * k) s[m][j] = s[m][j] + u;
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (sl[j] == NONE) continue;
+                float *dst = a.L + (size_t)sl[j] * a.FS + f0 + i0 + h;
+#pragma unroll
+                for (int m = 0; m < MB; ++m)
+                    if (f0 + i0 + h + m < a.nf) dst[m] = s[m][j];
+            }
+        }
+    }
+}
+
+template <bool GAIN, bool VEC>
+__global__ __launch_bounds__(P1_WG) void mixrooms_partials(MapArgs a) {
+    __shared__ float lds[P1_WG / 64][MB * MROW];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t item = blockIdx.x * (P1_WG / 64) + wave;
+    if (item >= a.nspans * a.nchunks) return;
+    const uint32_t k = item / a.nchunks, f0 = (item - k * a.nchunks) * CHUNK;
+    const uint32_t sw = a.swhole[k];
+    if (sw == SKIP) return;
+    if (sw != NONE) whole_span<CHUNK, GAIN, VEC>(a, k, sw, f0, lane);
+    else mapped_span<CHUNK, GAIN, VEC>(a, lds[wave], k, f0, lane);
+}
+
+struct RetMapArgs {
+    const float *x;              // may be `out`: no __restrict__
+    float *out;
+    const float *gain;           // [N]
+    const float *S;              // [nf][G] raw sums
+    const uint32_t *room;        // [nspans * SPAN]; NONE: unseated
+    const float *rdiv;           // [G], as RetArgs::rdiv for the room's member count
+    uint32_t N, Wrow, nf, G, nspans, nchunks, norm;
+};
+
+template <bool GAIN, bool VEC>
+__global__ __launch_bounds__(P1_WG) void mixrooms_returns(RetMapArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t item = blockIdx.x * (P1_WG / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (item >= a.nspans * a.nchunks) return;
+    const uint32_t k = item / a.nchunks, f0 = (item - k * a.nchunks) * RCHUNK;
+    const uint32_t ch = k * SPAN + 4 * lane;
+    if (ch >= a.N) return;
+    const uint4 rm = *(const uint4 *)(a.room + ch);
+    const uint32_t r4[4] = {rm.x, rm.y, rm.z, rm.w};
+    uint32_t gi[4];
+    float dv[4], gn[4];
+    bool valid[4];
+    size_t b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t c = ch + i;
+        valid[i] = c < a.N;
+        const bool seated = r4[i] != NONE;
+        gi[i] = seated ? r4[i] : 0u;                 // (a row of S always has room 0)
+        dv[i] = seated ? a.rdiv[gi[i]] : 0.0f;
+        gn[i] = (GAIN && valid[i]) ? a.gain[c] : 1.0f;
+        b[i] = (valid[i] && (i == 0 || !VEC)) ? chan_base(c, a.Wrow, a.nf) : 0;
+    }
+    returns_rows<GAIN, VEC, true>(a.x, a.out, a.S, a.Wrow, a.nf, a.G, a.norm != 0, f0, gi, dv, gn, valid, b);
 }
 
 // ---- the plan: pure host -------------------------------------------------------------------------------------------------
@@ -463,6 +665,158 @@ struct Store {
     hipEvent_t ev = nullptr;
 };
 
+
+// ---- a seating (mapped mode): pure host ---------------------------------------------------------------------------------
+struct RoomPlan {
+    std::vector<uint64_t> count;         // [G] members
+    std::vector<uint64_t> npieces;       // [G]
+    std::vector<uint64_t> first;         // [G] the room's first piece row; its pieces follow in ascending span order
+    std::vector<uint32_t> pdepth;        // [G] the deepest piece
+    uint64_t pieces = 0;
+    std::vector<uint8_t> pos, rank;      // MapArgs
+    std::vector<uint32_t> slot, swhole, room;    // room: padded to whole spans with NONE
+};
+
+uint32_t room_depth(const RoomPlan &pl, uint32_t g) {
+    GroupPieces gp;
+    gp.m = pl.npieces[g];
+    gp.depth = pl.pdepth[g];
+    return depth_of(gp);
+}
+
+// room_of[N], every id < G or NONE (checked by the caller); tables: the kernels' tables too
+void plan_rooms(const uint32_t *room_of, uint64_t N, uint32_t G, bool tables, RoomPlan &pl) {
+    const uint64_t nspans = (N + SPAN - 1) / SPAN;
+    pl.count.assign(G, 0);
+    pl.npieces.assign(G, 0);
+    pl.first.assign(G, 0);
+    pl.pdepth.assign(G, 0);
+    std::vector<uint8_t> ord((size_t)nspans * SPAN);             // the channel (of its span) at a sorted position
+    std::vector<uint8_t> whole(nspans, 0);                       // 1: one room holds the span; 2: nobody is seated in it
+    uint32_t key[SPAN];
+    uint16_t idx[SPAN];
+    for (uint64_t k = 0; k < nspans; ++k) {
+        const uint64_t c0 = k * SPAN;
+        bool sorted = true;
+        for (uint32_t i = 0; i < SPAN; ++i) {
+            key[i] = c0 + i < N ? room_of[c0 + i] : NONE;
+            idx[i] = (uint16_t)i;
+            if (i && key[i] < key[i - 1]) sorted = false;
+        }
+        if (!sorted) std::stable_sort(idx, idx + SPAN, [&](uint16_t x, uint16_t y) { return key[x] < key[y]; });
+        uint8_t *o = ord.data() + c0;
+        for (uint32_t i = 0; i < SPAN; ++i) o[i] = (uint8_t)idx[i];
+        if (key[idx[0]] == NONE) whole[k] = 2;
+        else if (key[idx[0]] == key[idx[SPAN - 1]]) whole[k] = 1;    // 256 members: the span is full
+        for (uint32_t i = 0; i < SPAN;) {                        // the segments
+            const uint32_t g = key[idx[i]];
+            uint32_t e = i + 1;
+            while (e < SPAN && key[idx[e]] == g) ++e;
+            if (g != NONE) {
+                pl.count[g] += e - i;
+                pl.npieces[g] += 1;
+                pl.pdepth[g] = std::max(pl.pdepth[g], whole[k] == 1 ? 8u : ceil_log2(e - i));
+            }
+            i = e;
+        }
+    }
+    pl.pieces = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        pl.first[g] = pl.pieces;
+        pl.pieces += pl.npieces[g];
+    }
+    if (!tables) return;
+    pl.pos.assign((size_t)nspans * SPAN, 0);
+    pl.rank.assign((size_t)nspans * SPAN, 0);
+    pl.slot.assign((size_t)nspans * SPAN, NONE);
+    pl.swhole.assign(nspans, NONE);
+    pl.room.assign((size_t)nspans * SPAN, NONE);
+    std::copy(room_of, room_of + N, pl.room.begin());
+    std::vector<uint64_t> next = pl.first;
+    for (uint64_t k = 0; k < nspans; ++k) {
+        const uint64_t c0 = k * SPAN;
+        const uint8_t *o = ord.data() + c0;
+        if (whole[k] == 2) pl.swhole[k] = SKIP;
+        for (uint32_t i = 0; i < SPAN;) {
+            const uint32_t g = pl.room[c0 + o[i]];
+            uint32_t e = i;
+            for (; e < SPAN && pl.room[c0 + o[e]] == g; ++e) {
+                pl.pos[c0 + o[e]] = (uint8_t)e;
+                pl.rank[c0 + e] = (uint8_t)(e - i);
+            }
+            if (g != NONE) {
+                const uint32_t row = (uint32_t)next[g]++;
+                pl.slot[c0 + e - 1] = row;
+                if (whole[k] == 1) pl.swhole[k] = row;
+            }
+            i = e;
+        }
+    }
+}
+
+int check_rooms(const uint32_t *room_of, uint64_t first, uint64_t count, uint32_t G, std::string &err) {
+    char buf[160];
+    for (uint64_t i = 0; i < count; ++i)
+        if (room_of[i] >= G && room_of[i] != NONE) {
+            std::snprintf(buf, sizeof buf, "mixgroups: channel %llu is given room %u, and there are %u rooms (or DSPFX_MIXGROUPS_NO_ROOM)",
+                          (unsigned long long)(first + i), room_of[i], G);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+    return DSPFX_OK;
+}
+
+struct Seating {
+    std::vector<uint32_t> room;          // [N], host
+    uint64_t pieces = 0;
+    uint8_t *pos = nullptr, *rank = nullptr;
+    uint32_t *slot = nullptr, *swhole = nullptr, *droom = nullptr;
+    float *gdiv = nullptr, *rdiv = nullptr;      // [G]
+    float *P = nullptr;                  // [pieces][FS]
+    std::vector<Level> levels;           // (dtasks_raw with the seating, in a normalising bank)
+    hipEvent_t ev = nullptr;             // of a retired seating: behind the last run that was given it
+};
+
+void free_seating(Seating *t) {
+    if (!t) return;
+    for (void *d : {(void *)t->pos, (void *)t->rank, (void *)t->slot, (void *)t->swhole, (void *)t->droom, (void *)t->gdiv,
+                    (void *)t->rdiv, (void *)t->P})
+        if (d) (void)hipFree(d);
+    for (Level &l : t->levels) {
+        if (l.dtasks) (void)hipFree(l.dtasks);
+        if (l.dtasks_raw) (void)hipFree(l.dtasks_raw);
+        if (l.out) (void)hipFree(l.out);
+    }
+    if (t->ev) (void)hipEventDestroy(t->ev);
+    delete t;
+}
+
+struct Pending {
+    uint32_t g, src0, m, rslot;
+    float div;
+};
+
+// the reduce levels over every group's pieces: up to FAN pieces a task, further levels over the tasks' results
+std::vector<Level> build_levels(std::vector<Pending> cur) {
+    std::vector<Level> levels;
+    while (!cur.empty()) {
+        Level lv;
+        std::vector<Pending> next;
+        for (const Pending &q : cur) {
+            if (q.m <= FAN) {
+                lv.tasks.push_back({q.src0, q.m, q.rslot, q.g, q.div, 1u});
+                continue;
+            }
+            const uint32_t nch = (q.m + FAN - 1) / FAN, base = lv.rows;
+            for (uint32_t c = 0; c < nch; ++c)
+                lv.tasks.push_back({q.src0 + c * FAN, std::min(FAN, q.m - c * FAN), c == 0 ? q.rslot : NONE, lv.rows++, 1.0f, 0u});
+            next.push_back({q.g, base, nch, NONE, q.div});
+        }
+        levels.push_back(std::move(lv));
+        cur.swap(next);
+    }
+    return levels;
+}
 }  // namespace
 
 struct dspfx_mixgroups {
@@ -487,6 +841,11 @@ struct dspfx_mixgroups {
     float *gdiv_raw = nullptr;                   // [G] of 1.0 (a bank with normalise = 0 uses gdiv itself)
     float *rdiv = nullptr;                       // [G]
     uint32_t *sfirst = nullptr;                  // [nspans + 1]
+    // mapped mode (dspfx_mixgroups_assign): nullptr until the first assign
+    std::mutex amu;                              // one assign at a time; taken before mu
+    Seating *seat = nullptr;                     // written under amu and mu
+    std::vector<Seating *> retired;              // replaced seatings that a run in flight may still read (mu)
+    hipStream_t astream = nullptr;               // the table copies of an assign (amu)
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
@@ -515,6 +874,9 @@ void release(dspfx_mixgroups *p) {
     }
     for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
     if (p->ev) (void)hipEventDestroy(p->ev);
+    free_seating(p->seat);
+    for (Seating *t : p->retired) free_seating(t);
+    if (p->astream) (void)hipStreamDestroy(p->astream);
     delete p;
 }
 
@@ -649,10 +1011,6 @@ extern "C" int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mi
     std::vector<uint32_t> gstart(G + 1);
     std::vector<float> gdiv(G, 1.0f);
     std::vector<uint8_t> slow(p->nspans, 0);
-    struct Pending {
-        uint32_t g, src0, m, rslot;
-        float div;
-    };
     std::vector<Pending> cur;
     uint64_t last_n = ~0ull;
     float last_div = 1.0f;
@@ -673,22 +1031,7 @@ extern "C" int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mi
         if (n == 0 || pc.m) cur.push_back({g, (uint32_t)(pc.has_r ? pc.lfirst - 1 : pc.lfirst), (uint32_t)pc.m,
                                            pc.has_r ? (uint32_t)pc.k0 : NONE, gdiv[g]});
     }
-    while (!cur.empty()) {
-        Level lv;
-        std::vector<Pending> next;
-        for (const Pending &q : cur) {
-            if (q.m <= FAN) {
-                lv.tasks.push_back({q.src0, q.m, q.rslot, q.g, q.div, 1u});
-                continue;
-            }
-            const uint32_t nch = (q.m + FAN - 1) / FAN, base = lv.rows;
-            for (uint32_t c = 0; c < nch; ++c)
-                lv.tasks.push_back({q.src0 + c * FAN, std::min(FAN, q.m - c * FAN), c == 0 ? q.rslot : NONE, lv.rows++, 1.0f, 0u});
-            next.push_back({q.g, base, nch, NONE, q.div});
-        }
-        p->levels.push_back(std::move(lv));
-        cur.swap(next);
-    }
+    p->levels = build_levels(std::move(cur));
 
     const size_t prow = (size_t)p->nspans * p->FS * sizeof(float);
     bool ok = hipMalloc((void **)&p->gain, (size_t)N * sizeof(float)) == hipSuccess && hipMalloc((void **)&p->L, prow) == hipSuccess &&
@@ -765,6 +1108,46 @@ extern "C" int dspfx_mixgroups_set_gains(dspfx_mixgroups *p, const float *host_v
     return DSPFX_OK;
 }
 
+namespace {
+
+// the sums of a mapped bank: the pieces, then the reduce levels into dst ([nf][G]; raw: undivided)
+int mapped_sums(dspfx_mixgroups *p, const Seating &t, const float *block, uint32_t n_frames, float *dst, bool raw, bool gain, hipStream_t s) {
+    MapArgs a;
+    a.x = block;
+    a.gain = p->gain;
+    a.L = t.P;
+    a.pos = t.pos;
+    a.rank = t.rank;
+    a.slot = t.slot;
+    a.swhole = t.swhole;
+    a.N = p->desc.n_channels;
+    a.Wrow = p->desc.tile_channels ? p->desc.tile_channels : a.N;
+    a.nf = n_frames;
+    a.FS = p->FS;
+    a.nspans = p->nspans;
+    a.nchunks = (n_frames + CHUNK - 1) / CHUNK;
+    const bool vec = a.Wrow % 4 == 0 && ((uintptr_t)block & 15u) == 0;
+    const uint32_t items = a.nspans * a.nchunks, blocks = (items + P1_WG / 64 - 1) / (P1_WG / 64);
+    if (gain) {
+        if (vec) mixrooms_partials<true, true><<<blocks, P1_WG, 0, s>>>(a);
+        else mixrooms_partials<true, false><<<blocks, P1_WG, 0, s>>>(a);
+    } else {
+        if (vec) mixrooms_partials<false, true><<<blocks, P1_WG, 0, s>>>(a);
+        else mixrooms_partials<false, false><<<blocks, P1_WG, 0, s>>>(a);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(p, DSPFX_ERR_HIP, "mixrooms_partials");
+    const float *src = t.P;
+    for (const Level &l : t.levels) {
+        const dim3 grid((unsigned)l.tasks.size(), (n_frames + 63) / 64);
+        mixgroups_reduce<<<grid, RW * 64, 0, s>>>(raw ? l.dtasks_raw : l.dtasks, src, t.P, l.out, dst, n_frames, p->FS, p->desc.n_groups);
+        if (hipGetLastError() != hipSuccess) return fail(p, DSPFX_ERR_HIP, "mixgroups_reduce");
+        src = l.out;
+    }
+    return DSPFX_OK;
+}
+
+}  // namespace
+
 extern "C" int dspfx_mixgroups_run(dspfx_mixgroups *p, const float *block, uint32_t n_frames, float *buses, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
@@ -773,6 +1156,7 @@ extern "C" int dspfx_mixgroups_run(dspfx_mixgroups *p, const float *block, uint3
     MG_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
     MG_HIP(order(p, s), "stream order");
     MG_HIP(apply_stores(p, s), "fader store");
+    if (p->seat) return mapped_sums(p, *p->seat, block, n_frames, buses, false, p->n_faded != 0, s);
     P1Args a;
     a.x = block;
     a.gain = p->gain;
@@ -899,6 +1283,43 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
     MG_HIP(order(p, s), "stream order");
     MG_HIP(apply_stores(p, s), "fader store");       // once: the sums and the subtraction see the same table
     const bool raw = p->desc.normalise != 0;
+    if (p->seat) {
+        const Seating &t = *p->seat;
+        const bool gain = p->n_faded != 0;
+        const int st = mapped_sums(p, t, block, n_frames, p->S, raw, gain, s);
+        if (st != DSPFX_OK) return st;
+        const uint32_t G = p->desc.n_groups;
+        if (buses) {
+            const uint64_t total = (uint64_t)n_frames * G;
+            mixgroups_divide<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(p->S, t.gdiv, buses, G, total);
+            MG_HIP(hipGetLastError(), "mixgroups_divide");
+        }
+        RetMapArgs r;
+        r.x = block;
+        r.out = returns;
+        r.gain = p->gain;
+        r.S = p->S;
+        r.room = t.droom;
+        r.rdiv = t.rdiv;
+        r.N = p->desc.n_channels;
+        r.Wrow = p->desc.tile_channels ? p->desc.tile_channels : r.N;
+        r.nf = n_frames;
+        r.G = G;
+        r.nspans = p->nspans;
+        r.nchunks = (n_frames + RCHUNK - 1) / RCHUNK;
+        r.norm = raw ? 1u : 0u;
+        const bool vec = r.Wrow % 4 == 0 && (((uintptr_t)block | (uintptr_t)returns) & 15u) == 0;
+        const uint32_t items = r.nspans * r.nchunks, blocks = (items + P1_WG / 64 - 1) / (P1_WG / 64);
+        if (gain) {
+            if (vec) mixrooms_returns<true, true><<<blocks, P1_WG, 0, s>>>(r);
+            else mixrooms_returns<true, false><<<blocks, P1_WG, 0, s>>>(r);
+        } else {
+            if (vec) mixrooms_returns<false, true><<<blocks, P1_WG, 0, s>>>(r);
+            else mixrooms_returns<false, false><<<blocks, P1_WG, 0, s>>>(r);
+        }
+        MG_HIP(hipGetLastError(), "mixrooms_returns");
+        return DSPFX_OK;
+    }
     P1Args a;
     a.x = block;
     a.gain = p->gain;
@@ -947,5 +1368,209 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
     r.norm = raw ? 1u : 0u;
     const bool vec = a.Wrow % 4 == 0 && (((uintptr_t)block | (uintptr_t)returns) & 15u) == 0;
     MG_HIP(launch_returns(r, gain, vec, s), "mixgroups_returns");
+    return DSPFX_OK;
+}
+
+// ---- seating: a room id per channel ------------------------------------------------------------------------------------------
+namespace {
+
+// the tables of a seating, on the device before this returns (copied on the bank's own stream: no run is waited for)
+int make_seating(dspfx_mixgroups *p, std::vector<uint32_t> &&room, Seating **out, const char **why) {
+    const uint32_t G = p->desc.n_groups;
+    RoomPlan pl;
+    plan_rooms(room.data(), p->desc.n_channels, G, true, pl);
+    Seating *t = new (std::nothrow) Seating;
+    if (!t) {
+        *why = "mixgroups assign: no host memory";
+        return DSPFX_ERR_OOM;
+    }
+    t->room = std::move(room);
+    t->pieces = pl.pieces;
+    std::vector<float> gdiv(G, 1.0f), rdiv(G, 1.0f);
+    std::vector<Pending> cur;
+    cur.reserve(G);
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint64_t n = pl.count[g];
+        if (p->desc.normalise) gdiv[g] = dspfx_link_divisor(n);
+        if (n == 1) rdiv[g] = 0.0f;                  // no other pipe: the kernel writes +0.0
+        else if (p->desc.normalise && n >= 2) rdiv[g] = dspfx_link_divisor(n - 1);
+        cur.push_back({g, (uint32_t)pl.first[g], (uint32_t)pl.npieces[g], NONE, gdiv[g]});
+    }
+    t->levels = build_levels(std::move(cur));
+    const bool raw = p->desc.normalise != 0;
+    const size_t cells = (size_t)p->nspans * SPAN;
+    bool ok = hipMalloc((void **)&t->pos, cells) == hipSuccess && hipMalloc((void **)&t->rank, cells) == hipSuccess &&
+              hipMalloc((void **)&t->slot, cells * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc((void **)&t->swhole, (size_t)p->nspans * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc((void **)&t->droom, cells * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc((void **)&t->gdiv, (size_t)G * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&t->rdiv, (size_t)G * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&t->P, (size_t)std::max<uint64_t>(pl.pieces, 1) * p->FS * sizeof(float)) == hipSuccess;
+    for (Level &l : t->levels) {
+        ok = ok && hipMalloc((void **)&l.dtasks, l.tasks.size() * sizeof(Task)) == hipSuccess;
+        if (raw) ok = ok && hipMalloc((void **)&l.dtasks_raw, l.tasks.size() * sizeof(Task)) == hipSuccess;
+        if (l.rows) ok = ok && hipMalloc((void **)&l.out, (size_t)l.rows * p->FS * sizeof(float)) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        free_seating(t);
+        *why = "mixgroups assign: no device memory for the seating's tables and its pieces [pieces][max_frames]";
+        return DSPFX_ERR_OOM;
+    }
+    hipStream_t s = p->astream;
+    std::vector<std::vector<Task>> rawtasks;         // alive until the copies are done
+    ok = hipMemcpyAsync(t->pos, pl.pos.data(), cells, hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(t->rank, pl.rank.data(), cells, hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(t->slot, pl.slot.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(t->swhole, pl.swhole.data(), (size_t)p->nspans * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(t->droom, pl.room.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(t->gdiv, gdiv.data(), (size_t)G * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(t->rdiv, rdiv.data(), (size_t)G * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess;
+    for (Level &l : t->levels) {
+        ok = ok && hipMemcpyAsync(l.dtasks, l.tasks.data(), l.tasks.size() * sizeof(Task), hipMemcpyHostToDevice, s) == hipSuccess;
+        if (raw) {
+            rawtasks.push_back(l.tasks);
+            for (Task &q : rawtasks.back()) q.div = 1.0f;
+            ok = ok && hipMemcpyAsync(l.dtasks_raw, rawtasks.back().data(), l.tasks.size() * sizeof(Task), hipMemcpyHostToDevice, s) == hipSuccess;
+        }
+    }
+    const bool done = hipStreamSynchronize(s) == hipSuccess;     // (also after a failed copy: the host arrays go away)
+    if (!ok || !done) {
+        (void)hipGetLastError();
+        free_seating(t);
+        *why = "mixgroups assign: copying the seating's tables";
+        return DSPFX_ERR_HIP;
+    }
+    *out = t;
+    return DSPFX_OK;
+}
+
+int assign_fail(dspfx_mixgroups *p, int rc, const std::string &what) {
+    std::lock_guard<std::mutex> lk(p->mu);           // the reason is the bank's, and a run may be writing one
+    p->err = what;
+    return rc;
+}
+
+void rooms_of_table(const std::vector<uint32_t> &gs, std::vector<uint32_t> &room) {
+    for (size_t g = 0; g + 1 < gs.size(); ++g) std::fill(room.begin() + gs[g], room.begin() + gs[g + 1], (uint32_t)g);
+}
+
+}  // namespace
+
+extern "C" int dspfx_mixgroups_assign(dspfx_mixgroups *p, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> alk(p->amu);
+    const uint64_t N = p->desc.n_channels;
+    if (!host_room_ids || count == 0) return assign_fail(p, DSPFX_ERR_INVALID, "mixgroups assign: no ids");
+    if (first_channel >= N || count > N - first_channel) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "mixgroups assign: channels [%llu, %llu + %llu) are not inside the bank's %llu",
+                      (unsigned long long)first_channel, (unsigned long long)first_channel, (unsigned long long)count, (unsigned long long)N);
+        return assign_fail(p, DSPFX_ERR_INVALID, buf);
+    }
+    std::string why;
+    if (check_rooms(host_room_ids, first_channel, count, p->desc.n_groups, why) != DSPFX_OK) return assign_fail(p, DSPFX_ERR_INVALID, why);
+    // the map so far: only an assign changes it, and this is the only one running
+    std::vector<uint32_t> room;
+    try {
+        if (p->seat) {
+            room = p->seat->room;
+        } else {
+            room.assign(N, NONE);
+            rooms_of_table(p->hstart, room);
+        }
+    } catch (const std::bad_alloc &) {
+        return assign_fail(p, DSPFX_ERR_OOM, "mixgroups assign: no host memory");
+    }
+    std::copy(host_room_ids, host_room_ids + count, room.begin() + (size_t)first_channel);
+    if (hipSetDevice(p->desc.device) != hipSuccess) return assign_fail(p, DSPFX_ERR_HIP, "hipSetDevice");
+    if (!p->astream && hipStreamCreateWithFlags(&p->astream, hipStreamNonBlocking) != hipSuccess) {
+        p->astream = nullptr;
+        return assign_fail(p, DSPFX_ERR_HIP, "mixgroups assign: no stream for the table copies");
+    }
+    Seating *t = nullptr;
+    const char *what = "";
+    int rc;
+    try {
+        rc = make_seating(p, std::move(room), &t, &what);
+    } catch (const std::bad_alloc &) {
+        rc = DSPFX_ERR_OOM;
+        what = "mixgroups assign: no host memory";
+    }
+    if (rc != DSPFX_OK) return assign_fail(p, rc, what);
+    // the switch: every run submitted from here on is given the new seating; the old one stays until the last run given it is done
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (size_t i = 0; i < p->retired.size();) {
+        if (hipEventQuery(p->retired[i]->ev) == hipSuccess) {
+            free_seating(p->retired[i]);
+            p->retired[i] = p->retired.back();
+            p->retired.pop_back();
+        } else {
+            (void)hipGetLastError();
+            ++i;
+        }
+    }
+    Seating *old = p->seat;
+    p->seat = t;
+    if (old) {
+        if (p->used && hipEventCreateWithFlags(&old->ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(old->ev, p->last) == hipSuccess) {
+            p->retired.push_back(old);
+        } else {
+            if (p->used) (void)hipStreamSynchronize(p->last);    // no event to be had: wait instead
+            free_seating(old);
+        }
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixgroups_rooms(dspfx_mixgroups *p, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const uint64_t N = p->desc.n_channels;
+    if (!host_ids_out || first_channel > N || count > N - first_channel) return fail(p, DSPFX_ERR_INVALID, "mixgroups rooms: the array or the range");
+    if (p->seat) {
+        std::copy(p->seat->room.begin() + (size_t)first_channel, p->seat->room.begin() + (size_t)(first_channel + count), host_ids_out);
+        return DSPFX_OK;
+    }
+    uint32_t g = 0;
+    for (uint64_t c = first_channel; c < first_channel + count; ++c) {
+        while (p->hstart[g + 1] <= c) ++g;
+        host_ids_out[c - first_channel] = g;
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixgroups_room_plan(const uint32_t *room_of, uint64_t n_channels, uint32_t n_groups, uint32_t tile_channels,
+                                         uint64_t *count_out, uint32_t *depth_out, uint64_t *pieces_out) {
+    g_err.clear();
+    char buf[160];
+    if (!room_of || n_groups == 0) {
+        g_err = "mixgroups: no room ids, or no rooms";
+        return DSPFX_ERR_INVALID;
+    }
+    if (n_channels == 0 || n_channels > 0xFFFFFF00ull) {
+        g_err = "mixgroups: n_channels must be 1 .. 2^32 - 256";
+        return DSPFX_ERR_INVALID;
+    }
+    if (tile_channels && (!pow2(tile_channels) || n_channels % tile_channels)) {
+        std::snprintf(buf, sizeof buf, "mixgroups: tile_channels %u is not a power of two that divides n_channels %llu", tile_channels,
+                      (unsigned long long)n_channels);
+        g_err = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    const int rc = check_rooms(room_of, 0, n_channels, n_groups, g_err);
+    if (rc != DSPFX_OK) return rc;
+    RoomPlan pl;
+    try {
+        plan_rooms(room_of, n_channels, n_groups, false, pl);
+    } catch (const std::bad_alloc &) {
+        g_err = "mixgroups: no host memory";
+        return DSPFX_ERR_OOM;
+    }
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        if (count_out) count_out[g] = pl.count[g];
+        if (depth_out) depth_out[g] = room_depth(pl, g);
+        if (pieces_out) pieces_out[g] = pl.npieces[g];
+    }
     return DSPFX_OK;
 }

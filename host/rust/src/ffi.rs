@@ -211,6 +211,8 @@ pub const DSPFX_RESAMPLE_MAX_FRAMES: u32 = 4096;
 pub const DSPFX_CONVOLVE_MAX_TAPS: u32 = 524288;
 // the responses one convolver bank holds
 pub const DSPFX_CONVOLVE_MAX_RESPONSES: u32 = 256;
+/// `DSPFX_MIXGROUPS_NO_ROOM`: the id of a channel that sits in no room.
+pub const DSPFX_MIXGROUPS_NO_ROOM: u32 = 0xFFFF_FFFF;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -376,6 +378,9 @@ extern "C" {
     pub fn dspfx_mixgroups_returns(m: *mut dspfx_mixgroups, block: *const f32, n_frames: u32, buses: *mut f32, returns: *mut f32, stream: *mut c_void) -> c_int;
     pub fn dspfx_mixgroups_set_gains(m: *mut dspfx_mixgroups, host_values: *const f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixgroups_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, depth_out: *mut u32) -> c_int;
+    pub fn dspfx_mixgroups_assign(m: *mut dspfx_mixgroups, host_room_ids: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixgroups_rooms(m: *mut dspfx_mixgroups, host_ids_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixgroups_room_plan(room_of: *const u32, n_channels: u64, n_groups: u32, tile_channels: u32, count_out: *mut u64, depth_out: *mut u32, pieces_out: *mut u64) -> c_int;
     pub fn dspfx_convolve_create(desc: *const dspfx_convolve_desc, out: *mut *mut dspfx_convolve) -> c_int;
     pub fn dspfx_convolve_destroy(p: *mut dspfx_convolve) -> c_int;
     pub fn dspfx_convolve_reset(p: *mut dspfx_convolve) -> c_int;

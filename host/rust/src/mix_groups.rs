@@ -18,7 +18,7 @@ pub struct MixGroups {
     groups: u32,
 }
 unsafe impl Send for MixGroups {}
-// runs are serialised by the bank's own lock; fader stores only take the store queue's
+// runs are serialised by the bank's own lock; fader stores only take the store queue's, a seating change its own and then the bank's
 unsafe impl Sync for MixGroups {}
 
 fn reason(h: *const dspfx_mixgroups, what: &str) -> String {
@@ -78,6 +78,33 @@ impl MixGroups {
     pub fn clear_gains(&self, first_channel: u64, count: u64) -> Result<(), Error> {
         let rc = unsafe { dspfx_mixgroups_set_gains(self.h, ptr::null(), first_channel, count) };
         self.check(rc, "dspfx_mixgroups_set_gains")
+    }
+    /// Seats channels `first_channel ..` in the rooms `ids` (each `< groups()` or `DSPFX_MIXGROUPS_NO_ROOM`); a bad id or range
+    /// stores nothing.  Any thread, while runs are in flight: it holds for the runs submitted after it returns.  The channels'
+    /// faders, and their state in the engine, stay where they are: a participant changes rooms without a click.
+    pub fn assign(&self, ids: &[u32], first_channel: u64) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixgroups_assign(self.h, ids.as_ptr(), first_channel, ids.len() as u64) };
+        self.check(rc, "dspfx_mixgroups_assign")
+    }
+    /// The room of every channel as the next run sees it.
+    pub fn room_of(&self) -> Result<Vec<u32>, Error> {
+        let mut ids = vec![0u32; self.channels as usize];
+        let rc = unsafe { dspfx_mixgroups_rooms(self.h, ids.as_mut_ptr(), 0, ids.len() as u64) };
+        self.check(rc, "dspfx_mixgroups_rooms")?;
+        Ok(ids)
+    }
+    /// Checks a map (a room id or `DSPFX_MIXGROUPS_NO_ROOM` per channel) and gives, per room, (member count, depth D of its sum
+    /// in mapped mode, pieces); a pure host function.
+    pub fn room_plan(room_of: &[u32], groups: u32, tile_channels: u32) -> Result<(Vec<u64>, Vec<u32>, Vec<u64>), Error> {
+        let g = groups as usize;
+        let (mut count, mut depth, mut pieces) = (vec![0u64; g], vec![0u32; g], vec![0u64; g]);
+        let rc = unsafe {
+            dspfx_mixgroups_room_plan(room_of.as_ptr(), room_of.len() as u64, groups, tile_channels, count.as_mut_ptr(), depth.as_mut_ptr(), pieces.as_mut_ptr())
+        };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixgroups_room_plan") });
+        }
+        Ok((count, depth, pieces))
     }
     /// Checks a table and gives, per group, the longest chain of dependent f32 additions in its sum (a pure host function).
     pub fn plan(group_start: &[u64], channels: u64, tile_channels: u32) -> Result<Vec<u32>, Error> {

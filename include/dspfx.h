@@ -889,6 +889,50 @@ int dspfx_mixgroups_set_gains(dspfx_mixgroups *m, const float *host_values, uint
  * every addition the kernels make on the path).  depth_out may be NULL. */
 int dspfx_mixgroups_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
                          uint32_t *depth_out);
+/* Seating: a room id per channel, reseated live.  A channel is a participant -- its biquad state, delay ring and FIR history
+ * live at its index in the engine -- so a participant who changes rooms keeps the index and changes the id.  A bank has the G
+ * rooms of its create table and every channel starts in the room its range puts it in; dspfx_mixgroups_assign moves channels
+ * between those G rooms, or out of all of them (DSPFX_MIXGROUPS_NO_ROOM).  A bank on which assign is never called has no map
+ * and launches the kernels above with the arguments above.  MAPPED MODE starts with the first assign, whatever it stores; from
+ * then on a room that is still a contiguous range may differ from the unmapped bits, within the documented bound (the order
+ * below is another one).
+ * Arithmetic: dspfx_mixgroups_run and _returns as stated above with "group g" read as {c : room[c] == g} and n_g as its member
+ * count: the same terms t[f][c], one IEEE division by dspfx_link_divisor(n_g) (normalise = 0: the raw sums), an empty room
+ * gives +0.0, a return is fl32(fl32(S - t) / dspfx_link_divisor(n_g - 1)), +0.0 in a room of one; nothing is contracted.  A
+ * channel carrying +inf gets NaN in its own return and +inf in the others', a NaN channel makes every return of its room NaN.
+ * Faders belong to the channel and move with it.  An UNSEATED channel is in no sum and its return is +0.0 whatever it carries:
+ * it is left out, not multiplied by zero, so its NaN or inf reaches no bus and no return.
+ * Summation order: fixed, no atomics, and for one room a function of the room's MEMBER SET (and the layout) alone: the bus is
+ * the same bits whatever the other channels' seating is, whatever the room's own id is, whatever sequence of assigns produced
+ * the map, from run to run and on any stream.  Channels are cut into spans of 256 from channel 0.  A span whose 256 channels
+ * are all the room's: as above, (x0 + x1) + (x2 + x3) per lane and the lane tree.  Any other span: the room's members in the
+ * span, in ascending channel order, are summed by a Hillis-Steele scan over their RANKS (member r adds member r - step when
+ * r >= step, steps 1, 2, .. 128): the tree is decided by how many members the span holds, not by where they sit.  The spans'
+ * sums, in ascending span order, are added 64 at a time as above.  D, the longest chain of dependent additions, is at most
+ * 8 + the reduce rounds' and stays under 64 + ceil(log2(max(n, 1))); dspfx_mixgroups_room_plan reports it per room, and the
+ * error bounds of run and returns hold with this D.
+ * Memory: a seating holds 10 bytes per channel of tables and its pieces, [pieces][max_frames rounded up to 64] f32 with
+ * pieces = the sum over the spans of the rooms seated in the span: N / 256 for rooms that are whole spans, up to N -- one
+ * block, [max_frames][N] f32 -- when every channel of a span sits in another room.  While runs given the old seating are in
+ * flight, the old and the new one exist side by side. */
+#define DSPFX_MIXGROUPS_NO_ROOM 0xFFFFFFFFu
+/* Stores the room ids of channels [first_channel, first_channel + count) from a host array.  Every id (< G, or
+ * DSPFX_MIXGROUPS_NO_ROOM) and the range are checked before anything is stored: otherwise DSPFX_ERR_INVALID, the reason in
+ * dspfx_mixgroups_last_error, nothing changed.  It holds for every run submitted after it returns and for none submitted
+ * before: blocks in flight keep the old seating.  Callable from any thread while runs are in flight, and the caller need not
+ * idle the device: a seating change, not a per-block call -- O(N) host work, device memory for the new seating allocated on the
+ * calling thread (DSPFX_ERR_OOM: the seating is unchanged, a later call may try again), and the call waits for its own table
+ * copy, which travels on a stream of the bank's own. */
+int dspfx_mixgroups_assign(dspfx_mixgroups *m, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count);
+/* The room ids of channels [first_channel, first_channel + count) as the next run will see them (the create table's, on a bank
+ * without a map). */
+int dspfx_mixgroups_rooms(dspfx_mixgroups *m, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count);
+/* PURE HOST function (no GPU, no bank): checks a map room_of[n_channels] as assign does (an id that is neither < n_groups nor
+ * DSPFX_MIXGROUPS_NO_ROOM, or a tile that is not a power of two dividing n_channels: DSPFX_ERR_INVALID and the reason) and
+ * gives, per room, count_out[g] = n_g, depth_out[g] = D in mapped mode, and pieces_out[g] = the room's pieces (their sum is the
+ * seating's piece count).  Each of the three may be NULL.  A room's D and pieces depend on its own members alone. */
+int dspfx_mixgroups_room_plan(const uint32_t *room_of, uint64_t n_channels, uint32_t n_groups, uint32_t tile_channels,
+                              uint64_t *count_out, uint32_t *depth_out, uint64_t *pieces_out);
 
 /* ---- convolver bank: one long impulse response by partitioned FFT ----------------------------------------------
  * The FIR node takes any WAV file as its impulse response (nodes/fir.rs:86-173); the engine restates that arithmetic in the

@@ -26,6 +26,7 @@ struct Error : std::runtime_error {
 };
 
 constexpr std::size_t BUF_SIZE = DSPFX_BUF_SIZE;   // node.rs:257
+constexpr std::uint32_t NO_ROOM = DSPFX_MIXGROUPS_NO_ROOM;                         // MixGroups::assign: the channel sits in no room
 constexpr std::uint32_t CONVOLVE_MAX_RESPONSES = DSPFX_CONVOLVE_MAX_RESPONSES;   // the responses one Convolver holds
 
 // nodes/distort.rs:18-28
@@ -457,6 +458,19 @@ class MixGroups {
     void set_gains(const float *host_values, std::uint64_t first_channel, std::uint64_t count) {
         chk(dspfx_mixgroups_set_gains(p_, host_values, first_channel, count));
     }
+    // seating (dspfx_mixgroups_assign): the rooms of channels [first_channel, first_channel + ids.size()), each < groups() or
+    // NO_ROOM; a bad id or range stores nothing.  Any thread; holds for the runs submitted after it returns, and the channels'
+    // faders (and their state in the engine) stay where they are
+    void assign(const std::vector<std::uint32_t> &ids, std::uint64_t first_channel = 0) {
+        chk(dspfx_mixgroups_assign(p_, ids.data(), first_channel, ids.size()));
+    }
+    void assign(std::uint32_t id, std::uint64_t first_channel) { chk(dspfx_mixgroups_assign(p_, &id, first_channel, 1)); }
+    // the room of each of `count` channels from first_channel, as the next run sees them
+    std::vector<std::uint32_t> room_of(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> ids(count);
+        chk(dspfx_mixgroups_rooms(p_, ids.data(), first_channel, count));
+        return ids;
+    }
     dspfx_mixgroups *raw() { return p_; }
 
   private:
@@ -475,6 +489,20 @@ inline std::vector<std::uint32_t> mixgroups_plan(const std::vector<std::uint64_t
     const int rc = dspfx_mixgroups_plan(group_start.data(), (std::uint32_t)depth.size(), channels, tile_channels, depth.data());
     if (rc != DSPFX_OK) throw Error(rc, dspfx_mixgroups_last_error(nullptr));
     return depth;
+}
+
+// Checks a map (a room id or NO_ROOM per channel) and gives, per room, its member count, the depth D of its sum in mapped mode
+// and its pieces (dspfx_mixgroups_room_plan: a pure host function, no GPU).
+struct RoomPlan {
+    std::vector<std::uint64_t> count;
+    std::vector<std::uint32_t> depth;
+    std::vector<std::uint64_t> pieces;
+};
+inline RoomPlan mixgroups_room_plan(const std::vector<std::uint32_t> &room_of, std::uint32_t groups, std::uint32_t tile_channels = 0) {
+    RoomPlan r{std::vector<std::uint64_t>(groups), std::vector<std::uint32_t>(groups), std::vector<std::uint64_t>(groups)};
+    const int rc = dspfx_mixgroups_room_plan(room_of.data(), room_of.size(), groups, tile_channels, r.count.data(), r.depth.data(), r.pieces.data());
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixgroups_last_error(nullptr));
+    return r;
 }
 
 // One long impulse response over N channels by partitioned FFT (dspfx_convolve_*): the FIR node's arithmetic for responses too

@@ -6,10 +6,13 @@ alternating input blocks filled with noise, every channel with a fader stored (t
   chain    Engine.process of [Gain(1.0)], which reads AND writes the block: twice the bank's bytes
   returns  MixGroups.returns (every channel's room minus itself) into a third buffer: run's read, one more read and one write of
            the block, three times the bank's bytes
+--seating S (contiguous | movers | random) reseats case (a) through MixGroups.assign first, so that the mapped kernels run:
+contiguous is the create table assigned unchanged, movers swaps one channel in 64 with a channel of another room, random
+permutes the rooms over the channels; the row's "pieces" is the seating's piece count (0 without --seating: no map).
 Device events around every call, --reps runs after 5 warm-ups, the median; the fraction of peak is block bytes / time / 8 TB/s.
 One JSON line per case, then a table.
 
-  python tools/mixgroups_rate.py [--channels 65536,262144,1048576] [--reps 20]
+  python tools/mixgroups_rate.py [--channels 65536,262144,1048576] [--reps 20] [--seating contiguous|movers|random]
 """
 import argparse
 import json
@@ -49,7 +52,20 @@ def timed(torch, fn, reps):
     return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(reps)]))
 
 
-def measure(torch, n, reps):
+def seating_of(name, n):
+    """the room of every channel for case (a), reseated"""
+    rng = np.random.default_rng(71)
+    room = (np.arange(n) // 256).astype(np.uint32)
+    if name == "movers":
+        pick = np.arange(0, n, 64) + rng.integers(0, 64, n // 64)
+        partner = np.roll(pick, 7)
+        room[pick], room[partner] = room[partner].copy(), room[pick].copy()
+    elif name == "random":
+        room = rng.permutation(room)
+    return room
+
+
+def measure(torch, n, reps, seating=None):
     dev = torch.device("cuda:0")
     eng = pkg.Engine(n, B, link_flags=0, device=0, tile_channels=W)
     eng.set_chain([pkg.Gain(1.0)])
@@ -65,12 +81,15 @@ def measure(torch, n, reps):
         mg = pkg.MixGroups(n, group_start=table, tile_channels=W, max_frames=B)
         if fader:
             mg.set_gains(np.random.default_rng(61).uniform(0.0, 4.0, n).astype(np.float32))
+        if seating and case != "b":
+            mg.assign(seating_of(seating, n))
         buses = torch.empty((B, mg.groups), dtype=torch.float32, device=dev)
         ms = timed(torch, lambda i: mg.run(xs[i % 2], B, out=buses), reps)
         ret = timed(torch, lambda i: mg.returns(xs[i % 2], B, out=y), reps)
         r = {"channels": n, "case": case, "groups": mg.groups, "ms": ms, "fraction_of_peak": B * n * 4 / (ms * 1e-3) / PEAK,
              "returns_ms": ret, "returns_fraction_of_peak": 3 * B * n * 4 / (ret * 1e-3) / PEAK,
-             "chain_ms": chain, "chain_fraction_of_peak": 2 * B * n * 4 / (chain * 1e-3) / PEAK, "depth_max": int(mg.depth().max())}
+             "chain_ms": chain, "chain_fraction_of_peak": 2 * B * n * 4 / (chain * 1e-3) / PEAK, "depth_max": int(mg.depth().max()),
+             "seating": seating if case != "b" else None, "pieces": mg.pieces()}
         print(json.dumps(r), flush=True)
         rows.append(r)
         mg.close()
@@ -82,19 +101,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", default="65536,262144,1048576")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--seating", choices=["contiguous", "movers", "random"], default=None,
+                    help="reseat the uniform cases through assign(): the mapped kernels")
     a = ap.parse_args()
     import torch
     rows = []
     for n in (int(s) for s in a.channels.split(",")):
-        rows += measure(torch, n, a.reps)
+        rows += measure(torch, n, a.reps, a.seating)
         torch.cuda.empty_cache()
     print(f"\ntimes in ms, median of {a.reps}; fractions of the 8 TB/s HBM peak")
     print(f"{'channels':>9} {'case':>7} {'groups':>7} {'bank':>8} {'of peak':>8} {'chain':>8} {'of peak':>8} {'bank/chain':>10} "
-          f"{'returns':>8} {'of peak':>8}")
+          f"{'returns':>8} {'of peak':>8} {'pieces':>8}")
     for r in rows:
         print(f"{r['channels']:>9} {r['case']:>7} {r['groups']:>7} {r['ms']:>8.4f} {r['fraction_of_peak']:>8.3f} {r['chain_ms']:>8.4f} "
               f"{r['chain_fraction_of_peak']:>8.3f} {r['ms'] / r['chain_ms']:>10.2f} {r['returns_ms']:>8.4f} "
-              f"{r['returns_fraction_of_peak']:>8.3f}")
+              f"{r['returns_fraction_of_peak']:>8.3f} {r['pieces']:>8}")
 
 
 if __name__ == "__main__":
