@@ -53,6 +53,7 @@ SPECTRUM_RATE = 48000.0         # spectrogram.rs:238 sampling_rate: bin k of an 
 CONVOLVE_MAX_TAPS = 524288      # DSPFX_CONVOLVE_MAX_TAPS: the longest response a Convolver takes (4096 partitions of 128)
 NO_ROOM = 0xFFFFFFFF            # DSPFX_MIXGROUPS_NO_ROOM: MixGroups.assign, the channel sits in no room
 CONVOLVE_MAX_RESPONSES = 256    # DSPFX_CONVOLVE_MAX_RESPONSES: the responses one Convolver holds
+STRIPS_MAX_BANDS = 8            # DSPFX_STRIPS_MAX_BANDS: the BiQuad bands one ChannelStrips bank holds per channel
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -80,6 +81,8 @@ EXPORTS = [
     "dspfx_convolve_create", "dspfx_convolve_destroy", "dspfx_convolve_reset", "dspfx_convolve_run", "dspfx_convolve_set_taps",
     "dspfx_convolve_plan", "dspfx_convolve_response_add", "dspfx_convolve_response_set", "dspfx_convolve_assign",
     "dspfx_convolve_response_count",
+    "dspfx_strips_create", "dspfx_strips_destroy", "dspfx_strips_last_error", "dspfx_strips_run", "dspfx_strips_set_gain",
+    "dspfx_strips_set_band", "dspfx_strips_reset", "dspfx_strips_present", "dspfx_strips_coeffs",
 ]
 COMM_ID_BYTES = 128
 
@@ -139,6 +142,11 @@ class _MixGroupsDesc(C.Structure):
 class _ConvolveDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("channels", C.c_uint32), ("tile_channels", C.c_uint32),
                 ("n_taps", C.c_uint32), ("max_taps", C.c_uint32), ("mode", C.c_int32), ("taps_reversed", C.POINTER(C.c_double))]
+
+
+class _StripsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("bands", C.c_uint32), ("link_flags", C.c_uint32)]
 
 
 class _Ctl(C.Structure):
@@ -293,6 +301,16 @@ def lib():
     L.dspfx_convolve_response_set.argtypes = [vp, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_int]
     L.dspfx_convolve_assign.argtypes = [vp, C.POINTER(C.c_uint16), C.c_uint64, C.c_uint64]
     L.dspfx_convolve_response_count.argtypes = [vp]
+    L.dspfx_strips_create.argtypes = [C.POINTER(_StripsDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_strips_destroy.argtypes = [vp]
+    L.dspfx_strips_last_error.restype = C.c_char_p
+    L.dspfx_strips_last_error.argtypes = [vp]
+    L.dspfx_strips_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_strips_set_gain.argtypes = [vp, C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
+    L.dspfx_strips_set_band.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
+    L.dspfx_strips_reset.argtypes = [vp]
+    L.dspfx_strips_present.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
+    L.dspfx_strips_coeffs.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1459,6 +1477,111 @@ class Convolver:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.L.dspfx_convolve_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def strips_coeffs(raw6) -> np.ndarray:
+    """dspfx_strips_coeffs, a pure host function (no GPU): the raw BiQuad sliders a0, a1, a2, b0, b1, b2 -> float32[5] =
+    a1, a2, b0, b1, b2 normalised as regenerate_filter does (biquad.rs:66-70), exactly as the device gets them."""
+    L = lib()
+    r = np.ascontiguousarray(raw6, np.float32).reshape(-1)
+    if len(r) != 6:
+        raise DspfxError(-1, "a BiQuad band is six raw sliders: a0, a1, a2, b0, b1, b2")
+    out = np.zeros(5, np.float32)
+    rc = L.dspfx_strips_coeffs(r.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    return out
+
+
+class ChannelStrips:
+    """Per-channel Gain and BiQuad sliders (include/dspfx.h, dspfx_strips_*): the strip of channel c is a chain of up to
+    1 + `bands` optional nodes in a fixed order -- a Gain node, then BiQuad bands 0 .. bands-1 -- each with the channel's own
+    slider values, over a device block in the layout of `tile_channels` (as Engine's).  A node exists for a channel from the
+    first store that names it until it is dropped (None); a fresh bank copies its input.  `link_flags` as Engine's: the
+    collect_and_average hops into a channel's first present node (LINK_INPUT) and between its present nodes (LINK_INTERNAL).
+    Between eng.process and MixGroups.run / returns, or ahead of the chain.  Asynchronous on `stream`."""
+
+    def __init__(self, channels: int, bands: int = 1, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
+                 device: int = 0):
+        self.L = lib()
+        self.channels, self.bands, self.tile_channels = int(channels), int(bands), int(tile_channels)
+        self.max_frames, self.link_flags, self.device = int(max_frames), int(link_flags), int(device)
+        self.h = C.c_void_p()
+        d = _StripsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
+                        self.bands & 0xFFFFFFFF, self.link_flags & 0xFFFFFFFF)
+        rc = self.L.dspfx_strips_create(C.byref(d), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_strips_last_error(None).decode() or self.L.dspfx_strerror(rc).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_strips_last_error(self.h).decode() or self.L.dspfx_strerror(rc).decode())
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every channel's strip -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_strips_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        return out
+
+    def set_gain(self, levels, first_channel: int = 0, count: Optional[int] = None):
+        """Store the Gain level of channels from first_channel: an array (one level per channel), or a scalar for `count`
+        channels (default: all from first_channel); levels=None drops the Gain node of `count` channels.  Any thread; applies
+        to the runs submitted after it."""
+        first = int(first_channel)
+        if levels is None or np.ndim(levels) == 0:
+            n = self.channels - first if count is None else int(count)
+            if levels is None:
+                self._chk(self.L.dspfx_strips_set_gain(self.h, None, first, n))
+                return
+            levels = np.full(max(n, 0), levels, np.float32)
+        v = np.ascontiguousarray(levels, np.float32).reshape(-1)
+        self._chk(self.L.dspfx_strips_set_gain(self.h, v.ctypes.data_as(C.POINTER(C.c_float)), first, len(v)))
+
+    def set_band(self, band: int, coeffs, first_channel: int = 0, count: Optional[int] = None):
+        """Store BiQuad band `band` of channels from first_channel: `coeffs` is [count][6] raw sliders a0, a1, a2, b0, b1, b2
+        (one row per channel), or one 6-vector for `count` channels (default: all from first_channel); coeffs=None drops the
+        band.  The store zeroes the band's state on exactly those channels, as the reference's slider change does.  Any thread;
+        applies to the runs submitted after it."""
+        first = int(first_channel)
+        if coeffs is None or np.ndim(coeffs) == 1:
+            n = self.channels - first if count is None else int(count)
+            if coeffs is None:
+                self._chk(self.L.dspfx_strips_set_band(self.h, int(band) & 0xFFFFFFFF, None, first, n))
+                return
+            coeffs = np.tile(np.asarray(coeffs, np.float32).reshape(1, -1), (max(n, 0), 1))
+        v = np.ascontiguousarray(coeffs, np.float32)
+        if v.ndim != 2 or v.shape[1] != 6:
+            raise DspfxError(-1, "a BiQuad band is six raw sliders per channel: a0, a1, a2, b0, b1, b2")
+        self._chk(self.L.dspfx_strips_set_band(self.h, int(band) & 0xFFFFFFFF, v.ctypes.data_as(C.POINTER(C.c_float)), first, len(v)))
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the node mask of every channel as the next run sees it; bit 0 = Gain, bit 1 + b = band b."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        v = np.zeros(max(n, 0), np.uint32)
+        self._chk(self.L.dspfx_strips_present(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
+        return v
+
+    def reset(self):
+        """Zero all state (on the stream last used); the sliders and the nodes stay."""
+        self._chk(self.L.dspfx_strips_reset(self.h))
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_strips_destroy(h)
             h.value = None
 
     def __del__(self):

@@ -124,6 +124,25 @@ pub struct dspfx_spectrum_desc {
     pub gain: *const f32,
 }
 
+/// Opaque channel-strip bank handle (`typedef struct dspfx_strips dspfx_strips`).
+#[repr(C)]
+pub struct dspfx_strips {
+    _private: [u8; 0],
+}
+
+/// The channel-strip bank's descriptor (`dspfx_strips_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_strips_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub bands: u32,
+    pub link_flags: u32,
+}
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -211,6 +230,8 @@ pub const DSPFX_RESAMPLE_MAX_FRAMES: u32 = 4096;
 pub const DSPFX_CONVOLVE_MAX_TAPS: u32 = 524288;
 // the responses one convolver bank holds
 pub const DSPFX_CONVOLVE_MAX_RESPONSES: u32 = 256;
+/// the BiQuad bands one channel-strip bank holds per channel
+pub const DSPFX_STRIPS_MAX_BANDS: u32 = 8;
 /// `DSPFX_MIXGROUPS_NO_ROOM`: the id of a channel that sits in no room.
 pub const DSPFX_MIXGROUPS_NO_ROOM: u32 = 0xFFFF_FFFF;
 
@@ -391,4 +412,13 @@ extern "C" {
     pub fn dspfx_convolve_response_set(p: *mut dspfx_convolve, id: u32, taps_reversed: *const f64, n_taps: u32, mode: c_int) -> c_int;
     pub fn dspfx_convolve_assign(p: *mut dspfx_convolve, host_ids: *const u16, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_convolve_response_count(p: *const dspfx_convolve) -> c_int;
+    pub fn dspfx_strips_create(desc: *const dspfx_strips_desc, out: *mut *mut dspfx_strips) -> c_int;
+    pub fn dspfx_strips_destroy(s: *mut dspfx_strips) -> c_int;
+    pub fn dspfx_strips_last_error(s: *const dspfx_strips) -> *const c_char;
+    pub fn dspfx_strips_run(s: *mut dspfx_strips, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_strips_set_gain(s: *mut dspfx_strips, host_levels: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_strips_set_band(s: *mut dspfx_strips, band: u32, host_raw6: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_strips_reset(s: *mut dspfx_strips) -> c_int;
+    pub fn dspfx_strips_present(s: *mut dspfx_strips, host_masks_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_strips_coeffs(raw6: *const f32, out5: *mut f32) -> c_int;
 }

@@ -6,3 +6,4 @@ pub mod gpu_chain;
 pub mod mix_groups;
 pub mod convolver;
 pub mod convolver_responses;
+pub mod channel_strips;

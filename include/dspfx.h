@@ -1024,6 +1024,70 @@ int dspfx_convolve_response_count(const dspfx_convolve *p);
 /* In all four, the checks that need no device -- a NULL bank, NULL taps or ids, count == 0, the mode, the rules for the taps
  * -- come first and return DSPFX_ERR_INVALID with or without a GPU. */
 
+/* ---- channel strips: per-channel Gain and BiQuad sliders ---------------------------------------------------------
+ * An engine runs one chain for all its channels with ONE set of slider values.  In the reference every graph has its own node
+ * instances and its own Atomic<f32> sliders (gain.rs:21-22, biquad.rs:18-41): N channels are N independent sets of settings.
+ * This bank is that for the two node kinds where a participant's own settings matter most -- an input trim and a high-pass or
+ * EQ ahead of the room.  It sits between the N-channel chain and dspfx_mixgroups_run / _returns, or ahead of the chain.
+ * The strip of channel c is a chain of up to 1 + K optional nodes in a fixed order:
+ *       a Gain node                 out = in * level[c]                                           gain.rs:25-38
+ *       BiQuad bands 0 .. K-1       y = b0*x + b1*x1 + b2*x2 - a1*y1 - a2*y2, then the DF1 shift  biquad.rs:62-88
+ * A node EXISTS for a channel from the first store that names it until it is dropped; a fresh bank has no node anywhere and
+ * run copies in to out bit for bit.  A channel's output is what the reference gives a graph made of exactly that channel's
+ * present nodes with that channel's slider values.  The level is taken as given, as a restored config's is (no clamp to the
+ * slider range 0..=10).  The biquad step is evaluated left to right in f32 with nothing contracted -- the engine's BIQUAD
+ * expression -- on four f32 of state per band and channel (x1, x2, y1, y2), kept between runs, zero after create and reset.
+ * link_flags has the meaning of dspfx_engine_desc.link_flags: DSPFX_LINK_INPUT puts one collect_and_average hop,
+ * (0.0f + v) / f32(0.0001 + 1.0) (node.rs:162-194, an IEEE division), ahead of a channel's first present node,
+ * DSPFX_LINK_INTERNAL one between consecutive present nodes; a channel without a node gets no hop.
+ * A channel's output is the same bits in either layout, in place or not, in one call of 256 frames or two of 128, on any
+ * stream, and whatever its neighbours carry (a NaN channel changes no other channel). */
+#define DSPFX_STRIPS_MAX_BANDS 8
+typedef struct dspfx_strips dspfx_strips;
+typedef struct dspfx_strips_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t bands;           /* K: 1 ..= DSPFX_STRIPS_MAX_BANDS */
+    uint32_t link_flags;      /* DSPFX_LINK_INTERNAL | DSPFX_LINK_INPUT; any other bit: DSPFX_ERR_INVALID */
+} dspfx_strips_desc;
+/* A bad descriptor is DSPFX_ERR_INVALID with the reason in dspfx_strips_last_error of a NULL bank (kept per thread); all of
+ * that is checked before any device work.  Memory: (9 K' + 2) * 4 bytes per channel, K' = K rounded up to 1, 2, 4 or 8. */
+int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips **out);
+int dspfx_strips_destroy(dspfx_strips *s);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create. */
+const char *dspfx_strips_last_error(const dspfx_strips *s);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out == in works in place
+ * (a thread rewrites the elements it read); any other overlap is the caller's error.  Asynchronous on `stream`; a run on
+ * another stream than the one before first waits (on the device) for that one, since the state is the bank's (the rules of
+ * dspfx_mixgroups_run).  Queued slider stores go onto the stream ahead of the kernel, in the order they were made. */
+int dspfx_strips_run(dspfx_strips *s, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Stores the Gain level of channels [first_channel, first_channel + count) from a host array; host_levels = NULL removes the
+ * Gain node for that range.  The contract of dspfx_mixgroups_set_gains: callable from any thread while runs are in flight,
+ * never waits for the device or for a run; the values are copied into a page-locked staging buffer and queued, and the next
+ * run applies the queued stores in order: a run submitted after the call returns sees the new values, the runs submitted
+ * before it the old ones.  A range past the bank's channels stores nothing: DSPFX_ERR_INVALID, the reason in
+ * dspfx_strips_last_error. */
+int dspfx_strips_set_gain(dspfx_strips *s, const float *host_levels, uint64_t first_channel, uint64_t count);
+/* Stores band `band` of channels [first_channel, first_channel + count): host_raw6 is [count][6] raw sliders in the reference's
+ * field order a0, a1, a2, b0, b1, b2 (biquad.rs:18-41).  The host normalises as regenerate_filter does (biquad.rs:66-70: five
+ * f32 divisions by a0; a0 = 0 gives the infinities or NaNs the reference would get, no check is made), and the store zeroes
+ * the four state values of exactly the stored channels' band (reset_state, biquad.rs:74) and touches nothing else: the
+ * reference's after_settings_change.  host_raw6 = NULL removes the band for the range; a later store starts it from zero
+ * state.  Threading and ordering as dspfx_strips_set_gain.  band >= K or a range past the channels: DSPFX_ERR_INVALID and the
+ * reason, nothing stored. */
+int dspfx_strips_set_band(dspfx_strips *s, uint32_t band, const float *host_raw6, uint64_t first_channel, uint64_t count);
+/* Zeroes all state and keeps the sliders and the nodes; queued on the stream last used. */
+int dspfx_strips_reset(dspfx_strips *s);
+/* The node mask of channels [first_channel, first_channel + count) as the next run will see it: bit 0 = the Gain node,
+ * bit 1 + b = band b. */
+int dspfx_strips_present(dspfx_strips *s, uint32_t *host_masks_out, uint64_t first_channel, uint64_t count);
+/* PURE HOST function (no GPU, no bank): out5 = a1, a2, b0, b1, b2, the five normalised coefficients of the raw sliders raw6
+ * exactly as the device gets them. */
+int dspfx_strips_coeffs(const float *raw6, float *out5);
+
 #ifdef __cplusplus
 }
 #endif

@@ -505,6 +505,61 @@ inline RoomPlan mixgroups_room_plan(const std::vector<std::uint32_t> &room_of, s
     return r;
 }
 
+// Per-channel Gain and BiQuad sliders (include/dspfx.h, dspfx_strips_*): the strip of channel c is a chain of up to 1 + bands
+// optional nodes in a fixed order -- a Gain node, then BiQuad bands 0 .. bands-1 -- each with the channel's own slider values,
+// over a device block in the layout of tile_channels.  A node exists for a channel from the first store that names it until it
+// is dropped (nullptr); a fresh bank copies its input.  Between Engine::process and MixGroups::run / returns, or ahead of the chain.
+class ChannelStrips {
+  public:
+    ChannelStrips(std::uint32_t channels, std::uint32_t bands = 1, std::uint32_t tile_channels = 0,
+                  std::uint32_t max_frames = DSPFX_BUF_SIZE, std::uint32_t link_flags = 0, int device = 0)
+        : bands_(bands) {
+        const dspfx_strips_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, bands, link_flags};
+        const int rc = dspfx_strips_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_strips_last_error(nullptr) ? dspfx_strips_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelStrips() { dspfx_strips_destroy(p_); }
+    ChannelStrips(const ChannelStrips &) = delete;
+    ChannelStrips &operator=(const ChannelStrips &) = delete;
+    std::uint32_t bands() const { return bands_; }
+    // device block of n_frames -> device block in the same layout (out == in: in place); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_strips_run(p_, in, out, n_frames, stream)); }
+    // Gain levels of channels [first_channel, first_channel + count) from a host array; nullptr drops the node.  Any thread; never waits.
+    void set_gain(const float *host_levels, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_strips_set_gain(p_, host_levels, first_channel, count));
+    }
+    // band `band` of those channels from [count][6] raw sliders a0, a1, a2, b0, b1, b2; nullptr drops the band.  The store zeroes the
+    // band's state on exactly those channels (the reference's after_settings_change).  Any thread; never waits.
+    void set_band(std::uint32_t band, const float *host_raw6, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_strips_set_band(p_, band, host_raw6, first_channel, count));
+    }
+    // zero all state, keep the sliders and the nodes
+    void reset() { chk(dspfx_strips_reset(p_)); }
+    // the node mask of each of `count` channels from first_channel, as the next run sees it: bit 0 = Gain, bit 1 + b = band b
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_strips_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    dspfx_strips *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_strips_last_error(p_) ? dspfx_strips_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_strips *p_ = nullptr;
+    std::uint32_t bands_;
+};
+
+// The five normalised coefficients a1, a2, b0, b1, b2 of six raw BiQuad sliders exactly as the device gets them
+// (dspfx_strips_coeffs: a pure host function, no GPU).
+inline std::vector<float> strips_coeffs(const float (&raw6)[6]) {
+    std::vector<float> k(5);
+    const int rc = dspfx_strips_coeffs(raw6, k.data());
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_strerror(rc));
+    return k;
+}
+
 // One long impulse response over N channels by partitioned FFT (dspfx_convolve_*): the FIR node's arithmetic for responses too
 // long for its tap table, e.g. a convolution reverb on the G buses of a MixGroups.  `taps_reversed` as dspfx_set_taps takes them.
 class Convolver {
