@@ -54,6 +54,8 @@ CONVOLVE_MAX_TAPS = 524288      # DSPFX_CONVOLVE_MAX_TAPS: the longest response 
 NO_ROOM = 0xFFFFFFFF            # DSPFX_MIXGROUPS_NO_ROOM: MixGroups.assign, the channel sits in no room
 CONVOLVE_MAX_RESPONSES = 256    # DSPFX_CONVOLVE_MAX_RESPONSES: the responses one Convolver holds
 STRIPS_MAX_BANDS = 8            # DSPFX_STRIPS_MAX_BANDS: the BiQuad bands one ChannelStrips bank holds per channel
+MIXMATRIX_MAX_ROOM = 1024       # DSPFX_MIXMATRIX_MAX_ROOM: the most members a MixMatrix room has
+MIXMATRIX_MIX_MINUS, MIXMATRIX_ZERO = 0, 1      # DSPFX_MIXMATRIX_*: MixMatrix.fill presets
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -83,6 +85,8 @@ EXPORTS = [
     "dspfx_convolve_response_count",
     "dspfx_strips_create", "dspfx_strips_destroy", "dspfx_strips_last_error", "dspfx_strips_run", "dspfx_strips_set_gain",
     "dspfx_strips_set_band", "dspfx_strips_reset", "dspfx_strips_present", "dspfx_strips_coeffs",
+    "dspfx_mixmatrix_plan", "dspfx_mixmatrix_create", "dspfx_mixmatrix_destroy", "dspfx_mixmatrix_last_error", "dspfx_mixmatrix_run",
+    "dspfx_mixmatrix_set_rows", "dspfx_mixmatrix_set_cols", "dspfx_mixmatrix_fill", "dspfx_mixmatrix_reset",
 ]
 COMM_ID_BYTES = 128
 
@@ -147,6 +151,12 @@ class _ConvolveDesc(C.Structure):
 class _StripsDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("bands", C.c_uint32), ("link_flags", C.c_uint32)]
+
+
+class _MixMatrixDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("n_groups", C.c_uint32), ("normalise", C.c_uint32),
+                ("group_start", C.POINTER(C.c_uint64))]
 
 
 class _Ctl(C.Structure):
@@ -311,6 +321,17 @@ def lib():
     L.dspfx_strips_reset.argtypes = [vp]
     L.dspfx_strips_present.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
     L.dspfx_strips_coeffs.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.dspfx_mixmatrix_plan.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.dspfx_mixmatrix_create.argtypes = [C.POINTER(_MixMatrixDesc), C.POINTER(vp)]
+    L.dspfx_mixmatrix_destroy.argtypes = [vp]
+    L.dspfx_mixmatrix_last_error.restype = C.c_char_p
+    L.dspfx_mixmatrix_last_error.argtypes = [vp]
+    L.dspfx_mixmatrix_run.argtypes = [vp, f32p, C.c_uint32, f32p, vp]
+    L.dspfx_mixmatrix_set_rows.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32, C.c_uint64, C.c_uint64]
+    L.dspfx_mixmatrix_set_cols.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32, C.c_uint64, C.c_uint64]
+    L.dspfx_mixmatrix_fill.argtypes = [vp, C.c_int64, C.c_uint32]
+    L.dspfx_mixmatrix_reset.argtypes = [vp]
     _lib = L
     return L
 
@@ -1582,6 +1603,104 @@ class ChannelStrips:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.L.dspfx_strips_destroy(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mixmatrix_plan(channels: int, group_start=None, group_size=None, tile_channels: int = 0):
+    """dspfx_mixmatrix_plan, a pure host function (no GPU): checks the room table as MixMatrix does (DspfxError with the reason
+    when it is bad: an empty room, one above MIXMATRIX_MAX_ROOM, a table that does not cover the channels) and ->
+    (count uint32[G], edge uint32[G], offset uint64[G], total_bytes): per room its members, the edge of its padded table (the
+    count rounded up to 32) and the element offset of that table, and the bytes of all the tables."""
+    L = lib()
+    t = _group_table(int(channels), group_start, group_size)
+    G = len(t) - 1
+    count, edge, offset = np.zeros(G, np.uint32), np.zeros(G, np.uint32), np.zeros(G, np.uint64)
+    total = C.c_uint64(0)
+    u32 = C.POINTER(C.c_uint32)
+    rc = L.dspfx_mixmatrix_plan(t.ctypes.data_as(C.POINTER(C.c_uint64)), G, int(channels), int(tile_channels), count.ctypes.data_as(u32),
+                                edge.ctypes.data_as(u32), offset.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    if rc != 0:
+        raise DspfxError(rc, L.dspfx_mixmatrix_last_error(None).decode() or L.dspfx_strerror(rc).decode())
+    return count, edge, offset, int(total.value)
+
+
+class MixMatrix:
+    """Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an
+    n_r x n_r float32 matrix M[l][s] (listener, source), and out[f][c0 + l] = (sum_s M[l][s] * x[f][c0 + s]) / link_divisor(w),
+    w = the listener's non-zero entries (a row of zeros gives +0.0; normalise=False writes the raw sum), for a device block in the
+    layout of `tile_channels` (as Engine's).  Rooms as MixGroups takes them: group_start (G + 1 indices) or group_size; every
+    room has 1 .. MIXMATRIX_MAX_ROOM members.  A fresh bank holds mix-minus (1.0 off the diagonal), which is MixGroups.returns
+    without faders.  Between ChannelStrips.run and the listeners' Resampler, as an alternative to returns.  The rooms are fixed: a
+    host that reseats channels with MixGroups.assign makes a new MixMatrix for the new table.  Asynchronous on `stream`."""
+
+    def __init__(self, channels: int, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE,
+                 normalise: bool = True, device: int = 0, abi_version: int = ABI_VERSION):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.max_frames, self.normalise = int(max_frames), bool(normalise)
+        self.group_start = _group_table(self.channels, group_start, group_size)
+        self.groups = len(self.group_start) - 1
+        self.h = C.c_void_p()
+        d = _MixMatrixDesc(int(abi_version) & 0xFFFFFFFF, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF,
+                           self.tile_channels & 0xFFFFFFFF, self.groups, int(self.normalise),
+                           self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
+        rc = self.L.dspfx_mixmatrix_create(C.byref(d), C.byref(self.h))        # the table is copied before this returns
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise DspfxError(rc, self.L.dspfx_mixmatrix_last_error(None).decode() or self.L.dspfx_strerror(rc).decode())
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DspfxError(rc, self.L.dspfx_mixmatrix_last_error(self.h).decode() or self.L.dspfx_strerror(rc).decode())
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every room's matrix -> `out`, a device block in the same layout (made when not given).
+        `out` may not overlap `block`: every listener reads every source of its room, so there is no in-place form."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_mixmatrix_run(self.h, _ptr(block), int(n_frames), _ptr(out), C.c_void_p(stream) if stream else None))
+        return out
+
+    def _lines(self, fn, values, first_channel, count):
+        v = np.ascontiguousarray(values, np.float32)
+        if v.ndim == 1:
+            v = v.reshape(1, -1)
+        if v.ndim != 2 or (count is not None and int(count) != v.shape[0]):
+            raise DspfxError(-1, "values is [count][n_r]: one line of the room's member count per channel")
+        self._chk(fn(self.h, v.ctypes.data_as(C.POINTER(C.c_float)), v.shape[1] & 0xFFFFFFFF, int(first_channel), v.shape[0]))
+
+    def set_rows(self, values, first_channel: int, count: Optional[int] = None):
+        """What listeners first_channel .. hear: values[count][n_r], row i = the gains of listener first_channel + i on the n_r
+        sources of its room (one row may be given as a vector).  All listeners must be in one room.  Any thread; never waits for a
+        run; applies, whole, to the runs submitted after it."""
+        self._lines(self.L.dspfx_mixmatrix_set_rows, values, first_channel, count)
+
+    def set_cols(self, values, first_channel: int, count: Optional[int] = None):
+        """How loud sources first_channel .. are: values[count][n_r], row i = the gain of source first_channel + i for each of the
+        n_r listeners of its room (a source fader; zeros mute someone for everybody).  Rules as set_rows."""
+        self._lines(self.L.dspfx_mixmatrix_set_cols, values, first_channel, count)
+
+    def fill(self, room: Optional[int] = None, preset: int = MIXMATRIX_MIX_MINUS):
+        """Room `room` (None: every room) back to a preset: MIXMATRIX_MIX_MINUS (1.0 off the diagonal) or MIXMATRIX_ZERO."""
+        self._chk(self.L.dspfx_mixmatrix_fill(self.h, -1 if room is None else int(room), int(preset) & 0xFFFFFFFF))
+
+    def reset(self):
+        """The fresh state: mix-minus in every room (queued like a store)."""
+        self._chk(self.L.dspfx_mixmatrix_reset(self.h))
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.L.dspfx_mixmatrix_destroy(h)
             h.value = None
 
     def __del__(self):

@@ -124,6 +124,26 @@ pub struct dspfx_spectrum_desc {
     pub gain: *const f32,
 }
 
+/// Opaque mix-matrix bank handle (`typedef struct dspfx_mixmatrix dspfx_mixmatrix`).
+#[repr(C)]
+pub struct dspfx_mixmatrix {
+    _private: [u8; 0],
+}
+
+/// The mix-matrix bank's descriptor (`dspfx_mixmatrix_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_mixmatrix_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub n_groups: u32,
+    pub normalise: u32,
+    pub group_start: *const u64,
+}
+
 /// Opaque channel-strip bank handle (`typedef struct dspfx_strips dspfx_strips`).
 #[repr(C)]
 pub struct dspfx_strips {
@@ -232,6 +252,9 @@ pub const DSPFX_CONVOLVE_MAX_TAPS: u32 = 524288;
 pub const DSPFX_CONVOLVE_MAX_RESPONSES: u32 = 256;
 /// the BiQuad bands one channel-strip bank holds per channel
 pub const DSPFX_STRIPS_MAX_BANDS: u32 = 8;
+pub const DSPFX_MIXMATRIX_MAX_ROOM: u32 = 1024;
+pub const DSPFX_MIXMATRIX_MIX_MINUS: u32 = 0;
+pub const DSPFX_MIXMATRIX_ZERO: u32 = 1;
 /// `DSPFX_MIXGROUPS_NO_ROOM`: the id of a channel that sits in no room.
 pub const DSPFX_MIXGROUPS_NO_ROOM: u32 = 0xFFFF_FFFF;
 
@@ -421,4 +444,13 @@ extern "C" {
     pub fn dspfx_strips_reset(s: *mut dspfx_strips) -> c_int;
     pub fn dspfx_strips_present(s: *mut dspfx_strips, host_masks_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_strips_coeffs(raw6: *const f32, out5: *mut f32) -> c_int;
+    pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
+    pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;
+    pub fn dspfx_mixmatrix_last_error(m: *const dspfx_mixmatrix) -> *const c_char;
+    pub fn dspfx_mixmatrix_run(m: *mut dspfx_mixmatrix, block: *const f32, n_frames: u32, out: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_mixmatrix_set_rows(m: *mut dspfx_mixmatrix, host_values: *const f32, row_len: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixmatrix_set_cols(m: *mut dspfx_mixmatrix, host_values: *const f32, row_len: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixmatrix_fill(m: *mut dspfx_mixmatrix, room: i64, preset: u32) -> c_int;
+    pub fn dspfx_mixmatrix_reset(m: *mut dspfx_mixmatrix) -> c_int;
 }

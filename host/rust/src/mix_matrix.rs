@@ -1,0 +1,115 @@
+//! `MixMatrix`: each listener's own mix of their room (`dspfx_mixmatrix_*`).
+//!
+//! In the reference every participant has an Output node of their own and wires it to whichever of the others they like through
+//! Gain nodes of their own (output.rs:215-249, node.rs:162-194, gain.rs:25-38): a gain per (listener, source) pair.  Room r of n_r
+//! contiguous channels owns an n_r x n_r matrix `M[l][s]`, and a DEVICE block gives
+//! `out[f][c0 + l] = (sum_s M[l][s] * x[f][c0 + s]) / link_divisor(w)`, w = the listener's entries that are not zero.  A fresh bank
+//! holds mix-minus, which is `MixGroups::returns` without faders; a host binds it between `ChannelStrips::run` and the listeners'
+//! resampler when listeners need mixes of their own.  The GUI thread stores rows and columns, which never wait for the device: the
+//! next `run` applies them in order, each whole.  The rooms are fixed: a host that reseats makes a new bank for the new table.
+//! NOT compiled in the build container (no rustc).
+use super::engine::Error;
+use super::ffi::*;
+use std::ffi::CStr;
+use std::os::raw::{c_int, c_void};
+use std::ptr;
+
+pub struct MixMatrix {
+    h: *mut dspfx_mixmatrix,
+    channels: u32,
+    rooms: u32,
+}
+unsafe impl Send for MixMatrix {}
+// runs are serialised by the bank's own lock; stores only take the store queue's
+unsafe impl Sync for MixMatrix {}
+
+fn reason(h: *const dspfx_mixmatrix, what: &str) -> String {
+    let msg = unsafe { CStr::from_ptr(dspfx_mixmatrix_last_error(h)) }.to_string_lossy().into_owned();
+    if msg.is_empty() { what.into() } else { msg }
+}
+
+/// What `dspfx_mixmatrix_plan` reports: per room its members, the edge of its padded matrix and that matrix's element offset.
+pub struct MixMatrixPlan {
+    pub count: Vec<u32>,
+    pub edge: Vec<u32>,
+    pub offset: Vec<u64>,
+    pub total_bytes: u64,
+}
+
+impl MixMatrix {
+    /// `group_start`: G + 1 channel indices from 0 to `channels`, every room 1 ..= `DSPFX_MIXMATRIX_MAX_ROOM` members;
+    /// `tile_channels`: 0 (frame-major) or the engine's W.
+    pub fn new(device: i32, channels: u32, group_start: &[u64], tile_channels: u32, max_frames: u32, normalise: bool) -> Result<Self, Error> {
+        let rooms = group_start.len().saturating_sub(1) as u32;
+        let desc = dspfx_mixmatrix_desc {
+            abi_version: DSPFX_ABI_VERSION,
+            device,
+            n_channels: channels,
+            max_frames,
+            tile_channels,
+            n_groups: rooms,
+            normalise: normalise as u32,
+            group_start: group_start.as_ptr(),
+        };
+        let mut h = ptr::null_mut();
+        let rc = unsafe { dspfx_mixmatrix_create(&desc, &mut h) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_create") });
+        }
+        Ok(MixMatrix { h, channels, rooms })
+    }
+    fn check(&self, rc: c_int, what: &str) -> Result<(), Error> {
+        if rc == DSPFX_OK { Ok(()) } else { Err(Error { status: rc, message: reason(self.h, what) }) }
+    }
+    pub fn channels(&self) -> u32 { self.channels }
+    pub fn rooms(&self) -> u32 { self.rooms }
+    /// A DEVICE block of `n_frames` frames in the bank's layout through every room's matrix into the DEVICE block `out`, which
+    /// may not overlap `block`.  Asynchronous on `stream`.
+    pub unsafe fn run(&self, block: *const f32, n_frames: u32, out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+        let rc = dspfx_mixmatrix_run(self.h, block, n_frames, out, stream);
+        self.check(rc, "dspfx_mixmatrix_run")
+    }
+    /// What listeners `first_channel ..` of one room hear: `values` is `[count][row_len]`, `row_len` the room's member count.
+    pub fn set_rows(&self, values: &[f32], row_len: u32, first_channel: u64) -> Result<(), Error> {
+        let count = if row_len == 0 { 0 } else { values.len() as u64 / row_len as u64 };
+        let rc = unsafe { dspfx_mixmatrix_set_rows(self.h, values.as_ptr(), row_len, first_channel, count) };
+        self.check(rc, "dspfx_mixmatrix_set_rows")
+    }
+    /// How loud sources `first_channel ..` are for each listener of their room: `values` is `[count][row_len]`.
+    pub fn set_cols(&self, values: &[f32], row_len: u32, first_channel: u64) -> Result<(), Error> {
+        let count = if row_len == 0 { 0 } else { values.len() as u64 / row_len as u64 };
+        let rc = unsafe { dspfx_mixmatrix_set_cols(self.h, values.as_ptr(), row_len, first_channel, count) };
+        self.check(rc, "dspfx_mixmatrix_set_cols")
+    }
+    /// Room `room` (`None`: every room) back to `DSPFX_MIXMATRIX_MIX_MINUS` or `DSPFX_MIXMATRIX_ZERO`.
+    pub fn fill(&self, room: Option<u32>, preset: u32) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixmatrix_fill(self.h, room.map_or(-1, |r| r as i64), preset) };
+        self.check(rc, "dspfx_mixmatrix_fill")
+    }
+    /// The fresh state: mix-minus in every room.
+    pub fn reset(&self) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixmatrix_reset(self.h) };
+        self.check(rc, "dspfx_mixmatrix_reset")
+    }
+    /// The table's plan without a GPU (a pure host function); `Err` with the reason for a table `new` would refuse.
+    pub fn plan(channels: u64, group_start: &[u64], tile_channels: u32) -> Result<MixMatrixPlan, Error> {
+        let g = group_start.len().saturating_sub(1);
+        let mut p = MixMatrixPlan { count: vec![0; g], edge: vec![0; g], offset: vec![0; g], total_bytes: 0 };
+        let rc = unsafe {
+            dspfx_mixmatrix_plan(group_start.as_ptr(), g as u32, channels, tile_channels, p.count.as_mut_ptr(), p.edge.as_mut_ptr(),
+                                 p.offset.as_mut_ptr(), &mut p.total_bytes)
+        };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_plan") });
+        }
+        Ok(p)
+    }
+}
+
+impl Drop for MixMatrix {
+    fn drop(&mut self) {
+        unsafe {
+            dspfx_mixmatrix_destroy(self.h);
+        }
+    }
+}

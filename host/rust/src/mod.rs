@@ -7,3 +7,4 @@ pub mod mix_groups;
 pub mod convolver;
 pub mod convolver_responses;
 pub mod channel_strips;
+pub mod mix_matrix;

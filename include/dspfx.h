@@ -1088,6 +1088,85 @@ int dspfx_strips_present(dspfx_strips *s, uint32_t *host_masks_out, uint64_t fir
  * exactly as the device gets them. */
 int dspfx_strips_coeffs(const float *raw6, float *out5);
 
+/* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
+ * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
+ * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain
+ * nodes of their own (nodes/output.rs:215-249, node.rs:162-194, gain.rs:25-38): "A mutes B for themself only", "C turns D up"
+ * and "nearer people are louder" are all a gain per (listener, source) pair.  This bank holds that pair table.
+ * Rooms are contiguous channel ranges given as dspfx_mixgroups_create takes them (group_start, G + 1 indices); room r has
+ * 1 <= n_r <= DSPFX_MIXMATRIX_MAX_ROOM members and owns an n_r x n_r f32 matrix M_r[l][s] (listener l, source s, room-local
+ * indices).  For a device block x of n_frames frames in the desc's layout (tile_channels as dspfx_engine_desc):
+ *       out[f][c0 + l] = (sum over s in [0, n_r) of M_r[l][s] * x[f][c0 + s]) / d[c0 + l]
+ * normalise = 1: d = dspfx_link_divisor(w), w = the WIRED entries of the listener's row, an entry being wired when it is not
+ * +-0.0; one IEEE f32 division.  A row without a wired entry gives +0.0 whatever the samples are, as dspfx_mixgroups_returns
+ * does in a room of one.  normalise = 0 writes the raw sum (and still +0.0 for a row without a wired entry).  A fresh bank
+ * holds mix-minus in every room -- 1.0 off the diagonal, +0.0 on it -- so it is dspfx_mixgroups_returns of a bank without
+ * faders, up to the order of summation.
+ * KNOWN DIFFERENCE from the reference: a wire through a Gain node of level 0 counts in the reference's divisor and not here.  A
+ * caller who needs that uses normalise = 0 and scales the rows.
+ * Non-finite samples: unwired entries are multiplications by zero, not omissions, so a NaN or an infinity in a source reaches
+ * every listener OF ITS OWN ROOM (0 * inf = NaN), and no listener of another room: sources outside the room are never read.
+ * Arithmetic: v_mfma_f32_32x32x2_f32, which is bit for bit an f32 fmaf chain: a listener's sources are added in ascending
+ * room-local order into one chain (then zero terms up to n_r rounded up to 32), so the result is within
+ *       (n_r + 2) 2^-24 (sum over s of |M[l][s] x[s]|) / d + 2^-149
+ * of the exact value, and a room's output bits are a function of its own matrix, its own samples and n_r alone: the same from
+ * run to run, on any stream, in either layout, for any n_frames, and whatever the other rooms hold.  No atomics.
+ * Memory: the matrices are kept source-major with edges padded to a multiple of 32: 4 * sum over the rooms of
+ * (n_r rounded up to 32)^2 bytes (dspfx_mixmatrix_plan gives it; 1 GiB for 4096 rooms of 256), 8 bytes per channel beside it.
+ * Rooms are fixed: a host that reseats participants with dspfx_mixgroups_assign destroys the bank and creates one for the new
+ * table (and stores the rows again); rooms above the limit, sparse tables and reduced precision are not offered. */
+#define DSPFX_MIXMATRIX_MAX_ROOM 1024
+/* dspfx_mixmatrix_fill presets: 1.0 off the diagonal and +0.0 on it; all +0.0 */
+#define DSPFX_MIXMATRIX_MIX_MINUS 0
+#define DSPFX_MIXMATRIX_ZERO 1
+typedef struct dspfx_mixmatrix dspfx_mixmatrix;
+typedef struct dspfx_mixmatrix_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t n_groups;        /* G >= 1 rooms */
+    uint32_t normalise;       /* 1: divide by the link divisor of the listener's wired count; 0: the raw sums */
+    const uint64_t *group_start; /* host, [n_groups + 1], read at create and copied: room g is channels [group_start[g],
+                                 group_start[g + 1]); increasing, [0] = 0, [G] = N; every room has 1 .. 1024 members */
+} dspfx_mixmatrix_desc;
+/* PURE HOST function (no GPU, no bank): checks a table as create does and gives, per room, count_out[g] = n_g, edge_out[g] =
+ * n_g rounded up to 32 (the edge of its padded table) and offset_out[g] = the element offset of its table, and
+ * *total_bytes_out = the bytes of all tables.  Each of the four may be NULL.  A table that decreases, does not start at 0 or end
+ * at n_channels, an empty room, a room above DSPFX_MIXMATRIX_MAX_ROOM, or a tile that is not a power of two dividing
+ * n_channels: DSPFX_ERR_INVALID, the reason in dspfx_mixmatrix_last_error(NULL). */
+int dspfx_mixmatrix_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
+                         uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out);
+/* A bad descriptor (what dspfx_mixmatrix_plan refuses, another ABI version, max_frames of 0) is DSPFX_ERR_INVALID with the
+ * reason in dspfx_mixmatrix_last_error of a NULL bank (kept per thread); all of that is checked before any device work. */
+int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mixmatrix **out);
+int dspfx_mixmatrix_destroy(dspfx_mixmatrix *m);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_mixmatrix_last_error(const dspfx_mixmatrix *m);
+/* block, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out may NOT overlap block:
+ * a room's inputs are all needed after its first outputs exist, so there is no in-place form; an overlap is DSPFX_ERR_INVALID
+ * and nothing is launched.  Asynchronous on `stream`; a run on another stream than the one before first waits (on the device)
+ * for that one (the rules of dspfx_mixgroups_run).  Queued stores go onto the stream ahead of the kernel, in the order they
+ * were made. */
+int dspfx_mixmatrix_run(dspfx_mixmatrix *m, const float *block, uint32_t n_frames, float *out, void *stream);
+/* What listeners [first_channel, first_channel + count) hear: host_values is [count][row_len], row i = M[l][0 .. n_r) of
+ * listener first_channel + i.  All listeners must be in ONE room and row_len must be that room's n_r; otherwise, or with a range
+ * past the channels, DSPFX_ERR_INVALID, the reason in dspfx_mixmatrix_last_error, nothing stored.  The contract of
+ * dspfx_mixgroups_set_gains: callable from any thread while runs are in flight, never waits for the device or for a run; the
+ * values are copied into a page-locked staging buffer and queued, and the next run applies the queued stores in order, each
+ * whole: a run submitted after the call returns sees the new values, the runs submitted before it the old ones.  The wired
+ * counts and divisors of the listeners touched are recomputed on the device behind the store. */
+int dspfx_mixmatrix_set_rows(dspfx_mixmatrix *m, const float *host_values, uint32_t row_len, uint64_t first_channel, uint64_t count);
+/* How loud sources [first_channel, first_channel + count) are: host_values is [count][row_len], row i = M[0 .. n_r)[s] of
+ * source first_channel + i, one value per listener of its room (a source fader, or muting someone for everybody).  Rules,
+ * threading and ordering as dspfx_mixmatrix_set_rows. */
+int dspfx_mixmatrix_set_cols(dspfx_mixmatrix *m, const float *host_values, uint32_t row_len, uint64_t first_channel, uint64_t count);
+/* Room `room` (-1: every room) back to a preset, DSPFX_MIXMATRIX_MIX_MINUS or DSPFX_MIXMATRIX_ZERO; queued like a store. */
+int dspfx_mixmatrix_fill(dspfx_mixmatrix *m, int64_t room, uint32_t preset);
+/* The fresh state: mix-minus in every room; queued like a store. */
+int dspfx_mixmatrix_reset(dspfx_mixmatrix *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -560,6 +560,64 @@ inline std::vector<float> strips_coeffs(const float (&raw6)[6]) {
     return k;
 }
 
+// Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
+// matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
+// MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
+// faders.  Between ChannelStrips::run and the listeners' Resampler, as an alternative to returns.  The rooms are fixed.
+class MixMatrix {
+  public:
+    MixMatrix(std::uint32_t channels, const std::vector<std::uint64_t> &group_start, std::uint32_t tile_channels = 0,
+              std::uint32_t max_frames = DSPFX_BUF_SIZE, bool normalise = true, int device = 0) {
+        const dspfx_mixmatrix_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels,
+                                     (std::uint32_t)(group_start.empty() ? 0 : group_start.size() - 1), normalise ? 1u : 0u, group_start.data()};
+        const int rc = dspfx_mixmatrix_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_mixmatrix_last_error(nullptr) ? dspfx_mixmatrix_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~MixMatrix() { dspfx_mixmatrix_destroy(p_); }
+    MixMatrix(const MixMatrix &) = delete;
+    MixMatrix &operator=(const MixMatrix &) = delete;
+    // device block of n_frames -> device block in the same layout; out may not overlap block (no in-place form); asynchronous on `stream`
+    void run(const float *block, std::uint32_t n_frames, float *out, void *stream = nullptr) { chk(dspfx_mixmatrix_run(p_, block, n_frames, out, stream)); }
+    // what listeners [first_channel, first_channel + count) of ONE room hear: host_values[count][row_len], row_len = the room's members.
+    // Any thread; never waits; applies, whole, to the runs submitted after it.
+    void set_rows(const float *host_values, std::uint32_t row_len, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_mixmatrix_set_rows(p_, host_values, row_len, first_channel, count));
+    }
+    // how loud sources [first_channel, first_channel + count) are for each listener of their room: host_values[count][row_len]
+    void set_cols(const float *host_values, std::uint32_t row_len, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_mixmatrix_set_cols(p_, host_values, row_len, first_channel, count));
+    }
+    // room `room` (-1: every room) back to DSPFX_MIXMATRIX_MIX_MINUS or DSPFX_MIXMATRIX_ZERO
+    void fill(std::int64_t room = -1, std::uint32_t preset = DSPFX_MIXMATRIX_MIX_MINUS) { chk(dspfx_mixmatrix_fill(p_, room, preset)); }
+    // the fresh state: mix-minus in every room
+    void reset() { chk(dspfx_mixmatrix_reset(p_)); }
+    dspfx_mixmatrix *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_mixmatrix_last_error(p_) ? dspfx_mixmatrix_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_mixmatrix *p_ = nullptr;
+};
+
+// Per room of a table: its members, the edge of its padded matrix and the element offset of that matrix, and the bytes of all of
+// them (dspfx_mixmatrix_plan: a pure host function, no GPU; throws with the reason for a table MixMatrix would refuse).
+struct MixMatrixPlan {
+    std::vector<std::uint32_t> count, edge;
+    std::vector<std::uint64_t> offset;
+    std::uint64_t total_bytes = 0;
+};
+inline MixMatrixPlan mixmatrix_plan(std::uint64_t channels, const std::vector<std::uint64_t> &group_start, std::uint32_t tile_channels = 0) {
+    const std::uint32_t G = (std::uint32_t)(group_start.empty() ? 0 : group_start.size() - 1);
+    MixMatrixPlan r;
+    r.count.resize(G);
+    r.edge.resize(G);
+    r.offset.resize(G);
+    const int rc = dspfx_mixmatrix_plan(group_start.data(), G, channels, tile_channels, r.count.data(), r.edge.data(), r.offset.data(), &r.total_bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
+    return r;
+}
+
 // One long impulse response over N channels by partitioned FFT (dspfx_convolve_*): the FIR node's arithmetic for responses too
 // long for its tap table, e.g. a convolution reverb on the G buses of a MixGroups.  `taps_reversed` as dspfx_set_taps takes them.
 class Convolver {

@@ -1,0 +1,87 @@
+"""Mix-matrix bank rate (dspfx_mixmatrix_*) beside MixGroups.returns on the same buffers.  Setup: B = 128, tiled W = 256, one input
+block of uniform noise, one output block, uniform rooms of --room members, fresh (mix-minus) matrices plus a few stored rows.  At each
+--channels and each --room:
+  matrix   MixMatrix.run
+  returns  MixGroups.returns with the same table (what a fresh matrix computes, in O(n) per room instead of O(n^2))
+  copy     a flat torch copy of the block's bytes
+flop = 2 * channels * room * frames; the bank's own bytes = the block in, the block out and every matrix once (edges padded to 32).
+Device events around every call, --reps runs after 5 warm-ups, the median.  The fractions are of the 157.3 TFLOP/s f32 peak and of the
+8 TB/s HBM peak.  One JSON line per case, then a table.
+
+  python tools/mixmatrix_rate.py [--channels 65536,262144,1048576] [--room 32,256,1024] [--reps 20]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+pkg = load_package()
+
+B, W = 128, 256
+PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
+
+
+def timed(torch, fn, reps):
+    for _ in range(5):
+        fn()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+    torch.cuda.synchronize()
+    ev[0].record()
+    for i in range(reps):
+        fn()
+        ev[i + 1].record()
+    torch.cuda.synchronize()
+    return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(reps)]))
+
+
+def measure(torch, n, room, reps):
+    dev = torch.device("cuda:0")
+    torch.manual_seed(91)
+    x = torch.rand(B * n, dtype=torch.float32, device=dev) * 2.0 - 1.0
+    y = torch.empty_like(x)
+    _, _, _, table_bytes = pkg.mixmatrix_plan(n, group_size=room, tile_channels=W)
+    mix = pkg.MixMatrix(n, group_size=room, tile_channels=W, max_frames=B)
+    rooms = pkg.MixGroups(n, group_size=room, tile_channels=W, max_frames=B)
+    rows = np.random.default_rng(92).uniform(0.0, 10.0, (min(3, room), room)).astype(np.float32)
+    mix.set_rows(rows, 0)
+    mix.set_rows(rows, n - room)
+    ms = timed(torch, lambda: mix.run(x, B, out=y), reps)
+    ret = timed(torch, lambda: rooms.returns(x, B, out=y), reps)
+    copy = timed(torch, lambda: y.copy_(x), reps)
+    mix.close()
+    rooms.close()
+    flop, own = 2.0 * n * room * B, 2 * B * n * 4 + table_bytes
+    r = {"channels": n, "room": room, "ms": ms, "tflops": flop / (ms * 1e-3) / 1e12, "fraction_of_flop_peak": flop / (ms * 1e-3) / PEAK_FLOPS,
+         "bytes": own, "gbs": own / (ms * 1e-3) / 1e9, "fraction_of_hbm_peak": own / (ms * 1e-3) / PEAK_BYTES, "returns_ms": ret,
+         "x_returns": ms / ret, "copy_ms": copy}
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--channels", default="65536,262144,1048576")
+    ap.add_argument("--room", default="32,256,1024")
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    import torch
+    rows = []
+    for n in (int(s) for s in a.channels.split(",")):
+        for room in (int(s) for s in a.room.split(",")):
+            rows.append(measure(torch, n, room, a.reps))
+            torch.cuda.empty_cache()
+    print(f"\ntimes in ms, median of {a.reps}; TFLOP/s of 157.3; GB/s on the bank's own bytes of 8 TB/s")
+    print(f"{'channels':>9} {'room':>5} {'matrix':>8} {'TFLOP/s':>8} {'of peak':>8} {'GB/s':>8} {'of peak':>8} {'returns':>8} {'x returns':>9} {'copy':>8}")
+    for r in rows:
+        print(f"{r['channels']:>9} {r['room']:>5} {r['ms']:>8.4f} {r['tflops']:>8.1f} {r['fraction_of_flop_peak']:>8.3f} {r['gbs']:>8.0f} "
+              f"{r['fraction_of_hbm_peak']:>8.3f} {r['returns_ms']:>8.4f} {r['x_returns']:>9.2f} {r['copy_ms']:>8.4f}")
+
+
+if __name__ == "__main__":
+    main()
