@@ -18,6 +18,10 @@
 //             level of the same over the results.  The last level divides (IEEE) and writes the bus.
 // Which additions make a group's sum follows from the group's own first channel and length (and the layout) alone: no atomics,
 // nothing depends on the order waves run in or on the other groups.  dspfx_mixgroups_plan gives the depth of that tree.
+// The sign of a zero bus: the reference's collect_and_average starts from +0.0 and adds pipe by pipe, so terms that are all -0.0
+// (silence through a negative fader) give +0.0, where a tree gives (-0) + (-0) = -0.  Wherever a finished sum becomes a bus -- the
+// last reduce level, and a group complete inside its span -- it is written as +0.0 + sum, before the division: that is the sum
+// itself for every value but -0.0.  The raw sums that returns read go through the same two places.
 //
 // Per-channel returns (dspfx_mixgroups_returns): returns[f][c] = fl32(fl32(S[f][g] - t[f][c]) / link_divisor(n_g - 1)), every
 // channel hears its room minus itself.  The two kernels above, unchanged, are pointed at divisor tables of 1.0 and at the bank's
@@ -183,7 +187,7 @@ __device__ __forceinline__ void cut_span(const P1Args &a, uint32_t k, uint32_t f
                 if (lane >= head[r] + d) v += u;
             }
             if (joins[r] && head[r] == 0) v = carry + v;
-            if (direct[r]) a.bus[(size_t)f * a.G + gi[r]] = __fdiv_rn(v, dv[r]);
+            if (direct[r]) a.bus[(size_t)f * a.G + gi[r]] = __fdiv_rn(__fadd_rn(0.0f, v), dv[r]);   // (+0.0 + sum: see the head)
             if (r == l_row) lval = __shfl(v, l_lane, 64);
             carry = goes_on[r] ? __shfl(v, 63, 64) : 0.0f;
         }
@@ -230,7 +234,7 @@ __global__ __launch_bounds__(RW * 64) void mixgroups_reduce(const Task *__restri
     if (t.count == 2) tot = tot + s[1][lane];
     else if (t.count == 3) tot = (tot + s[1][lane]) + s[2][lane];
     else if (t.count > 3) tot = (tot + s[1][lane]) + (s[2][lane] + s[3][lane]);
-    if (t.final) bus[(size_t)f * G + t.dst] = __fdiv_rn(tot, t.div);
+    if (t.final) bus[(size_t)f * G + t.dst] = __fdiv_rn(__fadd_rn(0.0f, tot), t.div);    // (+0.0 + sum: see the head)
     else next[(size_t)t.dst * FS + f] = tot;
 }
 

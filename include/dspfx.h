@@ -849,7 +849,11 @@ int dspfx_mixgroups_destroy(dspfx_mixgroups *m);
 const char *dspfx_mixgroups_last_error(const dspfx_mixgroups *m);
 /* block: device, n_frames frames in the desc's layout (1 <= n_frames <= max_frames); buses: device, [n_frames][G] f32.
  * Asynchronous on `stream`; a run on another stream than the one before first waits (on the device) for that one, since the
- * partial sums are the bank's. */
+ * partial sums are the bank's.
+ * The sign of a zero bus is the reference's: collect_and_average (node.rs:162-194) starts from +0.0 and adds pipe by pipe, so a
+ * group whose terms are all -0.0 (samples of -0.0, or silence through a negative fader: +0.0 * -1.0) gives +0.0, not the -0.0 a
+ * tree of additions gives.  The bank writes +0.0 + sum wherever a finished sum becomes a bus, ahead of the division; that changes
+ * no other value.  The raw sums that dspfx_mixgroups_returns subtracts from are the same, so such a group's returns are +0.0 too. */
 int dspfx_mixgroups_run(dspfx_mixgroups *m, const float *block, uint32_t n_frames, float *buses, void *stream);
 /* Per-channel returns: every participant of a room has an Output node of their own, wired to the OTHER n_g - 1 channels of
  * the room, so that nobody hears themself.  With t[f][c] = fl32(x[f][c] * gain[c]) (x[f][c] itself for a channel without a

@@ -164,3 +164,16 @@ def same_bits_or_nan(got, base, table=None, what=""):
     cls = table.get(idx[-1], "noise") if table is not None else None
     raise AssertionError("%s: bits differ at %r (%s): 0x%08x against 0x%08x; %d elements differ" % (
         what, idx, cls, int(got.view(U)[idx]), int(base.view(U)[idx]), int((~ok).sum())))
+
+
+def worst_ulp_by_class(got, ref, table):
+    """{class name: the largest ulp_diff over the elements where both are finite}, "noise" for the channels outside the table."""
+    got, ref = np.asarray(got, F), np.asarray(ref, F)
+    fin = np.isfinite(got) & np.isfinite(ref)
+    with np.errstate(invalid="ignore"):
+        d = np.where(fin, ulp_diff(got, ref), 0)
+    worst = {}
+    for c in range(ref.shape[1]):
+        name = table.get(c, "noise")
+        worst[name] = max(worst.get(name, 0), int(d[:, c].max()))
+    return worst

@@ -108,3 +108,54 @@ def random_mats(table, seed, zero_fraction=1.0 / 3.0):
         m[rng.uniform(0.0, 1.0, (n, n)) < zero_fraction] = np.float32(0.0)
         out.append(m)
     return out
+
+
+CLASSES = ("finite", "nan", "+inf", "-inf")
+
+
+def classify(x, table, mats, normalise=True):
+    """-> [F][N] array of "nan", "+inf", "-inf" or "finite": what the output of frame f and listener l must be, from the terms
+    x[f][s] * M[l][s] formed in numpy float32 alone.  "nan": some term is NaN (0 * inf is one), or infinite terms of both signs are
+    present; a signed infinity: infinite terms of that sign only; "finite" otherwise -- and for a row without a wired entry, whose
+    output is +0.0 whatever the samples are (the documented rule).  A division by the link divisor (finite, >= 1) changes no class,
+    so `normalise` changes nothing here; it is taken so that the call reads like exact() and eval_f32().
+    This classification is independent of the summation order and of fusing only while no FINITE product or partial sum can
+    overflow: an order that overflows to +inf on the way and meets -inf later gives NaN where another order gives -inf.  So the
+    inputs must satisfy  max|x finite| * max|M finite| * n < 2^120  (asserted), which keeps every finite partial sum eight binades
+    under the f32 maximum; 3.4e38 therefore has no place in a mix-matrix edge block."""
+    x = np.asarray(x, np.float32)
+    out = np.full(x.shape, "finite", dtype="<U6")
+    _, wired = divisors(mats, normalise)
+    for (c0, n), m in zip(rooms(table), mats):
+        m = np.asarray(m, np.float32)
+        xs = x[:, c0:c0 + n]
+        big_x = np.abs(xs[np.isfinite(xs)]).max(initial=0.0)
+        big_m = np.abs(m[np.isfinite(m)]).max(initial=0.0)
+        assert float(big_x) * float(big_m) * n < 2.0 ** 120, (c0, n, big_x, big_m)
+        with np.errstate(all="ignore"):
+            prod = (xs[:, None, :] * m[None, :, :]).astype(np.float32)            # [F][l][s]
+        nan = np.isnan(prod).any(axis=2)
+        pos, neg = np.isposinf(prod).any(axis=2), np.isneginf(prod).any(axis=2)
+        room = np.full(nan.shape, "finite", dtype="<U6")
+        room[pos & ~neg] = "+inf"
+        room[neg & ~pos] = "-inf"
+        room[nan | (pos & neg)] = "nan"
+        out[:, c0:c0 + n] = room
+    out[:, ~wired] = "finite"
+    return out
+
+
+def scaled_int_product(k, table, mats, e):
+    """Integer samples k [F][N] standing for x = k * 2^e, integer-valued matrices: -> the f32 of (int64 product) * 2^e.  Asserted:
+    sum_s |M[l][s] k[f][s]| < 2^24 for every output, so every partial sum of every order is an integer below 2^24 times 2^e --
+    exactly representable in f32 down to e = -149, where inputs and outputs are subnormal or barely normal -- and the result is
+    the only value a correct kernel of any summation order can give."""
+    ki = np.asarray(k).astype(np.int64)
+    assert (ki == np.asarray(k)).all() and e >= -149
+    out = np.zeros(ki.shape, np.int64)
+    for (c0, n), m in zip(rooms(table), mats):
+        mi = np.asarray(m).astype(np.int64)
+        assert (mi == np.asarray(m)).all() and mi.shape == (n, n)
+        out[:, c0:c0 + n] = ki[:, c0:c0 + n] @ mi.T
+        assert (np.abs(ki[:, c0:c0 + n]) @ np.abs(mi).T).max() < 1 << 24
+    return np.ldexp(out.astype(np.float64), e).astype(np.float32)

@@ -81,7 +81,7 @@ def run_blocks(dspfx, torch, bank, x, n, tile, nf=NF, inplace=False):
 
 # ---- 1. parity ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("flags", [0, 3])
-@pytest.mark.parametrize("K", [1, 3, 8])
+@pytest.mark.parametrize("K", [1, 2, 3, 8])
 @pytest.mark.parametrize("n,tile", SHAPES)
 def test_parity_with_the_oracle(dspfx, torch_cuda, n, tile, K, flags):
     su = Setup(n, K, 1000 + 10 * K + flags)
@@ -243,7 +243,7 @@ def test_a_nan_channel_changes_no_other_channel(dspfx, torch_cuda, n, tile):
 
 # ---- 5. against what it generalises ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("flags", [0, 3])
-@pytest.mark.parametrize("K", [1, 3, 8])
+@pytest.mark.parametrize("K", [1, 2, 3, 8])
 @pytest.mark.parametrize("n,tile", [(256, 64), (70, 0)])
 def test_uniform_strips_equal_the_engine(dspfx, torch_cuda, n, tile, K, flags):
     torch = torch_cuda
