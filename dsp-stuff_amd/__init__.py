@@ -880,25 +880,55 @@ class Comm:
             pass
 
 
-class PitchBank:
+def _raise(L, prefix, rc, h=None):
+    """rc != 0 -> DspfxError: the reason dspfx_<prefix>_last_error(h) keeps (prefix None: there is none), else the status's name."""
+    if rc != 0:
+        why = getattr(L, f"dspfx_{prefix}_last_error")(h).decode() if prefix else ""
+        raise DspfxError(rc, why or L.dspfx_strerror(rc).decode())
+
+
+class _Bank:
+    """What the bank classes share: the handle `h` of dspfx_<_C>_create, its status checks and its end."""
+
+    _C = ""             # the bank's name in the C ABI
+    _WHY = False        # it has a dspfx_<_C>_last_error
+
+    def _create(self, desc):
+        self.h = C.c_void_p()
+        rc = getattr(self.L, f"dspfx_{self._C}_create")(C.byref(desc), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            _raise(self.L, self._C if self._WHY else None, rc)
+
+    def _chk(self, rc):
+        _raise(self.L, self._C if self._WHY else None, rc, self.h)
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            getattr(self.L, f"dspfx_{self._C}_destroy")(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PitchBank(_Bank):
     """The Pitch Detector node (nodes/pitch.rs) for N channels (include/dspfx.h, dspfx_pitch_*): blocks pushed in the layout
     of `tile_channels` (as Engine's), a McLeod pitch and clarity per channel for every 1024 frames, held until the next
     window that gives one.  Device tensors in, device tensors out; asynchronous on `stream` like Engine.process."""
+
+    _C = "pitch"
 
     def __init__(self, channels: int, device: int = 0, tile_channels: int = 0, power_thresh: float = 0.5,
                  clarity_thresh: float = 0.5, pick_thresh: float = 0.5):
         self.L = lib()
         self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
-        self.h = C.c_void_p()
         d = _PitchDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, power_thresh, clarity_thresh, pick_thresh)
-        rc = self.L.dspfx_pitch_create(C.byref(d), C.byref(self.h))
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+        self._create(d)
 
     def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
         """Append a device block [n_frames][N] (or the tiled form); runs the windows that fall due."""
@@ -944,17 +974,6 @@ class PitchBank:
     def windows(self) -> int:
         return int(self.L.dspfx_pitch_windows(self.h))
 
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_pitch_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def resample_plan(target_hz: int, value: float, idx: int, n_out: int):
@@ -970,8 +989,7 @@ def resample_plan(target_hz: int, value: float, idx: int, n_out: int):
     rc = L.dspfx_resample_plan(int(target_hz), C.byref(v), C.byref(i), int(n_out), adv.ctypes.data_as(C.POINTER(C.c_uint32)),
                                dep.ctypes.data_as(C.POINTER(C.c_uint32)), coeff.ctypes.data_as(C.POINTER(C.c_double)),
                                C.byref(il), C.byref(pl))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    _raise(L, None, rc)
     return {"advance": adv, "depth": dep, "coeff": coeff, "value": v.value, "idx": i.value, "input_len": il.value,
             "pulled": pl.value}
 
@@ -979,12 +997,14 @@ def resample_plan(target_hz: int, value: float, idx: int, n_out: int):
 _PCM_TORCH = {SAMPLE_F32: "float32", SAMPLE_I16: "int16", SAMPLE_U16: "int16", SAMPLE_I32: "int32"}
 
 
-class Resampler:
+class Resampler(_Bank):
     """The output resampler bank (include/dspfx.h, dspfx_resample_*): the reference's output callback (devices.rs:394-498) for
     N channels whose device runs at `target_hz`.  Blocks of engine output (48 kHz, the layout of `tile_channels`, as Engine's)
     are pushed into a FIFO of `slots` slots of `block_frames` frames; pull(n_out) is one callback: n_out device frames of
     every channel through dasp's Converter + 16-frame Sinc, in `out_format` with `out_channels` samples per frame.
     Asynchronous on `stream` like Engine.process; the counters are host values."""
+
+    _C = "resample"
 
     def __init__(self, channels: int, target_hz: int, device: int = 0, tile_channels: int = 0, block_frames: int = BUF_SIZE,
                  slots: int = 4, out_format: int = SAMPLE_F32, out_channels: int = 1):
@@ -992,17 +1012,9 @@ class Resampler:
         self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
         self.block_frames, self.slots, self.target_hz = int(block_frames), int(slots), int(target_hz)
         self.out_format, self.out_channels = int(out_format), int(out_channels)
-        self.h = C.c_void_p()
         d = _ResampleDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, self.block_frames, self.slots,
                           self.target_hz, self.out_format, self.out_channels)
-        rc = self.L.dspfx_resample_create(C.byref(d), C.byref(self.h))
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+        self._create(d)
 
     def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
         """Append a device block [n_frames][N] (or the tiled form for n_frames).  slot_tensor() itself: nothing is copied.
@@ -1055,17 +1067,6 @@ class Resampler:
     def reset(self):
         self._chk(self.L.dspfx_resample_reset(self.h))
 
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_resample_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def graph_source(nodes: Sequence[NodeSpec], links: Sequence[Tuple[int, int, int]]) -> str:
@@ -1074,8 +1075,7 @@ def graph_source(nodes: Sequence[NodeSpec], links: Sequence[Tuple[int, int, int]
     arr, larr = Engine._graph_arrays(nodes, links)
     buf = C.create_string_buffer(1 << 18)
     rc = L.dspfx_graph_source(arr, len(nodes), larr, len(links), buf, len(buf))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    _raise(L, None, rc)
     return buf.value.decode()
 
 
@@ -1088,8 +1088,7 @@ def spectrum_plan(fft_size: int):
     win = np.zeros(n if ok else 1, np.float32)
     hz = np.zeros(max(n // 2, 1) if ok else 1, np.float32)
     rc = L.dspfx_spectrum_plan(n & 0xFFFFFFFF, win.ctypes.data_as(C.POINTER(C.c_float)), hz.ctypes.data_as(C.POINTER(C.c_float)))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    _raise(L, None, rc)
     return win, hz
 
 
@@ -1104,19 +1103,20 @@ def spectrum_bins(fft_size: int, lower_hz: float, upper_hz: float):
     return k_lo, k_hi, hz[k_lo:k_hi]
 
 
-class SpectrumBank:
+class SpectrumBank(_Bank):
     """The Spectrogram node (nodes/spectrogram.rs) for N channels (include/dspfx.h, dspfx_spectrum_*): blocks pushed in the
     layout of `tile_channels` (as Engine's); every `fft_size` frames one column vol[k] = |FFT(window * x)[k]| * gain[k],
     k in [0, fft_size/2), per channel, the newest `columns` of them kept on the device.  `window` (float32[fft_size]) and
     `gain` (float32[fft_size/2]) are host tables: None = the Hann window of spectrum_plan / 1.0.  audioviz's volume
     normalisation is not restated: a caller that wants it passes it as `gain`.  Asynchronous on `stream` like Engine.process."""
 
+    _C = "spectrum"
+
     def __init__(self, channels: int, fft_size: int = 512, columns: int = 1, tile_channels: int = 0, window=None, gain=None,
                  device: int = 0):
         self.L = lib()
         self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
         self.fft_size, self.columns = int(fft_size), int(columns)
-        self.h = C.c_void_p()
         fp = C.POINTER(C.c_float)
         tables = []
         for name, tab, length in (("window", window, self.fft_size), ("gain", gain, self.fft_size // 2)):
@@ -1127,14 +1127,7 @@ class SpectrumBank:
             tables.append(tab)
         d = _SpectrumDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, self.fft_size & 0xFFFFFFFF,
                           self.columns & 0xFFFFFFFF, *(fp() if tab is None else tab.ctypes.data_as(fp) for tab in tables))
-        rc = self.L.dspfx_spectrum_create(C.byref(d), C.byref(self.h))         # the tables are copied before this returns
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+        self._create(d)  # the tables are copied before this returns
 
     def _view(self, addr, elems):
         import torch
@@ -1180,17 +1173,6 @@ class SpectrumBank:
     def windows(self) -> int:
         return int(self.L.dspfx_spectrum_windows(self.h))
 
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_spectrum_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _group_table(channels: int, group_start=None, group_size=None) -> np.ndarray:
@@ -1214,8 +1196,7 @@ def mixgroups_plan(channels: int, group_start=None, group_size=None, tile_channe
     depth = np.zeros(len(t) - 1, np.uint32)
     rc = L.dspfx_mixgroups_plan(t.ctypes.data_as(C.POINTER(C.c_uint64)), len(t) - 1, int(channels), int(tile_channels),
                                 depth.ctypes.data_as(C.POINTER(C.c_uint32)))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_mixgroups_last_error(None).decode() or L.dspfx_strerror(rc).decode())
+    _raise(L, "mixgroups", rc)
     return depth
 
 
@@ -1240,12 +1221,11 @@ def mixgroups_room_plan(room_of, groups: int, tile_channels: int = 0):
     u64 = C.POINTER(C.c_uint64)
     rc = L.dspfx_mixgroups_room_plan(v.ctypes.data_as(C.POINTER(C.c_uint32)), len(v), G & 0xFFFFFFFF, int(tile_channels),
                                      count.ctypes.data_as(u64), depth.ctypes.data_as(C.POINTER(C.c_uint32)), pieces.ctypes.data_as(u64))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_mixgroups_last_error(None).decode() or L.dspfx_strerror(rc).decode())
+    _raise(L, "mixgroups", rc)
     return count, depth, pieces
 
 
-class MixGroups:
+class MixGroups(_Bank):
     """One Output bus per contiguous channel range, with a per-channel fader (include/dspfx.h, dspfx_mixgroups_*):
     buses[f][g] = (sum over group g of fl32(x[f][c] * gain[c])) / link_divisor(n_g) for a device block in the layout of
     `tile_channels` (as Engine's).  group_start: G + 1 channel indices, nondecreasing from 0 to N; or group_size for uniform
@@ -1254,6 +1234,9 @@ class MixGroups:
     Every channel starts in the room its range puts it in; `assign` reseats channels live among the G rooms (or in none,
     NO_ROOM): run and returns then read "group g" as the channels whose room is g.  A bank that never calls it runs as before."""
 
+    _C = "mixgroups"
+    _WHY = True
+
     def __init__(self, channels: int, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE,
                  normalise: bool = True, device: int = 0):
         self.L = lib()
@@ -1261,17 +1244,9 @@ class MixGroups:
         self.max_frames, self.normalise = int(max_frames), bool(normalise)
         self.group_start = _group_table(self.channels, group_start, group_size)
         self.groups = len(self.group_start) - 1
-        self.h = C.c_void_p()
         d = _MixGroupsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
                            self.groups, int(self.normalise), self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
-        rc = self.L.dspfx_mixgroups_create(C.byref(d), C.byref(self.h))        # the table is copied before this returns
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_mixgroups_last_error(None).decode() or self.L.dspfx_strerror(rc).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_mixgroups_last_error(self.h).decode() or self.L.dspfx_strerror(rc).decode())
+        self._create(d)  # the table is copied before this returns
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """The buses of one device block -> `out` [n_frames, G] float32 on the device (made when not given)."""
@@ -1339,17 +1314,6 @@ class MixGroups:
             return mixgroups_room_plan(self.room_of(), self.groups, self.tile_channels)[1]
         return mixgroups_plan(self.channels, group_start=self.group_start, tile_channels=self.tile_channels)
 
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_mixgroups_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _taps_reversed(impulse_response) -> np.ndarray:
@@ -1368,16 +1332,14 @@ def convolve_plan(impulse_response):
     dp = C.POINTER(C.c_double)
     parts = C.c_uint32()
     rc = L.dspfx_convolve_plan(t.ctypes.data_as(dp), len(t), C.byref(parts), None)
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    _raise(L, None, rc)
     table = np.zeros((128, int(parts.value), 2), np.float32)
     rc = L.dspfx_convolve_plan(t.ctypes.data_as(dp), len(t), C.byref(parts), table.ctypes.data_as(C.POINTER(C.c_float)))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    _raise(L, None, rc)
     return int(parts.value), table
 
 
-class Convolver:
+class Convolver(_Bank):
     """One long impulse response over N channels by partitioned FFT (include/dspfx.h, dspfx_convolve_*): per 128-frame block
     y[n] = fl32(sum_j h[j] x[n - j]) * divisor, divisor 1 (FIR_BALANCED) or 1 / T (FIR_AVERAGE), the FIR node's arithmetic for
     responses too long for its tap table: a convolution reverb on the G buses of a MixGroups.  `impulse_response` is h in
@@ -1388,19 +1350,17 @@ class Convolver:
     (the one given here is 0, and every channel starts on it), `assign` points channels at an id and keeps their history.
     Each channel gets the bits a Convolver of its response alone would give it."""
 
+    _C = "convolve"
+
     def __init__(self, channels: int, impulse_response, mode: int = FIR_BALANCED, max_taps: int = 0, tile_channels: int = 0,
                  device: int = 0):
         self.L = lib()
         self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
         self.max_taps = int(max_taps)
-        self.h = C.c_void_p()
         t = _taps_reversed(impulse_response)
         d = _ConvolveDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.tile_channels, len(t),
                           self.max_taps & 0xFFFFFFFF, int(mode), t.ctypes.data_as(C.POINTER(C.c_double)))
-        rc = self.L.dspfx_convolve_create(C.byref(d), C.byref(self.h))         # the taps are copied before this returns
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
+        self._create(d)  # the taps are copied before this returns
         self.n_taps, self.mode = len(t), int(mode)
         self._responses = [(self.n_taps, self.mode)]                           # (taps, mode) of every response, by id
         self._ids = np.zeros(self.channels, np.uint16)
@@ -1411,10 +1371,6 @@ class Convolver:
         resampling to 48 kHz)."""
         from . import ir
         return cls(channels, ir.load_impulse_response(path, resample=resample), **kw)
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_strerror(rc).decode())
 
     @property
     def partitions(self) -> int:
@@ -1494,17 +1450,6 @@ class Convolver:
         """Back to silence (ahead of the next run)."""
         self._chk(self.L.dspfx_convolve_reset(self.h))
 
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_convolve_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def strips_coeffs(raw6) -> np.ndarray:
@@ -1516,12 +1461,11 @@ def strips_coeffs(raw6) -> np.ndarray:
         raise DspfxError(-1, "a BiQuad band is six raw sliders: a0, a1, a2, b0, b1, b2")
     out = np.zeros(5, np.float32)
     rc = L.dspfx_strips_coeffs(r.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_strerror(rc).decode())
+    _raise(L, None, rc)
     return out
 
 
-class ChannelStrips:
+class ChannelStrips(_Bank):
     """Per-channel Gain and BiQuad sliders (include/dspfx.h, dspfx_strips_*): the strip of channel c is a chain of up to
     1 + `bands` optional nodes in a fixed order -- a Gain node, then BiQuad bands 0 .. bands-1 -- each with the channel's own
     slider values, over a device block in the layout of `tile_channels` (as Engine's).  A node exists for a channel from the
@@ -1529,22 +1473,17 @@ class ChannelStrips:
     collect_and_average hops into a channel's first present node (LINK_INPUT) and between its present nodes (LINK_INTERNAL).
     Between eng.process and MixGroups.run / returns, or ahead of the chain.  Asynchronous on `stream`."""
 
+    _C = "strips"
+    _WHY = True
+
     def __init__(self, channels: int, bands: int = 1, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
                  device: int = 0):
         self.L = lib()
         self.channels, self.bands, self.tile_channels = int(channels), int(bands), int(tile_channels)
         self.max_frames, self.link_flags, self.device = int(max_frames), int(link_flags), int(device)
-        self.h = C.c_void_p()
         d = _StripsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
                         self.bands & 0xFFFFFFFF, self.link_flags & 0xFFFFFFFF)
-        rc = self.L.dspfx_strips_create(C.byref(d), C.byref(self.h))
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_strips_last_error(None).decode() or self.L.dspfx_strerror(rc).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_strips_last_error(self.h).decode() or self.L.dspfx_strerror(rc).decode())
+        self._create(d)
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's strip -> `out`, a device block in the same layout (made when not given;
@@ -1599,17 +1538,6 @@ class ChannelStrips:
         """Zero all state (on the stream last used); the sliders and the nodes stay."""
         self._chk(self.L.dspfx_strips_reset(self.h))
 
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_strips_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def mixmatrix_plan(channels: int, group_start=None, group_size=None, tile_channels: int = 0):
@@ -1625,12 +1553,11 @@ def mixmatrix_plan(channels: int, group_start=None, group_size=None, tile_channe
     u32 = C.POINTER(C.c_uint32)
     rc = L.dspfx_mixmatrix_plan(t.ctypes.data_as(C.POINTER(C.c_uint64)), G, int(channels), int(tile_channels), count.ctypes.data_as(u32),
                                 edge.ctypes.data_as(u32), offset.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
-    if rc != 0:
-        raise DspfxError(rc, L.dspfx_mixmatrix_last_error(None).decode() or L.dspfx_strerror(rc).decode())
+    _raise(L, "mixmatrix", rc)
     return count, edge, offset, int(total.value)
 
 
-class MixMatrix:
+class MixMatrix(_Bank):
     """Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an
     n_r x n_r float32 matrix M[l][s] (listener, source), and out[f][c0 + l] = (sum_s M[l][s] * x[f][c0 + s]) / link_divisor(w),
     w = the listener's non-zero entries (a row of zeros gives +0.0; normalise=False writes the raw sum), for a device block in the
@@ -1639,6 +1566,9 @@ class MixMatrix:
     without faders.  Between ChannelStrips.run and the listeners' Resampler, as an alternative to returns.  The rooms are fixed: a
     host that reseats channels with MixGroups.assign makes a new MixMatrix for the new table.  Asynchronous on `stream`."""
 
+    _C = "mixmatrix"
+    _WHY = True
+
     def __init__(self, channels: int, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE,
                  normalise: bool = True, device: int = 0, abi_version: int = ABI_VERSION):
         self.L = lib()
@@ -1646,18 +1576,10 @@ class MixMatrix:
         self.max_frames, self.normalise = int(max_frames), bool(normalise)
         self.group_start = _group_table(self.channels, group_start, group_size)
         self.groups = len(self.group_start) - 1
-        self.h = C.c_void_p()
         d = _MixMatrixDesc(int(abi_version) & 0xFFFFFFFF, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF,
                            self.tile_channels & 0xFFFFFFFF, self.groups, int(self.normalise),
                            self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
-        rc = self.L.dspfx_mixmatrix_create(C.byref(d), C.byref(self.h))        # the table is copied before this returns
-        if rc != 0:
-            self.h = C.c_void_p()
-            raise DspfxError(rc, self.L.dspfx_mixmatrix_last_error(None).decode() or self.L.dspfx_strerror(rc).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise DspfxError(rc, self.L.dspfx_mixmatrix_last_error(self.h).decode() or self.L.dspfx_strerror(rc).decode())
+        self._create(d)  # the table is copied before this returns
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every room's matrix -> `out`, a device block in the same layout (made when not given).
@@ -1696,15 +1618,3 @@ class MixMatrix:
     def reset(self):
         """The fresh state: mix-minus in every room (queued like a store)."""
         self._chk(self.L.dspfx_mixmatrix_reset(self.h))
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.dspfx_mixmatrix_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,12 +1,17 @@
-// bank_common.hip.h -- the stateless helpers the banks share (pitch, resample, spectrum, mixgroups, convolve _kernels.hip):
-// the desc's layout, 4-channel loads and stores in it, the slot copy, and small host helpers.  Host and device, hipcc only.
-// The FFT is in fft_core.hip.h.  A bank's struct, ring and create / destroy / reset are its own.
+// bank_common.hip.h -- what the banks share (pitch, resample, spectrum, convolve, mixgroups, strips, mixmatrix _kernels.hip):
+// the desc's layout, 4-channel loads and stores in it, the slot copy, and small host helpers -- all stateless -- and the scaffold of
+// the three slider banks (mixgroups, strips, mixmatrix): the error holder, the shape / range / table checks of their arguments,
+// open_device and close_bank.  Host and device, hipcc only.  The FFT is in fft_core.hip.h, the slider banks' staged stores in
+// store_queue.hip.h.  A bank's struct, its ring and the rest of create / reset are its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <mutex>
+#include <string>
 
 #include "../../include/dspfx.h"
 
@@ -14,6 +19,12 @@
 #define BANK_HIP(call)                                  \
     do {                                                \
         if ((call) != hipSuccess) return DSPFX_ERR_HIP; \
+    } while (0)
+
+// ... of a bank that keeps the reason (BankError): the function returns p->fail(DSPFX_ERR_HIP, what)
+#define BANK_HIP_WHY(call, what)                                        \
+    do {                                                                \
+        if ((call) != hipSuccess) return p->fail(DSPFX_ERR_HIP, what); \
     } while (0)
 
 namespace {
@@ -108,6 +119,110 @@ hipError_t order(Bank *p, hipStream_t s) {
     p->last = s;
     p->used = true;
     return err;
+}
+
+// ---- the slider banks' scaffold -------------------------------------------------------------------------------------------
+// the reason of a bank's last failed call, for its *_last_error; a bank derives from it
+struct BankError {
+    std::mutex emu;              // err: stores fail on any thread
+    std::string err;
+    int fail(int rc, const char *what) {
+        std::lock_guard<std::mutex> lk(emu);
+        err = what;
+        return rc;
+    }
+};
+
+// n_channels and tile_channels of a desc or a plan; `name` is the bank's, the prefix of every reason
+int check_shape(const char *name, uint64_t N, uint32_t W, std::string &err) {
+    char buf[192];
+    if (N == 0 || N > 0xFFFFFF00ull) {
+        err = std::string(name) + ": n_channels must be 1 .. 2^32 - 256";
+        return DSPFX_ERR_INVALID;
+    }
+    if (W && (!pow2(W) || N % W)) {
+        std::snprintf(buf, sizeof buf, "%s: tile_channels %u is not a power of two that divides n_channels %llu", name, W, (unsigned long long)N);
+        err = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    return DSPFX_OK;
+}
+
+// channels [first, first + count) of a call lie inside the bank's N; end_ok: an empty range at N itself does
+int check_range(const char *name, const char *call, uint64_t first, uint64_t count, uint64_t N, std::string &err, bool end_ok = true) {
+    if (first > N || count > N - first || (!end_ok && first == N)) {
+        char buf[192];
+        std::snprintf(buf, sizeof buf, "%s %s: channels [%llu, %llu + %llu) are not inside the bank's %llu", name, call, (unsigned long long)first,
+                      (unsigned long long)first, (unsigned long long)count, (unsigned long long)N);
+        err = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    return DSPFX_OK;
+}
+
+// a group table gs[G + 1] over N channels: starts at 0, never decreases, ends at N.  max_room = 0: a group may be empty and as long
+// as it likes; otherwise every group is a room of 1 .. max_room members
+int check_table(const char *name, const uint64_t *gs, uint32_t G, uint64_t N, uint32_t W, uint32_t max_room, std::string &err) {
+    char buf[192];
+    if (!gs || G == 0) {
+        err = std::string(name) + ": no group table";
+        return DSPFX_ERR_INVALID;
+    }
+    const int rc = check_shape(name, N, W, err);
+    if (rc != DSPFX_OK) return rc;
+    if (gs[0] != 0) {
+        std::snprintf(buf, sizeof buf, "%s: group_start[0] is %llu, not 0", name, (unsigned long long)gs[0]);
+        err = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+        if (gs[g + 1] < gs[g]) {
+            std::snprintf(buf, sizeof buf, "%s: group_start decreases at entry %u (%llu after %llu)", name, g + 1, (unsigned long long)gs[g + 1],
+                          (unsigned long long)gs[g]);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        const uint64_t n = gs[g + 1] - gs[g];
+        if (max_room && n == 0) {
+            std::snprintf(buf, sizeof buf, "%s: room %u is empty (a room has 1 .. %u members)", name, g, max_room);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        if (max_room && n > max_room) {
+            std::snprintf(buf, sizeof buf, "%s: room %u has %llu members, above DSPFX_MIXMATRIX_MAX_ROOM = %u", name, g, (unsigned long long)n, max_room);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+    }
+    if (gs[G] != N) {
+        std::snprintf(buf, sizeof buf, "%s: group_start[%u] is %llu, not n_channels %llu", name, G, (unsigned long long)gs[G], (unsigned long long)N);
+        err = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    return DSPFX_OK;
+}
+
+// create's device lines: the device exists and is the thread's current one.  err may be null (a bank that keeps no reason)
+int open_device(const char *name, int device, std::string *err) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
+    if (device < 0 || device >= count) {
+        if (err) *err = std::string(name) + ": no such device";
+        return DSPFX_ERR_INVALID;
+    }
+    if (hipSetDevice(device) != hipSuccess) return DSPFX_ERR_HIP;
+    return DSPFX_OK;
+}
+
+// destroy: no run is inside the bank, its work on the device is done, then `release` frees it.  Bank has mu, desc, last, used
+template <class Bank>
+void close_bank(Bank *p, void (*release)(Bank *)) {
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        (void)hipSetDevice(p->desc.device);
+        if (p->used) (void)hipStreamSynchronize(p->last);    // the bank's work is ordered on the last stream it used
+    }
+    release(p);
 }
 
 }  // namespace

@@ -573,10 +573,8 @@ extern "C" int dspfx_convolve_create(const dspfx_convolve_desc *desc, dspfx_conv
     if (rc != DSPFX_OK) return rc;
     const uint32_t max_taps = desc->max_taps ? desc->max_taps : desc->n_taps;
     if (max_taps < desc->n_taps || max_taps > DSPFX_CONVOLVE_MAX_TAPS) return DSPFX_ERR_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-    if (desc->device < 0 || desc->device >= count) return DSPFX_ERR_INVALID;
-    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    const int dev_rc = open_device(nullptr, desc->device, nullptr);
+    if (dev_rc != DSPFX_OK) return dev_rc;
     dspfx_convolve *p = new (std::nothrow) dspfx_convolve;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;

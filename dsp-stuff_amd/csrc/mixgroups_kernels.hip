@@ -32,12 +32,14 @@
 //             when the first returns call is made) and S[f][g] is one wave-uniform load; a cut span looks its channels' groups up
 //             once per wave, between the first group of this span and the first group of the next, and gathers S per frame.
 //             A lane rewrites the elements it read, so returns may be the block itself.
+//
+// Fader stores (dspfx_mixgroups_set_gains) go through the staged-store queue (store_queue.hip.h): staged in page-locked memory, queued,
+// and put on the next run's stream ahead of its kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <mutex>
 #include <new>
 #include <string>
@@ -45,6 +47,7 @@
 
 #include "../../include/dspfx.h"
 #include "bank_common.hip.h"
+#include "store_queue.hip.h"
 #include "chain_kernels.hip.h"
 
 namespace {
@@ -619,41 +622,6 @@ uint32_t depth_of(const GroupPieces &p) {
     return d;
 }
 
-int check_table(const uint64_t *gs, uint32_t G, uint64_t N, uint32_t W, std::string &err) {
-    char buf[160];
-    if (!gs || G == 0) {
-        err = "mixgroups: no group table";
-        return DSPFX_ERR_INVALID;
-    }
-    if (N == 0 || N > 0xFFFFFF00ull) {
-        err = "mixgroups: n_channels must be 1 .. 2^32 - 256";
-        return DSPFX_ERR_INVALID;
-    }
-    if (W && (!pow2(W) || N % W)) {
-        std::snprintf(buf, sizeof buf, "mixgroups: tile_channels %u is not a power of two that divides n_channels %llu", W, (unsigned long long)N);
-        err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    if (gs[0] != 0) {
-        std::snprintf(buf, sizeof buf, "mixgroups: group_start[0] is %llu, not 0", (unsigned long long)gs[0]);
-        err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    for (uint32_t g = 0; g < G; ++g)
-        if (gs[g + 1] < gs[g]) {
-            std::snprintf(buf, sizeof buf, "mixgroups: group_start decreases at entry %u (%llu after %llu)", g + 1,
-                          (unsigned long long)gs[g + 1], (unsigned long long)gs[g]);
-            err = buf;
-            return DSPFX_ERR_INVALID;
-        }
-    if (gs[G] != N) {
-        std::snprintf(buf, sizeof buf, "mixgroups: group_start[%u] is %llu, not n_channels %llu", G, (unsigned long long)gs[G], (unsigned long long)N);
-        err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    return DSPFX_OK;
-}
-
 struct Level {
     std::vector<Task> tasks;
     uint32_t rows = 0;           // rows of partial sums it leaves for the next level
@@ -662,13 +630,12 @@ struct Level {
     float *out = nullptr;
 };
 
-struct Store {
-    float *vals = nullptr;       // page-locked; nullptr: back to 1.0 ("no multiply")
-    size_t cap = 0;
+// a fader store's vals: [count]; none: back to 1.0 ("no multiply")
+struct StoreFields {
     uint64_t first = 0, count = 0;
-    hipEvent_t ev = nullptr;
 };
-
+typedef StoreQueue<StoreFields> Stores;
+typedef Stores::Store Store;
 
 // ---- a seating (mapped mode): pure host ---------------------------------------------------------------------------------
 struct RoomPlan {
@@ -823,14 +790,10 @@ std::vector<Level> build_levels(std::vector<Pending> cur) {
 }
 }  // namespace
 
-struct dspfx_mixgroups {
+struct dspfx_mixgroups : BankError {
     dspfx_mixgroups_desc desc{};
     std::mutex mu;                               // run / destroy
-    std::mutex qmu;                              // the store queue and the free staging buffers
-    std::deque<Store> queue;                     // stores not yet handed to a stream
-    std::vector<Store> spare;                    // staging buffers free for the next store
-    std::vector<Store> flying;                   // copies queued on a stream (mu)
-    std::vector<hipEvent_t> events;              // spare events (mu)
+    Stores stores;                               // the fader stores (store_queue.hip.h)
     std::vector<uint8_t> faded;                  // per channel: a fader value is stored (mu)
     uint64_t n_faded = 0;
     uint32_t nspans = 0, FS = 0;
@@ -853,7 +816,6 @@ struct dspfx_mixgroups {
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
-    std::string err;
 };
 
 namespace {
@@ -868,15 +830,7 @@ void release(dspfx_mixgroups *p) {
         if (l.dtasks_raw) (void)hipFree(l.dtasks_raw);
         if (l.out) (void)hipFree(l.out);
     }
-    for (Store &s : p->queue)
-        if (s.vals) (void)hipHostFree(s.vals);
-    for (Store &s : p->spare)
-        if (s.vals) (void)hipHostFree(s.vals);
-    for (Store &s : p->flying) {
-        if (s.vals) (void)hipHostFree(s.vals);
-        if (s.ev) (void)hipEventDestroy(s.ev);
-    }
-    for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
+    p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
     free_seating(p->seat);
     for (Seating *t : p->retired) free_seating(t);
@@ -884,63 +838,21 @@ void release(dspfx_mixgroups *p) {
     delete p;
 }
 
-int fail(dspfx_mixgroups *p, int rc, const char *what) {
-    p->err = what;
-    return rc;
+// one fader store onto the stream, and into the count of faded channels (mu)
+hipError_t apply_store(dspfx_mixgroups *p, const Store &st, hipStream_t s) {
+    uint8_t *fl = p->faded.data() + st.first;
+    const uint8_t to = st.vals ? 1 : 0;
+    for (uint64_t i = 0; i < st.count; ++i) {
+        p->n_faded += (uint64_t)to - fl[i];
+        fl[i] = to;
+    }
+    if (!st.vals) return hipMemsetD32Async((hipDeviceptr_t)(p->gain + st.first), 0x3F800000, st.count, s);
+    return hipMemcpyAsync(p->gain + st.first, st.vals, st.count * sizeof(float), hipMemcpyHostToDevice, s);
 }
 
-// the stores made so far, in order, onto the stream ahead of the run; staging buffers whose copy is done go back
+// the stores made so far, in order, onto the stream ahead of the run
 hipError_t apply_stores(dspfx_mixgroups *p, hipStream_t s) {
-    std::vector<Store> done;
-    for (size_t i = 0; i < p->flying.size();) {
-        if (hipEventQuery(p->flying[i].ev) == hipSuccess) {
-            p->events.push_back(p->flying[i].ev);
-            p->flying[i].ev = nullptr;
-            done.push_back(p->flying[i]);
-            p->flying[i] = p->flying.back();
-            p->flying.pop_back();
-        } else {
-            (void)hipGetLastError();
-            ++i;
-        }
-    }
-    std::deque<Store> q;
-    {
-        std::lock_guard<std::mutex> lk(p->qmu);
-        for (Store &d : done) p->spare.push_back(d);
-        q.swap(p->queue);
-    }
-    hipError_t err = hipSuccess;
-    while (!q.empty()) {
-        Store st = q.front();
-        q.pop_front();
-        if (err != hipSuccess) {                 // a failed call drops the stores behind it; their buffers are still freed
-            if (st.vals) (void)hipHostFree(st.vals);
-            continue;
-        }
-        uint8_t *fl = p->faded.data() + st.first;
-        const uint8_t to = st.vals ? 1 : 0;
-        for (uint64_t i = 0; i < st.count; ++i) {
-            p->n_faded += (uint64_t)to - fl[i];
-            fl[i] = to;
-        }
-        if (!st.vals) {
-            err = hipMemsetD32Async((hipDeviceptr_t)(p->gain + st.first), 0x3F800000, st.count, s);
-            continue;
-        }
-        err = hipMemcpyAsync(p->gain + st.first, st.vals, st.count * sizeof(float), hipMemcpyHostToDevice, s);
-        if (err == hipSuccess) {
-            if (p->events.empty()) {
-                err = hipEventCreateWithFlags(&st.ev, hipEventDisableTiming);
-            } else {
-                st.ev = p->events.back();
-                p->events.pop_back();
-            }
-        }
-        if (err == hipSuccess) err = hipEventRecord(st.ev, s);
-        p->flying.push_back(st);                 // (with or without an event: destroy frees it after the device is idle)
-    }
-    return err;
+    return p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); });
 }
 
 template <int F>
@@ -958,18 +870,12 @@ hipError_t launch_partials(const P1Args &a, bool gain, bool vec, hipStream_t s) 
 
 }  // namespace
 
-// (not BANK_HIP: this bank keeps the reason of a failure for dspfx_mixgroups_last_error)
-#define MG_HIP(call, what)                                         \
-    do {                                                           \
-        if ((call) != hipSuccess) return fail(p, DSPFX_ERR_HIP, what); \
-    } while (0)
-
 extern "C" const char *dspfx_mixgroups_last_error(const dspfx_mixgroups *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
 extern "C" int dspfx_mixgroups_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
                                     uint32_t *depth_out) {
     g_err.clear();
-    const int rc = check_table(group_start, n_groups, n_channels, tile_channels, g_err);
+    const int rc = check_table("mixgroups", group_start, n_groups, n_channels, tile_channels, 0, g_err);
     if (rc != DSPFX_OK) return rc;
     if (depth_out)
         for (uint32_t g = 0; g < n_groups; ++g) depth_out[g] = depth_of(pieces_of(group_start[g], group_start[g + 1]));
@@ -987,15 +893,10 @@ extern "C" int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mi
         g_err = "mixgroups: abi_version or max_frames";
         return DSPFX_ERR_INVALID;
     }
-    int rc = check_table(desc->group_start, desc->n_groups, desc->n_channels, desc->tile_channels, g_err);
+    int rc = check_table("mixgroups", desc->group_start, desc->n_groups, desc->n_channels, desc->tile_channels, 0, g_err);
     if (rc != DSPFX_OK) return rc;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-    if (desc->device < 0 || desc->device >= count) {
-        g_err = "mixgroups: no such device";
-        return DSPFX_ERR_INVALID;
-    }
-    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    rc = open_device("mixgroups", desc->device, &g_err);
+    if (rc != DSPFX_OK) return rc;
     dspfx_mixgroups *p = new (std::nothrow) dspfx_mixgroups;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -1069,46 +970,27 @@ extern "C" int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mi
 
 extern "C" int dspfx_mixgroups_destroy(dspfx_mixgroups *p) {
     if (!p) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        (void)hipSetDevice(p->desc.device);
-        if (p->used) (void)hipStreamSynchronize(p->last);    // the bank's work is ordered on the last stream it used
-    }
-    release(p);
+    close_bank(p, release);
     return DSPFX_OK;
 }
 
 extern "C" int dspfx_mixgroups_set_gains(dspfx_mixgroups *p, const float *host_values, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
-    if (first_channel > p->desc.n_channels || count > p->desc.n_channels - first_channel) return DSPFX_ERR_INVALID;
+    std::string why;
+    if (check_range("mixgroups", "set_gains", first_channel, count, p->desc.n_channels, why) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, why.c_str());
     if (count == 0) return DSPFX_OK;
     Store st;
     st.first = first_channel;
     st.count = count;
     if (host_values) {
-        {
-            std::lock_guard<std::mutex> lk(p->qmu);
-            for (size_t i = 0; i < p->spare.size(); ++i)
-                if (p->spare[i].cap >= count) {
-                    st.vals = p->spare[i].vals;
-                    st.cap = p->spare[i].cap;
-                    p->spare[i] = p->spare.back();
-                    p->spare.pop_back();
-                    break;
-                }
-        }
-        if (!st.vals) {
-            if (hipSetDevice(p->desc.device) != hipSuccess) return DSPFX_ERR_HIP;
-            if (hipHostMalloc((void **)&st.vals, count * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                return DSPFX_ERR_OOM;
-            }
-            st.cap = count;
+        if (!p->stores.staging(p->desc.device, count, st)) {
+            const bool dev = hipSetDevice(p->desc.device) == hipSuccess;     // which of staging's two calls it was
+            return dev ? p->fail(DSPFX_ERR_OOM, "mixgroups set_gains: no page-locked memory for the staged values")
+                       : p->fail(DSPFX_ERR_HIP, "hipSetDevice");
         }
         std::memcpy(st.vals, host_values, count * sizeof(float));
     }
-    std::lock_guard<std::mutex> lk(p->qmu);
-    p->queue.push_back(st);
+    p->stores.push(st);
     return DSPFX_OK;
 }
 
@@ -1139,12 +1021,12 @@ int mapped_sums(dspfx_mixgroups *p, const Seating &t, const float *block, uint32
         if (vec) mixrooms_partials<false, true><<<blocks, P1_WG, 0, s>>>(a);
         else mixrooms_partials<false, false><<<blocks, P1_WG, 0, s>>>(a);
     }
-    if (hipGetLastError() != hipSuccess) return fail(p, DSPFX_ERR_HIP, "mixrooms_partials");
+    if (hipGetLastError() != hipSuccess) return p->fail(DSPFX_ERR_HIP, "mixrooms_partials");
     const float *src = t.P;
     for (const Level &l : t.levels) {
         const dim3 grid((unsigned)l.tasks.size(), (n_frames + 63) / 64);
         mixgroups_reduce<<<grid, RW * 64, 0, s>>>(raw ? l.dtasks_raw : l.dtasks, src, t.P, l.out, dst, n_frames, p->FS, p->desc.n_groups);
-        if (hipGetLastError() != hipSuccess) return fail(p, DSPFX_ERR_HIP, "mixgroups_reduce");
+        if (hipGetLastError() != hipSuccess) return p->fail(DSPFX_ERR_HIP, "mixgroups_reduce");
         src = l.out;
     }
     return DSPFX_OK;
@@ -1155,11 +1037,11 @@ int mapped_sums(dspfx_mixgroups *p, const Seating &t, const float *block, uint32
 extern "C" int dspfx_mixgroups_run(dspfx_mixgroups *p, const float *block, uint32_t n_frames, float *buses, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!block || !buses || n_frames == 0 || n_frames > p->desc.max_frames) return fail(p, DSPFX_ERR_INVALID, "mixgroups run: block, buses or n_frames");
+    if (!block || !buses || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "mixgroups run: block, buses or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    MG_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
-    MG_HIP(order(p, s), "stream order");
-    MG_HIP(apply_stores(p, s), "fader store");
+    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
+    BANK_HIP_WHY(order(p, s), "stream order");
+    BANK_HIP_WHY(apply_stores(p, s), "fader store");
     if (p->seat) return mapped_sums(p, *p->seat, block, n_frames, buses, false, p->n_faded != 0, s);
     P1Args a;
     a.x = block;
@@ -1179,12 +1061,12 @@ extern "C" int dspfx_mixgroups_run(dspfx_mixgroups *p, const float *block, uint3
     const bool gain = p->n_faded != 0;
     const bool vec = a.Wrow % 4 == 0 && ((uintptr_t)block & 15u) == 0;
     a.nchunks = (n_frames + CHUNK - 1) / CHUNK;
-    MG_HIP(launch_partials<CHUNK>(a, gain, vec, s), "mixgroups_partials");
+    BANK_HIP_WHY(launch_partials<CHUNK>(a, gain, vec, s), "mixgroups_partials");
     const float *src = p->L;
     for (Level &l : p->levels) {
         const dim3 grid((unsigned)l.tasks.size(), (n_frames + 63) / 64);
         mixgroups_reduce<<<grid, RW * 64, 0, s>>>(l.dtasks, src, p->R, l.out, buses, n_frames, p->FS, a.G);
-        MG_HIP(hipGetLastError(), "mixgroups_reduce");
+        BANK_HIP_WHY(hipGetLastError(), "mixgroups_reduce");
         src = l.out;
     }
     return DSPFX_OK;
@@ -1229,7 +1111,7 @@ int prepare_returns(dspfx_mixgroups *p) {
     int rc = DSPFX_OK;
     if (!ok) {
         (void)hipGetLastError();
-        rc = fail(p, DSPFX_ERR_OOM, "mixgroups returns: no device memory for the raw sums [max_frames][G] and the returns tables");
+        rc = p->fail(DSPFX_ERR_OOM, "mixgroups returns: no device memory for the raw sums [max_frames][G] and the returns tables");
     } else {
         ok = hipMemcpy(p->rdiv, rdiv.data(), (size_t)G * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemcpy(p->sfirst, sfirst.data(), sfirst.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
@@ -1241,7 +1123,7 @@ int prepare_returns(dspfx_mixgroups *p) {
                 ok = ok && hipMemcpy(l.dtasks_raw, t.data(), t.size() * sizeof(Task), hipMemcpyHostToDevice) == hipSuccess;
             }
         }
-        if (!ok) rc = fail(p, DSPFX_ERR_HIP, "mixgroups returns: copying the returns tables");
+        if (!ok) rc = p->fail(DSPFX_ERR_HIP, "mixgroups returns: copying the returns tables");
     }
     if (rc != DSPFX_OK) {                        // all or nothing: the next call tries again
         for (void **d : {(void **)&p->S, (void **)&p->rdiv, (void **)&p->sfirst, (void **)&p->gdiv_raw})
@@ -1279,13 +1161,13 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     if (!block || !returns || n_frames == 0 || n_frames > p->desc.max_frames)
-        return fail(p, DSPFX_ERR_INVALID, "mixgroups returns: block, returns or n_frames");
+        return p->fail(DSPFX_ERR_INVALID, "mixgroups returns: block, returns or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    MG_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
+    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
     const int rc = prepare_returns(p);
     if (rc != DSPFX_OK) return rc;
-    MG_HIP(order(p, s), "stream order");
-    MG_HIP(apply_stores(p, s), "fader store");       // once: the sums and the subtraction see the same table
+    BANK_HIP_WHY(order(p, s), "stream order");
+    BANK_HIP_WHY(apply_stores(p, s), "fader store");       // once: the sums and the subtraction see the same table
     const bool raw = p->desc.normalise != 0;
     if (p->seat) {
         const Seating &t = *p->seat;
@@ -1296,7 +1178,7 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
         if (buses) {
             const uint64_t total = (uint64_t)n_frames * G;
             mixgroups_divide<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(p->S, t.gdiv, buses, G, total);
-            MG_HIP(hipGetLastError(), "mixgroups_divide");
+            BANK_HIP_WHY(hipGetLastError(), "mixgroups_divide");
         }
         RetMapArgs r;
         r.x = block;
@@ -1321,7 +1203,7 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
             if (vec) mixrooms_returns<false, true><<<blocks, P1_WG, 0, s>>>(r);
             else mixrooms_returns<false, false><<<blocks, P1_WG, 0, s>>>(r);
         }
-        MG_HIP(hipGetLastError(), "mixrooms_returns");
+        BANK_HIP_WHY(hipGetLastError(), "mixrooms_returns");
         return DSPFX_OK;
     }
     P1Args a;
@@ -1341,18 +1223,18 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
     a.nspans = p->nspans;
     const bool gain = p->n_faded != 0;
     a.nchunks = (n_frames + CHUNK - 1) / CHUNK;
-    MG_HIP(launch_partials<CHUNK>(a, gain, a.Wrow % 4 == 0 && ((uintptr_t)block & 15u) == 0, s), "mixgroups_partials");
+    BANK_HIP_WHY(launch_partials<CHUNK>(a, gain, a.Wrow % 4 == 0 && ((uintptr_t)block & 15u) == 0, s), "mixgroups_partials");
     const float *src = p->L;
     for (Level &l : p->levels) {
         const dim3 grid((unsigned)l.tasks.size(), (n_frames + 63) / 64);
         mixgroups_reduce<<<grid, RW * 64, 0, s>>>(raw ? l.dtasks_raw : l.dtasks, src, p->R, l.out, p->S, n_frames, p->FS, a.G);
-        MG_HIP(hipGetLastError(), "mixgroups_reduce");
+        BANK_HIP_WHY(hipGetLastError(), "mixgroups_reduce");
         src = l.out;
     }
     if (buses) {
         const uint64_t total = (uint64_t)n_frames * a.G;
         mixgroups_divide<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(p->S, p->gdiv, buses, a.G, total);
-        MG_HIP(hipGetLastError(), "mixgroups_divide");
+        BANK_HIP_WHY(hipGetLastError(), "mixgroups_divide");
     }
     RetArgs r;
     r.x = block;
@@ -1371,7 +1253,7 @@ extern "C" int dspfx_mixgroups_returns(dspfx_mixgroups *p, const float *block, u
     r.nchunks = (n_frames + RCHUNK - 1) / RCHUNK;
     r.norm = raw ? 1u : 0u;
     const bool vec = a.Wrow % 4 == 0 && (((uintptr_t)block | (uintptr_t)returns) & 15u) == 0;
-    MG_HIP(launch_returns(r, gain, vec, s), "mixgroups_returns");
+    BANK_HIP_WHY(launch_returns(r, gain, vec, s), "mixgroups_returns");
     return DSPFX_OK;
 }
 
@@ -1449,11 +1331,7 @@ int make_seating(dspfx_mixgroups *p, std::vector<uint32_t> &&room, Seating **out
     return DSPFX_OK;
 }
 
-int assign_fail(dspfx_mixgroups *p, int rc, const std::string &what) {
-    std::lock_guard<std::mutex> lk(p->mu);           // the reason is the bank's, and a run may be writing one
-    p->err = what;
-    return rc;
-}
+int assign_fail(dspfx_mixgroups *p, int rc, const std::string &what) { return p->fail(rc, what.c_str()); }
 
 void rooms_of_table(const std::vector<uint32_t> &gs, std::vector<uint32_t> &room) {
     for (size_t g = 0; g + 1 < gs.size(); ++g) std::fill(room.begin() + gs[g], room.begin() + gs[g + 1], (uint32_t)g);
@@ -1531,7 +1409,7 @@ extern "C" int dspfx_mixgroups_rooms(dspfx_mixgroups *p, uint32_t *host_ids_out,
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     const uint64_t N = p->desc.n_channels;
-    if (!host_ids_out || first_channel > N || count > N - first_channel) return fail(p, DSPFX_ERR_INVALID, "mixgroups rooms: the array or the range");
+    if (!host_ids_out || first_channel > N || count > N - first_channel) return p->fail(DSPFX_ERR_INVALID, "mixgroups rooms: the array or the range");
     if (p->seat) {
         std::copy(p->seat->room.begin() + (size_t)first_channel, p->seat->room.begin() + (size_t)(first_channel + count), host_ids_out);
         return DSPFX_OK;
@@ -1547,22 +1425,13 @@ extern "C" int dspfx_mixgroups_rooms(dspfx_mixgroups *p, uint32_t *host_ids_out,
 extern "C" int dspfx_mixgroups_room_plan(const uint32_t *room_of, uint64_t n_channels, uint32_t n_groups, uint32_t tile_channels,
                                          uint64_t *count_out, uint32_t *depth_out, uint64_t *pieces_out) {
     g_err.clear();
-    char buf[160];
     if (!room_of || n_groups == 0) {
         g_err = "mixgroups: no room ids, or no rooms";
         return DSPFX_ERR_INVALID;
     }
-    if (n_channels == 0 || n_channels > 0xFFFFFF00ull) {
-        g_err = "mixgroups: n_channels must be 1 .. 2^32 - 256";
-        return DSPFX_ERR_INVALID;
-    }
-    if (tile_channels && (!pow2(tile_channels) || n_channels % tile_channels)) {
-        std::snprintf(buf, sizeof buf, "mixgroups: tile_channels %u is not a power of two that divides n_channels %llu", tile_channels,
-                      (unsigned long long)n_channels);
-        g_err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    const int rc = check_rooms(room_of, 0, n_channels, n_groups, g_err);
+    int rc = check_shape("mixgroups", n_channels, tile_channels, g_err);
+    if (rc != DSPFX_OK) return rc;
+    rc = check_rooms(room_of, 0, n_channels, n_groups, g_err);
     if (rc != DSPFX_OK) return rc;
     RoomPlan pl;
     try {

@@ -26,16 +26,15 @@
 // out may not overlap the block: a room's inputs are all needed after its first outputs exist (every listener reads every source),
 // so in place cannot work; the run refuses it.
 //
-// Stores (dspfx_mixmatrix_set_rows / _set_cols / _fill / _reset) follow the mix-group bank's fader stores: validated, staged in
-// page-locked memory, queued under the queue's own lock, and put on the next run's stream ahead of its kernel in the order they were
-// made: a copy, a scatter into the source-major table, and a recount of w and d for the listeners touched -- d is computed on the
+// Stores (dspfx_mixmatrix_set_rows / _set_cols / _fill / _reset) go through the staged-store queue (store_queue.hip.h): validated,
+// staged in page-locked memory, queued under the queue's own lock, and put on the next run's stream ahead of its kernel in the order they
+// were made: a copy, a scatter into the source-major table, and a recount of w and d for the listeners touched -- d is computed on the
 // device with dspfx_link_divisor's own f32 expression, so no store waits for the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <mutex>
 #include <new>
 #include <string>
@@ -43,6 +42,7 @@
 
 #include "../../include/dspfx.h"
 #include "bank_common.hip.h"
+#include "store_queue.hip.h"
 
 namespace {
 
@@ -216,75 +216,23 @@ __global__ __launch_bounds__(WG) void mixmatrix_recount(const float *__restrict_
 
 thread_local std::string g_err;        // the reason of the last failed create or plan on this thread
 
-struct Store {
+// a store's vals: [count][n]; a fill has none
+struct StoreFields {
     int kind = 0;                // 0: rows, 1: columns, 2: fill
-    float *vals = nullptr;       // page-locked, [count][n]; fill: none
-    size_t cap = 0;              // floats
     uint32_t room = 0, l0 = 0, count = 0;        // rows / columns: room-local first index and count; fill: rooms [room, room + count)
     uint32_t preset = 0;
-    hipEvent_t ev = nullptr;
 };
-
-int check_table(const uint64_t *gs, uint32_t G, uint64_t N, uint32_t W, std::string &err) {
-    char buf[192];
-    if (!gs || G == 0) {
-        err = "mixmatrix: no group table";
-        return DSPFX_ERR_INVALID;
-    }
-    if (N == 0 || N > 0xFFFFFF00ull) {
-        err = "mixmatrix: n_channels must be 1 .. 2^32 - 256";
-        return DSPFX_ERR_INVALID;
-    }
-    if (W && (!pow2(W) || N % W)) {
-        std::snprintf(buf, sizeof buf, "mixmatrix: tile_channels %u is not a power of two that divides n_channels %llu", W, (unsigned long long)N);
-        err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    if (gs[0] != 0) {
-        std::snprintf(buf, sizeof buf, "mixmatrix: group_start[0] is %llu, not 0", (unsigned long long)gs[0]);
-        err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    for (uint32_t g = 0; g < G; ++g) {
-        if (gs[g + 1] < gs[g]) {
-            std::snprintf(buf, sizeof buf, "mixmatrix: group_start decreases at entry %u (%llu after %llu)", g + 1, (unsigned long long)gs[g + 1],
-                          (unsigned long long)gs[g]);
-            err = buf;
-            return DSPFX_ERR_INVALID;
-        }
-        const uint64_t n = gs[g + 1] - gs[g];
-        if (n == 0) {
-            std::snprintf(buf, sizeof buf, "mixmatrix: room %u is empty (a room has 1 .. %u members)", g, MAXN);
-            err = buf;
-            return DSPFX_ERR_INVALID;
-        }
-        if (n > MAXN) {
-            std::snprintf(buf, sizeof buf, "mixmatrix: room %u has %llu members, above DSPFX_MIXMATRIX_MAX_ROOM = %u", g, (unsigned long long)n, MAXN);
-            err = buf;
-            return DSPFX_ERR_INVALID;
-        }
-    }
-    if (gs[G] != N) {
-        std::snprintf(buf, sizeof buf, "mixmatrix: group_start[%u] is %llu, not n_channels %llu", G, (unsigned long long)gs[G], (unsigned long long)N);
-        err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    return DSPFX_OK;
-}
+typedef StoreQueue<StoreFields> Stores;
+typedef Stores::Store Store;
 
 }  // namespace
 
-struct dspfx_mixmatrix {
+struct dspfx_mixmatrix : BankError {
     dspfx_mixmatrix_desc desc{};
     std::vector<uint64_t> gs;                    // the table, [G + 1]
     std::vector<Room> hrooms;
     std::mutex mu;                               // run / destroy
-    std::mutex qmu;                              // the store queue, the free staging buffers
-    std::mutex emu;                              // err
-    std::deque<Store> queue;                     // stores not yet handed to a stream
-    std::vector<Store> spare;                    // staging buffers free for the next store
-    std::vector<Store> flying;                   // copies queued on a stream (mu)
-    std::vector<hipEvent_t> events;              // spare events (mu)
+    Stores stores;                               // the matrix stores
     float *tab = nullptr, *div = nullptr, *stage = nullptr;      // stage: [maxn][maxn], where a drained store's values land
     Room *rooms = nullptr;
     Item *items = nullptr;
@@ -293,7 +241,6 @@ struct dspfx_mixmatrix {
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
-    std::string err;
 };
 
 namespace {
@@ -302,23 +249,9 @@ void release(dspfx_mixmatrix *p) {
     (void)hipSetDevice(p->desc.device);
     for (void *d : {(void *)p->tab, (void *)p->div, (void *)p->stage, (void *)p->rooms, (void *)p->items, (void *)p->room_of})
         if (d) (void)hipFree(d);
-    for (Store &s : p->queue)
-        if (s.vals) (void)hipHostFree(s.vals);
-    for (Store &s : p->spare)
-        if (s.vals) (void)hipHostFree(s.vals);
-    for (Store &s : p->flying) {
-        if (s.vals) (void)hipHostFree(s.vals);
-        if (s.ev) (void)hipEventDestroy(s.ev);
-    }
-    for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
+    p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
-}
-
-int fail(dspfx_mixmatrix *p, int rc, const char *what) {
-    std::lock_guard<std::mutex> lk(p->emu);
-    p->err = what;
-    return rc;
 }
 
 hipError_t recount(dspfx_mixmatrix *p, uint32_t first, uint32_t count, hipStream_t s) {
@@ -334,114 +267,40 @@ hipError_t fill_rooms(dspfx_mixmatrix *p, uint32_t first_room, uint32_t count, u
     return recount(p, c0, c1 - c0, s);
 }
 
-// the stores made so far, in order, onto the stream ahead of the run; staging buffers whose copy is done go back
-hipError_t apply_stores(dspfx_mixmatrix *p, hipStream_t s) {
-    std::vector<Store> done;
-    for (size_t i = 0; i < p->flying.size();) {
-        if (hipEventQuery(p->flying[i].ev) == hipSuccess) {
-            p->events.push_back(p->flying[i].ev);
-            p->flying[i].ev = nullptr;
-            done.push_back(p->flying[i]);
-            p->flying[i] = p->flying.back();
-            p->flying.pop_back();
-        } else {
-            (void)hipGetLastError();
-            ++i;
-        }
-    }
-    std::deque<Store> q;
-    {
-        std::lock_guard<std::mutex> lk(p->qmu);
-        for (Store &d : done) p->spare.push_back(d);
-        q.swap(p->queue);
-    }
-    hipError_t err = hipSuccess;
-    while (!q.empty()) {
-        Store st = q.front();
-        q.pop_front();
-        if (err != hipSuccess) {                 // a failed call drops the stores behind it; their buffers are still freed
-            if (st.vals) (void)hipHostFree(st.vals);
-            continue;
-        }
-        if (st.kind == 2) {
-            err = fill_rooms(p, st.room, st.count, st.preset, s);
-            continue;
-        }
-        const Room &rm = p->hrooms[st.room];
-        const uint32_t cells = st.count * rm.n;
-        err = hipMemcpyAsync(p->stage, st.vals, (size_t)cells * sizeof(float), hipMemcpyHostToDevice, s);
-        if (err == hipSuccess) {
-            mixmatrix_store<<<(cells + WG - 1) / WG, WG, 0, s>>>(p->tab, p->stage, rm.off, rm.n, st.l0, st.count, (uint32_t)st.kind);
-            err = hipGetLastError();
-        }
-        // a row store changes the wired count of its listeners, a column store that of every listener of the room
-        if (err == hipSuccess) err = st.kind == 0 ? recount(p, rm.c0 + st.l0, st.count, s) : recount(p, rm.c0, rm.n, s);
-        if (err == hipSuccess) {
-            if (p->events.empty()) {
-                err = hipEventCreateWithFlags(&st.ev, hipEventDisableTiming);
-            } else {
-                st.ev = p->events.back();
-                p->events.pop_back();
-            }
-        }
-        if (err == hipSuccess) err = hipEventRecord(st.ev, s);
-        if (st.ev) {
-            p->flying.push_back(st);
-        } else {                                 // no event to tell when the copy is done: wait, then the buffer is free
-            (void)hipStreamSynchronize(s);
-            (void)hipHostFree(st.vals);
-        }
-    }
-    return err;
-}
-
-// a staging buffer of at least `floats`, from the spare ones or new; nullptr: none to be had
-float *staging(dspfx_mixmatrix *p, size_t floats, size_t *cap) {
-    {
-        std::lock_guard<std::mutex> lk(p->qmu);
-        for (size_t i = 0; i < p->spare.size(); ++i)
-            if (p->spare[i].cap >= floats) {
-                float *v = p->spare[i].vals;
-                *cap = p->spare[i].cap;
-                p->spare[i] = p->spare.back();
-                p->spare.pop_back();
-                return v;
-            }
-    }
-    float *v = nullptr;
-    if (hipSetDevice(p->desc.device) != hipSuccess) return nullptr;
-    if (hipHostMalloc((void **)&v, floats * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    *cap = floats;
-    return v;
+// one store onto the stream: a fill, or the values into `stage`, the scatter into the table and the recount
+hipError_t apply_store(dspfx_mixmatrix *p, const Store &st, hipStream_t s) {
+    if (st.kind == 2) return fill_rooms(p, st.room, st.count, st.preset, s);
+    const Room &rm = p->hrooms[st.room];
+    const uint32_t cells = st.count * rm.n;
+    hipError_t err = hipMemcpyAsync(p->stage, st.vals, (size_t)cells * sizeof(float), hipMemcpyHostToDevice, s);
+    if (err != hipSuccess) return err;
+    mixmatrix_store<<<(cells + WG - 1) / WG, WG, 0, s>>>(p->tab, p->stage, rm.off, rm.n, st.l0, st.count, (uint32_t)st.kind);
+    err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    // a row store changes the wired count of its listeners, a column store that of every listener of the room
+    return st.kind == 0 ? recount(p, rm.c0 + st.l0, st.count, s) : recount(p, rm.c0, rm.n, s);
 }
 
 // rows or columns [first, first + count) of one room, row_len values each
 int store_lines(dspfx_mixmatrix *p, int kind, const float *vals, uint32_t row_len, uint64_t first, uint64_t count) {
     const char *what = kind ? "set_cols" : "set_rows";
     char buf[224];
-    const uint64_t N = p->desc.n_channels;
     if (!vals) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: no values", what);
-        return fail(p, DSPFX_ERR_INVALID, buf);
+        return p->fail(DSPFX_ERR_INVALID, buf);
     }
-    if (first >= N || count > N - first) {
-        std::snprintf(buf, sizeof buf, "mixmatrix %s: channels [%llu, %llu + %llu) are not inside the bank's %llu", what, (unsigned long long)first,
-                      (unsigned long long)first, (unsigned long long)count, (unsigned long long)N);
-        return fail(p, DSPFX_ERR_INVALID, buf);
-    }
+    std::string why;                             // (a range that begins at N is in no room: not even an empty one is inside)
+    if (check_range("mixmatrix", what, first, count, p->desc.n_channels, why, false) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, why.c_str());
     const uint32_t room = (uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), first) - p->gs.begin()) - 1;
     const Room &rm = p->hrooms[room];
     if (first + count > (uint64_t)rm.c0 + rm.n) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: channels [%llu, %llu + %llu) are not in one room (room %u is [%u, %u))", what,
                       (unsigned long long)first, (unsigned long long)first, (unsigned long long)count, room, rm.c0, rm.c0 + rm.n);
-        return fail(p, DSPFX_ERR_INVALID, buf);
+        return p->fail(DSPFX_ERR_INVALID, buf);
     }
     if (row_len != rm.n) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: a row of %u values, and room %u has %u members", what, row_len, room, rm.n);
-        return fail(p, DSPFX_ERR_INVALID, buf);
+        return p->fail(DSPFX_ERR_INVALID, buf);
     }
     if (count == 0) return DSPFX_OK;
     Store st;
@@ -450,30 +309,23 @@ int store_lines(dspfx_mixmatrix *p, int kind, const float *vals, uint32_t row_le
     st.l0 = (uint32_t)first - rm.c0;
     st.count = (uint32_t)count;
     const size_t cells = (size_t)count * rm.n;
-    st.vals = staging(p, cells, &st.cap);
-    if (!st.vals) {
+    if (!p->stores.staging(p->desc.device, cells, st)) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: no page-locked memory for the staged values", what);
-        return fail(p, DSPFX_ERR_OOM, buf);
+        return p->fail(DSPFX_ERR_OOM, buf);
     }
     std::memcpy(st.vals, vals, cells * sizeof(float));
-    std::lock_guard<std::mutex> lk(p->qmu);
-    p->queue.push_back(st);
+    p->stores.push(st);
     return DSPFX_OK;
 }
 
 }  // namespace
-
-#define MM_HIP(call, what)                                             \
-    do {                                                               \
-        if ((call) != hipSuccess) return fail(p, DSPFX_ERR_HIP, what); \
-    } while (0)
 
 extern "C" const char *dspfx_mixmatrix_last_error(const dspfx_mixmatrix *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
 extern "C" int dspfx_mixmatrix_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
                                     uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
     g_err.clear();
-    const int rc = check_table(group_start, n_groups, n_channels, tile_channels, g_err);
+    const int rc = check_table("mixmatrix", group_start, n_groups, n_channels, tile_channels, MAXN, g_err);
     if (rc != DSPFX_OK) return rc;
     uint64_t off = 0;
     for (uint32_t g = 0; g < n_groups; ++g) {
@@ -519,13 +371,8 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
             g_err = "mixmatrix: n_channels x max_frames is too large";
             return DSPFX_ERR_INVALID;
         }
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-        if (desc->device < 0 || desc->device >= count) {
-            g_err = "mixmatrix: no such device";
-            return DSPFX_ERR_INVALID;
-        }
-        if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+        const int dev_rc = open_device("mixmatrix", desc->device, &g_err);
+        if (dev_rc != DSPFX_OK) return dev_rc;
         p = new dspfx_mixmatrix;
         p->desc = *desc;
         p->gs.assign(desc->group_start, desc->group_start + G + 1);
@@ -575,12 +422,7 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
 
 extern "C" int dspfx_mixmatrix_destroy(dspfx_mixmatrix *p) {
     if (!p) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        (void)hipSetDevice(p->desc.device);
-        if (p->used) (void)hipStreamSynchronize(p->last);    // the bank's work is ordered on the last stream it used
-    }
-    release(p);
+    close_bank(p, release);
     return DSPFX_OK;
 }
 
@@ -600,19 +442,18 @@ extern "C" int dspfx_mixmatrix_fill(dspfx_mixmatrix *p, int64_t room, uint32_t p
     const uint32_t G = p->desc.n_groups;
     if (preset != DSPFX_MIXMATRIX_MIX_MINUS && preset != DSPFX_MIXMATRIX_ZERO) {
         std::snprintf(buf, sizeof buf, "mixmatrix fill: preset %u (DSPFX_MIXMATRIX_MIX_MINUS and DSPFX_MIXMATRIX_ZERO are known)", preset);
-        return fail(p, DSPFX_ERR_INVALID, buf);
+        return p->fail(DSPFX_ERR_INVALID, buf);
     }
     if (room < -1 || room >= (int64_t)G) {
         std::snprintf(buf, sizeof buf, "mixmatrix fill: room %lld, and the bank has %u (-1: every room)", (long long)room, G);
-        return fail(p, DSPFX_ERR_INVALID, buf);
+        return p->fail(DSPFX_ERR_INVALID, buf);
     }
     Store st;
     st.kind = 2;
     st.room = room < 0 ? 0u : (uint32_t)room;
     st.count = room < 0 ? G : 1u;
     st.preset = preset;
-    std::lock_guard<std::mutex> lk(p->qmu);
-    p->queue.push_back(st);
+    p->stores.push(st);
     return DSPFX_OK;
 }
 
@@ -621,14 +462,14 @@ extern "C" int dspfx_mixmatrix_reset(dspfx_mixmatrix *p) { return dspfx_mixmatri
 extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint32_t n_frames, float *out, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!block || !out || n_frames == 0 || n_frames > p->desc.max_frames) return fail(p, DSPFX_ERR_INVALID, "mixmatrix run: block, out or n_frames");
+    if (!block || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: block, out or n_frames");
     const uintptr_t bytes = (uintptr_t)p->desc.n_channels * n_frames * sizeof(float), b0 = (uintptr_t)block, o0 = (uintptr_t)out;
     if (b0 < o0 + bytes && o0 < b0 + bytes)
-        return fail(p, DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block (every listener reads every source of its room: no in-place form)");
+        return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block (every listener reads every source of its room: no in-place form)");
     hipStream_t s = (hipStream_t)stream;
-    MM_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
-    MM_HIP(order(p, s), "stream order");
-    MM_HIP(apply_stores(p, s), "matrix store");
+    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
+    BANK_HIP_WHY(order(p, s), "stream order");
+    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "matrix store");
     RunArgs a;
     a.in = block;
     a.out = out;
@@ -641,6 +482,6 @@ extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint3
     a.nf = n_frames;
     a.normalise = p->desc.normalise;
     mixmatrix_run<<<dim3(p->n_items, (n_frames + FT - 1) / FT), WG, 0, s>>>(a);
-    MM_HIP(hipGetLastError(), "mixmatrix_run");
+    BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run");
     return DSPFX_OK;
 }

@@ -388,10 +388,8 @@ extern "C" int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **ou
     if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
     const uint32_t N = desc->channels, W = desc->tile_channels;
     if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-    if (desc->device < 0 || desc->device >= count) return DSPFX_ERR_INVALID;
-    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    const int dev_rc = open_device(nullptr, desc->device, nullptr);
+    if (dev_rc != DSPFX_OK) return dev_rc;
     dspfx_pitch *p = new (std::nothrow) dspfx_pitch;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;

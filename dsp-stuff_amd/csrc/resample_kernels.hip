@@ -395,10 +395,8 @@ extern "C" int dspfx_resample_create(const dspfx_resample_desc *desc, dspfx_resa
     if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
     if (desc->block_frames == 0 || desc->block_frames > MAX_FRAMES || desc->slots < 3 || desc->target_hz == 0) return DSPFX_ERR_INVALID;
     if (!dspfx::pcm_format_ok(desc->out_format) || !dspfx::pcm_channels_ok(desc->out_channels)) return DSPFX_ERR_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-    if (desc->device < 0 || desc->device >= count) return DSPFX_ERR_INVALID;
-    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    const int dev_rc = open_device(nullptr, desc->device, nullptr);
+    if (dev_rc != DSPFX_OK) return dev_rc;
     dspfx_resample *r = new (std::nothrow) dspfx_resample;
     if (!r) return DSPFX_ERR_OOM;
     r->desc = *desc;

@@ -228,10 +228,8 @@ extern "C" int dspfx_spectrum_create(const dspfx_spectrum_desc *desc, dspfx_spec
     if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
     const int rc = check_size(n);
     if (rc != DSPFX_OK) return rc;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-    if (desc->device < 0 || desc->device >= count) return DSPFX_ERR_INVALID;
-    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    const int dev_rc = open_device(nullptr, desc->device, nullptr);
+    if (dev_rc != DSPFX_OK) return dev_rc;
     dspfx_spectrum *p = new (std::nothrow) dspfx_spectrum;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;

@@ -13,14 +13,13 @@
 // result.  Nothing is shared between channels: no LDS, no atomics, and a channel's bits do not depend on its neighbours.
 // A lane rewrites the elements it read, so out may be in.
 //
-// Slider stores (dspfx_strips_set_gain / _set_band) follow the mix-group bank's fader stores: staged in page-locked memory, queued,
-// and put on the next run's stream ahead of its kernel; a band store also zeroes the band's state on the stored channels
+// Slider stores (dspfx_strips_set_gain / _set_band) go through the staged-store queue (store_queue.hip.h): staged in page-locked
+// memory, queued, and put on the next run's stream ahead of its kernel; a band store also zeroes the band's state on the stored channels
 // (after_settings_change -> regenerate_filter -> reset_state, biquad.rs:62-76).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <mutex>
 #include <new>
 #include <string>
@@ -28,6 +27,7 @@
 
 #include "../../include/dspfx.h"
 #include "bank_common.hip.h"
+#include "store_queue.hip.h"
 
 namespace {
 
@@ -267,36 +267,30 @@ __global__ __launch_bounds__(WG) void strips_store(uint32_t *__restrict__ mask, 
 
 thread_local std::string g_err;        // the reason of the last failed create on this thread
 
-struct Store {
+// a store's vals: [count] levels or [5][count] coefficients; none: the node is dropped
+struct StoreFields {
     int node = 0;                // 0: the Gain node; 1 + b: band b
-    float *vals = nullptr;       // page-locked, [count] levels or [5][count] coefficients; nullptr: the node is dropped
-    size_t cap = 0;              // floats
     uint32_t first = 0, count = 0;
-    hipEvent_t ev = nullptr;
 };
+typedef StoreQueue<StoreFields> Stores;
+typedef Stores::Store Store;
 
 uint32_t bands_built(uint32_t K) { return K <= 1 ? 1u : K <= 2 ? 2u : K <= 4 ? 4u : 8u; }
 
 }  // namespace
 
-struct dspfx_strips {
+struct dspfx_strips : BankError {
     dspfx_strips_desc desc{};
     uint32_t KB = 1;                             // the kernel's band count: 1, 2, 4 or 8
     std::mutex mu;                               // run / reset / destroy
-    std::mutex qmu;                              // the store queue, the free staging buffers, hmask
-    std::mutex emu;                              // err
-    std::deque<Store> queue;                     // stores not yet handed to a stream
-    std::vector<Store> spare;                    // staging buffers free for the next store
-    std::vector<Store> flying;                   // copies queued on a stream (mu)
-    std::vector<hipEvent_t> events;              // spare events (mu)
-    std::vector<uint32_t> hmask;                 // the node masks with every store made so far (qmu): what the next run sees
+    Stores stores;                               // the slider stores; its qmu guards hmask too
+    std::vector<uint32_t> hmask;                 // the node masks with every store made so far (stores.qmu): what the next run sees
     float *coef = nullptr, *state = nullptr, *level = nullptr;
     uint32_t *mask = nullptr;
     float div = 1.0f;
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
-    std::string err;
 };
 
 namespace {
@@ -305,137 +299,50 @@ void release(dspfx_strips *p) {
     (void)hipSetDevice(p->desc.device);
     for (void *d : {(void *)p->coef, (void *)p->state, (void *)p->level, (void *)p->mask})
         if (d) (void)hipFree(d);
-    for (Store &s : p->queue)
-        if (s.vals) (void)hipHostFree(s.vals);
-    for (Store &s : p->spare)
-        if (s.vals) (void)hipHostFree(s.vals);
-    for (Store &s : p->flying) {
-        if (s.vals) (void)hipHostFree(s.vals);
-        if (s.ev) (void)hipEventDestroy(s.ev);
-    }
-    for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
+    p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
 }
 
-int fail(dspfx_strips *p, int rc, const char *what) {
-    std::lock_guard<std::mutex> lk(p->emu);
-    p->err = what;
-    return rc;
-}
-
-// the stores made so far, in order, onto the stream ahead of the run; staging buffers whose copy is done go back
-hipError_t apply_stores(dspfx_strips *p, hipStream_t s) {
-    std::vector<Store> done;
-    for (size_t i = 0; i < p->flying.size();) {
-        if (hipEventQuery(p->flying[i].ev) == hipSuccess) {
-            p->events.push_back(p->flying[i].ev);
-            p->flying[i].ev = nullptr;
-            done.push_back(p->flying[i]);
-            p->flying[i] = p->flying.back();
-            p->flying.pop_back();
-        } else {
-            (void)hipGetLastError();
-            ++i;
-        }
-    }
-    std::deque<Store> q;
-    {
-        std::lock_guard<std::mutex> lk(p->qmu);
-        for (Store &d : done) p->spare.push_back(d);
-        q.swap(p->queue);
-    }
+// one store onto the stream: its values, then the node bit (and a band's zeroed state) on its channels
+hipError_t apply_store(dspfx_strips *p, const Store &st, hipStream_t s) {
     const uint32_t N = p->desc.n_channels;
+    const uint32_t bit = 1u << st.node, blocks = (st.count + WG - 1) / WG;
+    if (!st.vals) {
+        strips_store<<<blocks, WG, 0, s>>>(p->mask, nullptr, N, st.first, st.count, 0u, bit);
+        return hipGetLastError();
+    }
     hipError_t err = hipSuccess;
-    while (!q.empty()) {
-        Store st = q.front();
-        q.pop_front();
-        if (err != hipSuccess) {                 // a failed call drops the stores behind it; their buffers are still freed
-            if (st.vals) (void)hipHostFree(st.vals);
-            continue;
-        }
-        const uint32_t bit = 1u << st.node, blocks = (st.count + WG - 1) / WG;
-        if (!st.vals) {
-            strips_store<<<blocks, WG, 0, s>>>(p->mask, nullptr, N, st.first, st.count, 0u, bit);
-            err = hipGetLastError();
-            continue;
-        }
-        float *band_state = nullptr;
-        if (st.node == 0) {
-            err = hipMemcpyAsync(p->level + st.first, st.vals, (size_t)st.count * sizeof(float), hipMemcpyHostToDevice, s);
-        } else {
-            const uint32_t b = (uint32_t)st.node - 1;
-            band_state = p->state + (size_t)b * 4 * N;
-            for (uint32_t r = 0; r < 5 && err == hipSuccess; ++r)
-                err = hipMemcpyAsync(p->coef + ((size_t)b * 5 + r) * N + st.first, st.vals + (size_t)r * st.count,
-                                     (size_t)st.count * sizeof(float), hipMemcpyHostToDevice, s);
-        }
-        if (err == hipSuccess) {
-            strips_store<<<blocks, WG, 0, s>>>(p->mask, band_state, N, st.first, st.count, bit, 0u);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) {
-            if (p->events.empty()) {
-                err = hipEventCreateWithFlags(&st.ev, hipEventDisableTiming);
-            } else {
-                st.ev = p->events.back();
-                p->events.pop_back();
-            }
-        }
-        if (err == hipSuccess) err = hipEventRecord(st.ev, s);
-        if (st.ev) {
-            p->flying.push_back(st);
-        } else {                                 // no event to tell when the copies are done: wait, then the buffer is free
-            (void)hipStreamSynchronize(s);
-            (void)hipHostFree(st.vals);
-        }
+    float *band_state = nullptr;
+    if (st.node == 0) {
+        err = hipMemcpyAsync(p->level + st.first, st.vals, (size_t)st.count * sizeof(float), hipMemcpyHostToDevice, s);
+    } else {
+        const uint32_t b = (uint32_t)st.node - 1;
+        band_state = p->state + (size_t)b * 4 * N;
+        for (uint32_t r = 0; r < 5 && err == hipSuccess; ++r)
+            err = hipMemcpyAsync(p->coef + ((size_t)b * 5 + r) * N + st.first, st.vals + (size_t)r * st.count,
+                                 (size_t)st.count * sizeof(float), hipMemcpyHostToDevice, s);
     }
-    return err;
-}
-
-// a staging buffer of at least `floats`, from the spare ones or new; nullptr: none to be had
-float *staging(dspfx_strips *p, size_t floats, size_t *cap) {
-    {
-        std::lock_guard<std::mutex> lk(p->qmu);
-        for (size_t i = 0; i < p->spare.size(); ++i)
-            if (p->spare[i].cap >= floats) {
-                float *v = p->spare[i].vals;
-                *cap = p->spare[i].cap;
-                p->spare[i] = p->spare.back();
-                p->spare.pop_back();
-                return v;
-            }
-    }
-    float *v = nullptr;
-    if (hipSetDevice(p->desc.device) != hipSuccess) return nullptr;
-    if (hipHostMalloc((void **)&v, floats * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    *cap = floats;
-    return v;
+    if (err != hipSuccess) return err;
+    strips_store<<<blocks, WG, 0, s>>>(p->mask, band_state, N, st.first, st.count, bit, 0u);
+    return hipGetLastError();
 }
 
 int check_range(dspfx_strips *p, const char *what, uint64_t first, uint64_t count) {
-    const uint64_t N = p->desc.n_channels;
-    if (first > N || count > N - first) {
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "strips %s: channels [%llu, %llu + %llu) are not inside the bank's %llu", what,
-                      (unsigned long long)first, (unsigned long long)first, (unsigned long long)count, (unsigned long long)N);
-        return fail(p, DSPFX_ERR_INVALID, buf);
-    }
-    return DSPFX_OK;
+    std::string why;
+    const int rc = check_range("strips", what, first, count, p->desc.n_channels, why);
+    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
 }
 
 // the store joins the queue and the masks the next run will see
 void enqueue(dspfx_strips *p, const Store &st) {
-    std::lock_guard<std::mutex> lk(p->qmu);
-    const uint32_t bit = 1u << st.node;
-    for (uint32_t i = 0; i < st.count; ++i) {
-        uint32_t &m = p->hmask[st.first + i];
-        m = st.vals ? (m | bit) : (m & ~bit);
-    }
-    p->queue.push_back(st);
+    p->stores.push(st, [&] {
+        const uint32_t bit = 1u << st.node;
+        for (uint32_t i = 0; i < st.count; ++i) {
+            uint32_t &m = p->hmask[st.first + i];
+            m = st.vals ? (m | bit) : (m & ~bit);
+        }
+    });
 }
 
 // the lane width per band count: four channels while their coefficients and state fit in registers beside the rows, then two, then one
@@ -456,11 +363,6 @@ hipError_t launch(uint32_t KB, bool vec, const StripArgs &a, hipStream_t s) {
 }
 
 }  // namespace
-
-#define ST_HIP(call, what)                                             \
-    do {                                                               \
-        if ((call) != hipSuccess) return fail(p, DSPFX_ERR_HIP, what); \
-    } while (0)
 
 extern "C" const char *dspfx_strips_last_error(const dspfx_strips *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
@@ -483,16 +385,9 @@ extern "C" int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips *
         g_err = "strips: abi_version or max_frames";
         return DSPFX_ERR_INVALID;
     }
-    if (desc->n_channels == 0 || desc->n_channels > 0xFFFFFF00u) {
-        g_err = "strips: n_channels must be 1 .. 2^32 - 256";
-        return DSPFX_ERR_INVALID;
-    }
-    const uint32_t N = desc->n_channels, W = desc->tile_channels;
-    if (W && (!pow2(W) || N % W)) {
-        std::snprintf(buf, sizeof buf, "strips: tile_channels %u is not a power of two that divides n_channels %u", W, N);
-        g_err = buf;
-        return DSPFX_ERR_INVALID;
-    }
+    const uint32_t N = desc->n_channels;
+    int rc = check_shape("strips", N, desc->tile_channels, g_err);
+    if (rc != DSPFX_OK) return rc;
     if (desc->bands < 1 || desc->bands > DSPFX_STRIPS_MAX_BANDS) {
         std::snprintf(buf, sizeof buf, "strips: %u bands, not 1 .. %d", desc->bands, DSPFX_STRIPS_MAX_BANDS);
         g_err = buf;
@@ -503,13 +398,8 @@ extern "C" int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips *
         g_err = buf;
         return DSPFX_ERR_INVALID;
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return DSPFX_ERR_NO_DEVICE;
-    if (desc->device < 0 || desc->device >= count) {
-        g_err = "strips: no such device";
-        return DSPFX_ERR_INVALID;
-    }
-    if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
+    rc = open_device("strips", desc->device, &g_err);
+    if (rc != DSPFX_OK) return rc;
     dspfx_strips *p = new (std::nothrow) dspfx_strips;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -544,12 +434,7 @@ extern "C" int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips *
 
 extern "C" int dspfx_strips_destroy(dspfx_strips *p) {
     if (!p) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        (void)hipSetDevice(p->desc.device);
-        if (p->used) (void)hipStreamSynchronize(p->last);    // the bank's work is ordered on the last stream it used
-    }
-    release(p);
+    close_bank(p, release);
     return DSPFX_OK;
 }
 
@@ -563,8 +448,7 @@ extern "C" int dspfx_strips_set_gain(dspfx_strips *p, const float *host_levels, 
     st.first = (uint32_t)first_channel;
     st.count = (uint32_t)count;
     if (host_levels) {
-        st.vals = staging(p, count, &st.cap);
-        if (!st.vals) return fail(p, DSPFX_ERR_OOM, "strips set_gain: no page-locked memory for the staged levels");
+        if (!p->stores.staging(p->desc.device, count, st)) return p->fail(DSPFX_ERR_OOM, "strips set_gain: no page-locked memory for the staged levels");
         std::memcpy(st.vals, host_levels, count * sizeof(float));
     }
     enqueue(p, st);
@@ -576,7 +460,7 @@ extern "C" int dspfx_strips_set_band(dspfx_strips *p, uint32_t band, const float
     if (band >= p->desc.bands) {
         char buf[96];
         std::snprintf(buf, sizeof buf, "strips set_band: band %u, and the bank has %u", band, p->desc.bands);
-        return fail(p, DSPFX_ERR_INVALID, buf);
+        return p->fail(DSPFX_ERR_INVALID, buf);
     }
     const int rc = check_range(p, "set_band", first_channel, count);
     if (rc != DSPFX_OK) return rc;
@@ -586,8 +470,7 @@ extern "C" int dspfx_strips_set_band(dspfx_strips *p, uint32_t band, const float
     st.first = (uint32_t)first_channel;
     st.count = (uint32_t)count;
     if (host_raw6) {
-        st.vals = staging(p, 5 * count, &st.cap);
-        if (!st.vals) return fail(p, DSPFX_ERR_OOM, "strips set_band: no page-locked memory for the staged coefficients");
+        if (!p->stores.staging(p->desc.device, 5 * count, st)) return p->fail(DSPFX_ERR_OOM, "strips set_band: no page-locked memory for the staged coefficients");
         for (uint64_t i = 0; i < count; ++i) {           // regenerate_filter per channel, transposed to [5][count]
             float k5[5];
             (void)dspfx_strips_coeffs(host_raw6 + 6 * i, k5);
@@ -600,10 +483,10 @@ extern "C" int dspfx_strips_set_band(dspfx_strips *p, uint32_t band, const float
 
 extern "C" int dspfx_strips_present(dspfx_strips *p, uint32_t *host_masks_out, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
-    if (!host_masks_out) return fail(p, DSPFX_ERR_INVALID, "strips present: no array");
+    if (!host_masks_out) return p->fail(DSPFX_ERR_INVALID, "strips present: no array");
     const int rc = check_range(p, "present", first_channel, count);
     if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->qmu);
+    std::lock_guard<std::mutex> lk(p->stores.qmu);
     std::memcpy(host_masks_out, p->hmask.data() + first_channel, count * sizeof(uint32_t));
     return DSPFX_OK;
 }
@@ -611,11 +494,11 @@ extern "C" int dspfx_strips_present(dspfx_strips *p, uint32_t *host_masks_out, u
 extern "C" int dspfx_strips_run(dspfx_strips *p, const float *in, float *out, uint32_t n_frames, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return fail(p, DSPFX_ERR_INVALID, "strips run: in, out or n_frames");
+    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "strips run: in, out or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    ST_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
-    ST_HIP(order(p, s), "stream order");
-    ST_HIP(apply_stores(p, s), "slider store");
+    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
+    BANK_HIP_WHY(order(p, s), "stream order");
+    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "slider store");
     StripArgs a;
     a.in = in;
     a.out = out;
@@ -630,7 +513,7 @@ extern "C" int dspfx_strips_run(dspfx_strips *p, const float *in, float *out, ui
     a.div = p->div;
     // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
     const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
-    ST_HIP(launch(p->KB, vec, a, s), "strips_run");
+    BANK_HIP_WHY(launch(p->KB, vec, a, s), "strips_run");
     return DSPFX_OK;
 }
 
@@ -638,7 +521,7 @@ extern "C" int dspfx_strips_reset(dspfx_strips *p) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     if (!p->used) return DSPFX_OK;               // no run yet: the state is as create left it, and a queued band store only zeroes
-    ST_HIP(hipSetDevice(p->desc.device), "hipSetDevice");
-    ST_HIP(hipMemsetAsync(p->state, 0, (size_t)p->KB * 4 * p->desc.n_channels * sizeof(float), p->last), "strips reset");
+    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
+    BANK_HIP_WHY(hipMemsetAsync(p->state, 0, (size_t)p->KB * 4 * p->desc.n_channels * sizeof(float), p->last), "strips reset");
     return DSPFX_OK;
 }
