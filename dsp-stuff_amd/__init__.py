@@ -87,6 +87,8 @@ EXPORTS = [
     "dspfx_strips_set_band", "dspfx_strips_reset", "dspfx_strips_present", "dspfx_strips_coeffs",
     "dspfx_mixmatrix_plan", "dspfx_mixmatrix_create", "dspfx_mixmatrix_destroy", "dspfx_mixmatrix_last_error", "dspfx_mixmatrix_run",
     "dspfx_mixmatrix_set_rows", "dspfx_mixmatrix_set_cols", "dspfx_mixmatrix_fill", "dspfx_mixmatrix_reset",
+    "dspfx_mixmatrix_set_pairs", "dspfx_mixmatrix_create_seats", "dspfx_mixmatrix_plan_seats", "dspfx_mixmatrix_assign",
+    "dspfx_mixmatrix_rooms", "dspfx_mixmatrix_seats", "dspfx_mixmatrix_occupancy", "dspfx_mixmatrix_reseat",
 ]
 COMM_ID_BYTES = 128
 
@@ -332,6 +334,16 @@ def lib():
     L.dspfx_mixmatrix_set_cols.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32, C.c_uint64, C.c_uint64]
     L.dspfx_mixmatrix_fill.argtypes = [vp, C.c_int64, C.c_uint32]
     L.dspfx_mixmatrix_reset.argtypes = [vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.dspfx_mixmatrix_set_pairs.argtypes = [vp, u32p, u32p, C.POINTER(C.c_float), C.c_uint64]
+    L.dspfx_mixmatrix_create_seats.argtypes = [C.POINTER(_MixMatrixDesc), u32p, C.POINTER(vp)]
+    L.dspfx_mixmatrix_plan_seats.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, u32p, u32p, u32p,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.dspfx_mixmatrix_assign.argtypes = [vp, u32p, C.c_uint64, C.c_uint64, C.c_uint32]
+    L.dspfx_mixmatrix_rooms.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_mixmatrix_seats.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_mixmatrix_occupancy.argtypes = [vp, u32p]
+    L.dspfx_mixmatrix_reseat.argtypes = [u32p, u32p, u32p, C.c_uint32, C.c_uint64, u32p, C.c_uint64, C.c_uint64]
     _lib = L
     return L
 
@@ -1540,21 +1552,56 @@ class ChannelStrips(_Bank):
 
 
 
-def mixmatrix_plan(channels: int, group_start=None, group_size=None, tile_channels: int = 0):
+def _seat_counts(seats, groups: int) -> np.ndarray:
+    """a scalar or [G] -> uint32[G]"""
+    v = np.asarray(seats)
+    if v.dtype.kind not in "iu" or v.size not in (1, groups) or (v.size and (v.min() < 0 or v.max() > 0xFFFFFFFF)):
+        raise DspfxError(-1, "seats is one count, or one per room")
+    return np.ascontiguousarray(np.broadcast_to(v.reshape(-1), (groups,)), np.uint32)
+
+
+def mixmatrix_plan(channels: int, group_start=None, group_size=None, tile_channels: int = 0, seats=None):
     """dspfx_mixmatrix_plan, a pure host function (no GPU): checks the room table as MixMatrix does (DspfxError with the reason
     when it is bad: an empty room, one above MIXMATRIX_MAX_ROOM, a table that does not cover the channels) and ->
     (count uint32[G], edge uint32[G], offset uint64[G], total_bytes): per room its members, the edge of its padded table (the
-    count rounded up to 32) and the element offset of that table, and the bytes of all the tables."""
+    count rounded up to 32) and the element offset of that table, and the bytes of all the tables.  seats (a scalar or [G]):
+    dspfx_mixmatrix_plan_seats, the plan of a seated bank, whose edges are the seats rounded up to 32."""
     L = lib()
     t = _group_table(int(channels), group_start, group_size)
     G = len(t) - 1
     count, edge, offset = np.zeros(G, np.uint32), np.zeros(G, np.uint32), np.zeros(G, np.uint64)
     total = C.c_uint64(0)
     u32 = C.POINTER(C.c_uint32)
-    rc = L.dspfx_mixmatrix_plan(t.ctypes.data_as(C.POINTER(C.c_uint64)), G, int(channels), int(tile_channels), count.ctypes.data_as(u32),
-                                edge.ctypes.data_as(u32), offset.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    if seats is None:
+        rc = L.dspfx_mixmatrix_plan(t.ctypes.data_as(C.POINTER(C.c_uint64)), G, int(channels), int(tile_channels), count.ctypes.data_as(u32),
+                                    edge.ctypes.data_as(u32), offset.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    else:
+        s = _seat_counts(seats, G)
+        rc = L.dspfx_mixmatrix_plan_seats(t.ctypes.data_as(C.POINTER(C.c_uint64)), G, int(channels), int(tile_channels), s.ctypes.data_as(u32),
+                                          count.ctypes.data_as(u32), edge.ctypes.data_as(u32), offset.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          C.byref(total))
     _raise(L, "mixmatrix", rc)
     return count, edge, offset, int(total.value)
+
+
+def mixmatrix_reseat(room_of, seat_of, seats, ids, first_channel: int = 0):
+    """dspfx_mixmatrix_reseat, a pure host function (no GPU): MixMatrix.assign's seating rule on host arrays.  room_of, seat_of:
+    uint32[N], a room (NO_ROOM: none) and a seat per channel; seats: a scalar or [G], rounded up to 32.  The channels from
+    first_channel whose id is not their room leave, then those that enter a room do so in ascending channel order, each into the
+    lowest free seat.  -> (room_of, seat_of) after the call, as new arrays; a bad id, a bad range or a room over capacity is a
+    DspfxError with the reason, as assign's."""
+    L = lib()
+    r, q = np.array(room_of, np.uint32).reshape(-1), np.array(seat_of, np.uint32).reshape(-1)
+    s = np.atleast_1d(np.asarray(seats)).reshape(-1)
+    if len(r) != len(q) or s.dtype.kind not in "iu" or (s.size and (s.min() < 0 or s.max() > 0xFFFFFFFF)):
+        raise DspfxError(-1, "room_of and seat_of are [N], seats is [G]")
+    s = np.ascontiguousarray(s, np.uint32)
+    v = _room_ids(ids)
+    u32 = C.POINTER(C.c_uint32)
+    rc = L.dspfx_mixmatrix_reseat(r.ctypes.data_as(u32), q.ctypes.data_as(u32), s.ctypes.data_as(u32), len(s), len(r), v.ctypes.data_as(u32),
+                                  int(first_channel), len(v))
+    _raise(L, "mixmatrix", rc)
+    return r, q
 
 
 class MixMatrix(_Bank):
@@ -1563,14 +1610,19 @@ class MixMatrix(_Bank):
     w = the listener's non-zero entries (a row of zeros gives +0.0; normalise=False writes the raw sum), for a device block in the
     layout of `tile_channels` (as Engine's).  Rooms as MixGroups takes them: group_start (G + 1 indices) or group_size; every
     room has 1 .. MIXMATRIX_MAX_ROOM members.  A fresh bank holds mix-minus (1.0 off the diagonal), which is MixGroups.returns
-    without faders.  Between ChannelStrips.run and the listeners' Resampler, as an alternative to returns.  The rooms are fixed: a
-    host that reseats channels with MixGroups.assign makes a new MixMatrix for the new table.  Asynchronous on `stream`."""
+    without faders.  Between ChannelStrips.run and the listeners' Resampler, as an alternative to returns.  Asynchronous on
+    `stream`.
+    seats=None: the rooms are fixed.  seats (a scalar or [G], each at least the room's members, rounded up to 32, at most
+    MIXMATRIX_MAX_ROOM): a SEATED bank (dspfx_mixmatrix_create_seats), whose room r owns seats[r] seats and an S_r x S_r table
+    that never moves; a channel holds one seat of one room, or none, and `assign` reseats channels live as MixGroups.assign does:
+    no table is rebuilt and those who stay keep their gains.  Rows and columns of a seated bank are S_r long and indexed by seat;
+    set_pairs addresses gains by channel number on either kind."""
 
     _C = "mixmatrix"
     _WHY = True
 
     def __init__(self, channels: int, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE,
-                 normalise: bool = True, device: int = 0, abi_version: int = ABI_VERSION):
+                 normalise: bool = True, device: int = 0, abi_version: int = ABI_VERSION, seats=None):
         self.L = lib()
         self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
         self.max_frames, self.normalise = int(max_frames), bool(normalise)
@@ -1579,7 +1631,58 @@ class MixMatrix(_Bank):
         d = _MixMatrixDesc(int(abi_version) & 0xFFFFFFFF, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF,
                            self.tile_channels & 0xFFFFFFFF, self.groups, int(self.normalise),
                            self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
-        self._create(d)  # the table is copied before this returns
+        self.seats = None
+        if seats is None:
+            self._create(d)  # the table is copied before this returns
+            return
+        s = _seat_counts(seats, self.groups)
+        self.h = C.c_void_p()
+        rc = self.L.dspfx_mixmatrix_create_seats(C.byref(d), s.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            _raise(self.L, "mixmatrix", rc)
+        self.seats = (s + 31) // 32 * 32                  # uint32[G]: S_r
+
+    def assign(self, ids, first_channel: int = 0, preset: int = MIXMATRIX_MIX_MINUS):
+        """A seated bank: seat channels [first_channel, first_channel + len(ids)) in the rooms `ids` (an int for one channel, or
+        any integer sequence, numpy array or torch tensor; each in [0, groups) or NO_ROOM).  A channel whose id is its room keeps
+        its seat and its gains; the others leave (their seat's row and column become +0.0), then enter in ascending channel order,
+        each into the lowest free seat of its new room, wired by `preset`: MIXMATRIX_MIX_MINUS (1.0 to and from every other
+        taken seat) or MIXMATRIX_ZERO (silent both ways: the host stores its own).  A bad id, a range past the channels or a room
+        over capacity stores nothing.  Any thread, while runs are in flight; never waits for a run; holds, whole, for the runs
+        submitted after it returns."""
+        v = _room_ids(ids)
+        self._chk(self.L.dspfx_mixmatrix_assign(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), len(v),
+                                                int(preset) & 0xFFFFFFFF))
+
+    def room_of(self) -> np.ndarray:
+        """uint32[channels]: the room of every channel (NO_ROOM: none) by every call made so far."""
+        v = np.zeros(self.channels, np.uint32)
+        self._chk(self.L.dspfx_mixmatrix_rooms(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), 0, len(v)))
+        return v
+
+    def seat_of(self) -> np.ndarray:
+        """uint32[channels]: the seat of every channel in its room (0xFFFFFFFF: in no room) by every call made so far."""
+        v = np.zeros(self.channels, np.uint32)
+        self._chk(self.L.dspfx_mixmatrix_seats(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), 0, len(v)))
+        return v
+
+    def occupancy(self) -> np.ndarray:
+        """uint32[G]: the taken seats of every room."""
+        v = np.zeros(self.groups, np.uint32)
+        self._chk(self.L.dspfx_mixmatrix_occupancy(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return v
+
+    def set_pairs(self, listeners, sources, gains):
+        """M[listeners[i]][sources[i]] = gains[i], by CHANNEL number, in order (a later duplicate wins); gains may be one value for
+        all pairs.  Each pair must be two channels of one room, or nothing is stored.  Queued like every other store."""
+        u32 = C.POINTER(C.c_uint32)
+        l, s = _room_ids(listeners), _room_ids(sources)
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(gains, np.float32).reshape(-1), (len(l),)) if np.size(gains) == 1 else gains,
+                                 np.float32).reshape(-1)
+        if not len(l) == len(s) == len(g):
+            raise DspfxError(-1, "listeners, sources and gains are equally long")
+        self._chk(self.L.dspfx_mixmatrix_set_pairs(self.h, l.ctypes.data_as(u32), s.ctypes.data_as(u32), g.ctypes.data_as(C.POINTER(C.c_float)), len(l)))
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every room's matrix -> `out`, a device block in the same layout (made when not given).
@@ -1603,7 +1706,8 @@ class MixMatrix(_Bank):
     def set_rows(self, values, first_channel: int, count: Optional[int] = None):
         """What listeners first_channel .. hear: values[count][n_r], row i = the gains of listener first_channel + i on the n_r
         sources of its room (one row may be given as a vector).  All listeners must be in one room.  Any thread; never waits for a
-        run; applies, whole, to the runs submitted after it."""
+        run; applies, whole, to the runs submitted after it.  On a seated bank a row is seats[r] values indexed by SEAT (seat_of()
+        tells who sits where), the listeners must share a room by the seating so far, and values at empty seats are stored as +0.0."""
         self._lines(self.L.dspfx_mixmatrix_set_rows, values, first_channel, count)
 
     def set_cols(self, values, first_channel: int, count: Optional[int] = None):

@@ -30,6 +30,11 @@
 // staged in page-locked memory, queued under the queue's own lock, and put on the next run's stream ahead of its kernel in the order they
 // were made: a copy, a scatter into the source-major table, and a recount of w and d for the listeners touched -- d is computed on the
 // device with dspfx_link_divisor's own f32 expression, so no store waits for the device.
+//
+// Seated banks (dspfx_mixmatrix_create_seats; the second group of kernels): a room owns S_r seats and an S_r x S_r table that never
+// moves, a channel holds one seat of one room or none, and dspfx_mixmatrix_assign reseats channels live through the same queue: one
+// row and one column per mover, never the table.  The seating rule is reseat() below, once, for the bank and for
+// dspfx_mixmatrix_reseat.  A bank made by dspfx_mixmatrix_create runs what it always ran.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +43,8 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/dspfx.h"
@@ -171,6 +178,200 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
     }
 }
 
+// ---- seated banks (dspfx_mixmatrix_create_seats) --------------------------------------------------------------------------------
+// A room of a seated bank is S_r seats (a multiple of 32, so its table has no padding): Room.n = S_r and Room.c0 = the room's first
+// entry of seat_chan, which holds the channel in every seat (NONE: the seat is empty).  An empty seat's row and column are +0.0 in
+// the table -- every store keeps that -- so a room computes what the kernel above computes for S_r contiguous members of which the
+// absent ones carry +0.0: the same chain, term for term.
+constexpr uint32_t NONE = DSPFX_MIXMATRIX_NO_ROOM;
+
+struct SeatedArgs {
+    RunArgs r;
+    const uint32_t *__restrict__ seat_chan;
+};
+
+// mixmatrix_run with two addresses changed: the source in seat s is x[..][seat_chan[s]], and listener seat l's row goes to
+// out[..][seat_chan[l]].  An empty seat is not loaded (+0.0 in LDS) and not stored.  The seat index of a chunk is fetched one chunk
+// ahead of the chunk's own loads, so the samples' addresses never wait for it
+__global__ __launch_bounds__(WG, 3) void mixmatrix_run_seated(SeatedArgs sa) {
+    __shared__ float xs[FT * XS];                        // [frame][source of the chunk]
+    const RunArgs &a = sa.r;
+    const Item it = a.items[blockIdx.x];
+    const Room rm = a.rooms[it.room];
+    const uint32_t P = rm.n;
+    const uint32_t *sc = sa.seat_chan + rm.c0;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t r = lane & 31u, h = lane >> 5;        // MFMA operand maps: A[i = r][k = h], B[k = h][j = r]
+    const uint32_t lt = it.l0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) * 32u;     // the wave's listener tile (uniform)
+    const bool active = lt < P;                          // wave-uniform; an idle wave still stages its share of x
+    const uint32_t ss = tid & 31u, sf = tid >> 5;        // staging: seat ss of the chunk, frames sf + 8 i
+    const size_t rs = a.W ? a.W : a.N;
+    const uint32_t f0 = blockIdx.y * FT;
+    f32x16 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    float st[16], bn[KC / 2];
+    const uint32_t left = a.nf - f0, nst = left > sf ? (left - sf + 7u) / 8u : 0u;
+    const float *tabr = a.tab + rm.off;
+    const uint32_t bcol = (active ? lt + r : 0u) + h * P;
+    uint32_t cn = sc[ss];                                // who sits in this thread's seat of the next chunk to load (P >= 32)
+    auto gload = [&](uint32_t k0) {
+        const uint32_t ch = cn;
+        if (k0 + KC < P) cn = sc[k0 + KC + ss];
+        const bool taken = ch != NONE;
+        const float *p = a.in + lay(0, taken ? ch : 0u, a.nf, a.N, a.W) + (size_t)(f0 + sf) * rs;
+        const uint32_t cnt = taken ? nst : 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) {
+            st[i] = i < cnt ? *p : 0.0f;
+            p += 8u * rs;
+        }
+        if (active) {
+            const uint32_t o = k0 * P + bcol;
+#pragma unroll
+            for (uint32_t j = 0; j < KC / 2; ++j) bn[j] = tabr[o + 2u * j * P];
+        }
+    };
+    gload(0);
+#pragma unroll 1
+    for (uint32_t k0 = 0; k0 < P; k0 += KC) {
+        __syncthreads();                                 // the chunk before is read
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) xs[(sf + 8u * i) * XS + ss] = st[i];
+        float b[KC / 2];
+#pragma unroll
+        for (uint32_t j = 0; j < KC / 2; ++j) b[j] = bn[j];
+        __syncthreads();
+        if (k0 + KC < P) gload(k0 + KC);
+        if (active) {
+            const float *xr = xs + r * XS + h;
+            float an[4], ac[4];
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t) an[t] = xr[t * 32u * XS];
+#pragma unroll
+            for (uint32_t j = 0; j < KC / 2; ++j) {
+#pragma unroll
+                for (uint32_t t = 0; t < 4; ++t) ac[t] = an[t];
+                if (j + 1 < KC / 2) {
+#pragma unroll
+                    for (uint32_t t = 0; t < 4; ++t) an[t] = xr[t * 32u * XS + 2u * (j + 1)];
+                }
+#pragma unroll
+                for (uint32_t t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[t], b[j], acc[t], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    // C/D: column = r (the listener's seat), row = (reg & 3) + 8 (reg >> 2) + 4 h (the frame of the tile)
+    const uint32_t c = active ? sc[lt + r] : NONE;
+    if (c != NONE) {
+        const float d = a.div[c];
+        float *po = a.out + lay(0, c, a.nf, a.N, a.W);
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t)
+#pragma unroll
+            for (uint32_t i = 0; i < 16; ++i) {
+                const uint32_t f = f0 + t * 32u + (i & 3u) + 8u * (i >> 2) + 4u * h;
+                if (f < a.nf) {
+                    float v = acc[t][i];
+                    if (d == 0.0f) v = 0.0f;
+                    else if (a.normalise) v = __fdiv_rn(v, d);
+                    __builtin_nontemporal_store(v, po + (size_t)f * rs);
+                }
+                if ((i & 3u) == 3u) __builtin_amdgcn_sched_barrier(0);
+            }
+    }
+}
+
+// the channels in no room read +0.0 in every frame; launched ahead of mixmatrix_run_seated while the bank has any
+__global__ __launch_bounds__(WG) void mixmatrix_zero_roomless(float *__restrict__ out, const uint32_t *__restrict__ room_of, uint32_t N, uint32_t W, uint32_t nf) {
+    const uint32_t c = blockIdx.x * WG + threadIdx.x;
+    if (c >= N || room_of[c] != NONE) return;
+    float *po = out + lay(0, c, nf, N, W);
+    const size_t rs = W ? W : N;
+    for (uint32_t f = 0; f < nf; ++f) po[(size_t)f * rs] = 0.0f;
+}
+
+// a preset into the tables of rooms [first_room, first_room + gridDim.x) of a seated bank: mix-minus is 1.0 between two different
+// TAKEN seats
+__global__ __launch_bounds__(WG) void mixmatrix_fill_seated(float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
+                                                            uint32_t first_room, uint32_t preset) {
+    const Room rm = rooms[first_room + blockIdx.x];
+    const uint32_t S = rm.n;
+    const uint32_t *sc = seat_chan + rm.c0;
+    float *t = tab + rm.off;
+    for (uint32_t e = threadIdx.x; e < S * S; e += WG) {
+        const uint32_t s = e / S, l = e - s * S;
+        t[e] = (preset == DSPFX_MIXMATRIX_MIX_MINUS && s != l && sc[s] != NONE && sc[l] != NONE) ? 1.0f : 0.0f;
+    }
+}
+
+// staged lines of a seated room: words = [count] seats, then [count][S] values; line i belongs to seat words[i], laid as
+// mixmatrix_store lays it.  A value at an empty seat is stored as +0.0
+__global__ __launch_bounds__(WG) void mixmatrix_store_seated(float *__restrict__ tab, const uint32_t *__restrict__ words, const uint32_t *__restrict__ seat_chan,
+                                                             Room rm, uint32_t count, uint32_t cols) {
+    const uint32_t e = blockIdx.x * WG + threadIdx.x, S = rm.n;
+    if (e >= count * S) return;
+    const uint32_t i = e / S, j = e - i * S, q = words[i];
+    const float v = seat_chan[rm.c0 + j] != NONE ? __uint_as_float(words[count + e]) : 0.0f;
+    float *t = tab + rm.off;
+    if (cols) t[q * S + j] = v;
+    else t[j * S + q] = v;
+}
+
+// words = [n] (seat_chan index, channel or NONE) pairs: the seats an assign changed, each with who sits there after the call
+__global__ __launch_bounds__(WG) void mixmatrix_seat_set(uint32_t *__restrict__ dst, const uint32_t *__restrict__ words, uint32_t n) {
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i < n) dst[words[2u * i]] = words[2u * i + 1u];
+}
+
+// words = [gridDim.x] (room, seat | preset << 31) pairs: the seats an assign emptied (preset bit clear) or gave to a newcomer.  The
+// seat's row and column: mix-minus (bit set) is 1.0 towards every other taken seat by the seating AFTER the call (seat_chan already
+// holds it), everything else +0.0.  Two changed seats of one room write the entries between them twice, with the same value
+__global__ __launch_bounds__(WG) void mixmatrix_seat_lines(float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
+                                                           const uint32_t *__restrict__ words) {
+    const Room rm = rooms[words[2u * blockIdx.x]];
+    const uint32_t w = words[2u * blockIdx.x + 1u], q = w & 0x7FFFFFFFu, S = rm.n;
+    float *t = tab + rm.off;
+    for (uint32_t j = threadIdx.x; j < S; j += WG) {
+        const float v = ((w >> 31) && j != q && seat_chan[rm.c0 + j] != NONE) ? 1.0f : 0.0f;
+        t[q * S + j] = v;
+        t[j * S + q] = v;
+    }
+}
+
+// words = [n] (room, listener index << 16 | source index, gain) triples into the source-major tables (indices are seats in a seated
+// bank and room-local members otherwise); the host has dropped all but the last of equal pairs
+__global__ __launch_bounds__(WG) void mixmatrix_pairs(float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ words, uint32_t n) {
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    const Room rm = rooms[words[3u * i]];
+    const uint32_t ls = words[3u * i + 1u], P = edge(rm.n);
+    tab[rm.off + (size_t)(ls & 0xFFFFu) * P + (ls >> 16)] = __uint_as_float(words[3u * i + 2u]);
+}
+
+// w and d of every taken seat's listener of the rooms list[blockIdx.x] (list = nullptr: first_room + blockIdx.x), as
+// mixmatrix_recount counts them
+__global__ __launch_bounds__(WG) void mixmatrix_recount_seated(const float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
+                                                               float *__restrict__ div, const uint32_t *__restrict__ list, uint32_t first_room) {
+    const Room rm = rooms[list ? list[blockIdx.x] : first_room + blockIdx.x];
+    const uint32_t S = rm.n, l = blockIdx.y * WG + threadIdx.x;
+    if (l >= S) return;
+    const uint32_t c = seat_chan[rm.c0 + l];
+    if (c == NONE) return;
+    const float *t = tab + rm.off + l;
+    uint32_t w = 0;
+    for (uint32_t s = 0; s < S; ++s) w += t[(size_t)s * S] != 0.0f;
+    float d = 0.0f;
+    if (w) {
+        d = 0.0001f;
+        for (uint32_t k = 0; k < w; ++k) d = d + 1.0f;
+    }
+    div[c] = d;
+}
+
 // a preset into the tables of rooms [first_room, first_room + gridDim.x): one workgroup per room, the padding zero
 __global__ __launch_bounds__(WG) void mixmatrix_fill(float *__restrict__ tab, const Room *__restrict__ rooms, uint32_t first_room, uint32_t preset) {
     const Room rm = rooms[first_room + blockIdx.x];
@@ -217,13 +418,145 @@ __global__ __launch_bounds__(WG) void mixmatrix_recount(const float *__restrict_
 thread_local std::string g_err;        // the reason of the last failed create or plan on this thread
 
 // a store's vals: [count][n]; a fill has none
+// ... of a seated bank: [count] seats, then [count][S_r] values (the buffer is 4-byte words: integers travel as their bits).  An
+// assign's words: [n_seats] (seat_chan index, channel) pairs, [n_chans] (channel, room) pairs, [n_lines] (room, seat | preset << 31)
+// pairs, [n_rooms] rooms to recount.  Pairs: [n_lines] (room, listener << 16 | source, gain) triples, [n_rooms] rooms
 struct StoreFields {
-    int kind = 0;                // 0: rows, 1: columns, 2: fill
+    int kind = 0;                // 0: rows, 1: columns, 2: fill, 3: an assign, 4: pairs
     uint32_t room = 0, l0 = 0, count = 0;        // rows / columns: room-local first index and count; fill: rooms [room, room + count)
     uint32_t preset = 0;
+    size_t n_seats = 0, n_chans = 0, n_lines = 0, n_rooms = 0;
+    uint64_t roomless = 0;       // an assign: the channels in no room once it is applied
 };
 typedef StoreQueue<StoreFields> Stores;
 typedef Stores::Store Store;
+
+// one channel of an assign that changes rooms: from seat q0 of room r0 to seat q1 of room r1 (NONE: no room, no seat)
+struct Move {
+    uint32_t c, r0, q0, r1, q1;
+};
+
+// host tables of a seating: who sits where.  S[g] = the seats of room g (a multiple of 32), off[g] = its first entry of seat_chan
+struct Seats {
+    uint32_t *room_of, *seat_of, *seat_chan, *occ;
+    const uint32_t *S, *off;
+    uint32_t G;
+    uint64_t N;
+};
+
+// THE SEATING RULE (include/dspfx.h, dspfx_mixmatrix_assign), for the bank and for dspfx_mixmatrix_reseat.  The range, every id and
+// every room's capacity are checked before anything changes.  Then the named channels whose id is not their room leave (their seat
+// is free), and those that enter a room do so in ascending channel order, each into the lowest free seat.  -> the moves made.
+// O(count + the seats of the rooms entered)
+int reseat(const Seats &t, const uint32_t *ids, uint64_t first, uint64_t count, std::string &why, std::vector<Move> &moves) {
+    char buf[192];
+    if (!ids || count == 0) {
+        why = "mixmatrix assign: no ids";
+        return DSPFX_ERR_INVALID;
+    }
+    if (first >= t.N || count > t.N - first) {
+        std::snprintf(buf, sizeof buf, "mixmatrix assign: channels [%llu, %llu + %llu) are not inside the bank's %llu", (unsigned long long)first,
+                      (unsigned long long)first, (unsigned long long)count, (unsigned long long)t.N);
+        why = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    std::unordered_map<uint32_t, int64_t> delta;         // per room touched: enters - leaves
+    size_t n_moves = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t g = ids[i], was = t.room_of[first + i];
+        if (g != NONE && g >= t.G) {
+            std::snprintf(buf, sizeof buf, "mixmatrix assign: channel %llu is given room %u, and there are %u rooms (or DSPFX_MIXMATRIX_NO_ROOM)",
+                          (unsigned long long)(first + i), g, t.G);
+            why = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        if (g == was) continue;
+        ++n_moves;
+        if (was != NONE) --delta[was];
+        if (g != NONE) ++delta[g];
+    }
+    uint32_t full = NONE;                                // the lowest room that would overflow
+    for (const auto &d : delta)
+        if ((int64_t)t.occ[d.first] + d.second > (int64_t)t.S[d.first] && d.first < full) full = d.first;
+    if (full != NONE) {
+        std::snprintf(buf, sizeof buf, "mixmatrix assign: room %u would hold %lld participants, and has %u seats (capacity)", full,
+                      (long long)((int64_t)t.occ[full] + delta[full]), t.S[full]);
+        why = buf;
+        return DSPFX_ERR_INVALID;
+    }
+    moves.clear();
+    moves.reserve(n_moves);
+    for (uint64_t i = 0; i < count; ++i) {               // the leaves
+        const uint32_t c = (uint32_t)(first + i), was = t.room_of[c];
+        if (ids[i] == was) continue;
+        moves.push_back(Move{c, was, t.seat_of[c], ids[i], NONE});
+        if (was != NONE) {
+            t.seat_chan[t.off[was] + t.seat_of[c]] = NONE;
+            --t.occ[was];
+        }
+        t.room_of[c] = NONE;
+        t.seat_of[c] = NONE;
+    }
+    std::unordered_map<uint32_t, uint32_t> from;         // per room entered: no seat below this one is free
+    for (Move &m : moves) {                              // the enters, in ascending channel order
+        if (m.r1 == NONE) continue;
+        uint32_t &q = from[m.r1];
+        while (t.seat_chan[t.off[m.r1] + q] != NONE) ++q;        // (the capacity check has shown there is one)
+        m.q1 = q;
+        t.seat_chan[t.off[m.r1] + q] = m.c;
+        ++t.occ[m.r1];
+        t.room_of[m.c] = m.r1;
+        t.seat_of[m.c] = q;
+    }
+    return DSPFX_OK;
+}
+
+// takes the moves back, for an assign that could not be queued
+void unseat(const Seats &t, const std::vector<Move> &moves) {
+    for (const Move &m : moves)
+        if (m.r1 != NONE) {
+            t.seat_chan[t.off[m.r1] + m.q1] = NONE;
+            --t.occ[m.r1];
+        }
+    for (const Move &m : moves) {
+        if (m.r0 != NONE) {
+            t.seat_chan[t.off[m.r0] + m.q0] = m.c;
+            ++t.occ[m.r0];
+        }
+        t.room_of[m.c] = m.r0;
+        t.seat_of[m.c] = m.q0;
+    }
+}
+
+// seats[g] rounded up to 32 into S and the rooms' first seat_chan entries into off; members = nullptr: no lower limit
+int check_seats(const char *what, const uint32_t *seats, const uint32_t *members, uint32_t G, std::vector<uint32_t> &S, std::vector<uint32_t> &off,
+                std::string &why) {
+    char buf[192];
+    if (!seats) {
+        why = std::string(what) + ": no seats";
+        return DSPFX_ERR_INVALID;
+    }
+    S.resize(G);
+    off.resize(G);
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint32_t n = members ? members[g] : 1u;
+        if (seats[g] < n || seats[g] > MAXN) {
+            std::snprintf(buf, sizeof buf, "%s: room %u is given %u seats, and it has %u members (a room has at most DSPFX_MIXMATRIX_MAX_ROOM = %u seats)",
+                          what, g, seats[g], members ? n : 0u, MAXN);
+            why = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        S[g] = edge(seats[g]);
+        off[g] = (uint32_t)total;
+        total += S[g];
+        if (total > 0xFFFFFF00ull) {
+            why = std::string(what) + ": more than 2^32 - 256 seats";
+            return DSPFX_ERR_INVALID;
+        }
+    }
+    return DSPFX_OK;
+}
 
 }  // namespace
 
@@ -238,16 +571,26 @@ struct dspfx_mixmatrix : BankError {
     Item *items = nullptr;
     uint32_t *room_of = nullptr;
     uint32_t n_items = 0, maxn = 0;
+    size_t stage_words = 0;                      // the size of `stage`; longer word lists go through it in slices
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
+    // a seated bank (dspfx_mixmatrix_create_seats): Room.n is the room's seats and Room.c0 its first entry of seat_chan.  The host
+    // tables hold the seating after every assign made so far; the device ones (room_of, seat_chan) what the runs drained so far see
+    bool seated = false;
+    std::mutex smu;                              // the host tables, held from a store's checks to its push (smu, then the queue's lock)
+    std::vector<uint32_t> hroom_of, hseat_of, hseat_chan, occ, hS, hoff;
+    uint64_t hroomless = 0;                      // channels in no room (smu)
+    uint64_t roomless = 0;                       // ... by the assigns drained so far (mu)
+    uint32_t *seat_chan = nullptr;
+    Seats seats() { return Seats{hroom_of.data(), hseat_of.data(), hseat_chan.data(), occ.data(), hS.data(), hoff.data(), desc.n_groups, desc.n_channels}; }
 };
 
 namespace {
 
 void release(dspfx_mixmatrix *p) {
     (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->tab, (void *)p->div, (void *)p->stage, (void *)p->rooms, (void *)p->items, (void *)p->room_of})
+    for (void *d : {(void *)p->tab, (void *)p->div, (void *)p->stage, (void *)p->rooms, (void *)p->items, (void *)p->room_of, (void *)p->seat_chan})
         if (d) (void)hipFree(d);
     p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
@@ -259,7 +602,36 @@ hipError_t recount(dspfx_mixmatrix *p, uint32_t first, uint32_t count, hipStream
     return hipGetLastError();
 }
 
+// n records of `rec` words at src (page-locked) through `stage`, a slice at a time: launch(the slice on the device, its records)
+template <class F>
+hipError_t sliced(dspfx_mixmatrix *p, const uint32_t *src, size_t n, uint32_t rec, hipStream_t s, F launch) {
+    const size_t per = p->stage_words / rec;
+    for (size_t i = 0; i < n; i += per) {
+        const size_t k = std::min(per, n - i);
+        hipError_t err = hipMemcpyAsync(p->stage, src + i * rec, k * rec * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        if (err != hipSuccess) return err;
+        launch((const uint32_t *)p->stage, (uint32_t)k);
+        err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+// a seated bank: the divisors of every listener of the n rooms listed at src (page-locked)
+hipError_t recount_rooms(dspfx_mixmatrix *p, const uint32_t *src, size_t n, hipStream_t s) {
+    return sliced(p, src, n, 1, s, [&](const uint32_t *w, uint32_t k) {
+        mixmatrix_recount_seated<<<dim3(k, (p->maxn + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, w, 0);
+    });
+}
+
 hipError_t fill_rooms(dspfx_mixmatrix *p, uint32_t first_room, uint32_t count, uint32_t preset, hipStream_t s) {
+    if (p->seated) {
+        mixmatrix_fill_seated<<<count, WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, first_room, preset);
+        hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+        mixmatrix_recount_seated<<<dim3(count, (p->maxn + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, nullptr, first_room);
+        return hipGetLastError();
+    }
     mixmatrix_fill<<<count, WG, 0, s>>>(p->tab, p->rooms, first_room, preset);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
@@ -270,7 +642,46 @@ hipError_t fill_rooms(dspfx_mixmatrix *p, uint32_t first_room, uint32_t count, u
 // one store onto the stream: a fill, or the values into `stage`, the scatter into the table and the recount
 hipError_t apply_store(dspfx_mixmatrix *p, const Store &st, hipStream_t s) {
     if (st.kind == 2) return fill_rooms(p, st.room, st.count, st.preset, s);
+    const uint32_t *words = (const uint32_t *)st.vals;
+    if (st.kind == 3) {                          // an assign: the seats, the rooms of the channels, the lines, the divisors -- in that order
+        hipError_t err = sliced(p, words, st.n_seats, 2, s, [&](const uint32_t *w, uint32_t k) {
+            mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->seat_chan, w, k);
+        });
+        if (err != hipSuccess) return err;
+        words += 2 * st.n_seats;
+        err = sliced(p, words, st.n_chans, 2, s, [&](const uint32_t *w, uint32_t k) {
+            mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->room_of, w, k);
+        });
+        if (err != hipSuccess) return err;
+        words += 2 * st.n_chans;
+        err = sliced(p, words, st.n_lines, 2, s, [&](const uint32_t *w, uint32_t k) {
+            mixmatrix_seat_lines<<<k, WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, w);
+        });
+        if (err != hipSuccess) return err;
+        p->roomless = st.roomless;
+        return recount_rooms(p, words + 2 * st.n_lines, st.n_rooms, s);
+    }
+    if (st.kind == 4) {
+        hipError_t err = sliced(p, words, st.n_lines, 3, s, [&](const uint32_t *w, uint32_t k) {
+            mixmatrix_pairs<<<(k + WG - 1) / WG, WG, 0, s>>>(p->tab, p->rooms, w, k);
+        });
+        if (err != hipSuccess) return err;
+        words += 3 * st.n_lines;
+        if (p->seated) return recount_rooms(p, words, st.n_rooms, s);
+        for (size_t i = 0; i < st.n_rooms && err == hipSuccess; ++i) err = recount(p, p->hrooms[words[i]].c0, p->hrooms[words[i]].n, s);
+        return err;
+    }
     const Room &rm = p->hrooms[st.room];
+    if (p->seated) {
+        const size_t n = (size_t)st.count * (rm.n + 1);
+        hipError_t err = hipMemcpyAsync(p->stage, st.vals, n * sizeof(float), hipMemcpyHostToDevice, s);
+        if (err != hipSuccess) return err;
+        mixmatrix_store_seated<<<(st.count * rm.n + WG - 1) / WG, WG, 0, s>>>(p->tab, (const uint32_t *)p->stage, p->seat_chan, rm, st.count, (uint32_t)st.kind);
+        err = hipGetLastError();
+        if (err != hipSuccess) return err;
+        mixmatrix_recount_seated<<<dim3(1, (rm.n + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, nullptr, st.room);
+        return hipGetLastError();
+    }
     const uint32_t cells = st.count * rm.n;
     hipError_t err = hipMemcpyAsync(p->stage, st.vals, (size_t)cells * sizeof(float), hipMemcpyHostToDevice, s);
     if (err != hipSuccess) return err;
@@ -291,7 +702,37 @@ int store_lines(dspfx_mixmatrix *p, int kind, const float *vals, uint32_t row_le
     }
     std::string why;                             // (a range that begins at N is in no room: not even an empty one is inside)
     if (check_range("mixmatrix", what, first, count, p->desc.n_channels, why, false) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, why.c_str());
-    const uint32_t room = (uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), first) - p->gs.begin()) - 1;
+    if (p->seated) {
+        // lines by seat: the channels must share a room by the seating so far (any seats of it), and a line is S_r values
+        std::lock_guard<std::mutex> lk(p->smu);
+        const uint32_t room = p->hroom_of[first];
+        for (uint64_t c = first; c < first + count || c == first; ++c)
+            if (p->hroom_of[c] != room || room == NONE) {
+                std::snprintf(buf, sizeof buf, "mixmatrix %s: channels [%llu, %llu + %llu) are not in one room by the seating (channel %llu is not in the room of the first)",
+                              what, (unsigned long long)first, (unsigned long long)first, (unsigned long long)count, (unsigned long long)c);
+                return p->fail(DSPFX_ERR_INVALID, buf);
+            }
+        const uint32_t S = p->hS[room];
+        if (row_len != S) {
+            std::snprintf(buf, sizeof buf, "mixmatrix %s: a row of %u values, and room %u has %u seats", what, row_len, room, S);
+            return p->fail(DSPFX_ERR_INVALID, buf);
+        }
+        if (count == 0) return DSPFX_OK;
+        Store st;
+        st.kind = kind;
+        st.room = room;
+        st.count = (uint32_t)count;
+        const size_t cells = (size_t)count * S;
+        if (!p->stores.staging(p->desc.device, count + cells, st)) {
+            std::snprintf(buf, sizeof buf, "mixmatrix %s: no page-locked memory for the staged values", what);
+            return p->fail(DSPFX_ERR_OOM, buf);
+        }
+        std::memcpy(st.vals, p->hseat_of.data() + first, count * sizeof(uint32_t));
+        std::memcpy(st.vals + count, vals, cells * sizeof(float));
+        p->stores.push(st);
+        return DSPFX_OK;
+    }
+    const uint32_t room =(uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), first) - p->gs.begin()) - 1;
     const Room &rm = p->hrooms[room];
     if (first + count > (uint64_t)rm.c0 + rm.n) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: channels [%llu, %llu + %llu) are not in one room (room %u is [%u, %u))", what,
@@ -339,7 +780,45 @@ extern "C" int dspfx_mixmatrix_plan(const uint64_t *group_start, uint32_t n_grou
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mixmatrix **out) {
+extern "C" int dspfx_mixmatrix_plan_seats(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats,
+                                          uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
+    g_err.clear();
+    const int rc = check_table("mixmatrix", group_start, n_groups, n_channels, tile_channels, MAXN, g_err);
+    if (rc != DSPFX_OK) return rc;
+    try {
+        std::vector<uint32_t> cnt(n_groups), S, off;
+        for (uint32_t g = 0; g < n_groups; ++g) cnt[g] = (uint32_t)(group_start[g + 1] - group_start[g]);
+        const int src = check_seats("mixmatrix", seats, cnt.data(), n_groups, S, off, g_err);
+        if (src != DSPFX_OK) return src;
+        uint64_t at = 0;
+        for (uint32_t g = 0; g < n_groups; ++g) {
+            if (count_out) count_out[g] = cnt[g];
+            if (edge_out) edge_out[g] = S[g];
+            if (offset_out) offset_out[g] = at;
+            at += (uint64_t)S[g] * S[g];
+        }
+        if (total_bytes_out) *total_bytes_out = at * sizeof(float);
+    } catch (const std::bad_alloc &) {
+        g_err = "mixmatrix: no host memory for the room tables";
+        return DSPFX_ERR_OOM;
+    }
+    return DSPFX_OK;
+}
+
+namespace {
+int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool seated, dspfx_mixmatrix **out);
+}
+
+extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mixmatrix **out) { return create_bank(desc, nullptr, false, out); }
+
+extern "C" int dspfx_mixmatrix_create_seats(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, dspfx_mixmatrix **out) {
+    return create_bank(desc, seats, true, out);
+}
+
+namespace {
+
+// seats: a seated bank's seats per room (host, [n_groups])
+int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool seated, dspfx_mixmatrix **out) {
     if (!desc || !out) {
         g_err = "mixmatrix: null argument";
         return DSPFX_ERR_INVALID;
@@ -358,14 +837,16 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
     }
     const uint32_t G = desc->n_groups, N = desc->n_channels;
     uint64_t total_bytes = 0;
-    std::vector<uint32_t> cnt, room_of;
+    std::vector<uint32_t> cnt, edges, room_of;
     std::vector<uint64_t> offs;
     std::vector<Item> items;
     dspfx_mixmatrix *p = nullptr;
     try {
         cnt.resize(G ? G : 1);
         offs.resize(G ? G : 1);
-        const int rc = dspfx_mixmatrix_plan(desc->group_start, G, N, desc->tile_channels, cnt.data(), nullptr, offs.data(), &total_bytes);
+        edges.resize(G ? G : 1);
+        const int rc = seated ? dspfx_mixmatrix_plan_seats(desc->group_start, G, N, desc->tile_channels, seats, cnt.data(), edges.data(), offs.data(), &total_bytes)
+                              : dspfx_mixmatrix_plan(desc->group_start, G, N, desc->tile_channels, cnt.data(), edges.data(), offs.data(), &total_bytes);
         if (rc != DSPFX_OK) return rc;
         if ((uint64_t)N * desc->max_frames > (1ull << 40)) {
             g_err = "mixmatrix: n_channels x max_frames is too large";
@@ -379,12 +860,32 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
         p->desc.group_start = nullptr;
         p->hrooms.resize(G);
         room_of.resize(N);
+        p->seated = seated;
+        uint32_t seat0 = 0;
         for (uint32_t g = 0; g < G; ++g) {
-            p->hrooms[g] = Room{offs[g], (uint32_t)p->gs[g], cnt[g]};
-            p->maxn = std::max(p->maxn, cnt[g]);
-            for (uint32_t l0 = 0; l0 < edge(cnt[g]); l0 += LT) items.push_back(Item{g, l0});
+            p->hrooms[g] = seated ? Room{offs[g], seat0, edges[g]} : Room{offs[g], (uint32_t)p->gs[g], cnt[g]};
+            p->maxn = std::max(p->maxn, p->hrooms[g].n);
+            for (uint32_t l0 = 0; l0 < edges[g]; l0 += LT) items.push_back(Item{g, l0});
             std::fill(room_of.begin() + p->gs[g], room_of.begin() + p->gs[g + 1], g);
+            seat0 += seated ? edges[g] : 0u;
         }
+        if (seated) {                                    // channel c0 + i of a room sits in its seat i
+            p->hroom_of = room_of;
+            p->hseat_of.resize(N);
+            p->hseat_chan.assign(seat0, NONE);
+            p->occ = cnt;
+            p->hS = edges;
+            p->hoff.resize(G);
+            for (uint32_t g = 0; g < G; ++g) {
+                p->hoff[g] = p->hrooms[g].c0;
+                for (uint32_t i = 0; i < cnt[g]; ++i) {
+                    p->hseat_of[p->gs[g] + i] = i;
+                    p->hseat_chan[p->hoff[g] + i] = (uint32_t)p->gs[g] + i;
+                }
+            }
+        }
+        // `stage` takes a room's lines (and their seats) at once, and at least a page of an assign's or a pair store's words
+        p->stage_words = std::max<size_t>((size_t)p->maxn * p->maxn + p->maxn, 4096);
     } catch (const std::bad_alloc &) {
         delete p;
         g_err = "mixmatrix: no host memory for the room tables";
@@ -397,7 +898,8 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
     }
     p->n_items = (uint32_t)items.size();
     bool ok = hipMalloc((void **)&p->tab, total_bytes) == hipSuccess && hipMalloc((void **)&p->div, (size_t)N * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&p->stage, (size_t)p->maxn * p->maxn * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&p->stage, p->stage_words * sizeof(float)) == hipSuccess &&
+              (!seated || hipMalloc((void **)&p->seat_chan, p->hseat_chan.size() * sizeof(uint32_t)) == hipSuccess) &&
               hipMalloc((void **)&p->rooms, (size_t)G * sizeof(Room)) == hipSuccess &&
               hipMalloc((void **)&p->items, items.size() * sizeof(Item)) == hipSuccess &&
               hipMalloc((void **)&p->room_of, (size_t)N * sizeof(uint32_t)) == hipSuccess;
@@ -410,6 +912,7 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
     ok = hipMemcpy(p->rooms, p->hrooms.data(), (size_t)G * sizeof(Room), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(p->items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(p->room_of, room_of.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
+         (!seated || hipMemcpy(p->seat_chan, p->hseat_chan.data(), p->hseat_chan.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) &&
          fill_rooms(p, 0, G, DSPFX_MIXMATRIX_MIX_MINUS, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
          hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -417,6 +920,186 @@ extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mi
         return DSPFX_ERR_HIP;
     }
     *out = p;
+    return DSPFX_OK;
+}
+
+// the room and the room-local index (the seat, in a seated bank) of channel c; smu is held on a seated bank
+void place_of(dspfx_mixmatrix *p, uint32_t c, uint32_t &room, uint32_t &index) {
+    if (p->seated) {
+        room = p->hroom_of[c];
+        index = p->hseat_of[c];
+    } else {
+        room = (uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), (uint64_t)c) - p->gs.begin()) - 1;
+        index = c - (uint32_t)p->gs[room];
+    }
+}
+
+}  // namespace
+
+extern "C" int dspfx_mixmatrix_reseat(uint32_t *room_of_io, uint32_t *seat_of_io, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
+                                      const uint32_t *room_ids, uint64_t first_channel, uint64_t count) {
+    g_err.clear();
+    if (!room_of_io || !seat_of_io || n_groups == 0 || n_channels == 0 || n_channels > 0xFFFFFF00ull) {
+        g_err = "mixmatrix reseat: no tables, no rooms or no channels";
+        return DSPFX_ERR_INVALID;
+    }
+    try {
+        std::vector<uint32_t> S, off, chan, occ(n_groups, 0);
+        const int rc = check_seats("mixmatrix reseat", seats, nullptr, n_groups, S, off, g_err);
+        if (rc != DSPFX_OK) return rc;
+        chan.assign((size_t)off[n_groups - 1] + S[n_groups - 1], NONE);
+        for (uint64_t c = 0; c < n_channels; ++c) {
+            const uint32_t g = room_of_io[c], q = seat_of_io[c];
+            if (g == NONE) continue;
+            if (g >= n_groups || q >= S[g] || chan[off[g] + q] != NONE) {
+                char buf[160];
+                std::snprintf(buf, sizeof buf, "mixmatrix reseat: channel %llu is in seat %u of room %u, which does not exist or is held twice", (unsigned long long)c, q, g);
+                g_err = buf;
+                return DSPFX_ERR_INVALID;
+            }
+            chan[off[g] + q] = (uint32_t)c;
+            ++occ[g];
+        }
+        std::vector<Move> moves;
+        return reseat(Seats{room_of_io, seat_of_io, chan.data(), occ.data(), S.data(), off.data(), n_groups, n_channels}, room_ids, first_channel, count, g_err, moves);
+    } catch (const std::bad_alloc &) {
+        g_err = "mixmatrix reseat: no host memory";
+        return DSPFX_ERR_OOM;
+    }
+}
+
+extern "C" int dspfx_mixmatrix_assign(dspfx_mixmatrix *p, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count, uint32_t preset) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (!p->seated) return p->fail(DSPFX_ERR_STATE, "mixmatrix assign: the bank has no seats (it was not made by dspfx_mixmatrix_create_seats)");
+    if (preset != DSPFX_MIXMATRIX_MIX_MINUS && preset != DSPFX_MIXMATRIX_ZERO)
+        return p->fail(DSPFX_ERR_INVALID, "mixmatrix assign: the preset (DSPFX_MIXMATRIX_MIX_MINUS and DSPFX_MIXMATRIX_ZERO are known)");
+    std::lock_guard<std::mutex> lk(p->smu);
+    const Seats t = p->seats();
+    std::vector<Move> moves;
+    std::string why;
+    try {
+        const int rc = reseat(t, host_room_ids, first_channel, count, why, moves);
+        if (rc != DSPFX_OK) return p->fail(rc, why.c_str());
+        if (moves.empty()) return DSPFX_OK;
+        // what the device needs, by the seating after the call: who sits in every seat touched, the room of every mover, the seats
+        // whose row and column change (emptied: +0.0; a newcomer's: the preset), and the rooms whose divisors change
+        std::vector<uint32_t> w_seats, w_chans, w_lines, w_rooms;
+        std::unordered_set<uint32_t> seen;
+        const uint32_t bit = preset == DSPFX_MIXMATRIX_MIX_MINUS ? 0x80000000u : 0u;
+        for (const Move &m : moves) {
+            w_chans.insert(w_chans.end(), {m.c, m.r1});
+            if (m.r0 != NONE) {
+                const uint32_t at = t.off[m.r0] + m.q0;
+                w_seats.insert(w_seats.end(), {at, t.seat_chan[at]});
+                if (t.seat_chan[at] == NONE) w_lines.insert(w_lines.end(), {m.r0, m.q0});       // (taken again: the newcomer's line covers it)
+                if (seen.insert(m.r0).second) w_rooms.push_back(m.r0);
+            }
+            if (m.r1 != NONE) {
+                w_seats.insert(w_seats.end(), {t.off[m.r1] + m.q1, m.c});
+                w_lines.insert(w_lines.end(), {m.r1, m.q1 | bit});
+                if (seen.insert(m.r1).second) w_rooms.push_back(m.r1);
+            }
+        }
+        int64_t gone = 0;
+        for (const Move &m : moves) gone += (m.r1 == NONE) - (m.r0 == NONE);
+        Store st;
+        st.kind = 3;
+        st.preset = preset;
+        st.n_seats = w_seats.size() / 2;
+        st.n_chans = w_chans.size() / 2;
+        st.n_lines = w_lines.size() / 2;
+        st.n_rooms = w_rooms.size();
+        st.roomless = (uint64_t)((int64_t)p->hroomless + gone);
+        const size_t words = w_seats.size() + w_chans.size() + w_lines.size() + w_rooms.size();
+        if (!p->stores.staging(p->desc.device, words, st)) {
+            unseat(t, moves);
+            return p->fail(DSPFX_ERR_OOM, "mixmatrix assign: no page-locked memory for the staged seats");
+        }
+        uint32_t *w = (uint32_t *)st.vals;
+        for (const std::vector<uint32_t> *v : {&w_seats, &w_chans, &w_lines, &w_rooms}) {
+            std::memcpy(w, v->data(), v->size() * sizeof(uint32_t));
+            w += v->size();
+        }
+        p->hroomless = st.roomless;
+        p->stores.push(st);
+    } catch (const std::bad_alloc &) {
+        if (!moves.empty()) unseat(t, moves);
+        return p->fail(DSPFX_ERR_OOM, "mixmatrix assign: no host memory");
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_set_pairs(dspfx_mixmatrix *p, const uint32_t *listeners, const uint32_t *sources, const float *gains, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (!listeners || !sources || !gains) return p->fail(DSPFX_ERR_INVALID, "mixmatrix set_pairs: no listeners, sources or gains");
+    if (count == 0) return DSPFX_OK;
+    char buf[192];
+    std::lock_guard<std::mutex> lk(p->smu);
+    try {
+        std::vector<uint32_t> words, rooms;
+        std::unordered_map<uint64_t, size_t> at;         // (room, listener, source) -> its triple: a later duplicate takes its place
+        std::unordered_set<uint32_t> seen;
+        const uint32_t N = p->desc.n_channels;
+        for (uint64_t i = 0; i < count; ++i) {
+            uint32_t rl = NONE, rs = NONE, il = 0, is = 0;
+            if (listeners[i] < N) place_of(p, listeners[i], rl, il);
+            if (sources[i] < N) place_of(p, sources[i], rs, is);
+            if (rl == NONE || rl != rs) {
+                std::snprintf(buf, sizeof buf, "mixmatrix set_pairs: pair %llu: listener %u and source %u are not two channels of one room",
+                              (unsigned long long)i, listeners[i], sources[i]);
+                return p->fail(DSPFX_ERR_INVALID, buf);
+            }
+            uint32_t g;
+            std::memcpy(&g, &gains[i], sizeof g);
+            const auto ins = at.emplace((uint64_t)rl << 20 | (uint64_t)il << 10 | is, words.size());
+            if (ins.second) words.insert(words.end(), {rl, il << 16 | is, g});
+            else words[ins.first->second + 2] = g;
+            if (seen.insert(rl).second) rooms.push_back(rl);
+        }
+        Store st;
+        st.kind = 4;
+        st.n_lines = words.size() / 3;
+        st.n_rooms = rooms.size();
+        if (!p->stores.staging(p->desc.device, words.size() + rooms.size(), st))
+            return p->fail(DSPFX_ERR_OOM, "mixmatrix set_pairs: no page-locked memory for the staged values");
+        std::memcpy(st.vals, words.data(), words.size() * sizeof(uint32_t));
+        std::memcpy(st.vals + words.size(), rooms.data(), rooms.size() * sizeof(uint32_t));
+        p->stores.push(st);
+    } catch (const std::bad_alloc &) {
+        return p->fail(DSPFX_ERR_OOM, "mixmatrix set_pairs: no host memory");
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_rooms(dspfx_mixmatrix *p, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    const uint64_t N = p->desc.n_channels;
+    if (!host_ids_out || first_channel > N || count > N - first_channel) return p->fail(DSPFX_ERR_INVALID, "mixmatrix rooms: the array or the range");
+    std::lock_guard<std::mutex> lk(p->smu);
+    for (uint64_t i = 0; i < count; ++i) {
+        uint32_t index;
+        place_of(p, (uint32_t)(first_channel + i), host_ids_out[i], index);
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_seats(dspfx_mixmatrix *p, uint32_t *host_seats_out, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    const uint64_t N = p->desc.n_channels;
+    if (!host_seats_out || first_channel > N || count > N - first_channel) return p->fail(DSPFX_ERR_INVALID, "mixmatrix seats: the array or the range");
+    std::lock_guard<std::mutex> lk(p->smu);
+    for (uint64_t i = 0; i < count; ++i) {
+        uint32_t room;
+        place_of(p, (uint32_t)(first_channel + i), room, host_seats_out[i]);
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_occupancy(dspfx_mixmatrix *p, uint32_t *host_counts_out) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (!host_counts_out) return p->fail(DSPFX_ERR_INVALID, "mixmatrix occupancy: no array");
+    std::lock_guard<std::mutex> lk(p->smu);
+    for (uint32_t g = 0; g < p->desc.n_groups; ++g) host_counts_out[g] = p->seated ? p->occ[g] : p->hrooms[g].n;
     return DSPFX_OK;
 }
 
@@ -481,6 +1164,15 @@ extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint3
     a.W = p->desc.tile_channels;
     a.nf = n_frames;
     a.normalise = p->desc.normalise;
+    if (p->seated) {
+        if (p->roomless) {
+            mixmatrix_zero_roomless<<<(a.N + WG - 1) / WG, WG, 0, s>>>(out, p->room_of, a.N, a.W, n_frames);
+            BANK_HIP_WHY(hipGetLastError(), "mixmatrix_zero_roomless");
+        }
+        mixmatrix_run_seated<<<dim3(p->n_items, (n_frames + FT - 1) / FT), WG, 0, s>>>(SeatedArgs{a, p->seat_chan});
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run_seated");
+        return DSPFX_OK;
+    }
     mixmatrix_run<<<dim3(p->n_items, (n_frames + FT - 1) / FT), WG, 0, s>>>(a);
     BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run");
     return DSPFX_OK;

@@ -257,6 +257,8 @@ pub const DSPFX_MIXMATRIX_MIX_MINUS: u32 = 0;
 pub const DSPFX_MIXMATRIX_ZERO: u32 = 1;
 /// `DSPFX_MIXGROUPS_NO_ROOM`: the id of a channel that sits in no room.
 pub const DSPFX_MIXGROUPS_NO_ROOM: u32 = 0xFFFF_FFFF;
+/// `DSPFX_MIXMATRIX_NO_ROOM`: the same, for `dspfx_mixmatrix_assign`.
+pub const DSPFX_MIXMATRIX_NO_ROOM: u32 = 0xFFFF_FFFF;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -453,4 +455,12 @@ extern "C" {
     pub fn dspfx_mixmatrix_set_cols(m: *mut dspfx_mixmatrix, host_values: *const f32, row_len: u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixmatrix_fill(m: *mut dspfx_mixmatrix, room: i64, preset: u32) -> c_int;
     pub fn dspfx_mixmatrix_reset(m: *mut dspfx_mixmatrix) -> c_int;
+    pub fn dspfx_mixmatrix_set_pairs(m: *mut dspfx_mixmatrix, listeners: *const u32, sources: *const u32, gains: *const f32, count: u64) -> c_int;
+    pub fn dspfx_mixmatrix_create_seats(desc: *const dspfx_mixmatrix_desc, seats: *const u32, out: *mut *mut dspfx_mixmatrix) -> c_int;
+    pub fn dspfx_mixmatrix_plan_seats(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, seats: *const u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_mixmatrix_assign(m: *mut dspfx_mixmatrix, host_room_ids: *const u32, first_channel: u64, count: u64, preset: u32) -> c_int;
+    pub fn dspfx_mixmatrix_rooms(m: *mut dspfx_mixmatrix, host_ids_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixmatrix_seats(m: *mut dspfx_mixmatrix, host_seats_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixmatrix_occupancy(m: *mut dspfx_mixmatrix, host_counts_out: *mut u32) -> c_int;
+    pub fn dspfx_mixmatrix_reseat(room_of_io: *mut u32, seat_of_io: *mut u32, seats: *const u32, n_groups: u32, n_channels: u64, room_ids: *const u32, first_channel: u64, count: u64) -> c_int;
 }

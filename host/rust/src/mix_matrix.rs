@@ -6,7 +6,8 @@
 //! `out[f][c0 + l] = (sum_s M[l][s] * x[f][c0 + s]) / link_divisor(w)`, w = the listener's entries that are not zero.  A fresh bank
 //! holds mix-minus, which is `MixGroups::returns` without faders; a host binds it between `ChannelStrips::run` and the listeners'
 //! resampler when listeners need mixes of their own.  The GUI thread stores rows and columns, which never wait for the device: the
-//! next `run` applies them in order, each whole.  The rooms are fixed: a host that reseats makes a new bank for the new table.
+//! next `run` applies them in order, each whole.  A bank made by `new` has fixed rooms; one made by `with_seats` gives every room a
+//! number of seats and follows live moves with `assign`, as `MixGroups::assign` does, without rebuilding a table.
 //! NOT compiled in the build container (no rustc).
 use super::engine::Error;
 use super::ffi::*;
@@ -57,6 +58,96 @@ impl MixMatrix {
             return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_create") });
         }
         Ok(MixMatrix { h, channels, rooms })
+    }
+    /// A SEATED bank (`dspfx_mixmatrix_create_seats`): room r owns `seats[r]` seats (at least its members, rounded up to 32, at
+    /// most `DSPFX_MIXMATRIX_MAX_ROOM`) and an S_r x S_r table that never moves; `assign` then reseats channels live.
+    pub fn with_seats(device: i32, channels: u32, group_start: &[u64], seats: &[u32], tile_channels: u32, max_frames: u32, normalise: bool) -> Result<Self, Error> {
+        let rooms = group_start.len().saturating_sub(1) as u32;
+        if seats.len() != rooms as usize {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "seats: one count per room".into() });
+        }
+        let desc = dspfx_mixmatrix_desc {
+            abi_version: DSPFX_ABI_VERSION,
+            device,
+            n_channels: channels,
+            max_frames,
+            tile_channels,
+            n_groups: rooms,
+            normalise: normalise as u32,
+            group_start: group_start.as_ptr(),
+        };
+        let mut h = ptr::null_mut();
+        let rc = unsafe { dspfx_mixmatrix_create_seats(&desc, seats.as_ptr(), &mut h) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_create_seats") });
+        }
+        Ok(MixMatrix { h, channels, rooms })
+    }
+    /// Seats channels `first_channel ..` in the rooms `ids` (each `< rooms()` or `DSPFX_MIXMATRIX_NO_ROOM`): those whose id is
+    /// their room stay as they are, the others leave and then enter in ascending channel order, each into the lowest free seat,
+    /// wired by `preset`.  A bad id or range, or a room over capacity, stores nothing.  Any thread; never waits for a run.
+    pub fn assign(&self, ids: &[u32], first_channel: u64, preset: u32) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixmatrix_assign(self.h, ids.as_ptr(), first_channel, ids.len() as u64, preset) };
+        self.check(rc, "dspfx_mixmatrix_assign")
+    }
+    /// The room of every channel (`DSPFX_MIXMATRIX_NO_ROOM`: none) by every call made so far.
+    pub fn room_of(&self) -> Result<Vec<u32>, Error> {
+        let mut v = vec![0u32; self.channels as usize];
+        let rc = unsafe { dspfx_mixmatrix_rooms(self.h, v.as_mut_ptr(), 0, v.len() as u64) };
+        self.check(rc, "dspfx_mixmatrix_rooms")?;
+        Ok(v)
+    }
+    /// The seat of every channel in its room (`0xFFFF_FFFF`: in no room).
+    pub fn seat_of(&self) -> Result<Vec<u32>, Error> {
+        let mut v = vec![0u32; self.channels as usize];
+        let rc = unsafe { dspfx_mixmatrix_seats(self.h, v.as_mut_ptr(), 0, v.len() as u64) };
+        self.check(rc, "dspfx_mixmatrix_seats")?;
+        Ok(v)
+    }
+    /// The taken seats of every room.
+    pub fn occupancy(&self) -> Result<Vec<u32>, Error> {
+        let mut v = vec![0u32; self.rooms as usize];
+        let rc = unsafe { dspfx_mixmatrix_occupancy(self.h, v.as_mut_ptr()) };
+        self.check(rc, "dspfx_mixmatrix_occupancy")?;
+        Ok(v)
+    }
+    /// `M[listeners[i]][sources[i]] = gains[i]` by channel number, in order; each pair two channels of one room.
+    pub fn set_pairs(&self, listeners: &[u32], sources: &[u32], gains: &[f32]) -> Result<(), Error> {
+        if listeners.len() != sources.len() || listeners.len() != gains.len() {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "listeners, sources and gains are equally long".into() });
+        }
+        let rc = unsafe { dspfx_mixmatrix_set_pairs(self.h, listeners.as_ptr(), sources.as_ptr(), gains.as_ptr(), gains.len() as u64) };
+        self.check(rc, "dspfx_mixmatrix_set_pairs")
+    }
+    /// The seating rule on host arrays (a pure host function): what `assign` does to the bank's tables.
+    pub fn reseat(room_of: &mut [u32], seat_of: &mut [u32], seats: &[u32], ids: &[u32], first_channel: u64) -> Result<(), Error> {
+        if room_of.len() != seat_of.len() {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "room_of and seat_of are equally long".into() });
+        }
+        let rc = unsafe {
+            dspfx_mixmatrix_reseat(room_of.as_mut_ptr(), seat_of.as_mut_ptr(), seats.as_ptr(), seats.len() as u32, room_of.len() as u64,
+                                   ids.as_ptr(), first_channel, ids.len() as u64)
+        };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_reseat") });
+        }
+        Ok(())
+    }
+    /// `plan` for a seated bank: the edges are the seats rounded up to 32.
+    pub fn plan_seats(channels: u64, group_start: &[u64], seats: &[u32], tile_channels: u32) -> Result<MixMatrixPlan, Error> {
+        let g = group_start.len().saturating_sub(1);
+        if seats.len() != g {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "seats: one count per room".into() });
+        }
+        let mut p = MixMatrixPlan { count: vec![0; g], edge: vec![0; g], offset: vec![0; g], total_bytes: 0 };
+        let rc = unsafe {
+            dspfx_mixmatrix_plan_seats(group_start.as_ptr(), g as u32, channels, tile_channels, seats.as_ptr(), p.count.as_mut_ptr(),
+                                       p.edge.as_mut_ptr(), p.offset.as_mut_ptr(), &mut p.total_bytes)
+        };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_plan_seats") });
+        }
+        Ok(p)
     }
     fn check(&self, rc: c_int, what: &str) -> Result<(), Error> {
         if rc == DSPFX_OK { Ok(()) } else { Err(Error { status: rc, message: reason(self.h, what) }) }

@@ -1117,9 +1117,12 @@ int dspfx_strips_coeffs(const float *raw6, float *out5);
  * run to run, on any stream, in either layout, for any n_frames, and whatever the other rooms hold.  No atomics.
  * Memory: the matrices are kept source-major with edges padded to a multiple of 32: 4 * sum over the rooms of
  * (n_r rounded up to 32)^2 bytes (dspfx_mixmatrix_plan gives it; 1 GiB for 4096 rooms of 256), 8 bytes per channel beside it.
- * Rooms are fixed: a host that reseats participants with dspfx_mixgroups_assign destroys the bank and creates one for the new
- * table (and stores the rows again); rooms above the limit, sparse tables and reduced precision are not offered. */
+ * A bank made by dspfx_mixmatrix_create has fixed rooms.  A host that reseats participants live (dspfx_mixgroups_assign) makes
+ * the bank with dspfx_mixmatrix_create_seats and follows every move with dspfx_mixmatrix_assign (below): no table is rebuilt and
+ * the gains of those who stay are kept.  Rooms above the limit, sparse tables and reduced precision are not offered. */
 #define DSPFX_MIXMATRIX_MAX_ROOM 1024
+/* dspfx_mixmatrix_assign: the channel sits in no room */
+#define DSPFX_MIXMATRIX_NO_ROOM 0xFFFFFFFFu
 /* dspfx_mixmatrix_fill presets: 1.0 off the diagonal and +0.0 on it; all +0.0 */
 #define DSPFX_MIXMATRIX_MIX_MINUS 0
 #define DSPFX_MIXMATRIX_ZERO 1
@@ -1170,6 +1173,60 @@ int dspfx_mixmatrix_set_cols(dspfx_mixmatrix *m, const float *host_values, uint3
 int dspfx_mixmatrix_fill(dspfx_mixmatrix *m, int64_t room, uint32_t preset);
 /* The fresh state: mix-minus in every room; queued like a store. */
 int dspfx_mixmatrix_reset(dspfx_mixmatrix *m);
+/* Gains by channel number, for both kinds of bank: M[listeners[i]][sources[i]] = gains[i] for i in [0, count), in that order, so
+ * a later duplicate wins ("A mutes B" needs no seat lookup).  Each pair must be two channels of ONE room (by the seating so far);
+ * otherwise DSPFX_ERR_INVALID, the reason, nothing stored.  Queued like every other store; the divisors of the rooms touched are
+ * recounted behind it. */
+int dspfx_mixmatrix_set_pairs(dspfx_mixmatrix *m, const uint32_t *listeners, const uint32_t *sources, const float *gains, uint64_t count);
+
+/* ---- seated banks: participants change rooms live -----------------------------------------------------------------------
+ * dspfx_mixmatrix_create_seats makes a bank whose room r owns S_r SEATS: seats[r] rounded up to 32, n_r <= S_r <=
+ * DSPFX_MIXMATRIX_MAX_ROOM (a value below n_r or above the limit is DSPFX_ERR_INVALID with the reason in
+ * dspfx_mixmatrix_last_error(NULL), before any device work).  The room's table is S_r x S_r and its memory never changes after
+ * create; a channel holds one seat of one room, or none.  At first channel c0 + i of room r sits in seat i and the table holds
+ * mix-minus among the taken seats; every entry in the row or the column of an empty seat is +0.0, and every store keeps it so.
+ * For a channel c in seat l of room r, with chan_r(s) the channel in seat s:
+ *       out[f][c] = (sum over the taken seats s of M_r[l][s] * x[f][chan_r(s)]) / d[c]
+ * d, w and normalise as above.  A channel in no room reads +0.0 in every frame whatever it carries; its samples are never read.
+ * The sources are added in ascending SEAT order into one fmaf chain with a +0.0 * +0.0 term at every empty seat: the chain of
+ * a dspfx_mixmatrix_create room of S_r contiguous members whose absent members carry +0.0 samples and zero rows and columns, bit
+ * for bit.  A room's bits are a function of its table, its samples and its seat arrangement alone; the error bound is the one
+ * above with n = the taken seats (zero terms are exact).
+ * Memory: 4 * sum of S_r^2 bytes of tables (dspfx_mixmatrix_plan_seats), 4 bytes per seat and 8 per channel on the device, and
+ * 4 bytes per seat and 8 per channel on the host.
+ * Stores on a seated bank: set_rows / set_cols take lines of row_len = S_r values indexed by SEAT; the channels named must all
+ * sit in one room by the seating so far (in any seats of it); a value given for an empty seat is stored as +0.0.
+ * dspfx_mixmatrix_fill with DSPFX_MIXMATRIX_MIX_MINUS means 1.0 between two different taken seats. */
+int dspfx_mixmatrix_create_seats(const dspfx_mixmatrix_desc *desc, const uint32_t *seats /* host, [n_groups] */, dspfx_mixmatrix **out);
+/* PURE HOST function: dspfx_mixmatrix_plan for a seated bank: edge_out[g] = S_g, the offsets and the bytes of S_g x S_g tables. */
+int dspfx_mixmatrix_plan_seats(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats,
+                               uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out);
+/* Seats channels [first_channel, first_channel + count) in the rooms host_room_ids (each < n_groups, or
+ * DSPFX_MIXMATRIX_NO_ROOM).  DSPFX_ERR_STATE on a bank not made by dspfx_mixmatrix_create_seats.  The contract of
+ * dspfx_mixgroups_assign: the range, every id and every room's capacity are checked before anything is stored
+ * (DSPFX_ERR_INVALID, the reason, nothing changed); callable from any thread while runs are in flight; never waits for the device
+ * or for a run; holds, whole, for every run submitted after it returns and for none submitted before.  Queued in order with the
+ * other stores.
+ * THE SEATING RULE.  A channel whose id is its current room is untouched: it keeps its seat and its gains.  All other named
+ * channels first LEAVE: their seat is free, its row and column in the old room's table become +0.0.  Then the channels that
+ * enter a room do so in ascending channel order, each into the LOWEST FREE SEAT of its new room (so two participants can swap
+ * between two full rooms in one call, and somebody who comes back gets the lowest free seat, not the old one).
+ * The newcomer's wiring, by the seating after the whole call: DSPFX_MIXMATRIX_MIX_MINUS: 1.0 in the newcomer's row at every
+ * other taken seat and in their column for every other seated listener, +0.0 on the diagonal; DSPFX_MIXMATRIX_ZERO: row and
+ * column +0.0 (the host then stores its own).  Entries between two participants who both stayed are never touched.  The
+ * divisors of every listener of a room somebody left or entered are recounted on the device.
+ * Cost: O(count + the seats of the rooms entered) on the host, one row and one column per mover on the device. */
+int dspfx_mixmatrix_assign(dspfx_mixmatrix *m, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count, uint32_t preset);
+/* The room (DSPFX_MIXMATRIX_NO_ROOM: none) and the seat (0xFFFFFFFF: none) of channels [first_channel, first_channel + count), and
+ * the taken seats of every room ([n_groups]), by every call made so far.  A bank without seats answers by its table. */
+int dspfx_mixmatrix_rooms(dspfx_mixmatrix *m, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count);
+int dspfx_mixmatrix_seats(dspfx_mixmatrix *m, uint32_t *host_seats_out, uint64_t first_channel, uint64_t count);
+int dspfx_mixmatrix_occupancy(dspfx_mixmatrix *m, uint32_t *host_counts_out);
+/* PURE HOST function: the seating rule on host arrays.  room_of_io[n_channels] and seat_of_io[n_channels] hold a seating of rooms
+ * with seats[g] seats (rounded up to 32) and are changed as dspfx_mixmatrix_assign changes the bank's; the same checks, the reason
+ * in dspfx_mixmatrix_last_error(NULL), nothing changed on a refusal.  dspfx_mixmatrix_assign uses the same code. */
+int dspfx_mixmatrix_reseat(uint32_t *room_of_io, uint32_t *seat_of_io, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
+                           const uint32_t *room_ids, uint64_t first_channel, uint64_t count);
 
 #ifdef __cplusplus
 }

@@ -563,7 +563,8 @@ inline std::vector<float> strips_coeffs(const float (&raw6)[6]) {
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
-// faders.  Between ChannelStrips::run and the listeners' Resampler, as an alternative to returns.  The rooms are fixed.
+// faders.  Between ChannelStrips::run and the listeners' Resampler, as an alternative to returns.  The rooms are fixed, unless
+// the bank is made with seats (the second constructor): then assign() reseats channels live, as MixGroups::assign does.
 class MixMatrix {
   public:
     MixMatrix(std::uint32_t channels, const std::vector<std::uint64_t> &group_start, std::uint32_t tile_channels = 0,
@@ -591,6 +592,47 @@ class MixMatrix {
     void fill(std::int64_t room = -1, std::uint32_t preset = DSPFX_MIXMATRIX_MIX_MINUS) { chk(dspfx_mixmatrix_fill(p_, room, preset)); }
     // the fresh state: mix-minus in every room
     void reset() { chk(dspfx_mixmatrix_reset(p_)); }
+    // a SEATED bank (dspfx_mixmatrix_create_seats): room r owns seats[r] seats (>= its members, rounded up to 32, <= the limit) and a
+    // table that never moves; assign() then reseats channels live.  Rows and columns are S_r long and indexed by seat
+    MixMatrix(std::uint32_t channels, const std::vector<std::uint64_t> &group_start, const std::vector<std::uint32_t> &seats,
+              std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE, bool normalise = true, int device = 0) {
+        const std::uint32_t G = (std::uint32_t)(group_start.empty() ? 0 : group_start.size() - 1);
+        if (seats.size() != G) throw Error(DSPFX_ERR_INVALID, "seats: one count per room");
+        const dspfx_mixmatrix_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, G, normalise ? 1u : 0u, group_start.data()};
+        const int rc = dspfx_mixmatrix_create_seats(&d, seats.data(), &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_mixmatrix_last_error(nullptr) ? dspfx_mixmatrix_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    // seating (dspfx_mixmatrix_assign): the rooms of channels [first_channel, first_channel + ids.size()), each < the rooms or NO_ROOM.
+    // Those whose id is their room stay as they are; the others leave, then enter in ascending channel order, each into the lowest
+    // free seat, wired by `preset`.  A bad id or range, or a room over capacity, stores nothing.  Any thread; never waits for a run
+    void assign(const std::vector<std::uint32_t> &ids, std::uint64_t first_channel = 0, std::uint32_t preset = DSPFX_MIXMATRIX_MIX_MINUS) {
+        chk(dspfx_mixmatrix_assign(p_, ids.data(), first_channel, ids.size(), preset));
+    }
+    void assign(std::uint32_t id, std::uint64_t first_channel, std::uint32_t preset = DSPFX_MIXMATRIX_MIX_MINUS) {
+        chk(dspfx_mixmatrix_assign(p_, &id, first_channel, 1, preset));
+    }
+    // the room (NO_ROOM: none) and the seat (0xFFFFFFFF: none) of channels [first_channel, first_channel + count), and the taken seats
+    // of each of `rooms` rooms, by every call made so far
+    std::vector<std::uint32_t> room_of(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> v(count);
+        chk(dspfx_mixmatrix_rooms(p_, v.data(), first_channel, count));
+        return v;
+    }
+    std::vector<std::uint32_t> seat_of(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> v(count);
+        chk(dspfx_mixmatrix_seats(p_, v.data(), first_channel, count));
+        return v;
+    }
+    std::vector<std::uint32_t> occupancy(std::uint32_t rooms) {
+        std::vector<std::uint32_t> v(rooms);
+        chk(dspfx_mixmatrix_occupancy(p_, v.data()));
+        return v;
+    }
+    // M[listeners[i]][sources[i]] = gains[i] by channel number, in order; each pair two channels of one room
+    void set_pairs(const std::vector<std::uint32_t> &listeners, const std::vector<std::uint32_t> &sources, const std::vector<float> &gains) {
+        if (listeners.size() != sources.size() || listeners.size() != gains.size()) throw Error(DSPFX_ERR_INVALID, "listeners, sources and gains are equally long");
+        chk(dspfx_mixmatrix_set_pairs(p_, listeners.data(), sources.data(), gains.data(), gains.size()));
+    }
     dspfx_mixmatrix *raw() { return p_; }
 
   private:
@@ -616,6 +658,28 @@ inline MixMatrixPlan mixmatrix_plan(std::uint64_t channels, const std::vector<st
     const int rc = dspfx_mixmatrix_plan(group_start.data(), G, channels, tile_channels, r.count.data(), r.edge.data(), r.offset.data(), &r.total_bytes);
     if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
     return r;
+}
+// ... of a seated bank (dspfx_mixmatrix_plan_seats): the edges are the seats rounded up to 32
+inline MixMatrixPlan mixmatrix_plan(std::uint64_t channels, const std::vector<std::uint64_t> &group_start, const std::vector<std::uint32_t> &seats,
+                                    std::uint32_t tile_channels = 0) {
+    const std::uint32_t G = (std::uint32_t)(group_start.empty() ? 0 : group_start.size() - 1);
+    if (seats.size() != G) throw Error(DSPFX_ERR_INVALID, "seats: one count per room");
+    MixMatrixPlan r;
+    r.count.resize(G);
+    r.edge.resize(G);
+    r.offset.resize(G);
+    const int rc = dspfx_mixmatrix_plan_seats(group_start.data(), G, channels, tile_channels, seats.data(), r.count.data(), r.edge.data(), r.offset.data(),
+                                              &r.total_bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
+    return r;
+}
+// The seating rule on host arrays (dspfx_mixmatrix_reseat: a pure host function): what MixMatrix::assign does to the bank's tables
+inline void mixmatrix_reseat(std::vector<std::uint32_t> &room_of, std::vector<std::uint32_t> &seat_of, const std::vector<std::uint32_t> &seats,
+                             const std::vector<std::uint32_t> &ids, std::uint64_t first_channel = 0) {
+    if (room_of.size() != seat_of.size()) throw Error(DSPFX_ERR_INVALID, "room_of and seat_of are equally long");
+    const int rc = dspfx_mixmatrix_reseat(room_of.data(), seat_of.data(), seats.data(), (std::uint32_t)seats.size(), room_of.size(), ids.data(), first_channel,
+                                          ids.size());
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
 }
 
 // One long impulse response over N channels by partitioned FFT (dspfx_convolve_*): the FIR node's arithmetic for responses too

@@ -64,13 +64,83 @@ def measure(torch, n, room, reps):
     return r
 
 
+def measure_seated(torch, n, room, seats, moved, reps, movers=16):
+    """The seated bank beside the unseated one on the same buffers: ms per run unseated, seated at identity seating, and seated
+    after each share of `moved` of the channels (cumulatively, in the order given) has been reseated into a random room with room;
+    and the ms of the first run after an assign of `movers` channels (the queued seats, lines and recounts ride ahead of it)."""
+    dev = torch.device("cuda:0")
+    torch.manual_seed(91)
+    rng = np.random.default_rng(93)
+    x = torch.rand(B * n, dtype=torch.float32, device=dev) * 2.0 - 1.0
+    y = torch.empty_like(x)
+    plain = pkg.MixMatrix(n, group_size=room, tile_channels=W, max_frames=B)
+    r = {"channels": n, "room": room, "seats": seats, "unseated_ms": timed(torch, lambda: plain.run(x, B, out=y), reps)}
+    plain.close()
+    mix = pkg.MixMatrix(n, group_size=room, tile_channels=W, max_frames=B, seats=seats)
+    S = int(mix.seats[0])
+    r["identity_ms"] = timed(torch, lambda: mix.run(x, B, out=y), reps)
+    r["identity_x_unseated"] = r["identity_ms"] / r["unseated_ms"]
+    # the first run after a small assign, from (nearly) identity seating: `movers` channels swap rooms pairwise, then swap back
+    firsts = []
+    for _ in range(reps):
+        room_of = mix.room_of()
+        who = rng.choice(n, movers, replace=False)
+        ids = room_of.copy()
+        ids[who[0::2]], ids[who[1::2]] = room_of[who[1::2]], room_of[who[0::2]]
+        mix.assign(ids)                                   # (one call over all channels; leaves come before enters: full rooms can swap)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        mix.run(x, B, out=y)
+        ev[1].record()
+        torch.cuda.synchronize()
+        firsts.append(ev[0].elapsed_time(ev[1]))
+        mix.assign(room_of)
+        mix.run(x, B, out=y)
+    r["first_run_after_assign_ms"], r["movers"] = float(np.median(firsts)), movers
+    r["moved_ms"] = {}
+    for share in moved:
+        k = int(round(share * n))
+        if k:
+            # everybody chosen leaves, then each enters a random room that still has a seat (a full table when seats == room: they
+            # are dealt back into the seats the leavers freed, in another order)
+            who = np.sort(rng.choice(n, k, replace=False))
+            ids = mix.room_of()
+            ids[who] = pkg.NO_ROOM
+            mix.assign(ids)                               # (one call over all channels: those whose id is their room stay)
+            free = S - mix.occupancy().astype(np.int64)
+            ids[who] = rng.permutation(np.repeat(np.arange(len(free)), free))[:k]
+            mix.assign(ids)
+        r["moved_ms"][str(share)] = timed(torch, lambda: mix.run(x, B, out=y), reps)
+    mix.close()
+    print(json.dumps(r), flush=True)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", default="65536,262144,1048576")
     ap.add_argument("--room", default="32,256,1024")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--seats", type=int, default=0, help="S: measure the seated bank with S seats per room beside the unseated one")
+    ap.add_argument("--moved", default="0,0.01,0.1,1", help="with --seats: the shares of the channels reseated at random, cumulatively")
     a = ap.parse_args()
     import torch
+    if a.seats:
+        moved = [float(s) for s in a.moved.split(",")]
+        out = []
+        for n in (int(s) for s in a.channels.split(",")):
+            for room in (int(s) for s in a.room.split(",")):
+                if room <= a.seats:
+                    out.append(measure_seated(torch, n, room, a.seats, moved, a.reps))
+                    torch.cuda.empty_cache()
+        print(f"\ntimes in ms, median of {a.reps}; moved: the share of the channels reseated at random so far")
+        print(f"{'channels':>9} {'room':>5} {'seats':>5} {'unseated':>9} {'identity':>9} {'x':>6} " + " ".join(f"{'moved ' + str(m):>11}" for m in moved)
+              + f" {'first run after assign':>23}")
+        for r in out:
+            print(f"{r['channels']:>9} {r['room']:>5} {r['seats']:>5} {r['unseated_ms']:>9.4f} {r['identity_ms']:>9.4f} {r['identity_x_unseated']:>6.3f} "
+                  + " ".join(f"{r['moved_ms'][str(m)]:>11.4f}" for m in moved) + f" {r['first_run_after_assign_ms']:>23.4f}")
+        return
     rows = []
     for n in (int(s) for s in a.channels.split(",")):
         for room in (int(s) for s in a.room.split(",")):
