@@ -85,6 +85,8 @@ EXPORTS = [
     "dspfx_convolve_response_count",
     "dspfx_strips_create", "dspfx_strips_destroy", "dspfx_strips_last_error", "dspfx_strips_run", "dspfx_strips_set_gain",
     "dspfx_strips_set_band", "dspfx_strips_reset", "dspfx_strips_present", "dspfx_strips_coeffs",
+    "dspfx_delays_plan", "dspfx_delays_create", "dspfx_delays_destroy", "dspfx_delays_last_error", "dspfx_delays_run",
+    "dspfx_delays_set_delay", "dspfx_delays_reset", "dspfx_delays_present", "dspfx_delays_lengths",
     "dspfx_mixmatrix_plan", "dspfx_mixmatrix_create", "dspfx_mixmatrix_destroy", "dspfx_mixmatrix_last_error", "dspfx_mixmatrix_run",
     "dspfx_mixmatrix_set_rows", "dspfx_mixmatrix_set_cols", "dspfx_mixmatrix_fill", "dspfx_mixmatrix_reset",
     "dspfx_mixmatrix_set_pairs", "dspfx_mixmatrix_create_seats", "dspfx_mixmatrix_plan_seats", "dspfx_mixmatrix_assign",
@@ -153,6 +155,11 @@ class _ConvolveDesc(C.Structure):
 class _StripsDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("bands", C.c_uint32), ("link_flags", C.c_uint32)]
+
+
+class _DelaysDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("max_seconds", C.c_float), ("page_round", C.c_uint32), ("link_flags", C.c_uint32)]
 
 
 class _MixMatrixDesc(C.Structure):
@@ -323,6 +330,16 @@ def lib():
     L.dspfx_strips_reset.argtypes = [vp]
     L.dspfx_strips_present.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
     L.dspfx_strips_coeffs.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.dspfx_delays_plan.argtypes = [C.c_uint64, C.c_float, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.dspfx_delays_create.argtypes = [C.POINTER(_DelaysDesc), C.POINTER(C.c_void_p)]
+    L.dspfx_delays_destroy.argtypes = [vp]
+    L.dspfx_delays_last_error.restype = C.c_char_p
+    L.dspfx_delays_last_error.argtypes = [vp]
+    L.dspfx_delays_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_delays_set_delay.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, C.c_uint64]
+    L.dspfx_delays_reset.argtypes = [vp]
+    L.dspfx_delays_present.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
+    L.dspfx_delays_lengths.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]
     L.dspfx_mixmatrix_plan.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dspfx_mixmatrix_create.argtypes = [C.POINTER(_MixMatrixDesc), C.POINTER(vp)]
@@ -1549,6 +1566,94 @@ class ChannelStrips(_Bank):
     def reset(self):
         """Zero all state (on the stream last used); the sliders and the nodes stay."""
         self._chk(self.L.dspfx_strips_reset(self.h))
+
+
+
+def delays_plan(channels: int, max_seconds: float = 0.5, page_round: bool = False):
+    """dspfx_delays_plan, a pure host function (no GPU): (cap, bytes) of a ChannelDelays bank -- the ring frames per channel,
+    delay_len(max_seconds, page_round), and the ring bytes, channels * cap * 4.  Refuses what the bank's create would."""
+    L = lib()
+    cap, nbytes = C.c_uint32(), C.c_uint64()
+    rc = L.dspfx_delays_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, float(max_seconds), int(bool(page_round)), C.byref(cap), C.byref(nbytes))
+    _raise(L, "delays", rc)
+    return int(cap.value), int(nbytes.value)
+
+
+class ChannelDelays(_Bank):
+    """Per-channel Reverb (feedback delay) sliders (include/dspfx.h, dspfx_delays_*): channel c may carry one Reverb node with
+    its own `seconds` and `decay` and its own ring of delay_len(seconds, page_round) frames, over a device block in the layout of
+    `tile_channels` (as Engine's).  A node exists for a channel from the first store that names it until it is dropped; a fresh
+    bank copies its input.  Every store is the reference's slider change: the stored channels start again from a zero ring.
+    `max_seconds` sizes the rings (delays_plan).  `link_flags` as Engine's: LINK_INPUT puts the collect_and_average hop ahead of
+    the node.  Where ChannelStrips goes: between eng.process and the room mixes.  Asynchronous on `stream`."""
+
+    _C = "delays"
+    _WHY = True
+
+    def __init__(self, channels: int, max_seconds: float = 0.5, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
+                 page_round: bool = False, device: int = 0):
+        self.L = lib()
+        self.channels, self.max_seconds, self.tile_channels = int(channels), float(max_seconds), int(tile_channels)
+        self.max_frames, self.link_flags, self.page_round, self.device = int(max_frames), int(link_flags), bool(page_round), int(device)
+        d = _DelaysDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
+                        self.max_seconds, int(self.page_round), self.link_flags & 0xFFFFFFFF)
+        self._create(d)
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every channel's delay -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_delays_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        return out
+
+    def set_delay(self, seconds=None, decay=None, first_channel: int = 0, count: Optional[int] = None):
+        """Store the sliders of channels from first_channel: arrays (one value per channel) or scalars for `count` channels
+        (default: all from first_channel).  A slider left None keeps each channel's value (0.5 where never stored); both None
+        drops the node of `count` channels.  Every stored channel starts again from a zero ring, as the reference's slider
+        change does.  Refused whole when a channel would need more than the bank's ring.  Any thread; applies to the runs
+        submitted after it."""
+        first = int(first_channel)
+        n = None
+        for v in (seconds, decay):
+            if v is not None and np.ndim(v) != 0:
+                m = int(np.size(v))
+                if n is not None and m != n:
+                    raise DspfxError(-1, "delays set_delay: seconds and decay name different numbers of channels")
+                n = m
+        if n is None:
+            n = self.channels - first if count is None else int(count)
+
+        def arr(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
+            return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+        s, sp = arr(seconds)
+        d, dp = arr(decay)
+        self._chk(self.L.dspfx_delays_set_delay(self.h, sp, dp, first, n))
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        v = np.zeros(max(n, 0), np.uint32)
+        self._chk(self.L.dspfx_delays_present(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
+        return v
+
+    def lengths(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: every channel's ring length D, 0 where there is no node."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        v = np.zeros(max(n, 0), np.uint32)
+        self._chk(self.L.dspfx_delays_lengths(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
+        return v
+
+    def reset(self):
+        """Every present channel's ring back to zeros (on the stream last used); the sliders and the nodes stay."""
+        self._chk(self.L.dspfx_delays_reset(self.h))
 
 
 

@@ -163,6 +163,26 @@ pub struct dspfx_strips_desc {
     pub link_flags: u32,
 }
 
+/// Opaque channel-delay bank handle (`typedef struct dspfx_delays dspfx_delays`).
+#[repr(C)]
+pub struct dspfx_delays {
+    _private: [u8; 0],
+}
+
+/// The channel-delay bank's descriptor (`dspfx_delays_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_delays_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub max_seconds: f32,
+    pub page_round: u32,
+    pub link_flags: u32,
+}
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -446,6 +466,15 @@ extern "C" {
     pub fn dspfx_strips_reset(s: *mut dspfx_strips) -> c_int;
     pub fn dspfx_strips_present(s: *mut dspfx_strips, host_masks_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_strips_coeffs(raw6: *const f32, out5: *mut f32) -> c_int;
+    pub fn dspfx_delays_plan(channels: u64, max_seconds: f32, page_round: c_int, cap_out: *mut u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_delays_create(desc: *const dspfx_delays_desc, out: *mut *mut dspfx_delays) -> c_int;
+    pub fn dspfx_delays_destroy(d: *mut dspfx_delays) -> c_int;
+    pub fn dspfx_delays_last_error(d: *const dspfx_delays) -> *const c_char;
+    pub fn dspfx_delays_run(d: *mut dspfx_delays, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_delays_set_delay(d: *mut dspfx_delays, host_seconds: *const f32, host_decay: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_delays_reset(d: *mut dspfx_delays) -> c_int;
+    pub fn dspfx_delays_present(d: *mut dspfx_delays, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_delays_lengths(d: *mut dspfx_delays, host_lengths_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

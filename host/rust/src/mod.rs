@@ -7,4 +7,5 @@ pub mod mix_groups;
 pub mod convolver;
 pub mod convolver_responses;
 pub mod channel_strips;
+pub mod channel_delays;
 pub mod mix_matrix;

@@ -1092,6 +1092,73 @@ int dspfx_strips_present(dspfx_strips *s, uint32_t *host_masks_out, uint64_t fir
  * exactly as the device gets them. */
 int dspfx_strips_coeffs(const float *raw6, float *out5);
 
+/* ---- channel delays: per-channel Reverb (feedback delay) sliders ---------------------------------------------------
+ * An engine runs one Reverb(seconds, decay) for all its channels.  In the reference every graph owns its Reverb node with its
+ * own `seconds` and `decay` sliders and its own ring (nodes/reverb.rs:29-41).  This bank is that: channel c may carry one Reverb
+ * node with its own ring of D_c frames.  It goes where the channel strips go, between the N-channel chain and the room mixes.
+ * A node EXISTS for a channel from the first store that names it until it is dropped; a fresh bank has no node anywhere and run
+ * copies in to out bit for bit.  Per channel the bank keeps D_c, decay_c, seconds_c, a ring position and the count of frames
+ * whose tap still reads as zero.
+ * A store to a channel is the reference's slider change: ANY slider of the node, decay included, fires refresh_seconds
+ * (reverb.rs:19, 55-71), so the channel gets a NEW ZERO ring of D_c = dspfx_delay_len(seconds_c, page_round) frames at position 0
+ * and every echo in the old one is gone.  The values are taken as given: no clamp, NaN seconds is 128 frames as dspfx_delay_len says.
+ * One run of n_frames, per channel that carries a node (reverb.rs:76-110):
+ *       n_frames <= D_c    for i in order   tap = ring[(pos + i) % D_c]  (+0.0f while the new ring is still zeros)
+ *                                           out[i] = in[i] + tap * decay_c     one f32 multiply, one f32 add, nothing contracted
+ *                                           ring[(pos + i) % D_c] = out[i]
+ *                          then pos = (pos + n_frames) % D_c.  The arithmetic is done on the zero taps too: -0.0 + (+0.0 * -1.0) and
+ *                          +0.0 * inf come out as the reference gives them.
+ *       n_frames > D_c     out = in, ring and position untouched: "Reverb buffer is empty", reverb.rs:92-96 (only with
+ *                          max_frames above 128)
+ * link_flags has the meaning of dspfx_engine_desc.link_flags: DSPFX_LINK_INPUT puts one collect_and_average hop,
+ * (0.0f + v) / f32(0.0001 + 1.0) (node.rs:162-194, an IEEE division), ahead of the node on the channels that carry one (in
+ * either branch above); DSPFX_LINK_INTERNAL has nothing to act on.
+ * Memory: cap = dspfx_delay_len(max_seconds, page_round) frames of ring per channel, n_channels * cap * 4 bytes, allocated by
+ * create and NEVER zeroed: a store says that the channel's next D_c taps read as +0.0, so it costs one small kernel over the
+ * stored channels, never a memset.  Plus 16 bytes of tables per channel.
+ * A channel's output is the same bits in either layout, in place or not, on any stream, and whatever its neighbours carry. */
+typedef struct dspfx_delays dspfx_delays;
+typedef struct dspfx_delays_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    float max_seconds;        /* the longest delay a store may ask for: cap = dspfx_delay_len(max_seconds, page_round) */
+    uint32_t page_round;      /* 0 / 1: the reading of seconds -> frames, as dspfx_delay_len's */
+    uint32_t link_flags;      /* DSPFX_LINK_INTERNAL | DSPFX_LINK_INPUT; any other bit: DSPFX_ERR_INVALID */
+} dspfx_delays_desc;
+/* PURE HOST function (no GPU, no bank): the ring frames per channel and the ring bytes of a bank of `channels` channels.
+ * channels of 0 or above 2^32 - 256, or a cap above 2^31 frames: DSPFX_ERR_INVALID, the reason in dspfx_delays_last_error(NULL). */
+int dspfx_delays_plan(uint64_t channels, float max_seconds, int page_round, uint32_t *cap_out, uint64_t *bytes_out);
+/* A bad descriptor (what dspfx_delays_plan refuses, a tile that is not a power of two dividing n_channels, an unknown link flag,
+ * another ABI version, max_frames of 0) is DSPFX_ERR_INVALID with the reason in dspfx_delays_last_error of a NULL bank (kept per
+ * thread); all of that is checked before any device work.  Rings that do not fit the device: DSPFX_ERR_OOM and the reason. */
+int dspfx_delays_create(const dspfx_delays_desc *desc, dspfx_delays **out);
+int dspfx_delays_destroy(dspfx_delays *d);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_delays_last_error(const dspfx_delays *d);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out == in works in place
+ * (a thread rewrites the elements it read); any other overlap is the caller's error.  Asynchronous on `stream`; a run on
+ * another stream than the one before first waits (on the device) for that one, since the rings are the bank's (the rules of
+ * dspfx_strips_run).  Queued slider stores go onto the stream ahead of the kernel, in the order they were made. */
+int dspfx_delays_run(dspfx_delays *d, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Stores the sliders of channels [first_channel, first_channel + count) from host arrays of `count` values each.  host_seconds
+ * or host_decay may be NULL: that slider keeps each channel's value (0.5 for a channel never stored, or dropped since: the
+ * reference's defaults, reverb.rs:29-38), and the store still gives every channel of the range its new zero ring.  BOTH NULL
+ * removes the node for the range; a later store starts from a zero ring.  A store that needs D_c > cap on any of its channels,
+ * or whose range lies outside the bank's channels, is refused WHOLE: DSPFX_ERR_INVALID, the reason in dspfx_delays_last_error,
+ * nothing changed.  The contract of dspfx_strips_set_gain otherwise: callable from any thread while runs are in flight, never
+ * waits for the device or for a run; the values are staged in page-locked memory and queued, and a run submitted after the call
+ * returns sees the store, whole, the runs submitted before it do not. */
+int dspfx_delays_set_delay(dspfx_delays *d, const float *host_seconds, const float *host_decay, uint64_t first_channel, uint64_t count);
+/* Every present channel's ring back to zeros at position 0; the sliders and the nodes stay.  Queued on the stream last used. */
+int dspfx_delays_reset(dspfx_delays *d);
+/* 1 / 0 per channel of [first_channel, first_channel + count): it carries a node, as all stores made so far left it (host tables). */
+int dspfx_delays_present(dspfx_delays *d, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+/* D_c per channel of the range, 0 where there is no node, from the same host tables. */
+int dspfx_delays_lengths(dspfx_delays *d, uint32_t *host_lengths_out, uint64_t first_channel, uint64_t count);
+
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
  * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain

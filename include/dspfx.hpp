@@ -560,6 +560,63 @@ inline std::vector<float> strips_coeffs(const float (&raw6)[6]) {
     return k;
 }
 
+// Per-channel Reverb (feedback delay) sliders (include/dspfx.h, dspfx_delays_*): channel c may carry one Reverb node with its own
+// seconds and decay and its own ring of dspfx_delay_len(seconds, page_round) frames, over a device block in the layout of
+// tile_channels.  A node exists for a channel from the first store that names it until it is dropped; a fresh bank copies its
+// input.  Every store is the reference's slider change: the stored channels start again from a zero ring.  max_seconds sizes the
+// rings (delays_plan).  Where ChannelStrips goes: between Engine::process and the room mixes.
+class ChannelDelays {
+  public:
+    ChannelDelays(std::uint32_t channels, float max_seconds = 0.5f, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE,
+                  std::uint32_t link_flags = 0, bool page_round = false, int device = 0) {
+        const dspfx_delays_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, max_seconds, page_round ? 1u : 0u, link_flags};
+        const int rc = dspfx_delays_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_delays_last_error(nullptr) ? dspfx_delays_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelDelays() { dspfx_delays_destroy(p_); }
+    ChannelDelays(const ChannelDelays &) = delete;
+    ChannelDelays &operator=(const ChannelDelays &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_delays_run(p_, in, out, n_frames, stream)); }
+    // the sliders of channels [first_channel, first_channel + count) from host arrays; a nullptr slider keeps each channel's value, both
+    // nullptr drop the node.  Refused whole when a channel would need more than the bank's ring.  Any thread; never waits.
+    void set_delay(const float *host_seconds, const float *host_decay, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_delays_set_delay(p_, host_seconds, host_decay, first_channel, count));
+    }
+    // every present channel's ring back to zeros, the sliders and the nodes kept
+    void reset() { chk(dspfx_delays_reset(p_)); }
+    // 1 / 0 per channel: it carries a node; and each channel's ring length, 0 where there is none -- as all stores so far left them
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_delays_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> lengths(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_delays_lengths(p_, m.data(), first_channel, count));
+        return m;
+    }
+    dspfx_delays *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_delays_last_error(p_) ? dspfx_delays_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_delays *p_ = nullptr;
+};
+
+// The ring frames per channel and the ring bytes of a ChannelDelays bank (dspfx_delays_plan: a pure host function, no GPU).
+struct DelaysPlan {
+    std::uint32_t cap;
+    std::uint64_t bytes;
+};
+inline DelaysPlan delays_plan(std::uint64_t channels, float max_seconds = 0.5f, bool page_round = false) {
+    DelaysPlan r{0, 0};
+    const int rc = dspfx_delays_plan(channels, max_seconds, page_round ? 1 : 0, &r.cap, &r.bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_delays_last_error(nullptr));
+    return r;
+}
+
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
