@@ -31,10 +31,12 @@
 // were made: a copy, a scatter into the source-major table, and a recount of w and d for the listeners touched -- d is computed on the
 // device with dspfx_link_divisor's own f32 expression, so no store waits for the device.
 //
-// Seated banks (dspfx_mixmatrix_create_seats; the second group of kernels): a room owns S_r seats and an S_r x S_r table that never
-// moves, a channel holds one seat of one room or none, and dspfx_mixmatrix_assign reseats channels live through the same queue: one
-// row and one column per mover, never the table.  The seating rule is reseat() below, once, for the bank and for
-// dspfx_mixmatrix_reseat.  A bank made by dspfx_mixmatrix_create runs what it always ran.
+// Seated banks (dspfx_mixmatrix_create_seats): a room owns S_r seats and an S_r x S_r table that never moves, a channel holds one
+// seat of one room or none, and dspfx_mixmatrix_assign reseats channels live through the same queue: one row and one column per
+// mover, never the table.  The seating rule is reseat() below, once, for the bank and for dspfx_mixmatrix_reseat.  The two kinds of
+// bank share every kernel and every host path: what a room-local index means -- a member, or a seat -- is a template argument of the
+// run, fill, store and recount kernels ("the two seatings" below) and data on the host.  A bank made by dspfx_mixmatrix_create runs
+// the instantiation that is, instruction for instruction, what it always ran.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -72,6 +74,30 @@ struct Item {
 
 __host__ __device__ inline uint32_t edge(uint32_t n) { return (n + 31u) & ~31u; }
 
+constexpr uint32_t NONE = DSPFX_MIXMATRIX_NO_ROOM;
+
+// ---- the two seatings -----------------------------------------------------------------------------------------------------------
+// What a room-local index i means.  SEATED = false (dspfx_mixmatrix_create): member i of the room, channel c0 + i; the table's edge is
+// n rounded up to 32 and the indices from n on are its padding, which nobody holds.  SEATED = true (dspfx_mixmatrix_create_seats):
+// seat i of S_r = Room.n seats (a multiple of 32, so the table has no padding), and Room.c0 is the room's first entry of seat_chan,
+// which holds the channel in every seat (NONE: the seat is empty).  The row and the column of an index nobody holds are +0.0 in the
+// table -- every store keeps that -- so a seated room computes what an unseated one computes for S_r contiguous members of which
+// the absent ones carry +0.0: the same chain, term for term.
+template <bool SEATED>
+__device__ inline uint32_t table_edge(const Room &rm) {
+    return SEATED ? rm.n : edge(rm.n);
+}
+// the channel at index i (below the table's edge) of the room; NONE: nobody
+template <bool SEATED>
+__device__ inline uint32_t chan_of(const Room &rm, const uint32_t *__restrict__ seat_chan, uint32_t i) {
+    if (SEATED) return seat_chan[rm.c0 + i];
+    return i < rm.n ? rm.c0 + i : NONE;
+}
+template <bool SEATED>
+__device__ inline bool taken(const Room &rm, const uint32_t *__restrict__ seat_chan, uint32_t i) {
+    return chan_of<SEATED>(rm, seat_chan, i) != NONE;
+}
+
 struct RunArgs {
     const float *__restrict__ in;
     float *__restrict__ out;
@@ -80,13 +106,20 @@ struct RunArgs {
     const Room *__restrict__ rooms;
     const Item *__restrict__ items;
     uint32_t N, W, nf, normalise;
+    const uint32_t *__restrict__ seat_chan;      // a seated bank's; the other's kernel never reads it
 };
 
+// The seatings differ in the table's edge and in two addresses (written out here, not through chan_of: each instantiation keeps the
+// instruction stream it had as a kernel of its own): the source at index s is x[..][c0 + s], or x[..][seat_chan[s]], and listener
+// l's row goes to out[..][c0 + l], or out[..][seat_chan[l]].  An index nobody holds is not loaded (+0.0 in LDS) and not stored.  The
+// seat entry of a chunk is fetched one chunk ahead of the chunk's own loads, so the samples' addresses never wait for it
+template <bool SEATED>
 __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
     __shared__ float xs[FT * XS];                        // [frame][source of the chunk]
     const Item it = a.items[blockIdx.x];
     const Room rm = a.rooms[it.room];
-    const uint32_t n = rm.n, P = edge(n), c0 = rm.c0;
+    const uint32_t n = rm.n, P = SEATED ? n : edge(n), c0 = rm.c0;
+    const uint32_t *sc = a.seat_chan + c0;               // (SEATED)
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t r = lane & 31u, h = lane >> 5;        // MFMA operand maps: A[i = r][k = h], B[k = h][j = r]
     const uint32_t lt = it.l0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) * 32u;     // the wave's listener tile (uniform)
@@ -96,133 +129,34 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
 
     // (the frame pass is a grid dimension and not a loop here: a loop would have the compiler keep every row's offset live across it)
     const uint32_t f0 = blockIdx.y * FT;
-    {
-        f32x16 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-        float st[16], bn[KC / 2];
-        // the chunk from source k0 into registers: samples outside the room or the block are +0.0 and are not read
-        // the frames of the pass this thread stages: sf + 8 i for i < nst (a running pointer and one count: no offset per row is kept)
-        const uint32_t left = a.nf - f0, nst = left > sf ? (left - sf + 7u) / 8u : 0u;
-        const float *tabr = a.tab + rm.off;              // uniform; the table has P * P <= 2^20 elements: 32-bit offsets
-        const uint32_t bcol = (active ? lt + r : 0u) + h * P;
-        auto gload = [&](uint32_t k0) {
-            const uint32_t s = k0 + ss;
-            const float *p = a.in + lay(0, c0 + (s < n ? s : 0u), a.nf, a.N, a.W) + (size_t)(f0 + sf) * rs;
-            const uint32_t cnt = s < n ? nst : 0u;
-#pragma unroll
-            for (uint32_t i = 0; i < 16; ++i) {
-                st[i] = i < cnt ? *p : 0.0f;
-                p += 8u * rs;
-            }
-            if (active) {
-                const uint32_t o = k0 * P + bcol;
-#pragma unroll
-                for (uint32_t j = 0; j < KC / 2; ++j) bn[j] = tabr[o + 2u * j * P];
-            }
-        };
-        gload(0);
-#pragma unroll 1
-        for (uint32_t k0 = 0; k0 < P; k0 += KC) {
-            __syncthreads();                             // the chunk before is read
-#pragma unroll
-            for (uint32_t i = 0; i < 16; ++i) xs[(sf + 8u * i) * XS + ss] = st[i];
-            float b[KC / 2];
-#pragma unroll
-            for (uint32_t j = 0; j < KC / 2; ++j) b[j] = bn[j];
-            __syncthreads();
-            if (k0 + KC < P) gload(k0 + KC);
-            if (active) {
-                // the A values of k step j + 1 are read from LDS ahead of the MFMAs of step j; the fence keeps the compiler from
-                // hoisting all 64 reads of the chunk (and their registers) in front of the first MFMA
-                const float *xr = xs + r * XS + h;
-                float an[4], ac[4];
-#pragma unroll
-                for (uint32_t t = 0; t < 4; ++t) an[t] = xr[t * 32u * XS];
-#pragma unroll
-                for (uint32_t j = 0; j < KC / 2; ++j) {
-#pragma unroll
-                    for (uint32_t t = 0; t < 4; ++t) ac[t] = an[t];
-                    if (j + 1 < KC / 2) {
-#pragma unroll
-                        for (uint32_t t = 0; t < 4; ++t) an[t] = xr[t * 32u * XS + 2u * (j + 1)];
-                    }
-#pragma unroll
-                    for (uint32_t t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[t], b[j], acc[t], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        // C/D: column = r (the listener), row = (reg & 3) + 8 (reg >> 2) + 4 h (the frame of the tile)
-        const uint32_t l = lt + r;
-        if (active && l < n) {
-            const uint32_t c = c0 + l;
-            const float d = a.div[c];
-            float *po = a.out + lay(0, c, a.nf, a.N, a.W);
-#pragma unroll
-            for (uint32_t t = 0; t < 4; ++t)
-#pragma unroll
-                for (uint32_t i = 0; i < 16; ++i) {
-                    const uint32_t f = f0 + t * 32u + (i & 3u) + 8u * (i >> 2) + 4u * h;
-                    if (f < a.nf) {
-                        float v = acc[t][i];
-                        if (d == 0.0f) v = 0.0f;
-                        else if (a.normalise) v = __fdiv_rn(v, d);
-                        __builtin_nontemporal_store(v, po + (size_t)f * rs);
-                    }
-                    if ((i & 3u) == 3u) __builtin_amdgcn_sched_barrier(0);   // (four rows' addresses at a time, not sixty-four)
-                }
-        }
-    }
-}
-
-// ---- seated banks (dspfx_mixmatrix_create_seats) --------------------------------------------------------------------------------
-// A room of a seated bank is S_r seats (a multiple of 32, so its table has no padding): Room.n = S_r and Room.c0 = the room's first
-// entry of seat_chan, which holds the channel in every seat (NONE: the seat is empty).  An empty seat's row and column are +0.0 in
-// the table -- every store keeps that -- so a room computes what the kernel above computes for S_r contiguous members of which the
-// absent ones carry +0.0: the same chain, term for term.
-constexpr uint32_t NONE = DSPFX_MIXMATRIX_NO_ROOM;
-
-struct SeatedArgs {
-    RunArgs r;
-    const uint32_t *__restrict__ seat_chan;
-};
-
-// mixmatrix_run with two addresses changed: the source in seat s is x[..][seat_chan[s]], and listener seat l's row goes to
-// out[..][seat_chan[l]].  An empty seat is not loaded (+0.0 in LDS) and not stored.  The seat index of a chunk is fetched one chunk
-// ahead of the chunk's own loads, so the samples' addresses never wait for it
-__global__ __launch_bounds__(WG, 3) void mixmatrix_run_seated(SeatedArgs sa) {
-    __shared__ float xs[FT * XS];                        // [frame][source of the chunk]
-    const RunArgs &a = sa.r;
-    const Item it = a.items[blockIdx.x];
-    const Room rm = a.rooms[it.room];
-    const uint32_t P = rm.n;
-    const uint32_t *sc = sa.seat_chan + rm.c0;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t r = lane & 31u, h = lane >> 5;        // MFMA operand maps: A[i = r][k = h], B[k = h][j = r]
-    const uint32_t lt = it.l0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) * 32u;     // the wave's listener tile (uniform)
-    const bool active = lt < P;                          // wave-uniform; an idle wave still stages its share of x
-    const uint32_t ss = tid & 31u, sf = tid >> 5;        // staging: seat ss of the chunk, frames sf + 8 i
-    const size_t rs = a.W ? a.W : a.N;
-    const uint32_t f0 = blockIdx.y * FT;
     f32x16 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
     float st[16], bn[KC / 2];
+    // the chunk from source k0 into registers: samples outside the room or the block are +0.0 and are not read
+    // the frames of the pass this thread stages: sf + 8 i for i < nst (a running pointer and one count: no offset per row is kept)
     const uint32_t left = a.nf - f0, nst = left > sf ? (left - sf + 7u) / 8u : 0u;
-    const float *tabr = a.tab + rm.off;
+    const float *tabr = a.tab + rm.off;                  // uniform; the table has P * P <= 2^20 elements: 32-bit offsets
     const uint32_t bcol = (active ? lt + r : 0u) + h * P;
-    uint32_t cn = sc[ss];                                // who sits in this thread's seat of the next chunk to load (P >= 32)
+    uint32_t cn = 0;                                     // SEATED: who sits in this thread's seat of the next chunk to load (P >= 32)
+    if constexpr (SEATED) cn = sc[ss];
     auto gload = [&](uint32_t k0) {
-        const uint32_t ch = cn;
-        if (k0 + KC < P) cn = sc[k0 + KC + ss];
-        const bool taken = ch != NONE;
-        const float *p = a.in + lay(0, taken ? ch : 0u, a.nf, a.N, a.W) + (size_t)(f0 + sf) * rs;
-        const uint32_t cnt = taken ? nst : 0u;
+        bool held;
+        uint32_t ch;                                     // the channel whose samples p walks; nobody's index: any valid one, unread
+        if constexpr (SEATED) {
+            ch = cn;
+            if (k0 + KC < P) cn = sc[k0 + KC + ss];
+            held = ch != NONE;
+            if (!held) ch = 0u;
+        } else {
+            const uint32_t s = k0 + ss;
+            held = s < n;
+            ch = c0 + (held ? s : 0u);
+        }
+        const float *p = a.in + lay(0, ch, a.nf, a.N, a.W) + (size_t)(f0 + sf) * rs;
+        const uint32_t cnt = held ? nst : 0u;
 #pragma unroll
         for (uint32_t i = 0; i < 16; ++i) {
             st[i] = i < cnt ? *p : 0.0f;
@@ -246,6 +180,8 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run_seated(SeatedArgs sa) {
         __syncthreads();
         if (k0 + KC < P) gload(k0 + KC);
         if (active) {
+            // the A values of k step j + 1 are read from LDS ahead of the MFMAs of step j; the fence keeps the compiler from
+            // hoisting all 64 reads of the chunk (and their registers) in front of the first MFMA
             const float *xr = xs + r * XS + h;
             float an[4], ac[4];
 #pragma unroll
@@ -264,9 +200,18 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run_seated(SeatedArgs sa) {
             }
         }
     }
-    // C/D: column = r (the listener's seat), row = (reg & 3) + 8 (reg >> 2) + 4 h (the frame of the tile)
-    const uint32_t c = active ? sc[lt + r] : NONE;
-    if (c != NONE) {
+    // C/D: column = r (the listener), row = (reg & 3) + 8 (reg >> 2) + 4 h (the frame of the tile)
+    bool heard;
+    uint32_t c;
+    if constexpr (SEATED) {
+        c = active ? sc[lt + r] : NONE;
+        heard = c != NONE;
+    } else {
+        const uint32_t l = lt + r;
+        heard = active && l < n;
+        c = c0 + l;
+    }
+    if (heard) {
         const float d = a.div[c];
         float *po = a.out + lay(0, c, a.nf, a.N, a.W);
 #pragma unroll
@@ -280,12 +225,12 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run_seated(SeatedArgs sa) {
                     else if (a.normalise) v = __fdiv_rn(v, d);
                     __builtin_nontemporal_store(v, po + (size_t)f * rs);
                 }
-                if ((i & 3u) == 3u) __builtin_amdgcn_sched_barrier(0);
+                if ((i & 3u) == 3u) __builtin_amdgcn_sched_barrier(0);   // (four rows' addresses at a time, not sixty-four)
             }
     }
 }
 
-// the channels in no room read +0.0 in every frame; launched ahead of mixmatrix_run_seated while the bank has any
+// the channels in no room read +0.0 in every frame; launched ahead of a seated bank's mixmatrix_run while the bank has any
 __global__ __launch_bounds__(WG) void mixmatrix_zero_roomless(float *__restrict__ out, const uint32_t *__restrict__ room_of, uint32_t N, uint32_t W, uint32_t nf) {
     const uint32_t c = blockIdx.x * WG + threadIdx.x;
     if (c >= N || room_of[c] != NONE) return;
@@ -294,31 +239,33 @@ __global__ __launch_bounds__(WG) void mixmatrix_zero_roomless(float *__restrict_
     for (uint32_t f = 0; f < nf; ++f) po[(size_t)f * rs] = 0.0f;
 }
 
-// a preset into the tables of rooms [first_room, first_room + gridDim.x) of a seated bank: mix-minus is 1.0 between two different
-// TAKEN seats
-__global__ __launch_bounds__(WG) void mixmatrix_fill_seated(float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
-                                                            uint32_t first_room, uint32_t preset) {
+// a preset into the tables of rooms [first_room, first_room + gridDim.x): one workgroup per room.  Mix-minus is 1.0 between two
+// different TAKEN indices; everything else, the padding with it, is +0.0
+template <bool SEATED>
+__global__ __launch_bounds__(WG) void mixmatrix_fill(float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
+                                                     uint32_t first_room, uint32_t preset) {
     const Room rm = rooms[first_room + blockIdx.x];
-    const uint32_t S = rm.n;
-    const uint32_t *sc = seat_chan + rm.c0;
+    const uint32_t P = table_edge<SEATED>(rm);
     float *t = tab + rm.off;
-    for (uint32_t e = threadIdx.x; e < S * S; e += WG) {
-        const uint32_t s = e / S, l = e - s * S;
-        t[e] = (preset == DSPFX_MIXMATRIX_MIX_MINUS && s != l && sc[s] != NONE && sc[l] != NONE) ? 1.0f : 0.0f;
+    for (uint32_t e = threadIdx.x; e < P * P; e += WG) {
+        const uint32_t s = e / P, l = e - s * P;
+        t[e] = (preset == DSPFX_MIXMATRIX_MIX_MINUS && s != l && taken<SEATED>(rm, seat_chan, s) && taken<SEATED>(rm, seat_chan, l)) ? 1.0f : 0.0f;
     }
 }
 
-// staged lines of a seated room: words = [count] seats, then [count][S] values; line i belongs to seat words[i], laid as
-// mixmatrix_store lays it.  A value at an empty seat is stored as +0.0
-__global__ __launch_bounds__(WG) void mixmatrix_store_seated(float *__restrict__ tab, const uint32_t *__restrict__ words, const uint32_t *__restrict__ seat_chan,
-                                                             Room rm, uint32_t count, uint32_t cols) {
-    const uint32_t e = blockIdx.x * WG + threadIdx.x, S = rm.n;
-    if (e >= count * S) return;
-    const uint32_t i = e / S, j = e - i * S, q = words[i];
-    const float v = seat_chan[rm.c0 + j] != NONE ? __uint_as_float(words[count + e]) : 0.0f;
+// staged lines into the room's source-major table: words = [count] room-local indices, then [count][Room.n] values (a line is as long
+// as the room has members, or seats).  Line i belongs to index q = words[i].  cols = 0: it is what listener q hears, vals[i][s] ->
+// Mt[s][q]; cols = 1: it is how loud source q is for each listener, vals[i][l] -> Mt[q][l].  A value at an empty seat is stored as +0.0
+template <bool SEATED>
+__global__ __launch_bounds__(WG) void mixmatrix_store(float *__restrict__ tab, const uint32_t *__restrict__ words, const uint32_t *__restrict__ seat_chan,
+                                                      Room rm, uint32_t count, uint32_t cols) {
+    const uint32_t e = blockIdx.x * WG + threadIdx.x, n = rm.n, P = table_edge<SEATED>(rm);
+    if (e >= count * n) return;
+    const uint32_t i = e / n, j = e - i * n, q = words[i];
+    const float v = taken<SEATED>(rm, seat_chan, j) ? __uint_as_float(words[count + e]) : 0.0f;
     float *t = tab + rm.off;
-    if (cols) t[q * S + j] = v;
-    else t[j * S + q] = v;
+    if (cols) t[(size_t)q * P + j] = v;
+    else t[(size_t)j * P + q] = v;
 }
 
 // words = [n] (seat_chan index, channel or NONE) pairs: the seats an assign changed, each with who sits there after the call
@@ -352,61 +299,22 @@ __global__ __launch_bounds__(WG) void mixmatrix_pairs(float *__restrict__ tab, c
     tab[rm.off + (size_t)(ls & 0xFFFFu) * P + (ls >> 16)] = __uint_as_float(words[3u * i + 2u]);
 }
 
-// w and d of every taken seat's listener of the rooms list[blockIdx.x] (list = nullptr: first_room + blockIdx.x), as
-// mixmatrix_recount counts them
-__global__ __launch_bounds__(WG) void mixmatrix_recount_seated(const float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
-                                                               float *__restrict__ div, const uint32_t *__restrict__ list, uint32_t first_room) {
+// w and d of the listeners at indices [i0, i0 + count) -- those that exist and are taken -- of the rooms list[blockIdx.x] (list =
+// nullptr: first_room + blockIdx.x): w = the entries of the listener's row that are not +-0.0 (the padding never is); d =
+// dspfx_link_divisor(w) by its own f32 expression (node.rs:166,179: sequential f32 increments from 0.0001), 0.0 for a row without a
+// wired entry
+template <bool SEATED>
+__global__ __launch_bounds__(WG) void mixmatrix_recount(const float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ seat_chan,
+                                                        float *__restrict__ div, const uint32_t *__restrict__ list, uint32_t first_room, uint32_t i0,
+                                                        uint32_t count) {
     const Room rm = rooms[list ? list[blockIdx.x] : first_room + blockIdx.x];
-    const uint32_t S = rm.n, l = blockIdx.y * WG + threadIdx.x;
-    if (l >= S) return;
-    const uint32_t c = seat_chan[rm.c0 + l];
+    const uint32_t P = table_edge<SEATED>(rm), at = blockIdx.y * WG + threadIdx.x, l = i0 + at;
+    if (at >= count || l >= P) return;
+    const uint32_t c = chan_of<SEATED>(rm, seat_chan, l);
     if (c == NONE) return;
     const float *t = tab + rm.off + l;
     uint32_t w = 0;
-    for (uint32_t s = 0; s < S; ++s) w += t[(size_t)s * S] != 0.0f;
-    float d = 0.0f;
-    if (w) {
-        d = 0.0001f;
-        for (uint32_t k = 0; k < w; ++k) d = d + 1.0f;
-    }
-    div[c] = d;
-}
-
-// a preset into the tables of rooms [first_room, first_room + gridDim.x): one workgroup per room, the padding zero
-__global__ __launch_bounds__(WG) void mixmatrix_fill(float *__restrict__ tab, const Room *__restrict__ rooms, uint32_t first_room, uint32_t preset) {
-    const Room rm = rooms[first_room + blockIdx.x];
-    const uint32_t n = rm.n, P = edge(n);
-    float *t = tab + rm.off;
-    for (uint32_t e = threadIdx.x; e < P * P; e += WG) {
-        const uint32_t s = e / P, l = e - s * P;
-        t[e] = (preset == DSPFX_MIXMATRIX_MIX_MINUS && s < n && l < n && s != l) ? 1.0f : 0.0f;
-    }
-}
-
-// staged values [count][n] into the room's source-major table: cols = 0: row i is what listener l0 + i hears, vals[i][s] -> Mt[s][l0 + i];
-// cols = 1: row i is how loud source l0 + i is for each listener, vals[i][l] -> Mt[l0 + i][l]
-__global__ __launch_bounds__(WG) void mixmatrix_store(float *__restrict__ tab, const float *__restrict__ vals, uint64_t off, uint32_t n, uint32_t l0,
-                                                      uint32_t count, uint32_t cols) {
-    const uint32_t e = blockIdx.x * WG + threadIdx.x;
-    if (e >= count * n) return;
-    const uint32_t i = e / n, j = e - i * n, P = edge(n);
-    float *t = tab + off;
-    if (cols) t[(size_t)(l0 + i) * P + j] = vals[e];
-    else t[(size_t)j * P + l0 + i] = vals[e];
-}
-
-// w and d of listeners [first, first + count): w = the entries of the listener's row that are not +-0.0; d = dspfx_link_divisor(w) by
-// its own f32 expression (node.rs:166,179: sequential f32 increments from 0.0001), 0.0 for a row without a wired entry
-__global__ __launch_bounds__(WG) void mixmatrix_recount(const float *__restrict__ tab, const Room *__restrict__ rooms, const uint32_t *__restrict__ room_of,
-                                                        float *__restrict__ div, uint32_t first, uint32_t count) {
-    const uint32_t i = blockIdx.x * WG + threadIdx.x;
-    if (i >= count) return;
-    const uint32_t c = first + i;
-    const Room rm = rooms[room_of[c]];
-    const uint32_t n = rm.n, P = edge(n), l = c - rm.c0;
-    const float *t = tab + rm.off + l;
-    uint32_t w = 0;
-    for (uint32_t s = 0; s < n; ++s) w += t[(size_t)s * P] != 0.0f;
+    for (uint32_t s = 0; s < P; ++s) w += t[(size_t)s * P] != 0.0f;
     float d = 0.0f;
     if (w) {
         d = 0.0001f;
@@ -417,12 +325,13 @@ __global__ __launch_bounds__(WG) void mixmatrix_recount(const float *__restrict_
 
 thread_local std::string g_err;        // the reason of the last failed create or plan on this thread
 
-// a store's vals: [count][n]; a fill has none
-// ... of a seated bank: [count] seats, then [count][S_r] values (the buffer is 4-byte words: integers travel as their bits).  An
-// assign's words: [n_seats] (seat_chan index, channel) pairs, [n_chans] (channel, room) pairs, [n_lines] (room, seat | preset << 31)
-// pairs, [n_rooms] rooms to recount.  Pairs: [n_lines] (room, listener << 16 | source, gain) triples, [n_rooms] rooms
+// a store's vals (the buffer is 4-byte words: integers travel as their bits).  Rows or columns: [count] room-local indices (members,
+// or seats), then [count][Room.n] values; a fill has none.  An assign's words: [n_seats] (seat_chan index, channel) pairs, [n_chans]
+// (channel, room) pairs, [n_lines] (room, seat | preset << 31) pairs, [n_rooms] rooms to recount.  Pairs: [n_lines] (room,
+// listener << 16 | source, gain) triples, [n_rooms] rooms
+enum Kind { ROWS, COLS, FILL, ASSIGN, PAIRS };
 struct StoreFields {
-    int kind = 0;                // 0: rows, 1: columns, 2: fill, 3: an assign, 4: pairs
+    Kind kind = ROWS;
     uint32_t room = 0, l0 = 0, count = 0;        // rows / columns: room-local first index and count; fill: rooms [room, room + count)
     uint32_t preset = 0;
     size_t n_seats = 0, n_chans = 0, n_lines = 0, n_rooms = 0;
@@ -566,10 +475,9 @@ struct dspfx_mixmatrix : BankError {
     std::vector<Room> hrooms;
     std::mutex mu;                               // run / destroy
     Stores stores;                               // the matrix stores
-    float *tab = nullptr, *div = nullptr, *stage = nullptr;      // stage: [maxn][maxn], where a drained store's values land
+    float *tab = nullptr, *div = nullptr, *stage = nullptr;      // stage: [maxn][maxn + 1], where a drained store's words land
     Room *rooms = nullptr;
     Item *items = nullptr;
-    uint32_t *room_of = nullptr;
     uint32_t n_items = 0, maxn = 0;
     size_t stage_words = 0;                      // the size of `stage`; longer word lists go through it in slices
     hipEvent_t ev = nullptr;
@@ -579,10 +487,11 @@ struct dspfx_mixmatrix : BankError {
     // tables hold the seating after every assign made so far; the device ones (room_of, seat_chan) what the runs drained so far see
     bool seated = false;
     std::mutex smu;                              // the host tables, held from a store's checks to its push (smu, then the queue's lock)
-    std::vector<uint32_t> hroom_of, hseat_of, hseat_chan, occ, hS, hoff;
+    std::vector<uint32_t> hroom_of, hseat_of, hseat_chan, hS, hoff;
+    std::vector<uint32_t> occ;                   // participants per room (either kind of bank: the members, where nobody moves)
     uint64_t hroomless = 0;                      // channels in no room (smu)
     uint64_t roomless = 0;                       // ... by the assigns drained so far (mu)
-    uint32_t *seat_chan = nullptr;
+    uint32_t *room_of = nullptr, *seat_chan = nullptr;
     Seats seats() { return Seats{hroom_of.data(), hseat_of.data(), hseat_chan.data(), occ.data(), hS.data(), hoff.data(), desc.n_groups, desc.n_channels}; }
 };
 
@@ -597,8 +506,22 @@ void release(dspfx_mixmatrix *p) {
     delete p;
 }
 
-hipError_t recount(dspfx_mixmatrix *p, uint32_t first, uint32_t count, hipStream_t s) {
-    mixmatrix_recount<<<(count + WG - 1) / WG, WG, 0, s>>>(p->tab, p->rooms, p->room_of, p->div, first, count);
+// the room and the room-local index (the seat, in a seated bank) of channel c; smu is held on a seated bank
+void place_of(dspfx_mixmatrix *p, uint32_t c, uint32_t &room, uint32_t &index) {
+    if (p->seated) {
+        room = p->hroom_of[c];
+        index = p->hseat_of[c];
+    } else {
+        room = (uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), (uint64_t)c) - p->gs.begin()) - 1;
+        index = c - (uint32_t)p->gs[room];
+    }
+}
+
+// the divisors of the listeners at indices [i0, i0 + count) of rooms [first_room, first_room + n_rooms), or of the n_rooms listed at
+// `list` (device); a range past a room's edge ends there, so count = maxn means whole rooms
+hipError_t recount(dspfx_mixmatrix *p, const uint32_t *list, uint32_t first_room, uint32_t n_rooms, uint32_t i0, uint32_t count, hipStream_t s) {
+    const auto kernel = p->seated ? mixmatrix_recount<true> : mixmatrix_recount<false>;
+    kernel<<<dim3(n_rooms, (count + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, list, first_room, i0, count);
     return hipGetLastError();
 }
 
@@ -610,91 +533,72 @@ hipError_t sliced(dspfx_mixmatrix *p, const uint32_t *src, size_t n, uint32_t re
         const size_t k = std::min(per, n - i);
         hipError_t err = hipMemcpyAsync(p->stage, src + i * rec, k * rec * sizeof(uint32_t), hipMemcpyHostToDevice, s);
         if (err != hipSuccess) return err;
-        launch((const uint32_t *)p->stage, (uint32_t)k);
-        err = hipGetLastError();
+        err = launch((const uint32_t *)p->stage, (uint32_t)k);
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
 }
 
-// a seated bank: the divisors of every listener of the n rooms listed at src (page-locked)
+// the divisors of every listener of the n rooms listed at src (page-locked)
 hipError_t recount_rooms(dspfx_mixmatrix *p, const uint32_t *src, size_t n, hipStream_t s) {
-    return sliced(p, src, n, 1, s, [&](const uint32_t *w, uint32_t k) {
-        mixmatrix_recount_seated<<<dim3(k, (p->maxn + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, w, 0);
-    });
+    return sliced(p, src, n, 1, s, [&](const uint32_t *w, uint32_t k) { return recount(p, w, 0, k, 0, p->maxn, s); });
 }
 
 hipError_t fill_rooms(dspfx_mixmatrix *p, uint32_t first_room, uint32_t count, uint32_t preset, hipStream_t s) {
-    if (p->seated) {
-        mixmatrix_fill_seated<<<count, WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, first_room, preset);
-        hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return err;
-        mixmatrix_recount_seated<<<dim3(count, (p->maxn + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, nullptr, first_room);
-        return hipGetLastError();
-    }
-    mixmatrix_fill<<<count, WG, 0, s>>>(p->tab, p->rooms, first_room, preset);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return err;
-    const uint32_t c0 = (uint32_t)p->gs[first_room], c1 = (uint32_t)p->gs[first_room + count];
-    return recount(p, c0, c1 - c0, s);
+    const auto kernel = p->seated ? mixmatrix_fill<true> : mixmatrix_fill<false>;
+    kernel<<<count, WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, first_room, preset);
+    const hipError_t err = hipGetLastError();
+    return err != hipSuccess ? err : recount(p, nullptr, first_room, count, 0, p->maxn, s);
 }
 
 // one store onto the stream: a fill, or the values into `stage`, the scatter into the table and the recount
 hipError_t apply_store(dspfx_mixmatrix *p, const Store &st, hipStream_t s) {
-    if (st.kind == 2) return fill_rooms(p, st.room, st.count, st.preset, s);
+    if (st.kind == FILL) return fill_rooms(p, st.room, st.count, st.preset, s);
     const uint32_t *words = (const uint32_t *)st.vals;
-    if (st.kind == 3) {                          // an assign: the seats, the rooms of the channels, the lines, the divisors -- in that order
+    if (st.kind == ASSIGN) {                     // the seats, the rooms of the channels, the lines, the divisors -- in that order
         hipError_t err = sliced(p, words, st.n_seats, 2, s, [&](const uint32_t *w, uint32_t k) {
             mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->seat_chan, w, k);
+            return hipGetLastError();
         });
         if (err != hipSuccess) return err;
         words += 2 * st.n_seats;
         err = sliced(p, words, st.n_chans, 2, s, [&](const uint32_t *w, uint32_t k) {
             mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->room_of, w, k);
+            return hipGetLastError();
         });
         if (err != hipSuccess) return err;
         words += 2 * st.n_chans;
         err = sliced(p, words, st.n_lines, 2, s, [&](const uint32_t *w, uint32_t k) {
             mixmatrix_seat_lines<<<k, WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, w);
+            return hipGetLastError();
         });
         if (err != hipSuccess) return err;
         p->roomless = st.roomless;
         return recount_rooms(p, words + 2 * st.n_lines, st.n_rooms, s);
     }
-    if (st.kind == 4) {
-        hipError_t err = sliced(p, words, st.n_lines, 3, s, [&](const uint32_t *w, uint32_t k) {
+    if (st.kind == PAIRS) {
+        const hipError_t err = sliced(p, words, st.n_lines, 3, s, [&](const uint32_t *w, uint32_t k) {
             mixmatrix_pairs<<<(k + WG - 1) / WG, WG, 0, s>>>(p->tab, p->rooms, w, k);
+            return hipGetLastError();
         });
-        if (err != hipSuccess) return err;
-        words += 3 * st.n_lines;
-        if (p->seated) return recount_rooms(p, words, st.n_rooms, s);
-        for (size_t i = 0; i < st.n_rooms && err == hipSuccess; ++i) err = recount(p, p->hrooms[words[i]].c0, p->hrooms[words[i]].n, s);
-        return err;
+        return err != hipSuccess ? err : recount_rooms(p, words + 3 * st.n_lines, st.n_rooms, s);
     }
     const Room &rm = p->hrooms[st.room];
-    if (p->seated) {
-        const size_t n = (size_t)st.count * (rm.n + 1);
-        hipError_t err = hipMemcpyAsync(p->stage, st.vals, n * sizeof(float), hipMemcpyHostToDevice, s);
-        if (err != hipSuccess) return err;
-        mixmatrix_store_seated<<<(st.count * rm.n + WG - 1) / WG, WG, 0, s>>>(p->tab, (const uint32_t *)p->stage, p->seat_chan, rm, st.count, (uint32_t)st.kind);
-        err = hipGetLastError();
-        if (err != hipSuccess) return err;
-        mixmatrix_recount_seated<<<dim3(1, (rm.n + WG - 1) / WG), WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, p->div, nullptr, st.room);
-        return hipGetLastError();
-    }
-    const uint32_t cells = st.count * rm.n;
-    hipError_t err = hipMemcpyAsync(p->stage, st.vals, (size_t)cells * sizeof(float), hipMemcpyHostToDevice, s);
+    hipError_t err = hipMemcpyAsync(p->stage, st.vals, (size_t)st.count * (rm.n + 1) * sizeof(float), hipMemcpyHostToDevice, s);
     if (err != hipSuccess) return err;
-    mixmatrix_store<<<(cells + WG - 1) / WG, WG, 0, s>>>(p->tab, p->stage, rm.off, rm.n, st.l0, st.count, (uint32_t)st.kind);
+    const auto kernel = p->seated ? mixmatrix_store<true> : mixmatrix_store<false>;
+    kernel<<<(st.count * rm.n + WG - 1) / WG, WG, 0, s>>>(p->tab, (const uint32_t *)p->stage, p->seat_chan, rm, st.count, (uint32_t)(st.kind == COLS));
     err = hipGetLastError();
     if (err != hipSuccess) return err;
-    // a row store changes the wired count of its listeners, a column store that of every listener of the room
-    return st.kind == 0 ? recount(p, rm.c0 + st.l0, st.count, s) : recount(p, rm.c0, rm.n, s);
+    // a row store changes the wired count of its listeners -- adjacent members, or seats anywhere in the room -- and a column store
+    // that of every listener of the room
+    const bool own = st.kind == ROWS && !p->seated;
+    return recount(p, nullptr, st.room, 1, own ? st.l0 : 0u, own ? st.count : rm.n, s);
 }
 
 // rows or columns [first, first + count) of one room, row_len values each
-int store_lines(dspfx_mixmatrix *p, int kind, const float *vals, uint32_t row_len, uint64_t first, uint64_t count) {
-    const char *what = kind ? "set_cols" : "set_rows";
+int store_lines(dspfx_mixmatrix *p, Kind kind, const float *vals, uint32_t row_len, uint64_t first, uint64_t count) {
+    const char *what = kind == COLS ? "set_cols" : "set_rows";
     char buf[224];
     if (!vals) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: no values", what);
@@ -702,100 +606,67 @@ int store_lines(dspfx_mixmatrix *p, int kind, const float *vals, uint32_t row_le
     }
     std::string why;                             // (a range that begins at N is in no room: not even an empty one is inside)
     if (check_range("mixmatrix", what, first, count, p->desc.n_channels, why, false) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, why.c_str());
+    std::lock_guard<std::mutex> lk(p->smu);
+    uint32_t room, l0;
+    place_of(p, (uint32_t)first, room, l0);
     if (p->seated) {
-        // lines by seat: the channels must share a room by the seating so far (any seats of it), and a line is S_r values
-        std::lock_guard<std::mutex> lk(p->smu);
-        const uint32_t room = p->hroom_of[first];
+        // lines by seat: the channels must share a room by the seating so far (any seats of it)
         for (uint64_t c = first; c < first + count || c == first; ++c)
             if (p->hroom_of[c] != room || room == NONE) {
                 std::snprintf(buf, sizeof buf, "mixmatrix %s: channels [%llu, %llu + %llu) are not in one room by the seating (channel %llu is not in the room of the first)",
                               what, (unsigned long long)first, (unsigned long long)first, (unsigned long long)count, (unsigned long long)c);
                 return p->fail(DSPFX_ERR_INVALID, buf);
             }
-        const uint32_t S = p->hS[room];
-        if (row_len != S) {
-            std::snprintf(buf, sizeof buf, "mixmatrix %s: a row of %u values, and room %u has %u seats", what, row_len, room, S);
-            return p->fail(DSPFX_ERR_INVALID, buf);
-        }
-        if (count == 0) return DSPFX_OK;
-        Store st;
-        st.kind = kind;
-        st.room = room;
-        st.count = (uint32_t)count;
-        const size_t cells = (size_t)count * S;
-        if (!p->stores.staging(p->desc.device, count + cells, st)) {
-            std::snprintf(buf, sizeof buf, "mixmatrix %s: no page-locked memory for the staged values", what);
-            return p->fail(DSPFX_ERR_OOM, buf);
-        }
-        std::memcpy(st.vals, p->hseat_of.data() + first, count * sizeof(uint32_t));
-        std::memcpy(st.vals + count, vals, cells * sizeof(float));
-        p->stores.push(st);
-        return DSPFX_OK;
-    }
-    const uint32_t room =(uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), first) - p->gs.begin()) - 1;
-    const Room &rm = p->hrooms[room];
-    if (first + count > (uint64_t)rm.c0 + rm.n) {
+    } else if (first + count > p->gs[room + 1]) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: channels [%llu, %llu + %llu) are not in one room (room %u is [%u, %u))", what,
-                      (unsigned long long)first, (unsigned long long)first, (unsigned long long)count, room, rm.c0, rm.c0 + rm.n);
+                      (unsigned long long)first, (unsigned long long)first, (unsigned long long)count, room, (uint32_t)p->gs[room], (uint32_t)p->gs[room + 1]);
         return p->fail(DSPFX_ERR_INVALID, buf);
     }
-    if (row_len != rm.n) {
-        std::snprintf(buf, sizeof buf, "mixmatrix %s: a row of %u values, and room %u has %u members", what, row_len, room, rm.n);
+    const uint32_t len = p->hrooms[room].n;      // a line is as long as the room has members, or seats
+    if (row_len != len) {
+        std::snprintf(buf, sizeof buf, "mixmatrix %s: a row of %u values, and room %u has %u %s", what, row_len, room, len, p->seated ? "seats" : "members");
         return p->fail(DSPFX_ERR_INVALID, buf);
     }
     if (count == 0) return DSPFX_OK;
     Store st;
     st.kind = kind;
     st.room = room;
-    st.l0 = (uint32_t)first - rm.c0;
+    st.l0 = l0;
     st.count = (uint32_t)count;
-    const size_t cells = (size_t)count * rm.n;
-    if (!p->stores.staging(p->desc.device, cells, st)) {
+    const size_t cells = (size_t)count * len;
+    if (!p->stores.staging(p->desc.device, count + cells, st)) {
         std::snprintf(buf, sizeof buf, "mixmatrix %s: no page-locked memory for the staged values", what);
         return p->fail(DSPFX_ERR_OOM, buf);
     }
-    std::memcpy(st.vals, vals, cells * sizeof(float));
+    uint32_t *index = (uint32_t *)st.vals;
+    for (uint64_t i = 0; i < count; ++i) index[i] = p->seated ? p->hseat_of[first + i] : l0 + (uint32_t)i;
+    std::memcpy(st.vals + count, vals, cells * sizeof(float));
     p->stores.push(st);
     return DSPFX_OK;
 }
 
-}  // namespace
-
-extern "C" const char *dspfx_mixmatrix_last_error(const dspfx_mixmatrix *p) { return p ? p->err.c_str() : g_err.c_str(); }
-
-extern "C" int dspfx_mixmatrix_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
-                                    uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
-    g_err.clear();
-    const int rc = check_table("mixmatrix", group_start, n_groups, n_channels, tile_channels, MAXN, g_err);
-    if (rc != DSPFX_OK) return rc;
-    uint64_t off = 0;
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        const uint32_t n = (uint32_t)(group_start[g + 1] - group_start[g]), P = edge(n);
-        if (count_out) count_out[g] = n;
-        if (edge_out) edge_out[g] = P;
-        if (offset_out) offset_out[g] = off;
-        off += (uint64_t)P * P;
-    }
-    if (total_bytes_out) *total_bytes_out = off * sizeof(float);
-    return DSPFX_OK;
-}
-
-extern "C" int dspfx_mixmatrix_plan_seats(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats,
-                                          uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
+// counts, table edges, table offsets and the total of a bank's rooms.  The edge of a room is its seats rounded up to 32 in a seated
+// bank (seats: [n_groups]) and its members rounded up to 32 otherwise
+int plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats, bool seated,
+         uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
     g_err.clear();
     const int rc = check_table("mixmatrix", group_start, n_groups, n_channels, tile_channels, MAXN, g_err);
     if (rc != DSPFX_OK) return rc;
     try {
-        std::vector<uint32_t> cnt(n_groups), S, off;
-        for (uint32_t g = 0; g < n_groups; ++g) cnt[g] = (uint32_t)(group_start[g + 1] - group_start[g]);
-        const int src = check_seats("mixmatrix", seats, cnt.data(), n_groups, S, off, g_err);
-        if (src != DSPFX_OK) return src;
+        std::vector<uint32_t> S, off;
+        if (seated) {
+            std::vector<uint32_t> cnt(n_groups);
+            for (uint32_t g = 0; g < n_groups; ++g) cnt[g] = (uint32_t)(group_start[g + 1] - group_start[g]);
+            const int src = check_seats("mixmatrix", seats, cnt.data(), n_groups, S, off, g_err);
+            if (src != DSPFX_OK) return src;
+        }
         uint64_t at = 0;
         for (uint32_t g = 0; g < n_groups; ++g) {
-            if (count_out) count_out[g] = cnt[g];
-            if (edge_out) edge_out[g] = S[g];
+            const uint32_t n = (uint32_t)(group_start[g + 1] - group_start[g]), P = seated ? S[g] : edge(n);
+            if (count_out) count_out[g] = n;
+            if (edge_out) edge_out[g] = P;
             if (offset_out) offset_out[g] = at;
-            at += (uint64_t)S[g] * S[g];
+            at += (uint64_t)P * P;
         }
         if (total_bytes_out) *total_bytes_out = at * sizeof(float);
     } catch (const std::bad_alloc &) {
@@ -805,14 +676,18 @@ extern "C" int dspfx_mixmatrix_plan_seats(const uint64_t *group_start, uint32_t 
     return DSPFX_OK;
 }
 
-namespace {
-int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool seated, dspfx_mixmatrix **out);
+}  // namespace
+
+extern "C" const char *dspfx_mixmatrix_last_error(const dspfx_mixmatrix *p) { return p ? p->err.c_str() : g_err.c_str(); }
+
+extern "C" int dspfx_mixmatrix_plan(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels,
+                                    uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
+    return plan(group_start, n_groups, n_channels, tile_channels, nullptr, false, count_out, edge_out, offset_out, total_bytes_out);
 }
 
-extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mixmatrix **out) { return create_bank(desc, nullptr, false, out); }
-
-extern "C" int dspfx_mixmatrix_create_seats(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, dspfx_mixmatrix **out) {
-    return create_bank(desc, seats, true, out);
+extern "C" int dspfx_mixmatrix_plan_seats(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats,
+                                          uint32_t *count_out, uint32_t *edge_out, uint64_t *offset_out, uint64_t *total_bytes_out) {
+    return plan(group_start, n_groups, n_channels, tile_channels, seats, true, count_out, edge_out, offset_out, total_bytes_out);
 }
 
 namespace {
@@ -837,7 +712,7 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
     }
     const uint32_t G = desc->n_groups, N = desc->n_channels;
     uint64_t total_bytes = 0;
-    std::vector<uint32_t> cnt, edges, room_of;
+    std::vector<uint32_t> cnt, edges;
     std::vector<uint64_t> offs;
     std::vector<Item> items;
     dspfx_mixmatrix *p = nullptr;
@@ -845,8 +720,7 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
         cnt.resize(G ? G : 1);
         offs.resize(G ? G : 1);
         edges.resize(G ? G : 1);
-        const int rc = seated ? dspfx_mixmatrix_plan_seats(desc->group_start, G, N, desc->tile_channels, seats, cnt.data(), edges.data(), offs.data(), &total_bytes)
-                              : dspfx_mixmatrix_plan(desc->group_start, G, N, desc->tile_channels, cnt.data(), edges.data(), offs.data(), &total_bytes);
+        const int rc = plan(desc->group_start, G, N, desc->tile_channels, seats, seated, cnt.data(), edges.data(), offs.data(), &total_bytes);
         if (rc != DSPFX_OK) return rc;
         if ((uint64_t)N * desc->max_frames > (1ull << 40)) {
             g_err = "mixmatrix: n_channels x max_frames is too large";
@@ -859,32 +733,31 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
         p->gs.assign(desc->group_start, desc->group_start + G + 1);
         p->desc.group_start = nullptr;
         p->hrooms.resize(G);
-        room_of.resize(N);
         p->seated = seated;
+        p->occ = cnt;
         uint32_t seat0 = 0;
         for (uint32_t g = 0; g < G; ++g) {
             p->hrooms[g] = seated ? Room{offs[g], seat0, edges[g]} : Room{offs[g], (uint32_t)p->gs[g], cnt[g]};
             p->maxn = std::max(p->maxn, p->hrooms[g].n);
             for (uint32_t l0 = 0; l0 < edges[g]; l0 += LT) items.push_back(Item{g, l0});
-            std::fill(room_of.begin() + p->gs[g], room_of.begin() + p->gs[g + 1], g);
             seat0 += seated ? edges[g] : 0u;
         }
         if (seated) {                                    // channel c0 + i of a room sits in its seat i
-            p->hroom_of = room_of;
+            p->hroom_of.resize(N);
             p->hseat_of.resize(N);
             p->hseat_chan.assign(seat0, NONE);
-            p->occ = cnt;
             p->hS = edges;
             p->hoff.resize(G);
             for (uint32_t g = 0; g < G; ++g) {
                 p->hoff[g] = p->hrooms[g].c0;
+                std::fill(p->hroom_of.begin() + p->gs[g], p->hroom_of.begin() + p->gs[g + 1], g);
                 for (uint32_t i = 0; i < cnt[g]; ++i) {
                     p->hseat_of[p->gs[g] + i] = i;
                     p->hseat_chan[p->hoff[g] + i] = (uint32_t)p->gs[g] + i;
                 }
             }
         }
-        // `stage` takes a room's lines (and their seats) at once, and at least a page of an assign's or a pair store's words
+        // `stage` takes a room's lines (and their indices) at once, and at least a page of an assign's or a pair store's words
         p->stage_words = std::max<size_t>((size_t)p->maxn * p->maxn + p->maxn, 4096);
     } catch (const std::bad_alloc &) {
         delete p;
@@ -902,7 +775,7 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
               (!seated || hipMalloc((void **)&p->seat_chan, p->hseat_chan.size() * sizeof(uint32_t)) == hipSuccess) &&
               hipMalloc((void **)&p->rooms, (size_t)G * sizeof(Room)) == hipSuccess &&
               hipMalloc((void **)&p->items, items.size() * sizeof(Item)) == hipSuccess &&
-              hipMalloc((void **)&p->room_of, (size_t)N * sizeof(uint32_t)) == hipSuccess;
+              (!seated || hipMalloc((void **)&p->room_of, (size_t)N * sizeof(uint32_t)) == hipSuccess);
     if (!ok) {
         (void)hipGetLastError();
         release(p);
@@ -911,7 +784,7 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
     }
     ok = hipMemcpy(p->rooms, p->hrooms.data(), (size_t)G * sizeof(Room), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(p->items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->room_of, room_of.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
+         (!seated || hipMemcpy(p->room_of, p->hroom_of.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) &&
          (!seated || hipMemcpy(p->seat_chan, p->hseat_chan.data(), p->hseat_chan.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) &&
          fill_rooms(p, 0, G, DSPFX_MIXMATRIX_MIX_MINUS, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
          hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
@@ -923,18 +796,13 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
     return DSPFX_OK;
 }
 
-// the room and the room-local index (the seat, in a seated bank) of channel c; smu is held on a seated bank
-void place_of(dspfx_mixmatrix *p, uint32_t c, uint32_t &room, uint32_t &index) {
-    if (p->seated) {
-        room = p->hroom_of[c];
-        index = p->hseat_of[c];
-    } else {
-        room = (uint32_t)(std::upper_bound(p->gs.begin(), p->gs.end(), (uint64_t)c) - p->gs.begin()) - 1;
-        index = c - (uint32_t)p->gs[room];
-    }
-}
-
 }  // namespace
+
+extern "C" int dspfx_mixmatrix_create(const dspfx_mixmatrix_desc *desc, dspfx_mixmatrix **out) { return create_bank(desc, nullptr, false, out); }
+
+extern "C" int dspfx_mixmatrix_create_seats(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, dspfx_mixmatrix **out) {
+    return create_bank(desc, seats, true, out);
+}
 
 extern "C" int dspfx_mixmatrix_reseat(uint32_t *room_of_io, uint32_t *seat_of_io, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
                                       const uint32_t *room_ids, uint64_t first_channel, uint64_t count) {
@@ -1003,7 +871,7 @@ extern "C" int dspfx_mixmatrix_assign(dspfx_mixmatrix *p, const uint32_t *host_r
         int64_t gone = 0;
         for (const Move &m : moves) gone += (m.r1 == NONE) - (m.r0 == NONE);
         Store st;
-        st.kind = 3;
+        st.kind = ASSIGN;
         st.preset = preset;
         st.n_seats = w_seats.size() / 2;
         st.n_chans = w_chans.size() / 2;
@@ -1057,7 +925,7 @@ extern "C" int dspfx_mixmatrix_set_pairs(dspfx_mixmatrix *p, const uint32_t *lis
             if (seen.insert(rl).second) rooms.push_back(rl);
         }
         Store st;
-        st.kind = 4;
+        st.kind = PAIRS;
         st.n_lines = words.size() / 3;
         st.n_rooms = rooms.size();
         if (!p->stores.staging(p->desc.device, words.size() + rooms.size(), st))
@@ -1099,7 +967,7 @@ extern "C" int dspfx_mixmatrix_occupancy(dspfx_mixmatrix *p, uint32_t *host_coun
     if (!p) return DSPFX_ERR_INVALID;
     if (!host_counts_out) return p->fail(DSPFX_ERR_INVALID, "mixmatrix occupancy: no array");
     std::lock_guard<std::mutex> lk(p->smu);
-    for (uint32_t g = 0; g < p->desc.n_groups; ++g) host_counts_out[g] = p->seated ? p->occ[g] : p->hrooms[g].n;
+    for (uint32_t g = 0; g < p->desc.n_groups; ++g) host_counts_out[g] = p->occ[g];
     return DSPFX_OK;
 }
 
@@ -1111,12 +979,12 @@ extern "C" int dspfx_mixmatrix_destroy(dspfx_mixmatrix *p) {
 
 extern "C" int dspfx_mixmatrix_set_rows(dspfx_mixmatrix *p, const float *host_values, uint32_t row_len, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
-    return store_lines(p, 0, host_values, row_len, first_channel, count);
+    return store_lines(p, ROWS, host_values, row_len, first_channel, count);
 }
 
 extern "C" int dspfx_mixmatrix_set_cols(dspfx_mixmatrix *p, const float *host_values, uint32_t row_len, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
-    return store_lines(p, 1, host_values, row_len, first_channel, count);
+    return store_lines(p, COLS, host_values, row_len, first_channel, count);
 }
 
 extern "C" int dspfx_mixmatrix_fill(dspfx_mixmatrix *p, int64_t room, uint32_t preset) {
@@ -1132,7 +1000,7 @@ extern "C" int dspfx_mixmatrix_fill(dspfx_mixmatrix *p, int64_t room, uint32_t p
         return p->fail(DSPFX_ERR_INVALID, buf);
     }
     Store st;
-    st.kind = 2;
+    st.kind = FILL;
     st.room = room < 0 ? 0u : (uint32_t)room;
     st.count = room < 0 ? G : 1u;
     st.preset = preset;
@@ -1164,16 +1032,13 @@ extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint3
     a.W = p->desc.tile_channels;
     a.nf = n_frames;
     a.normalise = p->desc.normalise;
-    if (p->seated) {
-        if (p->roomless) {
-            mixmatrix_zero_roomless<<<(a.N + WG - 1) / WG, WG, 0, s>>>(out, p->room_of, a.N, a.W, n_frames);
-            BANK_HIP_WHY(hipGetLastError(), "mixmatrix_zero_roomless");
-        }
-        mixmatrix_run_seated<<<dim3(p->n_items, (n_frames + FT - 1) / FT), WG, 0, s>>>(SeatedArgs{a, p->seat_chan});
-        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run_seated");
-        return DSPFX_OK;
+    a.seat_chan = p->seat_chan;
+    if (p->roomless) {                           // (a seated bank's: the other has nobody without a room)
+        mixmatrix_zero_roomless<<<(a.N + WG - 1) / WG, WG, 0, s>>>(out, p->room_of, a.N, a.W, n_frames);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_zero_roomless");
     }
-    mixmatrix_run<<<dim3(p->n_items, (n_frames + FT - 1) / FT), WG, 0, s>>>(a);
-    BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run");
+    const auto kernel = p->seated ? mixmatrix_run<true> : mixmatrix_run<false>;
+    kernel<<<dim3(p->n_items, (n_frames + FT - 1) / FT), WG, 0, s>>>(a);
+    BANK_HIP_WHY(hipGetLastError(), p->seated ? "mixmatrix_run_seated" : "mixmatrix_run");
     return DSPFX_OK;
 }
