@@ -56,6 +56,7 @@ CONVOLVE_MAX_RESPONSES = 256    # DSPFX_CONVOLVE_MAX_RESPONSES: the responses on
 STRIPS_MAX_BANDS = 8            # DSPFX_STRIPS_MAX_BANDS: the BiQuad bands one ChannelStrips bank holds per channel
 MIXMATRIX_MAX_ROOM = 1024       # DSPFX_MIXMATRIX_MAX_ROOM: the most members a MixMatrix room has
 MIXMATRIX_MIX_MINUS, MIXMATRIX_ZERO = 0, 1      # DSPFX_MIXMATRIX_*: MixMatrix.fill presets
+MIXMATRIX_DIRECT, MIXMATRIX_STAGED = 0, 1       # DSPFX_MIXMATRIX_*: MixMatrix.set_staging modes
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -91,6 +92,7 @@ EXPORTS = [
     "dspfx_mixmatrix_set_rows", "dspfx_mixmatrix_set_cols", "dspfx_mixmatrix_fill", "dspfx_mixmatrix_reset",
     "dspfx_mixmatrix_set_pairs", "dspfx_mixmatrix_create_seats", "dspfx_mixmatrix_plan_seats", "dspfx_mixmatrix_assign",
     "dspfx_mixmatrix_rooms", "dspfx_mixmatrix_seats", "dspfx_mixmatrix_occupancy", "dspfx_mixmatrix_reseat",
+    "dspfx_mixmatrix_set_staging", "dspfx_mixmatrix_staging", "dspfx_mixmatrix_staging_bytes", "dspfx_mixmatrix_scatter",
 ]
 COMM_ID_BYTES = 128
 
@@ -361,6 +363,10 @@ def lib():
     L.dspfx_mixmatrix_seats.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_mixmatrix_occupancy.argtypes = [vp, u32p]
     L.dspfx_mixmatrix_reseat.argtypes = [u32p, u32p, u32p, C.c_uint32, C.c_uint64, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_mixmatrix_set_staging.argtypes = [vp, C.c_uint32]
+    L.dspfx_mixmatrix_staging.argtypes = [vp, u32p]
+    L.dspfx_mixmatrix_staging_bytes.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.dspfx_mixmatrix_scatter.argtypes = [u32p, u32p, u32p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -1709,6 +1715,40 @@ def mixmatrix_reseat(room_of, seat_of, seats, ids, first_channel: int = 0):
     return r, q
 
 
+def mixmatrix_staging_bytes(channels: int, seats, group_start=None, group_size=None, tile_channels: int = 0, max_frames: int = BUF_SIZE) -> int:
+    """dspfx_mixmatrix_staging_bytes, a pure host function (no GPU): the bytes MIXMATRIX_STAGED adds to the seated bank that
+    mixmatrix_plan(..., seats=seats) plans: two seat-ordered copies of (the sum of the seats, each rounded up to 32) x max_frames
+    float32, and 4 bytes per channel for the channel -> seat table.  The same checks as the plan's."""
+    L = lib()
+    t = _group_table(int(channels), group_start, group_size)
+    G = len(t) - 1
+    s = _seat_counts(seats, G)
+    total = C.c_uint64(0)
+    rc = L.dspfx_mixmatrix_staging_bytes(t.ctypes.data_as(C.POINTER(C.c_uint64)), G, int(channels), int(tile_channels),
+                                         s.ctypes.data_as(C.POINTER(C.c_uint32)), int(max_frames) & 0xFFFFFFFF, C.byref(total))
+    _raise(L, "mixmatrix", rc)
+    return int(total.value)
+
+
+def mixmatrix_scatter(room_of, seat_of, seats):
+    """dspfx_mixmatrix_scatter, a pure host function (no GPU): how scattered a seating is.  room_of, seat_of: uint32[N] as
+    mixmatrix_reseat takes them; seats: [G], one count per room.  -> (chunks, lines): the runs of 32 consecutive seats of a room that hold
+    anybody (a chunk of the direct run), and, summed over them, the distinct values of channel // 32 among a run's channels (the
+    lines the chunk reads per frame).  lines / chunks is 1 at the seating a fresh bank has when its rooms begin at multiples of
+    32, and approaches 32 once everybody has wandered: the figure to decide MixMatrix.set_staging by."""
+    L = lib()
+    r, q = np.ascontiguousarray(room_of, np.uint32).reshape(-1), np.ascontiguousarray(seat_of, np.uint32).reshape(-1)
+    s = np.atleast_1d(np.asarray(seats)).reshape(-1)
+    if len(r) != len(q) or s.dtype.kind not in "iu" or (s.size and (s.min() < 0 or s.max() > 0xFFFFFFFF)):
+        raise DspfxError(-1, "room_of and seat_of are [N], seats is [G]")
+    s = np.ascontiguousarray(s, np.uint32)
+    u32 = C.POINTER(C.c_uint32)
+    chunks, lines = C.c_uint64(0), C.c_uint64(0)
+    rc = L.dspfx_mixmatrix_scatter(r.ctypes.data_as(u32), q.ctypes.data_as(u32), s.ctypes.data_as(u32), len(s), len(r), C.byref(chunks), C.byref(lines))
+    _raise(L, "mixmatrix", rc)
+    return int(chunks.value), int(lines.value)
+
+
 class MixMatrix(_Bank):
     """Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an
     n_r x n_r float32 matrix M[l][s] (listener, source), and out[f][c0 + l] = (sum_s M[l][s] * x[f][c0 + s]) / link_divisor(w),
@@ -1778,6 +1818,28 @@ class MixMatrix(_Bank):
         self._chk(self.L.dspfx_mixmatrix_occupancy(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32))))
         return v
 
+    def set_staging(self, mode: int):
+        """A seated bank: the mode of the runs submitted after this returns.  MIXMATRIX_DIRECT: the run gathers every seat's channel
+        from the block (fastest while the seating is near the one the bank was made with).  MIXMATRIX_STAGED: the block is
+        transposed into a seat-ordered copy, the same chain runs over it and the result is transposed back, so the cost does not
+        depend on the seating, the bits are the direct run's, and run(out=block) works in place.  The first switch to STAGED
+        allocates mixmatrix_staging_bytes(...) of device memory, kept until the bank goes.  Any thread, while runs are in flight;
+        scatter() says when to switch."""
+        self._chk(self.L.dspfx_mixmatrix_set_staging(self.h, int(mode) & 0xFFFFFFFF))
+
+    @property
+    def staging(self) -> int:
+        """MIXMATRIX_DIRECT or MIXMATRIX_STAGED: the mode of the next run."""
+        v = C.c_uint32(0)
+        self._chk(self.L.dspfx_mixmatrix_staging(self.h, C.byref(v)))
+        return int(v.value)
+
+    def scatter(self):
+        """A seated bank: mixmatrix_scatter of the seating by every call made so far -> (chunks, lines)."""
+        if self.seats is None:
+            raise DspfxError(-6, "mixmatrix scatter: the bank has no seats")
+        return mixmatrix_scatter(self.room_of(), self.seat_of(), self.seats)
+
     def set_pairs(self, listeners, sources, gains):
         """M[listeners[i]][sources[i]] = gains[i], by CHANNEL number, in order (a later duplicate wins); gains may be one value for
         all pairs.  Each pair must be two channels of one room, or nothing is stored.  Queued like every other store."""
@@ -1791,7 +1853,8 @@ class MixMatrix(_Bank):
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every room's matrix -> `out`, a device block in the same layout (made when not given).
-        `out` may not overlap `block`: every listener reads every source of its room, so there is no in-place form."""
+        `out` may not overlap `block`: every listener reads every source of its room, so there is no in-place form -- except in
+        MIXMATRIX_STAGED, where `out` may be `block` itself."""
         import torch
         if n_frames is None:
             n_frames = block.numel() // self.channels

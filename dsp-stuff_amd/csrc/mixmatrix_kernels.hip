@@ -37,9 +37,17 @@
 // bank share every kernel and every host path: what a room-local index means -- a member, or a seat -- is a template argument of the
 // run, fill, store and recount kernels ("the two seatings" below) and data on the host.  A bank made by dspfx_mixmatrix_create runs
 // the instantiation that is, instruction for instruction, what it always ran.
+//
+// The staged run of a seated bank (dspfx_mixmatrix_set_staging): the direct run gathers x[f][seat_chan[s]], one lane per seat, and a
+// channel's frames are a whole row apart, so once participants have wandered a chunk of 32 seats reads up to 32 lines per frame
+// for 32 words, per listener tile, and stores the same way.  In DSPFX_MIXMATRIX_STAGED a run is three kernels on the stream, behind
+// the drained stores: mixmatrix_stage_in (the block, read once and coalesced, into a seat-ordered copy), mixmatrix_run<true, true>
+// (the same chain over the copy, reading and writing along frames) and mixmatrix_stage_out (the result back, +0.0 for the channels
+// in no room).  Every read of the block is over before the first write of out, so out == block is allowed in this mode.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -107,14 +115,27 @@ struct RunArgs {
     const Item *__restrict__ items;
     uint32_t N, W, nf, normalise;
     const uint32_t *__restrict__ seat_chan;      // a seated bank's; the other's kernel never reads it
+    // the staged mode's (only its instantiation reads them): the seat-ordered copy of the block and of the result, [seat][MF], a
+    // seat's row being its entry of seat_chan
+    const float *__restrict__ sin;
+    float *__restrict__ sout;
+    uint32_t MF;
 };
 
 // The seatings differ in the table's edge and in two addresses (written out here, not through chan_of: each instantiation keeps the
 // instruction stream it had as a kernel of its own): the source at index s is x[..][c0 + s], or x[..][seat_chan[s]], and listener
 // l's row goes to out[..][c0 + l], or out[..][seat_chan[l]].  An index nobody holds is not loaded (+0.0 in LDS) and not stored.  The
 // seat entry of a chunk is fetched one chunk ahead of the chunk's own loads, so the samples' addresses never wait for it
-template <bool SEATED>
+//
+// STAGED (a seated bank in DSPFX_MIXMATRIX_STAGED): the same chain over the seat-ordered copy.  The source at seat s is row c0 + s of
+// a.sin and listener l's result goes to row c0 + l of a.sout, both read and written ALONG FRAMES: a wave's load is 64 consecutive
+// frames of one seat (two whole lines wherever the row starts), and a lane's four consecutive accumulator rows are 16 contiguous
+// bytes of its listener's row.  seat_chan still decides who is loaded and who is stored: the row of an empty seat holds whatever its
+// last occupant left there and is never read.  The chunk lands in LDS in the same [frame][source] image, so the MFMA loop is the
+// direct kernel's, term for term
+template <bool SEATED, bool STAGED = false>
 __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
+    static_assert(SEATED || !STAGED, "only a seated bank has a staged run");
     __shared__ float xs[FT * XS];                        // [frame][source of the chunk]
     const Item it = a.items[blockIdx.x];
     const Room rm = a.rooms[it.room];
@@ -125,6 +146,7 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
     const uint32_t lt = it.l0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) * 32u;     // the wave's listener tile (uniform)
     const bool active = lt < P;                          // wave-uniform; an idle wave still stages its share of x
     const uint32_t ss = tid & 31u, sf = tid >> 5;        // staging: source ss of the chunk, frames sf + 8 i
+    const uint32_t fl = tid & 127u, sh = tid >> 7;       // (STAGED) staging: frame fl of the pass, sources sh + 2 i (wave-uniform)
     const size_t rs = a.W ? a.W : a.N;                   // a frame further is rs elements on in either layout
 
     // (the frame pass is a grid dimension and not a loop here: a loop would have the compiler keep every row's offset live across it)
@@ -143,6 +165,24 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
     uint32_t cn = 0;                                     // SEATED: who sits in this thread's seat of the next chunk to load (P >= 32)
     if constexpr (SEATED) cn = sc[ss];
     auto gload = [&](uint32_t k0) {
+        if constexpr (STAGED) {
+            // bit q: seat k0 + q is taken (lanes 0 .. 31 hold the chunk's 32 seats; the upper half repeats them)
+            const uint32_t held = (uint32_t)__ballot(cn != NONE);
+            if (k0 + KC < P) cn = sc[k0 + KC + ss];
+            const bool inside = f0 + fl < a.nf;
+            const float *p = a.sin + (size_t)(c0 + k0 + sh) * a.MF + f0 + fl;
+#pragma unroll
+            for (uint32_t i = 0; i < 16; ++i) {
+                st[i] = (inside && (held >> (sh + 2u * i) & 1u)) ? *p : 0.0f;
+                p += 2u * (size_t)a.MF;
+            }
+            if (active) {
+                const uint32_t o = k0 * P + bcol;
+#pragma unroll
+                for (uint32_t j = 0; j < KC / 2; ++j) bn[j] = tabr[o + 2u * j * P];
+            }
+            return;
+        }
         bool held;
         uint32_t ch;                                     // the channel whose samples p walks; nobody's index: any valid one, unread
         if constexpr (SEATED) {
@@ -173,7 +213,10 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
     for (uint32_t k0 = 0; k0 < P; k0 += KC) {
         __syncthreads();                                 // the chunk before is read
 #pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) xs[(sf + 8u * i) * XS + ss] = st[i];
+        for (uint32_t i = 0; i < 16; ++i) {
+            if constexpr (STAGED) xs[fl * XS + sh + 2u * i] = st[i];   // (33 fl: a half-wave's 32 frames fall in 32 banks)
+            else xs[(sf + 8u * i) * XS + ss] = st[i];
+        }
         float b[KC / 2];
 #pragma unroll
         for (uint32_t j = 0; j < KC / 2; ++j) b[j] = bn[j];
@@ -211,6 +254,34 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
         heard = active && l < n;
         c = c0 + l;
     }
+    if constexpr (STAGED) {
+        if (heard) {
+            const float d = a.div[c];
+            float *po = a.sout + (size_t)(c0 + lt + r) * a.MF + f0;
+            const bool vec = (a.MF & 3u) == 0u;          // every row starts on 16 bytes (f0 and the tile's rows are multiples of 4)
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t)
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) {
+                    const uint32_t fb = t * 32u + 8u * q + 4u * h;     // accumulator rows 4 q .. 4 q + 3: frames fb .. fb + 3
+                    float v[4];
+#pragma unroll
+                    for (uint32_t i = 0; i < 4; ++i) {
+                        v[i] = acc[t][4u * q + i];
+                        if (d == 0.0f) v[i] = 0.0f;
+                        else if (a.normalise) v[i] = __fdiv_rn(v[i], d);
+                    }
+                    if (vec && f0 + fb + 4u <= a.nf) {
+                        *(f32x4 *)(po + fb) = f32x4{v[0], v[1], v[2], v[3]};
+                    } else {
+#pragma unroll
+                        for (uint32_t i = 0; i < 4; ++i)
+                            if (f0 + fb + i < a.nf) po[fb + i] = v[i];
+                    }
+                }
+        }
+        return;
+    }
     if (heard) {
         const float d = a.div[c];
         float *po = a.out + lay(0, c, a.nf, a.N, a.W);
@@ -237,6 +308,84 @@ __global__ __launch_bounds__(WG) void mixmatrix_zero_roomless(float *__restrict_
     float *po = out + lay(0, c, nf, N, W);
     const size_t rs = W ? W : N;
     for (uint32_t f = 0; f < nf; ++f) po[(size_t)f * rs] = 0.0f;
+}
+
+// ---- the staged mode's transposes ---------------------------------------------------------------------------------------------
+// Between the block (a frame's channels adjacent, a channel's frames a whole row apart) and the seat-ordered copies (a seat's frames
+// adjacent).  A workgroup owns SG adjacent channels and the FT frames of one pass, and goes through an LDS tile [frame][channel]
+// of stride SG + 1: on the block's side a wave's lanes are 64 adjacent channels of one frame, on the copy's side 64 consecutive
+// frames of one channel, and both sides of the tile meet 32 banks per half-wave (lane = channel: consecutive words; lane = frame: a
+// stride of 65 words).  slot_of[c] is channel c's entry of seat_chan -- its row of the copies -- or NONE
+constexpr uint32_t SG = 64;
+constexpr uint32_t TS = SG + 1;
+
+// block -> sin: every seated channel's frames, contiguous, into its seat's row.  A channel in no room is not read
+__global__ __launch_bounds__(WG) void mixmatrix_stage_in(const float *__restrict__ in, float *__restrict__ sin, const uint32_t *__restrict__ slot_of,
+                                                         uint32_t N, uint32_t W, uint32_t nf, uint32_t MF) {
+    __shared__ float ts[FT * TS];
+    __shared__ uint32_t slot[SG];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t g0 = blockIdx.x * SG, f0 = blockIdx.y * FT, left = min(nf - f0, FT), c = g0 + lane;
+    const size_t rs = W ? W : N;
+    const uint32_t mine = c < N ? slot_of[c] : NONE;
+    if (wave == 0) slot[lane] = mine;
+    if (mine != NONE) {
+        const float *p = in + lay(0, c, nf, N, W) + (size_t)(f0 + wave) * rs;
+#pragma unroll 8
+        for (uint32_t f = wave; f < left; f += WG / 64u) {
+            ts[f * TS + lane] = *p;
+            p += (WG / 64u) * rs;
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = wave; j < SG; j += WG / 64u) {     // (j and the slot are wave-uniform)
+        const uint32_t sl = slot[j];
+        if (sl == NONE) continue;
+        float *q = sin + (size_t)sl * MF + f0;
+        for (uint32_t f = lane; f < left; f += 64u) q[f] = ts[f * TS + j];
+    }
+}
+
+// sout -> out: the inverse.  A channel in no room reads +0.0 in every frame (so a staged run launches no mixmatrix_zero_roomless)
+__global__ __launch_bounds__(WG) void mixmatrix_stage_out(const float *__restrict__ sout, float *__restrict__ out, const uint32_t *__restrict__ slot_of,
+                                                          uint32_t N, uint32_t W, uint32_t nf, uint32_t MF) {
+    __shared__ float ts[FT * TS];
+    __shared__ uint32_t slot[SG];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t g0 = blockIdx.x * SG, f0 = blockIdx.y * FT, left = min(nf - f0, FT), c = g0 + lane;
+    const size_t rs = W ? W : N;
+    if (wave == 0) slot[lane] = c < N ? slot_of[c] : NONE;       // (a channel past N: zeros in the tile, never stored)
+    __syncthreads();
+    // a wave takes channels wave, wave + 4, ..: four rows' loads (two halves of FT frames each) are issued before the first of them
+    // is needed, so a wave does not wait out one row's latency after the other
+    constexpr uint32_t NW = WG / 64u, UN = 4;
+#pragma unroll
+    for (uint32_t jb = 0; jb < SG / NW; jb += UN) {
+        float v[UN][FT / 64u];
+#pragma unroll
+        for (uint32_t u = 0; u < UN; ++u) {
+            const uint32_t sl = slot[wave + NW * (jb + u)];
+            const float *q = sout + (size_t)(sl != NONE ? sl : 0u) * MF + f0;
+#pragma unroll
+            for (uint32_t hh = 0; hh < FT / 64u; ++hh) {
+                const uint32_t f = lane + 64u * hh;
+                v[u][hh] = (sl != NONE && f < left) ? q[f] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < UN; ++u)
+#pragma unroll
+            for (uint32_t hh = 0; hh < FT / 64u; ++hh) ts[(lane + 64u * hh) * TS + wave + NW * (jb + u)] = v[u][hh];
+    }
+    __syncthreads();
+    if (c < N) {
+        float *p = out + lay(0, c, nf, N, W) + (size_t)(f0 + wave) * rs;
+#pragma unroll 8
+        for (uint32_t f = wave; f < left; f += WG / 64u) {
+            __builtin_nontemporal_store(ts[f * TS + lane], p);
+            p += (WG / 64u) * rs;
+        }
+    }
 }
 
 // a preset into the tables of rooms [first_room, first_room + gridDim.x): one workgroup per room.  Mix-minus is 1.0 between two
@@ -268,10 +417,25 @@ __global__ __launch_bounds__(WG) void mixmatrix_store(float *__restrict__ tab, c
     else t[(size_t)j * P + q] = v;
 }
 
-// words = [n] (seat_chan index, channel or NONE) pairs: the seats an assign changed, each with who sits there after the call
-__global__ __launch_bounds__(WG) void mixmatrix_seat_set(uint32_t *__restrict__ dst, const uint32_t *__restrict__ words, uint32_t n) {
+// words = [n] (channel, room or NONE) pairs: the movers of an assign.  Every mover leaves its row of the staged copies here;
+// mixmatrix_seat_set, behind it, gives those who sit down again their new one (so a swap between two full rooms comes out right)
+__global__ __launch_bounds__(WG) void mixmatrix_chan_set(uint32_t *__restrict__ room_of, uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ words,
+                                                         uint32_t n) {
     const uint32_t i = blockIdx.x * WG + threadIdx.x;
-    if (i < n) dst[words[2u * i]] = words[2u * i + 1u];
+    if (i >= n) return;
+    room_of[words[2u * i]] = words[2u * i + 1u];
+    slot_of[words[2u * i]] = NONE;
+}
+
+// words = [n] (seat_chan index, channel or NONE) pairs: the seats an assign changed, each with who sits there after the call (a
+// seat can be named twice, with the same occupant)
+__global__ __launch_bounds__(WG) void mixmatrix_seat_set(uint32_t *__restrict__ seat_chan, uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ words,
+                                                         uint32_t n) {
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t at = words[2u * i], c = words[2u * i + 1u];
+    seat_chan[at] = c;
+    if (c != NONE) slot_of[c] = at;
 }
 
 // words = [gridDim.x] (room, seat | preset << 31) pairs: the seats an assign emptied (preset bit clear) or gave to a newcomer.  The
@@ -492,6 +656,13 @@ struct dspfx_mixmatrix : BankError {
     uint64_t hroomless = 0;                      // channels in no room (smu)
     uint64_t roomless = 0;                       // ... by the assigns drained so far (mu)
     uint32_t *room_of = nullptr, *seat_chan = nullptr;
+    uint32_t *slot_of = nullptr;                 // [N]: the channel's entry of seat_chan (NONE: in no room), kept by every assign
+    // the staged mode (dspfx_mixmatrix_set_staging).  `mode` is read once by a run, so a run is wholly one mode; sbuf is written once,
+    // under gmu, before the first store of STAGED into mode, and kept until release
+    std::atomic<uint32_t> mode{DSPFX_MIXMATRIX_DIRECT};
+    std::mutex gmu;                              // set_staging
+    float *sbuf = nullptr;                       // the two seat-ordered copies, [2][n_slots][max_frames]; never zeroed
+    uint64_t n_slots = 0;                        // the sum of S_r: the entries of seat_chan
     Seats seats() { return Seats{hroom_of.data(), hseat_of.data(), hseat_chan.data(), occ.data(), hS.data(), hoff.data(), desc.n_groups, desc.n_channels}; }
 };
 
@@ -499,7 +670,8 @@ namespace {
 
 void release(dspfx_mixmatrix *p) {
     (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->tab, (void *)p->div, (void *)p->stage, (void *)p->rooms, (void *)p->items, (void *)p->room_of, (void *)p->seat_chan})
+    for (void *d : {(void *)p->tab, (void *)p->div, (void *)p->stage, (void *)p->rooms, (void *)p->items, (void *)p->room_of, (void *)p->seat_chan,
+                    (void *)p->slot_of, (void *)p->sbuf})
         if (d) (void)hipFree(d);
     p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
@@ -555,19 +727,18 @@ hipError_t fill_rooms(dspfx_mixmatrix *p, uint32_t first_room, uint32_t count, u
 hipError_t apply_store(dspfx_mixmatrix *p, const Store &st, hipStream_t s) {
     if (st.kind == FILL) return fill_rooms(p, st.room, st.count, st.preset, s);
     const uint32_t *words = (const uint32_t *)st.vals;
-    if (st.kind == ASSIGN) {                     // the seats, the rooms of the channels, the lines, the divisors -- in that order
-        hipError_t err = sliced(p, words, st.n_seats, 2, s, [&](const uint32_t *w, uint32_t k) {
-            mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->seat_chan, w, k);
+    if (st.kind == ASSIGN) {                     // the rooms of the channels, the seats, the lines, the divisors -- in that order
+        hipError_t err = sliced(p, words + 2 * st.n_seats, st.n_chans, 2, s, [&](const uint32_t *w, uint32_t k) {
+            mixmatrix_chan_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->room_of, p->slot_of, w, k);
             return hipGetLastError();
         });
         if (err != hipSuccess) return err;
-        words += 2 * st.n_seats;
-        err = sliced(p, words, st.n_chans, 2, s, [&](const uint32_t *w, uint32_t k) {
-            mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->room_of, w, k);
+        err = sliced(p, words, st.n_seats, 2, s, [&](const uint32_t *w, uint32_t k) {
+            mixmatrix_seat_set<<<(k + WG - 1) / WG, WG, 0, s>>>(p->seat_chan, p->slot_of, w, k);
             return hipGetLastError();
         });
         if (err != hipSuccess) return err;
-        words += 2 * st.n_chans;
+        words += 2 * st.n_seats + 2 * st.n_chans;
         err = sliced(p, words, st.n_lines, 2, s, [&](const uint32_t *w, uint32_t k) {
             mixmatrix_seat_lines<<<k, WG, 0, s>>>(p->tab, p->rooms, p->seat_chan, w);
             return hipGetLastError();
@@ -715,6 +886,7 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
     std::vector<uint32_t> cnt, edges;
     std::vector<uint64_t> offs;
     std::vector<Item> items;
+    std::vector<uint32_t> slots;                         // a seated bank's first slot_of
     dspfx_mixmatrix *p = nullptr;
     try {
         cnt.resize(G ? G : 1);
@@ -756,6 +928,9 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
                     p->hseat_chan[p->hoff[g] + i] = (uint32_t)p->gs[g] + i;
                 }
             }
+            p->n_slots = seat0;
+            slots.resize(N);
+            for (uint32_t c = 0; c < N; ++c) slots[c] = p->hoff[p->hroom_of[c]] + p->hseat_of[c];
         }
         // `stage` takes a room's lines (and their indices) at once, and at least a page of an assign's or a pair store's words
         p->stage_words = std::max<size_t>((size_t)p->maxn * p->maxn + p->maxn, 4096);
@@ -775,7 +950,8 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
               (!seated || hipMalloc((void **)&p->seat_chan, p->hseat_chan.size() * sizeof(uint32_t)) == hipSuccess) &&
               hipMalloc((void **)&p->rooms, (size_t)G * sizeof(Room)) == hipSuccess &&
               hipMalloc((void **)&p->items, items.size() * sizeof(Item)) == hipSuccess &&
-              (!seated || hipMalloc((void **)&p->room_of, (size_t)N * sizeof(uint32_t)) == hipSuccess);
+              (!seated || hipMalloc((void **)&p->room_of, (size_t)N * sizeof(uint32_t)) == hipSuccess) &&
+              (!seated || hipMalloc((void **)&p->slot_of, (size_t)N * sizeof(uint32_t)) == hipSuccess);
     if (!ok) {
         (void)hipGetLastError();
         release(p);
@@ -786,6 +962,7 @@ int create_bank(const dspfx_mixmatrix_desc *desc, const uint32_t *seats, bool se
          hipMemcpy(p->items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice) == hipSuccess &&
          (!seated || hipMemcpy(p->room_of, p->hroom_of.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) &&
          (!seated || hipMemcpy(p->seat_chan, p->hseat_chan.data(), p->hseat_chan.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) &&
+         (!seated || hipMemcpy(p->slot_of, slots.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess) &&
          fill_rooms(p, 0, G, DSPFX_MIXMATRIX_MIX_MINUS, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
          hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -834,6 +1011,100 @@ extern "C" int dspfx_mixmatrix_reseat(uint32_t *room_of_io, uint32_t *seat_of_io
         g_err = "mixmatrix reseat: no host memory";
         return DSPFX_ERR_OOM;
     }
+}
+
+extern "C" int dspfx_mixmatrix_scatter(const uint32_t *room_of, const uint32_t *seat_of, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
+                                       uint64_t *chunks_out, uint64_t *lines_out) {
+    g_err.clear();
+    if (!room_of || !seat_of || n_groups == 0 || n_channels == 0 || n_channels > 0xFFFFFF00ull) {
+        g_err = "mixmatrix scatter: no tables, no rooms or no channels";
+        return DSPFX_ERR_INVALID;
+    }
+    try {
+        std::vector<uint32_t> S, off, chan;
+        const int rc = check_seats("mixmatrix scatter", seats, nullptr, n_groups, S, off, g_err);
+        if (rc != DSPFX_OK) return rc;
+        chan.assign((size_t)off[n_groups - 1] + S[n_groups - 1], NONE);
+        for (uint64_t c = 0; c < n_channels; ++c) {
+            const uint32_t g = room_of[c], q = seat_of[c];
+            if (g == NONE) continue;
+            if (g >= n_groups || q >= S[g] || chan[off[g] + q] != NONE) {
+                char buf[160];
+                std::snprintf(buf, sizeof buf, "mixmatrix scatter: channel %llu is in seat %u of room %u, which does not exist or is held twice", (unsigned long long)c, q, g);
+                g_err = buf;
+                return DSPFX_ERR_INVALID;
+            }
+            chan[off[g] + q] = (uint32_t)c;
+        }
+        // (every S_r is a multiple of 32, so a run of 32 entries of `chan` from a multiple of 32 is a run of 32 seats of one room:
+        // a chunk of the direct run)
+        uint64_t chunks = 0, lines = 0;
+        uint32_t line[KC];
+        for (size_t k0 = 0; k0 < chan.size(); k0 += KC) {
+            uint32_t n = 0;
+            for (uint32_t i = 0; i < KC; ++i)
+                if (chan[k0 + i] != NONE) line[n++] = chan[k0 + i] / 32u;
+            if (n == 0) continue;
+            std::sort(line, line + n);
+            ++chunks;
+            lines += (uint64_t)(std::unique(line, line + n) - line);
+        }
+        if (chunks_out) *chunks_out = chunks;
+        if (lines_out) *lines_out = lines;
+    } catch (const std::bad_alloc &) {
+        g_err = "mixmatrix scatter: no host memory";
+        return DSPFX_ERR_OOM;
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_staging_bytes(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats,
+                                             uint32_t max_frames, uint64_t *bytes_out) {
+    uint64_t tables = 0;
+    std::vector<uint32_t> edges;
+    try {
+        edges.resize(n_groups ? n_groups : 1);
+    } catch (const std::bad_alloc &) {
+        g_err = "mixmatrix: no host memory for the room tables";
+        return DSPFX_ERR_OOM;
+    }
+    const int rc = plan(group_start, n_groups, n_channels, tile_channels, seats, true, nullptr, edges.data(), nullptr, &tables);
+    if (rc != DSPFX_OK) return rc;
+    if (max_frames == 0 || max_frames > (1u << 20)) {
+        g_err = "mixmatrix: max_frames must be 1 .. 2^20";
+        return DSPFX_ERR_INVALID;
+    }
+    uint64_t slots = 0;
+    for (uint32_t g = 0; g < n_groups; ++g) slots += edges[g];
+    if (bytes_out) *bytes_out = 2u * slots * max_frames * sizeof(float) + n_channels * sizeof(uint32_t);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_set_staging(dspfx_mixmatrix *p, uint32_t mode) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (!p->seated) return p->fail(DSPFX_ERR_STATE, "mixmatrix set_staging: the bank has no seats (it was not made by dspfx_mixmatrix_create_seats)");
+    if (mode != DSPFX_MIXMATRIX_DIRECT && mode != DSPFX_MIXMATRIX_STAGED)
+        return p->fail(DSPFX_ERR_INVALID, "mixmatrix set_staging: the mode (DSPFX_MIXMATRIX_DIRECT and DSPFX_MIXMATRIX_STAGED are known)");
+    std::lock_guard<std::mutex> lk(p->gmu);
+    if (mode == DSPFX_MIXMATRIX_STAGED && !p->sbuf) {
+        // on the caller's thread, as a slider store allocates a longer delay ring; kept until destroy, so no toggle frees what a run
+        // in flight reads.  Not zeroed: a run reads only what its own stage_in and run kernels wrote
+        if (hipSetDevice(p->desc.device) != hipSuccess ||
+            hipMalloc((void **)&p->sbuf, 2u * (size_t)p->n_slots * p->desc.max_frames * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            p->sbuf = nullptr;
+            return p->fail(DSPFX_ERR_OOM, "mixmatrix set_staging: no device memory for the seat-ordered copies (dspfx_mixmatrix_staging_bytes)");
+        }
+    }
+    p->mode.store(mode, std::memory_order_release);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_staging(dspfx_mixmatrix *p, uint32_t *mode_out) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (!mode_out) return p->fail(DSPFX_ERR_INVALID, "mixmatrix staging: no mode_out");
+    *mode_out = p->mode.load(std::memory_order_acquire);
+    return DSPFX_OK;
 }
 
 extern "C" int dspfx_mixmatrix_assign(dspfx_mixmatrix *p, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count, uint32_t preset) {
@@ -1015,8 +1286,14 @@ extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint3
     std::lock_guard<std::mutex> lk(p->mu);
     if (!block || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: block, out or n_frames");
     const uintptr_t bytes = (uintptr_t)p->desc.n_channels * n_frames * sizeof(float), b0 = (uintptr_t)block, o0 = (uintptr_t)out;
-    if (b0 < o0 + bytes && o0 < b0 + bytes)
-        return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block (every listener reads every source of its room: no in-place form)");
+    // (the mode is read once: a run is wholly one mode, the one of the last set_staging that returned before it)
+    const bool staged = p->mode.load(std::memory_order_acquire) == DSPFX_MIXMATRIX_STAGED;
+    if (b0 < o0 + bytes && o0 < b0 + bytes) {
+        if (!staged)
+            return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block (every listener reads every source of its room: no in-place form)");
+        // staged: stage_in has read the whole block before stage_out writes the first sample, so out == block is in place
+        if (b0 != o0) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block in part (a staged run takes out == block, or no overlap)");
+    }
     hipStream_t s = (hipStream_t)stream;
     BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
     BANK_HIP_WHY(order(p, s), "stream order");
@@ -1033,6 +1310,19 @@ extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint3
     a.nf = n_frames;
     a.normalise = p->desc.normalise;
     a.seat_chan = p->seat_chan;
+    a.sin = p->sbuf;
+    a.sout = p->sbuf ? p->sbuf + (size_t)p->n_slots * p->desc.max_frames : nullptr;
+    a.MF = p->desc.max_frames;
+    if (staged) {                                // block -> sin, the chain over the seats, sout -> out: all three behind the stores
+        const dim3 tg((a.N + SG - 1) / SG, (n_frames + FT - 1) / FT);
+        mixmatrix_stage_in<<<tg, WG, 0, s>>>(block, p->sbuf, p->slot_of, a.N, a.W, n_frames, a.MF);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_stage_in");
+        mixmatrix_run<true, true><<<dim3(p->n_items, tg.y), WG, 0, s>>>(a);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run_staged");
+        mixmatrix_stage_out<<<tg, WG, 0, s>>>(a.sout, out, p->slot_of, a.N, a.W, n_frames, a.MF);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_stage_out");
+        return DSPFX_OK;
+    }
     if (p->roomless) {                           // (a seated bank's: the other has nobody without a room)
         mixmatrix_zero_roomless<<<(a.N + WG - 1) / WG, WG, 0, s>>>(out, p->room_of, a.N, a.W, n_frames);
         BANK_HIP_WHY(hipGetLastError(), "mixmatrix_zero_roomless");

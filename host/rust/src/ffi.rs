@@ -275,6 +275,8 @@ pub const DSPFX_STRIPS_MAX_BANDS: u32 = 8;
 pub const DSPFX_MIXMATRIX_MAX_ROOM: u32 = 1024;
 pub const DSPFX_MIXMATRIX_MIX_MINUS: u32 = 0;
 pub const DSPFX_MIXMATRIX_ZERO: u32 = 1;
+pub const DSPFX_MIXMATRIX_DIRECT: u32 = 0;
+pub const DSPFX_MIXMATRIX_STAGED: u32 = 1;
 /// `DSPFX_MIXGROUPS_NO_ROOM`: the id of a channel that sits in no room.
 pub const DSPFX_MIXGROUPS_NO_ROOM: u32 = 0xFFFF_FFFF;
 /// `DSPFX_MIXMATRIX_NO_ROOM`: the same, for `dspfx_mixmatrix_assign`.
@@ -492,4 +494,8 @@ extern "C" {
     pub fn dspfx_mixmatrix_seats(m: *mut dspfx_mixmatrix, host_seats_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixmatrix_occupancy(m: *mut dspfx_mixmatrix, host_counts_out: *mut u32) -> c_int;
     pub fn dspfx_mixmatrix_reseat(room_of_io: *mut u32, seat_of_io: *mut u32, seats: *const u32, n_groups: u32, n_channels: u64, room_ids: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_mixmatrix_set_staging(m: *mut dspfx_mixmatrix, mode: u32) -> c_int;
+    pub fn dspfx_mixmatrix_staging(m: *mut dspfx_mixmatrix, mode_out: *mut u32) -> c_int;
+    pub fn dspfx_mixmatrix_staging_bytes(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, seats: *const u32, max_frames: u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_mixmatrix_scatter(room_of: *const u32, seat_of: *const u32, seats: *const u32, n_groups: u32, n_channels: u64, chunks_out: *mut u64, lines_out: *mut u64) -> c_int;
 }

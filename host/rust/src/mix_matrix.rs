@@ -133,6 +133,49 @@ impl MixMatrix {
         }
         Ok(())
     }
+    /// A seated bank: the mode of the runs submitted after the call, `DSPFX_MIXMATRIX_DIRECT` or `DSPFX_MIXMATRIX_STAGED`.  Staged
+    /// runs transpose the block into a seat-ordered copy, run the same chain over it and transpose back: the direct run's bits at a
+    /// cost that does not depend on the seating, and `run` with `out == block` in place.  The first switch allocates
+    /// `staging_bytes(..)` of device memory.  Any thread, while runs are in flight.
+    pub fn set_staging(&self, mode: u32) -> Result<(), Error> {
+        let rc = unsafe { dspfx_mixmatrix_set_staging(self.h, mode) };
+        self.check(rc, "dspfx_mixmatrix_set_staging")
+    }
+    /// The mode of the next run.
+    pub fn staging(&self) -> Result<u32, Error> {
+        let mut mode = 0u32;
+        let rc = unsafe { dspfx_mixmatrix_staging(self.h, &mut mode) };
+        self.check(rc, "dspfx_mixmatrix_staging")?;
+        Ok(mode)
+    }
+    /// The bytes `DSPFX_MIXMATRIX_STAGED` adds to the seated bank of this plan (a pure host function).
+    pub fn staging_bytes(channels: u64, group_start: &[u64], seats: &[u32], tile_channels: u32, max_frames: u32) -> Result<u64, Error> {
+        let g = group_start.len().saturating_sub(1);
+        if seats.len() != g {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "seats: one count per room".into() });
+        }
+        let mut bytes = 0u64;
+        let rc = unsafe { dspfx_mixmatrix_staging_bytes(group_start.as_ptr(), g as u32, channels, tile_channels, seats.as_ptr(), max_frames, &mut bytes) };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_staging_bytes") });
+        }
+        Ok(bytes)
+    }
+    /// How scattered a seating is (a pure host function): `(chunks, lines)`, the runs of 32 seats that hold anybody and the lines of
+    /// 32 adjacent channels they read per frame.  `lines / chunks` near 1: run direct; towards 32: run staged.
+    pub fn scatter(room_of: &[u32], seat_of: &[u32], seats: &[u32]) -> Result<(u64, u64), Error> {
+        if room_of.len() != seat_of.len() {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "room_of and seat_of are equally long".into() });
+        }
+        let (mut chunks, mut lines) = (0u64, 0u64);
+        let rc = unsafe {
+            dspfx_mixmatrix_scatter(room_of.as_ptr(), seat_of.as_ptr(), seats.as_ptr(), seats.len() as u32, room_of.len() as u64, &mut chunks, &mut lines)
+        };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_mixmatrix_scatter") });
+        }
+        Ok((chunks, lines))
+    }
     /// `plan` for a seated bank: the edges are the seats rounded up to 32.
     pub fn plan_seats(channels: u64, group_start: &[u64], seats: &[u32], tile_channels: u32) -> Result<MixMatrixPlan, Error> {
         let g = group_start.len().saturating_sub(1);
@@ -155,7 +198,7 @@ impl MixMatrix {
     pub fn channels(&self) -> u32 { self.channels }
     pub fn rooms(&self) -> u32 { self.rooms }
     /// A DEVICE block of `n_frames` frames in the bank's layout through every room's matrix into the DEVICE block `out`, which
-    /// may not overlap `block`.  Asynchronous on `stream`.
+    /// may not overlap `block` (in `DSPFX_MIXMATRIX_STAGED` it may BE `block`).  Asynchronous on `stream`.
     pub unsafe fn run(&self, block: *const f32, n_frames: u32, out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
         let rc = dspfx_mixmatrix_run(self.h, block, n_frames, out, stream);
         self.check(rc, "dspfx_mixmatrix_run")

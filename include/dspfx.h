@@ -1220,7 +1220,7 @@ int dspfx_mixmatrix_destroy(dspfx_mixmatrix *m);
 const char *dspfx_mixmatrix_last_error(const dspfx_mixmatrix *m);
 /* block, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out may NOT overlap block:
  * a room's inputs are all needed after its first outputs exist, so there is no in-place form; an overlap is DSPFX_ERR_INVALID
- * and nothing is launched.  Asynchronous on `stream`; a run on another stream than the one before first waits (on the device)
+ * and nothing is launched (a seated bank in DSPFX_MIXMATRIX_STAGED, below, takes out == block).  Asynchronous on `stream`; a run on another stream than the one before first waits (on the device)
  * for that one (the rules of dspfx_mixgroups_run).  Queued stores go onto the stream ahead of the kernel, in the order they
  * were made. */
 int dspfx_mixmatrix_run(dspfx_mixmatrix *m, const float *block, uint32_t n_frames, float *out, void *stream);
@@ -1259,8 +1259,8 @@ int dspfx_mixmatrix_set_pairs(dspfx_mixmatrix *m, const uint32_t *listeners, con
  * a dspfx_mixmatrix_create room of S_r contiguous members whose absent members carry +0.0 samples and zero rows and columns, bit
  * for bit.  A room's bits are a function of its table, its samples and its seat arrangement alone; the error bound is the one
  * above with n = the taken seats (zero terms are exact).
- * Memory: 4 * sum of S_r^2 bytes of tables (dspfx_mixmatrix_plan_seats), 4 bytes per seat and 8 per channel on the device, and
- * 4 bytes per seat and 8 per channel on the host.
+ * Memory: 4 * sum of S_r^2 bytes of tables (dspfx_mixmatrix_plan_seats), 4 bytes per seat and 12 per channel on the device (the
+ * last 4 are the channel -> seat table of the staged run, below), and 4 bytes per seat and 8 per channel on the host.
  * Stores on a seated bank: set_rows / set_cols take lines of row_len = S_r values indexed by SEAT; the channels named must all
  * sit in one room by the seating so far (in any seats of it); a value given for an empty seat is stored as +0.0.
  * dspfx_mixmatrix_fill with DSPFX_MIXMATRIX_MIX_MINUS means 1.0 between two different taken seats. */
@@ -1294,6 +1294,47 @@ int dspfx_mixmatrix_occupancy(dspfx_mixmatrix *m, uint32_t *host_counts_out);
  * in dspfx_mixmatrix_last_error(NULL), nothing changed on a refusal.  dspfx_mixmatrix_assign uses the same code. */
 int dspfx_mixmatrix_reseat(uint32_t *room_of_io, uint32_t *seat_of_io, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
                            const uint32_t *room_ids, uint64_t first_channel, uint64_t count);
+
+/* ---- seated banks: the staged run, whose cost does not depend on the seating -----------------------------------------------
+ * The direct run gathers: it reads x[f][chan_r(s)] for 32 seats at a time, one lane per seat, and in either layout a channel's
+ * consecutive frames are a whole row apart, so the only locality it can have is between seats whose CHANNEL NUMBERS are
+ * adjacent.  At the seating create gives, a chunk of 32 seats is one line per frame; once participants have wandered it is up
+ * to 32 lines per frame for 32 useful words, read again by every listener tile and paid again by the stores.  Ordering a room's
+ * seats by channel would not help: what counts is whether the members are neighbouring channels, not the order they sit in
+ * (and a new order would change the room's summation order, and so its bits).
+ * DSPFX_MIXMATRIX_STAGED runs three kernels instead: mixmatrix_stage_in reads the block once, coalesced, and writes every seated
+ * channel's frames contiguously into its seat's row of a seat-ordered copy; the same MFMA chain runs over that copy, reading
+ * and writing along frames; mixmatrix_stage_out transposes the result back and writes +0.0 for the channels in no room.  Every
+ * pass moves whole lines whatever the seating, and the accumulator chain is the direct run's term for term -- ascending seat
+ * order, +0.0 at empty seats, whose stale rows are never read -- so a room's bits are the same in both modes.  The mode costs
+ * four more passes over the block; dspfx_mixmatrix_scatter says when that is the cheaper way (DESIGN.md §8 has the figures).
+ * Memory: two copies of (sum of S_r) x max_frames f32, allocated by the first switch to STAGED and kept until destroy
+ * (dspfx_mixmatrix_staging_bytes; 1 GiB + 4 MiB for 4096 rooms of 256 seats and 128 frames).  The channel -> seat table the
+ * transposes go by (4 bytes per channel) is kept by every seated bank from create on, in order with the assigns. */
+#define DSPFX_MIXMATRIX_DIRECT 0
+#define DSPFX_MIXMATRIX_STAGED 1
+/* The mode of the runs submitted after the call returns; a run is wholly one mode.  Any thread, while runs are in flight; never
+ * waits for the device or for a run.  DSPFX_ERR_STATE on a bank not made by dspfx_mixmatrix_create_seats; an unknown mode is
+ * DSPFX_ERR_INVALID and changes nothing.  The first switch to DSPFX_MIXMATRIX_STAGED allocates the copies on the calling thread;
+ * if that fails the call is DSPFX_ERR_OOM and the mode is unchanged.  The memory is never zeroed and never freed before
+ * destroy.
+ * dspfx_mixmatrix_run in staged mode: the same contract, except that out == block (the very same pointer) is allowed: every
+ * read of the block is finished before the first write of out.  A partial overlap is still refused, and so is any overlap in
+ * direct mode. */
+int dspfx_mixmatrix_set_staging(dspfx_mixmatrix *m, uint32_t mode);
+int dspfx_mixmatrix_staging(dspfx_mixmatrix *m, uint32_t *mode_out);
+/* PURE HOST function: the bytes DSPFX_MIXMATRIX_STAGED adds to a seated bank of this plan (checked as dspfx_mixmatrix_plan_seats
+ * checks it): 2 * (sum of S_r) * max_frames * 4 for the two copies, and 4 * n_channels for the channel -> seat table. */
+int dspfx_mixmatrix_staging_bytes(const uint64_t *group_start, uint32_t n_groups, uint64_t n_channels, uint32_t tile_channels, const uint32_t *seats,
+                                  uint32_t max_frames, uint64_t *bytes_out);
+/* PURE HOST function: how scattered a seating is -- "is it time to turn staging on?".  room_of[n_channels], seat_of[n_channels]
+ * and seats[n_groups] as dspfx_mixmatrix_reseat takes them (the same checks).  Every run of 32 consecutive seats of a room that
+ * holds at least one channel is a CHUNK of the direct run, and the distinct values of channel / 32 among its channels are the
+ * LINES the chunk reads per frame in a layout whose rows are 128-byte aligned: *chunks_out and *lines_out are the totals (either
+ * may be NULL).  With rooms that begin at multiples of 32 the seating of create gives lines == chunks; a shuffled seating
+ * approaches 32 lines per chunk. */
+int dspfx_mixmatrix_scatter(const uint32_t *room_of, const uint32_t *seat_of, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
+                            uint64_t *chunks_out, uint64_t *lines_out);
 
 #ifdef __cplusplus
 }

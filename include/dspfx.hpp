@@ -634,7 +634,8 @@ class MixMatrix {
     ~MixMatrix() { dspfx_mixmatrix_destroy(p_); }
     MixMatrix(const MixMatrix &) = delete;
     MixMatrix &operator=(const MixMatrix &) = delete;
-    // device block of n_frames -> device block in the same layout; out may not overlap block (no in-place form); asynchronous on `stream`
+    // device block of n_frames -> device block in the same layout; out may not overlap block (no in-place form, except out == block
+    // in DSPFX_MIXMATRIX_STAGED); asynchronous on `stream`
     void run(const float *block, std::uint32_t n_frames, float *out, void *stream = nullptr) { chk(dspfx_mixmatrix_run(p_, block, n_frames, out, stream)); }
     // what listeners [first_channel, first_channel + count) of ONE room hear: host_values[count][row_len], row_len = the room's members.
     // Any thread; never waits; applies, whole, to the runs submitted after it.
@@ -684,6 +685,15 @@ class MixMatrix {
         std::vector<std::uint32_t> v(rooms);
         chk(dspfx_mixmatrix_occupancy(p_, v.data()));
         return v;
+    }
+    // a seated bank: the mode of the runs submitted after the call (dspfx_mixmatrix_set_staging).  DSPFX_MIXMATRIX_STAGED transposes the
+    // block into a seat-ordered copy, runs the same chain over it and transposes back: the direct run's bits at a cost that does not
+    // depend on the seating, and run(block, n, block) in place.  The first switch allocates mixmatrix_staging_bytes(...).  Any thread
+    void set_staging(std::uint32_t mode) { chk(dspfx_mixmatrix_set_staging(p_, mode)); }
+    std::uint32_t staging() {
+        std::uint32_t mode = 0;
+        chk(dspfx_mixmatrix_staging(p_, &mode));
+        return mode;
     }
     // M[listeners[i]][sources[i]] = gains[i] by channel number, in order; each pair two channels of one room
     void set_pairs(const std::vector<std::uint32_t> &listeners, const std::vector<std::uint32_t> &sources, const std::vector<float> &gains) {
@@ -737,6 +747,30 @@ inline void mixmatrix_reseat(std::vector<std::uint32_t> &room_of, std::vector<st
     const int rc = dspfx_mixmatrix_reseat(room_of.data(), seat_of.data(), seats.data(), (std::uint32_t)seats.size(), room_of.size(), ids.data(), first_channel,
                                           ids.size());
     if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
+}
+
+// The bytes DSPFX_MIXMATRIX_STAGED adds to the seated bank of this plan (dspfx_mixmatrix_staging_bytes: a pure host function)
+inline std::uint64_t mixmatrix_staging_bytes(std::uint64_t channels, const std::vector<std::uint64_t> &group_start, const std::vector<std::uint32_t> &seats,
+                                             std::uint32_t max_frames = DSPFX_BUF_SIZE, std::uint32_t tile_channels = 0) {
+    const std::uint32_t G = (std::uint32_t)(group_start.empty() ? 0 : group_start.size() - 1);
+    if (seats.size() != G) throw Error(DSPFX_ERR_INVALID, "seats: one count per room");
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_mixmatrix_staging_bytes(group_start.data(), G, channels, tile_channels, seats.data(), max_frames, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
+    return bytes;
+}
+// How scattered a seating is (dspfx_mixmatrix_scatter: a pure host function): the chunks of 32 seats that hold anybody, and the lines
+// of 32 adjacent channels they read per frame.  lines / chunks near 1: the direct run is the cheaper; towards 32: the staged one
+struct MixMatrixScatter {
+    std::uint64_t chunks = 0, lines = 0;
+};
+inline MixMatrixScatter mixmatrix_scatter(const std::vector<std::uint32_t> &room_of, const std::vector<std::uint32_t> &seat_of,
+                                          const std::vector<std::uint32_t> &seats) {
+    if (room_of.size() != seat_of.size()) throw Error(DSPFX_ERR_INVALID, "room_of and seat_of are equally long");
+    MixMatrixScatter r;
+    const int rc = dspfx_mixmatrix_scatter(room_of.data(), seat_of.data(), seats.data(), (std::uint32_t)seats.size(), room_of.size(), &r.chunks, &r.lines);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_mixmatrix_last_error(nullptr));
+    return r;
 }
 
 // One long impulse response over N channels by partitioned FFT (dspfx_convolve_*): the FIR node's arithmetic for responses too

@@ -9,6 +9,12 @@ Device events around every call, --reps runs after 5 warm-ups, the median.  The 
 8 TB/s HBM peak.  One JSON line per case, then a table.
 
   python tools/mixmatrix_rate.py [--channels 65536,262144,1048576] [--room 32,256,1024] [--reps 20]
+
+--seats S measures the seated bank beside the unseated one, at identity seating and after each share of --moved of the channels has
+been reseated at random; --staged adds, beside every one of those columns, the same bank on the same buffers in
+MIXMATRIX_STAGED, and the seating's lines per chunk (MixMatrix.scatter), the figure a host decides the mode by:
+
+  python tools/mixmatrix_rate.py --channels 1048576 --room 256 --seats 256 --moved 0,0.01,0.1,1 --staged
 """
 import argparse
 import json
@@ -64,10 +70,12 @@ def measure(torch, n, room, reps):
     return r
 
 
-def measure_seated(torch, n, room, seats, moved, reps, movers=16):
+def measure_seated(torch, n, room, seats, moved, reps, movers=16, staged=False):
     """The seated bank beside the unseated one on the same buffers: ms per run unseated, seated at identity seating, and seated
     after each share of `moved` of the channels (cumulatively, in the order given) has been reseated into a random room with room;
-    and the ms of the first run after an assign of `movers` channels (the queued seats, lines and recounts ride ahead of it)."""
+    and the ms of the first run after an assign of `movers` channels (the queued seats, lines and recounts ride ahead of it).
+    staged: beside every seated figure the same run in MIXMATRIX_STAGED (same process, same bank, same buffers), and the lines per
+    chunk of the seating."""
     dev = torch.device("cuda:0")
     torch.manual_seed(91)
     rng = np.random.default_rng(93)
@@ -80,6 +88,18 @@ def measure_seated(torch, n, room, seats, moved, reps, movers=16):
     S = int(mix.seats[0])
     r["identity_ms"] = timed(torch, lambda: mix.run(x, B, out=y), reps)
     r["identity_x_unseated"] = r["identity_ms"] / r["unseated_ms"]
+
+    def staged_too(into, key):
+        chunks, lines = mix.scatter()
+        r.setdefault("lines_per_chunk", {})[key] = lines / max(chunks, 1)
+        mix.set_staging(pkg.MIXMATRIX_STAGED)
+        into[key] = timed(torch, lambda: mix.run(x, B, out=y), reps)
+        mix.set_staging(pkg.MIXMATRIX_DIRECT)
+
+    r["staged_ms"] = {}
+    if staged:
+        r["staging_bytes"] = pkg.mixmatrix_staging_bytes(n, seats, group_size=room, tile_channels=W, max_frames=B)
+        staged_too(r["staged_ms"], "identity")
     # the first run after a small assign, from (nearly) identity seating: `movers` channels swap rooms pairwise, then swap back
     firsts = []
     for _ in range(reps):
@@ -112,6 +132,8 @@ def measure_seated(torch, n, room, seats, moved, reps, movers=16):
             ids[who] = rng.permutation(np.repeat(np.arange(len(free)), free))[:k]
             mix.assign(ids)
         r["moved_ms"][str(share)] = timed(torch, lambda: mix.run(x, B, out=y), reps)
+        if staged:
+            staged_too(r["staged_ms"], str(share))
     mix.close()
     print(json.dumps(r), flush=True)
     return r
@@ -124,6 +146,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--seats", type=int, default=0, help="S: measure the seated bank with S seats per room beside the unseated one")
     ap.add_argument("--moved", default="0,0.01,0.1,1", help="with --seats: the shares of the channels reseated at random, cumulatively")
+    ap.add_argument("--staged", action="store_true", help="with --seats: a MIXMATRIX_STAGED column beside every seated one, and the lines per chunk")
     a = ap.parse_args()
     import torch
     if a.seats:
@@ -132,8 +155,18 @@ def main():
         for n in (int(s) for s in a.channels.split(",")):
             for room in (int(s) for s in a.room.split(",")):
                 if room <= a.seats:
-                    out.append(measure_seated(torch, n, room, a.seats, moved, a.reps))
+                    out.append(measure_seated(torch, n, room, a.seats, moved, a.reps, staged=a.staged))
                     torch.cuda.empty_cache()
+        if a.staged:
+            print(f"\ntimes in ms, median of {a.reps}; per seating: direct | staged | lines per chunk (MixMatrix.scatter)")
+            print(f"{'channels':>9} {'room':>5} {'seats':>5} {'unseated':>9} {'identity':>26} " + " ".join(f"{'moved ' + str(m):>26}" for m in moved)
+                  + f" {'staging MiB':>12}")
+            for r in out:
+                cols = [(r["identity_ms"], r["staged_ms"]["identity"], r["lines_per_chunk"]["identity"])]
+                cols += [(r["moved_ms"][str(m)], r["staged_ms"][str(m)], r["lines_per_chunk"][str(m)]) for m in moved]
+                print(f"{r['channels']:>9} {r['room']:>5} {r['seats']:>5} {r['unseated_ms']:>9.4f} "
+                      + " ".join(f"{d:>8.4f} |{s:>8.4f} |{l:>6.2f}" for d, s, l in cols) + f" {r['staging_bytes'] / 2**20:>12.0f}")
+            return
         print(f"\ntimes in ms, median of {a.reps}; moved: the share of the channels reseated at random so far")
         print(f"{'channels':>9} {'room':>5} {'seats':>5} {'unseated':>9} {'identity':>9} {'x':>6} " + " ".join(f"{'moved ' + str(m):>11}" for m in moved)
               + f" {'first run after assign':>23}")
