@@ -57,6 +57,8 @@ STRIPS_MAX_BANDS = 8            # DSPFX_STRIPS_MAX_BANDS: the BiQuad bands one C
 MIXMATRIX_MAX_ROOM = 1024       # DSPFX_MIXMATRIX_MAX_ROOM: the most members a MixMatrix room has
 MIXMATRIX_MIX_MINUS, MIXMATRIX_ZERO = 0, 1      # DSPFX_MIXMATRIX_*: MixMatrix.fill presets
 MIXMATRIX_DIRECT, MIXMATRIX_STAGED = 0, 1       # DSPFX_MIXMATRIX_*: MixMatrix.set_staging modes
+TALKERS_MAX_ROOM, TALKERS_MAX_TOP = 1024, 8     # DSPFX_TALKERS_*: the most members a Talkers room has, the most talkers it names
+TALKERS_AUTO, TALKERS_OPEN, TALKERS_SHUT = 0, 1, 2      # DSPFX_TALKERS_*: Talkers.set_pin
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -93,6 +95,10 @@ EXPORTS = [
     "dspfx_mixmatrix_set_pairs", "dspfx_mixmatrix_create_seats", "dspfx_mixmatrix_plan_seats", "dspfx_mixmatrix_assign",
     "dspfx_mixmatrix_rooms", "dspfx_mixmatrix_seats", "dspfx_mixmatrix_occupancy", "dspfx_mixmatrix_reseat",
     "dspfx_mixmatrix_set_staging", "dspfx_mixmatrix_staging", "dspfx_mixmatrix_staging_bytes", "dspfx_mixmatrix_scatter",
+    "dspfx_envelope_gain", "dspfx_talkers_plan", "dspfx_talkers_select", "dspfx_talkers_create", "dspfx_talkers_destroy",
+    "dspfx_talkers_last_error", "dspfx_talkers_run", "dspfx_talkers_assign", "dspfx_talkers_set_detector", "dspfx_talkers_set_pin",
+    "dspfx_talkers_set_top", "dspfx_talkers_set_floor", "dspfx_talkers_reset", "dspfx_talkers_views", "dspfx_talkers_room_of",
+    "dspfx_talkers_counts",
 ]
 COMM_ID_BYTES = 128
 
@@ -167,6 +173,12 @@ class _DelaysDesc(C.Structure):
 class _MixMatrixDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("n_groups", C.c_uint32), ("normalise", C.c_uint32),
+                ("group_start", C.POINTER(C.c_uint64))]
+
+
+class _TalkersDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("n_groups", C.c_uint32), ("top", C.c_uint32),
                 ("group_start", C.POINTER(C.c_uint64))]
 
 
@@ -367,6 +379,25 @@ def lib():
     L.dspfx_mixmatrix_staging.argtypes = [vp, u32p]
     L.dspfx_mixmatrix_staging_bytes.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.dspfx_mixmatrix_scatter.argtypes = [u32p, u32p, u32p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    u8p, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_float)
+    L.dspfx_envelope_gain.restype = C.c_float
+    L.dspfx_envelope_gain.argtypes = [C.c_float]
+    L.dspfx_talkers_plan.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.dspfx_talkers_select.argtypes = [fp, u32p, C.c_uint64, C.c_uint32, u8p, C.c_float, u8p, C.POINTER(C.c_int32), fp, fp]
+    L.dspfx_talkers_create.argtypes = [C.POINTER(_TalkersDesc), C.POINTER(vp)]
+    L.dspfx_talkers_destroy.argtypes = [vp]
+    L.dspfx_talkers_last_error.restype = C.c_char_p
+    L.dspfx_talkers_last_error.argtypes = [vp]
+    L.dspfx_talkers_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_talkers_assign.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_talkers_set_detector.argtypes = [vp, fp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_talkers_set_pin.argtypes = [vp, u8p, C.c_uint64, C.c_uint64]
+    L.dspfx_talkers_set_top.argtypes = [vp, u8p, C.c_uint64, C.c_uint64]
+    L.dspfx_talkers_set_floor.argtypes = [vp, C.c_float]
+    L.dspfx_talkers_reset.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.dspfx_talkers_views.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.dspfx_talkers_room_of.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_talkers_counts.argtypes = [vp, u32p]
     _lib = L
     return L
 
@@ -1660,6 +1691,189 @@ class ChannelDelays(_Bank):
     def reset(self):
         """Every present channel's ring back to zeros (on the stream last used); the sliders and the nodes stay."""
         self._chk(self.L.dspfx_delays_reset(self.h))
+
+
+def envelope_gain(frames: float) -> np.float32:
+    """dspfx_envelope_gain, a pure host function: attack or release frames -> the detector's gain, 0 for 0 frames, else
+    powf(e, -1 / frames) -- what Talkers.set_detector stores and what an Engine computes for its Envelope node."""
+    return np.float32(lib().dspfx_envelope_gain(float(frames)))
+
+
+def talkers_plan(channels: int, groups: int) -> int:
+    """dspfx_talkers_plan, a pure host function (no GPU): the device bytes of a Talkers bank's tables, 29 per channel and 69 per
+    room plus 4."""
+    L = lib()
+    n = C.c_uint64()
+    rc = L.dspfx_talkers_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, int(groups) & 0xFFFFFFFF, C.byref(n))
+    _raise(L, "talkers", rc)
+    return int(n.value)
+
+
+def _u8_per(values, n: int, what: str) -> np.ndarray:
+    """a scalar or [n] small integers -> uint8[n]"""
+    v = np.asarray(values)
+    if v.dtype.kind not in "iu" or v.size not in (1, n) or (v.size and (v.min() < 0 or v.max() > 255)):
+        raise DspfxError(-1, f"{what}: one small integer, or one per entry")
+    return np.ascontiguousarray(np.broadcast_to(v.reshape(-1), (n,)), np.uint8)
+
+
+def talkers_select(levels, room_of, groups: int, top=3, floor: float = 0.0, pins=None):
+    """dspfx_talkers_select, a pure host function (no GPU): the bank's selection rule on host arrays.  levels float32[N] (as the bank
+    leaves them: non-negative, no NaN), room_of [N] (a room in [0, groups) or NO_ROOM), top a scalar or [groups] (1 .. 8), pins
+    None (all TALKERS_AUTO) or [N] -> (talkers int32[groups, 8], -1 where there is none; talker_levels float32[groups, 8]; target
+    float32[N]: 1.0 for a talker or an OPEN pin, 0.0 otherwise).  Per room the candidates are the AUTO members with level > floor,
+    ranked by level descending, then channel ascending."""
+    L = lib()
+    lv = np.ascontiguousarray(levels, np.float32).reshape(-1)
+    ro = _room_ids(room_of)
+    if len(ro) != len(lv):
+        raise DspfxError(-1, "talkers select: levels and room_of name different numbers of channels")
+    G = max(int(groups), 0)
+    tp = _u8_per(top, G, "talkers select: top")
+    pn = None if pins is None else _u8_per(pins, len(lv), "talkers select: pins")
+    talk, tl, tg = np.full((G, TALKERS_MAX_TOP), -1, np.int32), np.zeros((G, TALKERS_MAX_TOP), np.float32), np.zeros(len(lv), np.float32)
+    u8p, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_float)
+    rc = L.dspfx_talkers_select(lv.ctypes.data_as(fp), ro.ctypes.data_as(C.POINTER(C.c_uint32)), len(lv), G, tp.ctypes.data_as(u8p), float(floor),
+                                pn.ctypes.data_as(u8p) if pn is not None else None, talk.ctypes.data_as(C.POINTER(C.c_int32)),
+                                tl.ctypes.data_as(fp), tg.ctypes.data_as(fp))
+    _raise(L, "talkers", rc)
+    return talk, tl, tg
+
+
+class Talkers(_Bank):
+    """Per-channel levels and each room's loudest, gated live (include/dspfx.h, dspfx_talkers_*): every channel has its own Envelope
+    node (attack and release in frames, `set_detector`), every room -- group_start / group_size as MixGroups takes them, 1 .. 1024
+    members, reseated live by `assign` -- gets its `top` loudest members chosen on the device, and run() passes those members and
+    ramps the others out, over a device block in the layout of `tile_channels` (as Engine's).  A run first gates with the targets
+    the run before left, then meters, then selects: a selection is audible one block later, and a fresh bank copies its first
+    block.  Between ChannelStrips / ChannelDelays and the room mixes.  Asynchronous on `stream`."""
+
+    _C = "talkers"
+    _WHY = True
+
+    def __init__(self, channels: int, group_start=None, group_size=None, top: int = 3, tile_channels: int = 0, max_frames: int = BUF_SIZE,
+                 device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
+        self.max_frames, self.top = int(max_frames), int(top)
+        self.group_start = _group_table(self.channels, group_start, group_size)
+        self.groups = len(self.group_start) - 1
+        d = _TalkersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
+                         self.groups, self.top & 0xFFFFFFFF, self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
+        self._create(d)  # the table is copied before this returns
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._chk(self.L.dspfx_talkers_views(self.h, *[C.byref(p) for p in ptrs]))
+        self._views = [p.value for p in ptrs]
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, gate: bool = True, stream: int = 0):
+        """One device block: gate it with the targets of the run before -> `out`, a device block in the same layout (made when not
+        given; out=block works in place), then meter it and choose every room's talkers.  gate=False only meters and selects: no
+        sample is written, the gates stay, and None is returned."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if not gate:
+            out = None
+        elif out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_talkers_run(self.h, _ptr(block), _ptr(out) if out is not None else None, int(n_frames),
+                                           C.c_void_p(stream) if stream else None))
+        return out
+
+    def _range(self, first, count, arrays, total):
+        n = None
+        for v in arrays:
+            if v is not None and np.ndim(v) != 0:
+                m = int(np.size(v))
+                if n is not None and m != n:
+                    raise DspfxError(-1, "talkers: the arrays name different numbers of entries")
+                n = m
+        if n is None:
+            n = total - int(first) if count is None else int(count)
+        return n
+
+    def set_detector(self, attack=None, release=None, first_channel: int = 0, count: Optional[int] = None):
+        """Store the attack and release sliders (frames) of channels from first_channel: arrays (one value per channel) or scalars
+        for `count` channels (default: all from first_channel).  A slider left None keeps each channel's value.  No envelope is
+        touched.  Any thread; applies to the runs submitted after it."""
+        n = self._range(first_channel, count, (attack, release), self.channels)
+
+        def arr(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
+            return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+        a, ap = arr(attack)
+        r, rp = arr(release)
+        self._chk(self.L.dspfx_talkers_set_detector(self.h, ap, rp, int(first_channel), n))
+
+    def set_pin(self, pins, first_channel: int = 0, count: Optional[int] = None):
+        """Store the pins of channels from first_channel (TALKERS_AUTO, TALKERS_OPEN: always passed and never ranked, TALKERS_SHUT:
+        never passed): an array, or one value for `count` channels (default: all from first_channel)."""
+        n = self._range(first_channel, count, (pins,), self.channels)
+        v = _u8_per(pins, max(n, 0), "talkers set_pin")
+        self._chk(self.L.dspfx_talkers_set_pin(self.h, v.ctypes.data_as(C.POINTER(C.c_uint8)), int(first_channel), n))
+
+    def set_top(self, tops, first_room: int = 0, count: Optional[int] = None):
+        """Store the top (1 .. 8) of rooms from first_room: an array, or one value for `count` rooms (default: all from first_room)."""
+        n = self._range(first_room, count, (tops,), self.groups)
+        v = _u8_per(tops, max(n, 0), "talkers set_top")
+        self._chk(self.L.dspfx_talkers_set_top(self.h, v.ctypes.data_as(C.POINTER(C.c_uint8)), int(first_room), n))
+
+    def set_floor(self, floor: float):
+        """Store the bank's floor: only a level strictly above it makes a candidate."""
+        self._chk(self.L.dspfx_talkers_set_floor(self.h, float(floor)))
+
+    def assign(self, ids, first_channel: int = 0):
+        """Seat channels [first_channel, first_channel + len(ids)) in the rooms `ids` (an int for one channel, or any integer
+        sequence, numpy array or torch tensor; each in [0, groups) or NO_ROOM).  A bad id, a range past the channels, or a room
+        that would exceed 1024 members stores nothing.  Any thread, while runs are in flight: it holds for the runs submitted after
+        it returns."""
+        v = _room_ids(ids)
+        self._chk(self.L.dspfx_talkers_assign(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), len(v)))
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None):
+        """Envelope and level back to 0, gate and target to 1 on `count` channels from first_channel (default: all from it); queued
+        like a store.  The way out for a channel whose envelope became NaN."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        self._chk(self.L.dspfx_talkers_reset(self.h, int(first_channel), n))
+
+    def room_of(self) -> np.ndarray:
+        """uint32[channels]: the room of every channel (NO_ROOM: none) by every assign made so far."""
+        v = np.zeros(self.channels, np.uint32)
+        self._chk(self.L.dspfx_talkers_room_of(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), 0, len(v)))
+        return v
+
+    def counts(self) -> np.ndarray:
+        """uint32[G]: the members of every room."""
+        v = np.zeros(self.groups, np.uint32)
+        self._chk(self.L.dspfx_talkers_counts(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return v
+
+    def _view(self, which, shape, typestr):
+        import torch
+        addr = self._views[which]
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (addr, False), "version": 2}
+        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+
+    def levels(self):
+        """float32[channels] on the device: every channel's largest envelope of the last block (valid after a run, on its stream)."""
+        return self._view(0, (self.channels,), "<f4")
+
+    def targets(self):
+        """float32[channels] on the device: 1.0 where the next gated run passes the channel, 0.0 where it ramps it out."""
+        return self._view(1, (self.channels,), "<f4")
+
+    def talkers(self):
+        """int32[groups, 8] on the device: every room's talkers, loudest first, -1 where there is none."""
+        return self._view(2, (self.groups, TALKERS_MAX_TOP), "<i4")
+
+    def talker_levels(self):
+        """float32[groups, 8] on the device: the talkers' levels, 0.0 where there is none."""
+        return self._view(3, (self.groups, TALKERS_MAX_TOP), "<f4")
 
 
 

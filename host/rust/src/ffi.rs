@@ -183,6 +183,26 @@ pub struct dspfx_delays_desc {
     pub link_flags: u32,
 }
 
+/// Opaque talker bank handle (`typedef struct dspfx_talkers dspfx_talkers`).
+#[repr(C)]
+pub struct dspfx_talkers {
+    _private: [u8; 0],
+}
+
+/// The talker bank's descriptor (`dspfx_talkers_create`); `group_start` is a host table of `n_groups + 1` entries read at create.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_talkers_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub n_groups: u32,
+    pub top: u32,
+    pub group_start: *const u64,
+}
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -281,6 +301,15 @@ pub const DSPFX_MIXMATRIX_STAGED: u32 = 1;
 pub const DSPFX_MIXGROUPS_NO_ROOM: u32 = 0xFFFF_FFFF;
 /// `DSPFX_MIXMATRIX_NO_ROOM`: the same, for `dspfx_mixmatrix_assign`.
 pub const DSPFX_MIXMATRIX_NO_ROOM: u32 = 0xFFFF_FFFF;
+/// the most members a talker bank's room has, and the most talkers it names
+pub const DSPFX_TALKERS_MAX_ROOM: u32 = 1024;
+pub const DSPFX_TALKERS_MAX_TOP: u32 = 8;
+/// a channel's pin (`dspfx_talkers_set_pin`): ranked; always passed and never ranked; never passed
+pub const DSPFX_TALKERS_AUTO: u8 = 0;
+pub const DSPFX_TALKERS_OPEN: u8 = 1;
+pub const DSPFX_TALKERS_SHUT: u8 = 2;
+/// `DSPFX_TALKERS_NO_ROOM`: the same, for `dspfx_talkers_assign` and `dspfx_talkers_select`.
+pub const DSPFX_TALKERS_NO_ROOM: u32 = 0xFFFF_FFFF;
 
 // link flags
 pub const DSPFX_LINK_INTERNAL: u32 = 1;
@@ -477,6 +506,22 @@ extern "C" {
     pub fn dspfx_delays_reset(d: *mut dspfx_delays) -> c_int;
     pub fn dspfx_delays_present(d: *mut dspfx_delays, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_delays_lengths(d: *mut dspfx_delays, host_lengths_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_envelope_gain(frames: f32) -> f32;
+    pub fn dspfx_talkers_plan(channels: u64, n_groups: u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_talkers_select(levels: *const f32, room_of: *const u32, n_channels: u64, n_groups: u32, top: *const u8, floor: f32, pins: *const u8, talkers_out: *mut i32, levels_out: *mut f32, target_out: *mut f32) -> c_int;
+    pub fn dspfx_talkers_create(desc: *const dspfx_talkers_desc, out: *mut *mut dspfx_talkers) -> c_int;
+    pub fn dspfx_talkers_destroy(t: *mut dspfx_talkers) -> c_int;
+    pub fn dspfx_talkers_last_error(t: *const dspfx_talkers) -> *const c_char;
+    pub fn dspfx_talkers_run(t: *mut dspfx_talkers, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_talkers_assign(t: *mut dspfx_talkers, host_room_ids: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_talkers_set_detector(t: *mut dspfx_talkers, host_attack: *const f32, host_release: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_talkers_set_pin(t: *mut dspfx_talkers, host_pins: *const u8, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_talkers_set_top(t: *mut dspfx_talkers, host_tops: *const u8, first_room: u64, count: u64) -> c_int;
+    pub fn dspfx_talkers_set_floor(t: *mut dspfx_talkers, floor: f32) -> c_int;
+    pub fn dspfx_talkers_reset(t: *mut dspfx_talkers, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_talkers_views(t: *mut dspfx_talkers, level_out: *mut *const f32, target_out: *mut *const f32, talkers_out: *mut *const i32, talker_levels_out: *mut *const f32) -> c_int;
+    pub fn dspfx_talkers_room_of(t: *mut dspfx_talkers, host_ids_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_talkers_counts(t: *mut dspfx_talkers, host_counts_out: *mut u32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

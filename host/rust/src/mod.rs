@@ -8,4 +8,5 @@ pub mod convolver;
 pub mod convolver_responses;
 pub mod channel_strips;
 pub mod channel_delays;
+pub mod talkers;
 pub mod mix_matrix;

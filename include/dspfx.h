@@ -1159,6 +1159,125 @@ int dspfx_delays_present(dspfx_delays *d, uint32_t *host_present_out, uint64_t f
 /* D_c per channel of the range, 0 where there is no node, from the same host tables. */
 int dspfx_delays_lengths(dspfx_delays *d, uint32_t *host_lengths_out, uint64_t first_channel, uint64_t count);
 
+/* ---- talker bank: per-channel levels and each room's K loudest, gated live ------------------------------------------
+ * An engine's Envelope node (nodes/envelope.rs, a peak follower) has one (attack, release) pair for all N channels and replaces
+ * the signal with its envelope.  In the reference every graph owns its Envelope node and feeds slider ports from it: an Envelope
+ * into a Gain.  At the scale of a room that is a gate driven by the room's ranking.  This bank is both halves over N channels in
+ * the desc's layout (tile_channels as dspfx_engine_desc): every channel has its own Envelope node, every room gets its `top`
+ * loudest members chosen on the device, and a gate passes those members and ramps the others out, so dspfx_mixgroups_run /
+ * _returns and dspfx_mixmatrix_run downstream add only the talkers.  It sits behind the channel strips and delays, ahead of the
+ * room mixes.
+ * ROOMS.  Create takes contiguous rooms as dspfx_mixgroups_create does (group_start, G + 1 indices), each of 1 ..
+ * DSPFX_TALKERS_MAX_ROOM members; dspfx_talkers_assign moves channels as dspfx_mixgroups_assign does.  The host keeps room_of[N];
+ * the device gets a member list sorted by (room, channel) and room_start[G + 1], so a seating is a function of room_of alone, not
+ * of the calls that led to it, and the selection does not care how scattered a room's members are.
+ * PER CHANNEL.  State: env (f32, starts +0.0), gate and target (f32, start 1.0).  Sliders: attack and release in frames, taken
+ * as given (no clamp), 0 and 0 by default as the node's; the host converts them with dspfx_envelope_gain.  A pin, one uint8_t:
+ * DSPFX_TALKERS_AUTO (the default), DSPFX_TALKERS_OPEN (always passed, never ranked, takes no slot) or DSPFX_TALKERS_SHUT (never
+ * passed, never ranked).
+ * PER ROOM: top, 1 .. DSPFX_TALKERS_MAX_TOP, the desc's value until dspfx_talkers_set_top stores another.  BANK-WIDE: floor, f32,
+ * 0.0 by default.
+ * ONE RUN does three things, in this order.
+ *   1. Queued stores go onto the stream, in the order they were made.
+ *   2. Pass A, per channel, frames in order.  The envelope as the engine's Envelope node computes it:
+ *            d = x < 0 ? -x : x        gain = env < d ? ga : gr        env = d + (env + (-d)) * gain       nothing contracted
+ *      so env after every frame is what the reference's node writes, bit for bit (a NaN where it has a NaN).  level[c] starts at
+ *      +0.0 and takes each frame's env whenever env > level: the block's largest env.  A NaN or a -0.0 envelope never raises it, so
+ *      a level is always a non-negative, non-NaN f32.  With out not NULL:
+ *            out[f][c] = in[f][c] * (gate + (target - gate) * r[f])            r[f] = f32(f + 1) / f32(n_frames)
+ *      one IEEE division, one f32 subtraction, multiply and add for the ramp, one multiply for the sample, nothing contracted.
+ *      With gate and target in {0, 1}: exactly 1.0; exactly +0.0; a ramp up; a ramp down; the last frame is exactly at the
+ *      target.  These are multiplications, not omissions: a NaN sample in a closed channel stays a NaN (as dspfx_mixmatrix_run
+ *      documents for unwired entries).  After the block gate = target.  out == in works in place.  out == NULL meters and selects
+ *      only: no sample is written and gate stays as it is.
+ *   3. Pass B, per room, with the tables as of this run.  The candidates are the members with pin AUTO and level > floor,
+ *      strictly; ranked by level descending, then channel number ascending; the first min(top_r, candidates) are the room's
+ *      talkers.  It writes talkers[G][8] (int32_t channel numbers, -1 where there is none), talker_levels[G][8] (f32, +0.0 where
+ *      there is none) and target[c] for EVERY channel: 1.0 for a talker and for an OPEN pin (in a room or not), +0.0 for everybody
+ *      else, SHUT pins and AUTO channels in no room included.
+ * So a selection is audible in the run after the one that measured it, and a store governs the selection at the end of the first
+ * run submitted after it: one rule and no second read of the block, at the cost of at most one block plus the one-block ramp
+ * before a new talker is fully open.  A fresh bank passes its first block bit for bit: every gate is at 1.0.
+ * A channel's output and a room's tables are the same bits in either layout, in place or not, on any stream, and whatever the
+ * other rooms carry.  No atomics; every step in a fixed order.
+ * Memory: 29 bytes per channel and 69 per room of tables on the device (dspfx_talkers_plan), 12 per channel on the host. */
+#define DSPFX_TALKERS_MAX_ROOM 1024
+#define DSPFX_TALKERS_MAX_TOP 8
+#define DSPFX_TALKERS_AUTO 0
+#define DSPFX_TALKERS_OPEN 1
+#define DSPFX_TALKERS_SHUT 2
+/* dspfx_talkers_assign, dspfx_talkers_select: the channel sits in no room */
+#define DSPFX_TALKERS_NO_ROOM 0xFFFFFFFFu
+typedef struct dspfx_talkers dspfx_talkers;
+typedef struct dspfx_talkers_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t n_groups;        /* G >= 1 rooms */
+    uint32_t top;             /* every room's top until dspfx_talkers_set_top: 1 ..= DSPFX_TALKERS_MAX_TOP */
+    const uint64_t *group_start; /* host, [n_groups + 1], read at create and copied: room g is channels [group_start[g],
+                                 group_start[g + 1]); increasing, [0] = 0, [G] = N; every room has 1 .. 1024 members */
+} dspfx_talkers_desc;
+/* PURE HOST function (no GPU, no bank): frames -> the gain the detector multiplies by, frames == 0 ? 0 : powf(e, -1 / frames)
+ * (dasp_envelope's calc_gain, with the host's libm as the reference calls it): what dspfx_talkers_set_detector stores and what
+ * dspfx_chain_set computes for an Envelope node. */
+float dspfx_envelope_gain(float frames);
+/* PURE HOST function: *bytes_out = the device bytes of a bank's tables, 29 * channels + 69 * n_groups + 4.  channels of 0 or above
+ * 2^32 - 256, or no rooms: DSPFX_ERR_INVALID, the reason in dspfx_talkers_last_error(NULL). */
+int dspfx_talkers_plan(uint64_t channels, uint32_t n_groups, uint64_t *bytes_out);
+/* PURE HOST function: pass B's rule on host arrays.  levels[n_channels] (as the bank leaves them: non-negative, no NaN),
+ * room_of[n_channels] (each below n_groups, or DSPFX_TALKERS_NO_ROOM), top[n_groups] (1 .. 8 each), pins[n_channels] or NULL for
+ * all AUTO -> talkers_out[n_groups][8], levels_out[n_groups][8], target_out[n_channels]; each of the three may be NULL.  A bad
+ * id, a bad top, or a room above DSPFX_TALKERS_MAX_ROOM: DSPFX_ERR_INVALID, the reason in dspfx_talkers_last_error(NULL). */
+int dspfx_talkers_select(const float *levels, const uint32_t *room_of, uint64_t n_channels, uint32_t n_groups, const uint8_t *top, float floor,
+                         const uint8_t *pins, int32_t *talkers_out, float *levels_out, float *target_out);
+/* A bad descriptor (a table that decreases, does not start at 0 or end at n_channels, an empty room or one above
+ * DSPFX_TALKERS_MAX_ROOM, a top of 0 or above DSPFX_TALKERS_MAX_TOP, a tile that is not a power of two dividing n_channels, another
+ * ABI version, max_frames of 0) is DSPFX_ERR_INVALID with the reason in dspfx_talkers_last_error of a NULL bank (kept per thread);
+ * all of that is checked before any device work. */
+int dspfx_talkers_create(const dspfx_talkers_desc *desc, dspfx_talkers **out);
+int dspfx_talkers_destroy(dspfx_talkers *t);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create, plan or select. */
+const char *dspfx_talkers_last_error(const dspfx_talkers *t);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames); out may be in, or NULL (meter and
+ * select only); any other overlap is the caller's error.  Asynchronous on `stream`; a run on another stream than the one before
+ * first waits (on the device) for that one, since the state is the bank's (the rules of dspfx_strips_run). */
+int dspfx_talkers_run(dspfx_talkers *t, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Seats channels [first_channel, first_channel + count) in the rooms host_room_ids (each below n_groups, or
+ * DSPFX_TALKERS_NO_ROOM).  The range, every id and every room's size after the call (at most DSPFX_TALKERS_MAX_ROOM) are checked
+ * before anything is stored: otherwise DSPFX_ERR_INVALID, the reason in dspfx_talkers_last_error, nothing changed.  Callable from
+ * any thread while runs are in flight, never waits for the device or for a run, and holds, whole, for every run submitted after it
+ * returns and for none submitted before.  A seating change, not a per-block call: O(N + G) host work and a staged copy of the
+ * member list.  A channel's envelope, gate and pin stay with the channel. */
+int dspfx_talkers_assign(dspfx_talkers *t, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count);
+/* Stores the attack and release sliders (frames) of channels [first_channel, first_channel + count) from host arrays of `count`
+ * values each; either may be NULL, which keeps each channel's value.  The store touches no envelope: the reference's slider
+ * change sets only the gain.  The contract of dspfx_strips_set_gain: any thread, never waits, staged and queued, whole for the runs
+ * submitted after it returns.  A range past the channels: DSPFX_ERR_INVALID and the reason, nothing stored. */
+int dspfx_talkers_set_detector(dspfx_talkers *t, const float *host_attack, const float *host_release, uint64_t first_channel, uint64_t count);
+/* Stores the pins of channels [first_channel, first_channel + count); a value above DSPFX_TALKERS_SHUT or a range past the
+ * channels: DSPFX_ERR_INVALID and the reason, nothing stored.  Threading and ordering as dspfx_talkers_set_detector. */
+int dspfx_talkers_set_pin(dspfx_talkers *t, const uint8_t *host_pins, uint64_t first_channel, uint64_t count);
+/* Stores the top of rooms [first_room, first_room + count); a value of 0 or above DSPFX_TALKERS_MAX_TOP, or a range past the
+ * rooms: DSPFX_ERR_INVALID and the reason, nothing stored.  Threading and ordering as dspfx_talkers_set_detector. */
+int dspfx_talkers_set_top(dspfx_talkers *t, const uint8_t *host_tops, uint64_t first_room, uint64_t count);
+/* Stores the floor (taken as given; under a NaN floor nobody is a candidate).  Queued like the other stores. */
+int dspfx_talkers_set_floor(dspfx_talkers *t, float floor);
+/* env and level back to +0.0, gate and target to 1.0 on channels [first_channel, first_channel + count); the sliders, pins and
+ * seats stay.  Queued like a store.  Also the way out for a channel whose envelope became NaN and, as in the reference, stays
+ * NaN. */
+int dspfx_talkers_reset(dspfx_talkers *t, uint64_t first_channel, uint64_t count);
+/* The device pointers of level[N], target[N], talkers[G][8] and talker_levels[G][8] (each out pointer may be NULL).  The pointers
+ * never change; what they hold is valid after a run, on its stream. */
+int dspfx_talkers_views(dspfx_talkers *t, const float **level_out, const float **target_out, const int32_t **talkers_out,
+                        const float **talker_levels_out);
+/* The room ids of channels [first_channel, first_channel + count), and every room's member count ([n_groups]), by every assign made
+ * so far (host tables). */
+int dspfx_talkers_room_of(dspfx_talkers *t, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count);
+int dspfx_talkers_counts(dspfx_talkers *t, uint32_t *host_counts_out);
+
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
  * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain

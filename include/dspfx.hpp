@@ -617,6 +617,81 @@ inline DelaysPlan delays_plan(std::uint64_t channels, float max_seconds = 0.5f, 
     return r;
 }
 
+// Per-channel levels and each room's loudest, gated live (include/dspfx.h, dspfx_talkers_*): every channel has its own Envelope node
+// (attack and release in frames), every room -- rooms as MixGroups takes them, 1 .. DSPFX_TALKERS_MAX_ROOM members, reseated live by
+// assign() -- gets its `top` loudest members chosen on the device, and run() passes those members and ramps the others out.  A run
+// gates with the targets the run before left, then meters, then selects: a selection is audible one block later, and a fresh bank
+// copies its first block.  Between ChannelStrips / ChannelDelays and the room mixes.
+class Talkers {
+  public:
+    struct Views {
+        const float *level;            // [N]
+        const float *target;           // [N]
+        const std::int32_t *talkers;   // [G][8], -1 where there is none
+        const float *talker_levels;    // [G][8]
+    };
+    Talkers(std::uint32_t channels, const std::vector<std::uint64_t> &group_start, std::uint32_t top = 3, std::uint32_t tile_channels = 0,
+            std::uint32_t max_frames = DSPFX_BUF_SIZE, int device = 0)
+        : groups_((std::uint32_t)(group_start.empty() ? 0 : group_start.size() - 1)) {
+        const dspfx_talkers_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, groups_, top, group_start.data()};
+        const int rc = dspfx_talkers_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_talkers_last_error(nullptr) ? dspfx_talkers_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~Talkers() { dspfx_talkers_destroy(p_); }
+    Talkers(const Talkers &) = delete;
+    Talkers &operator=(const Talkers &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place; out == nullptr: meter and select only, the
+    // gates stay); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_talkers_run(p_, in, out, n_frames, stream)); }
+    // the rooms of channels [first_channel, first_channel + ids.size()): each below the bank's rooms, or DSPFX_TALKERS_NO_ROOM.  Refused
+    // whole on a bad id or a room that would exceed DSPFX_TALKERS_MAX_ROOM.  Any thread; never waits.
+    void assign(const std::vector<std::uint32_t> &ids, std::uint64_t first_channel) { chk(dspfx_talkers_assign(p_, ids.data(), first_channel, ids.size())); }
+    // attack and release (frames) from host arrays; a nullptr slider keeps each channel's value.  No envelope is touched
+    void set_detector(const float *host_attack, const float *host_release, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_talkers_set_detector(p_, host_attack, host_release, first_channel, count));
+    }
+    // DSPFX_TALKERS_AUTO, _OPEN (always passed, never ranked) or _SHUT (never passed) per channel
+    void set_pin(const std::vector<std::uint8_t> &pins, std::uint64_t first_channel) { chk(dspfx_talkers_set_pin(p_, pins.data(), first_channel, pins.size())); }
+    // 1 .. DSPFX_TALKERS_MAX_TOP per room
+    void set_top(const std::vector<std::uint8_t> &tops, std::uint64_t first_room) { chk(dspfx_talkers_set_top(p_, tops.data(), first_room, tops.size())); }
+    void set_floor(float floor) { chk(dspfx_talkers_set_floor(p_, floor)); }
+    // envelope and level back to 0, gate and target to 1 on the range; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_talkers_reset(p_, first_channel, count)); }
+    // the device tables: valid after a run, on its stream
+    Views views() {
+        Views v{nullptr, nullptr, nullptr, nullptr};
+        chk(dspfx_talkers_views(p_, &v.level, &v.target, &v.talkers, &v.talker_levels));
+        return v;
+    }
+    // every channel's room and every room's member count, by every assign made so far
+    std::vector<std::uint32_t> room_of(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_talkers_room_of(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> counts() {
+        std::vector<std::uint32_t> m(groups_);
+        chk(dspfx_talkers_counts(p_, m.data()));
+        return m;
+    }
+    dspfx_talkers *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_talkers_last_error(p_) ? dspfx_talkers_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_talkers *p_ = nullptr;
+    std::uint32_t groups_ = 0;
+};
+
+// The device bytes of a Talkers bank's tables (dspfx_talkers_plan: a pure host function, no GPU).
+inline std::uint64_t talkers_plan(std::uint64_t channels, std::uint32_t groups) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_talkers_plan(channels, groups, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_talkers_last_error(nullptr));
+    return bytes;
+}
+
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
