@@ -98,6 +98,8 @@ struct ChainArgs {
     double third_rc;         // f64 1/3.0f  (SoftClip's powi(3)/3.0)
     int fast_div;            // every constant divisor of this launch passed the exhaustive check
     int xcd_remap;           // 1: blocks of one XCD (b % 8) cover a contiguous range of channel tiles
+    int walk_rev;            // 1: this launch walks its tiles back to front (work_block): what the launch before it touched last comes first
+    unsigned walk_zone;      // chain_kernel: the first and the last walk_zone workgroups of the launch store their output rows on the default cache policy (walk_cached_out)
     // Pipelined mix bus (mixpipe_prologue): the second and third reduction stage of EARLIER blocks ride in this
     // launch's first workgroups instead of separate kernels on a second stream.
     int skip_store;          // in-place launch of an empty chain that only feeds the mix bus: nothing to write back
@@ -177,7 +179,7 @@ __device__ __forceinline__ void mixpipe_prologue(const ChainArgs &a) {
 struct ColdArgs {
     float *mixpart;
     unsigned nframes, mix_stride, wave_base, n_launch;
-    int xcd_remap;
+    int xcd_remap, walk_rev;
     float mt_div;
     int mix_per_wave;
     unsigned *mt_tickets;
@@ -194,6 +196,7 @@ __device__ __forceinline__ ColdArgs cold_args() {
     c.wave_base = ka->wave_base;
     c.n_launch = ka->n_launch;
     c.xcd_remap = ka->xcd_remap;
+    c.walk_rev = ka->walk_rev;
     c.mt_div = ka->mt_div;
     c.mix_per_wave = ka->mix_per_wave;
     c.mt_tickets = ka->mt_tickets;
@@ -370,7 +373,7 @@ template <> struct NVecT<4> { typedef float type __attribute__((ext_vector_type(
 
 // streams (DSPFX_NT is a mask over them)
 constexpr int S_IN = 1, S_RING_LD = 2, S_RING_ST = 4, S_OUT = 8, S_STATE = 0;
-constexpr bool nt_for(int stream) { return (DSPFX_NT & stream) != 0; }
+constexpr bool nt_for(int stream, int mask = DSPFX_NT) { return (mask & stream) != 0; }
 
 // Every pointer the kernels dereference is hipMalloc'ed device memory: the explicit global address space
 // turns loads through pointers that were themselves loaded (delay-ring group table) from FLAT into GLOBAL
@@ -752,10 +755,11 @@ constexpr int BUF_AUX_NT = 2;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const float *base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7fffffff, 0x00020000);
 }
-template <int CPL, int STREAM>
+// NTM: the stream mask of this access (DSPFX_NT, or DSPFX_NT without the stream for rows that are to stay in the last-level cache)
+template <int CPL, int STREAM, int NTM = DSPFX_NT>
 __device__ __forceinline__ void load_row(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float (&v)[CPL]) {
     static_assert(CPL == 1 || CPL == 2 || CPL == 4, "one, two or four channels per lane");
-    constexpr int aux = nt_for(STREAM) ? BUF_AUX_NT : 0;
+    constexpr int aux = nt_for(STREAM, NTM) ? BUF_AUX_NT : 0;
     if constexpr (CPL == 1) {
         v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, aux));
     } else if constexpr (CPL == 2) {
@@ -770,9 +774,9 @@ __device__ __forceinline__ void load_row(__amdgpu_buffer_rsrc_t r, unsigned voff
         v[3] = __uint_as_float(t.w);
     }
 }
-template <int CPL, int STREAM>
+template <int CPL, int STREAM, int NTM = DSPFX_NT>
 __device__ __forceinline__ void store_row(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const float (&v)[CPL]) {
-    constexpr int aux = nt_for(STREAM) ? BUF_AUX_NT : 0;
+    constexpr int aux = nt_for(STREAM, NTM) ? BUF_AUX_NT : 0;
     if constexpr (CPL == 1) {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), r, (int)voff, (int)soff, aux);
     } else if constexpr (CPL == 2) {
@@ -1350,11 +1354,25 @@ __device__ __forceinline__ bool mixbus_lane_writes(int lane) {
 // onto few of that XCD's L2 channels (measured: TCP_TCR_TCP_STALL_CYCLES x6.4 and +18 % kernel time for
 // unlucky physical placements, profiles/r01_placement.txt).  Remapped, XCD x owns blocks
 // [x*nb/8, (x+1)*nb/8): neighbouring workgroups of an XCD touch neighbouring 128 KiB tiles.
-// Placement only affects speed, never results (every block index is still covered exactly once).
-__device__ __forceinline__ unsigned work_block(int remap) {
+// rev (ChainArgs::walk_rev) mirrors the walk: the engine flips it from one whole-range launch to the next, so the tiles a launch
+// finishes with are the ones the next launch starts with, and their output lines and state rows are still in the 256 MiB
+// last-level cache when they are touched again (profiles/llc_reuse.txt).  Remapped, the mirror stays inside each XCD's eighth.
+// Placement and direction only affect speed, never results (every block index is still covered exactly once).
+__device__ __forceinline__ unsigned work_block(int remap, int rev) {
     const unsigned b = blockIdx.x, nb = gridDim.x;
-    if (!remap || (nb & 7u)) return b;
-    return (b & 7u) * (nb >> 3) + (b >> 3);
+    if (!remap || (nb & 7u)) return rev ? nb - 1u - b : b;
+    const unsigned per = nb >> 3, i = b >> 3;
+    return (b & 7u) * per + (rev ? per - 1u - i : i);
+}
+
+// Under the alternating walk the output rows a launch writes LAST are the ones the next launch rewrites FIRST.  Stores with the
+// nontemporal hint do not allocate in the last-level cache, default-policy stores do, and a rewrite of a line that is still
+// there saves one of the two trips to HBM (profiles/llc_reuse.txt).  But default-policy stores on ALL output rows cost more than
+// the hits at the two ends give back (they displace each other long before the next launch comes round).  So only the
+// workgroups at the two ends of the launch -- dispatch order, i.e. blockIdx, whichever direction the tiles are walked in --
+// take the hint off their output stores: the first `zone` rewrite what is resident, the last `zone` leave it there.
+__device__ __forceinline__ bool walk_cached_out(unsigned zone) {
+    return blockIdx.x < zone || blockIdx.x + zone >= gridDim.x;
 }
 
 // ---- the fused chain kernel, statically specialised ---------------------------------
@@ -1436,7 +1454,7 @@ __device__ __forceinline__ void mixbus_after_chunk(const ChainArgs &hot, MixStag
     if (end % MIX_SEG != 0 && end != hot.nframes) return;
     const ColdArgs a = cold_args();
     const unsigned len = end % MIX_SEG ? end % MIX_SEG : MIX_SEG;
-    const unsigned wb = blockDim.x == WG ? work_block(a.xcd_remap) : blockIdx.x;   // guarded tail launches use 64-lane blocks
+    const unsigned wb = blockDim.x == WG ? work_block(a.xcd_remap, a.walk_rev) : blockIdx.x;   // guarded tail launches use 64-lane blocks
     const int nw = mixbus_live_waves<CPL>(a, (size_t)wb * blockDim.x * CPL, (int)(blockDim.x / 64));
     const bool per_wave = a.mix_per_wave && blockDim.x == WG;
     mixbus_flush(a, ms, end - len, len, a.wave_base + (per_wave ? wb * (WG / 64) : wb), nw, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, per_wave);
@@ -1451,7 +1469,7 @@ __device__ __forceinline__ void mix_tail_rows(unsigned wb, int wave, int lane) {
 
 template <int F, int CPL, class SL, bool MOD = false>
 __device__ __forceinline__ void chain_chunk(const ChainArgs &a, float (&st)[MAX_SLOTS][4][CPL], size_t c, const WaveAddr &w,
-                                            unsigned f0, int lane, MixStage &ms, int wave) {
+                                            unsigned f0, int lane, MixStage &ms, int wave, bool out_cached) {
     float v[F][CPL];
 #pragma unroll
     for (int f = 0; f < F; ++f) load_row<CPL, S_IN>(row_rsrc(a.in + w.io_base0 + (size_t)f0 * a.ld), w.io_off, (unsigned)f * (a.ld * 4u), v[f]);
@@ -1470,9 +1488,16 @@ __device__ __forceinline__ void chain_chunk(const ChainArgs &a, float (&st)[MAX_
     }
     DSPFX_FOR_SLOTS(DSPFX_RUN)
 #undef DSPFX_RUN
+    if (!a.skip_store) {
+        const __amdgpu_buffer_rsrc_t r_out = row_rsrc(a.out + w.io_base0 + (size_t)f0 * a.ld);
+        if (out_cached) {           // (workgroup-uniform: walk_cached_out)
 #pragma unroll
-    for (int f = 0; f < F; ++f)
-        if (!a.skip_store) store_row<CPL, S_OUT>(row_rsrc(a.out + w.io_base0 + (size_t)f0 * a.ld), w.io_off, (unsigned)f * (a.ld * 4u), v[f]);
+            for (int f = 0; f < F; ++f) store_row<CPL, S_OUT, DSPFX_NT & ~S_OUT>(r_out, w.io_off, (unsigned)f * (a.ld * 4u), v[f]);
+        } else {
+#pragma unroll
+            for (int f = 0; f < F; ++f) store_row<CPL, S_OUT>(r_out, w.io_off, (unsigned)f * (a.ld * 4u), v[f]);
+        }
+    }
     if (a.mixpart) mixbus_partial<F, CPL>(ms, v, true, f0, lane, wave);
 }
 
@@ -1503,7 +1528,7 @@ __global__ void __launch_bounds__(WG) chain_kernel(const ChainArgs a) {
     DSPFX_WG_IN
     __shared__ MixStage ms;
     if (a.mp_stage) mixpipe_prologue(a);
-    const unsigned wb = work_block(a.xcd_remap);
+    const unsigned wb = work_block(a.xcd_remap, a.walk_rev);
     const unsigned tid = wb * WG + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t rel = (size_t)tid * CPL;
@@ -1514,14 +1539,15 @@ __global__ void __launch_bounds__(WG) chain_kernel(const ChainArgs a) {
     DSPFX_FOR_SLOTS(DSPFX_LD)
 #undef DSPFX_LD
     const WaveAddr w = wave_addr(a, c);
+    const bool out_cached = walk_cached_out(a.walk_zone);
     unsigned f0 = 0;
     for (; f0 + F <= a.nframes; f0 += F) {
-        chain_chunk<F, CPL, SL, MOD>(a, st, c, w, f0, lane, ms, wave);
+        chain_chunk<F, CPL, SL, MOD>(a, st, c, w, f0, lane, ms, wave, out_cached);
         if (a.mixpart) mixbus_after_chunk<F, CPL>(a, ms, f0);
     }
     if constexpr (F > 1)
         for (; f0 < a.nframes; ++f0) {
-            chain_chunk<1, CPL, SL, MOD>(a, st, c, w, f0, lane, ms, wave);
+            chain_chunk<1, CPL, SL, MOD>(a, st, c, w, f0, lane, ms, wave, out_cached);
             if (a.mixpart) mixbus_after_chunk<1, CPL>(a, ms, f0);
         }
 #define DSPFX_ST(I)                                                                              \
@@ -1530,7 +1556,7 @@ __global__ void __launch_bounds__(WG) chain_kernel(const ChainArgs a) {
     DSPFX_FOR_SLOTS(DSPFX_ST)
 #undef DSPFX_ST
     DSPFX_WG_OUT(wb, wave)
-    if (a.mt_tickets) mix_tail_rows(work_block(a.xcd_remap), wave, lane);
+    if (a.mt_tickets) mix_tail_rows(work_block(a.xcd_remap, a.walk_rev), wave, lane);
 }
 
 // ---- the fused chain kernel, time-sliced: few channels ------------------------------------------------
@@ -1679,7 +1705,7 @@ __global__ void __launch_bounds__(WG) chain_ts_kernel(const ChainArgs a) {
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // time slice of this wave
     // (Rotating the slices over the waves per workgroup -- so that co-resident workgroups take their turns on different
     // SIMDs -- changes nothing: profiles/r02_small_n.txt.)
-    const unsigned group = work_block(a.xcd_remap);                        // channel group of 64*CPL channels
+    const unsigned group = work_block(a.xcd_remap, a.walk_rev);                        // channel group of 64*CPL channels
     const unsigned wave_global = a.wave_base + group;
     const size_t rel = ((size_t)group * 64 + lane) * CPL;
     bool active = true;
@@ -1765,7 +1791,7 @@ __global__ void __launch_bounds__(WG) chain_dyn_kernel(const ChainArgs a) {
     extern __shared__ float lds[];
     __shared__ MixStage ms;
     if (a.mp_stage) mixpipe_prologue(a);
-    const unsigned wb = blockDim.x == WG ? work_block(a.xcd_remap) : blockIdx.x;   // tail launches use 64-lane blocks
+    const unsigned wb = blockDim.x == WG ? work_block(a.xcd_remap, a.walk_rev) : blockIdx.x;   // tail launches use 64-lane blocks
     const unsigned tid = wb * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t rel = (size_t)tid * CPL;

@@ -329,6 +329,7 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
     // DSPFX_XCD_REMAP=0 / 1 switches the XCD-contiguous block mapping off / on (A/B runs; EnvSwitches)
     const bool xcd_env = e->env.xcd_remap >= 0;
     a.xcd_remap = xcd_env ? e->env.xcd_remap : 1;
+    a.walk_rev = c.walk_rev ? 1 : 0;
     a.n_slots = st.count;
     a.skip_store = (st.count == 0 && src == c.out) ? 1 : 0;   // an empty stage in place exists only for the mix bus
     // hop flag of the side input and of control links (both are ordinary links between nodes);
@@ -353,6 +354,9 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
         // tiled, 24.2 -> 23.7 frame-major (profiles/r03_small_n.txt).  The large kernels keep the contiguous mapping.
         if (!xcd_env) a.xcd_remap = 0;
     }
+    // The time-sliced kernels keep the forward walk: every stream of theirs carries the hint, so nothing of one launch is left in
+    // the last-level cache for the next, and mirrored they ran 0.5-1.5 % slower at 16384 ... 65536 channels (profiles/llc_reuse.txt).
+    if (v->ts) a.walk_rev = 0;
     const uint32_t per_wave = 64u * v->cpl;
     // A few-channel engine (the time-sliced kernel is its main launch) whose N is not whole waves: two launches in a
     // row would both be latency-bound (11 + 11 us), so the guarded time-sliced kernel takes ALL channels in one
@@ -411,6 +415,13 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
         a.c_base = w0;
         a.n_launch = w1 - w0;
         a.wave_base = (v->ts || rows_per_wave) ? w0 / per_wave : w0 / (per_wave * (WG / 64));   // rows of the windows before this one
+        // workgroups at each end whose output rows stay in the last-level cache (walk_cached_out): the standard kernels at two
+        // or more channels per lane -- the large engines.  One channel per lane and the time-sliced kernels (few channels) ran
+        // 1.5-6 % slower with their sample block on the default policy (profiles/llc_reuse.txt) and keep the hint everywhere.
+        if (c.walk_alt && !v->ts && v->cpl >= 2) {
+            const uint64_t wg_bytes = (uint64_t)WG * v->cpl * nframes * sizeof(float);
+            a.walk_zone = (unsigned)std::min<uint64_t>(((uint64_t)walk_zone_mib(e) << 20) / wg_bytes, 0x7fffffffu);
+        }
         ProfScope ps(e, si, stream);
         if (launch_variant(v, a, v->ts ? (w1 - w0) / per_wave : ((w1 - w0) / v->cpl + WG - 1) / WG, WG, (unsigned)(rows * WG * v->cpl * sizeof(float)), stream)) {
             if (tail_bus) (void)hipMemsetAsync(e->mt_tickets, 0, (MIX_SLICES + 1) * sizeof(unsigned), stream);
@@ -418,6 +429,7 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
         }
     }
     a.mp_stage = 0;   // the guarded tail launch never hosts the prologue
+    a.walk_zone = 0;
     if ((N % per_wave || whole_guard) && (!c.window_n || c.window_c0 + c.window_n >= N)) {   // ragged tail: guarded one-wave blocks, lane per channel
         const uint32_t n_tail = N - n_main;
         a.c_base = n_main;
@@ -425,6 +437,7 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
         a.wave_base = rows_main;
         if (st.var_ts_tail && tail == e->tail && nframes == 4u * (uint32_t)st.var_ts_tail->ts) {
             a.xcd_remap = 0;            // whole 128-frame blocks: four slices per 64 channels (pick_ts_tail_variant)
+            a.walk_rev = 0;             // (time-sliced: forward, see above)
             if (whole_guard) {          // the stage's only launch: it is the one dspfx_profile_read reports
                 ProfScope ps(e, si, stream);
                 (void)launch_variant(st.var_ts_tail, a, (n_tail + 63) / 64, WG, 0, stream);
@@ -1413,9 +1426,13 @@ static int process_block(dspfx_engine *e, const BlockCall &c, bool pieces = fals
         if (const uint32_t tsb = ts_sub_block(e, c))
             if (pn > tsb && pn % tsb == 0 && sub >= tsb && sub % tsb == 0) sub = tsb;
         for (uint32_t f0 = p0; f0 < p0 + pn; f0 += sub) {
-            const BlockCall s = sub_block(e, c, f0, std::min(sub, p0 + pn - f0));
+            BlockCall s = sub_block(e, c, f0, std::min(sub, p0 + pn - f0));
+            const bool alternate = walk_alternates(e) && !s.window_n;
+            s.walk_alt = alternate;
+            s.walk_rev = alternate && (e->walk_parity & 1u);
             if (const int rc = run_subblock(e, s)) return rc;
             e->frames_submitted += s.n_frames;
+            if (alternate) e->walk_parity ^= 1u;
         }
     }
     return DSPFX_OK;

@@ -112,6 +112,8 @@ struct Pref {
 // moment, and the calls are not free (tests/test_abi_cpu.py greps for it).  -1 = not set.
 struct EnvSwitches {
     int xcd_remap = -1;          // DSPFX_XCD_REMAP
+    int walk = -1;               // DSPFX_WALK (0: every launch walks its tiles front to back; 1: consecutive whole-range launches alternate)
+    int walk_zone_mib = -1;      // DSPFX_WALK_ZONE_MIB (output rows at each end of an alternating launch that stay in the last-level cache; unset: WALK_ZONE_MIB)
     int mix_tail = -1;           // DSPFX_MIX_TAIL (0: stand-alone bus kernels)
     int fast_div = -1;           // DSPFX_FAST_DIV (0: IEEE division everywhere)
     int jit = -1, jit_async = -1;   // DSPFX_JIT, DSPFX_JIT_ASYNC
@@ -171,6 +173,10 @@ struct BlockCall {
     // finishes the block (ring positions advance, sliders latch: once)
     uint32_t window_c0 = 0, window_n = 0;
     bool window_last = true;
+    // this (sub-)block's launches walk their tiles back to front (ChainArgs::walk_rev): set by process_block from the engine's
+    // walk parity for launches over the whole channel range; channel windows and the placement probe keep the forward walk
+    bool walk_rev = false;
+    bool walk_alt = false;            // ... and alternate at all: the launches' two ends keep their output rows in the last-level cache
 
     BlockCall(const float *in_, const float *side_, float *out_, float *mix_, uint32_t n_frames_, hipStream_t s)
         : in(in_), side(side_), out(out_), mix(mix_), n_frames(n_frames_), tile_frames(n_frames_), stream(s) {}
@@ -244,6 +250,9 @@ struct dspfx_engine {
     std::deque<dspfx_param_event> log;        // the stores already applied, oldest first (bounded)
     uint64_t next_seq = 1;
     uint64_t frames_submitted = 0;            // frames handed to the process calls so far
+    // direction of the next whole-range launch's tile walk (bit 0), advanced under api_mu with frames_submitted.  Only speed
+    // depends on it, so dspfx_reset, placement tuning and a state import leave it as it is.
+    uint32_t walk_parity = 0;
     // the stream the DSP state was last touched on: every state write (biquad reset, dspfx_reset, ...) is queued on
     // it, and a call on a different stream first waits for an event recorded there
     hipStream_t cur_stream = nullptr;
@@ -338,6 +347,14 @@ bool stage_fast_div(const dspfx_engine *e, const Stage &st, bool have_device = t
 bool fusable(const Node &n);
 int node_hop(const dspfx_engine *e, int idx);
 inline const Pref &read_pref(const dspfx_engine *e) { return e->env.pref; }
+// Do consecutive whole-range launches walk their tiles in opposite directions?  DSPFX_WALK=0 / 1 decides (A/B runs); unset: yes
+// (profiles/llc_reuse.txt).
+constexpr bool WALK_ALTERNATES_DEFAULT = true;
+inline bool walk_alternates(const dspfx_engine *e) { return e->env.walk >= 0 ? e->env.walk != 0 : WALK_ALTERNATES_DEFAULT; }
+// MiB of output rows at each end of an alternating launch that are stored on the default cache policy (chain_kernels.hip.h,
+// walk_cached_out).  From the sweep in profiles/llc_reuse.txt.
+constexpr uint32_t WALK_ZONE_MIB = 96;
+inline uint32_t walk_zone_mib(const dspfx_engine *e) { return e->env.walk_zone_mib >= 0 ? (uint32_t)e->env.walk_zone_mib : WALK_ZONE_MIB; }
 void async_jit_submit(const std::shared_ptr<AsyncJit> &job);   // jit.hip: background specialisation for small engines
 bool async_jit_wait(const std::shared_ptr<AsyncJit> &job, int wait_ms);   // ... until the compiler is done with `job` (bounded)
 int validate_node(dspfx_engine *e, const dspfx_node_desc &d);

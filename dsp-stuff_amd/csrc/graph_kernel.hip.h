@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(WG) graph_kernel(const GraphArgs g) {
     const ChainArgs &a = g.c;
     __shared__ MixStage ms;
     if (a.mp_stage) mixpipe_prologue(a);
-    const unsigned wb = work_block(a.xcd_remap);
+    const unsigned wb = work_block(a.xcd_remap, a.walk_rev);
     const unsigned tid = wb * WG + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t rel = (size_t)tid * CPL;

@@ -315,6 +315,13 @@ extern "C" int dspfx_describe(const dspfx_engine *e, char *dst, size_t cap) {
                     s += buf;
                 }
         }
+    if (walk_alternates(e)) {
+        snprintf(buf, sizeof buf, "tile walk: consecutive launches over all channels alternate front-to-back / back-to-front; "
+                                  "standard kernels at two or more channels per lane keep %u MiB of output rows at each end of a launch in the last-level cache\n", walk_zone_mib(e));
+        s += buf;
+    } else {
+        s += "tile walk: every launch front to back\n";
+    }
     {
         const std::string &cdir = e->env.cache_dir;
         snprintf(buf, sizeof buf, "run-time kernels of this process: %llu compiled, %llu loaded from the disk cache, %llu written to it (%s)\n",
