@@ -98,7 +98,7 @@ EXPORTS = [
     "dspfx_envelope_gain", "dspfx_talkers_plan", "dspfx_talkers_select", "dspfx_talkers_create", "dspfx_talkers_destroy",
     "dspfx_talkers_last_error", "dspfx_talkers_run", "dspfx_talkers_assign", "dspfx_talkers_set_detector", "dspfx_talkers_set_pin",
     "dspfx_talkers_set_top", "dspfx_talkers_set_floor", "dspfx_talkers_reset", "dspfx_talkers_views", "dspfx_talkers_room_of",
-    "dspfx_talkers_counts",
+    "dspfx_talkers_counts", "dspfx_talkers_audible", "dspfx_talkers_audible_views", "dspfx_mixmatrix_run_sparse",
 ]
 COMM_ID_BYTES = 128
 
@@ -398,6 +398,9 @@ def lib():
     L.dspfx_talkers_views.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.dspfx_talkers_room_of.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_talkers_counts.argtypes = [vp, u32p]
+    L.dspfx_talkers_audible.argtypes = [fp, fp, u32p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32), u32p, u32p]
+    L.dspfx_talkers_audible_views.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
 
@@ -1701,7 +1704,7 @@ def envelope_gain(frames: float) -> np.float32:
 
 def talkers_plan(channels: int, groups: int) -> int:
     """dspfx_talkers_plan, a pure host function (no GPU): the device bytes of a Talkers bank's tables, 29 per channel and 69 per
-    room plus 4."""
+    room plus 4 (a bank that hands out Talkers.audible() holds 4 per channel and 4 per room more)."""
     L = lib()
     n = C.c_uint64()
     rc = L.dspfx_talkers_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, int(groups) & 0xFFFFFFFF, C.byref(n))
@@ -1740,6 +1743,27 @@ def talkers_select(levels, room_of, groups: int, top=3, floor: float = 0.0, pins
     return talk, tl, tg
 
 
+def talkers_audible(gate, target, room_of, groups: int):
+    """dspfx_talkers_audible, a pure host function (no GPU): which members of each room can be non-zero in the block a gated run
+    is about to gate.  gate, target float32[N] as that run finds them, room_of [N] (a room in [0, groups) or NO_ROOM) ->
+    (list int32[N], start uint32[groups + 1], count uint32[groups]): a channel is audible iff its gate or its target is not
+    +-0.0, and room r's audible members, in ascending channel order, are list[start[r] : start[r] + count[r]] (the entries of a
+    segment past its count, and those past start[groups], are unspecified).  What Talkers.audible() holds on the device."""
+    L = lib()
+    g = np.ascontiguousarray(gate, np.float32).reshape(-1)
+    t = np.ascontiguousarray(target, np.float32).reshape(-1)
+    ro = _room_ids(room_of)
+    if not len(g) == len(t) == len(ro):
+        raise DspfxError(-1, "talkers audible: gate, target and room_of name different numbers of channels")
+    G = max(int(groups), 0)
+    lst, start, count = np.full(len(g), -1, np.int32), np.zeros(G + 1, np.uint32), np.zeros(G, np.uint32)
+    fp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    rc = L.dspfx_talkers_audible(g.ctypes.data_as(fp), t.ctypes.data_as(fp), ro.ctypes.data_as(u32p), len(g), G,
+                                 lst.ctypes.data_as(C.POINTER(C.c_int32)), start.ctypes.data_as(u32p), count.ctypes.data_as(u32p))
+    _raise(L, "talkers", rc)
+    return lst, start, count
+
+
 class Talkers(_Bank):
     """Per-channel levels and each room's loudest, gated live (include/dspfx.h, dspfx_talkers_*): every channel has its own Envelope
     node (attack and release in frames, `set_detector`), every room -- group_start / group_size as MixGroups takes them, 1 .. 1024
@@ -1764,6 +1788,7 @@ class Talkers(_Bank):
         ptrs = [C.c_void_p() for _ in range(4)]
         self._chk(self.L.dspfx_talkers_views(self.h, *[C.byref(p) for p in ptrs]))
         self._views = [p.value for p in ptrs]
+        self._audible = None                              # the three device addresses of audible(), once it has been asked for
 
     def run(self, block, n_frames: Optional[int] = None, out=None, gate: bool = True, stream: int = 0):
         """One device block: gate it with the targets of the run before -> `out`, a device block in the same layout (made when not
@@ -1851,9 +1876,22 @@ class Talkers(_Bank):
         self._chk(self.L.dspfx_talkers_counts(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32))))
         return v
 
-    def _view(self, which, shape, typestr):
+    def audible(self):
+        """(list int32[channels], start uint32[groups + 1], count uint32[groups]) on the device: room r's audible members -- those
+        whose gate or target was not +-0.0 when the last gated run began, the only ones that can be non-zero in the block it
+        gated -- in ascending channel order, are list[start[r] : start[r] + count[r]].  The first call allocates the tables and
+        switches the bank on: every gated run submitted after it also writes them (one more kernel, ahead of the gate).  Valid
+        after a gated run, on its stream; a metering run leaves them.  What MixMatrix.run(sources=...) takes."""
+        if self._audible is None:
+            ptrs = [C.c_void_p() for _ in range(3)]
+            self._chk(self.L.dspfx_talkers_audible_views(self.h, *[C.byref(p) for p in ptrs]))
+            self._audible = [p.value for p in ptrs]
+        lst, start, count = self._audible
+        return (self._view(lst, (self.channels,), "<i4"), self._view(start, (self.groups + 1,), "<u4"),
+                self._view(count, (self.groups,), "<u4"))
+
+    def _view(self, addr, shape, typestr):
         import torch
-        addr = self._views[which]
 
         class _Mem:
             __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (addr, False), "version": 2}
@@ -1861,19 +1899,19 @@ class Talkers(_Bank):
 
     def levels(self):
         """float32[channels] on the device: every channel's largest envelope of the last block (valid after a run, on its stream)."""
-        return self._view(0, (self.channels,), "<f4")
+        return self._view(self._views[0], (self.channels,), "<f4")
 
     def targets(self):
         """float32[channels] on the device: 1.0 where the next gated run passes the channel, 0.0 where it ramps it out."""
-        return self._view(1, (self.channels,), "<f4")
+        return self._view(self._views[1], (self.channels,), "<f4")
 
     def talkers(self):
         """int32[groups, 8] on the device: every room's talkers, loudest first, -1 where there is none."""
-        return self._view(2, (self.groups, TALKERS_MAX_TOP), "<i4")
+        return self._view(self._views[2], (self.groups, TALKERS_MAX_TOP), "<i4")
 
     def talker_levels(self):
         """float32[groups, 8] on the device: the talkers' levels, 0.0 where there is none."""
-        return self._view(3, (self.groups, TALKERS_MAX_TOP), "<f4")
+        return self._view(self._views[3], (self.groups, TALKERS_MAX_TOP), "<f4")
 
 
 
@@ -2065,16 +2103,29 @@ class MixMatrix(_Bank):
             raise DspfxError(-1, "listeners, sources and gains are equally long")
         self._chk(self.L.dspfx_mixmatrix_set_pairs(self.h, l.ctypes.data_as(u32), s.ctypes.data_as(u32), g.ctypes.data_as(C.POINTER(C.c_float)), len(l)))
 
-    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0, sources=None):
         """One device block through every room's matrix -> `out`, a device block in the same layout (made when not given).
         `out` may not overlap `block`: every listener reads every source of its room, so there is no in-place form -- except in
-        MIXMATRIX_STAGED, where `out` may be `block` itself."""
+        MIXMATRIX_STAGED, where `out` may be `block` itself.
+        sources=(list, start, count), device tensors (int32 channel numbers, uint32[G + 1], uint32[G]; Talkers.audible() gives them):
+        the SPARSE run (dspfx_mixmatrix_run_sparse): room r adds only the sources named in list[start[r] : start[r] + count[r]],
+        in ascending room-local order, and reads no other.  Where every unlisted source carries +-0.0 it is the dense run bit for
+        bit.  Entries that are negative, past the channels or of another room are ignored; the list's producer and this run
+        share a stream."""
         import torch
         if n_frames is None:
             n_frames = block.numel() // self.channels
         if out is None:
             out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_mixmatrix_run(self.h, _ptr(block), int(n_frames), _ptr(out), C.c_void_p(stream) if stream else None))
+        s = C.c_void_p(stream) if stream else None
+        if sources is None:
+            self._chk(self.L.dspfx_mixmatrix_run(self.h, _ptr(block), int(n_frames), _ptr(out), s))
+            return out
+        lst, start, count = sources
+        if start.numel() != self.groups + 1 or count.numel() != self.groups or any(t.element_size() != 4 or t.is_floating_point() for t in sources):
+            raise DspfxError(-1, "mixmatrix run: sources is (list, start[groups + 1], count[groups]) of 32-bit integers")
+        self._chk(self.L.dspfx_mixmatrix_run_sparse(self.h, _ptr(block), int(n_frames), _ptr(out), _ptr(lst), int(lst.numel()), _ptr(start),
+                                                    _ptr(count), s))
         return out
 
     def _lines(self, fn, values, first_channel, count):

@@ -301,6 +301,223 @@ __global__ __launch_bounds__(WG, 3) void mixmatrix_run(RunArgs a) {
     }
 }
 
+// ---- the sparse run (dspfx_mixmatrix_run_sparse) ----------------------------------------------------------------------------------
+// The same chain over a LISTED set of sources per room: A_r = the room-local indices held by the channels of
+// list[start[r] .. start[r] + min(count[r], MAXN)), e.g. the talker bank's audible list.  A source outside A_r is not read.
+//
+// Why the bits are the dense run's when every unlisted source carries +-0.0 and the room's table is finite.  The dense chain of a
+// listener is acc = fmaf(x[s], Mt[s][l], acc) over ascending s from acc = +0.0.  (1) fmaf(m, +-0.0, acc) == acc for finite m unless
+// acc is -0.0: the product is an exact zero and adding a zero of either sign changes neither a non-zero acc nor +0.0.  (2) The
+// chain starts at +0.0.  (3) An exact cancellation gives +0.0 under round-to-nearest.  So acc is never -0.0 -- unless a non-zero
+// product has underflowed to -0.0 on the way, the one excepted case, which can change the sign of a zero result -- every unlisted
+// step is the identity, and what is left is the chain over the listed sources in ascending order: this kernel's.  With everybody
+// listed it is the dense chain on any block.  The MFMA places listed source number k at k step k instead of s; the chain does not
+// care where a term sits, only in which order the terms come.
+//
+//   1. a 1024-bit mask in LDS: the threads stride over the room's segment of the list and set the bit of every entry that names a
+//      channel of this room (LDS atomicOr: order-free, so deterministic; duplicates count once, any order of the list gives the
+//      same set).  An entry that is negative, >= N, past list_len or of another room sets nothing.
+//   2. one wave turns the mask into idx[K], ascending, by a popcount prefix over its 32 words.
+//   3. the dense kernel's chunk loop over the K listed sources: x[f][chan(idx[k])] into the same [frame][source] LDS image,
+//      the B operand of a k step from rows Mt[idx[k]] (32 adjacent listeners: one coalesced load), K padded up to the k step with
+//      +0.0 * +0.0 terms that are not loaded, the k loop of the last chunk trimmed to ceil(K / 2) steps.  The same epilogue.
+// STAGED here means the epilogue only: the few listed sources are read straight from the block (no mixmatrix_stage_in), the result
+// goes to the seat-ordered sout rows along frames, and mixmatrix_stage_out carries it to out in whole lines.
+struct SparseArgs {
+    RunArgs r;
+    const int32_t *__restrict__ list;            // device: channel numbers
+    const uint32_t *__restrict__ start;          // device, [G + 1]
+    const uint32_t *__restrict__ count;          // device, [G]
+    uint64_t list_len;
+    const uint32_t *__restrict__ room_of;        // a seated bank's: the channel's room, and its entry of seat_chan
+    const uint32_t *__restrict__ slot_of;
+};
+
+template <bool SEATED, bool STAGED = false>
+__global__ __launch_bounds__(WG, 3) void mixmatrix_run_sparse(SparseArgs sa) {
+    static_assert(SEATED || !STAGED, "only a seated bank has a staged run");
+    const RunArgs &a = sa.r;
+    __shared__ float xs[FT * XS];                        // [frame][listed source of the chunk]
+    __shared__ uint32_t idx[MAXN];                       // the listed indices, ascending
+    __shared__ uint32_t mask[MAXN / 32];
+    __shared__ uint32_t listed;                          // K
+    const Item it = a.items[blockIdx.x];
+    const Room rm = a.rooms[it.room];
+    const uint32_t n = rm.n, P = SEATED ? n : edge(n), c0 = rm.c0;
+    const uint32_t *sc = a.seat_chan + c0;               // (SEATED)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t r = lane & 31u, h = lane >> 5;        // MFMA operand maps: A[i = r][k = h], B[k = h][j = r]
+    const uint32_t lt = it.l0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) * 32u;     // the wave's listener tile (uniform)
+    const bool active = lt < P;                          // wave-uniform; an idle wave still stages its share of x
+    const uint32_t ss = tid & 31u, sf = tid >> 5;        // staging: listed source ss of the chunk, frames sf + 8 i
+    const size_t rs = a.W ? a.W : a.N;                   // a frame further is rs elements on in either layout
+    const uint32_t f0 = blockIdx.y * FT;
+
+    // 1. the mask
+    if (tid < MAXN / 32) mask[tid] = 0u;
+    __syncthreads();
+    {
+        const uint64_t s0 = sa.start[it.room];
+        const uint32_t cnt = min(sa.count[it.room], MAXN);
+        for (uint32_t i = tid; i < cnt; i += WG) {
+            const uint64_t e = s0 + i;
+            if (e >= sa.list_len) break;
+            const int32_t c = sa.list[e];
+            if (c < 0 || (uint32_t)c >= a.N) continue;
+            uint32_t l;
+            if constexpr (SEATED) {
+                if (sa.room_of[c] != it.room) continue;
+                l = sa.slot_of[c] - c0;                  // the channel's seat (its entry of seat_chan, less the room's first)
+            } else {
+                l = (uint32_t)c - c0;
+            }
+            if (l < n) atomicOr(&mask[l >> 5], 1u << (l & 31u));
+        }
+    }
+    __syncthreads();
+    // 2. the list: lane w < 32 of wave 0 owns word w, and writes its bits behind those of the words below
+    if (wave == 0) {
+        uint32_t w = lane < MAXN / 32 ? mask[lane] : 0u;
+        uint32_t incl = (uint32_t)__popc(w);
+#pragma unroll
+        for (uint32_t q = 0; q < 5; ++q) {
+            const uint32_t o = (uint32_t)__shfl_up((int)incl, 1u << q);
+            if (lane >= (1u << q)) incl += o;
+        }
+        uint32_t at = incl - (uint32_t)__popc(w);
+        while (w) {
+            idx[at++] = lane * 32u + (uint32_t)__ffs((int)w) - 1u;       // (at < K <= n <= MAXN)
+            w &= w - 1u;
+        }
+        if (lane == 31) listed = incl;
+    }
+    __syncthreads();
+    const uint32_t K = listed;
+
+    // 3. the chain over the K listed sources
+    f32x16 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    float st[16], bn[KC / 2];
+    const uint32_t left = a.nf - f0, nst = left > sf ? (left - sf + 7u) / 8u : 0u;
+    const float *tabr = a.tab + rm.off;                  // uniform; the table has P * P <= 2^20 elements: 32-bit offsets
+    const uint32_t bcol = active ? lt + r : 0u;
+    // the chunk from listed source k0 into registers: a position past K is a +0.0 * +0.0 term and is not read
+    auto gload = [&](uint32_t k0) {
+        bool held = k0 + ss < K;
+        const uint32_t s = held ? idx[k0 + ss] : 0u;
+        uint32_t ch;                                     // the channel whose samples p walks; nobody's: any valid one, unread
+        if constexpr (SEATED) {
+            ch = sc[s];
+            held = held && ch != NONE;
+            if (!held) ch = 0u;
+        } else {
+            ch = c0 + s;                                 // (s < n)
+        }
+        const float *p = a.in + lay(0, ch, a.nf, a.N, a.W) + (size_t)(f0 + sf) * rs;
+        const uint32_t cnt = held ? nst : 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) {
+            st[i] = i < cnt ? *p : 0.0f;
+            p += 8u * rs;
+        }
+        if (active) {
+#pragma unroll
+            for (uint32_t j = 0; j < KC / 2; ++j) {
+                const uint32_t k = k0 + 2u * j + h;
+                bn[j] = k < K ? tabr[idx[k < K ? k : 0u] * P + bcol] : 0.0f;
+            }
+        }
+    };
+    if (K) gload(0);
+#pragma unroll 1
+    for (uint32_t k0 = 0; k0 < K; k0 += KC) {
+        __syncthreads();                                 // the chunk before is read
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) xs[(sf + 8u * i) * XS + ss] = st[i];
+        float b[KC / 2];
+#pragma unroll
+        for (uint32_t j = 0; j < KC / 2; ++j) b[j] = bn[j];
+        __syncthreads();
+        if (k0 + KC < K) gload(k0 + KC);
+        if (active) {
+            const uint32_t steps = (min(K - k0, KC) + 1u) / 2u;          // (uniform) the last chunk: ceil of what is left / 2
+            const float *xr = xs + r * XS + h;
+            float an[4], ac[4];
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t) an[t] = xr[t * 32u * XS];
+#pragma unroll
+            for (uint32_t j = 0; j < KC / 2; ++j) {
+                if (j < steps) {                         // (a uniform branch per step; no break: the loop unrolls, b[j] stays a register)
+#pragma unroll
+                    for (uint32_t t = 0; t < 4; ++t) ac[t] = an[t];
+                    if (j + 1 < KC / 2) {
+#pragma unroll
+                        for (uint32_t t = 0; t < 4; ++t) an[t] = xr[t * 32u * XS + 2u * (j + 1)];
+                    }
+#pragma unroll
+                    for (uint32_t t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[t], b[j], acc[t], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    }
+    // the dense kernel's epilogue.  C/D: column = r (the listener), row = (reg & 3) + 8 (reg >> 2) + 4 h (the frame of the tile)
+    bool heard;
+    uint32_t c;
+    if constexpr (SEATED) {
+        c = active ? sc[lt + r] : NONE;
+        heard = c != NONE;
+    } else {
+        const uint32_t l = lt + r;
+        heard = active && l < n;
+        c = c0 + l;
+    }
+    if (!heard) return;
+    const float d = a.div[c];
+    if constexpr (STAGED) {
+        float *po = a.sout + (size_t)(c0 + lt + r) * a.MF + f0;
+        const bool vec = (a.MF & 3u) == 0u;              // every row starts on 16 bytes (f0 and the tile's rows are multiples of 4)
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t)
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                const uint32_t fb = t * 32u + 8u * q + 4u * h;         // accumulator rows 4 q .. 4 q + 3: frames fb .. fb + 3
+                float v[4];
+#pragma unroll
+                for (uint32_t i = 0; i < 4; ++i) {
+                    v[i] = acc[t][4u * q + i];
+                    if (d == 0.0f) v[i] = 0.0f;
+                    else if (a.normalise) v[i] = __fdiv_rn(v[i], d);
+                }
+                if (vec && f0 + fb + 4u <= a.nf) {
+                    *(f32x4 *)(po + fb) = f32x4{v[0], v[1], v[2], v[3]};
+                } else {
+#pragma unroll
+                    for (uint32_t i = 0; i < 4; ++i)
+                        if (f0 + fb + i < a.nf) po[fb + i] = v[i];
+                }
+            }
+    } else {
+        float *po = a.out + lay(0, c, a.nf, a.N, a.W);
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t)
+#pragma unroll
+            for (uint32_t i = 0; i < 16; ++i) {
+                const uint32_t f = f0 + t * 32u + (i & 3u) + 8u * (i >> 2) + 4u * h;
+                if (f < a.nf) {
+                    float v = acc[t][i];
+                    if (d == 0.0f) v = 0.0f;
+                    else if (a.normalise) v = __fdiv_rn(v, d);
+                    __builtin_nontemporal_store(v, po + (size_t)f * rs);
+                }
+                if ((i & 3u) == 3u) __builtin_amdgcn_sched_barrier(0);   // (four rows' addresses at a time, not sixty-four)
+            }
+    }
+}
+
 // the channels in no room read +0.0 in every frame; launched ahead of a seated bank's mixmatrix_run while the bank has any
 __global__ __launch_bounds__(WG) void mixmatrix_zero_roomless(float *__restrict__ out, const uint32_t *__restrict__ room_of, uint32_t N, uint32_t W, uint32_t nf) {
     const uint32_t c = blockIdx.x * WG + threadIdx.x;
@@ -1281,24 +1498,25 @@ extern "C" int dspfx_mixmatrix_fill(dspfx_mixmatrix *p, int64_t room, uint32_t p
 
 extern "C" int dspfx_mixmatrix_reset(dspfx_mixmatrix *p) { return dspfx_mixmatrix_fill(p, -1, DSPFX_MIXMATRIX_MIX_MINUS); }
 
-extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint32_t n_frames, float *out, void *stream) {
-    if (!p) return DSPFX_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(p->mu);
-    if (!block || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: block, out or n_frames");
+namespace {
+
+// what the two runs share, under mu: the argument checks (`what`: "run" or "run_sparse"), the stream order, the queued stores onto
+// the stream, and the kernels' arguments.  The mode is read once: a run is wholly one mode, the one of the last set_staging that
+// returned before it
+int begin_run(dspfx_mixmatrix *p, const char *what, const float *block, uint32_t n_frames, float *out, hipStream_t s, bool &staged, RunArgs &a) {
+    const std::string pre = std::string("mixmatrix ") + what + ": ";
+    if (!block || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, (pre + "block, out or n_frames").c_str());
     const uintptr_t bytes = (uintptr_t)p->desc.n_channels * n_frames * sizeof(float), b0 = (uintptr_t)block, o0 = (uintptr_t)out;
-    // (the mode is read once: a run is wholly one mode, the one of the last set_staging that returned before it)
-    const bool staged = p->mode.load(std::memory_order_acquire) == DSPFX_MIXMATRIX_STAGED;
+    staged = p->mode.load(std::memory_order_acquire) == DSPFX_MIXMATRIX_STAGED;
     if (b0 < o0 + bytes && o0 < b0 + bytes) {
         if (!staged)
-            return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block (every listener reads every source of its room: no in-place form)");
-        // staged: stage_in has read the whole block before stage_out writes the first sample, so out == block is in place
-        if (b0 != o0) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run: out overlaps the block in part (a staged run takes out == block, or no overlap)");
+            return p->fail(DSPFX_ERR_INVALID, (pre + "out overlaps the block (every listener reads every source of its room: no in-place form)").c_str());
+        // staged: every read of the block is over before stage_out writes the first sample, so out == block is in place
+        if (b0 != o0) return p->fail(DSPFX_ERR_INVALID, (pre + "out overlaps the block in part (a staged run takes out == block, or no overlap)").c_str());
     }
-    hipStream_t s = (hipStream_t)stream;
     BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
     BANK_HIP_WHY(order(p, s), "stream order");
     BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "matrix store");
-    RunArgs a;
     a.in = block;
     a.out = out;
     a.tab = p->tab;
@@ -1313,7 +1531,55 @@ extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint3
     a.sin = p->sbuf;
     a.sout = p->sbuf ? p->sbuf + (size_t)p->n_slots * p->desc.max_frames : nullptr;
     a.MF = p->desc.max_frames;
-    if (staged) {                                // block -> sin, the chain over the seats, sout -> out: all three behind the stores
+    return DSPFX_OK;
+}
+
+}  // namespace
+
+extern "C" int dspfx_mixmatrix_run_sparse(dspfx_mixmatrix *p, const float *block, uint32_t n_frames, float *out, const int32_t *list, uint64_t list_len,
+                                          const uint32_t *start, const uint32_t *count, void *stream) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!list || !start || !count) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run_sparse: list, start or count");
+    if (list_len > 0xFFFFFFFFull) return p->fail(DSPFX_ERR_INVALID, "mixmatrix run_sparse: list_len is above 2^32 - 1");
+    hipStream_t s = (hipStream_t)stream;
+    bool staged = false;
+    SparseArgs sa;
+    const int rc = begin_run(p, "run_sparse", block, n_frames, out, s, staged, sa.r);
+    if (rc != DSPFX_OK) return rc;
+    sa.list = list;
+    sa.start = start;
+    sa.count = count;
+    sa.list_len = list_len;
+    sa.room_of = p->room_of;
+    sa.slot_of = p->slot_of;
+    const dim3 grid(p->n_items, (n_frames + FT - 1) / FT);
+    if (staged) {                                // the listed sources straight from the block, the seat-ordered result, sout -> out
+        mixmatrix_run_sparse<true, true><<<grid, WG, 0, s>>>(sa);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_run_sparse_staged");
+        mixmatrix_stage_out<<<dim3((sa.r.N + SG - 1) / SG, grid.y), WG, 0, s>>>(sa.r.sout, out, p->slot_of, sa.r.N, sa.r.W, n_frames, sa.r.MF);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_stage_out");
+        return DSPFX_OK;
+    }
+    if (p->roomless) {
+        mixmatrix_zero_roomless<<<(sa.r.N + WG - 1) / WG, WG, 0, s>>>(out, p->room_of, sa.r.N, sa.r.W, n_frames);
+        BANK_HIP_WHY(hipGetLastError(), "mixmatrix_zero_roomless");
+    }
+    const auto kernel = p->seated ? mixmatrix_run_sparse<true> : mixmatrix_run_sparse<false>;
+    kernel<<<grid, WG, 0, s>>>(sa);
+    BANK_HIP_WHY(hipGetLastError(), p->seated ? "mixmatrix_run_sparse_seated" : "mixmatrix_run_sparse");
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_mixmatrix_run(dspfx_mixmatrix *p, const float *block, uint32_t n_frames, float *out, void *stream) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    hipStream_t s = (hipStream_t)stream;
+    bool staged = false;
+    RunArgs a;
+    const int rc = begin_run(p, "run", block, n_frames, out, s, staged, a);
+    if (rc != DSPFX_OK) return rc;
+    if (staged) {                               // block -> sin, the chain over the seats, sout -> out: all three behind the stores
         const dim3 tg((a.N + SG - 1) / SG, (n_frames + FT - 1) / FT);
         mixmatrix_stage_in<<<tg, WG, 0, s>>>(block, p->sbuf, p->slot_of, a.N, a.W, n_frames, a.MF);
         BANK_HIP_WHY(hipGetLastError(), "mixmatrix_stage_in");

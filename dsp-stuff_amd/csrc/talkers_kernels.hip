@@ -18,6 +18,8 @@
 //            ascending; 0 is "no candidate" (a channel number is below 2^32 - 256, so no real key is 0).  `top` rounds: the
 //            lane's own maximum, a 64-lane __shfl_xor maximum, the winner retired.  Lane 0 writes the room's row of the tables
 //            and the winner's target.  No atomics, no LDS, every step in a fixed order.
+// A bank that has handed out its audible list (dspfx_talkers_audible_views) launches a third kernel, talkers_audible, ahead of pass A
+// of every gated run: per room the members that can be non-zero in the block about to be gated, for dspfx_mixmatrix_run_sparse.
 //
 // Stores (sliders, pins, tops, the floor, seatings, resets) go through the staged-store queue (store_queue.hip.h).  A seating is
 // the member list and room_start[G + 1], built on the host from room_of[N] alone.
@@ -221,6 +223,38 @@ __global__ __launch_bounds__(WG) void talkers_pick(const float *__restrict__ lev
     }
 }
 
+// the audible list (dspfx_talkers_audible_views): wave w of the grid takes room w, ahead of pass A, which overwrites `gate`.  A member
+// is audible iff its gate or its target is not +-0.0: only then can gate + (target - gate) * r[f] be non-zero in the block about to be
+// gated.  Member slots are lane + 64 k as in talkers_pick; round k's audible members go behind those of the rounds before, in lane
+// order (a ballot and a count of the lanes below), so a room's segment list[room_start[r] ..] comes out in member order, which is
+// ascending channel order.  A room writes inside its own segment only.  No atomics, no LDS
+__global__ __launch_bounds__(WG) void talkers_audible(const float *__restrict__ gate, const float *__restrict__ target, const uint32_t *__restrict__ members,
+                                                      const uint32_t *__restrict__ room_start, int32_t *__restrict__ list, uint32_t *__restrict__ count,
+                                                      uint32_t G, uint32_t N) {
+    const uint64_t r64 = (uint64_t)blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+    if (r64 >= G) return;                                  // (wave-uniform)
+    const uint32_t r = (uint32_t)r64, lane = threadIdx.x & 63u;
+    const uint32_t s0 = room_start[r], n = min(room_start[r + 1] - s0, MAX_ROOM);
+    // selects, not branches, as in talkers_pick: a slot past the room's end reads a valid entry of the list and is nobody
+    uint32_t ch[PER_LANE];
+    bool aud[PER_LANE];
+#pragma unroll
+    for (uint32_t k = 0; k < PER_LANE; ++k) {
+        const uint32_t i = lane + 64 * k;
+        const uint32_t c = min(members[min((size_t)s0 + i, (size_t)N - 1)], N - 1u);
+        ch[k] = c;
+        aud[k] = i < n && (gate[c] != 0.0f || target[c] != 0.0f);
+    }
+    uint32_t at = 0;                                       // the audible members of the rounds before (wave-uniform)
+#pragma unroll
+    for (uint32_t k = 0; k < PER_LANE; ++k) {
+        const unsigned long long b = __ballot(aud[k]);
+        if (aud[k]) list[(size_t)s0 + at + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = (int32_t)ch[k];     // (at + below < n)
+        at += (uint32_t)__popcll(b);
+    }
+    if (lane == 0) count[r] = at;
+}
+
 // a reset's device side, in stream order, on channels [first, first + count): the fresh state
 __global__ __launch_bounds__(WG) void talkers_fresh(float *__restrict__ env, float *__restrict__ level, float *__restrict__ gate, float *__restrict__ target,
                                                     uint32_t first, uint32_t count) {
@@ -321,6 +355,10 @@ struct dspfx_talkers : BankError {
     uint8_t *pin = nullptr, *top = nullptr;
     uint32_t *members = nullptr, *room_start = nullptr;
     int32_t *talkers = nullptr;
+    // the audible list (dspfx_talkers_audible_views): made by the first call, under mu, and kept until release; while alist is set
+    // every gated run launches talkers_audible
+    int32_t *alist = nullptr;                    // [N]
+    uint32_t *acount = nullptr;                  // [G]
     float floor = 0.0f;                          // as of the stores drained so far (mu)
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
@@ -332,7 +370,7 @@ namespace {
 void release(dspfx_talkers *p) {
     (void)hipSetDevice(p->desc.device);
     for (void *d : {(void *)p->env, (void *)p->gate, (void *)p->target, (void *)p->level, (void *)p->ga, (void *)p->gr, (void *)p->tlev, (void *)p->pin,
-                    (void *)p->top, (void *)p->members, (void *)p->room_start, (void *)p->talkers})
+                    (void *)p->top, (void *)p->members, (void *)p->room_start, (void *)p->talkers, (void *)p->alist, (void *)p->acount})
         if (d) (void)hipFree(d);
     p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
@@ -434,6 +472,36 @@ extern "C" int dspfx_talkers_select(const float *levels, const uint32_t *room_of
             if (levels_out) levels_out[(size_t)g * MAX_TOP + t] = best < n ? levels[m[best]] : 0.0f;
             if (target_out && best < n) target_out[m[best]] = 1.0f;
         }
+    }
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_talkers_audible(const float *gate, const float *target, const uint32_t *room_of, uint64_t n_channels, uint32_t n_groups,
+                                     int32_t *list_out, uint32_t *start_out, uint32_t *count_out) {
+    g_err.clear();
+    if (!gate || !target || !room_of || !list_out || !start_out || !count_out || n_groups == 0) {
+        g_err = "talkers audible: gate, target, room_of, list_out, start_out, count_out or n_groups";
+        return DSPFX_ERR_INVALID;
+    }
+    int rc = check_shape("talkers", n_channels, 0, g_err);
+    if (rc == DSPFX_OK && n_channels > 0x7FFFFFFFull) {
+        g_err = "talkers audible: the list holds int32_t channel numbers, and there are more than 2^31 - 1 channels";
+        rc = DSPFX_ERR_INVALID;
+    }
+    if (rc == DSPFX_OK) rc = check_ids("audible", room_of, 0, n_channels, n_groups, g_err);
+    if (rc != DSPFX_OK) return rc;
+    // the members, sorted by (room, channel), straight into list_out; then every segment compacted in place, in order
+    build_seating([&](uint64_t c) { return room_of[c]; }, n_channels, n_groups, (uint32_t *)list_out, start_out);
+    for (uint32_t g = 0; g < n_groups; ++g)
+        if (start_out[g + 1] - start_out[g] > MAX_ROOM) return room_too_large("audible", g, start_out[g + 1] - start_out[g], g_err);
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        int32_t *seg = list_out + start_out[g];
+        uint32_t k = 0;
+        for (uint32_t i = 0; i < start_out[g + 1] - start_out[g]; ++i) {
+            const int32_t c = seg[i];
+            if (gate[c] != 0.0f || target[c] != 0.0f) seg[k++] = c;
+        }
+        count_out[g] = k;
     }
     return DSPFX_OK;
 }
@@ -678,6 +746,33 @@ extern "C" int dspfx_talkers_assign(dspfx_talkers *p, const uint32_t *host_room_
     return DSPFX_OK;
 }
 
+extern "C" int dspfx_talkers_audible_views(dspfx_talkers *p, const int32_t **list_out, const uint32_t **start_out, const uint32_t **count_out) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->alist) {
+        const size_t N = p->desc.n_channels, G = p->desc.n_groups;
+        if (N > 0x7FFFFFFFull) return p->fail(DSPFX_ERR_INVALID, "talkers audible: the list holds int32_t channel numbers, and the bank has more than 2^31 - 1 channels");
+        // on the caller's thread, once; count starts at 0 (nobody listed) and the device is idle on it before the first run reads it
+        int32_t *list = nullptr;
+        uint32_t *count = nullptr;
+        const bool ok = hipSetDevice(p->desc.device) == hipSuccess && hipMalloc((void **)&list, N * sizeof(int32_t)) == hipSuccess &&
+                        hipMalloc((void **)&count, G * sizeof(uint32_t)) == hipSuccess && hipMemset(list, 0xFF, N * sizeof(int32_t)) == hipSuccess &&
+                        hipMemset(count, 0, G * sizeof(uint32_t)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (list) (void)hipFree(list);
+            if (count) (void)hipFree(count);
+            return p->fail(DSPFX_ERR_OOM, "talkers audible: no device memory for the list (4 bytes per channel and 4 per room)");
+        }
+        p->acount = count;
+        p->alist = list;
+    }
+    if (list_out) *list_out = p->alist;
+    if (start_out) *start_out = p->room_start;
+    if (count_out) *count_out = p->acount;
+    return DSPFX_OK;
+}
+
 extern "C" int dspfx_talkers_room_of(dspfx_talkers *p, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
     if (!host_ids_out) return p->fail(DSPFX_ERR_INVALID, "talkers room_of: no array");
@@ -730,12 +825,16 @@ extern "C" int dspfx_talkers_run(dspfx_talkers *p, const float *in, float *out, 
     // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
     const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
     const uint32_t lanes = vec ? a.N / 4 : a.N, blocks = (lanes + WG - 1) / WG;
+    const uint32_t G = p->desc.n_groups;
+    if (p->alist && out) {                       // behind the stores and ahead of pass A, which overwrites gate
+        talkers_audible<<<(G + WG / 64 - 1) / (WG / 64), WG, 0, s>>>(p->gate, p->target, p->members, p->room_start, p->alist, p->acount, G, a.N);
+        BANK_HIP_WHY(hipGetLastError(), "talkers_audible");
+    }
     if (vec && out) talkers_run<4, true><<<blocks, WG, 0, s>>>(a);
     else if (vec) talkers_run<4, false><<<blocks, WG, 0, s>>>(a);
     else if (out) talkers_run<1, true><<<blocks, WG, 0, s>>>(a);
     else talkers_run<1, false><<<blocks, WG, 0, s>>>(a);
     BANK_HIP_WHY(hipGetLastError(), "talkers_run");
-    const uint32_t G = p->desc.n_groups;
     talkers_pick<<<(G + WG / 64 - 1) / (WG / 64), WG, 0, s>>>(p->level, p->pin, p->members, p->room_start, p->top, p->floor, p->target, p->talkers, p->tlev, G,
                                                             a.N);
     BANK_HIP_WHY(hipGetLastError(), "talkers_pick");

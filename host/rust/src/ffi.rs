@@ -522,6 +522,8 @@ extern "C" {
     pub fn dspfx_talkers_views(t: *mut dspfx_talkers, level_out: *mut *const f32, target_out: *mut *const f32, talkers_out: *mut *const i32, talker_levels_out: *mut *const f32) -> c_int;
     pub fn dspfx_talkers_room_of(t: *mut dspfx_talkers, host_ids_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_talkers_counts(t: *mut dspfx_talkers, host_counts_out: *mut u32) -> c_int;
+    pub fn dspfx_talkers_audible(gate: *const f32, target: *const f32, room_of: *const u32, n_channels: u64, n_groups: u32, list_out: *mut i32, start_out: *mut u32, count_out: *mut u32) -> c_int;
+    pub fn dspfx_talkers_audible_views(t: *mut dspfx_talkers, list_out: *mut *const i32, start_out: *mut *const u32, count_out: *mut *const u32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;
@@ -543,4 +545,5 @@ extern "C" {
     pub fn dspfx_mixmatrix_staging(m: *mut dspfx_mixmatrix, mode_out: *mut u32) -> c_int;
     pub fn dspfx_mixmatrix_staging_bytes(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, seats: *const u32, max_frames: u32, bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_scatter(room_of: *const u32, seat_of: *const u32, seats: *const u32, n_groups: u32, n_channels: u64, chunks_out: *mut u64, lines_out: *mut u64) -> c_int;
+    pub fn dspfx_mixmatrix_run_sparse(m: *mut dspfx_mixmatrix, block: *const f32, n_frames: u32, out: *mut f32, list: *const i32, list_len: u64, start: *const u32, count: *const u32, stream: *mut c_void) -> c_int;
 }

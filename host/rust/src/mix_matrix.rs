@@ -203,6 +203,15 @@ impl MixMatrix {
         let rc = dspfx_mixmatrix_run(self.h, block, n_frames, out, stream);
         self.check(rc, "dspfx_mixmatrix_run")
     }
+    /// The sparse run: room r adds only the sources named in `list[start[r] .. start[r] + count[r])` (DEVICE pointers: `i32` channel
+    /// numbers, `start[rooms + 1]`, `count[rooms]`; `Talkers::audible` gives them), in ascending room-local order, and reads no
+    /// other.  Where every unlisted source carries +-0.0 it is `run` bit for bit.  Entries that are negative, past the channels,
+    /// at or past `list_len`, or of another room are ignored.  The list's producer and this run share a stream.
+    pub unsafe fn run_sparse(&self, block: *const f32, n_frames: u32, out: *mut f32, list: *const i32, list_len: u64, start: *const u32, count: *const u32,
+                             stream: *mut c_void) -> Result<(), Error> {
+        let rc = dspfx_mixmatrix_run_sparse(self.h, block, n_frames, out, list, list_len, start, count, stream);
+        self.check(rc, "dspfx_mixmatrix_run_sparse")
+    }
     /// What listeners `first_channel ..` of one room hear: `values` is `[count][row_len]`, `row_len` the room's member count.
     pub fn set_rows(&self, values: &[f32], row_len: u32, first_channel: u64) -> Result<(), Error> {
         let count = if row_len == 0 { 0 } else { values.len() as u64 / row_len as u64 };

@@ -30,6 +30,13 @@ pub struct TalkerViews {
     pub talker_levels: *const f32,
 }
 
+/// The device tables of the audible list (`Talkers::audible`): `list[N]`, `start[G + 1]`, `count[G]`.
+pub struct AudibleViews {
+    pub list: *const i32,
+    pub start: *const u32,
+    pub count: *const u32,
+}
+
 fn reason(h: *const dspfx_talkers, what: &str) -> String {
     let msg = unsafe { CStr::from_ptr(dspfx_talkers_last_error(h)) }.to_string_lossy().into_owned();
     if msg.is_empty() { what.into() } else { msg }
@@ -116,6 +123,30 @@ impl Talkers {
         let rc = unsafe { dspfx_talkers_views(self.h, &mut v.level, &mut v.target, &mut v.talkers, &mut v.talker_levels) };
         self.check(rc, "dspfx_talkers_views")?;
         Ok(v)
+    }
+    /// The audible list on the device: room r's members whose gate or target was not +-0.0 when the last gated run began, in
+    /// ascending channel order, are `list[start[r] .. start[r] + count[r])`.  The first call allocates `list[N]` and `count[G]` and
+    /// switches the bank on: every gated run submitted after it also writes them.  The pointers are stable for the life of the
+    /// bank; what they hold is valid after a gated run, on its stream.  What `MixMatrix::run_sparse` takes.
+    pub fn audible(&self) -> Result<AudibleViews, Error> {
+        let mut v = AudibleViews { list: ptr::null(), start: ptr::null(), count: ptr::null() };
+        let rc = unsafe { dspfx_talkers_audible_views(self.h, &mut v.list, &mut v.start, &mut v.count) };
+        self.check(rc, "dspfx_talkers_audible_views")?;
+        Ok(v)
+    }
+    /// The audible rule on host arrays (a pure host function): `(list[N], start[groups + 1], count[groups])`.
+    pub fn audible_of(gate: &[f32], target: &[f32], room_of: &[u32], groups: u32) -> Result<(Vec<i32>, Vec<u32>, Vec<u32>), Error> {
+        if gate.len() != target.len() || gate.len() != room_of.len() {
+            return Err(Error { status: DSPFX_ERR_INVALID, message: "gate, target and room_of are equally long".into() });
+        }
+        let (mut list, mut start, mut count) = (vec![-1i32; gate.len()], vec![0u32; groups as usize + 1], vec![0u32; groups as usize]);
+        let rc = unsafe {
+            dspfx_talkers_audible(gate.as_ptr(), target.as_ptr(), room_of.as_ptr(), gate.len() as u64, groups, list.as_mut_ptr(), start.as_mut_ptr(), count.as_mut_ptr())
+        };
+        if rc != DSPFX_OK {
+            return Err(Error { status: rc, message: reason(ptr::null(), "dspfx_talkers_audible") });
+        }
+        Ok((list, start, count))
     }
     /// Every channel's room (`DSPFX_TALKERS_NO_ROOM`: none), by every assign made so far.
     pub fn room_of(&self) -> Result<Vec<u32>, Error> {

@@ -1225,7 +1225,8 @@ typedef struct dspfx_talkers_desc {
  * dspfx_chain_set computes for an Envelope node. */
 float dspfx_envelope_gain(float frames);
 /* PURE HOST function: *bytes_out = the device bytes of a bank's tables, 29 * channels + 69 * n_groups + 4.  channels of 0 or above
- * 2^32 - 256, or no rooms: DSPFX_ERR_INVALID, the reason in dspfx_talkers_last_error(NULL). */
+ * 2^32 - 256, or no rooms: DSPFX_ERR_INVALID, the reason in dspfx_talkers_last_error(NULL).  A bank that asks for its audible list
+ * (dspfx_talkers_audible_views) holds 4 * channels + 4 * n_groups more, which this figure leaves out. */
 int dspfx_talkers_plan(uint64_t channels, uint32_t n_groups, uint64_t *bytes_out);
 /* PURE HOST function: pass B's rule on host arrays.  levels[n_channels] (as the bank leaves them: non-negative, no NaN),
  * room_of[n_channels] (each below n_groups, or DSPFX_TALKERS_NO_ROOM), top[n_groups] (1 .. 8 each), pins[n_channels] or NULL for
@@ -1277,6 +1278,31 @@ int dspfx_talkers_views(dspfx_talkers *t, const float **level_out, const float *
  * so far (host tables). */
 int dspfx_talkers_room_of(dspfx_talkers *t, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count);
 int dspfx_talkers_counts(dspfx_talkers *t, uint32_t *host_counts_out);
+/* ---- the audible list: which members of each room can be non-zero in the block a run has just gated -------------------------
+ * talkers[G][8] is not that list: the gate ramps over one block, so in the block after a talker change the members fading out
+ * are still non-zero, and OPEN pins pass without taking a talker slot (a fresh or reset bank passes everybody).
+ * THE RULE.  A channel is AUDIBLE in a gated run iff its gate or its target, as the run finds them after the queued stores have
+ * been applied, is not +-0.0.  These are exactly the channels whose factor gate + (target - gate) * r[f] can be non-zero; every
+ * other channel's gated sample is x * 0, exactly zero for finite input.  From the third gated block after a fresh state a room
+ * lists at most 2 * top_r members (those fading in or held, those fading out) plus its OPEN pins.
+ * PURE HOST function: the rule on host arrays.  gate[n_channels], target[n_channels], room_of[n_channels] (each below n_groups, or
+ * DSPFX_TALKERS_NO_ROOM) -> start_out[n_groups + 1], the members' prefix table (room r has start[r + 1] - start[r] members: the
+ * room_start a bank makes from room_of); list_out[n_channels]: room r's audible members, in ascending channel order, are
+ * list_out[start[r] .. start[r] + count[r]), the entries of a segment past count[r] and the entries past start[n_groups] are
+ * unspecified; count_out[n_groups].  A bad id, a room above DSPFX_TALKERS_MAX_ROOM, more than 2^31 - 1 channels or a NULL pointer:
+ * DSPFX_ERR_INVALID, the reason in dspfx_talkers_last_error(NULL). */
+int dspfx_talkers_audible(const float *gate, const float *target, const uint32_t *room_of, uint64_t n_channels, uint32_t n_groups,
+                          int32_t *list_out, uint32_t *start_out, uint32_t *count_out);
+/* The device form.  The first call allocates list[N] (int32_t) and count[G] (4 bytes per channel and 4 per room beside
+ * dspfx_talkers_plan's figure; DSPFX_ERR_OOM if that fails, DSPFX_ERR_INVALID on a bank above 2^31 - 1 channels) and switches the
+ * bank on: every GATED run submitted after it launches one more kernel, talkers_audible, behind the drained stores and ahead of
+ * pass A (which overwrites gate): one wave per room gathers gate and target through the member list and compacts by ballot, in
+ * member order.  No atomics.  A metering run (out == NULL) gates nothing and leaves the tables as they were.  -> the device
+ * pointers of list, start (the bank's own room_start[G + 1], which dspfx_talkers_assign rewrites in stream order) and count; each
+ * out pointer may be NULL.  The pointers are stable for the life of the bank; what they hold is valid after a gated run, on its
+ * stream (before the first one: nobody is listed).  A bank that never calls this launches what it always launched.  The list is
+ * what dspfx_mixmatrix_run_sparse takes. */
+int dspfx_talkers_audible_views(dspfx_talkers *t, const int32_t **list_out, const uint32_t **start_out, const uint32_t **count_out);
 
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
@@ -1454,6 +1480,36 @@ int dspfx_mixmatrix_staging_bytes(const uint64_t *group_start, uint32_t n_groups
  * approaches 32 lines per chunk. */
 int dspfx_mixmatrix_scatter(const uint32_t *room_of, const uint32_t *seat_of, const uint32_t *seats, uint32_t n_groups, uint64_t n_channels,
                             uint64_t *chunks_out, uint64_t *lines_out);
+
+/* ---- the sparse run: only a listed set of sources per room --------------------------------------------------------------
+ * Behind a talker bank nearly every term of dspfx_mixmatrix_run is a multiplication by an exact zero.  This run reads only the
+ * sources a list names.  list (int32_t channel numbers), start[G + 1] and count[G] are DEVICE pointers, G the bank's room count:
+ * what dspfx_talkers_audible_views gives, or anything of that shape.
+ * CONTRACT.  For room r let A_r be the set of room-local indices held by the channels in
+ *       list[start[r] .. start[r] + min(count[r], DSPFX_MIXMATRIX_MAX_ROOM))
+ * a room-local index being a member index c - c0 in a bank made by dspfx_mixmatrix_create and a seat in a seated one.  An entry
+ * is IGNORED if it is negative, if it is >= N, if it lies at or past list_len, or if it names a channel that does not sit in room r;
+ * duplicates count once; the order of a segment does not matter.  Then for every taken index l of the room
+ *       out[f][chan(l)] = (fmaf chain from +0.0 over s in A_r, ascending s, of x[f][chan(s)] * Mt[s][l]) / d[chan(l)]
+ * d, normalise, "a row without a wired entry gives +0.0", the channels in no room (+0.0) and the layouts are those of
+ * dspfx_mixmatrix_run, and d still counts the WHOLE row's wired entries, listed or not.  A source outside A_r is NOT READ, whatever
+ * it carries: the documented difference from the dense run, where an unlisted NaN still reaches its room.  An empty A_r gives +0.0
+ * to every listener of the room.
+ * BITS.  If every source of the room outside A_r carries +-0.0 and the room's matrix is finite, the result is the dense run's bit
+ * for bit: fmaf(m, +-0.0, acc) == acc for finite m unless acc is -0.0; the chain starts at +0.0; an exact cancellation gives
+ * +0.0; so the dense chain's unlisted steps are all the identity.  The one exception is the sign of a zero result when a non-zero
+ * product has underflowed to -0.0 on the way.  With everybody listed it is the dense run on any block.  The error bound is the
+ * dense run's with n = the listed sources.
+ * MODES.  In DSPFX_MIXMATRIX_DIRECT out is written as the dense direct run writes it, out may not overlap the block, and the
+ * channels in no room are zeroed as there.  In DSPFX_MIXMATRIX_STAGED the few listed sources are read straight from the block
+ * (no mixmatrix_stage_in), the result goes to the seat-ordered copy and mixmatrix_stage_out writes out in whole lines whatever
+ * the seating; out == block is allowed.  Queued stores drain first, as in dspfx_mixmatrix_run.  The caller orders the list's
+ * producer and this run on one stream, or by an event, as for any device block.
+ * The host checks the pointers, n_frames, the overlap and list_len (at most 2^32 - 1): DSPFX_ERR_INVALID, the reason, nothing
+ * launched.  What the list holds is validated on the device, which never reads outside list[0 .. list_len), start[0 .. G] and
+ * count[0 .. G): a bad list yields ignored entries, not an error.  LDS atomics only (an order-free OR); no global atomics. */
+int dspfx_mixmatrix_run_sparse(dspfx_mixmatrix *m, const float *block, uint32_t n_frames, float *out, const int32_t *list, uint64_t list_len,
+                               const uint32_t *start, const uint32_t *count, void *stream);
 
 #ifdef __cplusplus
 }

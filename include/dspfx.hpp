@@ -663,6 +663,20 @@ class Talkers {
         chk(dspfx_talkers_views(p_, &v.level, &v.target, &v.talkers, &v.talker_levels));
         return v;
     }
+    // the audible list on the device: room r's members whose gate or target was not +-0.0 when the last gated run began -- the only
+    // ones that can be non-zero in the block it gated -- in ascending channel order, are list[start[r] .. start[r] + count[r]).  The
+    // first call allocates list and count and switches the bank on: every gated run submitted after it also writes them.  Stable
+    // pointers; valid after a gated run, on its stream.  What MixMatrix::run_sparse takes
+    struct Audible {
+        const std::int32_t *list;      // [N]
+        const std::uint32_t *start;    // [G + 1]
+        const std::uint32_t *count;    // [G]
+    };
+    Audible audible() {
+        Audible v{nullptr, nullptr, nullptr};
+        chk(dspfx_talkers_audible_views(p_, &v.list, &v.start, &v.count));
+        return v;
+    }
     // every channel's room and every room's member count, by every assign made so far
     std::vector<std::uint32_t> room_of(std::uint64_t first_channel, std::uint64_t count) {
         std::vector<std::uint32_t> m(count);
@@ -712,6 +726,13 @@ class MixMatrix {
     // device block of n_frames -> device block in the same layout; out may not overlap block (no in-place form, except out == block
     // in DSPFX_MIXMATRIX_STAGED); asynchronous on `stream`
     void run(const float *block, std::uint32_t n_frames, float *out, void *stream = nullptr) { chk(dspfx_mixmatrix_run(p_, block, n_frames, out, stream)); }
+    // the sparse run: room r adds only the sources named in list[start[r] .. start[r] + count[r]) (device pointers: channel numbers,
+    // start[G + 1], count[G]; Talkers::audible gives them), in ascending room-local order, and reads no other.  Where every unlisted
+    // source carries +-0.0 it is run() bit for bit.  Bad entries are ignored.  The list's producer and this run share a stream
+    void run_sparse(const float *block, std::uint32_t n_frames, float *out, const std::int32_t *list, std::uint64_t list_len, const std::uint32_t *start,
+                    const std::uint32_t *count, void *stream = nullptr) {
+        chk(dspfx_mixmatrix_run_sparse(p_, block, n_frames, out, list, list_len, start, count, stream));
+    }
     // what listeners [first_channel, first_channel + count) of ONE room hear: host_values[count][row_len], row_len = the room's members.
     // Any thread; never waits; applies, whole, to the runs submitted after it.
     void set_rows(const float *host_values, std::uint32_t row_len, std::uint64_t first_channel, std::uint64_t count) {

@@ -15,6 +15,11 @@ been reseated at random; --staged adds, beside every one of those columns, the s
 MIXMATRIX_STAGED, and the seating's lines per chunk (MixMatrix.scatter), the figure a host decides the mode by:
 
   python tools/mixmatrix_rate.py --channels 1048576 --room 256 --seats 256 --moved 0,0.01,0.1,1 --staged
+
+--sparse K adds the sparse run (MixMatrix.run(sources=...), dspfx_mixmatrix_run_sparse) with K listed sources per room, drawn at
+random, beside every dense figure: a column of the plain table, and with --seats a table of its own (direct, and staged with --staged):
+
+  python tools/mixmatrix_rate.py --channels 1048576 --room 256 --sparse 6
 """
 import argparse
 import json
@@ -46,7 +51,21 @@ def timed(torch, fn, reps):
     return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(reps)]))
 
 
-def measure(torch, n, room, reps):
+def listed_sources(torch, mix, k, rng):
+    """(list, start, count) on the device for MixMatrix.run(sources=...): k members of every room (all of a smaller one), drawn at
+    random by the bank's seating so far, each segment ascending"""
+    room_of = mix.room_of()
+    order = np.argsort(room_of, kind="stable")           # members by (room, channel); the channels in no room come last
+    sizes = np.bincount(room_of[room_of != pkg.NO_ROOM].astype(np.int64), minlength=mix.groups)
+    first = np.concatenate([[0], np.cumsum(sizes)])
+    segs = [np.sort(rng.choice(order[first[g]:first[g + 1]], min(k, int(sizes[g])), replace=False)) for g in range(mix.groups)]
+    count = np.asarray([len(s) for s in segs], np.uint32)
+    start = np.concatenate([[0], np.cumsum(count)]).astype(np.uint32)
+    lst = np.concatenate(segs + [np.full(1, -1, np.int64)]).astype(np.int32)
+    return tuple(torch.from_numpy(v).cuda() for v in (lst, start, count))
+
+
+def measure(torch, n, room, reps, sparse=0):
     dev = torch.device("cuda:0")
     torch.manual_seed(91)
     x = torch.rand(B * n, dtype=torch.float32, device=dev) * 2.0 - 1.0
@@ -60,17 +79,21 @@ def measure(torch, n, room, reps):
     ms = timed(torch, lambda: mix.run(x, B, out=y), reps)
     ret = timed(torch, lambda: rooms.returns(x, B, out=y), reps)
     copy = timed(torch, lambda: y.copy_(x), reps)
-    mix.close()
-    rooms.close()
     flop, own = 2.0 * n * room * B, 2 * B * n * 4 + table_bytes
     r = {"channels": n, "room": room, "ms": ms, "tflops": flop / (ms * 1e-3) / 1e12, "fraction_of_flop_peak": flop / (ms * 1e-3) / PEAK_FLOPS,
          "bytes": own, "gbs": own / (ms * 1e-3) / 1e9, "fraction_of_hbm_peak": own / (ms * 1e-3) / PEAK_BYTES, "returns_ms": ret,
          "x_returns": ms / ret, "copy_ms": copy}
+    if sparse:
+        src = listed_sources(torch, mix, sparse, np.random.default_rng(94))
+        r["sparse"], r["sparse_ms"] = sparse, timed(torch, lambda: mix.run(x, B, out=y, sources=src), reps)
+        r["sparse_x_dense"] = r["sparse_ms"] / ms
+    mix.close()
+    rooms.close()
     print(json.dumps(r), flush=True)
     return r
 
 
-def measure_seated(torch, n, room, seats, moved, reps, movers=16, staged=False):
+def measure_seated(torch, n, room, seats, moved, reps, movers=16, staged=False, sparse=0):
     """The seated bank beside the unseated one on the same buffers: ms per run unseated, seated at identity seating, and seated
     after each share of `moved` of the channels (cumulatively, in the order given) has been reseated into a random room with room;
     and the ms of the first run after an assign of `movers` channels (the queued seats, lines and recounts ride ahead of it).
@@ -96,10 +119,22 @@ def measure_seated(torch, n, room, seats, moved, reps, movers=16, staged=False):
         into[key] = timed(torch, lambda: mix.run(x, B, out=y), reps)
         mix.set_staging(pkg.MIXMATRIX_DIRECT)
 
+    def sparse_too(key):
+        """the sparse run over `sparse` listed sources per room at this seating, direct and (with staged) staged"""
+        if not sparse:
+            return
+        src = listed_sources(torch, mix, sparse, rng)
+        r.setdefault("sparse_ms", {})[key] = timed(torch, lambda: mix.run(x, B, out=y, sources=src), reps)
+        if staged:
+            mix.set_staging(pkg.MIXMATRIX_STAGED)
+            r.setdefault("sparse_staged_ms", {})[key] = timed(torch, lambda: mix.run(x, B, out=y, sources=src), reps)
+            mix.set_staging(pkg.MIXMATRIX_DIRECT)
+
     r["staged_ms"] = {}
     if staged:
         r["staging_bytes"] = pkg.mixmatrix_staging_bytes(n, seats, group_size=room, tile_channels=W, max_frames=B)
         staged_too(r["staged_ms"], "identity")
+    sparse_too("identity")
     # the first run after a small assign, from (nearly) identity seating: `movers` channels swap rooms pairwise, then swap back
     firsts = []
     for _ in range(reps):
@@ -134,6 +169,7 @@ def measure_seated(torch, n, room, seats, moved, reps, movers=16, staged=False):
         r["moved_ms"][str(share)] = timed(torch, lambda: mix.run(x, B, out=y), reps)
         if staged:
             staged_too(r["staged_ms"], str(share))
+        sparse_too(str(share))
     mix.close()
     print(json.dumps(r), flush=True)
     return r
@@ -147,6 +183,7 @@ def main():
     ap.add_argument("--seats", type=int, default=0, help="S: measure the seated bank with S seats per room beside the unseated one")
     ap.add_argument("--moved", default="0,0.01,0.1,1", help="with --seats: the shares of the channels reseated at random, cumulatively")
     ap.add_argument("--staged", action="store_true", help="with --seats: a MIXMATRIX_STAGED column beside every seated one, and the lines per chunk")
+    ap.add_argument("--sparse", type=int, default=0, help="K: also MixMatrix.run(sources=...) with K listed sources per room, beside every dense figure")
     a = ap.parse_args()
     import torch
     if a.seats:
@@ -155,8 +192,15 @@ def main():
         for n in (int(s) for s in a.channels.split(",")):
             for room in (int(s) for s in a.room.split(",")):
                 if room <= a.seats:
-                    out.append(measure_seated(torch, n, room, a.seats, moved, a.reps, staged=a.staged))
+                    out.append(measure_seated(torch, n, room, a.seats, moved, a.reps, staged=a.staged, sparse=a.sparse))
                     torch.cuda.empty_cache()
+        if a.sparse:
+            print(f"\nthe sparse run, {a.sparse} listed sources per room, ms, median of {a.reps}; per seating: direct" + (" | staged" if a.staged else ""))
+            print(f"{'channels':>9} {'room':>5} {'seats':>5} {'identity':>19} " + " ".join(f"{'moved ' + str(m):>19}" for m in moved))
+            for r in out:
+                keys = ["identity"] + [str(m) for m in moved]
+                print(f"{r['channels']:>9} {r['room']:>5} {r['seats']:>5} "
+                      + " ".join(f"{r['sparse_ms'][k]:>9.4f}" + (f" |{r['sparse_staged_ms'][k]:>8.4f}" if a.staged else " " * 10) for k in keys))
         if a.staged:
             print(f"\ntimes in ms, median of {a.reps}; per seating: direct | staged | lines per chunk (MixMatrix.scatter)")
             print(f"{'channels':>9} {'room':>5} {'seats':>5} {'unseated':>9} {'identity':>26} " + " ".join(f"{'moved ' + str(m):>26}" for m in moved)
@@ -177,13 +221,14 @@ def main():
     rows = []
     for n in (int(s) for s in a.channels.split(",")):
         for room in (int(s) for s in a.room.split(",")):
-            rows.append(measure(torch, n, room, a.reps))
+            rows.append(measure(torch, n, room, a.reps, a.sparse))
             torch.cuda.empty_cache()
     print(f"\ntimes in ms, median of {a.reps}; TFLOP/s of 157.3; GB/s on the bank's own bytes of 8 TB/s")
     print(f"{'channels':>9} {'room':>5} {'matrix':>8} {'TFLOP/s':>8} {'of peak':>8} {'GB/s':>8} {'of peak':>8} {'returns':>8} {'x returns':>9} {'copy':>8}")
     for r in rows:
         print(f"{r['channels']:>9} {r['room']:>5} {r['ms']:>8.4f} {r['tflops']:>8.1f} {r['fraction_of_flop_peak']:>8.3f} {r['gbs']:>8.0f} "
-              f"{r['fraction_of_hbm_peak']:>8.3f} {r['returns_ms']:>8.4f} {r['x_returns']:>9.2f} {r['copy_ms']:>8.4f}")
+              f"{r['fraction_of_hbm_peak']:>8.3f} {r['returns_ms']:>8.4f} {r['x_returns']:>9.2f} {r['copy_ms']:>8.4f}"
+              + (f"   sparse, {r['sparse']} listed per room: {r['sparse_ms']:.4f} ms, x {r['sparse_x_dense']:.3f} of the dense run" if a.sparse else ""))
 
 
 if __name__ == "__main__":
