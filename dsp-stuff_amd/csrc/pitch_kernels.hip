@@ -7,7 +7,9 @@
 // one being filled while the window before it has not been detected yet (it falls due only with its next frame).
 //
 // pitch_detect, one workgroup of 256 threads per PAIR of channels (c0, c0 + 1): the pair is one complex signal
-// z = x0 + i x1, zero-padded to 2048.  Z = FFT(z); X0 = (Z + conj Z(-k)) / 2, X1 = (Z - conj Z(-k)) / 2i;
+// z = x0 + i x1, zero-padded to 2048, each channel first scaled by its own power of two (max |x| into [2, 4), exact) and a
+// non-finite channel replaced by zeros, so that neither channel's level or poison reaches the other through the shared
+// transforms (tests/test_pitch_pairs_gpu.py).  Z = FFT(z); X0 = (Z + conj Z(-k)) / 2, X1 = (Z - conj Z(-k)) / 2i;
 // IFFT(|X0|^2 + i |X1|^2) = r_lin0 + i r_lin1, the two linear autocorrelations, exact for every lag < 1024 (2048 >= 2 * 1024 - 1).
 // The crate's FFT is 1536 long, so its lags alias: r(tau) = r_lin(tau) + r_lin(1536 - tau) for tau > 512, added here.
 // The FFTs are radix-4 (x5) + radix-2 Stockham passes between two LDS buffers, twiddles from a table rounded once from f64.
@@ -107,7 +109,8 @@ __global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
     __shared__ float2 A[FFT_N];
     __shared__ float2 B[FFT_N];
     __shared__ float wsum[2][DT / 64];
-    __shared__ int s_flag[2], s_lobe[2], s_M[2], s_t1[2], s_end[2], s_bmax[2], s_arg[2];
+    __shared__ uint32_t wmax[2][DT / 64];
+    __shared__ int s_lobe[2], s_M[2], s_t1[2], s_end[2], s_bmax[2], s_arg[2];
     const int t = threadIdx.x;
     // consecutive pairs on one XCD (workgroups are dealt round-robin over the 8), so their shared cache lines meet in one L2
     uint32_t blk = blockIdx.x;
@@ -117,7 +120,6 @@ __global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
     // c0 is even, so (c0, c0 + 1) share a tile when W >= 2, and every row starts 8-byte aligned when N is even
     const bool pair2 = has1 && (a.W ? a.W >= 2 : a.N % 2 == 0);
     if (t < 2) {
-        s_flag[t] = 0;
         s_lobe[t] = WIN;
         s_M[t] = 0;
         s_t1[t] = WIN;
@@ -127,8 +129,9 @@ __global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
     }
 
     // ---- the window: frames [CHUNK t, CHUNK t + CHUNK) of both channels, kept in registers to the end
+    // mb: the largest bit pattern of |x|, which orders as |x| does and puts inf and every NaN on top
     float x0[CHUNK], x1[CHUNK];
-    bool bad0 = false, bad1 = false, nz0 = false, nz1 = false;
+    uint32_t mb0 = 0, mb1 = 0;
 #pragma unroll
     for (int i = 0; i < CHUNK; ++i) {
         const uint32_t j = CHUNK * t + i;
@@ -144,21 +147,44 @@ __global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
             x0[i] = base[e0];
             x1[i] = has1 ? base[lay(j % SLOT, c0 + 1, SLOT, a.N, a.W)] : 0.0f;
         }
-        bad0 |= !isfinite(x0[i]);
-        bad1 |= !isfinite(x1[i]);
-        nz0 |= x0[i] != 0.0f;
-        nz1 |= x1[i] != 0.0f;
-        A[j] = make_float2(x0[i], x1[i]);
-        A[j + WIN] = make_float2(0.0f, 0.0f);
+        mb0 = max(mb0, __float_as_uint(x0[i]) & 0x7fffffffu);
+        mb1 = max(mb1, __float_as_uint(x1[i]) & 0x7fffffffu);
     }
-    // prefix sums of x^2: P[k] = sum_{j<k} x_j^2 for this thread's k, from a scan of the per-thread sums
+    const int lane = t & 63, wv = t >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+        mb0 = max(mb0, (uint32_t)__shfl_xor((int)mb0, d, 64));
+        mb1 = max(mb1, (uint32_t)__shfl_xor((int)mb1, d, 64));
+    }
+    if (lane == 0) {
+        wmax[0][wv] = mb0;
+        wmax[1][wv] = mb1;
+    }
+    __syncthreads();
+    for (int w = 0; w < DT / 64; ++w) {
+        mb0 = max(mb0, wmax[0][w]);
+        mb1 = max(mb1, wmax[1][w]);
+    }
+    // Each channel goes into the pair scaled by its OWN power of two, 2^(128 - E) with E the biased exponent of its max |x|
+    // (max |x| lands in [2, 4); a subnormal maximum takes E = 1): exact, and from here on neither channel's level reaches the
+    // other's rounding.  A non-finite channel goes in as zeros; it has no result anyway.  n(tau) is a ratio and needs no
+    // scaling back; the power does (pw_scale).
+    const bool bad0 = mb0 >= 0x7f800000u, bad1 = mb1 >= 0x7f800000u;
+    const uint32_t E0 = max(mb0 >> 23, 1u), E1 = max(mb1 >> 23, 1u);
+    const float sc0 = bad0 ? 0.0f : __uint_as_float((255u - E0) << 23);
+    const float sc1 = bad1 ? 0.0f : __uint_as_float((255u - E1) << 23);
     float q0 = 0.0f, q1 = 0.0f;
 #pragma unroll
     for (int i = 0; i < CHUNK; ++i) {
+        const uint32_t j = CHUNK * t + i;
+        x0[i] = bad0 ? 0.0f : x0[i] * sc0;
+        x1[i] = bad1 ? 0.0f : x1[i] * sc1;
+        A[j] = make_float2(x0[i], x1[i]);
+        A[j + WIN] = make_float2(0.0f, 0.0f);
         q0 += x0[i] * x0[i];
         q1 += x1[i] * x1[i];
     }
-    const int lane = t & 63, wv = t >> 6;
+    // prefix sums of x^2: P[k] = sum_{j<k} x_j^2 for this thread's k, from a scan of the per-thread sums
     float i0 = q0, i1 = q1;
 #pragma unroll
     for (int d = 1; d < 64; d *= 2) {
@@ -173,10 +199,6 @@ __global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
         wsum[1][wv] = i1;
     }
     __syncthreads();
-    if (bad0) atomicOr(&s_flag[0], 1);
-    if (bad1) atomicOr(&s_flag[1], 1);
-    if (nz0) atomicOr(&s_flag[0], 2);
-    if (nz1) atomicOr(&s_flag[1], 2);
     float e0 = i0 - q0, e1 = i1 - q1, tot0 = 0.0f, tot1 = 0.0f;
     for (int w = 0; w < DT / 64; ++w) {
         if (w < wv) {
@@ -303,8 +325,11 @@ __global__ __launch_bounds__(DT) void pitch_detect(DetArgs a) {
 
     // ---- the result
     if (lt != 0 || (ch == 1 && !has1)) return;
-    const int flag = s_flag[ch];
-    if ((flag & 1) || !(flag & 2) || tot < a.P) return;          // non-finite, all zero, power below the threshold
+    const uint32_t mb = ch ? mb1 : mb0;
+    if (mb >= 0x7f800000u || mb == 0) return;                    // non-finite, all zero
+    // the window's own power: tot is that of x 2^(128 - E), so times 2^(2 (E - 128)), in f64 for the range
+    const double pw_scale = __longlong_as_double((long long)(2 * (int)(ch ? E1 : E0) - 256 + 1023) << 52);
+    if ((double)tot * pw_scale < (double)a.P) return;            // power below the threshold
     const int k = s_arg[ch];
     if (s_M[ch] == 0 || t1 >= (int)WIN || k >= (int)WIN) return;
     const float b = nb[k];

@@ -615,6 +615,15 @@ double dspfx_algorithmic_bytes_per_sample(const dspfx_engine *e, uint32_t n_fram
  *   parabola through its neighbours a, b, c: delta = (c - a) / (2 (2b - a - c)) (0 if that is 0/0 or tau = 1023),
  *       frequency = 48000 / (tau + delta), clarity = (b + (c - a) delta / 4) / n(0).
  * The result is held per channel (0, 0 initially) and replaced only when a window gives one.
+ * Independence: a channel's result depends on its own window alone, whatever any other channel carries -- non-finite
+ * samples, the largest float in every frame, or a level 2^200 away from its own.  (The kernel transforms two channels
+ * at a time; each enters that pair scaled by its own power of two, and a non-finite channel enters it as zeros.)
+ * Level: the result is the restatement's (within the f32 accuracy the tests state) for every finite window whose
+ * max |x| is a normal float, 2^-126 <= max |x| <= FLT_MAX: frequency and clarity do not depend on the level, only
+ * the power test does, and `power` is compared with power_thresh without overflow or underflow (in f64).  Outside
+ * that range: a window with a NaN or an infinity gives no result, as above; a window whose max |x| is subnormal
+ * (or 0) has power < 2^-242 and gives no result at any power_thresh > 0; at power_thresh <= 0 it is scaled by
+ * 2^127 and detected like any other window, from the few significant bits its samples have (all zero: no result).
  * Layout: every block pushed is in the layout of the desc, exactly as dspfx_engine_desc's channels / tile_channels
  * (the tiled form for a block of n_frames).  The bank stores the samples in 128-frame slots, each in that layout. */
 typedef struct dspfx_pitch dspfx_pitch;

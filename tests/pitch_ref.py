@@ -36,17 +36,19 @@ def autocorr_direct(x):
     return np.array([sum(xp[j] * xp[(j + t) % L] for j in range(L)) for t in range(SIZE)])
 
 
-def nsdf(x):
+def nsdf(x, r=None):
     """n(tau) = 2 r(tau) / m(tau).  m(0) = 2 r(0), m(tau) = m(tau-1) - x[tau-1]^2 - x[1024-tau]^2 (the energy of the pairs that
     r_lin(tau) multiplies); for tau > 512, where r carries the aliased pairs r_lin(1536 - tau), m carries their energy
     m(1536 - tau) too, so that |n| <= 1.  (Without it the aliased tail reaches n ~ 30 for any periodic window and every pick lands
     there: a 440 Hz sine reads as 47.6 Hz.  With it the alias changes the result below about 94 Hz only.)  Where m(tau) <= 0 (a
-    window whose ends are exactly zero) n(tau) is taken as 0."""
+    window whose ends are exactly zero) n(tau) is taken as 0.  `r` replaces autocorr(x) (a model of some other arithmetic for
+    r(tau), lags [0, 1024)); m(tau) is always the float64 one."""
     x = np.asarray(x, np.float64)
-    r = autocorr(x)
+    r_own = autocorr(x)
+    r = r_own if r is None else np.asarray(r, np.float64)
     sq = x * x
     m_lin = np.empty(SIZE)
-    m_lin[0] = 2.0 * r[0]
+    m_lin[0] = 2.0 * r_own[0]
     m_lin[1:] = m_lin[0] - np.cumsum(sq[:SIZE - 1] + sq[::-1][:SIZE - 1])
     m = m_lin.copy()
     t = np.arange(PADDING + 1, SIZE)
@@ -77,7 +79,7 @@ def key_maxima(n):
     return out
 
 
-def detect(x, P=0.5, C=0.5, K=0.5):
+def detect(x, P=0.5, C=0.5, K=0.5, r=None):
     x = np.asarray(x, np.float64)
     none = (False, -1, 0.0, 0.0)
     if not np.all(np.isfinite(x)) or not np.any(x):
@@ -86,7 +88,7 @@ def detect(x, P=0.5, C=0.5, K=0.5):
     margins = [abs(power - P)]
     if power < P:
         return none + (min(margins),)
-    n = nsdf(x)
+    n = nsdf(x, r)
     keys = key_maxima(n)
     if not keys:
         return none + (min(margins + [float(np.min(np.abs(n[1:])))]),)
