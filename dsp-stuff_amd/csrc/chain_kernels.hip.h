@@ -99,7 +99,8 @@ struct ChainArgs {
     int fast_div;            // every constant divisor of this launch passed the exhaustive check
     int xcd_remap;           // 1: blocks of one XCD (b % 8) cover a contiguous range of channel tiles
     int walk_rev;            // 1: this launch walks its tiles back to front (work_block): what the launch before it touched last comes first
-    unsigned walk_zone;      // chain_kernel: the first and the last walk_zone workgroups of the launch store their output rows on the default cache policy (walk_cached_out)
+    unsigned walk_zone;      // chain_kernel: the first walk_zone and the last walk_tail workgroups of the launch (dispatch order) store their output
+    unsigned walk_tail;      // rows on the default cache policy (walk_cached_out); the engine sets the widths (head zone: 0 when it keeps the hint)
     // Pipelined mix bus (mixpipe_prologue): the second and third reduction stage of EARLIER blocks ride in this
     // launch's first workgroups instead of separate kernels on a second stream.
     int skip_store;          // in-place launch of an empty chain that only feeds the mix bus: nothing to write back
@@ -1370,9 +1371,11 @@ __device__ __forceinline__ unsigned work_block(int remap, int rev) {
 // there saves one of the two trips to HBM (profiles/llc_reuse.txt).  But default-policy stores on ALL output rows cost more than
 // the hits at the two ends give back (they displace each other long before the next launch comes round).  So only the
 // workgroups at the two ends of the launch -- dispatch order, i.e. blockIdx, whichever direction the tiles are walked in --
-// take the hint off their output stores: the first `zone` rewrite what is resident, the last `zone` leave it there.
-__device__ __forceinline__ bool walk_cached_out(unsigned zone) {
-    return blockIdx.x < zone || blockIdx.x + zone >= gridDim.x;
+// take the hint off their output stores: the last `tail` leave their rows there, the first `zone` rewrite what is resident.
+// (The rewrite saves its trip to HBM with the hint on it too, at about half the rate, and then the rewritten rows do not
+// stay behind the launch's other traffic -- profiles/llc_zones.txt; the engine chooses, a head zone of 0 keeps the hint.)
+__device__ __forceinline__ bool walk_cached_out(unsigned zone, unsigned tail) {
+    return blockIdx.x < zone || blockIdx.x + tail >= gridDim.x;
 }
 
 // ---- the fused chain kernel, statically specialised ---------------------------------
@@ -1539,7 +1542,7 @@ __global__ void __launch_bounds__(WG) chain_kernel(const ChainArgs a) {
     DSPFX_FOR_SLOTS(DSPFX_LD)
 #undef DSPFX_LD
     const WaveAddr w = wave_addr(a, c);
-    const bool out_cached = walk_cached_out(a.walk_zone);
+    const bool out_cached = walk_cached_out(a.walk_zone, a.walk_tail);
     unsigned f0 = 0;
     for (; f0 + F <= a.nframes; f0 += F) {
         chain_chunk<F, CPL, SL, MOD>(a, st, c, w, f0, lane, ms, wave, out_cached);

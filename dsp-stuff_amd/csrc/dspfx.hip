@@ -420,7 +420,11 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
         // 1.5-6 % slower with their sample block on the default policy (profiles/llc_reuse.txt) and keep the hint everywhere.
         if (c.walk_alt && !v->ts && v->cpl >= 2) {
             const uint64_t wg_bytes = (uint64_t)WG * v->cpl * nframes * sizeof(float);
-            a.walk_zone = (unsigned)std::min<uint64_t>(((uint64_t)walk_zone_mib(e) << 20) / wg_bytes, 0x7fffffffu);
+            const unsigned grid = ((w1 - w0) / v->cpl + WG - 1) / WG;
+            const uint64_t head = ((uint64_t)walk_zone_mib(e) << 20) / wg_bytes, tail = ((uint64_t)walk_tail_mib(e) << 20) / wg_bytes;
+            // zones that meet or overlap: the whole output block on the default policy (every workgroup is a tail-zone workgroup)
+            a.walk_tail = head + tail >= grid ? grid : (unsigned)tail;
+            a.walk_zone = head + tail >= grid || walk_head_policy(e) ? 0u : (unsigned)head;
         }
         ProfScope ps(e, si, stream);
         if (launch_variant(v, a, v->ts ? (w1 - w0) / per_wave : ((w1 - w0) / v->cpl + WG - 1) / WG, WG, (unsigned)(rows * WG * v->cpl * sizeof(float)), stream)) {
@@ -429,7 +433,7 @@ static int run_fused(dspfx_engine *e, const BlockCall &c, size_t si, const float
         }
     }
     a.mp_stage = 0;   // the guarded tail launch never hosts the prologue
-    a.walk_zone = 0;
+    a.walk_zone = a.walk_tail = 0;
     if ((N % per_wave || whole_guard) && (!c.window_n || c.window_c0 + c.window_n >= N)) {   // ragged tail: guarded one-wave blocks, lane per channel
         const uint32_t n_tail = N - n_main;
         a.c_base = n_main;

@@ -114,6 +114,8 @@ struct EnvSwitches {
     int xcd_remap = -1;          // DSPFX_XCD_REMAP
     int walk = -1;               // DSPFX_WALK (0: every launch walks its tiles front to back; 1: consecutive whole-range launches alternate)
     int walk_zone_mib = -1;      // DSPFX_WALK_ZONE_MIB (output rows at each end of an alternating launch that stay in the last-level cache; unset: WALK_ZONE_MIB)
+    int walk_head = -1;          // DSPFX_WALK_HEAD (policy of the head zone's output stores: 0 default policy, 1 nontemporal hint; unset: WALK_HEAD_POLICY)
+    int walk_tail_mib = -1;      // DSPFX_WALK_TAIL_MIB (the tail zone's size on its own; unset: DSPFX_WALK_ZONE_MIB, else WALK_TAIL_MIB)
     int mix_tail = -1;           // DSPFX_MIX_TAIL (0: stand-alone bus kernels)
     int fast_div = -1;           // DSPFX_FAST_DIV (0: IEEE division everywhere)
     int jit = -1, jit_async = -1;   // DSPFX_JIT, DSPFX_JIT_ASYNC
@@ -355,6 +357,18 @@ inline bool walk_alternates(const dspfx_engine *e) { return e->env.walk >= 0 ? e
 // walk_cached_out).  From the sweep in profiles/llc_reuse.txt.
 constexpr uint32_t WALK_ZONE_MIB = 96;
 inline uint32_t walk_zone_mib(const dspfx_engine *e) { return e->env.walk_zone_mib >= 0 ? (uint32_t)e->env.walk_zone_mib : WALK_ZONE_MIB; }
+// The two zones apart (profiles/llc_zones.txt).  The tail zone -- the last workgroups of a launch -- leaves its rows in the cache;
+// the head zone -- the first of the next -- rewrites them.  Head policy 0: default-policy stores (the rewritten rows stay resident, so
+// both zones share the cache); 1: the head zone keeps the hint like the middle.  Whatever the policy, an engine whose output block
+// fits head + tail zone stores all of it on the default policy.  DSPFX_WALK_ZONE_MIB sets both sizes, DSPFX_WALK_TAIL_MIB the tail's.
+// Measured (llc_zones.txt): with the hint the rewrite still saves its trip to HBM, the tail zone has the cache to itself and can be
+// as large as the cache: head policy 1, tail zone 256 MiB (224 and 288 MiB within 0.5 % of it; the 96 MiB pair 0.8-1.1 % slower).
+constexpr int WALK_HEAD_POLICY = 1;
+constexpr uint32_t WALK_TAIL_MIB = 256;
+inline int walk_head_policy(const dspfx_engine *e) { return e->env.walk_head >= 0 ? (e->env.walk_head ? 1 : 0) : WALK_HEAD_POLICY; }
+inline uint32_t walk_tail_mib(const dspfx_engine *e) {
+    return e->env.walk_tail_mib >= 0 ? (uint32_t)e->env.walk_tail_mib : e->env.walk_zone_mib >= 0 ? (uint32_t)e->env.walk_zone_mib : WALK_TAIL_MIB;
+}
 void async_jit_submit(const std::shared_ptr<AsyncJit> &job);   // jit.hip: background specialisation for small engines
 bool async_jit_wait(const std::shared_ptr<AsyncJit> &job, int wait_ms);   // ... until the compiler is done with `job` (bounded)
 int validate_node(dspfx_engine *e, const dspfx_node_desc &d);

@@ -91,6 +91,8 @@ EnvSwitches read_env_switches() {
     s.xcd_remap = env_int("DSPFX_XCD_REMAP");
     s.walk = env_int("DSPFX_WALK");
     s.walk_zone_mib = env_int("DSPFX_WALK_ZONE_MIB");
+    s.walk_head = env_int("DSPFX_WALK_HEAD");
+    s.walk_tail_mib = env_int("DSPFX_WALK_TAIL_MIB");
     s.mix_tail = env_int("DSPFX_MIX_TAIL");
     s.fast_div = env_int("DSPFX_FAST_DIV");
     s.jit = env_int("DSPFX_JIT");

@@ -316,8 +316,12 @@ extern "C" int dspfx_describe(const dspfx_engine *e, char *dst, size_t cap) {
                 }
         }
     if (walk_alternates(e)) {
-        snprintf(buf, sizeof buf, "tile walk: consecutive launches over all channels alternate front-to-back / back-to-front; "
-                                  "standard kernels at two or more channels per lane keep %u MiB of output rows at each end of a launch in the last-level cache\n", walk_zone_mib(e));
+        s += "tile walk: consecutive launches over all channels alternate front-to-back / back-to-front; ";     // (one line)
+        snprintf(buf, sizeof buf, "standard kernels at two or more channels per lane keep the last %u MiB of a launch's output rows in the last-level cache (tail zone), ",
+                 walk_tail_mib(e));
+        s += buf;
+        snprintf(buf, sizeof buf, "the next launch rewrites them first (head zone: %u MiB, %s)\n", walk_zone_mib(e),
+                 walk_head_policy(e) ? "stores with the nontemporal hint" : "default-policy stores");
         s += buf;
     } else {
         s += "tile walk: every launch front to back\n";

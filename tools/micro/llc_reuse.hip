@@ -4,10 +4,12 @@
 // timed launch(es), median of REPS repetitions after warm-up; every repetition rebuilds the cache state it measures.
 //   hipcc --offload-arch=gfx950 -O3 -o tools/micro/llc_reuse tools/micro/llc_reuse.hip && tools/micro/llc_reuse
 // (profiles/llc_reuse.txt, section 1, holds one run and what it was read as.)
+// `llc_reuse zones` runs the second part alone: the output stores' policy by dispatch-order zone (profiles/llc_zones.txt).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -67,6 +69,62 @@ __global__ void __launch_bounds__(WG) chainpat(const char *in, char *ring, char 
     }
 }
 
+// chainpat with the output stores' policy chosen per workgroup, by its place in DISPATCH order (blockIdx, whichever way the
+// tiles are walked): the first `head` workgroups rewrite what the launch before left, the last `tail` leave theirs for the
+// next launch, the middle streams.  Where the zones meet or overlap every workgroup is a tail-zone workgroup.
+// aux bits: 1 = sc0, 2 = nt, 16 = sc1.  state: a 32 MiB stream of 8 KiB per tile, read at the tile's start and written at its
+// end (the chain kernels' state rows): 0 = none, 1 = default policy everywhere, 2 = nt outside the zones.
+struct Zones {
+    unsigned head, tail;        // workgroups
+    int aux_head, aux_mid, aux_tail, state;
+};
+constexpr unsigned ST_ROWS = 4;                                                                 // 8 KiB of state per tile
+template <int AUX_OUT, int AUX_ST>
+__device__ __forceinline__ void zone_tile(const char *in, char *ring, char *out, char *state, unsigned tile, bool with_state) {
+    const __amdgpu_buffer_rsrc_t ri = tile_rsrc(in, tile), rr = tile_rsrc(ring, tile), ro = tile_rsrc(out, tile);
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(state + (size_t)tile * (ST_ROWS * ROW_BYTES), 0, (int)(ST_ROWS * ROW_BYTES), 0x00020000);
+    u32x2 s[ST_ROWS];
+    if (with_state)
+#pragma unroll
+        for (unsigned k = 0; k < ST_ROWS; ++k) s[k] = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(threadIdx.x * 8), (int)(k * ROW_BYTES), AUX_ST);
+    for (unsigned row0 = 0; row0 < ROWS; row0 += 8) {
+        u32x2 x[8], y[8];
+#pragma unroll
+        for (unsigned k = 0; k < 8; ++k) {
+            x[k] = __builtin_amdgcn_raw_buffer_load_b64(ri, (int)(threadIdx.x * 8), (int)((row0 + k) * ROW_BYTES), 2);
+            y[k] = __builtin_amdgcn_raw_buffer_load_b64(rr, (int)(threadIdx.x * 8), (int)((row0 + k) * ROW_BYTES), 2);
+        }
+#pragma unroll
+        for (unsigned k = 0; k < 8; ++k) {
+            __builtin_amdgcn_raw_buffer_store_b64(x[k], rr, (int)(threadIdx.x * 8), (int)((row0 + k) * ROW_BYTES), 2);
+            __builtin_amdgcn_raw_buffer_store_b64(x[k] + y[k], ro, (int)(threadIdx.x * 8), (int)((row0 + k) * ROW_BYTES), AUX_OUT);
+        }
+    }
+    if (with_state)
+#pragma unroll
+        for (unsigned k = 0; k < ST_ROWS; ++k) __builtin_amdgcn_raw_buffer_store_b64(s[k] + 1u, rs, (int)(threadIdx.x * 8), (int)(k * ROW_BYTES), AUX_ST);
+}
+__global__ void __launch_bounds__(WG) zonepat(const char *in, char *ring, char *out, char *state, int rev, Zones z) {
+    const unsigned tile = tile_of(rev);
+    const bool in_tail = blockIdx.x + z.tail >= gridDim.x, in_head = !in_tail && blockIdx.x < z.head;
+    const int aux = in_tail ? z.aux_tail : in_head ? z.aux_head : z.aux_mid;
+    const bool st_nt = z.state == 2 && !in_tail && !in_head;
+#define ZONE_CASE(A)                                                                 \
+    case A:                                                                          \
+        if (st_nt) zone_tile<A, 2>(in, ring, out, state, tile, true);                \
+        else zone_tile<A, 0>(in, ring, out, state, tile, z.state != 0);              \
+        break;
+    switch (aux) {
+        ZONE_CASE(0)
+        ZONE_CASE(2)
+        ZONE_CASE(16)
+        ZONE_CASE(17)
+        ZONE_CASE(18)
+    }
+#undef ZONE_CASE
+}
+
 static unsigned *g_sink;
 static void read_buf(const char *b, size_t bytes, int aux, int rev = 0) {
     const unsigned tiles = (unsigned)(bytes / TILE_BYTES);
@@ -103,7 +161,68 @@ static float median_us(PRE pre, TIMED timed) {
     return v[v.size() / 2];
 }
 
-int main() {
+// Section 2 (profiles/llc_zones.txt): the alternating chain pattern with a head zone, a middle and a tail zone, steady state
+// (8 alternating launches after 2), microseconds per launch.  `state` is a 32 MiB buffer, the others 512 MiB.
+static void zones_section(const char *in, char *ring, char *out, char *state, size_t bytes) {
+    const unsigned tiles = (unsigned)(bytes / TILE_BYTES);
+    const unsigned per_mib = (unsigned)(MiB / TILE_BYTES);
+    struct Pol { int aux; const char *name; };
+    const Pol heads[] = {{0, "default"}, {2, "nt"}, {16, "sc1"}, {17, "sc0 sc1"}, {18, "nt sc1"}};
+    const Pol tails[] = {{0, "default"}, {16, "sc1"}, {17, "sc0 sc1"}};
+    const unsigned zs[] = {64, 96, 128, 160, 192, 224};
+    const char *states[] = {"no state stream", "32 MiB state stream beside it, default policy", "32 MiB state stream beside it, nt outside the zones"};
+    auto steady = [&](Zones z) {
+        auto go = [&](int n) { for (int k = 0; k < n; ++k) hipLaunchKernelGGL(zonepat, dim3(tiles), dim3(WG), 0, 0, in, ring, out, state, k & 1, z); };
+        return median_us([&] { go(2); }, [&] { go(8); }) / 8.0f;
+    };
+    printf("\n## zones: alternating chain pattern, output stores by dispatch-order zone (head | middle nt | tail), us per launch\n");
+    for (int st = 0; st < 3; ++st) {
+        printf("### %s\n", states[st]);
+        printf("no zones (all nt)                %8.2f\n", steady(Zones{0, 0, 2, 2, 2, st}));
+        for (const Pol &t : tails) {
+            printf("# tail %-8s   head \\ Z MiB", t.name);
+            for (unsigned z : zs) printf(" %8u", z);
+            printf("\n");
+            for (const Pol &h : heads) {
+                printf("tail %-8s head %-8s     ", t.name, h.name);
+                for (unsigned z : zs) printf(" %8.2f", steady(Zones{z * per_mib, z * per_mib, h.aux, 2, t.aux, st}));
+                printf("\n");
+                fflush(stdout);
+            }
+        }
+    }
+    printf("### no state stream, tail default: head zone HALF the tail zone (columns: tail Z MiB)\n");
+    const unsigned zt[] = {128, 192, 224};
+    for (const Pol &h : heads) {
+        printf("tail default  head %-8s     ", h.name);
+        for (unsigned z : zt) printf(" %8.2f", steady(Zones{z / 2 * per_mib, z * per_mib, h.aux, 2, 0, 0}));
+        printf("\n");
+    }
+    // head nt is the middle's policy, i.e. NO head zone: the tail zone alone may then grow past half the buffer
+    printf("### tail zone alone (head = middle = nt), tail default (columns: tail Z MiB; 512 = every output store on the default policy)\n");
+    const unsigned zl[] = {192, 224, 256, 288, 320, 384, 512};
+    printf("#                                ");
+    for (unsigned z : zl) printf(" %8u", z);
+    printf("\n");
+    for (int st = 0; st < 3; ++st) {
+        printf("state mode %d                     ", st);
+        for (unsigned z : zl) printf(" %8.2f", steady(Zones{0, z * per_mib, 2, 2, 0, st}));
+        printf("\n");
+    }
+    // what one figure above is good for: the write-through candidates against today's pair, three interleaved passes
+    printf("### repeatability: three interleaved passes (columns: Z 96 / Z 128 without, Z 96 / Z 128 with the default-policy state stream)\n");
+    const int cand[][2] = {{0, 0}, {16, 0}, {17, 0}, {0, 16}, {16, 16}};       // {head aux, tail aux}
+    for (int pass = 0; pass < 3; ++pass)
+        for (const auto &c : cand) {
+            printf("pass %d  head aux %2d  tail aux %2d    ", pass, c[0], c[1]);
+            for (int st = 0; st < 2; ++st)
+                for (unsigned z : {96u, 128u}) printf(" %8.2f", steady(Zones{z * per_mib, z * per_mib, c[0], 2, c[1], st}));
+            printf("\n");
+        }
+}
+
+int main(int argc, char **argv) {
+    const bool zones_only = argc > 1 && !strcmp(argv[1], "zones");      // `llc_reuse zones`: section 2 alone
     const size_t S = 32 * MiB, L = 512 * MiB;
     char *small, *ta, *tb, *big[4];
     CHECK(hipMalloc(&small, S));
@@ -121,6 +240,12 @@ int main() {
     // 64 MiB of other traffic: 32 MiB read, 32 MiB written
     auto traffic64 = [&](int aux) { read_buf(ta, S, aux); write_buf(tb, S, aux); };
 
+    if (zones_only) {
+        printf("# llc_reuse zones: median of %d repetitions, microseconds (HIP events around the timed launches)\n", REPS);
+        zones_section(big[1], big[2], big[0], small, L);
+        CHECK(hipDeviceSynchronize());
+        return 0;
+    }
     printf("# llc_reuse: median of %d repetitions, microseconds (HIP events around the timed launch)\n", REPS);
     const float t_empty = median_us([] {}, [&] { read_buf(small, TILE_BYTES, 0); });
     printf("one-tile launch (event overhead)        %8.2f\n", t_empty);
@@ -174,6 +299,7 @@ int main() {
                                       [&] { for (int k = 0; k < 8; ++k) chain_pat(big[1], big[2], big[0], L, a * 2, alt ? k & 1 : 0); }) / 8.0f;
             printf("out aux %d in chain, %s         %8.2f   %7.0f\n", a * 2, alt ? "alternating " : "all forward ", t, 4.0 * L / (t * 1e-6) / 1e9);
         }
+    zones_section(big[1], big[2], big[0], small, L);
     CHECK(hipDeviceSynchronize());
     return 0;
 }

@@ -3,6 +3,7 @@
 tuned, two alternating inputs and one output buffer per arm as bench.py has them, >= 200 launches per arm.
 Each arm = "name[:key=val,...]" with keys
   lib=<path to a libdspfx build>   walk=0|1 (DSPFX_WALK)   zone=<MiB> (DSPFX_WALK_ZONE_MIB)
+  head=0|1 (DSPFX_WALK_HEAD: the head zone's stores on the default policy | with the hint)   tail=<MiB> (DSPFX_WALK_TAIL_MIB)
 Example (parent/libdspfx.so: the parent commit's build of the library):
   python tools/walk_ab.py parent:lib=parent/libdspfx.so fwd:walk=0 alt:walk=1 alt64:walk=1,zone=64
   python tools/walk_ab.py --chain chain3 --channels 131072 --tune 0 parent:lib=parent/libdspfx.so branch
@@ -17,7 +18,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-ENV = {"walk": "DSPFX_WALK", "zone": "DSPFX_WALK_ZONE_MIB"}
+ENV = {"walk": "DSPFX_WALK", "zone": "DSPFX_WALK_ZONE_MIB", "head": "DSPFX_WALK_HEAD", "tail": "DSPFX_WALK_TAIL_MIB"}
 
 
 def load_pkg(lib_path, tag):
