@@ -99,6 +99,9 @@ EXPORTS = [
     "dspfx_talkers_last_error", "dspfx_talkers_run", "dspfx_talkers_assign", "dspfx_talkers_set_detector", "dspfx_talkers_set_pin",
     "dspfx_talkers_set_top", "dspfx_talkers_set_floor", "dspfx_talkers_reset", "dspfx_talkers_views", "dspfx_talkers_room_of",
     "dspfx_talkers_counts", "dspfx_talkers_audible", "dspfx_talkers_audible_views", "dspfx_mixmatrix_run_sparse",
+    "dspfx_dynamics_plan", "dspfx_dynamics_gain", "dspfx_dynamics_create", "dspfx_dynamics_destroy", "dspfx_dynamics_last_error",
+    "dspfx_dynamics_run", "dspfx_dynamics_set", "dspfx_dynamics_drop", "dspfx_dynamics_reset", "dspfx_dynamics_present",
+    "dspfx_dynamics_views",
 ]
 COMM_ID_BYTES = 128
 
@@ -180,6 +183,11 @@ class _TalkersDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("n_groups", C.c_uint32), ("top", C.c_uint32),
                 ("group_start", C.POINTER(C.c_uint64))]
+
+
+class _DynamicsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32)]
 
 
 class _Ctl(C.Structure):
@@ -400,6 +408,19 @@ def lib():
     L.dspfx_talkers_counts.argtypes = [vp, u32p]
     L.dspfx_talkers_audible.argtypes = [fp, fp, u32p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32), u32p, u32p]
     L.dspfx_talkers_audible_views.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.dspfx_dynamics_plan.argtypes = [C.c_uint64, C.POINTER(C.c_uint64)]
+    L.dspfx_dynamics_gain.restype = C.c_float
+    L.dspfx_dynamics_gain.argtypes = [C.c_float, C.c_float, C.c_float, fp]
+    L.dspfx_dynamics_create.argtypes = [C.POINTER(_DynamicsDesc), C.POINTER(vp)]
+    L.dspfx_dynamics_destroy.argtypes = [vp]
+    L.dspfx_dynamics_last_error.restype = C.c_char_p
+    L.dspfx_dynamics_last_error.argtypes = [vp]
+    L.dspfx_dynamics_run.argtypes = [vp, f32p, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_dynamics_set.argtypes = [vp, fp, fp, fp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_dynamics_drop.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.dspfx_dynamics_reset.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.dspfx_dynamics_present.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_dynamics_views.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -1912,6 +1933,117 @@ class Talkers(_Bank):
     def talker_levels(self):
         """float32[groups, 8] on the device: the talkers' levels, 0.0 where there is none."""
         return self._view(self._views[3], (self.groups, TALKERS_MAX_TOP), "<f4")
+
+
+def dynamics_plan(channels: int) -> int:
+    """dspfx_dynamics_plan, a pure host function (no GPU): the device bytes of a ChannelDynamics bank's tables, 29 per channel."""
+    L = lib()
+    n = C.c_uint64()
+    rc = L.dspfx_dynamics_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
+    _raise(L, "dynamics", rc)
+    return int(n.value)
+
+
+def dynamics_gain(env: float, threshold: float, makeup: float = 1.0):
+    """dspfx_dynamics_gain, a pure host function (no GPU): the gain computer on one envelope value -> (makeup * q, q) as float32,
+    q = env > threshold ? threshold / env : 1 -- the factor a ChannelDynamics run multiplies the sample by, bit for bit."""
+    q = C.c_float()
+    g = lib().dspfx_dynamics_gain(float(env), float(threshold), float(makeup), C.byref(q))
+    return np.float32(g), np.float32(q.value)
+
+
+class ChannelDynamics(_Bank):
+    """Per-channel levellers and limiters (include/dspfx.h, dspfx_dynamics_*): channel c may carry its own Envelope node (attack and
+    release in frames) feeding its own gain computer, q = env > threshold ? threshold / env : 1, out = in * (makeup * q), over a
+    device block in the layout of `tile_channels` (as Engine's).  A node exists for a channel from the first `set` that names it
+    until `drop`; a fresh bank copies its input.  A limiter: set(threshold=ceiling, release=..) -- attack 0 is a brick wall at
+    threshold * makeup.  A leveller towards `target` with at most `max_gain`: set(threshold=target / max_gain, makeup=max_gain,
+    ..).  Ahead of Talkers as a leveller, behind the room mixes as a limiter.  Asynchronous on `stream`."""
+
+    _C = "dynamics"
+    _WHY = True
+
+    def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+        d = _DynamicsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
+        self._create(d)
+        ptrs = [C.c_void_p() for _ in range(2)]
+        self._chk(self.L.dspfx_dynamics_views(self.h, *[C.byref(p) for p in ptrs]))
+        self._views = [p.value for p in ptrs]
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, key=None, stream: int = 0):
+        """One device block through every channel's dynamics -> `out`, a device block in the same layout (made when not given;
+        out=block works in place).  `key`, a device block of the same shape, is what the detector follows instead of `block`
+        (key=block is no key); it must not overlap `out` unless it is `block`."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_dynamics_run(self.h, _ptr(block), _ptr(key) if key is not None else None, _ptr(out), int(n_frames),
+                                            C.c_void_p(stream) if stream else None))
+        return out
+
+    def set(self, threshold=None, makeup=None, attack=None, release=None, first_channel: int = 0, count: Optional[int] = None):
+        """Store the sliders of channels from first_channel, and give each of them its node: arrays (one value per channel) or
+        scalars for `count` channels (default: all from first_channel).  A slider left None keeps each channel's value (attack 0,
+        release 0, threshold 1, makeup 1 where never stored).  No envelope is touched.  Refused whole: a threshold that is NaN or
+        below +0.0, a makeup that is NaN, infinite or negative, a range past the channels.  Any thread; applies to the runs
+        submitted after it."""
+        n = None
+        for v in (threshold, makeup, attack, release):
+            if v is not None and np.ndim(v) != 0:
+                m = int(np.size(v))
+                if n is not None and m != n:
+                    raise DspfxError(-1, "dynamics set: the arrays name different numbers of channels")
+                n = m
+        if n is None:
+            n = self.channels - int(first_channel) if count is None else int(count)
+
+        def arr(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
+            return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+        keep = [arr(v) for v in (threshold, makeup, attack, release)]
+        self._chk(self.L.dspfx_dynamics_set(self.h, *[p for _, p in keep], int(first_channel), n))
+
+    def drop(self, first_channel: int = 0, count: Optional[int] = None):
+        """Remove the node of `count` channels from first_channel (default: all from it) and clear their envelope; queued like a
+        store."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        self._chk(self.L.dspfx_dynamics_drop(self.h, int(first_channel), n))
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None):
+        """Envelope and level back to 0 and reduction to 1 on `count` channels from first_channel (default: all from it); the
+        sliders and the nodes stay; queued like a store.  The way out for a channel whose envelope became NaN."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        self._chk(self.L.dspfx_dynamics_reset(self.h, int(first_channel), n))
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        v = np.zeros(max(n, 0), np.uint32)
+        self._chk(self.L.dspfx_dynamics_present(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
+        return v
+
+    def _view(self, addr):
+        import torch
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": (self.channels,), "typestr": "<f4", "data": (addr, False), "version": 2}
+        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+
+    def levels(self):
+        """float32[channels] on the device: every channel's largest envelope of the last block, 0.0 without a node (valid after a
+        run, on its stream)."""
+        return self._view(self._views[0])
+
+    def reductions(self):
+        """float32[channels] on the device: every channel's smallest q of the last block -- 1.0 where it was never turned down."""
+        return self._view(self._views[1])
 
 
 

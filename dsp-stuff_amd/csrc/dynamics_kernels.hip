@@ -1,0 +1,469 @@
+// dynamics_kernels.hip -- the channel-dynamics bank (include/dspfx.h, dspfx_dynamics_*): every channel may carry its own Envelope
+// node (nodes/envelope.rs, a peak follower with its own attack and release sliders) feeding its own gain computer: the envelope
+// turns the gain DOWN above a threshold, and a makeup gain follows.  One bank object is a leveller ahead of the talker bank or a
+// limiter behind the room mixes; the detector may follow another block than the one it turns down (the key).
+//
+// One run is one kernel behind the queued stores, in the shape of talkers_run (talkers_kernels.hip): time is a serial recurrence
+// per channel, so a lane owns its channels for the whole block -- four adjacent channels with one 16-byte load and one nontemporal
+// 16-byte store per frame when the layout allows it (bank_common's load4 / store4 with vec = 1, on the lane's own address), one
+// channel otherwise.  Frames are taken in chunks of F rows and the next chunk's loads are issued ahead of this one's arithmetic,
+// so the chain env -> env does not wait for memory; a keyed run holds two such streams and takes chunks half as long, the same
+// registers.  Per frame: the envelope as K_ENVELOPE computes it (chain_kernels.hip.h), q = env > thr ? thr / env : 1 with one IEEE
+// division, the sample times mk * q, the block's largest envelope into `level` and its smallest q into `reduction`.  The tables are
+// read once and env, level and reduction written once.  A lane rewrites the elements it read, so out may be in.  A channel without
+// a node keeps its sample's bits and its tables at rest.  Nothing is shared between channels: no LDS, no atomics.
+//
+// Stores (sliders, drops, resets) go through the staged-store queue (store_queue.hip.h).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/dspfx.h"
+#include "bank_common.hip.h"
+#include "store_queue.hip.h"
+
+namespace {
+
+constexpr uint32_t WG = 256;
+
+struct DynArgs {
+    const float *in;             // may be `out`: no __restrict__
+    const float *key;            // the keyed form only; may be neither `in` (the host takes that for no key) nor overlap `out`
+    float *out;
+    float *env, *level, *red;    // [N] each
+    const float *ga, *gr, *thr, *mk;             // [N] each
+    const uint8_t *pres;         // [N]: 1 where the channel carries a node
+    uint32_t N, W, nf;
+};
+
+// CPL adjacent values at p (aligned to CPL values) in one load / one store: the four-channel form is what load4 and store4 of
+// bank_common do with vec = 1, on the lane's own address.  (These four helpers are talkers_kernels.hip's; that file is left as it
+// is, so they are not shared yet)
+template <int CPL, typename T>
+__device__ __forceinline__ void loadv(const T *p, T (&o)[CPL]) {
+    typedef T vec __attribute__((ext_vector_type(CPL)));
+    if constexpr (CPL == 1) {
+        o[0] = *p;
+    } else {
+        const vec t = *(const vec *)p;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) o[j] = t[j];
+    }
+}
+
+template <int CPL, bool NT>
+__device__ __forceinline__ void storev(float *p, const float (&o)[CPL]) {
+    typedef float vec __attribute__((ext_vector_type(CPL)));
+    if constexpr (CPL == 1) {
+        if (NT) __builtin_nontemporal_store(o[0], p);
+        else *p = o[0];
+    } else {
+        vec t;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) t[j] = o[j];
+        if (NT) __builtin_nontemporal_store(t, (vec *)p);
+        else *(vec *)p = t;
+    }
+}
+
+// R rows from frame f0 of the lane's channels; `lane` is the lane's element of frame 0 (bank_common's lay(0, c, ..)), a frame
+// further is `rs` elements on in either layout, so no row pays lay()'s division
+template <int CPL, int R>
+__device__ __forceinline__ void load_rows(const float *lane, size_t rs, uint32_t f0, float (&v)[R][CPL]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) loadv<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
+}
+
+template <int CPL, int R>
+__device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) storev<CPL, true>(lane + (size_t)(f0 + i) * rs, v[i]);
+}
+
+// the lane's state over a block
+template <int CPL>
+struct Chan {
+    float env[CPL], ga[CPL], gr[CPL], thr[CPL], mk[CPL], lvl[CPL], red[CPL];
+    bool on[CPL];
+};
+
+// R rows: envelope.rs:34-52 (Detector::next over full_wave) per detector sample k, then the gain computer on the sample x.
+// v holds x and takes the output; k is v itself when there is no key
+template <int CPL, int R>
+__device__ __forceinline__ void dyn_rows(float (&v)[R][CPL], const float (&k)[R][CPL], Chan<CPL> &s) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const float x = v[i][j], kk = k[i][j];
+            const float d = kk < 0.0f ? -kk : kk;
+            const float l = s.env[j];
+            const float gain = l < d ? s.ga[j] : s.gr[j];
+            const float e = __fadd_rn(d, __fmul_rn(__fadd_rn(l, -d), gain));
+            const float q = e > s.thr[j] ? s.thr[j] / e : 1.0f;      // (a NaN envelope compares false)
+            const float y = __fmul_rn(x, __fmul_rn(s.mk[j], q));
+            if (s.on[j]) {
+                s.env[j] = e;
+                if (e > s.lvl[j]) s.lvl[j] = e;      // a NaN or a -0.0 never raises it
+                if (q < s.red[j]) s.red[j] = q;
+                v[i][j] = y;                         // no node: the sample's own bits
+            }
+        }
+    }
+}
+
+template <int CPL, bool KEYED>
+__global__ __launch_bounds__(WG) void dynamics_run(DynArgs a) {
+    constexpr int F = KEYED ? 4 : 8;                       // frame rows per chunk (two chunks of every stream are in registers)
+    const uint64_t c64 = ((uint64_t)blockIdx.x * WG + threadIdx.x) * CPL;
+    if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
+    const uint32_t c = (uint32_t)c64;
+    Chan<CPL> s;
+    uint8_t pres[CPL];
+    loadv<CPL>(a.env + c, s.env);
+    loadv<CPL>(a.ga + c, s.ga);
+    loadv<CPL>(a.gr + c, s.gr);
+    loadv<CPL>(a.thr + c, s.thr);
+    loadv<CPL>(a.mk + c, s.mk);
+    loadv<CPL>(a.pres + c, pres);
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        s.lvl[j] = 0.0f;
+        s.red[j] = 1.0f;
+        s.on[j] = pres[j] != 0;
+    }
+    const size_t lane0 = lay(0, c, a.nf, a.N, a.W), rs = a.W ? a.W : a.N;
+    const float *lin = a.in + lane0, *lkey = KEYED ? a.key + lane0 : nullptr;
+    float *lout = a.out + lane0;
+    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
+    const uint32_t nfull = a.nf / F;
+    float cur[F][CPL], nxt[F][CPL], kcur[KEYED ? F : 1][CPL], knxt[KEYED ? F : 1][CPL];
+    if (nfull) {
+        load_rows<CPL, F>(lin, rs, 0, cur);
+        if constexpr (KEYED) load_rows<CPL, F>(lkey, rs, 0, kcur);
+    }
+#pragma unroll 1
+    for (uint32_t ch = 0; ch < nfull; ++ch) {
+        if (ch + 1 < nfull) {
+            load_rows<CPL, F>(lin, rs, (ch + 1) * F, nxt);
+            if constexpr (KEYED) load_rows<CPL, F>(lkey, rs, (ch + 1) * F, knxt);
+        }
+        if constexpr (KEYED) dyn_rows<CPL, F>(cur, kcur, s);
+        else dyn_rows<CPL, F>(cur, cur, s);
+        store_rows<CPL, F>(lout, rs, ch * F, cur);
+#pragma unroll
+        for (int i = 0; i < F; ++i)
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                cur[i][j] = nxt[i][j];
+                if constexpr (KEYED) kcur[i][j] = knxt[i][j];
+            }
+    }
+#pragma unroll 1
+    for (uint32_t f = nfull * F; f < a.nf; ++f) {
+        float one[1][CPL], kone[1][CPL];
+        load_rows<CPL, 1>(lin, rs, f, one);
+        if constexpr (KEYED) {
+            load_rows<CPL, 1>(lkey, rs, f, kone);
+            dyn_rows<CPL, 1>(one, kone, s);
+        } else {
+            dyn_rows<CPL, 1>(one, one, s);
+        }
+        store_rows<CPL, 1>(lout, rs, f, one);
+    }
+    storev<CPL, false>(a.env + c, s.env);                  // (without a node: what was read, +0.0)
+    storev<CPL, false>(a.level + c, s.lvl);
+    storev<CPL, false>(a.red + c, s.red);
+}
+
+// a reset's and a drop's device side, in stream order, on channels [first, first + count): the state at rest
+__global__ __launch_bounds__(WG) void dynamics_fresh(float *__restrict__ env, float *__restrict__ level, float *__restrict__ red, uint32_t first,
+                                                     uint32_t count) {
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t c = first + i;
+    env[c] = 0.0f;
+    level[c] = 0.0f;
+    red[c] = 1.0f;
+}
+
+thread_local std::string g_err;        // the reason of the last failed create or plan on this thread
+
+enum StoreKind : uint32_t { ST_SLIDERS, ST_DROP, ST_RESET };
+
+// a store's vals: SLIDERS four runs of [count]: attack gains, release gains, thresholds, makeups; DROP and RESET carry none
+struct StoreFields {
+    StoreKind kind = ST_RESET;
+    uint32_t first = 0, count = 0;
+};
+typedef StoreQueue<StoreFields> Stores;
+typedef Stores::Store Store;
+
+// the table bytes of a bank on the device: ga, gr, thr, mk, env, level and reduction (28) and the presence (1) per channel
+uint64_t table_bytes(uint64_t N) { return 29 * N; }
+
+}  // namespace
+
+struct dspfx_dynamics : BankError {
+    dspfx_dynamics_desc desc{};
+    std::mutex mu;                               // run / destroy
+    std::mutex smu;                              // one store at a time: it reads the host tables, then queues
+    Stores stores;                               // its qmu guards the host tables' writes and their readers
+    std::vector<float> hga, hgr, hthr, hmk;      // [N]: the sliders with every store made so far (a NULL slider keeps them)
+    std::vector<uint8_t> hpres;                  // [N]
+    float *env = nullptr, *level = nullptr, *red = nullptr, *ga = nullptr, *gr = nullptr, *thr = nullptr, *mk = nullptr;
+    uint8_t *pres = nullptr;
+    hipEvent_t ev = nullptr;
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+
+namespace {
+
+void release(dspfx_dynamics *p) {
+    (void)hipSetDevice(p->desc.device);
+    for (void *d : {(void *)p->env, (void *)p->level, (void *)p->red, (void *)p->ga, (void *)p->gr, (void *)p->thr, (void *)p->mk, (void *)p->pres})
+        if (d) (void)hipFree(d);
+    p->stores.free_all();
+    if (p->ev) (void)hipEventDestroy(p->ev);
+    delete p;
+}
+
+// one store onto the stream
+hipError_t apply_store(dspfx_dynamics *p, const Store &st, hipStream_t s) {
+    const size_t n = st.count, bytes = n * sizeof(float);
+    hipError_t err = hipSuccess;
+    switch (st.kind) {
+    case ST_SLIDERS: {
+        float *const tabs[4] = {p->ga, p->gr, p->thr, p->mk};
+        for (int t = 0; t < 4 && err == hipSuccess; ++t) err = hipMemcpyAsync(tabs[t] + st.first, st.vals + t * n, bytes, hipMemcpyHostToDevice, s);
+        if (err == hipSuccess) err = hipMemsetAsync(p->pres + st.first, 1, n, s);
+        return err;
+    }
+    case ST_DROP:
+        err = hipMemsetAsync(p->pres + st.first, 0, n, s);
+        if (err != hipSuccess) return err;
+        [[fallthrough]];
+    case ST_RESET:
+        dynamics_fresh<<<(st.count + WG - 1) / WG, WG, 0, s>>>(p->env, p->level, p->red, st.first, st.count);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+int check_range(dspfx_dynamics *p, const char *what, uint64_t first, uint64_t count) {
+    std::string why;
+    const int rc = check_range("dynamics", what, first, count, p->desc.n_channels, why);
+    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
+}
+
+// a store without values over a range
+int store_plain(dspfx_dynamics *p, StoreKind kind, const char *call, uint64_t first, uint64_t count) {
+    const int rc = check_range(p, call, first, count);
+    if (rc != DSPFX_OK) return rc;
+    if (count == 0) return DSPFX_OK;
+    Store st;
+    st.kind = kind;
+    st.first = (uint32_t)first;
+    st.count = (uint32_t)count;
+    std::lock_guard<std::mutex> one(p->smu);
+    p->stores.push(st, [&] {
+        if (kind != ST_DROP) return;
+        for (uint64_t c = first; c < first + count; ++c) {         // a later store meets the defaults again
+            p->hga[c] = p->hgr[c] = 0.0f;
+            p->hthr[c] = p->hmk[c] = 1.0f;
+            p->hpres[c] = 0;
+        }
+    });
+    return DSPFX_OK;
+}
+
+}  // namespace
+
+extern "C" const char *dspfx_dynamics_last_error(const dspfx_dynamics *p) { return p ? p->err.c_str() : g_err.c_str(); }
+
+extern "C" float dspfx_dynamics_gain(float env, float threshold, float makeup, float *q_out) {
+    const float q = env > threshold ? threshold / env : 1.0f;
+    if (q_out) *q_out = q;
+    return makeup * q;
+}
+
+extern "C" int dspfx_dynamics_plan(uint64_t channels, uint64_t *bytes_out) {
+    g_err.clear();
+    const int rc = check_shape("dynamics", channels, 0, g_err);
+    if (rc != DSPFX_OK) return rc;
+    if (bytes_out) *bytes_out = table_bytes(channels);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_dynamics_create(const dspfx_dynamics_desc *desc, dspfx_dynamics **out) {
+    if (!desc || !out) {
+        g_err = "dynamics: null argument";
+        return DSPFX_ERR_INVALID;
+    }
+    *out = nullptr;
+    g_err.clear();
+    if (desc->abi_version != DSPFX_ABI_VERSION || desc->max_frames == 0 || desc->max_frames > (1u << 20)) {
+        g_err = "dynamics: abi_version or max_frames";
+        return DSPFX_ERR_INVALID;
+    }
+    const uint32_t N = desc->n_channels;
+    int rc = check_shape("dynamics", N, desc->tile_channels, g_err);
+    if (rc != DSPFX_OK) return rc;
+    rc = open_device("dynamics", desc->device, &g_err);
+    if (rc != DSPFX_OK) return rc;
+    dspfx_dynamics *p = new (std::nothrow) dspfx_dynamics;
+    if (!p) return DSPFX_ERR_OOM;
+    p->desc = *desc;
+    try {
+        p->hga.assign(N, 0.0f);
+        p->hgr.assign(N, 0.0f);
+        p->hthr.assign(N, 1.0f);
+        p->hmk.assign(N, 1.0f);
+        p->hpres.assign(N, 0);
+    } catch (const std::bad_alloc &) {
+        delete p;
+        return DSPFX_ERR_OOM;
+    }
+    const size_t tab = (size_t)N * sizeof(float);
+    bool ok = hipMalloc((void **)&p->env, tab) == hipSuccess && hipMalloc((void **)&p->level, tab) == hipSuccess &&
+              hipMalloc((void **)&p->red, tab) == hipSuccess && hipMalloc((void **)&p->ga, tab) == hipSuccess &&
+              hipMalloc((void **)&p->gr, tab) == hipSuccess && hipMalloc((void **)&p->thr, tab) == hipSuccess &&
+              hipMalloc((void **)&p->mk, tab) == hipSuccess && hipMalloc((void **)&p->pres, N) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        release(p);
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "dynamics: no device memory for %llu bytes of tables (%u channels)", (unsigned long long)table_bytes(N), N);
+        g_err = buf;
+        return DSPFX_ERR_OOM;
+    }
+    // the fresh state: no node anywhere
+    dynamics_fresh<<<(N + WG - 1) / WG, WG>>>(p->env, p->level, p->red, 0u, N);
+    ok = hipGetLastError() == hipSuccess && hipMemset(p->ga, 0, tab) == hipSuccess && hipMemset(p->gr, 0, tab) == hipSuccess &&
+         hipMemset(p->thr, 0, tab) == hipSuccess && hipMemset(p->mk, 0, tab) == hipSuccess && hipMemset(p->pres, 0, N) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess && hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        release(p);
+        return DSPFX_ERR_HIP;
+    }
+    *out = p;
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_dynamics_destroy(dspfx_dynamics *p) {
+    if (!p) return DSPFX_ERR_INVALID;
+    close_bank(p, release);
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_dynamics_set(dspfx_dynamics *p, const float *host_threshold, const float *host_makeup, const float *host_attack,
+                                  const float *host_release, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    const int rc = check_range(p, "set", first_channel, count);
+    if (rc != DSPFX_OK) return rc;
+    char buf[192];
+    for (uint64_t i = 0; i < count; ++i) {
+        // (a NaN fails every comparison; -0.0 is below +0.0 here: it would turn the sign of every sample it meets)
+        if (host_threshold && (!(host_threshold[i] >= 0.0f) || std::signbit(host_threshold[i]))) {
+            std::snprintf(buf, sizeof buf, "dynamics set: channel %llu is given threshold %g (NaN or below +0.0)", (unsigned long long)(first_channel + i),
+                          (double)host_threshold[i]);
+            return p->fail(DSPFX_ERR_INVALID, buf);
+        }
+        if (host_makeup && (!(host_makeup[i] >= 0.0f) || std::signbit(host_makeup[i]) || std::isinf(host_makeup[i]))) {
+            std::snprintf(buf, sizeof buf, "dynamics set: channel %llu is given makeup %g (NaN, infinite or negative)", (unsigned long long)(first_channel + i),
+                          (double)host_makeup[i]);
+            return p->fail(DSPFX_ERR_INVALID, buf);
+        }
+    }
+    if (count == 0) return DSPFX_OK;
+    Store st;
+    st.kind = ST_SLIDERS;
+    st.first = (uint32_t)first_channel;
+    st.count = (uint32_t)count;
+    std::lock_guard<std::mutex> one(p->smu);
+    if (!p->stores.staging(p->desc.device, 4 * count, st)) return p->fail(DSPFX_ERR_OOM, "dynamics set: no page-locked memory for the staged sliders");
+    float *a = st.vals, *r = a + count, *t = r + count, *m = t + count;
+    for (uint64_t i = 0; i < count; ++i) {
+        a[i] = host_attack ? dspfx_envelope_gain(host_attack[i]) : p->hga[first_channel + i];
+        r[i] = host_release ? dspfx_envelope_gain(host_release[i]) : p->hgr[first_channel + i];
+        t[i] = host_threshold ? host_threshold[i] : p->hthr[first_channel + i];
+        m[i] = host_makeup ? host_makeup[i] : p->hmk[first_channel + i];
+    }
+    p->stores.push(st, [&] {
+        std::memcpy(p->hga.data() + first_channel, a, count * sizeof(float));
+        std::memcpy(p->hgr.data() + first_channel, r, count * sizeof(float));
+        std::memcpy(p->hthr.data() + first_channel, t, count * sizeof(float));
+        std::memcpy(p->hmk.data() + first_channel, m, count * sizeof(float));
+        std::memset(p->hpres.data() + first_channel, 1, count);
+    });
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_dynamics_drop(dspfx_dynamics *p, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    return store_plain(p, ST_DROP, "drop", first_channel, count);
+}
+
+extern "C" int dspfx_dynamics_reset(dspfx_dynamics *p, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    return store_plain(p, ST_RESET, "reset", first_channel, count);
+}
+
+extern "C" int dspfx_dynamics_present(dspfx_dynamics *p, uint32_t *host_present_out, uint64_t first_channel, uint64_t count) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (!host_present_out) return p->fail(DSPFX_ERR_INVALID, "dynamics present: no array");
+    const int rc = check_range(p, "present", first_channel, count);
+    if (rc != DSPFX_OK) return rc;
+    std::lock_guard<std::mutex> lk(p->stores.qmu);
+    for (uint64_t i = 0; i < count; ++i) host_present_out[i] = p->hpres[first_channel + i];
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_dynamics_views(dspfx_dynamics *p, const float **level_out, const float **reduction_out) {
+    if (!p) return DSPFX_ERR_INVALID;
+    if (level_out) *level_out = p->level;
+    if (reduction_out) *reduction_out = p->red;
+    return DSPFX_OK;
+}
+
+extern "C" int dspfx_dynamics_run(dspfx_dynamics *p, const float *in, const float *key, float *out, uint32_t n_frames, void *stream) {
+    if (!p) return DSPFX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "dynamics run: in, out or n_frames");
+    hipStream_t s = (hipStream_t)stream;
+    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
+    BANK_HIP_WHY(order(p, s), "stream order");
+    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "dynamics store");
+    if (key == in) key = nullptr;                // the detector follows the block itself: one stream of loads
+    DynArgs a;
+    a.in = in;
+    a.key = key;
+    a.out = out;
+    a.env = p->env;
+    a.level = p->level;
+    a.red = p->red;
+    a.ga = p->ga;
+    a.gr = p->gr;
+    a.thr = p->thr;
+    a.mk = p->mk;
+    a.pres = p->pres;
+    a.N = p->desc.n_channels;
+    a.W = p->desc.tile_channels;
+    a.nf = n_frames;
+    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
+    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out) | ((uintptr_t)key)) & 15u) == 0;
+    const uint32_t lanes = vec ? a.N / 4 : a.N, blocks = (lanes + WG - 1) / WG;
+    if (vec && key) dynamics_run<4, true><<<blocks, WG, 0, s>>>(a);
+    else if (vec) dynamics_run<4, false><<<blocks, WG, 0, s>>>(a);
+    else if (key) dynamics_run<1, true><<<blocks, WG, 0, s>>>(a);
+    else dynamics_run<1, false><<<blocks, WG, 0, s>>>(a);
+    BANK_HIP_WHY(hipGetLastError(), "dynamics_run");
+    return DSPFX_OK;
+}

@@ -203,6 +203,23 @@ pub struct dspfx_talkers_desc {
     pub group_start: *const u64,
 }
 
+/// Opaque channel-dynamics bank handle (`typedef struct dspfx_dynamics dspfx_dynamics`).
+#[repr(C)]
+pub struct dspfx_dynamics {
+    _private: [u8; 0],
+}
+
+/// The channel-dynamics bank's descriptor (`dspfx_dynamics_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_dynamics_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+}
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -524,6 +541,18 @@ extern "C" {
     pub fn dspfx_talkers_counts(t: *mut dspfx_talkers, host_counts_out: *mut u32) -> c_int;
     pub fn dspfx_talkers_audible(gate: *const f32, target: *const f32, room_of: *const u32, n_channels: u64, n_groups: u32, list_out: *mut i32, start_out: *mut u32, count_out: *mut u32) -> c_int;
     pub fn dspfx_talkers_audible_views(t: *mut dspfx_talkers, list_out: *mut *const i32, start_out: *mut *const u32, count_out: *mut *const u32) -> c_int;
+
+    pub fn dspfx_dynamics_plan(channels: u64, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_dynamics_gain(env: f32, threshold: f32, makeup: f32, q_out: *mut f32) -> f32;
+    pub fn dspfx_dynamics_create(desc: *const dspfx_dynamics_desc, out: *mut *mut dspfx_dynamics) -> c_int;
+    pub fn dspfx_dynamics_destroy(d: *mut dspfx_dynamics) -> c_int;
+    pub fn dspfx_dynamics_last_error(d: *const dspfx_dynamics) -> *const c_char;
+    pub fn dspfx_dynamics_run(d: *mut dspfx_dynamics, input: *const f32, key: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_dynamics_set(d: *mut dspfx_dynamics, host_threshold: *const f32, host_makeup: *const f32, host_attack: *const f32, host_release: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_dynamics_drop(d: *mut dspfx_dynamics, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_dynamics_reset(d: *mut dspfx_dynamics, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_dynamics_present(d: *mut dspfx_dynamics, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_dynamics_views(d: *mut dspfx_dynamics, level_out: *mut *const f32, reduction_out: *mut *const f32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

@@ -9,4 +9,5 @@ pub mod convolver_responses;
 pub mod channel_strips;
 pub mod channel_delays;
 pub mod talkers;
+pub mod channel_dynamics;
 pub mod mix_matrix;

@@ -1313,6 +1313,98 @@ int dspfx_talkers_audible(const float *gate, const float *target, const uint32_t
  * what dspfx_mixmatrix_run_sparse takes. */
 int dspfx_talkers_audible_views(dspfx_talkers *t, const int32_t **list_out, const uint32_t **start_out, const uint32_t **count_out);
 
+/* ---- channel dynamics: a bank of per-channel levellers and limiters --------------------------------------------------
+ * The talker bank uses the reference's "an Envelope into a Gain" as a gate.  This bank is the ordinary use, where the envelope
+ * turns the gain DOWN: channel c may carry its own Envelope node (nodes/envelope.rs) feeding its own gain computer, over N
+ * channels in the desc's layout (tile_channels as dspfx_engine_desc).  One bank object serves two places of the room pipeline: a
+ * LEVELLER ahead of dspfx_talkers_run, so that the ranking is not by microphone gain, and a LIMITER behind the room mixes, ahead of
+ * the resampler and the PCM conversion, which hard-clip.
+ * A node EXISTS for a channel from the first dspfx_dynamics_set that names it until dspfx_dynamics_drop; a fresh bank has no node
+ * anywhere and run copies in to out bit for bit.
+ * PER CHANNEL.  State: env (f32, starts +0.0).  Sliders: attack and release in frames, taken as given (no clamp) and converted on
+ * the host by dspfx_envelope_gain into ga and gr; threshold thr and makeup mk.  A slider the first store leaves out starts at 0,
+ * 0, 1.0 and 1.0.
+ * ONE RUN: queued stores go onto the stream in the order they were made, then per channel that carries a node, frames in order,
+ * nothing contracted:
+ *       k   = key ? key[f][c] : in[f][c]
+ *       d   = k < 0 ? -k : k
+ *       g   = env < d ? ga : gr
+ *       env = d + (env + (-d)) * g                 the engine's Envelope node, bit for bit (a NaN where it has a NaN)
+ *       q   = env > thr ? thr / env : 1.0f         one IEEE f32 division
+ *       out[f][c] = in[f][c] * (mk * q)            two f32 multiplications
+ *       level[c]     = env > level ? env : level   starts +0.0 every run: never NaN, never negative
+ *       reduction[c] = q < reduction ? q : reduction     starts 1.0 every run
+ * One curve covers both uses.  A limiter is mk = 1, thr = the ceiling, attack 0.  A leveller that brings everybody towards
+ * `target` with a gain of at most `max_gain` is thr = target / max_gain, mk = max_gain.  A ratio or a knee needs powf on the
+ * device, whose bits nothing pins: there is none.
+ * WHAT FOLLOWS.
+ *   - A channel without a node is copied bit for bit; its level is +0.0 and its reduction 1.0.
+ *   - A channel that never exceeds its threshold gets in * (mk * 1.0f): the bits of the engine's Gain(mk) node; with mk = 1 a copy.
+ *   - The gain is a multiplication, not an omission: a NaN sample stays a NaN.
+ *   - A NaN envelope compares false, so q = 1; as in the reference it stays NaN until dspfx_dynamics_reset.
+ *   - BRICK WALL: with attack 0 (ga = 0), no key, finite input, release >= 0 and thr * mk in the normal range, env >= |in| on every
+ *     frame (env is |in| exactly when it rises, and a release step rounds a value between |in| and the old env, monotonically),
+ *     so |out| <= thr * mk * (1 + 2^-24)^3: three roundings, the division and the two multiplications.  On a numpy model over noise
+ *     of amplitude 1e-3 .. 4, thresholds 0.001 .. 1, makeups 0.7 .. 3 and releases 0 .. 24000 the worst excess over thr * mk was
+ *     1.95 x 2^-24.  With attack ABOVE 0 there is NO such bound: the envelope lags the signal, and the model overshoots 4-fold on
+ *     the first samples at attack 48.  With a key there is none either: the envelope is the key's.
+ * THE KEY.  key, a block of the same shape, is what the detector follows while the gain is applied to in: the reference's Envelope
+ * of one signal into the Gain slider of another, turned downward (music ducked under an announcer; a detector ahead of an EQ).
+ * key == in gives the bits of no key (and is run as no key); key == NULL is no key.
+ * A channel's output and tables are the same bits in either layout, in place or not, on any stream, and whatever its neighbours
+ * carry.  No atomics, no LDS.
+ * Memory: 29 bytes per channel of tables on the device (ga, gr, thr, mk, env, level, reduction and the presence byte;
+ * dspfx_dynamics_plan), 17 per channel on the host. */
+typedef struct dspfx_dynamics dspfx_dynamics;
+typedef struct dspfx_dynamics_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+} dspfx_dynamics_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, 29 * channels.  channels of 0 or above
+ * 2^32 - 256: DSPFX_ERR_INVALID, the reason in dspfx_dynamics_last_error(NULL). */
+int dspfx_dynamics_plan(uint64_t channels, uint64_t *bytes_out);
+/* PURE HOST function: the gain computer's rule on one envelope value.  q = env > threshold ? threshold / env : 1.0f goes to *q_out
+ * (which may be NULL) and makeup * q is returned: the factor the device multiplies the sample by, bit for bit.  No check is made. */
+float dspfx_dynamics_gain(float env, float threshold, float makeup, float *q_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0) is DSPFX_ERR_INVALID with the reason in dspfx_dynamics_last_error of a NULL bank (kept per thread); all of that
+ * is checked before any device work. */
+int dspfx_dynamics_create(const dspfx_dynamics_desc *desc, dspfx_dynamics **out);
+int dspfx_dynamics_destroy(dspfx_dynamics *d);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_dynamics_last_error(const dspfx_dynamics *d);
+/* in, key, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames); key may be NULL.  out == in
+ * works in place, with or without a key (a thread rewrites the elements it read); key overlapping out while key != in, and any
+ * other overlap, is the caller's error.  Asynchronous on `stream`; a run on another stream than the one before first waits (on the
+ * device) for that one, since the state is the bank's (the rules of dspfx_strips_run).  Queued stores go onto the stream ahead of
+ * the kernel, in the order they were made. */
+int dspfx_dynamics_run(dspfx_dynamics *d, const float *in, const float *key, float *out, uint32_t n_frames, void *stream);
+/* Stores the sliders of channels [first_channel, first_channel + count) from host arrays of `count` values each, and gives every
+ * channel of the range its node.  Any of the four may be NULL, which keeps each channel's value (the defaults for a channel never
+ * stored, or dropped since); all four NULL only makes the nodes.  The store touches no envelope: the reference's slider change sets
+ * only the gain.  Refused WHOLE, DSPFX_ERR_INVALID with the reason in dspfx_dynamics_last_error and nothing stored: a threshold
+ * that is NaN or below +0.0 (-0.0 included: it would turn the sign of every sample above it), a makeup that is NaN, infinite or
+ * negative (-0.0 included), a range past the channels.  A threshold of +infinity is a channel that is never turned down.  The
+ * contract of dspfx_strips_set_gain otherwise: callable from any thread while runs are in flight, never waits for the device or for
+ * a run; the values are staged in page-locked memory and queued, and a run submitted after the call returns sees the store, whole,
+ * the runs submitted before it do not. */
+int dspfx_dynamics_set(dspfx_dynamics *d, const float *host_threshold, const float *host_makeup, const float *host_attack,
+                       const float *host_release, uint64_t first_channel, uint64_t count);
+/* Removes the node of channels [first_channel, first_channel + count) and clears their envelope; a later store starts from the
+ * default sliders and a zero envelope.  Queued like a store.  A range past the channels: DSPFX_ERR_INVALID and the reason. */
+int dspfx_dynamics_drop(dspfx_dynamics *d, uint64_t first_channel, uint64_t count);
+/* env and level back to +0.0 and reduction to 1.0 on the range; the sliders and the nodes stay.  Queued like a store.  Also the way
+ * out for a channel whose envelope became NaN. */
+int dspfx_dynamics_reset(dspfx_dynamics *d, uint64_t first_channel, uint64_t count);
+/* 1 / 0 per channel of [first_channel, first_channel + count): it carries a node, as all stores made so far left it (host tables). */
+int dspfx_dynamics_present(dspfx_dynamics *d, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+/* The device pointers of level[N] and reduction[N] (each out pointer may be NULL).  The pointers never change; what they hold is
+ * valid after a run, on its stream. */
+int dspfx_dynamics_views(dspfx_dynamics *d, const float **level_out, const float **reduction_out);
+
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
  * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain

@@ -706,6 +706,76 @@ inline std::uint64_t talkers_plan(std::uint64_t channels, std::uint32_t groups) 
     return bytes;
 }
 
+// Per-channel levellers and limiters (include/dspfx.h, dspfx_dynamics_*): channel c may carry its own Envelope node (attack and
+// release in frames) feeding its own gain computer, q = env > threshold ? threshold / env : 1, out = in * (makeup * q), over a
+// device block in the layout of tile_channels.  A node exists for a channel from the first set() that names it until drop(); a
+// fresh bank copies its input.  A limiter: threshold = the ceiling, makeup 1, attack 0 (a brick wall).  A leveller towards `target`
+// with at most `max_gain`: threshold = target / max_gain, makeup = max_gain.  Ahead of Talkers as a leveller, behind the room mixes
+// as a limiter.
+class ChannelDynamics {
+  public:
+    struct Views {
+        const float *level;            // [N]: the block's largest envelope, 0 without a node
+        const float *reduction;        // [N]: the block's smallest q, 1 where the channel was never turned down
+    };
+    ChannelDynamics(std::uint32_t channels, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE, int device = 0) {
+        const dspfx_dynamics_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels};
+        const int rc = dspfx_dynamics_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_dynamics_last_error(nullptr) ? dspfx_dynamics_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelDynamics() { dspfx_dynamics_destroy(p_); }
+    ChannelDynamics(const ChannelDynamics &) = delete;
+    ChannelDynamics &operator=(const ChannelDynamics &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place); key, a device block of the same shape or
+    // nullptr, is what the detector follows instead of `in`; asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, const float *key = nullptr, void *stream = nullptr) {
+        chk(dspfx_dynamics_run(p_, in, key, out, n_frames, stream));
+    }
+    // the sliders of channels [first_channel, first_channel + count) from host arrays, and a node for each of them; a nullptr slider
+    // keeps each channel's value.  No envelope is touched.  Refused whole on a threshold that is NaN or below +0.0 or a makeup that is
+    // NaN, infinite or negative.  Any thread; never waits
+    void set(const float *host_threshold, const float *host_makeup, const float *host_attack, const float *host_release, std::uint64_t first_channel,
+             std::uint64_t count) {
+        chk(dspfx_dynamics_set(p_, host_threshold, host_makeup, host_attack, host_release, first_channel, count));
+    }
+    // the node removed and its envelope cleared; queued like a store
+    void drop(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_dynamics_drop(p_, first_channel, count)); }
+    // envelope and level back to 0 and reduction to 1 on the range, the sliders and the nodes kept; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_dynamics_reset(p_, first_channel, count)); }
+    // 1 / 0 per channel: it carries a node, as all stores so far left it
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_dynamics_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    // the device tables: valid after a run, on its stream
+    Views views() {
+        Views v{nullptr, nullptr};
+        chk(dspfx_dynamics_views(p_, &v.level, &v.reduction));
+        return v;
+    }
+    dspfx_dynamics *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_dynamics_last_error(p_) ? dspfx_dynamics_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_dynamics *p_ = nullptr;
+};
+
+// The device bytes of a ChannelDynamics bank's tables (dspfx_dynamics_plan: a pure host function, no GPU).
+inline std::uint64_t dynamics_plan(std::uint64_t channels) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_dynamics_plan(channels, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_dynamics_last_error(nullptr));
+    return bytes;
+}
+
+// makeup * q, the factor a ChannelDynamics run multiplies the sample by for this envelope value (dspfx_dynamics_gain: a pure host function).
+inline float dynamics_gain(float env, float threshold, float makeup = 1.0f, float *q_out = nullptr) {
+    return dspfx_dynamics_gain(env, threshold, makeup, q_out);
+}
+
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
