@@ -59,6 +59,7 @@ MIXMATRIX_MIX_MINUS, MIXMATRIX_ZERO = 0, 1      # DSPFX_MIXMATRIX_*: MixMatrix.f
 MIXMATRIX_DIRECT, MIXMATRIX_STAGED = 0, 1       # DSPFX_MIXMATRIX_*: MixMatrix.set_staging modes
 TALKERS_MAX_ROOM, TALKERS_MAX_TOP = 1024, 8     # DSPFX_TALKERS_*: the most members a Talkers room has, the most talkers it names
 TALKERS_AUTO, TALKERS_OPEN, TALKERS_SHUT = 0, 1, 2      # DSPFX_TALKERS_*: Talkers.set_pin
+SHAPERS_NONE = 0xFFFFFFFF       # DSPFX_SHAPERS_NONE: ChannelShapers.kinds() without a node, .modes() without a Distort node
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -102,6 +103,9 @@ EXPORTS = [
     "dspfx_dynamics_plan", "dspfx_dynamics_gain", "dspfx_dynamics_create", "dspfx_dynamics_destroy", "dspfx_dynamics_last_error",
     "dspfx_dynamics_run", "dspfx_dynamics_set", "dspfx_dynamics_drop", "dspfx_dynamics_reset", "dspfx_dynamics_present",
     "dspfx_dynamics_views",
+    "dspfx_shapers_plan", "dspfx_shapers_create", "dspfx_shapers_destroy", "dspfx_shapers_last_error", "dspfx_shapers_run",
+    "dspfx_shapers_set_distort", "dspfx_shapers_set_overdrive", "dspfx_shapers_set_chebyshev", "dspfx_shapers_drop",
+    "dspfx_shapers_present", "dspfx_shapers_kinds", "dspfx_shapers_modes", "dspfx_shapers_sliders",
 ]
 COMM_ID_BYTES = 128
 
@@ -186,6 +190,11 @@ class _TalkersDesc(C.Structure):
 
 
 class _DynamicsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32)]
+
+
+class _ShapersDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32)]
 
@@ -421,6 +430,19 @@ def lib():
     L.dspfx_dynamics_reset.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.dspfx_dynamics_present.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_dynamics_views.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.dspfx_shapers_plan.argtypes = [C.c_uint64, C.POINTER(C.c_uint64)]
+    L.dspfx_shapers_create.argtypes = [C.POINTER(_ShapersDesc), C.POINTER(vp)]
+    L.dspfx_shapers_destroy.argtypes = [vp]
+    L.dspfx_shapers_last_error.restype = C.c_char_p
+    L.dspfx_shapers_last_error.argtypes = [vp]
+    L.dspfx_shapers_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_shapers_set_distort.argtypes = [vp, fp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_shapers_set_overdrive.argtypes = [vp, fp, fp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_shapers_set_chebyshev.argtypes = [vp, fp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_shapers_drop.argtypes = [vp, C.c_uint64, C.c_uint64]
+    for name in ("present", "kinds", "modes"):
+        getattr(L, f"dspfx_shapers_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_shapers_sliders.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2045,6 +2067,119 @@ class ChannelDynamics(_Bank):
         """float32[channels] on the device: every channel's smallest q of the last block -- 1.0 where it was never turned down."""
         return self._view(self._views[1])
 
+
+def shapers_plan(channels: int) -> int:
+    """dspfx_shapers_plan, a pure host function (no GPU): the device bytes of a ChannelShapers bank's tables, 13 per channel."""
+    L = lib()
+    n = C.c_uint64()
+    rc = L.dspfx_shapers_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
+    _raise(L, "shapers", rc)
+    return int(n.value)
+
+
+class ChannelShapers(_Bank):
+    """Per-channel waveshapers (include/dspfx.h, dspfx_shapers_*): channel c may carry one node of its own -- Distort with its own
+    level and mode, Overdrive or Chebyshev with their own sliders -- over a device block in the layout of `tile_channels` (as
+    Engine's).  A node exists for a channel from the first `set_*` that names it until `drop`; a fresh bank copies its input.  A
+    channel's output is bit for bit what Engine([that node], link_flags=0) writes for it.  A `set_*` of another family than the
+    channel carries replaces its node, which starts from the reference's defaults (every slider 0, mode SOFT_CLIP) for what the
+    call leaves None; a `set_*` of the same family keeps what it leaves None.  While a channel carries FUZZ, which is block-global
+    over 128 frames, n_frames must be a multiple of 128.  Several shapers per channel are several banks.  Asynchronous on
+    `stream`."""
+
+    _C = "shapers"
+    _WHY = True
+
+    def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+        d = _ShapersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
+        self._create(d)
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every channel's shaper -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        import torch
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.dspfx_shapers_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        return out
+
+    def _store(self, call, values, modes, first_channel, count):
+        n = None
+        for v in tuple(values) + (modes,):
+            if v is not None and np.ndim(v) != 0:
+                m = int(np.size(v))
+                if n is not None and m != n:
+                    raise DspfxError(-1, f"shapers {call}: the arrays name different numbers of channels")
+                n = m
+        if n is None:
+            n = self.channels - int(first_channel) if count is None else int(count)
+        keep = []                                               # the arrays live until the call returns
+        args = []
+        for v in values:
+            if v is None:
+                args.append(None)
+                continue
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
+            keep.append(a)
+            args.append(a.ctypes.data_as(C.POINTER(C.c_float)))
+        if call == "set_distort":
+            if modes is None:
+                args.append(None)
+            else:
+                m = np.asarray(modes)
+                if m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF)):
+                    raise DspfxError(-1, "shapers set_distort: a mode is one of the DSPFX_DIST_* values")
+                m = np.ascontiguousarray(np.broadcast_to(m.reshape(-1), (max(n, 0),)), np.uint32)
+                keep.append(m)
+                args.append(m.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self._chk(getattr(self.L, f"dspfx_shapers_{call}")(self.h, *args, int(first_channel), n))
+
+    def set_distort(self, level=None, mode=None, first_channel: int = 0, count: Optional[int] = None):
+        """Give channels from first_channel a Distort node: `level` and `mode` (HARD_CLIP .. CHEBYSHEV4) are arrays (one value per
+        channel) or scalars for `count` channels (default: all from first_channel).  None keeps a Distort channel's value and is
+        the default (0, SOFT_CLIP) where the channel carries another node or none.  Values are taken as given (no clamp).  An
+        unknown mode or a range past the channels refuses the whole store.  Any thread; applies to the runs submitted after it."""
+        self._store("set_distort", (level,), mode, first_channel, count)
+
+    def set_overdrive(self, boost=None, drive=None, level=None, first_channel: int = 0, count: Optional[int] = None):
+        """... an Overdrive node (sliders boost, drive, level; the defaults are 0).  Rules as set_distort."""
+        self._store("set_overdrive", (boost, drive, level), None, first_channel, count)
+
+    def set_chebyshev(self, level_pos=None, level_neg=None, first_channel: int = 0, count: Optional[int] = None):
+        """... a Chebyshev node (sliders level_pos, level_neg; the defaults are 0).  Rules as set_distort."""
+        self._store("set_chebyshev", (level_pos, level_neg), None, first_channel, count)
+
+    def drop(self, first_channel: int = 0, count: Optional[int] = None):
+        """Remove the node of `count` channels from first_channel (default: all from it): a copy again; queued like a store."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        self._chk(self.L.dspfx_shapers_drop(self.h, int(first_channel), n))
+
+    def _table(self, name, first_channel, count, dtype=np.uint32, per=1):
+        n = self.channels - int(first_channel) if count is None else int(count)
+        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
+        ct = C.c_float if dtype == np.float32 else C.c_uint32
+        self._chk(getattr(self.L, f"dspfx_shapers_{name}")(self.h, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
+        return v
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
+        return self._table("present", first_channel, count)
+
+    def kinds(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: DISTORT, OVERDRIVE, CHEBYSHEV, or SHAPERS_NONE without a node."""
+        return self._table("kinds", first_channel, count)
+
+    def modes(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: a Distort node's mode, SHAPERS_NONE for every other channel."""
+        return self._table("modes", first_channel, count)
+
+    def sliders(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """float32[count, 3]: the sliders in the order of the node's constructor, 0 where there are fewer and without a node."""
+        return self._table("sliders", first_channel, count, np.float32, 3)
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

@@ -220,6 +220,26 @@ pub struct dspfx_dynamics_desc {
     pub tile_channels: u32,
 }
 
+/// Opaque channel-shaper bank handle (`typedef struct dspfx_shapers dspfx_shapers`).
+#[repr(C)]
+pub struct dspfx_shapers {
+    _private: [u8; 0],
+}
+
+/// The channel-shaper bank's descriptor (`dspfx_shapers_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_shapers_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+}
+
+/// `dspfx_shapers_kinds`: the channel carries no node; `dspfx_shapers_modes`: it carries no Distort node.
+pub const DSPFX_SHAPERS_NONE: u32 = 0xFFFF_FFFF;
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -553,6 +573,20 @@ extern "C" {
     pub fn dspfx_dynamics_reset(d: *mut dspfx_dynamics, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_dynamics_present(d: *mut dspfx_dynamics, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_dynamics_views(d: *mut dspfx_dynamics, level_out: *mut *const f32, reduction_out: *mut *const f32) -> c_int;
+
+    pub fn dspfx_shapers_plan(channels: u64, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_shapers_create(desc: *const dspfx_shapers_desc, out: *mut *mut dspfx_shapers) -> c_int;
+    pub fn dspfx_shapers_destroy(s: *mut dspfx_shapers) -> c_int;
+    pub fn dspfx_shapers_last_error(s: *const dspfx_shapers) -> *const c_char;
+    pub fn dspfx_shapers_run(s: *mut dspfx_shapers, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_shapers_set_distort(s: *mut dspfx_shapers, host_level: *const f32, host_mode: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_set_overdrive(s: *mut dspfx_shapers, host_boost: *const f32, host_drive: *const f32, host_level: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_set_chebyshev(s: *mut dspfx_shapers, host_level_pos: *const f32, host_level_neg: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_drop(s: *mut dspfx_shapers, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_present(s: *mut dspfx_shapers, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_kinds(s: *mut dspfx_shapers, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_modes(s: *mut dspfx_shapers, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_shapers_sliders(s: *mut dspfx_shapers, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

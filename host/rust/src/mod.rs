@@ -10,4 +10,5 @@ pub mod channel_strips;
 pub mod channel_delays;
 pub mod talkers;
 pub mod channel_dynamics;
+pub mod channel_shapers;
 pub mod mix_matrix;

@@ -1405,6 +1405,93 @@ int dspfx_dynamics_present(dspfx_dynamics *d, uint32_t *host_present_out, uint64
  * valid after a run, on its stream. */
 int dspfx_dynamics_views(dspfx_dynamics *d, const float **level_out, const float **reduction_out);
 
+/* ---- channel shapers: a bank of per-channel Distort, Overdrive and Chebyshev -----------------------------------------
+ * An engine runs one chain with one set of slider values for all N channels; in the reference every graph owns its own node
+ * instances, sliders and mode combo box.  This bank is that for the waveshapers: channel c may carry ONE waveshaper node of its
+ * own -- Distort with its nine modes (nodes/distort.rs), Overdrive (nodes/overdrive.rs) or Chebyshev (nodes/chebyshev.rs) -- over N
+ * channels in the desc's layout (tile_channels as dspfx_engine_desc).  Several shapers per channel are several banks.
+ * A node EXISTS for a channel from the first store that names it until dspfx_shapers_drop; a fresh bank has no node anywhere and
+ * run copies in to out bit for bit.  The shapers have no state, so there is no reset.
+ * PER CHANNEL.  A kind (DSPFX_DISTORT, DSPFX_OVERDRIVE, DSPFX_CHEBYSHEV, or none), a mode (a DSPFX_DIST_* value, Distort only)
+ * and up to three sliders in the order of dspfx_node_desc.params: Distort level | Overdrive boost, drive, level | Chebyshev
+ * level_pos, level_neg.  Values are taken as given, as dspfx_set_param takes them: no clamp, NaN included.
+ * STORES.  A dspfx_shapers_set_* of a family the channel does not carry REPLACES its node: the sliders (and the mode) the call
+ * leaves out start from the reference's defaults (dspfx_node_defaults: every slider 0, mode SoftClip).  A set_* of the family it
+ * already carries keeps the sliders (and the mode) left out.  An unknown mode or a range past the channels refuses the WHOLE
+ * store: DSPFX_ERR_INVALID, the reason in dspfx_shapers_last_error, nothing stored.
+ * ONE RUN: queued stores go onto the stream in the order they were made, then per channel:
+ *   - out[f][c] is bit for bit what an engine whose chain is that one node, with link_flags = 0, writes for the channel.  The
+ *     bank calls the engine's own device functions; where the engine divides by a slider through its fast constant division,
+ *     which is exact wherever the engine uses it, the bank divides per lane in IEEE f32: the same bits.
+ *   - The bypasses are the reference's: Distort (every mode but Fuzz) and Overdrive give the sample's own bits when level < 0.001
+ *     (which a NaN level is not); Chebyshev bypasses per branch (level_pos < 0.001 for samples >= 0, level_neg < 0.001 for the
+ *     others, a NaN sample among them).  Its two tanh(level) denominators are computed per channel on the device, once per run.
+ *   - A channel without a node keeps its sample's bits.
+ * FUZZ (distort.rs:146-172) is block-global over the reference's blocks of 128 frames: three maxima over the channel's block, no
+ * bypass, an all-zero block gives NaN.  It runs as a second kernel, in place on out behind the first, launched only when a
+ * channel carries Fuzz, with the arithmetic and the order of the engine's Fuzz kernel.  While any channel carries Fuzz a run whose
+ * n_frames is not a multiple of DSPFX_BUF_SIZE is refused, as the engine refuses it (DSPFX_ERR_INVALID, the reason; the queued
+ * stores have gone onto the stream, nothing else is launched); a bank with no Fuzz channel takes any n_frames up to max_frames.
+ * Both decisions go by the stores the run has drained, not by the stores made so far: a drop made on another thread while a run
+ * is being submitted cannot take the Fuzz pass away from a run whose tables still hold Fuzz.
+ * The first kernel has the shape of the dynamics bank's: a lane owns four adjacent channels (one when the layout or the alignment
+ * forbids it), frames go in chunks with the next chunk's loads issued ahead of the arithmetic, stores are nontemporal.  The kinds
+ * differ per lane, so a wave ballots once per run for the kinds its lanes carry and runs, per chunk, the body of each kind that
+ * is present, wave-uniformly, keeping each result under a select: a wave of 256 channels of one kind pays for one body, a wave
+ * that carries all of them for their sum, a wave of copies for none.  The kernel exists twice: without the bodies that evaluate
+ * in f64 (Tanh, Sin, Atan, Overdrive, Chebyshev), whose constants cost 85 registers, for tables that hold no such kind, and with.
+ * A channel's output is the same bits in either layout, in place or not, on any stream, and whatever its neighbours carry.  No
+ * atomics; LDS only in the Fuzz kernel (3 KiB).
+ * Not here: control-port modulation of the sliders and link hops, which stay with the engine.
+ * Memory: 13 bytes per channel of tables on the device (three sliders and a kind byte; dspfx_shapers_plan), 14 on the host. */
+/* dspfx_shapers_kinds: the channel carries no node; dspfx_shapers_modes: it carries no Distort node */
+#define DSPFX_SHAPERS_NONE 0xFFFFFFFFu
+typedef struct dspfx_shapers dspfx_shapers;
+typedef struct dspfx_shapers_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+} dspfx_shapers_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, 13 * channels.  channels of 0 or above
+ * 2^32 - 256: DSPFX_ERR_INVALID, the reason in dspfx_shapers_last_error(NULL). */
+int dspfx_shapers_plan(uint64_t channels, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0) is DSPFX_ERR_INVALID with the reason in dspfx_shapers_last_error of a NULL bank (kept per thread); all of that
+ * is checked before any device work. */
+int dspfx_shapers_create(const dspfx_shapers_desc *desc, dspfx_shapers **out);
+int dspfx_shapers_destroy(dspfx_shapers *s);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_shapers_last_error(const dspfx_shapers *s);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames, a multiple of DSPFX_BUF_SIZE while
+ * a channel carries Fuzz).  out == in works in place (a thread rewrites the elements it read); any other overlap is the caller's
+ * error.  Asynchronous on `stream`; a run on another stream than the one before first waits (on the device) for that one (the
+ * rules of dspfx_strips_run).  Queued stores go onto the stream ahead of the kernels, in the order they were made. */
+int dspfx_shapers_run(dspfx_shapers *s, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Gives channels [first_channel, first_channel + count) a Distort node, from host arrays of `count` values each: the level
+ * sliders and the modes (DSPFX_DIST_*).  Either may be NULL: kept where the channel carries a Distort node, the default (level 0,
+ * SoftClip) where it carries another node or none.  The contract of dspfx_dynamics_set: callable from any thread while runs are in
+ * flight, never waits for the device or for a run; the values are staged in page-locked memory and queued, each store is whole,
+ * and a run submitted after the call returns sees it, the runs submitted before it do not. */
+int dspfx_shapers_set_distort(dspfx_shapers *s, const float *host_level, const uint32_t *host_mode, uint64_t first_channel, uint64_t count);
+/* ... an Overdrive node: boost, drive, level (each may be NULL; the defaults are 0).  Rules as dspfx_shapers_set_distort. */
+int dspfx_shapers_set_overdrive(dspfx_shapers *s, const float *host_boost, const float *host_drive, const float *host_level, uint64_t first_channel,
+                                uint64_t count);
+/* ... a Chebyshev node: level_pos, level_neg (each may be NULL; the defaults are 0).  Rules as dspfx_shapers_set_distort. */
+int dspfx_shapers_set_chebyshev(dspfx_shapers *s, const float *host_level_pos, const float *host_level_neg, uint64_t first_channel, uint64_t count);
+/* Removes the node of channels [first_channel, first_channel + count): a copy again, and a later store starts from the defaults.
+ * Queued like a store.  A range past the channels: DSPFX_ERR_INVALID and the reason. */
+int dspfx_shapers_drop(dspfx_shapers *s, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: present 1 / 0 (the channel
+ * carries a node); kinds DSPFX_DISTORT, DSPFX_OVERDRIVE, DSPFX_CHEBYSHEV or DSPFX_SHAPERS_NONE; modes the DSPFX_DIST_* value of a
+ * Distort node, DSPFX_SHAPERS_NONE for every other channel; sliders [count][3] in the order of dspfx_node_desc.params, 0 where the
+ * node has fewer than three and where there is no node. */
+int dspfx_shapers_present(dspfx_shapers *s, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_shapers_kinds(dspfx_shapers *s, uint32_t *host_kinds_out, uint64_t first_channel, uint64_t count);
+int dspfx_shapers_modes(dspfx_shapers *s, uint32_t *host_modes_out, uint64_t first_channel, uint64_t count);
+int dspfx_shapers_sliders(dspfx_shapers *s, float *host_sliders_out, uint64_t first_channel, uint64_t count);
+
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
  * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain

@@ -776,6 +776,76 @@ inline float dynamics_gain(float env, float threshold, float makeup = 1.0f, floa
     return dspfx_dynamics_gain(env, threshold, makeup, q_out);
 }
 
+// Per-channel waveshapers (include/dspfx.h, dspfx_shapers_*): channel c may carry one node of its own -- Distort with its own level
+// and mode (Fuzz included), Overdrive or Chebyshev with their own sliders -- over a device block in the layout of tile_channels; its
+// output is bit for bit what an engine whose chain is that node writes for it.  A node exists for a channel from the first set_*()
+// that names it until drop(); a fresh bank copies its input.  A set_*() of another family than the channel carries replaces its
+// node from the reference's defaults; one of the same family keeps the sliders passed as nullptr.  While a channel carries Fuzz,
+// n_frames must be a multiple of DSPFX_BUF_SIZE.  Several shapers per channel are several banks.
+class ChannelShapers {
+  public:
+    ChannelShapers(std::uint32_t channels, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE, int device = 0) {
+        const dspfx_shapers_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels};
+        const int rc = dspfx_shapers_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_shapers_last_error(nullptr) ? dspfx_shapers_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelShapers() { dspfx_shapers_destroy(p_); }
+    ChannelShapers(const ChannelShapers &) = delete;
+    ChannelShapers &operator=(const ChannelShapers &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_shapers_run(p_, in, out, n_frames, stream)); }
+    // a node for each of channels [first_channel, first_channel + count) from host arrays; an unknown mode refuses the whole store.
+    // Any thread; never waits
+    void set_distort(const float *host_level, const std::uint32_t *host_mode, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_shapers_set_distort(p_, host_level, host_mode, first_channel, count));
+    }
+    void set_overdrive(const float *host_boost, const float *host_drive, const float *host_level, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_shapers_set_overdrive(p_, host_boost, host_drive, host_level, first_channel, count));
+    }
+    void set_chebyshev(const float *host_level_pos, const float *host_level_neg, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_shapers_set_chebyshev(p_, host_level_pos, host_level_neg, first_channel, count));
+    }
+    // the node removed: a copy again; queued like a store
+    void drop(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_shapers_drop(p_, first_channel, count)); }
+    // the host tables, as all stores so far left them: 1 / 0; DSPFX_DISTORT .. or DSPFX_SHAPERS_NONE; a Distort node's mode or
+    // DSPFX_SHAPERS_NONE; [count][3] sliders
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_shapers_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> kinds(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_shapers_kinds(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> modes(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_shapers_modes(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<float> sliders(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<float> m(3 * count);
+        chk(dspfx_shapers_sliders(p_, m.data(), first_channel, count));
+        return m;
+    }
+    dspfx_shapers *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_shapers_last_error(p_) ? dspfx_shapers_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_shapers *p_ = nullptr;
+};
+
+// The device bytes of a ChannelShapers bank's tables (dspfx_shapers_plan: a pure host function, no GPU).
+inline std::uint64_t shapers_plan(std::uint64_t channels) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_shapers_plan(channels, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_shapers_last_error(nullptr));
+    return bytes;
+}
+
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
