@@ -60,6 +60,7 @@ MIXMATRIX_DIRECT, MIXMATRIX_STAGED = 0, 1       # DSPFX_MIXMATRIX_*: MixMatrix.s
 TALKERS_MAX_ROOM, TALKERS_MAX_TOP = 1024, 8     # DSPFX_TALKERS_*: the most members a Talkers room has, the most talkers it names
 TALKERS_AUTO, TALKERS_OPEN, TALKERS_SHUT = 0, 1, 2      # DSPFX_TALKERS_*: Talkers.set_pin
 SHAPERS_NONE = 0xFFFFFFFF       # DSPFX_SHAPERS_NONE: ChannelShapers.kinds() without a node, .modes() without a Distort node
+GENS_NONE = 0xFFFFFFFF          # DSPFX_GENS_NONE: ChannelGenerators.modes() without a node
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -106,6 +107,8 @@ EXPORTS = [
     "dspfx_shapers_plan", "dspfx_shapers_create", "dspfx_shapers_destroy", "dspfx_shapers_last_error", "dspfx_shapers_run",
     "dspfx_shapers_set_distort", "dspfx_shapers_set_overdrive", "dspfx_shapers_set_chebyshev", "dspfx_shapers_drop",
     "dspfx_shapers_present", "dspfx_shapers_kinds", "dspfx_shapers_modes", "dspfx_shapers_sliders",
+    "dspfx_gens_plan", "dspfx_gens_create", "dspfx_gens_destroy", "dspfx_gens_last_error", "dspfx_gens_run", "dspfx_gens_set",
+    "dspfx_gens_drop", "dspfx_gens_reset", "dspfx_gens_present", "dspfx_gens_modes", "dspfx_gens_sliders", "dspfx_gens_clocks",
 ]
 COMM_ID_BYTES = 128
 
@@ -195,6 +198,11 @@ class _DynamicsDesc(C.Structure):
 
 
 class _ShapersDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32)]
+
+
+class _GensDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32)]
 
@@ -443,6 +451,19 @@ def lib():
     for name in ("present", "kinds", "modes"):
         getattr(L, f"dspfx_shapers_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_shapers_sliders.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_gens_plan.argtypes = [C.c_uint64, C.POINTER(C.c_uint64)]
+    L.dspfx_gens_create.argtypes = [C.POINTER(_GensDesc), C.POINTER(vp)]
+    L.dspfx_gens_destroy.argtypes = [vp]
+    L.dspfx_gens_last_error.restype = C.c_char_p
+    L.dspfx_gens_last_error.argtypes = [vp]
+    L.dspfx_gens_run.argtypes = [vp, f32p, f32p, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_gens_set.argtypes = [vp, fp, fp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_gens_drop.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.dspfx_gens_reset.argtypes = [vp, C.c_uint64, C.c_uint64]
+    for name in ("present", "modes"):
+        getattr(L, f"dspfx_gens_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_gens_sliders.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_gens_clocks.argtypes = [vp, C.POINTER(vp)]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2180,6 +2201,123 @@ class ChannelShapers(_Bank):
     def sliders(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """float32[count, 3]: the sliders in the order of the node's constructor, 0 where there are fewer and without a node."""
         return self._table("sliders", first_channel, count, np.float32, 3)
+
+
+def gens_plan(channels: int) -> int:
+    """dspfx_gens_plan, a pure host function (no GPU): the device bytes of a ChannelGenerators bank's tables, 13 per channel."""
+    L = lib()
+    n = C.c_uint64()
+    rc = L.dspfx_gens_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
+    _raise(L, "gens", rc)
+    return int(n.value)
+
+
+class ChannelGenerators(_Bank):
+    """Per-channel Signal Generators (include/dspfx.h, dspfx_gens_*): channel c may carry one generator of its own -- amplitude,
+    frequency, mode (SIG_SINE .. SIG_CONSTANT) and clock -- over device blocks in the layout of `tile_channels` (as Engine's).  A
+    source that lives on the device: a node exists for a channel from the first `set` that names it until `drop`, starts as the
+    reference's (0.5, 100 Hz, Sine, clock 0) and keeps its clock through every later `set`; a fresh bank writes +0.0.  A channel's
+    sample is bit for bit what Engine([SignalGen(amplitude, frequency, mode)], link_flags=0) writes for it over the same sequence
+    of block lengths.  Unlike the reference, a control block is connected per call and is not latched into the slider.
+    Asynchronous on `stream`."""
+
+    _C = "gens"
+    _WHY = True
+
+    def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
+        self.L = lib()
+        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+        d = _GensDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
+        self._create(d)
+        p = C.c_void_p()
+        self._chk(self.L.dspfx_gens_clocks(self.h, C.byref(p)))
+        self._clock = p.value
+
+    def run(self, n_frames: int, out=None, add_to=None, amplitude=None, frequency=None, stream: Optional[int] = None):
+        """`n_frames` frames of every channel's generator -> `out`, a device block in the bank's layout (made when not given); a
+        channel without a node gets +0.0.  `add_to`, a device block of the same shape: out = add_to + sample, add_to's own bits
+        without a node (out=add_to works in place).  `amplitude`, `frequency`: device blocks of the same shape on the node's control
+        ports, mapped per sample from [-1, 1] onto -1 .. 1 and 0.1 .. 20000; the stored sliders are not changed."""
+        import torch
+        if out is None:
+            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+        opt = [_ptr(b) if b is not None else None for b in (add_to, amplitude, frequency)]
+        self._chk(self.L.dspfx_gens_run(self.h, *opt, _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        return out
+
+    def set(self, amplitude=None, frequency=None, mode=None, first_channel: int = 0, count: Optional[int] = None):
+        """Give channels from first_channel a generator: `amplitude`, `frequency` and `mode` (SIG_SINE .. SIG_CONSTANT) are arrays
+        (one value per channel) or scalars for `count` channels (default: all from first_channel).  None keeps the value of a
+        channel that carries a node and is the default (0.5, 100, SIG_SINE) where it carries none.  Values are taken as given (no
+        clamp); a node's clock is kept.  An unknown mode or a range past the channels refuses the whole store.  Any thread; applies
+        to the runs submitted after it."""
+        n = None
+        for v in (amplitude, frequency, mode):
+            if v is not None and np.ndim(v) != 0:
+                m = int(np.size(v))
+                if n is not None and m != n:
+                    raise DspfxError(-1, "gens set: the arrays name different numbers of channels")
+                n = m
+        if n is None:
+            n = self.channels - int(first_channel) if count is None else int(count)
+        keep = []                                               # the arrays live until the call returns
+        args = []
+        for v in (amplitude, frequency):
+            if v is None:
+                args.append(None)
+                continue
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
+            keep.append(a)
+            args.append(a.ctypes.data_as(C.POINTER(C.c_float)))
+        if mode is None:
+            args.append(None)
+        else:
+            m = np.asarray(mode)
+            if m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF)):
+                raise DspfxError(-1, "gens set: a mode is one of the DSPFX_SIG_* values")
+            m = np.ascontiguousarray(np.broadcast_to(m.reshape(-1), (max(n, 0),)), np.uint32)
+            keep.append(m)
+            args.append(m.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self._chk(self.L.dspfx_gens_set(self.h, *args, int(first_channel), n))
+
+    def drop(self, first_channel: int = 0, count: Optional[int] = None):
+        """Remove the node of `count` channels from first_channel (default: all from it): +0.0 again, and a later `set` starts from
+        the defaults at clock 0; queued like a store."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        self._chk(self.L.dspfx_gens_drop(self.h, int(first_channel), n))
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None):
+        """Clock back to +0.0 on the channels of the range that carry a node; sliders, modes and nodes stay; queued like a store."""
+        n = self.channels - int(first_channel) if count is None else int(count)
+        self._chk(self.L.dspfx_gens_reset(self.h, int(first_channel), n))
+
+    def _table(self, name, first_channel, count, dtype=np.uint32, per=1):
+        n = self.channels - int(first_channel) if count is None else int(count)
+        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
+        ct = C.c_float if dtype == np.float32 else C.c_uint32
+        self._chk(getattr(self.L, f"dspfx_gens_{name}")(self.h, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
+        return v
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
+        return self._table("present", first_channel, count)
+
+    def modes(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the node's SIG_* mode, GENS_NONE without a node."""
+        return self._table("modes", first_channel, count)
+
+    def sliders(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """float32[count, 2]: amplitude and frequency, 0 without a node."""
+        return self._table("sliders", first_channel, count, np.float32, 2)
+
+    def clocks(self):
+        """float32[channels] on the device: every channel's clock, the phase carried between blocks; +0.0 without a node (valid
+        after a run, on its stream)."""
+        import torch
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": (self.channels,), "typestr": "<f4", "data": (self._clock, False), "version": 2}
+        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

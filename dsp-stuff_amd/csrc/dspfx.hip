@@ -17,8 +17,11 @@ namespace dspfx_host {
 
 // The last error text is kept per engine AND per calling thread: a GUI thread whose slider store failed reads its own
 // message, not the one the audio thread produced a microsecond later.
-thread_local const dspfx_engine *tl_err_engine = nullptr;
+// The thread's copy is keyed by the engine's err_id, not by its address: a later engine may be allocated where a destroyed one
+// was, and must not show that one's message.
+thread_local uint64_t tl_err_id = 0;
 thread_local std::string tl_err;
+std::atomic<uint64_t> g_next_err_id{1};
 
 int fail(dspfx_engine *e, int code, const char *fmt, ...) {
     if (e) {
@@ -28,7 +31,7 @@ int fail(dspfx_engine *e, int code, const char *fmt, ...) {
         vsnprintf(buf, sizeof buf, fmt, ap);
         va_end(ap);
         tl_err = buf;
-        tl_err_engine = e;
+        tl_err_id = e->err_id;
         std::lock_guard<std::mutex> lk(e->err_mu);
         e->err = buf;
     }
@@ -915,6 +918,7 @@ extern "C" int dspfx_engine_create(const dspfx_engine_desc *desc, dspfx_engine *
     if (hipSetDevice(desc->device) != hipSuccess) return DSPFX_ERR_HIP;
     jit_arm_exit_guard();
     dspfx_engine *e = new dspfx_engine();
+    e->err_id = g_next_err_id++;
     e->env = read_env_switches();
     e->desc = *desc;
     e->device = desc->device;
@@ -994,10 +998,10 @@ extern "C" void dspfx_engine_destroy(dspfx_engine *e) {
 
 extern "C" const char *dspfx_last_error(const dspfx_engine *e) {
     if (!e) return "null engine";
-    if (tl_err_engine != e) {           // this thread has not failed on this engine: the engine's most recent message
+    if (tl_err_id != e->err_id) {       // this thread has not failed on this engine: the engine's most recent message
         std::lock_guard<std::mutex> lk(e->err_mu);
         tl_err = e->err;
-        tl_err_engine = e;
+        tl_err_id = e->err_id;
     }
     return tl_err.c_str();              // valid until this thread's next failing call
 }

@@ -273,6 +273,7 @@ struct dspfx_engine {
     std::vector<PubReverb> pub_rev;                   // [node] (REVERB nodes only carry meaning)
     uint64_t chain_gen = 0;                           // bumped by every chain / graph set (under pend_mu)
     mutable std::mutex err_mu;                        // err (also kept per calling thread: dspfx_last_error)
+    uint64_t err_id = 0;                              // one per engine ever created: what a thread's kept message is keyed by (an address comes back)
 };
 
 namespace dspfx_host {

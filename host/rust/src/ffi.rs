@@ -240,6 +240,26 @@ pub struct dspfx_shapers_desc {
 /// `dspfx_shapers_kinds`: the channel carries no node; `dspfx_shapers_modes`: it carries no Distort node.
 pub const DSPFX_SHAPERS_NONE: u32 = 0xFFFF_FFFF;
 
+/// Opaque channel-generator bank handle (`typedef struct dspfx_gens dspfx_gens`).
+#[repr(C)]
+pub struct dspfx_gens {
+    _private: [u8; 0],
+}
+
+/// The channel-generator bank's descriptor (`dspfx_gens_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_gens_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+}
+
+/// `dspfx_gens_modes`: the channel carries no node.
+pub const DSPFX_GENS_NONE: u32 = 0xFFFF_FFFF;
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -587,6 +607,18 @@ extern "C" {
     pub fn dspfx_shapers_kinds(s: *mut dspfx_shapers, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_shapers_modes(s: *mut dspfx_shapers, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_shapers_sliders(s: *mut dspfx_shapers, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_plan(channels: u64, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_gens_create(desc: *const dspfx_gens_desc, out: *mut *mut dspfx_gens) -> c_int;
+    pub fn dspfx_gens_destroy(g: *mut dspfx_gens) -> c_int;
+    pub fn dspfx_gens_last_error(g: *const dspfx_gens) -> *const c_char;
+    pub fn dspfx_gens_run(g: *mut dspfx_gens, add_to: *const f32, amplitude: *const f32, frequency: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_gens_set(g: *mut dspfx_gens, host_amplitude: *const f32, host_frequency: *const f32, host_mode: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_drop(g: *mut dspfx_gens, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_reset(g: *mut dspfx_gens, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_present(g: *mut dspfx_gens, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_modes(g: *mut dspfx_gens, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_sliders(g: *mut dspfx_gens, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_gens_clocks(g: *mut dspfx_gens, clock_out: *mut *const f32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

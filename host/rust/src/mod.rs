@@ -11,4 +11,5 @@ pub mod channel_delays;
 pub mod talkers;
 pub mod channel_dynamics;
 pub mod channel_shapers;
+pub mod channel_generators;
 pub mod mix_matrix;

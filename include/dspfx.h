@@ -1492,6 +1492,96 @@ int dspfx_shapers_kinds(dspfx_shapers *s, uint32_t *host_kinds_out, uint64_t fir
 int dspfx_shapers_modes(dspfx_shapers *s, uint32_t *host_modes_out, uint64_t first_channel, uint64_t count);
 int dspfx_shapers_sliders(dspfx_shapers *s, float *host_sliders_out, uint64_t first_channel, uint64_t count);
 
+/* ---- channel generators: a bank of per-channel Signal Generators -------------------------------------------------------
+ * An engine runs one Signal Generator (nodes/signal_gen.rs) with one amplitude, frequency and mode for all N channels.  This bank
+ * gives channel c ONE generator of its own, with its own sliders, mode and clock, over N channels in the desc's layout
+ * (tile_channels as dspfx_engine_desc).  It is a SOURCE that lives on the device: a run reads no signal block unless the caller has
+ * the sample added into one.  A line-check tone for one participant, a join beep in one listener's return, a hold tone for the
+ * channels in no room, an LFO of its own rate per channel feeding an engine's control port.
+ * A node EXISTS for a channel from the first dspfx_gens_set that names it until dspfx_gens_drop; a fresh bank has no node anywhere.
+ * A fresh node is the reference's (signal_gen.rs:40-52): amplitude 0.5, frequency 100, mode Sine, clock +0.0.
+ * PER CHANNEL.  Amplitude, frequency, a mode (DSPFX_SIG_*) and the clock, the phase carried between blocks.  Values are taken as
+ * given, as dspfx_set_param takes them: no clamp, NaN, infinities and values outside the slider's range included.
+ * STORES.  dspfx_gens_set keeps the sliders and the mode it leaves out where the channel carries a node, and starts from the
+ * defaults where it carries none.  A channel that carries a node keeps its CLOCK through any set (the reference has no
+ * after_settings_change here); a channel that carried none, or was dropped, starts at clock +0.0.  A mode outside DSPFX_SIG_SINE ..
+ * DSPFX_SIG_CONSTANT or a range past the channels refuses the WHOLE store: DSPFX_ERR_INVALID, the reason in dspfx_gens_last_error,
+ * nothing stored.
+ * ONE RUN: queued stores go onto the stream in the order they were made, then per channel:
+ *   - The sample is bit for bit what an engine whose chain is that one Signal Generator, with link_flags = 0, writes for the
+ *     channel over the same sequence of block lengths: the bank calls the engine's own device functions.  Square compares the
+ *     block-local total, not the phase, with 0.5, as the reference does.
+ *   - Without add_to, out[f][c] is the sample; a channel without a node gets +0.0 (an unconnected port, node.rs:162-194).
+ *   - With add_to, a block in the bank's layout, out[f][c] = add_to[f][c] + sample by one f32 addition (add.rs); a channel without
+ *     a node gets add_to's very bits.  out may be add_to.
+ *   - BLOCKS.  The run's frames are cut into the reference's blocks of DSPFX_BUF_SIZE frames from frame 0.  At every block end, and
+ *     at the end of a run that stops inside a block, clock = fmodf(clock + total, 1) and total = 0, as the engine does.  Constant
+ *     leaves the clock alone (signal_gen.rs:106-108).
+ *   - CONTROL PORTS.  amplitude and frequency are optional device blocks in the bank's layout, the reference's `as_input` slider
+ *     ports (dsp-stuff-derive/src/lib.rs:135-153): where one is given, a channel's slider value for sample f is the block's value
+ *     mapped from [-1, 1] onto the slider's range, -1 .. 1 for the amplitude and 0.1 .. 20000 for the frequency, per sample.
+ *     Channels without a node read neither block.
+ *     KNOWN DIFFERENCE from the reference: the bank does NOT latch a block's first value into the slider.  A port here is
+ *     connected per call, not wired: a later run without the block uses what the stores left.
+ *   - No link hops: the bank is link_flags = 0.
+ * The kernel has the shape of the shaper bank's: a lane owns four adjacent channels (one when the layout or the alignment forbids
+ * it), frames go in chunks with the next chunk's loads of add_to and the control blocks issued ahead of the arithmetic, stores are
+ * nontemporal.  The modes differ per lane, so a wave ballots once per run for the modes its lanes carry and runs, per chunk, the
+ * body of each mode that is present, wave-uniformly, keeping each result under a select: a wave of one mode pays for one body, a
+ * wave without a Sine channel never evaluates the f64 sine, a wave without a node does no arithmetic.  The clocks are read once and
+ * written once per run.  A channel's output is the same bits in either layout, with add_to in place or not, on any stream, and
+ * whatever its neighbours carry.  No atomics, no LDS.
+ * Memory: 13 bytes per channel of tables on the device (amplitude, frequency, clock and a mode / presence byte; dspfx_gens_plan),
+ * 9 on the host. */
+/* dspfx_gens_modes: the channel carries no node */
+#define DSPFX_GENS_NONE 0xFFFFFFFFu
+typedef struct dspfx_gens dspfx_gens;
+typedef struct dspfx_gens_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+} dspfx_gens_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, 13 * channels.  channels of 0 or above
+ * 2^32 - 256: DSPFX_ERR_INVALID, the reason in dspfx_gens_last_error(NULL). */
+int dspfx_gens_plan(uint64_t channels, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0) is DSPFX_ERR_INVALID with the reason in dspfx_gens_last_error of a NULL bank (kept per thread); all of that is
+ * checked before any device work. */
+int dspfx_gens_create(const dspfx_gens_desc *desc, dspfx_gens **out);
+int dspfx_gens_destroy(dspfx_gens *g);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_gens_last_error(const dspfx_gens *g);
+/* out: a device block of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  add_to, amplitude, frequency: device
+ * blocks of the same shape, each may be NULL (see ONE RUN).  out == add_to works in place (a thread rewrites the elements it read);
+ * any other overlap is the caller's error.  Asynchronous on `stream`; a run on another stream than the one before first waits (on
+ * the device) for that one (the rules of dspfx_strips_run).  Queued stores go onto the stream ahead of the kernel, in the order they
+ * were made. */
+int dspfx_gens_run(dspfx_gens *g, const float *add_to, const float *amplitude, const float *frequency, float *out, uint32_t n_frames,
+                   void *stream);
+/* Gives channels [first_channel, first_channel + count) a generator, from host arrays of `count` values each: the amplitudes, the
+ * frequencies and the modes (DSPFX_SIG_*).  Each may be NULL: kept where the channel carries a node, the default (0.5, 100, Sine)
+ * where it carries none.  The contract of dspfx_dynamics_set: callable from any thread while runs are in flight, never waits for the
+ * device or for a run; the values are staged in page-locked memory and queued, each store is whole, and a run submitted after the
+ * call returns sees it, the runs submitted before it do not. */
+int dspfx_gens_set(dspfx_gens *g, const float *host_amplitude, const float *host_frequency, const uint32_t *host_mode, uint64_t first_channel,
+                   uint64_t count);
+/* Removes the node of channels [first_channel, first_channel + count): +0.0 (or add_to's bits) again, and a later set starts from
+ * the defaults and from clock +0.0.  Queued like a store.  A range past the channels: DSPFX_ERR_INVALID and the reason. */
+int dspfx_gens_drop(dspfx_gens *g, uint64_t first_channel, uint64_t count);
+/* Sets the clocks of the channels of the range that carry a node to +0.0; sliders, modes and nodes stay.  Queued like a store. */
+int dspfx_gens_reset(dspfx_gens *g, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: present 1 / 0 (the channel
+ * carries a node); modes the DSPFX_SIG_* value, DSPFX_GENS_NONE without a node; sliders [count][2], amplitude then frequency, 0
+ * without a node. */
+int dspfx_gens_present(dspfx_gens *g, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_gens_modes(dspfx_gens *g, uint32_t *host_modes_out, uint64_t first_channel, uint64_t count);
+int dspfx_gens_sliders(dspfx_gens *g, float *host_sliders_out, uint64_t first_channel, uint64_t count);
+/* The device pointer of clock[N], f32: +0.0 for a channel without a node.  The pointer never changes; what it holds is valid after
+ * a run, on its stream. */
+int dspfx_gens_clocks(dspfx_gens *g, const float **clock_out);
+
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
  * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain

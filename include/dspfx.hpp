@@ -846,6 +846,77 @@ inline std::uint64_t shapers_plan(std::uint64_t channels) {
     return bytes;
 }
 
+// Per-channel Signal Generators (include/dspfx.h, dspfx_gens_*), a source that lives on the device: channel c may carry one
+// generator of its own -- amplitude, frequency, mode (DSPFX_SIG_*) and clock -- over device blocks in the layout of tile_channels; its
+// sample is bit for bit what an engine whose chain is that one Signal Generator writes for it over the same block lengths.  A node
+// exists for a channel from the first set() that names it until drop(), starts as the reference's (0.5, 100, Sine, clock +0.0) and
+// keeps its clock through every later set(); a fresh bank writes +0.0.  Unlike the reference, a control block is connected per run
+// and is not latched into the slider.
+class ChannelGenerators {
+  public:
+    ChannelGenerators(std::uint32_t channels, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE, int device = 0) {
+        const dspfx_gens_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels};
+        const int rc = dspfx_gens_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_gens_last_error(nullptr) ? dspfx_gens_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelGenerators() { dspfx_gens_destroy(p_); }
+    ChannelGenerators(const ChannelGenerators &) = delete;
+    ChannelGenerators &operator=(const ChannelGenerators &) = delete;
+    // n_frames of every channel's generator -> the device block out; add_to (out = add_to + sample; may be out), amplitude and
+    // frequency (control blocks, mapped per sample onto -1 .. 1 and 0.1 .. 20000) are device blocks of the same shape or nullptr;
+    // asynchronous on `stream`
+    void run(float *out, std::uint32_t n_frames, const float *add_to = nullptr, const float *amplitude = nullptr, const float *frequency = nullptr,
+             void *stream = nullptr) {
+        chk(dspfx_gens_run(p_, add_to, amplitude, frequency, out, n_frames, stream));
+    }
+    // a generator for each of channels [first_channel, first_channel + count) from host arrays (nullptr: kept, or the default where
+    // there is no node); an unknown mode refuses the whole store.  Any thread; never waits
+    void set(const float *host_amplitude, const float *host_frequency, const std::uint32_t *host_mode, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_gens_set(p_, host_amplitude, host_frequency, host_mode, first_channel, count));
+    }
+    // the node removed: +0.0 again; queued like a store
+    void drop(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_gens_drop(p_, first_channel, count)); }
+    // the clocks of the range's nodes back to +0.0; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_gens_reset(p_, first_channel, count)); }
+    // the host tables, as all stores so far left them: 1 / 0; the DSPFX_SIG_* mode or DSPFX_GENS_NONE; [count][2] amplitude, frequency
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_gens_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> modes(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_gens_modes(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<float> sliders(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<float> m(2 * count);
+        chk(dspfx_gens_sliders(p_, m.data(), first_channel, count));
+        return m;
+    }
+    // clock[N] on the device (valid after a run, on its stream)
+    const float *clocks() {
+        const float *c = nullptr;
+        chk(dspfx_gens_clocks(p_, &c));
+        return c;
+    }
+    dspfx_gens *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_gens_last_error(p_) ? dspfx_gens_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_gens *p_ = nullptr;
+};
+
+// The device bytes of a ChannelGenerators bank's tables (dspfx_gens_plan: a pure host function, no GPU).
+inline std::uint64_t gens_plan(std::uint64_t channels) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_gens_plan(channels, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_gens_last_error(nullptr));
+    return bytes;
+}
+
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
