@@ -1049,6 +1049,79 @@ class _Bank:
             pass
 
 
+class _ChannelBank(_Bank):
+    """What the per-channel banks share beyond _Bank: the fields every one of them has, how a store's arguments become a channel
+    count and arrays of it, a host table read back, a view of a device table, and the output block a run makes."""
+
+    _WHY = True
+
+    def _fields(self, channels, tile_channels, max_frames, device):
+        self.L = lib()
+        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+
+    def _n(self, first_channel, count):
+        return self.channels - int(first_channel) if count is None else int(count)
+
+    def _range(self, first, count, arrays, why, total=None):
+        """The entries a store names: the length its arrays agree on (else DspfxError(why)), or, with scalars only, `count`
+        (default: all from `first` up to `total`, the channels)."""
+        n = None
+        for v in arrays:
+            if v is not None and np.ndim(v) != 0:
+                m = int(np.size(v))
+                if n is not None and m != n:
+                    raise DspfxError(-1, why)
+                n = m
+        if n is None:
+            n = (self.channels if total is None else total) - int(first) if count is None else int(count)
+        return n
+
+    @staticmethod
+    def _f32s(values, n):
+        """Each of `values` (None, a scalar or an array) as float32[n] -> (the arrays, to be kept until the call returns, and the
+        pointers, None for None)."""
+        keep = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
+                for v in values]
+        return keep, [None if a is None else a.ctypes.data_as(C.POINTER(C.c_float)) for a in keep]
+
+    def _u32s(self, modes, n, call, what):
+        """`modes` (None, a scalar or an array of non-negative integers) as uint32[n] -> (the array, its pointer)."""
+        if modes is None:
+            return None, None
+        m = np.asarray(modes)
+        if m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF)):
+            raise DspfxError(-1, f"{self._C} {call}: a mode is one of the {what} values")
+        m = np.ascontiguousarray(np.broadcast_to(m.reshape(-1), (max(n, 0),)), np.uint32)
+        return m, m.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def _table(self, name, first_channel, count, dtype=np.uint32, per=1):
+        """dspfx_<bank>_<name>: a host table over `count` channels from first_channel (default: all from it), `per` values each."""
+        n = self._n(first_channel, count)
+        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
+        ct = C.c_float if dtype == np.float32 else C.c_uint32
+        self._chk(getattr(self.L, f"dspfx_{self._C}_{name}")(self.h, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
+        return v
+
+    def _view(self, addr, shape, typestr="<f4"):
+        """A device table of the bank's as a torch tensor that shares its memory."""
+        import torch
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (addr, False), "version": 2}
+        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+
+    def _frames(self, block, n_frames):
+        return block.numel() // self.channels if n_frames is None else n_frames
+
+    def _out(self, n_frames):
+        import torch
+        return torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+
+
+def _stream(stream):
+    return C.c_void_p(stream) if stream else None
+
+
 class PitchBank(_Bank):
     """The Pitch Detector node (nodes/pitch.rs) for N channels (include/dspfx.h, dspfx_pitch_*): blocks pushed in the layout
     of `tile_channels` (as Engine's), a McLeod pitch and clarity per channel for every 1024 frames, held until the next
@@ -1598,7 +1671,7 @@ def strips_coeffs(raw6) -> np.ndarray:
     return out
 
 
-class ChannelStrips(_Bank):
+class ChannelStrips(_ChannelBank):
     """Per-channel Gain and BiQuad sliders (include/dspfx.h, dspfx_strips_*): the strip of channel c is a chain of up to
     1 + `bands` optional nodes in a fixed order -- a Gain node, then BiQuad bands 0 .. bands-1 -- each with the channel's own
     slider values, over a device block in the layout of `tile_channels` (as Engine's).  A node exists for a channel from the
@@ -1607,13 +1680,11 @@ class ChannelStrips(_Bank):
     Between eng.process and MixGroups.run / returns, or ahead of the chain.  Asynchronous on `stream`."""
 
     _C = "strips"
-    _WHY = True
 
     def __init__(self, channels: int, bands: int = 1, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
                  device: int = 0):
-        self.L = lib()
-        self.channels, self.bands, self.tile_channels = int(channels), int(bands), int(tile_channels)
-        self.max_frames, self.link_flags, self.device = int(max_frames), int(link_flags), int(device)
+        self._fields(channels, tile_channels, max_frames, device)
+        self.bands, self.link_flags = int(bands), int(link_flags)
         d = _StripsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
                         self.bands & 0xFFFFFFFF, self.link_flags & 0xFFFFFFFF)
         self._create(d)
@@ -1621,12 +1692,10 @@ class ChannelStrips(_Bank):
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's strip -> `out`, a device block in the same layout (made when not given;
         out=block works in place)."""
-        import torch
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
+        n_frames = self._frames(block, n_frames)
         if out is None:
-            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_strips_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_strips_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
         return out
 
     def set_gain(self, levels, first_channel: int = 0, count: Optional[int] = None):
@@ -1635,7 +1704,7 @@ class ChannelStrips(_Bank):
         to the runs submitted after it."""
         first = int(first_channel)
         if levels is None or np.ndim(levels) == 0:
-            n = self.channels - first if count is None else int(count)
+            n = self._n(first, count)
             if levels is None:
                 self._chk(self.L.dspfx_strips_set_gain(self.h, None, first, n))
                 return
@@ -1650,7 +1719,7 @@ class ChannelStrips(_Bank):
         applies to the runs submitted after it."""
         first = int(first_channel)
         if coeffs is None or np.ndim(coeffs) == 1:
-            n = self.channels - first if count is None else int(count)
+            n = self._n(first, count)
             if coeffs is None:
                 self._chk(self.L.dspfx_strips_set_band(self.h, int(band) & 0xFFFFFFFF, None, first, n))
                 return
@@ -1662,10 +1731,7 @@ class ChannelStrips(_Bank):
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: the node mask of every channel as the next run sees it; bit 0 = Gain, bit 1 + b = band b."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        v = np.zeros(max(n, 0), np.uint32)
-        self._chk(self.L.dspfx_strips_present(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
-        return v
+        return self._table("present", first_channel, count)
 
     def reset(self):
         """Zero all state (on the stream last used); the sliders and the nodes stay."""
@@ -1683,7 +1749,7 @@ def delays_plan(channels: int, max_seconds: float = 0.5, page_round: bool = Fals
     return int(cap.value), int(nbytes.value)
 
 
-class ChannelDelays(_Bank):
+class ChannelDelays(_ChannelBank):
     """Per-channel Reverb (feedback delay) sliders (include/dspfx.h, dspfx_delays_*): channel c may carry one Reverb node with
     its own `seconds` and `decay` and its own ring of delay_len(seconds, page_round) frames, over a device block in the layout of
     `tile_channels` (as Engine's).  A node exists for a channel from the first store that names it until it is dropped; a fresh
@@ -1692,13 +1758,11 @@ class ChannelDelays(_Bank):
     the node.  Where ChannelStrips goes: between eng.process and the room mixes.  Asynchronous on `stream`."""
 
     _C = "delays"
-    _WHY = True
 
     def __init__(self, channels: int, max_seconds: float = 0.5, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
                  page_round: bool = False, device: int = 0):
-        self.L = lib()
-        self.channels, self.max_seconds, self.tile_channels = int(channels), float(max_seconds), int(tile_channels)
-        self.max_frames, self.link_flags, self.page_round, self.device = int(max_frames), int(link_flags), bool(page_round), int(device)
+        self._fields(channels, tile_channels, max_frames, device)
+        self.max_seconds, self.link_flags, self.page_round = float(max_seconds), int(link_flags), bool(page_round)
         d = _DelaysDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
                         self.max_seconds, int(self.page_round), self.link_flags & 0xFFFFFFFF)
         self._create(d)
@@ -1706,12 +1770,10 @@ class ChannelDelays(_Bank):
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's delay -> `out`, a device block in the same layout (made when not given;
         out=block works in place)."""
-        import torch
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
+        n_frames = self._frames(block, n_frames)
         if out is None:
-            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_delays_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_delays_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
         return out
 
     def set_delay(self, seconds=None, decay=None, first_channel: int = 0, count: Optional[int] = None):
@@ -1720,40 +1782,17 @@ class ChannelDelays(_Bank):
         drops the node of `count` channels.  Every stored channel starts again from a zero ring, as the reference's slider
         change does.  Refused whole when a channel would need more than the bank's ring.  Any thread; applies to the runs
         submitted after it."""
-        first = int(first_channel)
-        n = None
-        for v in (seconds, decay):
-            if v is not None and np.ndim(v) != 0:
-                m = int(np.size(v))
-                if n is not None and m != n:
-                    raise DspfxError(-1, "delays set_delay: seconds and decay name different numbers of channels")
-                n = m
-        if n is None:
-            n = self.channels - first if count is None else int(count)
-
-        def arr(v):
-            if v is None:
-                return None, None
-            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
-            return a, a.ctypes.data_as(C.POINTER(C.c_float))
-
-        s, sp = arr(seconds)
-        d, dp = arr(decay)
-        self._chk(self.L.dspfx_delays_set_delay(self.h, sp, dp, first, n))
+        n = self._range(first_channel, count, (seconds, decay), "delays set_delay: seconds and decay name different numbers of channels")
+        keep, ptrs = self._f32s((seconds, decay), n)
+        self._chk(self.L.dspfx_delays_set_delay(self.h, *ptrs, int(first_channel), n))
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        v = np.zeros(max(n, 0), np.uint32)
-        self._chk(self.L.dspfx_delays_present(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
-        return v
+        return self._table("present", first_channel, count)
 
     def lengths(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: every channel's ring length D, 0 where there is no node."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        v = np.zeros(max(n, 0), np.uint32)
-        self._chk(self.L.dspfx_delays_lengths(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
-        return v
+        return self._table("lengths", first_channel, count)
 
     def reset(self):
         """Every present channel's ring back to zeros (on the stream last used); the sliders and the nodes stay."""
@@ -1828,7 +1867,7 @@ def talkers_audible(gate, target, room_of, groups: int):
     return lst, start, count
 
 
-class Talkers(_Bank):
+class Talkers(_ChannelBank):
     """Per-channel levels and each room's loudest, gated live (include/dspfx.h, dspfx_talkers_*): every channel has its own Envelope
     node (attack and release in frames, `set_detector`), every room -- group_start / group_size as MixGroups takes them, 1 .. 1024
     members, reseated live by `assign` -- gets its `top` loudest members chosen on the device, and run() passes those members and
@@ -1837,13 +1876,12 @@ class Talkers(_Bank):
     block.  Between ChannelStrips / ChannelDelays and the room mixes.  Asynchronous on `stream`."""
 
     _C = "talkers"
-    _WHY = True
+    _ENTRIES = "talkers: the arrays name different numbers of entries"
 
     def __init__(self, channels: int, group_start=None, group_size=None, top: int = 3, tile_channels: int = 0, max_frames: int = BUF_SIZE,
                  device: int = 0):
-        self.L = lib()
-        self.channels, self.tile_channels, self.device = int(channels), int(tile_channels), int(device)
-        self.max_frames, self.top = int(max_frames), int(top)
+        self._fields(channels, tile_channels, max_frames, device)
+        self.top = int(top)
         self.group_start = _group_table(self.channels, group_start, group_size)
         self.groups = len(self.group_start) - 1
         d = _TalkersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
@@ -1858,55 +1896,32 @@ class Talkers(_Bank):
         """One device block: gate it with the targets of the run before -> `out`, a device block in the same layout (made when not
         given; out=block works in place), then meter it and choose every room's talkers.  gate=False only meters and selects: no
         sample is written, the gates stay, and None is returned."""
-        import torch
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
+        n_frames = self._frames(block, n_frames)
         if not gate:
             out = None
         elif out is None:
-            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_talkers_run(self.h, _ptr(block), _ptr(out) if out is not None else None, int(n_frames),
-                                           C.c_void_p(stream) if stream else None))
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_talkers_run(self.h, _ptr(block), _ptr(out) if out is not None else None, int(n_frames), _stream(stream)))
         return out
-
-    def _range(self, first, count, arrays, total):
-        n = None
-        for v in arrays:
-            if v is not None and np.ndim(v) != 0:
-                m = int(np.size(v))
-                if n is not None and m != n:
-                    raise DspfxError(-1, "talkers: the arrays name different numbers of entries")
-                n = m
-        if n is None:
-            n = total - int(first) if count is None else int(count)
-        return n
 
     def set_detector(self, attack=None, release=None, first_channel: int = 0, count: Optional[int] = None):
         """Store the attack and release sliders (frames) of channels from first_channel: arrays (one value per channel) or scalars
         for `count` channels (default: all from first_channel).  A slider left None keeps each channel's value.  No envelope is
         touched.  Any thread; applies to the runs submitted after it."""
-        n = self._range(first_channel, count, (attack, release), self.channels)
-
-        def arr(v):
-            if v is None:
-                return None, None
-            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
-            return a, a.ctypes.data_as(C.POINTER(C.c_float))
-
-        a, ap = arr(attack)
-        r, rp = arr(release)
-        self._chk(self.L.dspfx_talkers_set_detector(self.h, ap, rp, int(first_channel), n))
+        n = self._range(first_channel, count, (attack, release), self._ENTRIES)
+        keep, ptrs = self._f32s((attack, release), n)
+        self._chk(self.L.dspfx_talkers_set_detector(self.h, *ptrs, int(first_channel), n))
 
     def set_pin(self, pins, first_channel: int = 0, count: Optional[int] = None):
         """Store the pins of channels from first_channel (TALKERS_AUTO, TALKERS_OPEN: always passed and never ranked, TALKERS_SHUT:
         never passed): an array, or one value for `count` channels (default: all from first_channel)."""
-        n = self._range(first_channel, count, (pins,), self.channels)
+        n = self._range(first_channel, count, (pins,), self._ENTRIES)
         v = _u8_per(pins, max(n, 0), "talkers set_pin")
         self._chk(self.L.dspfx_talkers_set_pin(self.h, v.ctypes.data_as(C.POINTER(C.c_uint8)), int(first_channel), n))
 
     def set_top(self, tops, first_room: int = 0, count: Optional[int] = None):
         """Store the top (1 .. 8) of rooms from first_room: an array, or one value for `count` rooms (default: all from first_room)."""
-        n = self._range(first_room, count, (tops,), self.groups)
+        n = self._range(first_room, count, (tops,), self._ENTRIES, self.groups)
         v = _u8_per(tops, max(n, 0), "talkers set_top")
         self._chk(self.L.dspfx_talkers_set_top(self.h, v.ctypes.data_as(C.POINTER(C.c_uint8)), int(first_room), n))
 
@@ -1925,7 +1940,7 @@ class Talkers(_Bank):
     def reset(self, first_channel: int = 0, count: Optional[int] = None):
         """Envelope and level back to 0, gate and target to 1 on `count` channels from first_channel (default: all from it); queued
         like a store.  The way out for a channel whose envelope became NaN."""
-        n = self.channels - int(first_channel) if count is None else int(count)
+        n = self._n(first_channel, count)
         self._chk(self.L.dspfx_talkers_reset(self.h, int(first_channel), n))
 
     def room_of(self) -> np.ndarray:
@@ -1953,13 +1968,6 @@ class Talkers(_Bank):
         lst, start, count = self._audible
         return (self._view(lst, (self.channels,), "<i4"), self._view(start, (self.groups + 1,), "<u4"),
                 self._view(count, (self.groups,), "<u4"))
-
-    def _view(self, addr, shape, typestr):
-        import torch
-
-        class _Mem:
-            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (addr, False), "version": 2}
-        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
 
     def levels(self):
         """float32[channels] on the device: every channel's largest envelope of the last block (valid after a run, on its stream)."""
@@ -1995,7 +2003,7 @@ def dynamics_gain(env: float, threshold: float, makeup: float = 1.0):
     return np.float32(g), np.float32(q.value)
 
 
-class ChannelDynamics(_Bank):
+class ChannelDynamics(_ChannelBank):
     """Per-channel levellers and limiters (include/dspfx.h, dspfx_dynamics_*): channel c may carry its own Envelope node (attack and
     release in frames) feeding its own gain computer, q = env > threshold ? threshold / env : 1, out = in * (makeup * q), over a
     device block in the layout of `tile_channels` (as Engine's).  A node exists for a channel from the first `set` that names it
@@ -2004,11 +2012,9 @@ class ChannelDynamics(_Bank):
     ..).  Ahead of Talkers as a leveller, behind the room mixes as a limiter.  Asynchronous on `stream`."""
 
     _C = "dynamics"
-    _WHY = True
 
     def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self.L = lib()
-        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+        self._fields(channels, tile_channels, max_frames, device)
         d = _DynamicsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
         self._create(d)
         ptrs = [C.c_void_p() for _ in range(2)]
@@ -2019,13 +2025,10 @@ class ChannelDynamics(_Bank):
         """One device block through every channel's dynamics -> `out`, a device block in the same layout (made when not given;
         out=block works in place).  `key`, a device block of the same shape, is what the detector follows instead of `block`
         (key=block is no key); it must not overlap `out` unless it is `block`."""
-        import torch
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
+        n_frames = self._frames(block, n_frames)
         if out is None:
-            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_dynamics_run(self.h, _ptr(block), _ptr(key) if key is not None else None, _ptr(out), int(n_frames),
-                                            C.c_void_p(stream) if stream else None))
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_dynamics_run(self.h, _ptr(block), _ptr(key) if key is not None else None, _ptr(out), int(n_frames), _stream(stream)))
         return out
 
     def set(self, threshold=None, makeup=None, attack=None, release=None, first_channel: int = 0, count: Optional[int] = None):
@@ -2034,59 +2037,33 @@ class ChannelDynamics(_Bank):
         release 0, threshold 1, makeup 1 where never stored).  No envelope is touched.  Refused whole: a threshold that is NaN or
         below +0.0, a makeup that is NaN, infinite or negative, a range past the channels.  Any thread; applies to the runs
         submitted after it."""
-        n = None
-        for v in (threshold, makeup, attack, release):
-            if v is not None and np.ndim(v) != 0:
-                m = int(np.size(v))
-                if n is not None and m != n:
-                    raise DspfxError(-1, "dynamics set: the arrays name different numbers of channels")
-                n = m
-        if n is None:
-            n = self.channels - int(first_channel) if count is None else int(count)
-
-        def arr(v):
-            if v is None:
-                return None, None
-            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
-            return a, a.ctypes.data_as(C.POINTER(C.c_float))
-
-        keep = [arr(v) for v in (threshold, makeup, attack, release)]
-        self._chk(self.L.dspfx_dynamics_set(self.h, *[p for _, p in keep], int(first_channel), n))
+        sliders = (threshold, makeup, attack, release)
+        n = self._range(first_channel, count, sliders, "dynamics set: the arrays name different numbers of channels")
+        keep, ptrs = self._f32s(sliders, n)
+        self._chk(self.L.dspfx_dynamics_set(self.h, *ptrs, int(first_channel), n))
 
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node of `count` channels from first_channel (default: all from it) and clear their envelope; queued like a
         store."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        self._chk(self.L.dspfx_dynamics_drop(self.h, int(first_channel), n))
+        self._chk(self.L.dspfx_dynamics_drop(self.h, int(first_channel), self._n(first_channel, count)))
 
     def reset(self, first_channel: int = 0, count: Optional[int] = None):
         """Envelope and level back to 0 and reduction to 1 on `count` channels from first_channel (default: all from it); the
         sliders and the nodes stay; queued like a store.  The way out for a channel whose envelope became NaN."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        self._chk(self.L.dspfx_dynamics_reset(self.h, int(first_channel), n))
+        self._chk(self.L.dspfx_dynamics_reset(self.h, int(first_channel), self._n(first_channel, count)))
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        v = np.zeros(max(n, 0), np.uint32)
-        self._chk(self.L.dspfx_dynamics_present(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), n))
-        return v
-
-    def _view(self, addr):
-        import torch
-
-        class _Mem:
-            __cuda_array_interface__ = {"shape": (self.channels,), "typestr": "<f4", "data": (addr, False), "version": 2}
-        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+        return self._table("present", first_channel, count)
 
     def levels(self):
         """float32[channels] on the device: every channel's largest envelope of the last block, 0.0 without a node (valid after a
         run, on its stream)."""
-        return self._view(self._views[0])
+        return self._view(self._views[0], (self.channels,))
 
     def reductions(self):
         """float32[channels] on the device: every channel's smallest q of the last block -- 1.0 where it was never turned down."""
-        return self._view(self._views[1])
+        return self._view(self._views[1], (self.channels,))
 
 
 def shapers_plan(channels: int) -> int:
@@ -2098,7 +2075,7 @@ def shapers_plan(channels: int) -> int:
     return int(n.value)
 
 
-class ChannelShapers(_Bank):
+class ChannelShapers(_ChannelBank):
     """Per-channel waveshapers (include/dspfx.h, dspfx_shapers_*): channel c may carry one node of its own -- Distort with its own
     level and mode, Overdrive or Chebyshev with their own sliders -- over a device block in the layout of `tile_channels` (as
     Engine's).  A node exists for a channel from the first `set_*` that names it until `drop`; a fresh bank copies its input.  A
@@ -2109,54 +2086,27 @@ class ChannelShapers(_Bank):
     `stream`."""
 
     _C = "shapers"
-    _WHY = True
 
     def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self.L = lib()
-        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+        self._fields(channels, tile_channels, max_frames, device)
         d = _ShapersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
         self._create(d)
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's shaper -> `out`, a device block in the same layout (made when not given;
         out=block works in place)."""
-        import torch
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
+        n_frames = self._frames(block, n_frames)
         if out is None:
-            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_shapers_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_shapers_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
         return out
 
     def _store(self, call, values, modes, first_channel, count):
-        n = None
-        for v in tuple(values) + (modes,):
-            if v is not None and np.ndim(v) != 0:
-                m = int(np.size(v))
-                if n is not None and m != n:
-                    raise DspfxError(-1, f"shapers {call}: the arrays name different numbers of channels")
-                n = m
-        if n is None:
-            n = self.channels - int(first_channel) if count is None else int(count)
-        keep = []                                               # the arrays live until the call returns
-        args = []
-        for v in values:
-            if v is None:
-                args.append(None)
-                continue
-            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
-            keep.append(a)
-            args.append(a.ctypes.data_as(C.POINTER(C.c_float)))
+        n = self._range(first_channel, count, tuple(values) + (modes,), f"shapers {call}: the arrays name different numbers of channels")
+        keep, args = self._f32s(values, n)
         if call == "set_distort":
-            if modes is None:
-                args.append(None)
-            else:
-                m = np.asarray(modes)
-                if m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF)):
-                    raise DspfxError(-1, "shapers set_distort: a mode is one of the DSPFX_DIST_* values")
-                m = np.ascontiguousarray(np.broadcast_to(m.reshape(-1), (max(n, 0),)), np.uint32)
-                keep.append(m)
-                args.append(m.ctypes.data_as(C.POINTER(C.c_uint32)))
+            m, mp = self._u32s(modes, n, call, "DSPFX_DIST_*")
+            args.append(mp)
         self._chk(getattr(self.L, f"dspfx_shapers_{call}")(self.h, *args, int(first_channel), n))
 
     def set_distort(self, level=None, mode=None, first_channel: int = 0, count: Optional[int] = None):
@@ -2176,15 +2126,7 @@ class ChannelShapers(_Bank):
 
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node of `count` channels from first_channel (default: all from it): a copy again; queued like a store."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        self._chk(self.L.dspfx_shapers_drop(self.h, int(first_channel), n))
-
-    def _table(self, name, first_channel, count, dtype=np.uint32, per=1):
-        n = self.channels - int(first_channel) if count is None else int(count)
-        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
-        ct = C.c_float if dtype == np.float32 else C.c_uint32
-        self._chk(getattr(self.L, f"dspfx_shapers_{name}")(self.h, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
-        return v
+        self._chk(self.L.dspfx_shapers_drop(self.h, int(first_channel), self._n(first_channel, count)))
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
@@ -2212,7 +2154,7 @@ def gens_plan(channels: int) -> int:
     return int(n.value)
 
 
-class ChannelGenerators(_Bank):
+class ChannelGenerators(_ChannelBank):
     """Per-channel Signal Generators (include/dspfx.h, dspfx_gens_*): channel c may carry one generator of its own -- amplitude,
     frequency, mode (SIG_SINE .. SIG_CONSTANT) and clock -- over device blocks in the layout of `tile_channels` (as Engine's).  A
     source that lives on the device: a node exists for a channel from the first `set` that names it until `drop`, starts as the
@@ -2222,11 +2164,9 @@ class ChannelGenerators(_Bank):
     Asynchronous on `stream`."""
 
     _C = "gens"
-    _WHY = True
 
     def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self.L = lib()
-        self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+        self._fields(channels, tile_channels, max_frames, device)
         d = _GensDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
         self._create(d)
         p = C.c_void_p()
@@ -2238,11 +2178,10 @@ class ChannelGenerators(_Bank):
         channel without a node gets +0.0.  `add_to`, a device block of the same shape: out = add_to + sample, add_to's own bits
         without a node (out=add_to works in place).  `amplitude`, `frequency`: device blocks of the same shape on the node's control
         ports, mapped per sample from [-1, 1] onto -1 .. 1 and 0.1 .. 20000; the stored sliders are not changed."""
-        import torch
         if out is None:
-            out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
+            out = self._out(n_frames)
         opt = [_ptr(b) if b is not None else None for b in (add_to, amplitude, frequency)]
-        self._chk(self.L.dspfx_gens_run(self.h, *opt, _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        self._chk(self.L.dspfx_gens_run(self.h, *opt, _ptr(out), int(n_frames), _stream(stream)))
         return out
 
     def set(self, amplitude=None, frequency=None, mode=None, first_channel: int = 0, count: Optional[int] = None):
@@ -2251,52 +2190,19 @@ class ChannelGenerators(_Bank):
         channel that carries a node and is the default (0.5, 100, SIG_SINE) where it carries none.  Values are taken as given (no
         clamp); a node's clock is kept.  An unknown mode or a range past the channels refuses the whole store.  Any thread; applies
         to the runs submitted after it."""
-        n = None
-        for v in (amplitude, frequency, mode):
-            if v is not None and np.ndim(v) != 0:
-                m = int(np.size(v))
-                if n is not None and m != n:
-                    raise DspfxError(-1, "gens set: the arrays name different numbers of channels")
-                n = m
-        if n is None:
-            n = self.channels - int(first_channel) if count is None else int(count)
-        keep = []                                               # the arrays live until the call returns
-        args = []
-        for v in (amplitude, frequency):
-            if v is None:
-                args.append(None)
-                continue
-            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (max(n, 0),)), np.float32)
-            keep.append(a)
-            args.append(a.ctypes.data_as(C.POINTER(C.c_float)))
-        if mode is None:
-            args.append(None)
-        else:
-            m = np.asarray(mode)
-            if m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF)):
-                raise DspfxError(-1, "gens set: a mode is one of the DSPFX_SIG_* values")
-            m = np.ascontiguousarray(np.broadcast_to(m.reshape(-1), (max(n, 0),)), np.uint32)
-            keep.append(m)
-            args.append(m.ctypes.data_as(C.POINTER(C.c_uint32)))
-        self._chk(self.L.dspfx_gens_set(self.h, *args, int(first_channel), n))
+        n = self._range(first_channel, count, (amplitude, frequency, mode), "gens set: the arrays name different numbers of channels")
+        keep, args = self._f32s((amplitude, frequency), n)
+        m, mp = self._u32s(mode, n, "set", "DSPFX_SIG_*")
+        self._chk(self.L.dspfx_gens_set(self.h, *args, mp, int(first_channel), n))
 
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node of `count` channels from first_channel (default: all from it): +0.0 again, and a later `set` starts from
         the defaults at clock 0; queued like a store."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        self._chk(self.L.dspfx_gens_drop(self.h, int(first_channel), n))
+        self._chk(self.L.dspfx_gens_drop(self.h, int(first_channel), self._n(first_channel, count)))
 
     def reset(self, first_channel: int = 0, count: Optional[int] = None):
         """Clock back to +0.0 on the channels of the range that carry a node; sliders, modes and nodes stay; queued like a store."""
-        n = self.channels - int(first_channel) if count is None else int(count)
-        self._chk(self.L.dspfx_gens_reset(self.h, int(first_channel), n))
-
-    def _table(self, name, first_channel, count, dtype=np.uint32, per=1):
-        n = self.channels - int(first_channel) if count is None else int(count)
-        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
-        ct = C.c_float if dtype == np.float32 else C.c_uint32
-        self._chk(getattr(self.L, f"dspfx_gens_{name}")(self.h, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
-        return v
+        self._chk(self.L.dspfx_gens_reset(self.h, int(first_channel), self._n(first_channel, count)))
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
@@ -2313,11 +2219,7 @@ class ChannelGenerators(_Bank):
     def clocks(self):
         """float32[channels] on the device: every channel's clock, the phase carried between blocks; +0.0 without a node (valid
         after a run, on its stream)."""
-        import torch
-
-        class _Mem:
-            __cuda_array_interface__ = {"shape": (self.channels,), "typestr": "<f4", "data": (self._clock, False), "version": 2}
-        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+        return self._view(self._clock, (self.channels,))
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

@@ -1,8 +1,10 @@
-// bank_common.hip.h -- what the banks share (pitch, resample, spectrum, convolve, mixgroups, strips, mixmatrix _kernels.hip):
-// the desc's layout, 4-channel loads and stores in it, the slot copy, and small host helpers -- all stateless -- and the scaffold of
-// the three slider banks (mixgroups, strips, mixmatrix): the error holder, the shape / range / table checks of their arguments,
-// open_device and close_bank.  Host and device, hipcc only.  The FFT is in fft_core.hip.h, the slider banks' staged stores in
-// store_queue.hip.h.  A bank's struct, its ring and the rest of create / reset are its own.
+// bank_common.hip.h -- what the banks share (pitch, resample, spectrum, convolve, mixgroups, mixmatrix and the per-channel banks
+// strips, delays, talkers, dynamics, shapers, gens _kernels.hip): the desc's layout, 4-channel loads and stores in it, the slot copy,
+// and small host helpers -- all stateless -- and the scaffold of the banks that take live stores: the error holder, the shape /
+// range / table checks of their arguments, open_device, close_bank, release_bank and destroy_bank.  Host and device, hipcc only.
+// The FFT is in fft_core.hip.h, the staged stores in store_queue.hip.h, a lane's loads and stores of its own channels in
+// lane_io.hip.h, what the per-channel banks share beyond this in channel_bank.hip.h.  A bank's struct, its ring and the rest of
+// create / reset are its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 
@@ -121,7 +124,7 @@ hipError_t order(Bank *p, hipStream_t s) {
     return err;
 }
 
-// ---- the slider banks' scaffold -------------------------------------------------------------------------------------------
+// ---- the scaffold of the banks with stores -------------------------------------------------------------------------------------------
 // the reason of a bank's last failed call, for its *_last_error; a bank derives from it
 struct BankError {
     std::mutex emu;              // err: stores fail on any thread
@@ -223,6 +226,26 @@ void close_bank(Bank *p, void (*release)(Bank *)) {
         if (p->used) (void)hipStreamSynchronize(p->last);    // the bank's work is ordered on the last stream it used
     }
     release(p);
+}
+
+// a bank's `release`, where there is no more to it: the device pointers in `dev` (nullptr: never allocated), the staged stores'
+// buffers and events, the bank's event, the bank.  Bank has desc, stores (store_queue.hip.h) and ev
+template <class Bank>
+void release_bank(Bank *p, std::initializer_list<void *> dev) {
+    (void)hipSetDevice(p->desc.device);
+    for (void *d : dev)
+        if (d) (void)hipFree(d);
+    p->stores.free_all();
+    if (p->ev) (void)hipEventDestroy(p->ev);
+    delete p;
+}
+
+// the body of dspfx_<bank>_destroy
+template <class Bank>
+int destroy_bank(Bank *p, void (*release)(Bank *)) {
+    if (!p) return DSPFX_ERR_INVALID;
+    close_bank(p, release);
+    return DSPFX_OK;
 }
 
 }  // namespace

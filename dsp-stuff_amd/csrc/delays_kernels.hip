@@ -33,8 +33,8 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
-#include "bank_common.hip.h"
-#include "store_queue.hip.h"
+#include "channel_bank.hip.h"
+#include "lane_io.hip.h"
 
 namespace {
 
@@ -250,32 +250,19 @@ int plan(uint64_t N, float max_seconds, int page_round, uint32_t *cap_out, uint6
 
 }  // namespace
 
-struct dspfx_delays : BankError {
-    dspfx_delays_desc desc{};
+struct dspfx_delays : ChannelBank<dspfx_delays_desc, StoreFields> {
+    static constexpr const char *name = "delays";
     uint32_t cap = 0;
-    std::mutex mu;                               // run / reset / destroy
-    std::mutex smu;                              // one store at a time: it reads the host tables, then queues
-    Stores stores;                               // the slider stores; its qmu guards the host tables' writes and their readers
     std::vector<uint32_t> hlen;                  // D_c, 0: no node -- with every store made so far, as hsec and hdec
     std::vector<float> hsec, hdec;               // the sliders; 0.5 for a channel never stored (reverb.rs:29-38)
     float *ring = nullptr, *decay = nullptr;
     uint32_t *len = nullptr, *pos = nullptr, *zero = nullptr;
     float div = 1.0f;
-    hipEvent_t ev = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_delays *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->ring, (void *)p->decay, (void *)p->len, (void *)p->pos, (void *)p->zero})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_delays *p) { release_bank(p, {p->ring, p->decay, p->len, p->pos, p->zero}); }
 
 // one store onto the stream: its lengths and decays, then the new zero ring on its channels
 hipError_t apply_store(dspfx_delays *p, const Store &st, hipStream_t s) {
@@ -290,12 +277,6 @@ hipError_t apply_store(dspfx_delays *p, const Store &st, hipStream_t s) {
     return hipGetLastError();
 }
 
-int check_range(dspfx_delays *p, const char *what, uint64_t first, uint64_t count) {
-    std::string why;
-    const int rc = check_range("delays", what, first, count, p->desc.n_channels, why);
-    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
-}
-
 }  // namespace
 
 extern "C" const char *dspfx_delays_last_error(const dspfx_delays *p) { return p ? p->err.c_str() : g_err.c_str(); }
@@ -306,31 +287,19 @@ extern "C" int dspfx_delays_plan(uint64_t channels, float max_seconds, int page_
 }
 
 extern "C" int dspfx_delays_create(const dspfx_delays_desc *desc, dspfx_delays **out) {
-    if (!desc || !out) {
-        g_err = "delays: null argument";
-        return DSPFX_ERR_INVALID;
-    }
-    *out = nullptr;
-    g_err.clear();
     char buf[192];
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->max_frames == 0 || desc->max_frames > (1u << 20)) {
-        g_err = "delays: abi_version or max_frames";
-        return DSPFX_ERR_INVALID;
-    }
-    const uint32_t N = desc->n_channels;
-    int rc = check_shape("delays", N, desc->tile_channels, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (desc->link_flags & ~(DSPFX_LINK_INTERNAL | DSPFX_LINK_INPUT)) {
-        std::snprintf(buf, sizeof buf, "delays: unknown link flag in 0x%x (DSPFX_LINK_INTERNAL and DSPFX_LINK_INPUT are known)", desc->link_flags);
-        g_err = buf;
-        return DSPFX_ERR_INVALID;
-    }
     uint32_t cap = 0;
     uint64_t bytes = 0;
-    rc = plan(N, desc->max_seconds, (int)desc->page_round, &cap, &bytes, g_err);
+    const int rc = create_checks(desc, out, g_err, [&](std::string &err) -> int {
+        if (desc->link_flags & ~(DSPFX_LINK_INTERNAL | DSPFX_LINK_INPUT)) {
+            std::snprintf(buf, sizeof buf, "delays: unknown link flag in 0x%x (DSPFX_LINK_INTERNAL and DSPFX_LINK_INPUT are known)", desc->link_flags);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        return plan(desc->n_channels, desc->max_seconds, (int)desc->page_round, &cap, &bytes, err);
+    });
     if (rc != DSPFX_OK) return rc;
-    rc = open_device("delays", desc->device, &g_err);
-    if (rc != DSPFX_OK) return rc;
+    const uint32_t N = desc->n_channels;
     dspfx_delays *p = new (std::nothrow) dspfx_delays;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -368,11 +337,7 @@ extern "C" int dspfx_delays_create(const dspfx_delays_desc *desc, dspfx_delays *
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_delays_destroy(dspfx_delays *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_delays_destroy(dspfx_delays *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_delays_set_delay(dspfx_delays *p, const float *host_seconds, const float *host_decay, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
@@ -422,33 +387,19 @@ extern "C" int dspfx_delays_set_delay(dspfx_delays *p, const float *host_seconds
 }
 
 extern "C" int dspfx_delays_present(dspfx_delays *p, uint32_t *host_present_out, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!host_present_out) return p->fail(DSPFX_ERR_INVALID, "delays present: no array");
-    const int rc = check_range(p, "present", first_channel, count);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    for (uint64_t i = 0; i < count; ++i) host_present_out[i] = p->hlen[first_channel + i] != 0;
-    return DSPFX_OK;
+    return read_table(p, "present", host_present_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->hlen[c] != 0; });
 }
 
 extern "C" int dspfx_delays_lengths(dspfx_delays *p, uint32_t *host_lengths_out, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!host_lengths_out) return p->fail(DSPFX_ERR_INVALID, "delays lengths: no array");
-    const int rc = check_range(p, "lengths", first_channel, count);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    std::memcpy(host_lengths_out, p->hlen.data() + first_channel, count * sizeof(uint32_t));
-    return DSPFX_OK;
+    return read_table(p, "lengths", host_lengths_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->hlen[c]; });
 }
 
 extern "C" int dspfx_delays_run(dspfx_delays *p, const float *in, float *out, uint32_t n_frames, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "delays run: in, out or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
-    BANK_HIP_WHY(order(p, s), "stream order");
-    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "slider store");
+    const int rc = begin_run(p, in && out, n_frames, s, "delays run: in, out or n_frames", "slider store", apply_store);
+    if (rc != DSPFX_OK) return rc;
     DelayArgs a;
     a.in = in;
     a.out = out;
@@ -463,10 +414,8 @@ extern "C" int dspfx_delays_run(dspfx_delays *p, const float *in, float *out, ui
     a.flags = p->desc.link_flags;
     a.cap = p->cap;
     a.div = p->div;
-    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
-    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
-    const uint32_t blocks = (a.N + TC - 1) / TC;
-    if (vec) delays_run<true><<<blocks, WG, 0, s>>>(a);
+    const uint32_t blocks = (a.N + TC - 1) / TC;         // a workgroup takes TC channels; only the lane decision is lane_io's
+    if (lane_plan(a.N, a.W, (uintptr_t)in | (uintptr_t)out, WG).vec) delays_run<true><<<blocks, WG, 0, s>>>(a);
     else delays_run<false><<<blocks, WG, 0, s>>>(a);
     BANK_HIP_WHY(hipGetLastError(), "delays_run");
     return DSPFX_OK;

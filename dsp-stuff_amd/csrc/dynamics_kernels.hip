@@ -5,8 +5,7 @@
 //
 // One run is one kernel behind the queued stores, in the shape of talkers_run (talkers_kernels.hip): time is a serial recurrence
 // per channel, so a lane owns its channels for the whole block -- four adjacent channels with one 16-byte load and one nontemporal
-// 16-byte store per frame when the layout allows it (bank_common's load4 / store4 with vec = 1, on the lane's own address), one
-// channel otherwise.  Frames are taken in chunks of F rows and the next chunk's loads are issued ahead of this one's arithmetic,
+// 16-byte store per frame when the layout allows it (lane_io.hip.h), one channel otherwise.  Frames are taken in chunks of F rows and the next chunk's loads are issued ahead of this one's arithmetic,
 // so the chain env -> env does not wait for memory; a keyed run holds two such streams and takes chunks half as long, the same
 // registers.  Per frame: the envelope as K_ENVELOPE computes it (chain_kernels.hip.h), q = env > thr ? thr / env : 1 with one IEEE
 // division, the sample times mk * q, the block's largest envelope into `level` and its smallest q into `reduction`.  The tables are
@@ -25,8 +24,8 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
-#include "bank_common.hip.h"
-#include "store_queue.hip.h"
+#include "channel_bank.hip.h"
+#include "lane_io.hip.h"
 
 namespace {
 
@@ -41,50 +40,6 @@ struct DynArgs {
     const uint8_t *pres;         // [N]: 1 where the channel carries a node
     uint32_t N, W, nf;
 };
-
-// CPL adjacent values at p (aligned to CPL values) in one load / one store: the four-channel form is what load4 and store4 of
-// bank_common do with vec = 1, on the lane's own address.  (These four helpers are talkers_kernels.hip's; that file is left as it
-// is, so they are not shared yet)
-template <int CPL, typename T>
-__device__ __forceinline__ void loadv(const T *p, T (&o)[CPL]) {
-    typedef T vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        o[0] = *p;
-    } else {
-        const vec t = *(const vec *)p;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) o[j] = t[j];
-    }
-}
-
-template <int CPL, bool NT>
-__device__ __forceinline__ void storev(float *p, const float (&o)[CPL]) {
-    typedef float vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        if (NT) __builtin_nontemporal_store(o[0], p);
-        else *p = o[0];
-    } else {
-        vec t;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) t[j] = o[j];
-        if (NT) __builtin_nontemporal_store(t, (vec *)p);
-        else *(vec *)p = t;
-    }
-}
-
-// R rows from frame f0 of the lane's channels; `lane` is the lane's element of frame 0 (bank_common's lay(0, c, ..)), a frame
-// further is `rs` elements on in either layout, so no row pays lay()'s division
-template <int CPL, int R>
-__device__ __forceinline__ void load_rows(const float *lane, size_t rs, uint32_t f0, float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) loadv<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
-
-template <int CPL, int R>
-__device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) storev<CPL, true>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
 
 // the lane's state over a block
 template <int CPL>
@@ -210,30 +165,17 @@ uint64_t table_bytes(uint64_t N) { return 29 * N; }
 
 }  // namespace
 
-struct dspfx_dynamics : BankError {
-    dspfx_dynamics_desc desc{};
-    std::mutex mu;                               // run / destroy
-    std::mutex smu;                              // one store at a time: it reads the host tables, then queues
-    Stores stores;                               // its qmu guards the host tables' writes and their readers
+struct dspfx_dynamics : ChannelBank<dspfx_dynamics_desc, StoreFields> {
+    static constexpr const char *name = "dynamics";
     std::vector<float> hga, hgr, hthr, hmk;      // [N]: the sliders with every store made so far (a NULL slider keeps them)
     std::vector<uint8_t> hpres;                  // [N]
     float *env = nullptr, *level = nullptr, *red = nullptr, *ga = nullptr, *gr = nullptr, *thr = nullptr, *mk = nullptr;
     uint8_t *pres = nullptr;
-    hipEvent_t ev = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_dynamics *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->env, (void *)p->level, (void *)p->red, (void *)p->ga, (void *)p->gr, (void *)p->thr, (void *)p->mk, (void *)p->pres})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_dynamics *p) { release_bank(p, {p->env, p->level, p->red, p->ga, p->gr, p->thr, p->mk, p->pres}); }
 
 // one store onto the stream
 hipError_t apply_store(dspfx_dynamics *p, const Store &st, hipStream_t s) {
@@ -257,33 +199,6 @@ hipError_t apply_store(dspfx_dynamics *p, const Store &st, hipStream_t s) {
     return hipSuccess;
 }
 
-int check_range(dspfx_dynamics *p, const char *what, uint64_t first, uint64_t count) {
-    std::string why;
-    const int rc = check_range("dynamics", what, first, count, p->desc.n_channels, why);
-    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
-}
-
-// a store without values over a range
-int store_plain(dspfx_dynamics *p, StoreKind kind, const char *call, uint64_t first, uint64_t count) {
-    const int rc = check_range(p, call, first, count);
-    if (rc != DSPFX_OK) return rc;
-    if (count == 0) return DSPFX_OK;
-    Store st;
-    st.kind = kind;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    p->stores.push(st, [&] {
-        if (kind != ST_DROP) return;
-        for (uint64_t c = first; c < first + count; ++c) {         // a later store meets the defaults again
-            p->hga[c] = p->hgr[c] = 0.0f;
-            p->hthr[c] = p->hmk[c] = 1.0f;
-            p->hpres[c] = 0;
-        }
-    });
-    return DSPFX_OK;
-}
-
 }  // namespace
 
 extern "C" const char *dspfx_dynamics_last_error(const dspfx_dynamics *p) { return p ? p->err.c_str() : g_err.c_str(); }
@@ -303,21 +218,9 @@ extern "C" int dspfx_dynamics_plan(uint64_t channels, uint64_t *bytes_out) {
 }
 
 extern "C" int dspfx_dynamics_create(const dspfx_dynamics_desc *desc, dspfx_dynamics **out) {
-    if (!desc || !out) {
-        g_err = "dynamics: null argument";
-        return DSPFX_ERR_INVALID;
-    }
-    *out = nullptr;
-    g_err.clear();
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->max_frames == 0 || desc->max_frames > (1u << 20)) {
-        g_err = "dynamics: abi_version or max_frames";
-        return DSPFX_ERR_INVALID;
-    }
+    const int rc = create_checks(desc, out, g_err);
+    if (rc != DSPFX_OK) return rc;
     const uint32_t N = desc->n_channels;
-    int rc = check_shape("dynamics", N, desc->tile_channels, g_err);
-    if (rc != DSPFX_OK) return rc;
-    rc = open_device("dynamics", desc->device, &g_err);
-    if (rc != DSPFX_OK) return rc;
     dspfx_dynamics *p = new (std::nothrow) dspfx_dynamics;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -339,10 +242,7 @@ extern "C" int dspfx_dynamics_create(const dspfx_dynamics_desc *desc, dspfx_dyna
     if (!ok) {
         (void)hipGetLastError();
         release(p);
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "dynamics: no device memory for %llu bytes of tables (%u channels)", (unsigned long long)table_bytes(N), N);
-        g_err = buf;
-        return DSPFX_ERR_OOM;
+        return no_table_memory("dynamics", table_bytes(N), N, g_err);
     }
     // the fresh state: no node anywhere
     dynamics_fresh<<<(N + WG - 1) / WG, WG>>>(p->env, p->level, p->red, 0u, N);
@@ -357,11 +257,7 @@ extern "C" int dspfx_dynamics_create(const dspfx_dynamics_desc *desc, dspfx_dyna
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_dynamics_destroy(dspfx_dynamics *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_dynamics_destroy(dspfx_dynamics *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_dynamics_set(dspfx_dynamics *p, const float *host_threshold, const float *host_makeup, const float *host_attack,
                                   const float *host_release, uint64_t first_channel, uint64_t count) {
@@ -407,23 +303,21 @@ extern "C" int dspfx_dynamics_set(dspfx_dynamics *p, const float *host_threshold
 }
 
 extern "C" int dspfx_dynamics_drop(dspfx_dynamics *p, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    return store_plain(p, ST_DROP, "drop", first_channel, count);
+    return store_plain(p, ST_DROP, "drop", first_channel, count, [=] {
+        for (uint64_t c = first_channel; c < first_channel + count; ++c) {     // a later store meets the defaults again
+            p->hga[c] = p->hgr[c] = 0.0f;
+            p->hthr[c] = p->hmk[c] = 1.0f;
+            p->hpres[c] = 0;
+        }
+    });
 }
 
 extern "C" int dspfx_dynamics_reset(dspfx_dynamics *p, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
     return store_plain(p, ST_RESET, "reset", first_channel, count);
 }
 
 extern "C" int dspfx_dynamics_present(dspfx_dynamics *p, uint32_t *host_present_out, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!host_present_out) return p->fail(DSPFX_ERR_INVALID, "dynamics present: no array");
-    const int rc = check_range(p, "present", first_channel, count);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    for (uint64_t i = 0; i < count; ++i) host_present_out[i] = p->hpres[first_channel + i];
-    return DSPFX_OK;
+    return read_table(p, "present", host_present_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->hpres[c]; });
 }
 
 extern "C" int dspfx_dynamics_views(dspfx_dynamics *p, const float **level_out, const float **reduction_out) {
@@ -436,11 +330,9 @@ extern "C" int dspfx_dynamics_views(dspfx_dynamics *p, const float **level_out, 
 extern "C" int dspfx_dynamics_run(dspfx_dynamics *p, const float *in, const float *key, float *out, uint32_t n_frames, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "dynamics run: in, out or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
-    BANK_HIP_WHY(order(p, s), "stream order");
-    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "dynamics store");
+    const int rc = begin_run(p, in && out, n_frames, s, "dynamics run: in, out or n_frames", "dynamics store", apply_store);
+    if (rc != DSPFX_OK) return rc;
     if (key == in) key = nullptr;                // the detector follows the block itself: one stream of loads
     DynArgs a;
     a.in = in;
@@ -457,9 +349,7 @@ extern "C" int dspfx_dynamics_run(dspfx_dynamics *p, const float *in, const floa
     a.N = p->desc.n_channels;
     a.W = p->desc.tile_channels;
     a.nf = n_frames;
-    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
-    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out) | ((uintptr_t)key)) & 15u) == 0;
-    const uint32_t lanes = vec ? a.N / 4 : a.N, blocks = (lanes + WG - 1) / WG;
+    const auto [vec, lanes, blocks] = lane_plan(a.N, a.W, (uintptr_t)in | (uintptr_t)out | (uintptr_t)key, WG);
     if (vec && key) dynamics_run<4, true><<<blocks, WG, 0, s>>>(a);
     else if (vec) dynamics_run<4, false><<<blocks, WG, 0, s>>>(a);
     else if (key) dynamics_run<1, true><<<blocks, WG, 0, s>>>(a);

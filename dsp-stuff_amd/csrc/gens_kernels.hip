@@ -29,9 +29,9 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
-#include "bank_common.hip.h"
 #include "chain_kernels.hip.h"
-#include "store_queue.hip.h"
+#include "channel_bank.hip.h"
+#include "lane_io.hip.h"
 
 namespace {
 
@@ -49,57 +49,6 @@ struct GenArgs {
     const uint8_t *code;         // [N]
     uint32_t N, W, nf;
 };
-
-// CPL adjacent values at p (aligned to CPL values) in one load / one store (shapers_kernels.hip's helpers; that file is left as it is)
-template <int CPL, typename T>
-__device__ __forceinline__ void loadv(const T *p, T (&o)[CPL]) {
-    typedef T vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        o[0] = *p;
-    } else {
-        const vec t = *(const vec *)p;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) o[j] = t[j];
-    }
-}
-
-template <int CPL>
-__device__ __forceinline__ void storev(float *p, const float (&o)[CPL]) {
-    typedef float vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        *p = o[0];
-    } else {
-        vec t;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) t[j] = o[j];
-        *(vec *)p = t;
-    }
-}
-
-template <int CPL>
-__device__ __forceinline__ void storev_nt(float *p, const float (&o)[CPL]) {
-    typedef float vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        __builtin_nontemporal_store(o[0], p);
-    } else {
-        vec t;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) t[j] = o[j];
-        __builtin_nontemporal_store(t, (vec *)p);
-    }
-}
-
-template <int CPL, int R>
-__device__ __forceinline__ void load_rows(const float *lane, size_t rs, uint32_t f0, float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) loadv<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
-
-template <int CPL, int R>
-__device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) storev_nt<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
 
 // the lane's channels over a run
 template <int CPL>
@@ -255,7 +204,7 @@ __global__ __launch_bounds__(GWG) void gens_run(GenArgs a) {
         store_rows<CPL, 1>(l.out, l.rs, f, v);
     }
     if (clocked && (a.nf & 127u)) close_block<CPL>(s);     // the run stops inside a block
-    if (runs) storev<CPL>(a.clock + c, s.clock);
+    if (runs) storev<CPL, false>(a.clock + c, s.clock);
 }
 
 thread_local std::string g_err;        // the reason of the last failed create or plan on this thread
@@ -275,30 +224,17 @@ uint64_t table_bytes(uint64_t N) { return 13 * N; }
 
 }  // namespace
 
-struct dspfx_gens : BankError {
-    dspfx_gens_desc desc{};
-    std::mutex mu;                               // run / destroy
-    std::mutex smu;                              // one store at a time: it reads the host tables, then queues
-    Stores stores;                               // its qmu guards the host tables' writes and their readers
+struct dspfx_gens : ChannelBank<dspfx_gens_desc, StoreFields> {
+    static constexpr const char *name = "gens";
     std::vector<float> hamp, hfreq;              // [N] each: the sliders with every store made so far
     std::vector<uint8_t> hcode;                  // [N]: ... and the mode / presence bytes
     float *amp = nullptr, *freq = nullptr, *clock = nullptr;
     uint8_t *code = nullptr;
-    hipEvent_t ev = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_gens *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->amp, (void *)p->freq, (void *)p->clock, (void *)p->code})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_gens *p) { release_bank(p, {p->amp, p->freq, p->clock, p->code}); }
 
 // one store onto the stream (the bank's mu is held).  A channel without a node has clock +0.0 at all times, so SET writes no clock
 hipError_t apply_store(dspfx_gens *p, const Store &st, hipStream_t s) {
@@ -321,45 +257,6 @@ hipError_t apply_store(dspfx_gens *p, const Store &st, hipStream_t s) {
     return err;
 }
 
-int check_range(dspfx_gens *p, const char *what, uint64_t first, uint64_t count) {
-    std::string why;
-    const int rc = check_range("gens", what, first, count, p->desc.n_channels, why);
-    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
-}
-
-// a store without values over a range
-int store_plain(dspfx_gens *p, const char *call, StoreKind kind, uint64_t first, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    const int rc = check_range(p, call, first, count);
-    if (rc != DSPFX_OK) return rc;
-    if (count == 0) return DSPFX_OK;
-    Store st;
-    st.kind = kind;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    p->stores.push(st, [&] {
-        if (kind != ST_DROP) return;
-        for (uint64_t c = first; c < first + count; ++c) {     // a later store meets no node: the defaults again
-            p->hamp[c] = p->hfreq[c] = 0.0f;
-            p->hcode[c] = C_NONE;
-        }
-    });
-    return DSPFX_OK;
-}
-
-// a host table over a range, as every store made so far left it
-template <class T, class Get>
-int read_table(dspfx_gens *p, const char *call, T *out, uint64_t first, uint64_t count, Get get) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!out) return p->fail(DSPFX_ERR_INVALID, (std::string("gens ") + call + ": no array").c_str());
-    const int rc = check_range(p, call, first, count);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    for (uint64_t i = 0; i < count; ++i) get(out, i, first + i);
-    return DSPFX_OK;
-}
-
 }  // namespace
 
 extern "C" const char *dspfx_gens_last_error(const dspfx_gens *p) { return p ? p->err.c_str() : g_err.c_str(); }
@@ -373,21 +270,9 @@ extern "C" int dspfx_gens_plan(uint64_t channels, uint64_t *bytes_out) {
 }
 
 extern "C" int dspfx_gens_create(const dspfx_gens_desc *desc, dspfx_gens **out) {
-    if (!desc || !out) {
-        g_err = "gens: null argument";
-        return DSPFX_ERR_INVALID;
-    }
-    *out = nullptr;
-    g_err.clear();
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->max_frames == 0 || desc->max_frames > (1u << 20)) {
-        g_err = "gens: abi_version or max_frames";
-        return DSPFX_ERR_INVALID;
-    }
+    const int rc = create_checks(desc, out, g_err);
+    if (rc != DSPFX_OK) return rc;
     const uint32_t N = desc->n_channels;
-    int rc = check_shape("gens", N, desc->tile_channels, g_err);
-    if (rc != DSPFX_OK) return rc;
-    rc = open_device("gens", desc->device, &g_err);
-    if (rc != DSPFX_OK) return rc;
     dspfx_gens *p = new (std::nothrow) dspfx_gens;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -405,10 +290,7 @@ extern "C" int dspfx_gens_create(const dspfx_gens_desc *desc, dspfx_gens **out) 
     if (!ok) {
         (void)hipGetLastError();
         release(p);
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "gens: no device memory for %llu bytes of tables (%u channels)", (unsigned long long)table_bytes(N), N);
-        g_err = buf;
-        return DSPFX_ERR_OOM;
+        return no_table_memory("gens", table_bytes(N), N, g_err);
     }
     // the fresh state: no node anywhere, every clock +0.0
     ok = hipMemset(p->amp, 0, tab) == hipSuccess && hipMemset(p->freq, 0, tab) == hipSuccess && hipMemset(p->clock, 0, tab) == hipSuccess &&
@@ -422,11 +304,7 @@ extern "C" int dspfx_gens_create(const dspfx_gens_desc *desc, dspfx_gens **out) 
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_gens_destroy(dspfx_gens *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_gens_destroy(dspfx_gens *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_gens_set(dspfx_gens *p, const float *host_amplitude, const float *host_frequency, const uint32_t *host_mode,
                               uint64_t first_channel, uint64_t count) {
@@ -467,9 +345,16 @@ extern "C" int dspfx_gens_set(dspfx_gens *p, const float *host_amplitude, const 
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_gens_drop(dspfx_gens *p, uint64_t first_channel, uint64_t count) { return store_plain(p, "drop", ST_DROP, first_channel, count); }
+extern "C" int dspfx_gens_drop(dspfx_gens *p, uint64_t first_channel, uint64_t count) {
+    return store_plain(p, ST_DROP, "drop", first_channel, count, [=] {
+        for (uint64_t c = first_channel; c < first_channel + count; ++c) {     // a later store meets no node: the defaults again
+            p->hamp[c] = p->hfreq[c] = 0.0f;
+            p->hcode[c] = C_NONE;
+        }
+    });
+}
 
-extern "C" int dspfx_gens_reset(dspfx_gens *p, uint64_t first_channel, uint64_t count) { return store_plain(p, "reset", ST_RESET, first_channel, count); }
+extern "C" int dspfx_gens_reset(dspfx_gens *p, uint64_t first_channel, uint64_t count) { return store_plain(p, ST_RESET, "reset", first_channel, count); }
 
 extern "C" int dspfx_gens_present(dspfx_gens *p, uint32_t *host_present_out, uint64_t first_channel, uint64_t count) {
     return read_table(p, "present", host_present_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->hcode[c] != C_NONE; });
@@ -498,11 +383,9 @@ extern "C" int dspfx_gens_run(dspfx_gens *p, const float *add_to, const float *a
                               void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "gens run: out or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
-    BANK_HIP_WHY(order(p, s), "stream order");
-    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "gens store");
+    const int rc = begin_run(p, out != nullptr, n_frames, s, "gens run: out or n_frames", "gens store", apply_store);
+    if (rc != DSPFX_OK) return rc;
     GenArgs a;
     a.add = add_to;
     a.cam = amplitude;
@@ -515,10 +398,8 @@ extern "C" int dspfx_gens_run(dspfx_gens *p, const float *add_to, const float *a
     a.N = p->desc.n_channels;
     a.W = p->desc.tile_channels;
     a.nf = n_frames;
-    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
-    const uintptr_t bits = (uintptr_t)out | (uintptr_t)add_to | (uintptr_t)amplitude | (uintptr_t)frequency;
-    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && (bits & 15u) == 0, ctl = amplitude || frequency;
-    const uint32_t lanes = vec ? a.N / 4 : a.N, blocks = (lanes + GWG - 1) / GWG;
+    const auto [vec, lanes, blocks] = lane_plan(a.N, a.W, (uintptr_t)out | (uintptr_t)add_to | (uintptr_t)amplitude | (uintptr_t)frequency, GWG);
+    const bool ctl = amplitude || frequency;
     if (vec && ctl) gens_run<4, true><<<blocks, GWG, 0, s>>>(a);
     else if (vec) gens_run<4, false><<<blocks, GWG, 0, s>>>(a);
     else if (ctl) gens_run<1, true><<<blocks, GWG, 0, s>>>(a);

@@ -968,11 +968,7 @@ extern "C" int dspfx_mixgroups_create(const dspfx_mixgroups_desc *desc, dspfx_mi
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_mixgroups_destroy(dspfx_mixgroups *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_mixgroups_destroy(dspfx_mixgroups *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_mixgroups_set_gains(dspfx_mixgroups *p, const float *host_values, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;

@@ -885,15 +885,7 @@ struct dspfx_mixmatrix : BankError {
 
 namespace {
 
-void release(dspfx_mixmatrix *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->tab, (void *)p->div, (void *)p->stage, (void *)p->rooms, (void *)p->items, (void *)p->room_of, (void *)p->seat_chan,
-                    (void *)p->slot_of, (void *)p->sbuf})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_mixmatrix *p) { release_bank(p, {p->tab, p->div, p->stage, p->rooms, p->items, p->room_of, p->seat_chan, p->slot_of, p->sbuf}); }
 
 // the room and the room-local index (the seat, in a seated bank) of channel c; smu is held on a seated bank
 void place_of(dspfx_mixmatrix *p, uint32_t c, uint32_t &room, uint32_t &index) {
@@ -1459,11 +1451,7 @@ extern "C" int dspfx_mixmatrix_occupancy(dspfx_mixmatrix *p, uint32_t *host_coun
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_mixmatrix_destroy(dspfx_mixmatrix *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_mixmatrix_destroy(dspfx_mixmatrix *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_mixmatrix_set_rows(dspfx_mixmatrix *p, const float *host_values, uint32_t row_len, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;

@@ -33,9 +33,9 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
-#include "bank_common.hip.h"
 #include "chain_kernels.hip.h"
-#include "store_queue.hip.h"
+#include "channel_bank.hip.h"
+#include "lane_io.hip.h"
 
 namespace {
 
@@ -51,44 +51,6 @@ struct ShapeArgs {
     const uint8_t *code;         // [N]
     uint32_t N, W, nf;
 };
-
-// CPL adjacent values at p (aligned to CPL values) in one load / one store (dynamics_kernels.hip's helpers; that file is left as it is)
-template <int CPL, typename T>
-__device__ __forceinline__ void loadv(const T *p, T (&o)[CPL]) {
-    typedef T vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        o[0] = *p;
-    } else {
-        const vec t = *(const vec *)p;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) o[j] = t[j];
-    }
-}
-
-template <int CPL>
-__device__ __forceinline__ void storev_nt(float *p, const float (&o)[CPL]) {
-    typedef float vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        __builtin_nontemporal_store(o[0], p);
-    } else {
-        vec t;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) t[j] = o[j];
-        __builtin_nontemporal_store(t, (vec *)p);
-    }
-}
-
-template <int CPL, int R>
-__device__ __forceinline__ void load_rows(const float *lane, size_t rs, uint32_t f0, float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) loadv<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
-
-template <int CPL, int R>
-__device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) storev_nt<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
 
 // the lane's channels over a run.  code: the kind with the bypasses folded in (C_NONE: a copy in this kernel).  Chebyshev keeps
 // tanh(level_pos) in p2 and tanh(level_neg) in p3
@@ -294,11 +256,8 @@ uint32_t code_mode(uint8_t k) { return k >= C_DIST && k < C_OVER ? (uint32_t)(k 
 
 }  // namespace
 
-struct dspfx_shapers : BankError {
-    dspfx_shapers_desc desc{};
-    std::mutex mu;                               // run / destroy; also rcode, run_fuzz and run_heavy
-    std::mutex smu;                              // one store at a time: it reads the host tables, then queues
-    Stores stores;                               // its qmu guards the host tables' writes and their readers
+struct dspfx_shapers : ChannelBank<dspfx_shapers_desc, StoreFields> {        // mu: also rcode, run_fuzz and run_heavy
+    static constexpr const char *name = "shapers";
     std::vector<float> hp[3];                    // [N] each: the sliders with every store made so far
     std::vector<uint8_t> hcode;                  // [N]: ... and the kind codes
     // what the device tables hold once the stores DRAINED so far have run -- not the stores made so far: the second launch and
@@ -308,21 +267,11 @@ struct dspfx_shapers : BankError {
     uint64_t run_heavy = 0;                      // ... and those of a kind that evaluates in f64: which run kernel
     float *p[3] = {nullptr, nullptr, nullptr};
     uint8_t *code = nullptr;
-    hipEvent_t ev = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_shapers *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->p[0], (void *)p->p[1], (void *)p->p[2], (void *)p->code})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_shapers *p) { release_bank(p, {p->p[0], p->p[1], p->p[2], p->code}); }
 
 // one store onto the stream (the bank's mu is held): the device tables, and the run-order kind table beside them
 hipError_t apply_store(dspfx_shapers *p, const Store &st, hipStream_t s) {
@@ -340,12 +289,6 @@ hipError_t apply_store(dspfx_shapers *p, const Store &st, hipStream_t s) {
     for (int t = 0; t < 3 && err == hipSuccess; ++t) err = hipMemcpyAsync(p->p[t] + st.first, st.vals + t * n, bytes, hipMemcpyHostToDevice, s);
     if (err == hipSuccess) err = hipMemcpyAsync(p->code + st.first, codes, n, hipMemcpyHostToDevice, s);
     return err;
-}
-
-int check_range(dspfx_shapers *p, const char *what, uint64_t first, uint64_t count) {
-    std::string why;
-    const int rc = check_range("shapers", what, first, count, p->desc.n_channels, why);
-    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
 }
 
 // a store of one family over a range: vals[t] (NULL: keep, or the default where the channel carries another family or none) are the
@@ -405,21 +348,9 @@ extern "C" int dspfx_shapers_plan(uint64_t channels, uint64_t *bytes_out) {
 }
 
 extern "C" int dspfx_shapers_create(const dspfx_shapers_desc *desc, dspfx_shapers **out) {
-    if (!desc || !out) {
-        g_err = "shapers: null argument";
-        return DSPFX_ERR_INVALID;
-    }
-    *out = nullptr;
-    g_err.clear();
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->max_frames == 0 || desc->max_frames > (1u << 20)) {
-        g_err = "shapers: abi_version or max_frames";
-        return DSPFX_ERR_INVALID;
-    }
+    const int rc = create_checks(desc, out, g_err);
+    if (rc != DSPFX_OK) return rc;
     const uint32_t N = desc->n_channels;
-    int rc = check_shape("shapers", N, desc->tile_channels, g_err);
-    if (rc != DSPFX_OK) return rc;
-    rc = open_device("shapers", desc->device, &g_err);
-    if (rc != DSPFX_OK) return rc;
     dspfx_shapers *p = new (std::nothrow) dspfx_shapers;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -437,10 +368,7 @@ extern "C" int dspfx_shapers_create(const dspfx_shapers_desc *desc, dspfx_shaper
     if (!ok) {
         (void)hipGetLastError();
         release(p);
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "shapers: no device memory for %llu bytes of tables (%u channels)", (unsigned long long)table_bytes(N), N);
-        g_err = buf;
-        return DSPFX_ERR_OOM;
+        return no_table_memory("shapers", table_bytes(N), N, g_err);
     }
     // the fresh state: no node anywhere
     ok = hipMemset(p->p[0], 0, tab) == hipSuccess && hipMemset(p->p[1], 0, tab) == hipSuccess && hipMemset(p->p[2], 0, tab) == hipSuccess &&
@@ -454,11 +382,7 @@ extern "C" int dspfx_shapers_create(const dspfx_shapers_desc *desc, dspfx_shaper
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_shapers_destroy(dspfx_shapers *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_shapers_destroy(dspfx_shapers *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_shapers_set_distort(dspfx_shapers *p, const float *host_level, const uint32_t *host_mode, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
@@ -481,39 +405,13 @@ extern "C" int dspfx_shapers_set_chebyshev(dspfx_shapers *p, const float *host_l
 }
 
 extern "C" int dspfx_shapers_drop(dspfx_shapers *p, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    const int rc = check_range(p, "drop", first_channel, count);
-    if (rc != DSPFX_OK) return rc;
-    if (count == 0) return DSPFX_OK;
-    Store st;
-    st.kind = ST_DROP;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    p->stores.push(st, [&] {
+    return store_plain(p, ST_DROP, "drop", first_channel, count, [=] {
         for (uint64_t c = first_channel; c < first_channel + count; ++c) {     // a later store meets no node: the defaults again
             p->hp[0][c] = p->hp[1][c] = p->hp[2][c] = 0.0f;
             p->hcode[c] = C_NONE;
         }
     });
-    return DSPFX_OK;
 }
-
-namespace {
-
-// a host table over a range, as every store made so far left it
-template <class T, class Get>
-int read_table(dspfx_shapers *p, const char *call, T *out, uint64_t first, uint64_t count, Get get) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!out) return p->fail(DSPFX_ERR_INVALID, (std::string("shapers ") + call + ": no array").c_str());
-    const int rc = check_range(p, call, first, count);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    for (uint64_t i = 0; i < count; ++i) get(out, i, first + i);
-    return DSPFX_OK;
-}
-
-}  // namespace
 
 extern "C" int dspfx_shapers_present(dspfx_shapers *p, uint32_t *host_present_out, uint64_t first_channel, uint64_t count) {
     return read_table(p, "present", host_present_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->hcode[c] != C_NONE; });
@@ -536,11 +434,9 @@ extern "C" int dspfx_shapers_sliders(dspfx_shapers *p, float *host_sliders_out, 
 extern "C" int dspfx_shapers_run(dspfx_shapers *p, const float *in, float *out, uint32_t n_frames, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "shapers run: in, out or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
-    BANK_HIP_WHY(order(p, s), "stream order");
-    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "shapers store");
+    const int rc = begin_run(p, in && out, n_frames, s, "shapers run: in, out or n_frames", "shapers store", apply_store);
+    if (rc != DSPFX_OK) return rc;
     // by the tables this run has drained (run_fuzz), not by the stores made so far
     if (p->run_fuzz && n_frames % DSPFX_BUF_SIZE) {
         char buf[160];
@@ -558,9 +454,7 @@ extern "C" int dspfx_shapers_run(dspfx_shapers *p, const float *in, float *out, 
     a.N = p->desc.n_channels;
     a.W = p->desc.tile_channels;
     a.nf = n_frames;
-    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
-    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
-    const uint32_t lanes = vec ? a.N / 4 : a.N, blocks = (lanes + SWG - 1) / SWG;
+    const auto [vec, lanes, blocks] = lane_plan(a.N, a.W, (uintptr_t)in | (uintptr_t)out, SWG);
     if (vec && p->run_heavy) shapers_run<4, true><<<blocks, SWG, 0, s>>>(a);
     else if (vec) shapers_run<4, false><<<blocks, SWG, 0, s>>>(a);
     else if (p->run_heavy) shapers_run<1, true><<<blocks, SWG, 0, s>>>(a);

@@ -4,7 +4,7 @@
 //
 // One streaming pass: the block is read once and written once.  Time is a serial recurrence per channel, so a lane owns its
 // channels for the whole block: four adjacent channels with one 16-byte load and one nontemporal 16-byte store per frame when
-// the layout allows it (bank_common's vec), one channel otherwise -- and at K > 4, where the coefficients and the state of four
+// the layout allows it (lane_io.hip.h), one channel otherwise -- and at K > 4, where the coefficients and the state of four
 // channels (9 x 4 x 8 values) no longer fit in registers beside the frames.  A lane's coefficients ([band][5][N]), state
 // ([band][4][N]), level ([N]) and node mask ([N]) are read once per block into registers; adjacent lanes read adjacent
 // addresses in all of them.  Frames are taken in chunks of F rows; the next chunk's loads are issued before the arithmetic of
@@ -26,8 +26,8 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
-#include "bank_common.hip.h"
-#include "store_queue.hip.h"
+#include "channel_bank.hip.h"
+#include "lane_io.hip.h"
 
 namespace {
 
@@ -44,50 +44,6 @@ struct StripArgs {
     uint32_t N, W, nf, flags;
     float div;                   // f32(0.0001 + 1.0)
 };
-
-// CPL adjacent values at p (aligned to CPL floats) in one load / one store; NT: nontemporal
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int CPL, typename T>
-__device__ __forceinline__ void loadv(const T *p, T (&o)[CPL]) {
-    typedef T vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        o[0] = *p;
-    } else {
-        const vec t = *(const vec *)p;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) o[j] = t[j];
-    }
-}
-
-template <int CPL, bool NT>
-__device__ __forceinline__ void storev(float *p, const float (&o)[CPL]) {
-    typedef float vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        if (NT) __builtin_nontemporal_store(o[0], p);
-        else *p = o[0];
-    } else {
-        vec t;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) t[j] = o[j];
-        if (NT) __builtin_nontemporal_store(t, (vec *)p);
-        else *(vec *)p = t;
-    }
-}
-
-// F whole rows from frame f0 of the lane's channels.  `lane`: the lane's element of frame 0 (bank_common's lay(0, c, ..)); a frame
-// further is `rs` elements on in either layout, so no row pays lay()'s division.  The four-channel form is what load4 and
-// store4<true> of bank_common do with vec = 1, on that address
-template <int CPL, int F>
-__device__ __forceinline__ void load_rows(const float *lane, size_t rs, uint32_t f0, float (&v)[F][CPL]) {
-#pragma unroll
-    for (int i = 0; i < F; ++i) loadv<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
-
-template <int CPL, int F>
-__device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[F][CPL]) {
-#pragma unroll
-    for (int i = 0; i < F; ++i) storev<CPL, true>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
 
 // a where the mask is all ones, b where it is zero: one v_bfi_b32.  Not `on ? a : b`, which the compiler turns into a divergent
 // branch around the arithmetic that makes a -- one branch per frame and channel
@@ -279,30 +235,18 @@ uint32_t bands_built(uint32_t K) { return K <= 1 ? 1u : K <= 2 ? 2u : K <= 4 ? 4
 
 }  // namespace
 
-struct dspfx_strips : BankError {
-    dspfx_strips_desc desc{};
+struct dspfx_strips : ChannelBank<dspfx_strips_desc, StoreFields> {        // stores.qmu guards hmask too
+    static constexpr const char *name = "strips";
     uint32_t KB = 1;                             // the kernel's band count: 1, 2, 4 or 8
-    std::mutex mu;                               // run / reset / destroy
-    Stores stores;                               // the slider stores; its qmu guards hmask too
     std::vector<uint32_t> hmask;                 // the node masks with every store made so far (stores.qmu): what the next run sees
     float *coef = nullptr, *state = nullptr, *level = nullptr;
     uint32_t *mask = nullptr;
     float div = 1.0f;
-    hipEvent_t ev = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_strips *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->coef, (void *)p->state, (void *)p->level, (void *)p->mask})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_strips *p) { release_bank(p, {p->coef, p->state, p->level, p->mask}); }
 
 // one store onto the stream: its values, then the node bit (and a band's zeroed state) on its channels
 hipError_t apply_store(dspfx_strips *p, const Store &st, hipStream_t s) {
@@ -328,12 +272,6 @@ hipError_t apply_store(dspfx_strips *p, const Store &st, hipStream_t s) {
     return hipGetLastError();
 }
 
-int check_range(dspfx_strips *p, const char *what, uint64_t first, uint64_t count) {
-    std::string why;
-    const int rc = check_range("strips", what, first, count, p->desc.n_channels, why);
-    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
-}
-
 // the store joins the queue and the masks the next run will see
 void enqueue(dspfx_strips *p, const Store &st) {
     p->stores.push(st, [&] {
@@ -348,8 +286,7 @@ void enqueue(dspfx_strips *p, const Store &st) {
 // the lane width per band count: four channels while their coefficients and state fit in registers beside the rows, then two, then one
 template <int KB, int CPL>
 hipError_t launch(const StripArgs &a, hipStream_t s) {
-    const uint32_t lanes = (a.N + CPL - 1) / CPL, blocks = (lanes + WG - 1) / WG;
-    strips_run<KB, CPL><<<blocks, WG, 0, s>>>(a);
+    strips_run<KB, CPL><<<lane_blocks(a.N, CPL, WG), WG, 0, s>>>(a);
     return hipGetLastError();
 }
 
@@ -374,32 +311,22 @@ extern "C" int dspfx_strips_coeffs(const float *raw6, float *out5) {
 }
 
 extern "C" int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips **out) {
-    if (!desc || !out) {
-        g_err = "strips: null argument";
-        return DSPFX_ERR_INVALID;
-    }
-    *out = nullptr;
-    g_err.clear();
-    char buf[160];
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->max_frames == 0 || desc->max_frames > (1u << 20)) {
-        g_err = "strips: abi_version or max_frames";
-        return DSPFX_ERR_INVALID;
-    }
+    const int rc = create_checks(desc, out, g_err, [desc](std::string &err) -> int {
+        char buf[160];
+        if (desc->bands < 1 || desc->bands > DSPFX_STRIPS_MAX_BANDS) {
+            std::snprintf(buf, sizeof buf, "strips: %u bands, not 1 .. %d", desc->bands, DSPFX_STRIPS_MAX_BANDS);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        if (desc->link_flags & ~(DSPFX_LINK_INTERNAL | DSPFX_LINK_INPUT)) {
+            std::snprintf(buf, sizeof buf, "strips: unknown link flag in 0x%x (DSPFX_LINK_INTERNAL and DSPFX_LINK_INPUT are known)", desc->link_flags);
+            err = buf;
+            return DSPFX_ERR_INVALID;
+        }
+        return DSPFX_OK;
+    });
+    if (rc != DSPFX_OK) return rc;
     const uint32_t N = desc->n_channels;
-    int rc = check_shape("strips", N, desc->tile_channels, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (desc->bands < 1 || desc->bands > DSPFX_STRIPS_MAX_BANDS) {
-        std::snprintf(buf, sizeof buf, "strips: %u bands, not 1 .. %d", desc->bands, DSPFX_STRIPS_MAX_BANDS);
-        g_err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    if (desc->link_flags & ~(DSPFX_LINK_INTERNAL | DSPFX_LINK_INPUT)) {
-        std::snprintf(buf, sizeof buf, "strips: unknown link flag in 0x%x (DSPFX_LINK_INTERNAL and DSPFX_LINK_INPUT are known)", desc->link_flags);
-        g_err = buf;
-        return DSPFX_ERR_INVALID;
-    }
-    rc = open_device("strips", desc->device, &g_err);
-    if (rc != DSPFX_OK) return rc;
     dspfx_strips *p = new (std::nothrow) dspfx_strips;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -432,11 +359,7 @@ extern "C" int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips *
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_strips_destroy(dspfx_strips *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_strips_destroy(dspfx_strips *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_strips_set_gain(dspfx_strips *p, const float *host_levels, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
@@ -482,23 +405,15 @@ extern "C" int dspfx_strips_set_band(dspfx_strips *p, uint32_t band, const float
 }
 
 extern "C" int dspfx_strips_present(dspfx_strips *p, uint32_t *host_masks_out, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!host_masks_out) return p->fail(DSPFX_ERR_INVALID, "strips present: no array");
-    const int rc = check_range(p, "present", first_channel, count);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    std::memcpy(host_masks_out, p->hmask.data() + first_channel, count * sizeof(uint32_t));
-    return DSPFX_OK;
+    return read_table(p, "present", host_masks_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->hmask[c]; });
 }
 
 extern "C" int dspfx_strips_run(dspfx_strips *p, const float *in, float *out, uint32_t n_frames, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!in || !out || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "strips run: in, out or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
-    BANK_HIP_WHY(order(p, s), "stream order");
-    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "slider store");
+    const int rc = begin_run(p, in && out, n_frames, s, "strips run: in, out or n_frames", "slider store", apply_store);
+    if (rc != DSPFX_OK) return rc;
     StripArgs a;
     a.in = in;
     a.out = out;
@@ -511,9 +426,7 @@ extern "C" int dspfx_strips_run(dspfx_strips *p, const float *in, float *out, ui
     a.nf = n_frames;
     a.flags = p->desc.link_flags;
     a.div = p->div;
-    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
-    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
-    BANK_HIP_WHY(launch(p->KB, vec, a, s), "strips_run");
+    BANK_HIP_WHY(launch(p->KB, lane_plan(a.N, a.W, (uintptr_t)in | (uintptr_t)out, WG).vec, a, s), "strips_run");
     return DSPFX_OK;
 }
 

@@ -5,7 +5,7 @@
 // One run is two kernels behind the queued stores.
 //   pass A (talkers_run)   per channel, frames in order.  Time is a serial recurrence per channel, so a lane owns its channels
 //            for the whole block, as in strips_kernels.hip: four adjacent channels with one 16-byte load and one nontemporal
-//            16-byte store per frame when the layout allows it (bank_common's vec), one channel otherwise.  Frames are taken in
+//            16-byte store per frame when the layout allows it (lane_io.hip.h), one channel otherwise.  Frames are taken in
 //            chunks of F rows and the next chunk's loads are issued ahead of this one's arithmetic, so the chain env -> env does
 //            not wait for memory.  Per frame: the envelope as K_ENVELOPE computes it (chain_kernels.hip.h), the block's largest
 //            envelope into `level`, and -- the gated form -- the sample times gate + (target - gate) * r[f], r[f] = (f + 1) / nf.
@@ -34,8 +34,8 @@
 #include <vector>
 
 #include "../../include/dspfx.h"
-#include "bank_common.hip.h"
-#include "store_queue.hip.h"
+#include "channel_bank.hip.h"
+#include "lane_io.hip.h"
 
 namespace {
 
@@ -54,49 +54,6 @@ struct TalkArgs {
     const uint8_t *pin;          // [N]
     uint32_t N, W, nf;
 };
-
-// CPL adjacent values at p (aligned to CPL values) in one load / one store
-template <int CPL, typename T>
-__device__ __forceinline__ void loadv(const T *p, T (&o)[CPL]) {
-    typedef T vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        o[0] = *p;
-    } else {
-        const vec t = *(const vec *)p;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) o[j] = t[j];
-    }
-}
-
-template <int CPL, bool NT>
-__device__ __forceinline__ void storev(float *p, const float (&o)[CPL]) {
-    typedef float vec __attribute__((ext_vector_type(CPL)));
-    if constexpr (CPL == 1) {
-        if (NT) __builtin_nontemporal_store(o[0], p);
-        else *p = o[0];
-    } else {
-        vec t;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) t[j] = o[j];
-        if (NT) __builtin_nontemporal_store(t, (vec *)p);
-        else *(vec *)p = t;
-    }
-}
-
-// R rows from frame f0 of the lane's channels; `lane` is the lane's element of frame 0 (bank_common's lay(0, c, ..)), a frame
-// further is `rs` elements on in either layout, so no row pays lay()'s division.  The four-channel form is what load4 and
-// store4<true> of bank_common do with vec = 1, on that address (strips_kernels.hip's form)
-template <int CPL, int R>
-__device__ __forceinline__ void load_rows(const float *lane, size_t rs, uint32_t f0, float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) loadv<CPL>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
-
-template <int CPL, int R>
-__device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) storev<CPL, true>(lane + (size_t)(f0 + i) * rs, v[i]);
-}
 
 // the lane's state over a block
 template <int CPL>
@@ -343,11 +300,8 @@ uint32_t build_seating(RoomOf room_of, uint64_t N, uint32_t G, uint32_t *members
 
 }  // namespace
 
-struct dspfx_talkers : BankError {
-    dspfx_talkers_desc desc{};
-    std::mutex mu;                               // run / destroy
-    std::mutex smu;                              // one store at a time: it reads the host tables, then queues
-    Stores stores;                               // its qmu guards the host tables' writes and their readers
+struct dspfx_talkers : ChannelBank<dspfx_talkers_desc, StoreFields> {
+    static constexpr const char *name = "talkers";
     std::vector<uint32_t> room_of;               // [N], with every assign made so far
     std::vector<uint32_t> counts;                // [G]
     std::vector<float> hga, hgr;                 // [N]: the gains, with every store made so far (a NULL slider keeps them)
@@ -360,21 +314,13 @@ struct dspfx_talkers : BankError {
     int32_t *alist = nullptr;                    // [N]
     uint32_t *acount = nullptr;                  // [G]
     float floor = 0.0f;                          // as of the stores drained so far (mu)
-    hipEvent_t ev = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
 void release(dspfx_talkers *p) {
-    (void)hipSetDevice(p->desc.device);
-    for (void *d : {(void *)p->env, (void *)p->gate, (void *)p->target, (void *)p->level, (void *)p->ga, (void *)p->gr, (void *)p->tlev, (void *)p->pin,
-                    (void *)p->top, (void *)p->members, (void *)p->room_start, (void *)p->talkers, (void *)p->alist, (void *)p->acount})
-        if (d) (void)hipFree(d);
-    p->stores.free_all();
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
+    release_bank(p, {p->env, p->gate, p->target, p->level, p->ga, p->gr, p->tlev, p->pin, p->top, p->members, p->room_start, p->talkers, p->alist,
+                     p->acount});
 }
 
 // one store onto the stream
@@ -403,12 +349,6 @@ hipError_t apply_store(dspfx_talkers *p, const Store &st, hipStream_t s) {
         return hipGetLastError();
     }
     return hipSuccess;
-}
-
-int check_range(dspfx_talkers *p, const char *what, uint64_t first, uint64_t count, uint64_t N) {
-    std::string why;
-    const int rc = check_range("talkers", what, first, count, N, why);
-    return rc == DSPFX_OK ? rc : p->fail(rc, why.c_str());
 }
 
 }  // namespace
@@ -599,15 +539,11 @@ extern "C" int dspfx_talkers_create(const dspfx_talkers_desc *desc, dspfx_talker
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_talkers_destroy(dspfx_talkers *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    close_bank(p, release);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_talkers_destroy(dspfx_talkers *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_talkers_set_detector(dspfx_talkers *p, const float *host_attack, const float *host_release, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
-    const int rc = check_range(p, "set_detector", first_channel, count, p->desc.n_channels);
+    const int rc = check_range(p, "set_detector", first_channel, count);
     if (rc != DSPFX_OK) return rc;
     if (count == 0 || (!host_attack && !host_release)) return DSPFX_OK;
     Store st;
@@ -651,7 +587,7 @@ int store_bytes(dspfx_talkers *p, StoreKind kind, const char *call, const uint8_
 extern "C" int dspfx_talkers_set_pin(dspfx_talkers *p, const uint8_t *host_pins, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
     if (!host_pins) return p->fail(DSPFX_ERR_INVALID, "talkers set_pin: no array");
-    const int rc = check_range(p, "set_pin", first_channel, count, p->desc.n_channels);
+    const int rc = check_range(p, "set_pin", first_channel, count);
     if (rc != DSPFX_OK) return rc;
     for (uint64_t i = 0; i < count; ++i)
         if (host_pins[i] > DSPFX_TALKERS_SHUT) {
@@ -691,17 +627,7 @@ extern "C" int dspfx_talkers_set_floor(dspfx_talkers *p, float floor) {
 }
 
 extern "C" int dspfx_talkers_reset(dspfx_talkers *p, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    const int rc = check_range(p, "reset", first_channel, count, p->desc.n_channels);
-    if (rc != DSPFX_OK) return rc;
-    if (count == 0) return DSPFX_OK;
-    Store st;
-    st.kind = ST_RESET;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    p->stores.push(st);
-    return DSPFX_OK;
+    return store_plain(p, ST_RESET, "reset", first_channel, count);
 }
 
 extern "C" int dspfx_talkers_assign(dspfx_talkers *p, const uint32_t *host_room_ids, uint64_t first_channel, uint64_t count) {
@@ -709,7 +635,7 @@ extern "C" int dspfx_talkers_assign(dspfx_talkers *p, const uint32_t *host_room_
     if (!host_room_ids || count == 0) return p->fail(DSPFX_ERR_INVALID, "talkers assign: no ids");
     const uint64_t N = p->desc.n_channels;
     const uint32_t G = p->desc.n_groups;
-    int rc = check_range(p, "assign", first_channel, count, N);
+    int rc = check_range(p, "assign", first_channel, count);
     if (rc != DSPFX_OK) return rc;
     std::string why;
     if (check_ids("assign", host_room_ids, first_channel, count, G, why) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, why.c_str());
@@ -774,13 +700,7 @@ extern "C" int dspfx_talkers_audible_views(dspfx_talkers *p, const int32_t **lis
 }
 
 extern "C" int dspfx_talkers_room_of(dspfx_talkers *p, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count) {
-    if (!p) return DSPFX_ERR_INVALID;
-    if (!host_ids_out) return p->fail(DSPFX_ERR_INVALID, "talkers room_of: no array");
-    const int rc = check_range(p, "room_of", first_channel, count, p->desc.n_channels);
-    if (rc != DSPFX_OK) return rc;
-    std::lock_guard<std::mutex> lk(p->stores.qmu);
-    std::memcpy(host_ids_out, p->room_of.data() + first_channel, count * sizeof(uint32_t));
-    return DSPFX_OK;
+    return read_table(p, "room_of", host_ids_out, first_channel, count, [p](uint32_t *o, uint64_t i, uint64_t c) { o[i] = p->room_of[c]; });
 }
 
 extern "C" int dspfx_talkers_counts(dspfx_talkers *p, uint32_t *host_counts_out) {
@@ -804,11 +724,9 @@ extern "C" int dspfx_talkers_views(dspfx_talkers *p, const float **level_out, co
 extern "C" int dspfx_talkers_run(dspfx_talkers *p, const float *in, float *out, uint32_t n_frames, void *stream) {
     if (!p) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (!in || n_frames == 0 || n_frames > p->desc.max_frames) return p->fail(DSPFX_ERR_INVALID, "talkers run: in or n_frames");
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP_WHY(hipSetDevice(p->desc.device), "hipSetDevice");
-    BANK_HIP_WHY(order(p, s), "stream order");
-    BANK_HIP_WHY(p->stores.drain(s, [p](const Store &st, hipStream_t on) { return apply_store(p, st, on); }), "talkers store");
+    const int rc = begin_run(p, in != nullptr, n_frames, s, "talkers run: in or n_frames", "talkers store", apply_store);
+    if (rc != DSPFX_OK) return rc;
     TalkArgs a;
     a.in = in;
     a.out = out;
@@ -822,9 +740,7 @@ extern "C" int dspfx_talkers_run(dspfx_talkers *p, const float *in, float *out, 
     a.N = p->desc.n_channels;
     a.W = p->desc.tile_channels;
     a.nf = n_frames;
-    // every group of 4 channels from a multiple of 4 is contiguous, 16-byte aligned and inside N (the tile divides N)
-    const bool vec = (a.W ? a.W : a.N) % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
-    const uint32_t lanes = vec ? a.N / 4 : a.N, blocks = (lanes + WG - 1) / WG;
+    const auto [vec, lanes, blocks] = lane_plan(a.N, a.W, (uintptr_t)in | (uintptr_t)out, WG);
     const uint32_t G = p->desc.n_groups;
     if (p->alist && out) {                       // behind the stores and ahead of pass A, which overwrites gate
         talkers_audible<<<(G + WG / 64 - 1) / (WG / 64), WG, 0, s>>>(p->gate, p->target, p->members, p->room_start, p->alist, p->acount, G, a.N);
