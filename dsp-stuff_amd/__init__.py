@@ -61,6 +61,8 @@ TALKERS_MAX_ROOM, TALKERS_MAX_TOP = 1024, 8     # DSPFX_TALKERS_*: the most memb
 TALKERS_AUTO, TALKERS_OPEN, TALKERS_SHUT = 0, 1, 2      # DSPFX_TALKERS_*: Talkers.set_pin
 SHAPERS_NONE = 0xFFFFFFFF       # DSPFX_SHAPERS_NONE: ChannelShapers.kinds() without a node, .modes() without a Distort node
 GENS_NONE = 0xFFFFFFFF          # DSPFX_GENS_NONE: ChannelGenerators.modes() without a node
+BLENDS_NONE = 0xFFFFFFFF        # DSPFX_BLENDS_NONE: ChannelBlends.kinds() without a node
+BLENDS_NO_BUS = 0xFFFFFFFF      # DSPFX_BLENDS_NO_BUS: ChannelBlends.assign, the channel reads no bus (the same value as NO_ROOM)
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
 # every symbol include/dspfx.h declares
@@ -109,6 +111,9 @@ EXPORTS = [
     "dspfx_shapers_present", "dspfx_shapers_kinds", "dspfx_shapers_modes", "dspfx_shapers_sliders",
     "dspfx_gens_plan", "dspfx_gens_create", "dspfx_gens_destroy", "dspfx_gens_last_error", "dspfx_gens_run", "dspfx_gens_set",
     "dspfx_gens_drop", "dspfx_gens_reset", "dspfx_gens_present", "dspfx_gens_modes", "dspfx_gens_sliders", "dspfx_gens_clocks",
+    "dspfx_blends_plan", "dspfx_blends_create", "dspfx_blends_destroy", "dspfx_blends_last_error", "dspfx_blends_run",
+    "dspfx_blends_set_mix", "dspfx_blends_set_add", "dspfx_blends_set_send", "dspfx_blends_assign", "dspfx_blends_drop",
+    "dspfx_blends_kinds", "dspfx_blends_ratios", "dspfx_blends_sends", "dspfx_blends_bus_of",
 ]
 COMM_ID_BYTES = 128
 
@@ -205,6 +210,11 @@ class _ShapersDesc(C.Structure):
 class _GensDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32)]
+
+
+class _BlendsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("n_buses", C.c_uint32)]
 
 
 class _Ctl(C.Structure):
@@ -464,6 +474,21 @@ def lib():
         getattr(L, f"dspfx_gens_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_gens_sliders.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
     L.dspfx_gens_clocks.argtypes = [vp, C.POINTER(vp)]
+    L.dspfx_blends_plan.argtypes = [C.c_uint64, C.POINTER(C.c_uint64)]
+    L.dspfx_blends_create.argtypes = [C.POINTER(_BlendsDesc), C.POINTER(vp)]
+    L.dspfx_blends_destroy.argtypes = [vp]
+    L.dspfx_blends_last_error.restype = C.c_char_p
+    L.dspfx_blends_last_error.argtypes = [vp]
+    L.dspfx_blends_run.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_blends_set_mix.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_blends_set_add.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.dspfx_blends_set_send.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_blends_assign.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_blends_drop.argtypes = [vp, C.c_uint64, C.c_uint64]
+    for name in ("kinds", "bus_of"):
+        getattr(L, f"dspfx_blends_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_blends_ratios.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_blends_sends.argtypes = [vp, fp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2220,6 +2245,109 @@ class ChannelGenerators(_ChannelBank):
         """float32[channels] on the device: every channel's clock, the phase carried between blocks; +0.0 without a node (valid
         after a run, on its stream)."""
         return self._view(self._clock, (self.channels,))
+
+
+def blends_plan(channels: int) -> int:
+    """dspfx_blends_plan, a pure host function (no GPU): the device bytes of a ChannelBlends bank's tables, 13 per channel (ratio,
+    send level, bus id and a kind / presence byte)."""
+    L = lib()
+    n = C.c_uint64()
+    rc = L.dspfx_blends_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
+    _raise(L, "blends", rc)
+    return int(n.value)
+
+
+class ChannelBlends(_ChannelBank):
+    """Per-channel Add and Mix nodes (include/dspfx.h, dspfx_blends_*): channel c may carry an Add node or a Mix node with a ratio
+    of its own, a send (a Gain node on the node's second input) and a bus id, over device blocks in the layout of `tile_channels`
+    (as Engine's).  The second input of a run is an N-channel block `b`, or a [n_frames][buses] frame-major `bus` block that channel
+    c reads at bus_of[c] (+0.0 on NO_ROOM), or nothing (+0.0).  A fresh bank copies `a`.  A channel's sample is bit for bit what
+    Engine([Mix(ratio)], link_flags=0).process(a, side=b) -- or Engine([Add()]) -- writes for it.  group_size / group_start (as
+    MixGroups takes them) make one bus per group and assign every channel its group's.  Unlike the reference, the control block is
+    connected per call and is not latched into the slider.  Asynchronous on `stream`."""
+
+    _C = "blends"
+
+    def __init__(self, channels: int, buses: int = 0, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0,
+                 group_size=None, group_start=None):
+        self._fields(channels, tile_channels, max_frames, device)
+        table = None
+        if group_size is not None or group_start is not None:
+            table = _group_table(self.channels, group_start, group_size)
+            if buses not in (0, len(table) - 1):
+                raise ValueError(f"buses {buses} is not the {len(table) - 1} groups of the table")
+            buses = len(table) - 1
+        self.buses = int(buses)
+        d = _BlendsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF,
+                        self.buses & 0xFFFFFFFF)
+        self._create(d)
+        if table is not None:
+            self.assign(np.repeat(np.arange(self.buses, dtype=np.uint32), np.diff(table).astype(np.int64)))
+
+    def run(self, a, n_frames: Optional[int] = None, b=None, bus=None, ratio=None, out=None, stream: Optional[int] = None):
+        """One device block `a` -> `out`, a device block in the same layout (made when not given; out=a and out=b work in place).
+        `b`: a device block of a's shape, or `bus`: a device block [n_frames][buses]; with neither, the second input is +0.0.
+        `ratio`: a device block of a's shape on the Mix nodes' control port, mapped per sample from [-1, 1] onto 0 .. 1; the stored
+        ratios are not changed.  Both b and bus, or bus on a bank of buses=0, is refused."""
+        n_frames = self._frames(a, n_frames)
+        if out is None:
+            out = self._out(n_frames)
+        opt = [_ptr(t) if t is not None else None for t in (b, bus, ratio)]
+        self._chk(self.L.dspfx_blends_run(self.h, _ptr(a), *opt, _ptr(out), int(n_frames), _stream(stream)))
+        return out
+
+    def set_mix(self, ratio=None, first_channel: int = 0, count: Optional[int] = None):
+        """Give channels from first_channel a Mix node: `ratio` is an array (one value per channel) or a scalar for `count` channels
+        (default: all from first_channel).  None keeps the ratio of a channel that carries a Mix node and is 0.5 where it carries
+        none or an Add node.  Values are taken as given (no clamp).  A range past the channels refuses the whole store.  Any
+        thread; applies to the runs submitted after it."""
+        n = self._range(first_channel, count, (ratio,), "blends set_mix: the array names another number of channels")
+        keep, args = self._f32s((ratio,), n)
+        self._chk(self.L.dspfx_blends_set_mix(self.h, args[0], int(first_channel), n))
+
+    def set_add(self, first_channel: int = 0, count: Optional[int] = None):
+        """Give `count` channels from first_channel (default: all from it) an Add node; queued like every store."""
+        self._chk(self.L.dspfx_blends_set_add(self.h, int(first_channel), self._n(first_channel, count)))
+
+    def set_send(self, level, first_channel: int = 0, count: Optional[int] = None):
+        """Give channels from first_channel a send, a Gain node on the second input: `level` is an array or a scalar for `count`
+        channels.  level=None removes the send."""
+        n = self._range(first_channel, count, (level,), "blends set_send: the array names another number of channels")
+        keep, args = self._f32s((level,), n)
+        self._chk(self.L.dspfx_blends_set_send(self.h, args[0], int(first_channel), n))
+
+    def assign(self, ids, first_channel: int = 0):
+        """Channels [first_channel, first_channel + len(ids)) read the buses `ids` (an int for one channel, or any integer sequence,
+        numpy array or torch tensor; each in [0, buses) or NO_ROOM).  A bad id or a range past the channels stores nothing.  Any
+        thread, while runs are in flight: it holds for the runs submitted after it returns."""
+        v = _room_ids(ids)
+        self._chk(self.L.dspfx_blends_assign(self.h, v.ctypes.data_as(C.POINTER(C.c_uint32)), int(first_channel), len(v)))
+
+    def drop(self, first_channel: int = 0, count: Optional[int] = None):
+        """Remove the node and the send of `count` channels from first_channel (default: all from it): a copy of `a` again; the bus
+        id stays; queued like a store."""
+        self._chk(self.L.dspfx_blends_drop(self.h, int(first_channel), self._n(first_channel, count)))
+
+    def kinds(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: ADD, MIX or BLENDS_NONE, as every store made so far left it."""
+        return self._table("kinds", first_channel, count)
+
+    def ratios(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """float32[count]: the Mix node's ratio, 0 for every other channel."""
+        return self._table("ratios", first_channel, count, np.float32)
+
+    def sends(self, first_channel: int = 0, count: Optional[int] = None):
+        """(level float32[count], present uint32[count]): the send's level and whether the channel has one.  A presence array and
+        not a NaN: a level is taken as given, NaN included.  An absent send's level reads 0."""
+        n = self._n(first_channel, count)
+        level, present = np.zeros(max(n, 0), np.float32), np.zeros(max(n, 0), np.uint32)
+        self._chk(self.L.dspfx_blends_sends(self.h, level.ctypes.data_as(C.POINTER(C.c_float)), present.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            int(first_channel), n))
+        return level, present
+
+    def bus_of(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the bus of every channel (NO_ROOM: none) by every assign made so far."""
+        return self._table("bus_of", first_channel, count)
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

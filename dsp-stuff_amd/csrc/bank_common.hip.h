@@ -1,5 +1,5 @@
 // bank_common.hip.h -- what the banks share (pitch, resample, spectrum, convolve, mixgroups, mixmatrix and the per-channel banks
-// strips, delays, talkers, dynamics, shapers, gens _kernels.hip): the desc's layout, 4-channel loads and stores in it, the slot copy,
+// strips, delays, talkers, dynamics, shapers, gens, blends _kernels.hip): the desc's layout, 4-channel loads and stores in it, the slot copy,
 // and small host helpers -- all stateless -- and the scaffold of the banks that take live stores: the error holder, the shape /
 // range / table checks of their arguments, open_device, close_bank, release_bank and destroy_bank.  Host and device, hipcc only.
 // The FFT is in fft_core.hip.h, the staged stores in store_queue.hip.h, a lane's loads and stores of its own channels in

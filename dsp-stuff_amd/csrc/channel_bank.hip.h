@@ -1,4 +1,4 @@
-// channel_bank.hip.h -- the scaffold of the per-channel banks (strips, delays, talkers, dynamics, shapers, gens _kernels.hip): the
+// channel_bank.hip.h -- the scaffold of the per-channel banks (strips, delays, talkers, dynamics, shapers, gens, blends _kernels.hip): the
 // members they all have, and the host glue around BankError (bank_common.hip.h) and StoreQueue (store_queue.hip.h) that is the
 // same in each -- the range check, create's first lines, a run's first lines, a store without values, a host table read back.
 // A bank keeps what its stores mean (apply_store, its host tables, its validation), its kernels and its launch.  Host only.

@@ -260,6 +260,29 @@ pub struct dspfx_gens_desc {
 /// `dspfx_gens_modes`: the channel carries no node.
 pub const DSPFX_GENS_NONE: u32 = 0xFFFF_FFFF;
 
+/// Opaque channel-blend bank handle (`typedef struct dspfx_blends dspfx_blends`).
+#[repr(C)]
+pub struct dspfx_blends {
+    _private: [u8; 0],
+}
+
+/// The channel-blend bank's descriptor (`dspfx_blends_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_blends_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub n_buses: u32,
+}
+
+/// `dspfx_blends_assign`, `dspfx_blends_bus_of`: the channel reads no bus.
+pub const DSPFX_BLENDS_NO_BUS: u32 = 0xFFFF_FFFF;
+/// `dspfx_blends_kinds`: the channel carries no node.
+pub const DSPFX_BLENDS_NONE: u32 = 0xFFFF_FFFF;
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -619,6 +642,20 @@ extern "C" {
     pub fn dspfx_gens_modes(g: *mut dspfx_gens, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_gens_sliders(g: *mut dspfx_gens, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_gens_clocks(g: *mut dspfx_gens, clock_out: *mut *const f32) -> c_int;
+    pub fn dspfx_blends_plan(channels: u64, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_blends_create(desc: *const dspfx_blends_desc, out: *mut *mut dspfx_blends) -> c_int;
+    pub fn dspfx_blends_destroy(b: *mut dspfx_blends) -> c_int;
+    pub fn dspfx_blends_last_error(b: *const dspfx_blends) -> *const c_char;
+    pub fn dspfx_blends_run(b: *mut dspfx_blends, a: *const f32, side: *const f32, bus: *const f32, ratio: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_blends_set_mix(b: *mut dspfx_blends, host_ratio: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_set_add(b: *mut dspfx_blends, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_set_send(b: *mut dspfx_blends, host_level: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_assign(b: *mut dspfx_blends, host_ids: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_drop(b: *mut dspfx_blends, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_kinds(b: *mut dspfx_blends, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_ratios(b: *mut dspfx_blends, host_ratios_out: *mut f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_sends(b: *mut dspfx_blends, host_levels_out: *mut f32, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_blends_bus_of(b: *mut dspfx_blends, host_ids_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

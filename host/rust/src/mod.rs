@@ -12,4 +12,5 @@ pub mod talkers;
 pub mod channel_dynamics;
 pub mod channel_shapers;
 pub mod channel_generators;
+pub mod channel_blends;
 pub mod mix_matrix;

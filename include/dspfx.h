@@ -1582,6 +1582,99 @@ int dspfx_gens_sliders(dspfx_gens *g, float *host_sliders_out, uint64_t first_ch
  * a run, on its stream. */
 int dspfx_gens_clocks(dspfx_gens *g, const float **clock_out);
 
+/* ---- channel blends: a bank of per-channel Add and Mix nodes, and buses back into channels -----------------------------
+ * An engine runs an Add (nodes/add.rs) or a Mix node (nodes/mix.rs) with one ratio for all N channels and one N-channel side
+ * block.  This bank gives channel c ONE two-input node of its own -- none, Add, or Mix with its own ratio -- over N channels in the
+ * desc's layout (tile_channels as dspfx_engine_desc), and an optional Gain node (gain.rs) on the node's `b` input: the channel's
+ * SEND level, as the reference would wire b -> Gain -> Add.  Per-participant wet/dry after an echo, a shaper or the convolver; each
+ * room's reverberated bus added back into its members' returns; an announcement bus (n_buses = 1) into everybody's; a crossfade of
+ * a channel between two sources by a control block.
+ * PER CHANNEL.  A node (none / Add / Mix), the Mix node's ratio, the send (absent, or a level) and a bus id in [0, n_buses) or
+ * DSPFX_BLENDS_NO_BUS.  A fresh bank has no node, no send and DSPFX_BLENDS_NO_BUS everywhere: it copies a.  A new Mix node's ratio
+ * is dspfx_node_defaults' 0.5.  Values are taken as given, as dspfx_set_param takes them: no clamp, NaN, infinities and values
+ * outside the slider's range included.  The send EXISTS from the first dspfx_blends_set_send that names the channel until a
+ * set_send without levels or dspfx_blends_drop; a send on a channel without a node is kept and does nothing.
+ * ONE RUN: queued stores go onto the stream in the order they were made, then per channel c and frame f
+ *   - THE SECOND INPUT.  b, an N-channel block in the bank's layout: b[f][c].  Or bus, a [n_frames][n_buses] frame-major block (what
+ *     dspfx_mixgroups_run, dspfx_convolve_run and a frame-major engine of n_buses channels write): bus[f][bus_of[c]], +0.0 for a
+ *     channel on DSPFX_BLENDS_NO_BUS.  With neither, +0.0: an unconnected port (node.rs:288), as an engine's Add or Mix without a
+ *     side block.
+ *   - bb = the second input, times the send's level by one f32 multiplication where the channel has a send.
+ *   - Add: out = a + bb.  Mix: out = (bb * r) + (a * (1.0f - r)), in this order and never fused (mix.rs:45).  No node: a's very
+ *     bits, NaN payloads included.  Every weight is a multiplication, never an omission: Mix at r = 0 with b = inf gives NaN.
+ *     A channel's sample is bit for bit what an engine whose chain is that one node, with link_flags = 0, writes for it from the
+ *     same a and side block: the bank uses the engine's expressions.
+ *   - THE CONTROL PORT.  ratio is an optional device block in the bank's layout, the Mix node's `as_input` port
+ *     (dsp-stuff-derive/src/lib.rs:135-153): where given, a Mix channel's r for sample f is the block's value mapped from [-1, 1]
+ *     onto 0 .. 1, per sample.  Add channels and channels without a node do not read it.
+ *     KNOWN DIFFERENCE from the reference, as dspfx_gens_run's: the bank does NOT latch the block's first value into the slider.  A
+ *     later run without the block uses the stored ratio.
+ *   - No link hops: the bank is link_flags = 0.
+ * The kernel has the shape of the generator bank's: a lane owns four adjacent channels (one when the layout or the alignment forbids
+ * it), frames go in chunks with the next chunk's loads issued ahead of the arithmetic, stores are nontemporal.  The kinds run under
+ * per-channel selects.  A lane none of whose channels carries a node reads neither b, the bus nor the control block.  In bus mode every
+ * channel gathers its own bus[f][bus_of[c]] from the small bus block, which stays in L2.  A channel's output is the same bits in either layout, in place or not, on any stream, and whatever its
+ * neighbours carry.  No atomics, no LDS.
+ * Memory: 13 bytes per channel of tables on the device (ratio, send level, bus id and a kind / presence byte;
+ * dspfx_blends_plan), 13 on the host. */
+/* dspfx_blends_assign, dspfx_blends_bus_of: the channel reads no bus */
+#define DSPFX_BLENDS_NO_BUS 0xFFFFFFFFu
+/* dspfx_blends_kinds: the channel carries no node */
+#define DSPFX_BLENDS_NONE 0xFFFFFFFFu
+typedef struct dspfx_blends dspfx_blends;
+typedef struct dspfx_blends_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t n_buses;         /* G: the channels of a run's bus block; 0: the bank takes none */
+} dspfx_blends_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, 13 * channels.  channels of 0 or above
+ * 2^32 - 256: DSPFX_ERR_INVALID, the reason in dspfx_blends_last_error(NULL). */
+int dspfx_blends_plan(uint64_t channels, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0) is DSPFX_ERR_INVALID with the reason in dspfx_blends_last_error of a NULL bank (kept per thread); all of that is
+ * checked before any device work. */
+int dspfx_blends_create(const dspfx_blends_desc *desc, dspfx_blends **out);
+int dspfx_blends_destroy(dspfx_blends *b);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_blends_last_error(const dspfx_blends *b);
+/* a, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  side: a block of the same shape, or
+ * NULL; bus: a device block [n_frames][n_buses], or NULL; ratio: a block of a's shape, or NULL (see ONE RUN).  Both side and bus,
+ * bus on a bank of n_buses = 0, or n_frames of 0 or above max_frames: DSPFX_ERR_INVALID and the reason, before any device work and
+ * with the queued stores still queued.  out == a and out == side work in place (a thread rewrites the elements it read); any other
+ * overlap is the caller's error.  Asynchronous on `stream`; a run on another stream than the one before first waits (on the device)
+ * for that one (the rules of dspfx_strips_run).  Queued stores go onto the stream ahead of the kernel, in the order they were
+ * made. */
+int dspfx_blends_run(dspfx_blends *b, const float *a, const float *side, const float *bus, const float *ratio, float *out, uint32_t n_frames,
+                     void *stream);
+/* Gives channels [first_channel, first_channel + count) a Mix node, from a host array of `count` ratios.  NULL: the ratio is kept
+ * where the channel carries a Mix node, and is the default 0.5 where it carries none or an Add node.  The send and the bus id
+ * stay.  The contract of dspfx_gens_set: callable from any thread while runs are in flight, never waits for the device or for a
+ * run; the values are staged in page-locked memory and queued, each store is whole, and a run submitted after the call returns sees
+ * it, the runs submitted before it do not.  A range past the channels refuses the WHOLE store: DSPFX_ERR_INVALID, the reason in
+ * dspfx_blends_last_error, nothing stored.  The same holds for every store below. */
+int dspfx_blends_set_mix(dspfx_blends *b, const float *host_ratio, uint64_t first_channel, uint64_t count);
+/* ... an Add node.  The send and the bus id stay. */
+int dspfx_blends_set_add(dspfx_blends *b, uint64_t first_channel, uint64_t count);
+/* Gives the channels a send, a Gain node on the node's second input, from a host array of `count` levels; NULL removes it. */
+int dspfx_blends_set_send(dspfx_blends *b, const float *host_level, uint64_t first_channel, uint64_t count);
+/* Stores the bus ids of the channels from a host array of `count` ids, each below n_buses or DSPFX_BLENDS_NO_BUS; any other id
+ * refuses the whole store. */
+int dspfx_blends_assign(dspfx_blends *b, const uint32_t *host_ids, uint64_t first_channel, uint64_t count);
+/* Removes the node and the send of the channels: a copy of a again, and a later set_mix starts from the default.  The bus id
+ * stays.  Queued like a store. */
+int dspfx_blends_drop(dspfx_blends *b, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: kinds DSPFX_ADD, DSPFX_MIX or
+ * DSPFX_BLENDS_NONE; ratios the Mix node's, 0 for every other channel; sends the level and, in a presence array of its own, 1 / 0
+ * (a level may be any value, NaN included, so no value can stand for "absent"; the level of an absent send reads 0); bus_of the id
+ * or DSPFX_BLENDS_NO_BUS. */
+int dspfx_blends_kinds(dspfx_blends *b, uint32_t *host_kinds_out, uint64_t first_channel, uint64_t count);
+int dspfx_blends_ratios(dspfx_blends *b, float *host_ratios_out, uint64_t first_channel, uint64_t count);
+int dspfx_blends_sends(dspfx_blends *b, float *host_levels_out, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_blends_bus_of(dspfx_blends *b, uint32_t *host_ids_out, uint64_t first_channel, uint64_t count);
+
 /* ---- mix matrix: each listener's own mix of their room ---------------------------------------------------------------
  * dspfx_mixgroups_returns gives every listener of a room the same mix of the others, with one fader per SOURCE.  In the
  * reference every participant has an Output node of their own and wires it to whichever of the others they like through Gain

@@ -917,6 +917,79 @@ inline std::uint64_t gens_plan(std::uint64_t channels) {
     return bytes;
 }
 
+// Per-channel Add and Mix nodes (include/dspfx.h, dspfx_blends_*): channel c may carry an Add node or a Mix node with a ratio of its
+// own, a send (a Gain node on the node's second input) and a bus id, over device blocks in the layout of tile_channels; its sample
+// is bit for bit what an engine whose chain is that one node writes for it from the same inputs.  The second input of a run is an
+// N-channel block, a [n_frames][buses] frame-major bus block read through the bus ids (+0.0 on DSPFX_BLENDS_NO_BUS), or nothing
+// (+0.0).  A fresh bank copies a.  Unlike the reference, the control block is connected per run and is not latched into the slider.
+class ChannelBlends {
+  public:
+    ChannelBlends(std::uint32_t channels, std::uint32_t buses = 0, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE,
+                  int device = 0) {
+        const dspfx_blends_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, buses};
+        const int rc = dspfx_blends_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_blends_last_error(nullptr) ? dspfx_blends_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelBlends() { dspfx_blends_destroy(p_); }
+    ChannelBlends(const ChannelBlends &) = delete;
+    ChannelBlends &operator=(const ChannelBlends &) = delete;
+    // the device block a -> out (may be a or side); side (a block of a's shape) or bus ([n_frames][buses]) is the second input, both
+    // nullptr: +0.0, both given: refused; ratio: the control block of the Mix nodes' ratio or nullptr; asynchronous on `stream`
+    void run(const float *a, float *out, std::uint32_t n_frames, const float *side = nullptr, const float *bus = nullptr, const float *ratio = nullptr,
+             void *stream = nullptr) {
+        chk(dspfx_blends_run(p_, a, side, bus, ratio, out, n_frames, stream));
+    }
+    // a Mix node for each of channels [first_channel, first_channel + count) from a host array of ratios (nullptr: kept on a Mix
+    // node, else 0.5).  Any thread; never waits
+    void set_mix(const float *host_ratio, std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_blends_set_mix(p_, host_ratio, first_channel, count)); }
+    // ... an Add node
+    void set_add(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_blends_set_add(p_, first_channel, count)); }
+    // a send, the Gain node on the second input, from a host array of levels; nullptr removes it
+    void set_send(const float *host_level, std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_blends_set_send(p_, host_level, first_channel, count)); }
+    // the bus ids, each below buses or DSPFX_BLENDS_NO_BUS; a bad id refuses the whole store
+    void assign(const std::uint32_t *host_ids, std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_blends_assign(p_, host_ids, first_channel, count)); }
+    // the node and the send removed: a copy again; the bus id stays; queued like a store
+    void drop(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_blends_drop(p_, first_channel, count)); }
+    // the host tables, as all stores so far left them: DSPFX_ADD, DSPFX_MIX or DSPFX_BLENDS_NONE; the Mix ratio (0 elsewhere); the
+    // send's level and, in `present`, 1 / 0; the bus id or DSPFX_BLENDS_NO_BUS
+    std::vector<std::uint32_t> kinds(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_blends_kinds(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<float> ratios(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<float> m(count);
+        chk(dspfx_blends_ratios(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<float> sends(std::uint64_t first_channel, std::uint64_t count, std::vector<std::uint32_t> &present) {
+        std::vector<float> m(count);
+        present.assign(count, 0);
+        chk(dspfx_blends_sends(p_, m.data(), present.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> bus_of(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_blends_bus_of(p_, m.data(), first_channel, count));
+        return m;
+    }
+    dspfx_blends *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_blends_last_error(p_) ? dspfx_blends_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_blends *p_ = nullptr;
+};
+
+// The device bytes of a ChannelBlends bank's tables (dspfx_blends_plan: a pure host function, no GPU).
+inline std::uint64_t blends_plan(std::uint64_t channels) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_blends_plan(channels, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_blends_last_error(nullptr));
+    return bytes;
+}
+
 // Each listener's own mix of their room (include/dspfx.h, dspfx_mixmatrix_*): room r of n_r contiguous channels owns an n_r x n_r
 // matrix M[l][s] (listener, source), out[f][c0 + l] = (sum_s M[l][s] x[f][c0 + s]) / link_divisor(wired entries of row l).  Rooms as
 // MixGroups takes them, 1 .. DSPFX_MIXMATRIX_MAX_ROOM members each; a fresh bank holds mix-minus, which is MixGroups::returns without
