@@ -62,6 +62,7 @@ TALKERS_AUTO, TALKERS_OPEN, TALKERS_SHUT = 0, 1, 2      # DSPFX_TALKERS_*: Talke
 SHAPERS_NONE = 0xFFFFFFFF       # DSPFX_SHAPERS_NONE: ChannelShapers.kinds() without a node, .modes() without a Distort node
 GENS_NONE = 0xFFFFFFFF          # DSPFX_GENS_NONE: ChannelGenerators.modes() without a node
 BLENDS_NONE = 0xFFFFFFFF        # DSPFX_BLENDS_NONE: ChannelBlends.kinds() without a node
+FILTERS_NONE = 0xFFFFFFFF       # DSPFX_FILTERS_NONE: ChannelFilters.kinds() of an empty slot; reset(stage=None), every stage
 BLENDS_NO_BUS = 0xFFFFFFFF      # DSPFX_BLENDS_NO_BUS: ChannelBlends.assign, the channel reads no bus (the same value as NO_ROOM)
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
@@ -114,6 +115,9 @@ EXPORTS = [
     "dspfx_blends_plan", "dspfx_blends_create", "dspfx_blends_destroy", "dspfx_blends_last_error", "dspfx_blends_run",
     "dspfx_blends_set_mix", "dspfx_blends_set_add", "dspfx_blends_set_send", "dspfx_blends_assign", "dspfx_blends_drop",
     "dspfx_blends_kinds", "dspfx_blends_ratios", "dspfx_blends_sends", "dspfx_blends_bus_of",
+    "dspfx_filters_plan", "dspfx_filters_create", "dspfx_filters_destroy", "dspfx_filters_last_error", "dspfx_filters_run",
+    "dspfx_filters_set_low_pass", "dspfx_filters_set_high_pass", "dspfx_filters_set_envelope", "dspfx_filters_drop",
+    "dspfx_filters_reset", "dspfx_filters_present", "dspfx_filters_kinds", "dspfx_filters_sliders", "dspfx_filters_state",
 ]
 COMM_ID_BYTES = 128
 
@@ -215,6 +219,11 @@ class _GensDesc(C.Structure):
 class _BlendsDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("n_buses", C.c_uint32)]
+
+
+class _FiltersDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("stages", C.c_uint32)]
 
 
 class _Ctl(C.Structure):
@@ -489,6 +498,21 @@ def lib():
         getattr(L, f"dspfx_blends_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_blends_ratios.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
     L.dspfx_blends_sends.argtypes = [vp, fp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_filters_plan.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.dspfx_filters_create.argtypes = [C.POINTER(_FiltersDesc), C.POINTER(vp)]
+    L.dspfx_filters_destroy.argtypes = [vp]
+    L.dspfx_filters_last_error.restype = C.c_char_p
+    L.dspfx_filters_last_error.argtypes = [vp]
+    L.dspfx_filters_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    for name in ("set_low_pass", "set_high_pass"):
+        getattr(L, f"dspfx_filters_{name}").argtypes = [vp, C.c_uint32, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_filters_set_envelope.argtypes = [vp, C.c_uint32, fp, fp, C.c_uint64, C.c_uint64]
+    for name in ("drop", "reset"):
+        getattr(L, f"dspfx_filters_{name}").argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64]
+    L.dspfx_filters_present.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_filters_kinds.argtypes = [vp, C.c_uint32, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_filters_sliders.argtypes = [vp, C.c_uint32, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_filters_state.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2348,6 +2372,101 @@ class ChannelBlends(_ChannelBank):
     def bus_of(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: the bus of every channel (NO_ROOM: none) by every assign made so far."""
         return self._table("bus_of", first_channel, count)
+
+
+def filters_plan(channels: int, stages: int = 1) -> int:
+    """dspfx_filters_plan, a pure host function (no GPU): the device bytes of a ChannelFilters bank's tables, 13 per channel and
+    stage (two sliders, the state, the kind byte)."""
+    L = lib()
+    n = C.c_uint64()
+    rc = L.dspfx_filters_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, int(stages) & 0xFFFFFFFF, C.byref(n))
+    _raise(L, "filters", rc)
+    return int(n.value)
+
+
+class ChannelFilters(_ChannelBank):
+    """Per-channel one-pole filters and envelope followers (include/dspfx.h, dspfx_filters_*): channel c owns `stages` slots
+    (1 .. 4), run in slot order, each empty or a LowPass, a HighPass or an Envelope node (whose output is the envelope) with its own
+    sliders, over a device block in the layout of `tile_channels` (as Engine's).  An empty slot copies; a fresh bank copies its
+    input.  A channel's output is bit for bit what Engine([its present nodes in slot order], link_flags=0) writes for it, however
+    the frames are cut into runs.  A slot's node is new (state +0.0; ratio 0.5, attack 0, release 0 for what the call leaves None)
+    from the first `set_*` that names it and after a `set_*` of another kind; a `set_*` of the kind it carries keeps what the call
+    leaves None and keeps the state.  Asynchronous on `stream`."""
+
+    _C = "filters"
+
+    def __init__(self, channels: int, stages: int = 1, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
+        self._fields(channels, tile_channels, max_frames, device)
+        self.stages = int(stages)
+        d = _FiltersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF,
+                         self.stages & 0xFFFFFFFF)
+        self._create(d)
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every channel's slots -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        n_frames = self._frames(block, n_frames)
+        if out is None:
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_filters_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
+        return out
+
+    def _store(self, call, stage, values, first_channel, count):
+        n = self._range(first_channel, count, values, f"filters {call}: the arrays name different numbers of channels")
+        keep, args = self._f32s(values, n)
+        self._chk(getattr(self.L, f"dspfx_filters_{call}")(self.h, int(stage) & 0xFFFFFFFF, *args, int(first_channel), n))
+
+    def set_low_pass(self, stage: int, ratio=None, first_channel: int = 0, count: Optional[int] = None):
+        """Give slot `stage` of channels from first_channel a LowPass node: `ratio` is an array (one value per channel) or a scalar
+        for `count` channels (default: all from first_channel).  None keeps a LowPass slot's ratio and is the default 0.5 where
+        the slot carries another node or none.  Values are taken as given (no clamp).  A stage that is not one of the bank's or a
+        range past the channels refuses the whole store.  Any thread; applies to the runs submitted after it."""
+        self._store("set_low_pass", stage, (ratio,), first_channel, count)
+
+    def set_high_pass(self, stage: int, ratio=None, first_channel: int = 0, count: Optional[int] = None):
+        """... a HighPass node.  Rules as set_low_pass."""
+        self._store("set_high_pass", stage, (ratio,), first_channel, count)
+
+    def set_envelope(self, stage: int, attack=None, release=None, first_channel: int = 0, count: Optional[int] = None):
+        """... an Envelope node (attack and release in frames; the defaults are 0).  Rules as set_low_pass."""
+        self._store("set_envelope", stage, (attack, release), first_channel, count)
+
+    def drop(self, stage: int, first_channel: int = 0, count: Optional[int] = None):
+        """Empty slot `stage` of `count` channels from first_channel (default: all from it) and zero its state: that stage copies
+        again; queued like a store."""
+        self._chk(self.L.dspfx_filters_drop(self.h, int(stage) & 0xFFFFFFFF, int(first_channel), self._n(first_channel, count)))
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None, stage: Optional[int] = None):
+        """The state of slot `stage` (None: of every slot) back to +0.0 on `count` channels from first_channel (default: all from
+        it); the nodes and the sliders stay; queued like a store.  The way out for a slot whose state became NaN."""
+        s = FILTERS_NONE if stage is None else int(stage) & 0xFFFFFFFF
+        self._chk(self.L.dspfx_filters_reset(self.h, s, int(first_channel), self._n(first_channel, count)))
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where a slot of the channel carries a node, as every store made so far left it."""
+        return self._table("present", first_channel, count)
+
+    def _stage_table(self, name, stage, first_channel, count, dtype, per):
+        n = self._n(first_channel, count)
+        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
+        ct = C.c_float if dtype == np.float32 else C.c_uint32
+        self._chk(getattr(self.L, f"dspfx_filters_{name}")(self.h, int(stage) & 0xFFFFFFFF, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
+        return v
+
+    def kinds(self, stage: int, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: slot `stage` is LOW_PASS, HIGH_PASS, ENVELOPE, or FILTERS_NONE when empty."""
+        return self._stage_table("kinds", stage, first_channel, count, np.uint32, 1)
+
+    def sliders(self, stage: int, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """float32[count, 2]: slot `stage`'s sliders as they were given: ratio, 0 | attack, release (frames); 0, 0 when empty."""
+        return self._stage_table("sliders", stage, first_channel, count, np.float32, 2)
+
+    def state(self, stage: int):
+        """float32[channels] on the device: slot `stage`'s z or envelope after the last run, +0.0 when empty (valid after a run, on
+        its stream)."""
+        p = C.c_void_p()
+        self._chk(self.L.dspfx_filters_state(self.h, int(stage) & 0xFFFFFFFF, C.byref(p)))
+        return self._view(p.value, (self.channels,))
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

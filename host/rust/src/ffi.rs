@@ -283,6 +283,27 @@ pub const DSPFX_BLENDS_NO_BUS: u32 = 0xFFFF_FFFF;
 /// `dspfx_blends_kinds`: the channel carries no node.
 pub const DSPFX_BLENDS_NONE: u32 = 0xFFFF_FFFF;
 
+/// Opaque channel-filter bank handle (`typedef struct dspfx_filters dspfx_filters`).
+#[repr(C)]
+pub struct dspfx_filters {
+    _private: [u8; 0],
+}
+
+/// The channel-filter bank's descriptor (`dspfx_filters_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_filters_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub stages: u32,
+}
+
+/// `dspfx_filters_kinds`: the slot is empty; `dspfx_filters_reset`: every stage.
+pub const DSPFX_FILTERS_NONE: u32 = 0xFFFF_FFFF;
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -656,6 +677,20 @@ extern "C" {
     pub fn dspfx_blends_ratios(b: *mut dspfx_blends, host_ratios_out: *mut f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_blends_sends(b: *mut dspfx_blends, host_levels_out: *mut f32, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_blends_bus_of(b: *mut dspfx_blends, host_ids_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_plan(channels: u64, stages: u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_filters_create(desc: *const dspfx_filters_desc, out: *mut *mut dspfx_filters) -> c_int;
+    pub fn dspfx_filters_destroy(f: *mut dspfx_filters) -> c_int;
+    pub fn dspfx_filters_last_error(f: *const dspfx_filters) -> *const c_char;
+    pub fn dspfx_filters_run(f: *mut dspfx_filters, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_filters_set_low_pass(f: *mut dspfx_filters, stage: u32, host_ratio: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_set_high_pass(f: *mut dspfx_filters, stage: u32, host_ratio: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_set_envelope(f: *mut dspfx_filters, stage: u32, host_attack: *const f32, host_release: *const f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_drop(f: *mut dspfx_filters, stage: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_reset(f: *mut dspfx_filters, stage: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_present(f: *mut dspfx_filters, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_kinds(f: *mut dspfx_filters, stage: u32, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_sliders(f: *mut dspfx_filters, stage: u32, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_filters_state(f: *mut dspfx_filters, stage: u32, state_out: *mut *const f32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

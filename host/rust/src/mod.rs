@@ -13,4 +13,5 @@ pub mod channel_dynamics;
 pub mod channel_shapers;
 pub mod channel_generators;
 pub mod channel_blends;
+pub mod channel_filters;
 pub mod mix_matrix;

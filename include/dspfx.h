@@ -1492,6 +1492,97 @@ int dspfx_shapers_kinds(dspfx_shapers *s, uint32_t *host_kinds_out, uint64_t fir
 int dspfx_shapers_modes(dspfx_shapers *s, uint32_t *host_modes_out, uint64_t first_channel, uint64_t count);
 int dspfx_shapers_sliders(dspfx_shapers *s, float *host_sliders_out, uint64_t first_channel, uint64_t count);
 
+/* ---- channel filters: a bank of per-channel LowPass, HighPass and Envelope -------------------------------------------
+ * The three chain nodes that carry exactly one float of state, per channel: LowPass (nodes/low_pass.rs:36-39), HighPass
+ * (nodes/high_pass.rs:36-39) and Envelope (nodes/envelope.rs:34-52) as a node whose OUTPUT is the envelope -- the dynamics and
+ * talker banks keep theirs as a hidden detector.  A rumble and a hiss filter of each participant's own (HighPass then LowPass),
+ * a de-zipper on a per-channel control block ahead of an engine's control port, an envelope follower per channel with a smoothing
+ * LowPass behind it in the same launch.  Over N channels in the desc's layout (tile_channels as dspfx_engine_desc).
+ * PER CHANNEL.  `stages` SLOTS (1 .. 4), run in slot order 0 .. stages - 1.  A slot is empty, LowPass, HighPass or Envelope, with
+ * one float of state (z, or the envelope; starts +0.0) and its sliders: ratio r | attack and release in frames, converted on the
+ * host by dspfx_envelope_gain into ga and gr (as dspfx_talkers_set_detector and dspfx_dynamics_set do).  Values are taken as given,
+ * as dspfx_set_param takes them: no clamp, NaN, infinities and values outside the slider's range included.  A fresh bank has
+ * every slot of every channel empty: run copies in to out bit for bit and leaves every table at rest.
+ * STORES.  A slot's node is NEW from the first dspfx_filters_set_* that names it, and after a set_* of another kind than it
+ * carries: state +0.0, and the reference's defaults for the sliders the call leaves out (ratio 0.5, attack 0, release 0).  A set_*
+ * of the kind the slot already carries keeps the sliders left out AND THE STATE: none of the three nodes has an
+ * after_settings_change (low_pass.rs, high_pass.rs, envelope.rs; only reverb.rs:19 and biquad.rs:15 do), which is also what
+ * dspfx_set_param does for them.  Whether a store meets the same kind is decided when the store is made, from the host tables,
+ * whatever is in flight.  dspfx_filters_drop empties a slot and zeroes its state; dspfx_filters_reset zeroes state and keeps nodes
+ * and sliders.  A stage >= stages or a range past the channels refuses the WHOLE store: DSPFX_ERR_INVALID, the reason in
+ * dspfx_filters_last_error, nothing stored.
+ * ONE RUN: queued stores go onto the stream in the order they were made, then per channel, frames in order, slots in order,
+ * nothing contracted, every operation one IEEE f32 round-to-nearest:
+ *       LowPass    y = x * (1 - r) + r * z;   z = y                        (chain_kernels.hip.h K_LOW_PASS)
+ *       HighPass   z = x * (1 - r) + r * z;   y = x - z                    (K_HIGH_PASS)
+ *       Envelope   d = x < 0 ? -x : x;   g = z < d ? ga : gr;   z = d + (z + (-d)) * g;   y = z       (K_ENVELOPE)
+ *       empty      y = x: the sample's own bits, not a multiplication by one
+ * So out[f][c] is bit for bit what an engine whose chain is the channel's present nodes in slot order, with link_flags = 0,
+ * writes for the channel, in either layout, in place or not, on any stream, whatever its neighbours carry and however the frames
+ * are cut into runs (the recurrences carry no block structure); the state tables equal the engine's exported node state.
+ * The kernel has the shape of the dynamics bank's: a lane owns four adjacent channels (one when the layout or the alignment
+ * forbids it), frames go in chunks with the next chunk's loads issued ahead of the arithmetic, stores are nontemporal; `stages`
+ * is a template parameter and every slot lives in registers.  The kinds differ per lane: a wave ballots once per run, stage and
+ * kind, and takes per chunk and stage one wave-uniform branch: the body of the one kind its lanes carry, or, where they carry
+ * several, one body that computes the one-pole and the envelope for every value and selects by the channel's kind.
+ * A wave none of whose lanes carries a node in a stage does no arithmetic for that stage.  No atomics, no LDS.
+ * Not here: link hops, control-port modulation of the sliders (none of the three is a control input in the reference) and graph
+ * wiring, which stay with the engine.
+ * Memory: 13 bytes per channel and stage of tables on the device (two sliders, the state and a kind byte; dspfx_filters_plan),
+ * 9 on the host. */
+/* dspfx_filters_kinds: the slot is empty; dspfx_filters_reset: every stage */
+#define DSPFX_FILTERS_NONE 0xFFFFFFFFu
+typedef struct dspfx_filters dspfx_filters;
+typedef struct dspfx_filters_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t stages;          /* slots per channel, 1 .. 4 */
+} dspfx_filters_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, 13 * stages * channels.  channels of 0
+ * or above 2^32 - 256, stages outside 1 .. 4: DSPFX_ERR_INVALID, the reason in dspfx_filters_last_error(NULL). */
+int dspfx_filters_plan(uint64_t channels, uint32_t stages, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0, stages outside 1 .. 4) is DSPFX_ERR_INVALID with the reason in dspfx_filters_last_error of a NULL bank (kept
+ * per thread); all of that is checked before any device work. */
+int dspfx_filters_create(const dspfx_filters_desc *desc, dspfx_filters **out);
+int dspfx_filters_destroy(dspfx_filters *f);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_filters_last_error(const dspfx_filters *f);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out == in works in place (a
+ * thread rewrites the elements it read); any other overlap is the caller's error.  Asynchronous on `stream`; a run on another
+ * stream than the one before first waits (on the device) for that one, since the state is the bank's (the rules of
+ * dspfx_strips_run).  Queued stores go onto the stream ahead of the kernel, in the order they were made. */
+int dspfx_filters_run(dspfx_filters *f, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Gives slot `stage` of channels [first_channel, first_channel + count) a LowPass node, from a host array of `count` ratios.
+ * NULL: kept where the slot carries a LowPass node, the default 0.5 where it carries another node or none.  The contract of
+ * dspfx_dynamics_set: callable from any thread while runs are in flight, never waits for the device or for a run; the values are
+ * staged in page-locked memory and queued, each store is whole, and a run submitted after the call returns sees it, the runs
+ * submitted before it do not. */
+int dspfx_filters_set_low_pass(dspfx_filters *f, uint32_t stage, const float *host_ratio, uint64_t first_channel, uint64_t count);
+/* ... a HighPass node.  Rules as dspfx_filters_set_low_pass (a LowPass slot that becomes HighPass is a new node). */
+int dspfx_filters_set_high_pass(dspfx_filters *f, uint32_t stage, const float *host_ratio, uint64_t first_channel, uint64_t count);
+/* ... an Envelope node: attack and release in frames (each may be NULL; the defaults are 0).  Rules as dspfx_filters_set_low_pass. */
+int dspfx_filters_set_envelope(dspfx_filters *f, uint32_t stage, const float *host_attack, const float *host_release, uint64_t first_channel,
+                               uint64_t count);
+/* Empties slot `stage` of channels [first_channel, first_channel + count) and zeroes its state: that stage copies again, and a
+ * later store starts from the defaults.  Queued like a store. */
+int dspfx_filters_drop(dspfx_filters *f, uint32_t stage, uint64_t first_channel, uint64_t count);
+/* The state of slot `stage` (DSPFX_FILTERS_NONE: of every slot) back to +0.0 on the range; the nodes and the sliders stay.
+ * Queued like a store.  Also the way out for a slot whose state became NaN. */
+int dspfx_filters_reset(dspfx_filters *f, uint32_t stage, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: present 1 / 0 (a slot of
+ * the channel carries a node); kinds of slot `stage` DSPFX_LOW_PASS, DSPFX_HIGH_PASS, DSPFX_ENVELOPE or DSPFX_FILTERS_NONE; sliders
+ * of slot `stage` [count][2] as they were given: ratio, 0 | attack, release (frames); 0, 0 for an empty slot. */
+int dspfx_filters_present(dspfx_filters *f, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_filters_kinds(dspfx_filters *f, uint32_t stage, uint32_t *host_kinds_out, uint64_t first_channel, uint64_t count);
+int dspfx_filters_sliders(dspfx_filters *f, uint32_t stage, float *host_sliders_out, uint64_t first_channel, uint64_t count);
+/* The device pointer of slot `stage`'s state[N]: z of a one-pole, the envelope of an Envelope, +0.0 of an empty slot.  The pointer
+ * never changes; what it holds is valid after a run, on its stream. */
+int dspfx_filters_state(dspfx_filters *f, uint32_t stage, const float **state_out);
+
 /* ---- channel generators: a bank of per-channel Signal Generators -------------------------------------------------------
  * An engine runs one Signal Generator (nodes/signal_gen.rs) with one amplitude, frequency and mode for all N channels.  This bank
  * gives channel c ONE generator of its own, with its own sliders, mode and clock, over N channels in the desc's layout

@@ -846,6 +846,82 @@ inline std::uint64_t shapers_plan(std::uint64_t channels) {
     return bytes;
 }
 
+// Per-channel one-pole filters and envelope followers (include/dspfx.h, dspfx_filters_*): channel c owns `stages` slots (1 .. 4),
+// run in slot order, each empty or a LowPass, a HighPass or an Envelope node (whose output is the envelope) with its own sliders,
+// over a device block in the layout of tile_channels; its output is bit for bit what an engine whose chain is its present nodes in
+// slot order writes for it, however the frames are cut into runs.  A slot's node is new (state +0.0; ratio 0.5, attack 0, release 0
+// for a slider passed as nullptr) from the first set_*() that names it and after a set_*() of another kind; a set_*() of the kind
+// it carries keeps the sliders passed as nullptr and keeps the state.  A fresh bank copies its input.
+class ChannelFilters {
+  public:
+    ChannelFilters(std::uint32_t channels, std::uint32_t stages = 1, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE,
+                   int device = 0) {
+        const dspfx_filters_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, stages};
+        const int rc = dspfx_filters_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_filters_last_error(nullptr) ? dspfx_filters_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelFilters() { dspfx_filters_destroy(p_); }
+    ChannelFilters(const ChannelFilters &) = delete;
+    ChannelFilters &operator=(const ChannelFilters &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_filters_run(p_, in, out, n_frames, stream)); }
+    // a node in slot `stage` of channels [first_channel, first_channel + count) from host arrays; a stage that is not one of the
+    // bank's refuses the whole store.  Any thread; never waits
+    void set_low_pass(std::uint32_t stage, const float *host_ratio, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_filters_set_low_pass(p_, stage, host_ratio, first_channel, count));
+    }
+    void set_high_pass(std::uint32_t stage, const float *host_ratio, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_filters_set_high_pass(p_, stage, host_ratio, first_channel, count));
+    }
+    void set_envelope(std::uint32_t stage, const float *host_attack, const float *host_release, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_filters_set_envelope(p_, stage, host_attack, host_release, first_channel, count));
+    }
+    // the slot emptied and its state zeroed: that stage copies again; queued like a store
+    void drop(std::uint32_t stage, std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_filters_drop(p_, stage, first_channel, count)); }
+    // the state of slot `stage` (DSPFX_FILTERS_NONE: of every slot) back to +0.0; nodes and sliders stay; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count, std::uint32_t stage = DSPFX_FILTERS_NONE) {
+        chk(dspfx_filters_reset(p_, stage, first_channel, count));
+    }
+    // the host tables, as all stores so far left them: 1 / 0 (a slot of the channel carries a node); slot `stage`'s DSPFX_LOW_PASS ..
+    // or DSPFX_FILTERS_NONE; its [count][2] sliders as given (ratio, 0 | attack, release)
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_filters_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> kinds(std::uint32_t stage, std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_filters_kinds(p_, stage, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<float> sliders(std::uint32_t stage, std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<float> m(2 * count);
+        chk(dspfx_filters_sliders(p_, stage, m.data(), first_channel, count));
+        return m;
+    }
+    // slot `stage`'s state[channels] on the device: z or the envelope after the last run, on its stream
+    const float *state(std::uint32_t stage) {
+        const float *z = nullptr;
+        chk(dspfx_filters_state(p_, stage, &z));
+        return z;
+    }
+    dspfx_filters *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_filters_last_error(p_) ? dspfx_filters_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_filters *p_ = nullptr;
+};
+
+// The device bytes of a ChannelFilters bank's tables (dspfx_filters_plan: a pure host function, no GPU).
+inline std::uint64_t filters_plan(std::uint64_t channels, std::uint32_t stages) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_filters_plan(channels, stages, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_filters_last_error(nullptr));
+    return bytes;
+}
+
 // Per-channel Signal Generators (include/dspfx.h, dspfx_gens_*), a source that lives on the device: channel c may carry one
 // generator of its own -- amplitude, frequency, mode (DSPFX_SIG_*) and clock -- over device blocks in the layout of tile_channels; its
 // sample is bit for bit what an engine whose chain is that one Signal Generator writes for it over the same block lengths.  A node
