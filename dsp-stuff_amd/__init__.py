@@ -1103,10 +1103,24 @@ class _ChannelBank(_Bank):
     count and arrays of it, a host table read back, a view of a device table, and the output block a run makes."""
 
     _WHY = True
+    _DESC = None        # the bank's description in ctypes: abi_version, device, n_channels, max_frames, tile_channels, then its own fields
+
+    def __init__(self, channels, tile_channels, max_frames, device, *more):
+        """The fields, then the bank on the device; `more`: the description's fields behind the common five."""
+        self._fields(channels, tile_channels, max_frames, device)
+        self._open(*more)
 
     def _fields(self, channels, tile_channels, max_frames, device):
         self.L = lib()
         self.channels, self.tile_channels, self.max_frames, self.device = int(channels), int(tile_channels), int(max_frames), int(device)
+
+    def _open(self, *more):
+        self._create(self._DESC(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF,
+                                *more))
+
+    def _span(self, call, first_channel, count):
+        """dspfx_<bank>_<call> over `count` channels from first_channel (default: all from it): a drop, a reset."""
+        self._chk(getattr(self.L, f"dspfx_{self._C}_{call}")(self.h, int(first_channel), self._n(first_channel, count)))
 
     def _n(self, first_channel, count):
         return self.channels - int(first_channel) if count is None else int(count)
@@ -1169,6 +1183,15 @@ class _ChannelBank(_Bank):
 
 def _stream(stream):
     return C.c_void_p(stream) if stream else None
+
+
+def _plan_bytes(bank, channels, *more) -> int:
+    """dspfx_<bank>_plan(channels, more.., &bytes) -> bytes, of the banks whose plan is one byte count."""
+    L = lib()
+    n = C.c_uint64()
+    rc = getattr(L, f"dspfx_{bank}_plan")(int(channels) & 0xFFFFFFFFFFFFFFFF, *[int(m) & 0xFFFFFFFF for m in more], C.byref(n))
+    _raise(L, bank, rc)
+    return int(n.value)
 
 
 class PitchBank(_Bank):
@@ -1729,14 +1752,12 @@ class ChannelStrips(_ChannelBank):
     Between eng.process and MixGroups.run / returns, or ahead of the chain.  Asynchronous on `stream`."""
 
     _C = "strips"
+    _DESC = _StripsDesc
 
     def __init__(self, channels: int, bands: int = 1, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
                  device: int = 0):
-        self._fields(channels, tile_channels, max_frames, device)
         self.bands, self.link_flags = int(bands), int(link_flags)
-        d = _StripsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
-                        self.bands & 0xFFFFFFFF, self.link_flags & 0xFFFFFFFF)
-        self._create(d)
+        super().__init__(channels, tile_channels, max_frames, device, self.bands & 0xFFFFFFFF, self.link_flags & 0xFFFFFFFF)
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's strip -> `out`, a device block in the same layout (made when not given;
@@ -1807,14 +1828,12 @@ class ChannelDelays(_ChannelBank):
     the node.  Where ChannelStrips goes: between eng.process and the room mixes.  Asynchronous on `stream`."""
 
     _C = "delays"
+    _DESC = _DelaysDesc
 
     def __init__(self, channels: int, max_seconds: float = 0.5, tile_channels: int = 0, max_frames: int = BUF_SIZE, link_flags: int = 0,
                  page_round: bool = False, device: int = 0):
-        self._fields(channels, tile_channels, max_frames, device)
         self.max_seconds, self.link_flags, self.page_round = float(max_seconds), int(link_flags), bool(page_round)
-        d = _DelaysDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
-                        self.max_seconds, int(self.page_round), self.link_flags & 0xFFFFFFFF)
-        self._create(d)
+        super().__init__(channels, tile_channels, max_frames, device, self.max_seconds, int(self.page_round), self.link_flags & 0xFFFFFFFF)
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's delay -> `out`, a device block in the same layout (made when not given;
@@ -1857,11 +1876,7 @@ def envelope_gain(frames: float) -> np.float32:
 def talkers_plan(channels: int, groups: int) -> int:
     """dspfx_talkers_plan, a pure host function (no GPU): the device bytes of a Talkers bank's tables, 29 per channel and 69 per
     room plus 4 (a bank that hands out Talkers.audible() holds 4 per channel and 4 per room more)."""
-    L = lib()
-    n = C.c_uint64()
-    rc = L.dspfx_talkers_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, int(groups) & 0xFFFFFFFF, C.byref(n))
-    _raise(L, "talkers", rc)
-    return int(n.value)
+    return _plan_bytes("talkers", channels, groups)
 
 
 def _u8_per(values, n: int, what: str) -> np.ndarray:
@@ -1925,6 +1940,7 @@ class Talkers(_ChannelBank):
     block.  Between ChannelStrips / ChannelDelays and the room mixes.  Asynchronous on `stream`."""
 
     _C = "talkers"
+    _DESC = _TalkersDesc
     _ENTRIES = "talkers: the arrays name different numbers of entries"
 
     def __init__(self, channels: int, group_start=None, group_size=None, top: int = 3, tile_channels: int = 0, max_frames: int = BUF_SIZE,
@@ -1933,9 +1949,7 @@ class Talkers(_ChannelBank):
         self.top = int(top)
         self.group_start = _group_table(self.channels, group_start, group_size)
         self.groups = len(self.group_start) - 1
-        d = _TalkersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels,
-                         self.groups, self.top & 0xFFFFFFFF, self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))
-        self._create(d)  # the table is copied before this returns
+        self._open(self.groups, self.top & 0xFFFFFFFF, self.group_start.ctypes.data_as(C.POINTER(C.c_uint64)))  # (the table is copied in there)
         ptrs = [C.c_void_p() for _ in range(4)]
         self._chk(self.L.dspfx_talkers_views(self.h, *[C.byref(p) for p in ptrs]))
         self._views = [p.value for p in ptrs]
@@ -1989,8 +2003,7 @@ class Talkers(_ChannelBank):
     def reset(self, first_channel: int = 0, count: Optional[int] = None):
         """Envelope and level back to 0, gate and target to 1 on `count` channels from first_channel (default: all from it); queued
         like a store.  The way out for a channel whose envelope became NaN."""
-        n = self._n(first_channel, count)
-        self._chk(self.L.dspfx_talkers_reset(self.h, int(first_channel), n))
+        self._span("reset", first_channel, count)
 
     def room_of(self) -> np.ndarray:
         """uint32[channels]: the room of every channel (NO_ROOM: none) by every assign made so far."""
@@ -2037,11 +2050,7 @@ class Talkers(_ChannelBank):
 
 def dynamics_plan(channels: int) -> int:
     """dspfx_dynamics_plan, a pure host function (no GPU): the device bytes of a ChannelDynamics bank's tables, 29 per channel."""
-    L = lib()
-    n = C.c_uint64()
-    rc = L.dspfx_dynamics_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
-    _raise(L, "dynamics", rc)
-    return int(n.value)
+    return _plan_bytes("dynamics", channels)
 
 
 def dynamics_gain(env: float, threshold: float, makeup: float = 1.0):
@@ -2061,11 +2070,10 @@ class ChannelDynamics(_ChannelBank):
     ..).  Ahead of Talkers as a leveller, behind the room mixes as a limiter.  Asynchronous on `stream`."""
 
     _C = "dynamics"
+    _DESC = _DynamicsDesc
 
     def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self._fields(channels, tile_channels, max_frames, device)
-        d = _DynamicsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
-        self._create(d)
+        super().__init__(channels, tile_channels, max_frames, device)
         ptrs = [C.c_void_p() for _ in range(2)]
         self._chk(self.L.dspfx_dynamics_views(self.h, *[C.byref(p) for p in ptrs]))
         self._views = [p.value for p in ptrs]
@@ -2094,12 +2102,12 @@ class ChannelDynamics(_ChannelBank):
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node of `count` channels from first_channel (default: all from it) and clear their envelope; queued like a
         store."""
-        self._chk(self.L.dspfx_dynamics_drop(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("drop", first_channel, count)
 
     def reset(self, first_channel: int = 0, count: Optional[int] = None):
         """Envelope and level back to 0 and reduction to 1 on `count` channels from first_channel (default: all from it); the
         sliders and the nodes stay; queued like a store.  The way out for a channel whose envelope became NaN."""
-        self._chk(self.L.dspfx_dynamics_reset(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("reset", first_channel, count)
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
@@ -2117,11 +2125,7 @@ class ChannelDynamics(_ChannelBank):
 
 def shapers_plan(channels: int) -> int:
     """dspfx_shapers_plan, a pure host function (no GPU): the device bytes of a ChannelShapers bank's tables, 13 per channel."""
-    L = lib()
-    n = C.c_uint64()
-    rc = L.dspfx_shapers_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
-    _raise(L, "shapers", rc)
-    return int(n.value)
+    return _plan_bytes("shapers", channels)
 
 
 class ChannelShapers(_ChannelBank):
@@ -2135,11 +2139,10 @@ class ChannelShapers(_ChannelBank):
     `stream`."""
 
     _C = "shapers"
+    _DESC = _ShapersDesc
 
     def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self._fields(channels, tile_channels, max_frames, device)
-        d = _ShapersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
-        self._create(d)
+        super().__init__(channels, tile_channels, max_frames, device)
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's shaper -> `out`, a device block in the same layout (made when not given;
@@ -2175,7 +2178,7 @@ class ChannelShapers(_ChannelBank):
 
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node of `count` channels from first_channel (default: all from it): a copy again; queued like a store."""
-        self._chk(self.L.dspfx_shapers_drop(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("drop", first_channel, count)
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
@@ -2196,11 +2199,7 @@ class ChannelShapers(_ChannelBank):
 
 def gens_plan(channels: int) -> int:
     """dspfx_gens_plan, a pure host function (no GPU): the device bytes of a ChannelGenerators bank's tables, 13 per channel."""
-    L = lib()
-    n = C.c_uint64()
-    rc = L.dspfx_gens_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
-    _raise(L, "gens", rc)
-    return int(n.value)
+    return _plan_bytes("gens", channels)
 
 
 class ChannelGenerators(_ChannelBank):
@@ -2213,11 +2212,10 @@ class ChannelGenerators(_ChannelBank):
     Asynchronous on `stream`."""
 
     _C = "gens"
+    _DESC = _GensDesc
 
     def __init__(self, channels: int, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self._fields(channels, tile_channels, max_frames, device)
-        d = _GensDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF)
-        self._create(d)
+        super().__init__(channels, tile_channels, max_frames, device)
         p = C.c_void_p()
         self._chk(self.L.dspfx_gens_clocks(self.h, C.byref(p)))
         self._clock = p.value
@@ -2247,11 +2245,11 @@ class ChannelGenerators(_ChannelBank):
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node of `count` channels from first_channel (default: all from it): +0.0 again, and a later `set` starts from
         the defaults at clock 0; queued like a store."""
-        self._chk(self.L.dspfx_gens_drop(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("drop", first_channel, count)
 
     def reset(self, first_channel: int = 0, count: Optional[int] = None):
         """Clock back to +0.0 on the channels of the range that carry a node; sliders, modes and nodes stay; queued like a store."""
-        self._chk(self.L.dspfx_gens_reset(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("reset", first_channel, count)
 
     def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
@@ -2274,11 +2272,7 @@ class ChannelGenerators(_ChannelBank):
 def blends_plan(channels: int) -> int:
     """dspfx_blends_plan, a pure host function (no GPU): the device bytes of a ChannelBlends bank's tables, 13 per channel (ratio,
     send level, bus id and a kind / presence byte)."""
-    L = lib()
-    n = C.c_uint64()
-    rc = L.dspfx_blends_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, C.byref(n))
-    _raise(L, "blends", rc)
-    return int(n.value)
+    return _plan_bytes("blends", channels)
 
 
 class ChannelBlends(_ChannelBank):
@@ -2291,6 +2285,7 @@ class ChannelBlends(_ChannelBank):
     connected per call and is not latched into the slider.  Asynchronous on `stream`."""
 
     _C = "blends"
+    _DESC = _BlendsDesc
 
     def __init__(self, channels: int, buses: int = 0, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0,
                  group_size=None, group_start=None):
@@ -2302,9 +2297,7 @@ class ChannelBlends(_ChannelBank):
                 raise ValueError(f"buses {buses} is not the {len(table) - 1} groups of the table")
             buses = len(table) - 1
         self.buses = int(buses)
-        d = _BlendsDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF,
-                        self.buses & 0xFFFFFFFF)
-        self._create(d)
+        self._open(self.buses & 0xFFFFFFFF)
         if table is not None:
             self.assign(np.repeat(np.arange(self.buses, dtype=np.uint32), np.diff(table).astype(np.int64)))
 
@@ -2331,7 +2324,7 @@ class ChannelBlends(_ChannelBank):
 
     def set_add(self, first_channel: int = 0, count: Optional[int] = None):
         """Give `count` channels from first_channel (default: all from it) an Add node; queued like every store."""
-        self._chk(self.L.dspfx_blends_set_add(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("set_add", first_channel, count)
 
     def set_send(self, level, first_channel: int = 0, count: Optional[int] = None):
         """Give channels from first_channel a send, a Gain node on the second input: `level` is an array or a scalar for `count`
@@ -2350,7 +2343,7 @@ class ChannelBlends(_ChannelBank):
     def drop(self, first_channel: int = 0, count: Optional[int] = None):
         """Remove the node and the send of `count` channels from first_channel (default: all from it): a copy of `a` again; the bus
         id stays; queued like a store."""
-        self._chk(self.L.dspfx_blends_drop(self.h, int(first_channel), self._n(first_channel, count)))
+        self._span("drop", first_channel, count)
 
     def kinds(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
         """uint32[count]: ADD, MIX or BLENDS_NONE, as every store made so far left it."""
@@ -2377,11 +2370,7 @@ class ChannelBlends(_ChannelBank):
 def filters_plan(channels: int, stages: int = 1) -> int:
     """dspfx_filters_plan, a pure host function (no GPU): the device bytes of a ChannelFilters bank's tables, 13 per channel and
     stage (two sliders, the state, the kind byte)."""
-    L = lib()
-    n = C.c_uint64()
-    rc = L.dspfx_filters_plan(int(channels) & 0xFFFFFFFFFFFFFFFF, int(stages) & 0xFFFFFFFF, C.byref(n))
-    _raise(L, "filters", rc)
-    return int(n.value)
+    return _plan_bytes("filters", channels, stages)
 
 
 class ChannelFilters(_ChannelBank):
@@ -2394,13 +2383,11 @@ class ChannelFilters(_ChannelBank):
     leaves None and keeps the state.  Asynchronous on `stream`."""
 
     _C = "filters"
+    _DESC = _FiltersDesc
 
     def __init__(self, channels: int, stages: int = 1, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
-        self._fields(channels, tile_channels, max_frames, device)
         self.stages = int(stages)
-        d = _FiltersDesc(ABI_VERSION, self.device, self.channels & 0xFFFFFFFF, self.max_frames & 0xFFFFFFFF, self.tile_channels & 0xFFFFFFFF,
-                         self.stages & 0xFFFFFFFF)
-        self._create(d)
+        super().__init__(channels, tile_channels, max_frames, device, self.stages & 0xFFFFFFFF)
 
     def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
         """One device block through every channel's slots -> `out`, a device block in the same layout (made when not given;

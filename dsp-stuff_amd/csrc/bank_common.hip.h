@@ -1,5 +1,5 @@
 // bank_common.hip.h -- what the banks share (pitch, resample, spectrum, convolve, mixgroups, mixmatrix and the per-channel banks
-// strips, delays, talkers, dynamics, shapers, gens, blends _kernels.hip): the desc's layout, 4-channel loads and stores in it, the slot copy,
+// strips, delays, talkers, dynamics, shapers, gens, blends, filters _kernels.hip): the desc's layout, 4-channel loads and stores in it, the slot copy,
 // and small host helpers -- all stateless -- and the scaffold of the banks that take live stores: the error holder, the shape /
 // range / table checks of their arguments, open_device, close_bank, release_bank and destroy_bank.  Host and device, hipcc only.
 // The FFT is in fft_core.hip.h, the staged stores in store_queue.hip.h, a lane's loads and stores of its own channels in
@@ -228,16 +228,24 @@ void close_bank(Bank *p, void (*release)(Bank *)) {
     release(p);
 }
 
-// a bank's `release`, where there is no more to it: the device pointers in `dev` (nullptr: never allocated), the staged stores'
-// buffers and events, the bank's event, the bank.  Bank has desc, stores (store_queue.hip.h) and ev
-template <class Bank>
-void release_bank(Bank *p, std::initializer_list<void *> dev) {
+// a bank's `release`, where there is no more to it: free_tables() frees its device memory (the device is set), then the staged
+// stores' buffers and events, the bank's event, the bank.  Bank has desc, stores (store_queue.hip.h) and ev
+template <class Bank, class FreeTables>
+void release_bank_by(Bank *p, FreeTables free_tables) {
     (void)hipSetDevice(p->desc.device);
-    for (void *d : dev)
-        if (d) (void)hipFree(d);
+    free_tables();
     p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
+}
+
+// ... the device pointers in `dev` (nullptr: never allocated)
+template <class Bank>
+void release_bank(Bank *p, std::initializer_list<void *> dev) {
+    release_bank_by(p, [&] {
+        for (void *d : dev)
+            if (d) (void)hipFree(d);
+    });
 }
 
 // the body of dspfx_<bank>_destroy

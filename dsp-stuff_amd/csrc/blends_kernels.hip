@@ -26,7 +26,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -122,9 +121,8 @@ __device__ __forceinline__ void blend_chunk(const Lane<CPL> &s, const LanePtrs &
 template <int CPL, int SRC, bool CTL>
 __global__ __launch_bounds__(BWG) void blends_run(BlendArgs g) {
     constexpr int F = (SRC != S_NONE || CTL) ? 4 : 8;      // frame rows per chunk (two chunks are in registers)
-    const uint64_t c64 = ((uint64_t)blockIdx.x * BWG + threadIdx.x) * CPL;
-    if (c64 >= g.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
-    const uint32_t c = (uint32_t)c64;
+    uint32_t c;
+    if (!lane_channel<CPL>(BWG, g.N, c)) return;
     Lane<CPL> s;
     uint8_t code[CPL];
     loadv<CPL>(g.code + c, code);
@@ -188,9 +186,6 @@ struct StoreFields {
 typedef StoreQueue<StoreFields> Stores;
 typedef Stores::Store Store;
 
-// the table bytes of a bank on the device: ratio, send level and bus id (12) and the kind / presence byte (1) per channel
-uint64_t table_bytes(uint64_t N) { return 13 * N; }
-
 }  // namespace
 
 struct dspfx_blends : ChannelBank<dspfx_blends_desc, StoreFields> {
@@ -201,11 +196,18 @@ struct dspfx_blends : ChannelBank<dspfx_blends_desc, StoreFields> {
     float *ratio = nullptr, *level = nullptr;
     uint32_t *bus_of = nullptr;
     uint8_t *code = nullptr;
+    // the fresh state: no node and no send anywhere, every channel on no bus
+    template <class V>
+    static void tables(const dspfx_blends_desc &d, V v) {
+        const uint64_t N = d.n_channels;
+        v(4 * N, 0, &dspfx_blends::ratio);
+        v(4 * N, 0, &dspfx_blends::level);
+        v(4 * N, 0xFF, &dspfx_blends::bus_of);
+        v(N, C_NONE, &dspfx_blends::code);
+    }
 };
 
 namespace {
-
-void release(dspfx_blends *p) { release_bank(p, {p->ratio, p->level, p->bus_of, p->code}); }
 
 // one store onto the stream (the bank's mu is held)
 hipError_t apply_store(dspfx_blends *p, const Store &st, hipStream_t s) {
@@ -223,14 +225,11 @@ hipError_t apply_store(dspfx_blends *p, const Store &st, hipStream_t s) {
 template <class Fill>
 int store_copy(dspfx_blends *p, const char *call, Table table, bool codes, uint64_t first, uint64_t count, Fill fill) {
     Store st;
-    st.kind = ST_COPY;
     st.table = table;
     st.codes = codes;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, (table != T_NONE ? count : 0) + (codes ? (count + 3) / 4 : 0), st))
-        return p->fail(DSPFX_ERR_OOM, (std::string("blends ") + call + ": no page-locked memory for the staged values").c_str());
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, ST_COPY, call, first, count, (table != T_NONE ? count : 0) + (codes ? (count + 3) / 4 : 0), "staged values"))
+        return DSPFX_ERR_OOM;
     float *vals = table != T_NONE ? st.vals : nullptr;
     uint8_t *cs = codes ? (uint8_t *)(st.vals + (table != T_NONE ? count : 0)) : nullptr;
     fill(vals, cs);
@@ -247,51 +246,21 @@ int store_copy(dspfx_blends *p, const char *call, Table table, bool codes, uint6
 
 extern "C" const char *dspfx_blends_last_error(const dspfx_blends *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
-extern "C" int dspfx_blends_plan(uint64_t channels, uint64_t *bytes_out) {
-    g_err.clear();
-    const int rc = check_shape("blends", channels, 0, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (bytes_out) *bytes_out = table_bytes(channels);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_blends_plan(uint64_t channels, uint64_t *bytes_out) { return plan_bank<dspfx_blends>(channels, bytes_out, g_err); }
 
 extern "C" int dspfx_blends_create(const dspfx_blends_desc *desc, dspfx_blends **out) {
     const int rc = create_checks(desc, out, g_err);
     if (rc != DSPFX_OK) return rc;
-    const uint32_t N = desc->n_channels;
-    dspfx_blends *p = new (std::nothrow) dspfx_blends;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    try {
+    return create_bank(desc, out, g_err, [](dspfx_blends *p) {
+        const uint32_t N = p->desc.n_channels;
         p->hratio.assign(N, 0.0f);
         p->hlevel.assign(N, 0.0f);
         p->hbus.assign(N, DSPFX_BLENDS_NO_BUS);
         p->hcode.assign(N, C_NONE);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t tab = (size_t)N * sizeof(float);
-    bool ok = hipMalloc((void **)&p->ratio, tab) == hipSuccess && hipMalloc((void **)&p->level, tab) == hipSuccess &&
-              hipMalloc((void **)&p->bus_of, tab) == hipSuccess && hipMalloc((void **)&p->code, N) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        return no_table_memory("blends", table_bytes(N), N, g_err);
-    }
-    // the fresh state: no node and no send anywhere, every channel on no bus
-    ok = hipMemset(p->ratio, 0, tab) == hipSuccess && hipMemset(p->level, 0, tab) == hipSuccess && hipMemset(p->bus_of, 0xFF, tab) == hipSuccess &&
-         hipMemset(p->code, C_NONE, N) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    });
 }
 
-extern "C" int dspfx_blends_destroy(dspfx_blends *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_blends_destroy(dspfx_blends *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_blends_set_mix(dspfx_blends *p, const float *host_ratio, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;

@@ -28,7 +28,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -258,11 +257,19 @@ struct dspfx_delays : ChannelBank<dspfx_delays_desc, StoreFields> {
     float *ring = nullptr, *decay = nullptr;
     uint32_t *len = nullptr, *pos = nullptr, *zero = nullptr;
     float div = 1.0f;
+    // the fresh state: no node anywhere.  The rings are not zeroed: a channel's first store says its next D taps read as +0.0
+    template <class V>
+    static void tables(const dspfx_delays_desc &d, V v) {
+        const uint64_t N = d.n_channels;
+        v(N * dspfx_delay_len(d.max_seconds, d.page_round ? 1 : 0) * 4, TABLE_BY_HAND, &dspfx_delays::ring);
+        v(4 * N, 0, &dspfx_delays::decay);
+        v(4 * N, 0, &dspfx_delays::len);
+        v(4 * N, 0, &dspfx_delays::pos);
+        v(4 * N, 0, &dspfx_delays::zero);
+    }
 };
 
 namespace {
-
-void release(dspfx_delays *p) { release_bank(p, {p->ring, p->decay, p->len, p->pos, p->zero}); }
 
 // one store onto the stream: its lengths and decays, then the new zero ring on its channels
 hipError_t apply_store(dspfx_delays *p, const Store &st, hipStream_t s) {
@@ -300,44 +307,21 @@ extern "C" int dspfx_delays_create(const dspfx_delays_desc *desc, dspfx_delays *
     });
     if (rc != DSPFX_OK) return rc;
     const uint32_t N = desc->n_channels;
-    dspfx_delays *p = new (std::nothrow) dspfx_delays;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    p->cap = cap;
-    p->div = dspfx_link_divisor(1);
-    try {
-        p->hlen.assign(N, 0u);
-        p->hsec.assign(N, 0.5f);
-        p->hdec.assign(N, 0.5f);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t tab = (size_t)N * sizeof(uint32_t);
-    // the rings are not zeroed: a channel's first store says its next D taps read as +0.0
-    bool ok = hipMalloc((void **)&p->ring, (size_t)bytes) == hipSuccess && hipMalloc((void **)&p->decay, tab) == hipSuccess &&
-              hipMalloc((void **)&p->len, tab) == hipSuccess && hipMalloc((void **)&p->pos, tab) == hipSuccess &&
-              hipMalloc((void **)&p->zero, tab) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        std::snprintf(buf, sizeof buf, "delays: no device memory for %llu bytes of rings (%u channels of %u frames) and the tables",
-                      (unsigned long long)bytes, N, cap);
-        g_err = buf;
-        return DSPFX_ERR_OOM;
-    }
-    ok = hipMemset(p->decay, 0, tab) == hipSuccess && hipMemset(p->len, 0, tab) == hipSuccess && hipMemset(p->pos, 0, tab) == hipSuccess &&
-         hipMemset(p->zero, 0, tab) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    std::snprintf(buf, sizeof buf, "delays: no device memory for %llu bytes of rings (%u channels of %u frames) and the tables", (unsigned long long)bytes,
+                  N, cap);
+    return create_bank(
+        desc, out, g_err,
+        [N, cap](dspfx_delays *p) {
+            p->cap = cap;
+            p->div = dspfx_link_divisor(1);
+            p->hlen.assign(N, 0u);
+            p->hsec.assign(N, 0.5f);
+            p->hdec.assign(N, 0.5f);
+        },
+        nullptr, buf);
 }
 
-extern "C" int dspfx_delays_destroy(dspfx_delays *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_delays_destroy(dspfx_delays *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_delays_set_delay(dspfx_delays *p, const float *host_seconds, const float *host_decay, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
@@ -369,7 +353,7 @@ extern "C" int dspfx_delays_set_delay(dspfx_delays *p, const float *host_seconds
             return p->fail(DSPFX_ERR_INVALID, buf);
         }
     }
-    if (!p->stores.staging(p->desc.device, 2 * count, st)) return p->fail(DSPFX_ERR_OOM, "delays set_delay: no page-locked memory for the staged sliders");
+    if (!stage_store(p, st, nullptr, "set_delay", first_channel, count, 2 * count, "staged sliders")) return DSPFX_ERR_OOM;      // (smu is held)
     uint32_t *lens = (uint32_t *)st.vals;
     float *decs = st.vals + count;
     for (uint64_t i = 0; i < count; ++i) {

@@ -19,7 +19,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -76,9 +75,8 @@ __device__ __forceinline__ void dyn_rows(float (&v)[R][CPL], const float (&k)[R]
 template <int CPL, bool KEYED>
 __global__ __launch_bounds__(WG) void dynamics_run(DynArgs a) {
     constexpr int F = KEYED ? 4 : 8;                       // frame rows per chunk (two chunks of every stream are in registers)
-    const uint64_t c64 = ((uint64_t)blockIdx.x * WG + threadIdx.x) * CPL;
-    if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
-    const uint32_t c = (uint32_t)c64;
+    uint32_t c;
+    if (!lane_channel<CPL>(WG, a.N, c)) return;
     Chan<CPL> s;
     uint8_t pres[CPL];
     loadv<CPL>(a.env + c, s.env);
@@ -160,9 +158,6 @@ struct StoreFields {
 typedef StoreQueue<StoreFields> Stores;
 typedef Stores::Store Store;
 
-// the table bytes of a bank on the device: ga, gr, thr, mk, env, level and reduction (28) and the presence (1) per channel
-uint64_t table_bytes(uint64_t N) { return 29 * N; }
-
 }  // namespace
 
 struct dspfx_dynamics : ChannelBank<dspfx_dynamics_desc, StoreFields> {
@@ -171,11 +166,17 @@ struct dspfx_dynamics : ChannelBank<dspfx_dynamics_desc, StoreFields> {
     std::vector<uint8_t> hpres;                  // [N]
     float *env = nullptr, *level = nullptr, *red = nullptr, *ga = nullptr, *gr = nullptr, *thr = nullptr, *mk = nullptr;
     uint8_t *pres = nullptr;
+    // the fresh state: no node anywhere.  The state at rest is not one byte over (the reduction is 1.0): create runs dynamics_fresh
+    template <class V>
+    static void tables(const dspfx_dynamics_desc &d, V v) {
+        const uint64_t N = d.n_channels;
+        for (auto m : {&dspfx_dynamics::env, &dspfx_dynamics::level, &dspfx_dynamics::red}) v(4 * N, TABLE_BY_HAND, m);
+        for (auto m : {&dspfx_dynamics::ga, &dspfx_dynamics::gr, &dspfx_dynamics::thr, &dspfx_dynamics::mk}) v(4 * N, 0, m);
+        v(N, 0, &dspfx_dynamics::pres);
+    }
 };
 
 namespace {
-
-void release(dspfx_dynamics *p) { release_bank(p, {p->env, p->level, p->red, p->ga, p->gr, p->thr, p->mk, p->pres}); }
 
 // one store onto the stream
 hipError_t apply_store(dspfx_dynamics *p, const Store &st, hipStream_t s) {
@@ -209,55 +210,29 @@ extern "C" float dspfx_dynamics_gain(float env, float threshold, float makeup, f
     return makeup * q;
 }
 
-extern "C" int dspfx_dynamics_plan(uint64_t channels, uint64_t *bytes_out) {
-    g_err.clear();
-    const int rc = check_shape("dynamics", channels, 0, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (bytes_out) *bytes_out = table_bytes(channels);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_dynamics_plan(uint64_t channels, uint64_t *bytes_out) { return plan_bank<dspfx_dynamics>(channels, bytes_out, g_err); }
 
 extern "C" int dspfx_dynamics_create(const dspfx_dynamics_desc *desc, dspfx_dynamics **out) {
     const int rc = create_checks(desc, out, g_err);
     if (rc != DSPFX_OK) return rc;
     const uint32_t N = desc->n_channels;
-    dspfx_dynamics *p = new (std::nothrow) dspfx_dynamics;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    try {
-        p->hga.assign(N, 0.0f);
-        p->hgr.assign(N, 0.0f);
-        p->hthr.assign(N, 1.0f);
-        p->hmk.assign(N, 1.0f);
-        p->hpres.assign(N, 0);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t tab = (size_t)N * sizeof(float);
-    bool ok = hipMalloc((void **)&p->env, tab) == hipSuccess && hipMalloc((void **)&p->level, tab) == hipSuccess &&
-              hipMalloc((void **)&p->red, tab) == hipSuccess && hipMalloc((void **)&p->ga, tab) == hipSuccess &&
-              hipMalloc((void **)&p->gr, tab) == hipSuccess && hipMalloc((void **)&p->thr, tab) == hipSuccess &&
-              hipMalloc((void **)&p->mk, tab) == hipSuccess && hipMalloc((void **)&p->pres, N) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        return no_table_memory("dynamics", table_bytes(N), N, g_err);
-    }
-    // the fresh state: no node anywhere
-    dynamics_fresh<<<(N + WG - 1) / WG, WG>>>(p->env, p->level, p->red, 0u, N);
-    ok = hipGetLastError() == hipSuccess && hipMemset(p->ga, 0, tab) == hipSuccess && hipMemset(p->gr, 0, tab) == hipSuccess &&
-         hipMemset(p->thr, 0, tab) == hipSuccess && hipMemset(p->mk, 0, tab) == hipSuccess && hipMemset(p->pres, 0, N) == hipSuccess &&
-         hipDeviceSynchronize() == hipSuccess && hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    return create_bank(
+        desc, out, g_err,
+        [N](dspfx_dynamics *p) {
+            p->hga.assign(N, 0.0f);
+            p->hgr.assign(N, 0.0f);
+            p->hthr.assign(N, 1.0f);
+            p->hmk.assign(N, 1.0f);
+            p->hpres.assign(N, 0);
+        },
+        [N](dspfx_dynamics *p) {
+            dynamics_fresh<<<(N + WG - 1) / WG, WG>>>(p->env, p->level, p->red, 0u, N);
+            return hipGetLastError();
+        },
+        nullptr);
 }
 
-extern "C" int dspfx_dynamics_destroy(dspfx_dynamics *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_dynamics_destroy(dspfx_dynamics *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_dynamics_set(dspfx_dynamics *p, const float *host_threshold, const float *host_makeup, const float *host_attack,
                                   const float *host_release, uint64_t first_channel, uint64_t count) {
@@ -280,11 +255,8 @@ extern "C" int dspfx_dynamics_set(dspfx_dynamics *p, const float *host_threshold
     }
     if (count == 0) return DSPFX_OK;
     Store st;
-    st.kind = ST_SLIDERS;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, 4 * count, st)) return p->fail(DSPFX_ERR_OOM, "dynamics set: no page-locked memory for the staged sliders");
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, ST_SLIDERS, "set", first_channel, count, 4 * count, "staged sliders")) return DSPFX_ERR_OOM;
     float *a = st.vals, *r = a + count, *t = r + count, *m = t + count;
     for (uint64_t i = 0; i < count; ++i) {
         a[i] = host_attack ? dspfx_envelope_gain(host_attack[i]) : p->hga[first_channel + i];

@@ -26,7 +26,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -127,9 +126,8 @@ __device__ __forceinline__ void filt_stages(uint32_t kinds, float (&v)[R][CPL], 
 template <int S, int CPL>
 __global__ __launch_bounds__(FWG) void filters_run(FiltArgs a) {
     constexpr int F = CPL == 4 ? 4 : 8;
-    const uint64_t c64 = ((uint64_t)blockIdx.x * FWG + threadIdx.x) * CPL;
-    if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
-    const uint32_t c = (uint32_t)c64;
+    uint32_t c;
+    if (!lane_channel<CPL>(FWG, a.N, c)) return;
     Lane<S, CPL> s;
     uint32_t kinds = 0;
 #pragma unroll
@@ -212,9 +210,6 @@ struct StoreFields {
 typedef StoreQueue<StoreFields> Stores;
 typedef Stores::Store Store;
 
-// the table bytes of a bank on the device: two sliders (8), the state (4) and the kind code (1) per channel and stage
-uint64_t table_bytes(uint64_t N, uint32_t stages) { return 13 * (uint64_t)stages * N; }
-
 uint32_t code_kind(uint8_t k) { return k == C_LP ? DSPFX_LOW_PASS : k == C_HP ? DSPFX_HIGH_PASS : k == C_ENV ? DSPFX_ENVELOPE : DSPFX_FILTERS_NONE; }
 
 int check_stages(uint32_t stages, std::string &err) {
@@ -233,11 +228,18 @@ struct dspfx_filters : ChannelBank<dspfx_filters_desc, StoreFields> {
     std::vector<uint8_t> hkind;                  // [stages][N]: ... and the kind codes
     float *a = nullptr, *b = nullptr, *z = nullptr;
     uint8_t *kind = nullptr;
+    // the fresh state: every slot of every channel empty, every table at rest
+    template <class V>
+    static void tables(const dspfx_filters_desc &d, V v) {
+        const uint64_t slots = (uint64_t)d.stages * d.n_channels;
+        v(4 * slots, 0, &dspfx_filters::a);
+        v(4 * slots, 0, &dspfx_filters::b);
+        v(4 * slots, 0, &dspfx_filters::z);
+        v(slots, C_NONE, &dspfx_filters::kind);
+    }
 };
 
 namespace {
-
-void release(dspfx_filters *p) { release_bank(p, {p->a, p->b, p->z, p->kind}); }
 
 // one store onto the stream
 hipError_t apply_store(dspfx_filters *p, const Store &st, hipStream_t s) {
@@ -281,16 +283,9 @@ int store_nodes(dspfx_filters *p, const char *call, uint8_t code, int n_sliders,
     if (rc != DSPFX_OK) return rc;
     if (count == 0) return DSPFX_OK;
     Store st;
-    st.kind = ST_NODES;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
     st.stage = stage;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, 4 * count + (count + 3) / 4, st)) {
-        char buf[96];
-        std::snprintf(buf, sizeof buf, "filters %s: no page-locked memory for the staged sliders", call);
-        return p->fail(DSPFX_ERR_OOM, buf);
-    }
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, ST_NODES, call, first, count, 4 * count + (count + 3) / 4, "staged sliders")) return DSPFX_ERR_OOM;
     const size_t at = (size_t)stage * p->desc.n_channels + first;
     float *da = st.vals, *db = da + count, *given[2] = {db + count, db + 2 * count};
     uint8_t *codes = (uint8_t *)(st.vals + 4 * count);
@@ -309,22 +304,13 @@ int store_nodes(dspfx_filters *p, const char *call, uint8_t code, int n_sliders,
     return DSPFX_OK;
 }
 
-// channel_bank's store_plain with the stages a drop or a reset names: a store without values over a range of stages
-// [stage, stage + n_stages); `also` runs under the queue's lock as the store joins
+// channel_bank's store_plain with the stages a drop or a reset names: [stage, stage + n_stages)
 template <class Also>
 int store_stages(dspfx_filters *p, StoreKind kind, const char *call, uint32_t stage, uint32_t n_stages, uint64_t first, uint64_t count, Also also) {
-    const int rc = check_range(p, call, first, count);
-    if (rc != DSPFX_OK) return rc;
-    if (count == 0) return DSPFX_OK;
-    Store st;
-    st.kind = kind;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
-    st.stage = stage;
-    st.n_stages = n_stages;
-    std::lock_guard<std::mutex> one(p->smu);
-    p->stores.push(st, also);
-    return DSPFX_OK;
+    return store_plain(p, kind, call, first, count, also, [=](Store &st) {
+        st.stage = stage;
+        st.n_stages = n_stages;
+    });
 }
 
 template <int S>
@@ -338,50 +324,23 @@ void launch_run(const FiltArgs &a, bool vec, uint32_t blocks, hipStream_t s) {
 extern "C" const char *dspfx_filters_last_error(const dspfx_filters *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
 extern "C" int dspfx_filters_plan(uint64_t channels, uint32_t stages, uint64_t *bytes_out) {
-    g_err.clear();
-    int rc = check_shape("filters", channels, 0, g_err);
-    if (rc == DSPFX_OK) rc = check_stages(stages, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (bytes_out) *bytes_out = table_bytes(channels, stages);
-    return DSPFX_OK;
+    return plan_bank<dspfx_filters>(channels, bytes_out, g_err, [stages](dspfx_filters_desc &d, std::string &err) {
+        d.stages = stages;
+        return check_stages(stages, err);
+    });
 }
 
 extern "C" int dspfx_filters_create(const dspfx_filters_desc *desc, dspfx_filters **out) {
     const int rc = create_checks(desc, out, g_err, [desc](std::string &err) { return check_stages(desc->stages, err); });
     if (rc != DSPFX_OK) return rc;
-    const uint32_t N = desc->n_channels;
-    const size_t slots = (size_t)desc->stages * N;
-    dspfx_filters *p = new (std::nothrow) dspfx_filters;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    try {
+    return create_bank(desc, out, g_err, [](dspfx_filters *p) {
+        const size_t slots = (size_t)p->desc.stages * p->desc.n_channels;
         for (auto &h : p->hs) h.assign(slots, 0.0f);
         p->hkind.assign(slots, C_NONE);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t tab = slots * sizeof(float);
-    bool ok = hipMalloc((void **)&p->a, tab) == hipSuccess && hipMalloc((void **)&p->b, tab) == hipSuccess &&
-              hipMalloc((void **)&p->z, tab) == hipSuccess && hipMalloc((void **)&p->kind, slots) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        return no_table_memory("filters", table_bytes(N, desc->stages), N, g_err);
-    }
-    // the fresh state: every slot of every channel empty, every table at rest
-    ok = hipMemset(p->a, 0, tab) == hipSuccess && hipMemset(p->b, 0, tab) == hipSuccess && hipMemset(p->z, 0, tab) == hipSuccess &&
-         hipMemset(p->kind, C_NONE, slots) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    });
 }
 
-extern "C" int dspfx_filters_destroy(dspfx_filters *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_filters_destroy(dspfx_filters *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_filters_set_low_pass(dspfx_filters *p, uint32_t stage, const float *host_ratio, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;

@@ -24,7 +24,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -148,9 +147,8 @@ __device__ __forceinline__ void close_block(Lane<CPL> &s) {
 template <int CPL, bool CTL>
 __global__ __launch_bounds__(GWG) void gens_run(GenArgs a) {
     constexpr int F = CTL ? 4 : 8;                         // frame rows per chunk (two chunks are in registers); F divides 128
-    const uint64_t c64 = ((uint64_t)blockIdx.x * GWG + threadIdx.x) * CPL;
-    if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
-    const uint32_t c = (uint32_t)c64;
+    uint32_t c;
+    if (!lane_channel<CPL>(GWG, a.N, c)) return;
     Lane<CPL> s;
     uint8_t code[CPL];
     loadv<CPL>(a.amp + c, s.amp);
@@ -219,9 +217,6 @@ struct StoreFields {
 typedef StoreQueue<StoreFields> Stores;
 typedef Stores::Store Store;
 
-// the table bytes of a bank on the device: amplitude, frequency and clock (12) and the mode / presence byte (1) per channel
-uint64_t table_bytes(uint64_t N) { return 13 * N; }
-
 }  // namespace
 
 struct dspfx_gens : ChannelBank<dspfx_gens_desc, StoreFields> {
@@ -230,11 +225,18 @@ struct dspfx_gens : ChannelBank<dspfx_gens_desc, StoreFields> {
     std::vector<uint8_t> hcode;                  // [N]: ... and the mode / presence bytes
     float *amp = nullptr, *freq = nullptr, *clock = nullptr;
     uint8_t *code = nullptr;
+    // the fresh state: no node anywhere, every clock +0.0
+    template <class V>
+    static void tables(const dspfx_gens_desc &d, V v) {
+        const uint64_t N = d.n_channels;
+        v(4 * N, 0, &dspfx_gens::amp);
+        v(4 * N, 0, &dspfx_gens::freq);
+        v(4 * N, 0, &dspfx_gens::clock);
+        v(N, C_NONE, &dspfx_gens::code);
+    }
 };
 
 namespace {
-
-void release(dspfx_gens *p) { release_bank(p, {p->amp, p->freq, p->clock, p->code}); }
 
 // one store onto the stream (the bank's mu is held).  A channel without a node has clock +0.0 at all times, so SET writes no clock
 hipError_t apply_store(dspfx_gens *p, const Store &st, hipStream_t s) {
@@ -261,50 +263,20 @@ hipError_t apply_store(dspfx_gens *p, const Store &st, hipStream_t s) {
 
 extern "C" const char *dspfx_gens_last_error(const dspfx_gens *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
-extern "C" int dspfx_gens_plan(uint64_t channels, uint64_t *bytes_out) {
-    g_err.clear();
-    const int rc = check_shape("gens", channels, 0, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (bytes_out) *bytes_out = table_bytes(channels);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_gens_plan(uint64_t channels, uint64_t *bytes_out) { return plan_bank<dspfx_gens>(channels, bytes_out, g_err); }
 
 extern "C" int dspfx_gens_create(const dspfx_gens_desc *desc, dspfx_gens **out) {
     const int rc = create_checks(desc, out, g_err);
     if (rc != DSPFX_OK) return rc;
-    const uint32_t N = desc->n_channels;
-    dspfx_gens *p = new (std::nothrow) dspfx_gens;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    try {
+    return create_bank(desc, out, g_err, [](dspfx_gens *p) {
+        const uint32_t N = p->desc.n_channels;
         p->hamp.assign(N, 0.0f);
         p->hfreq.assign(N, 0.0f);
         p->hcode.assign(N, C_NONE);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t tab = (size_t)N * sizeof(float);
-    bool ok = hipMalloc((void **)&p->amp, tab) == hipSuccess && hipMalloc((void **)&p->freq, tab) == hipSuccess &&
-              hipMalloc((void **)&p->clock, tab) == hipSuccess && hipMalloc((void **)&p->code, N) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        return no_table_memory("gens", table_bytes(N), N, g_err);
-    }
-    // the fresh state: no node anywhere, every clock +0.0
-    ok = hipMemset(p->amp, 0, tab) == hipSuccess && hipMemset(p->freq, 0, tab) == hipSuccess && hipMemset(p->clock, 0, tab) == hipSuccess &&
-         hipMemset(p->code, C_NONE, N) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    });
 }
 
-extern "C" int dspfx_gens_destroy(dspfx_gens *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_gens_destroy(dspfx_gens *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_gens_set(dspfx_gens *p, const float *host_amplitude, const float *host_frequency, const uint32_t *host_mode,
                               uint64_t first_channel, uint64_t count) {
@@ -323,12 +295,8 @@ extern "C" int dspfx_gens_set(dspfx_gens *p, const float *host_amplitude, const 
     dspfx_node_desc def;
     if (dspfx_node_defaults(DSPFX_SIGNAL_GEN, &def) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, "gens: no such node kind");
     Store st;
-    st.kind = ST_SET;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, 2 * count + (count + 3) / 4, st))
-        return p->fail(DSPFX_ERR_OOM, "gens set: no page-locked memory for the staged sliders");
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, ST_SET, "set", first_channel, count, 2 * count + (count + 3) / 4, "staged sliders")) return DSPFX_ERR_OOM;
     uint8_t *codes = (uint8_t *)(st.vals + 2 * count);
     for (uint64_t i = 0; i < count; ++i) {
         const uint64_t c = first_channel + i;

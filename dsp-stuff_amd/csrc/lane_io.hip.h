@@ -1,6 +1,6 @@
-// lane_io.hip.h -- how a lane of the per-channel banks (strips, talkers, dynamics, shapers, gens, blends _kernels.hip) reads and writes the
-// channels it owns for a whole block: CPL adjacent channels in one load and one store per frame, and the host's decision whether
-// CPL may be 4.  Device, and one small host part.  hipcc only.
+// lane_io.hip.h -- how a lane of the per-channel banks (strips, talkers, dynamics, shapers, gens, blends, filters _kernels.hip) reads and writes the
+// channels it owns for a whole block: CPL adjacent channels in one load and one store per frame, which channels those are
+// (lane_channel), and the host's decision whether CPL may be 4.  Device, and one small host part.  hipcc only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +50,15 @@ template <int CPL, int R>
 __device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
 #pragma unroll
     for (int i = 0; i < R; ++i) storev<CPL, true>(lane + (size_t)(f0 + i) * rs, v[i]);
+}
+
+// the lane's first channel c in a launch of `wg` lanes per workgroup; false past N: the lane has none (CPL > 1 only with
+// N % 4 == 0, so a lane's channels are all inside or all outside)
+template <int CPL>
+__device__ __forceinline__ bool lane_channel(uint32_t wg, uint32_t N, uint32_t &c) {
+    const uint64_t c64 = ((uint64_t)blockIdx.x * wg + threadIdx.x) * CPL;
+    c = (uint32_t)c64;
+    return c64 < N;
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------

@@ -28,7 +28,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -105,9 +104,8 @@ __device__ __forceinline__ void shape_kinds(uint32_t kinds, float (&v)[R][CPL], 
 template <int CPL, bool HEAVY>
 __global__ __launch_bounds__(SWG) void shapers_run(ShapeArgs a) {
     constexpr int F = 8;                                   // frame rows per chunk (two chunks are in registers)
-    const uint64_t c64 = ((uint64_t)blockIdx.x * SWG + threadIdx.x) * CPL;
-    if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
-    const uint32_t c = (uint32_t)c64;
+    uint32_t c;
+    if (!lane_channel<CPL>(SWG, a.N, c)) return;
     Lane<CPL> s;
     uint8_t code[CPL];
     loadv<CPL>(a.p0 + c, s.p0);
@@ -247,9 +245,6 @@ struct StoreFields {
 typedef StoreQueue<StoreFields> Stores;
 typedef Stores::Store Store;
 
-// the table bytes of a bank on the device: three sliders (12) and the kind code (1) per channel
-uint64_t table_bytes(uint64_t N) { return 13 * N; }
-
 bool heavy(uint8_t k) { return k == C_DIST + DSPFX_DIST_TANH || k == C_DIST + DSPFX_DIST_SIN || k == C_DIST + DSPFX_DIST_ATAN || k == C_OVER || k == C_CHEB; }
 uint32_t code_kind(uint8_t k) { return k == C_NONE ? DSPFX_SHAPERS_NONE : k == C_OVER ? DSPFX_OVERDRIVE : k == C_CHEB ? DSPFX_CHEBYSHEV : DSPFX_DISTORT; }
 uint32_t code_mode(uint8_t k) { return k >= C_DIST && k < C_OVER ? (uint32_t)(k - C_DIST) : DSPFX_SHAPERS_NONE; }
@@ -267,11 +262,15 @@ struct dspfx_shapers : ChannelBank<dspfx_shapers_desc, StoreFields> {        // 
     uint64_t run_heavy = 0;                      // ... and those of a kind that evaluates in f64: which run kernel
     float *p[3] = {nullptr, nullptr, nullptr};
     uint8_t *code = nullptr;
+    // the fresh state: no node anywhere
+    template <class V>
+    static void tables(const dspfx_shapers_desc &d, V v) {
+        for (int t = 0; t < 3; ++t) v(4 * (uint64_t)d.n_channels, 0, &dspfx_shapers::p, t);
+        v(d.n_channels, C_NONE, &dspfx_shapers::code);
+    }
 };
 
 namespace {
-
-void release(dspfx_shapers *p) { release_bank(p, {p->p[0], p->p[1], p->p[2], p->code}); }
 
 // one store onto the stream (the bank's mu is held): the device tables, and the run-order kind table beside them
 hipError_t apply_store(dspfx_shapers *p, const Store &st, hipStream_t s) {
@@ -309,15 +308,8 @@ int store_nodes(dspfx_shapers *p, const char *call, int kind, int n_sliders, con
     dspfx_node_desc def;
     if (dspfx_node_defaults(kind, &def) != DSPFX_OK) return p->fail(DSPFX_ERR_INVALID, "shapers: no such node kind");
     Store st;
-    st.kind = ST_NODES;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, 3 * count + (count + 3) / 4, st)) {
-        char buf[96];
-        std::snprintf(buf, sizeof buf, "shapers %s: no page-locked memory for the staged sliders", call);
-        return p->fail(DSPFX_ERR_OOM, buf);
-    }
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, ST_NODES, call, first, count, 3 * count + (count + 3) / 4, "staged sliders")) return DSPFX_ERR_OOM;
     uint8_t *codes = (uint8_t *)(st.vals + 3 * count);
     for (uint64_t i = 0; i < count; ++i) {
         const uint64_t c = first + i;
@@ -339,50 +331,20 @@ int store_nodes(dspfx_shapers *p, const char *call, int kind, int n_sliders, con
 
 extern "C" const char *dspfx_shapers_last_error(const dspfx_shapers *p) { return p ? p->err.c_str() : g_err.c_str(); }
 
-extern "C" int dspfx_shapers_plan(uint64_t channels, uint64_t *bytes_out) {
-    g_err.clear();
-    const int rc = check_shape("shapers", channels, 0, g_err);
-    if (rc != DSPFX_OK) return rc;
-    if (bytes_out) *bytes_out = table_bytes(channels);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_shapers_plan(uint64_t channels, uint64_t *bytes_out) { return plan_bank<dspfx_shapers>(channels, bytes_out, g_err); }
 
 extern "C" int dspfx_shapers_create(const dspfx_shapers_desc *desc, dspfx_shapers **out) {
     const int rc = create_checks(desc, out, g_err);
     if (rc != DSPFX_OK) return rc;
-    const uint32_t N = desc->n_channels;
-    dspfx_shapers *p = new (std::nothrow) dspfx_shapers;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    try {
+    return create_bank(desc, out, g_err, [](dspfx_shapers *p) {
+        const uint32_t N = p->desc.n_channels;
         for (auto &h : p->hp) h.assign(N, 0.0f);
         p->hcode.assign(N, C_NONE);
         p->rcode.assign(N, C_NONE);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t tab = (size_t)N * sizeof(float);
-    bool ok = hipMalloc((void **)&p->p[0], tab) == hipSuccess && hipMalloc((void **)&p->p[1], tab) == hipSuccess &&
-              hipMalloc((void **)&p->p[2], tab) == hipSuccess && hipMalloc((void **)&p->code, N) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        return no_table_memory("shapers", table_bytes(N), N, g_err);
-    }
-    // the fresh state: no node anywhere
-    ok = hipMemset(p->p[0], 0, tab) == hipSuccess && hipMemset(p->p[1], 0, tab) == hipSuccess && hipMemset(p->p[2], 0, tab) == hipSuccess &&
-         hipMemset(p->code, C_NONE, N) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    });
 }
 
-extern "C" int dspfx_shapers_destroy(dspfx_shapers *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_shapers_destroy(dspfx_shapers *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_shapers_set_distort(dspfx_shapers *p, const float *host_level, const uint32_t *host_mode, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;

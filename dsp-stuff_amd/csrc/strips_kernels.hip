@@ -21,7 +21,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -131,6 +130,7 @@ constexpr int waves_for(int KB, int CPL) { return KB * CPL <= 4 ? 3 : 2; }
 template <int KB, int CPL>
 __global__ __launch_bounds__(WG, waves_for(KB, CPL)) void strips_run(StripArgs a) {
     constexpr int F = rows_for(KB, CPL);
+    // lane_io's lane_channel, written out: with the helper the register allocation of these kernels comes out otherwise
     const uint64_t c64 = ((uint64_t)blockIdx.x * WG + threadIdx.x) * CPL;
     if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
     const uint32_t c = (uint32_t)c64;
@@ -242,11 +242,18 @@ struct dspfx_strips : ChannelBank<dspfx_strips_desc, StoreFields> {        // st
     float *coef = nullptr, *state = nullptr, *level = nullptr;
     uint32_t *mask = nullptr;
     float div = 1.0f;
+    // the fresh state: no node anywhere, every state at rest, every level 1.0
+    template <class V>
+    static void tables(const dspfx_strips_desc &d, V v) {
+        const uint64_t N = d.n_channels, KB = bands_built(d.bands);
+        v(KB * 5 * N * 4, 0, &dspfx_strips::coef);
+        v(KB * 4 * N * 4, 0, &dspfx_strips::state);
+        v(4 * N, 0x3F800000, &dspfx_strips::level);
+        v(4 * N, 0, &dspfx_strips::mask);
+    }
 };
 
 namespace {
-
-void release(dspfx_strips *p) { release_bank(p, {p->coef, p->state, p->level, p->mask}); }
 
 // one store onto the stream: its values, then the node bit (and a band's zeroed state) on its channels
 hipError_t apply_store(dspfx_strips *p, const Store &st, hipStream_t s) {
@@ -326,40 +333,17 @@ extern "C" int dspfx_strips_create(const dspfx_strips_desc *desc, dspfx_strips *
         return DSPFX_OK;
     });
     if (rc != DSPFX_OK) return rc;
-    const uint32_t N = desc->n_channels;
-    dspfx_strips *p = new (std::nothrow) dspfx_strips;
-    if (!p) return DSPFX_ERR_OOM;
-    p->desc = *desc;
-    p->KB = bands_built(desc->bands);
-    p->div = dspfx_link_divisor(1);
-    try {
-        p->hmask.assign(N, 0u);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return DSPFX_ERR_OOM;
-    }
-    const size_t coef_b = (size_t)p->KB * 5 * N * sizeof(float), state_b = (size_t)p->KB * 4 * N * sizeof(float);
-    bool ok = hipMalloc((void **)&p->coef, coef_b) == hipSuccess && hipMalloc((void **)&p->state, state_b) == hipSuccess &&
-              hipMalloc((void **)&p->level, (size_t)N * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&p->mask, (size_t)N * sizeof(uint32_t)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(p);
-        g_err = "strips: no device memory for the coefficients, the state, the levels and the masks";
-        return DSPFX_ERR_OOM;
-    }
-    ok = hipMemset(p->coef, 0, coef_b) == hipSuccess && hipMemset(p->state, 0, state_b) == hipSuccess &&
-         hipMemsetD32((hipDeviceptr_t)p->level, 0x3F800000, N) == hipSuccess && hipMemset(p->mask, 0, (size_t)N * sizeof(uint32_t)) == hipSuccess &&
-         hipDeviceSynchronize() == hipSuccess && hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        release(p);
-        return DSPFX_ERR_HIP;
-    }
-    *out = p;
-    return DSPFX_OK;
+    return create_bank(
+        desc, out, g_err,
+        [](dspfx_strips *p) {
+            p->KB = bands_built(p->desc.bands);
+            p->div = dspfx_link_divisor(1);
+            p->hmask.assign(p->desc.n_channels, 0u);
+        },
+        nullptr, "strips: no device memory for the coefficients, the state, the levels and the masks");
 }
 
-extern "C" int dspfx_strips_destroy(dspfx_strips *p) { return destroy_bank(p, release); }
+extern "C" int dspfx_strips_destroy(dspfx_strips *p) { return destroy_bank(p); }
 
 extern "C" int dspfx_strips_set_gain(dspfx_strips *p, const float *host_levels, uint64_t first_channel, uint64_t count) {
     if (!p) return DSPFX_ERR_INVALID;
@@ -368,12 +352,8 @@ extern "C" int dspfx_strips_set_gain(dspfx_strips *p, const float *host_levels, 
     if (count == 0) return DSPFX_OK;
     Store st;
     st.node = 0;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
-    if (host_levels) {
-        if (!p->stores.staging(p->desc.device, count, st)) return p->fail(DSPFX_ERR_OOM, "strips set_gain: no page-locked memory for the staged levels");
-        std::memcpy(st.vals, host_levels, count * sizeof(float));
-    }
+    if (!stage_store(p, st, nullptr, "set_gain", first_channel, count, host_levels ? count : 0, "staged levels")) return DSPFX_ERR_OOM;
+    if (host_levels) std::memcpy(st.vals, host_levels, count * sizeof(float));
     enqueue(p, st);
     return DSPFX_OK;
 }
@@ -390,10 +370,8 @@ extern "C" int dspfx_strips_set_band(dspfx_strips *p, uint32_t band, const float
     if (count == 0) return DSPFX_OK;
     Store st;
     st.node = 1 + (int)band;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
+    if (!stage_store(p, st, nullptr, "set_band", first_channel, count, host_raw6 ? 5 * count : 0, "staged coefficients")) return DSPFX_ERR_OOM;
     if (host_raw6) {
-        if (!p->stores.staging(p->desc.device, 5 * count, st)) return p->fail(DSPFX_ERR_OOM, "strips set_band: no page-locked memory for the staged coefficients");
         for (uint64_t i = 0; i < count; ++i) {           // regenerate_filter per channel, transposed to [5][count]
             float k5[5];
             (void)dspfx_strips_coeffs(host_raw6 + 6 * i, k5);

@@ -85,9 +85,8 @@ __device__ __forceinline__ void talk_rows(float (&v)[R][CPL], Chan<CPL> &s, uint
 
 template <int CPL, bool GATED>
 __global__ __launch_bounds__(WG) void talkers_run(TalkArgs a) {
-    const uint64_t c64 = ((uint64_t)blockIdx.x * WG + threadIdx.x) * CPL;
-    if (c64 >= a.N) return;                                // (CPL > 1 only with N % 4 == 0: a lane's channels are all inside)
-    const uint32_t c = (uint32_t)c64;
+    uint32_t c;
+    if (!lane_channel<CPL>(WG, a.N, c)) return;
     Chan<CPL> s;
     uint8_t pin[CPL];
     float tgt[CPL];
@@ -274,7 +273,9 @@ int room_too_large(const char *call, uint64_t room, uint64_t n, std::string &err
 }
 
 // the table bytes of a bank on the device: env, gate, target, level and the two gains (24), the pin (1) and the member list (4)
-// per channel; room_start (4), top (1) and the two tables of 8 (64) per room, and room_start's last entry
+// per channel; room_start (4), top (1) and the two tables of 8 (64) per room, and room_start's last entry.  By hand, as create's
+// allocation and clearing are, not a channel_bank table list: the room tables go by G, the first seating is copied from host
+// tables that create builds in between, and the audible list joins the bank later
 uint64_t table_bytes(uint64_t N, uint64_t G) { return 29 * N + 69 * G + 4; }
 
 // the seating of room_of[N] (every id below G, or NONE): members sorted by (room, channel) and room_start[G + 1].
@@ -547,11 +548,8 @@ extern "C" int dspfx_talkers_set_detector(dspfx_talkers *p, const float *host_at
     if (rc != DSPFX_OK) return rc;
     if (count == 0 || (!host_attack && !host_release)) return DSPFX_OK;
     Store st;
-    st.kind = ST_DETECTOR;
-    st.first = (uint32_t)first_channel;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, 2 * count, st)) return p->fail(DSPFX_ERR_OOM, "talkers set_detector: no page-locked memory for the staged sliders");
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, ST_DETECTOR, "set_detector", first_channel, count, 2 * count, "staged sliders")) return DSPFX_ERR_OOM;
     float *a = st.vals, *r = st.vals + count;
     for (uint64_t i = 0; i < count; ++i) {
         a[i] = host_attack ? dspfx_envelope_gain(host_attack[i]) : p->hga[first_channel + i];
@@ -569,14 +567,8 @@ namespace {
 // count bytes for pin[first ..] or top[first ..]
 int store_bytes(dspfx_talkers *p, StoreKind kind, const char *call, const uint8_t *host, uint64_t first, uint64_t count) {
     Store st;
-    st.kind = kind;
-    st.first = (uint32_t)first;
-    st.count = (uint32_t)count;
-    std::lock_guard<std::mutex> one(p->smu);
-    if (!p->stores.staging(p->desc.device, bytes_as_floats(count), st)) {
-        const std::string why = std::string("talkers ") + call + ": no page-locked memory for the staged values";
-        return p->fail(DSPFX_ERR_OOM, why.c_str());
-    }
+    std::unique_lock<std::mutex> one;
+    if (!stage_store(p, st, &one, kind, call, first, count, bytes_as_floats(count), "staged values")) return DSPFX_ERR_OOM;
     std::memcpy(st.vals, host, count);
     p->stores.push(st);
     return DSPFX_OK;
@@ -659,9 +651,8 @@ extern "C" int dspfx_talkers_assign(dspfx_talkers *p, const uint32_t *host_room_
             return p->fail(DSPFX_ERR_INVALID, why.c_str());
         }
     }
-    Store st;
-    st.kind = ST_SEATS;
-    if (!p->stores.staging(p->desc.device, (size_t)N + G + 1, st)) return p->fail(DSPFX_ERR_OOM, "talkers assign: no page-locked memory for the seating's tables");
+    Store st;                                    // (smu is held; count: the members listed, below)
+    if (!stage_store(p, st, nullptr, ST_SEATS, "assign", 0, 0, (size_t)N + G + 1, "seating's tables")) return DSPFX_ERR_OOM;
     const uint32_t *old = p->room_of.data();
     st.count = build_seating([&](uint64_t c) { return c >= first_channel && c - first_channel < count ? host_room_ids[c - first_channel] : old[c]; }, N, G,
                              (uint32_t *)st.vals, (uint32_t *)st.vals + N);
