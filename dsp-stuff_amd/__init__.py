@@ -63,6 +63,8 @@ SHAPERS_NONE = 0xFFFFFFFF       # DSPFX_SHAPERS_NONE: ChannelShapers.kinds() wit
 GENS_NONE = 0xFFFFFFFF          # DSPFX_GENS_NONE: ChannelGenerators.modes() without a node
 BLENDS_NONE = 0xFFFFFFFF        # DSPFX_BLENDS_NONE: ChannelBlends.kinds() without a node
 FILTERS_NONE = 0xFFFFFFFF       # DSPFX_FILTERS_NONE: ChannelFilters.kinds() of an empty slot; reset(stage=None), every stage
+FIRS_NONE = 0xFFFFFFFF          # DSPFX_FIRS_NONE: ChannelFirs.modes() without a node; set_taps(mode=None), keep the node's mode
+FIRS_MAX_TAPS = 1024            # DSPFX_FIRS_MAX_TAPS: the longest response a ChannelFirs channel may carry
 BLENDS_NO_BUS = 0xFFFFFFFF      # DSPFX_BLENDS_NO_BUS: ChannelBlends.assign, the channel reads no bus (the same value as NO_ROOM)
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
@@ -118,6 +120,9 @@ EXPORTS = [
     "dspfx_filters_plan", "dspfx_filters_create", "dspfx_filters_destroy", "dspfx_filters_last_error", "dspfx_filters_run",
     "dspfx_filters_set_low_pass", "dspfx_filters_set_high_pass", "dspfx_filters_set_envelope", "dspfx_filters_drop",
     "dspfx_filters_reset", "dspfx_filters_present", "dspfx_filters_kinds", "dspfx_filters_sliders", "dspfx_filters_state",
+    "dspfx_firs_plan", "dspfx_firs_create", "dspfx_firs_destroy", "dspfx_firs_last_error", "dspfx_firs_run", "dspfx_firs_set_taps",
+    "dspfx_firs_set_mode", "dspfx_firs_drop", "dspfx_firs_reset", "dspfx_firs_present", "dspfx_firs_lengths", "dspfx_firs_modes",
+    "dspfx_firs_taps", "dspfx_firs_deque",
 ]
 COMM_ID_BYTES = 128
 
@@ -224,6 +229,11 @@ class _BlendsDesc(C.Structure):
 class _FiltersDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("stages", C.c_uint32)]
+
+
+class _FirsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("max_taps", C.c_uint32), ("general_only", C.c_uint32)]
 
 
 class _Ctl(C.Structure):
@@ -513,6 +523,20 @@ def lib():
     L.dspfx_filters_kinds.argtypes = [vp, C.c_uint32, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_filters_sliders.argtypes = [vp, C.c_uint32, fp, C.c_uint64, C.c_uint64]
     L.dspfx_filters_state.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.dspfx_firs_plan.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.dspfx_firs_create.argtypes = [C.POINTER(_FirsDesc), C.POINTER(vp)]
+    L.dspfx_firs_destroy.argtypes = [vp]
+    L.dspfx_firs_last_error.restype = C.c_char_p
+    L.dspfx_firs_last_error.argtypes = [vp]
+    L.dspfx_firs_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_firs_set_taps.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]
+    L.dspfx_firs_set_mode.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64]
+    for name in ("drop", "reset"):
+        getattr(L, f"dspfx_firs_{name}").argtypes = [vp, C.c_uint64, C.c_uint64]
+    for name in ("present", "lengths", "modes"):
+        getattr(L, f"dspfx_firs_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_firs_taps.argtypes = [vp, C.c_uint64, C.POINTER(C.c_double), u32p]
+    L.dspfx_firs_deque.argtypes = [vp, C.POINTER(vp)]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2454,6 +2478,99 @@ class ChannelFilters(_ChannelBank):
         p = C.c_void_p()
         self._chk(self.L.dspfx_filters_state(self.h, int(stage) & 0xFFFFFFFF, C.byref(p)))
         return self._view(p.value, (self.channels,))
+
+
+def firs_plan(channels: int, max_taps: int = 64) -> int:
+    """dspfx_firs_plan, a pure host function (no GPU): the device bytes of a ChannelFirs bank's tables,
+    channels * (12 * max_taps + 80): max_taps f64 taps, a ring of max_taps + 16 f32 samples, the node word and the three deque
+    words per channel."""
+    return _plan_bytes("firs", channels, max_taps)
+
+
+class ChannelFirs(_ChannelBank):
+    """Per-channel FIR nodes (include/dspfx.h, dspfx_firs_*): channel c may carry one FIR node of its own -- its own taps (f64),
+    tap count T (1 .. max_taps), mode (FIR_BALANCED, FIR_AVERAGE) and deque of past samples -- over a device block in the layout
+    of `tile_channels` (as Engine's).  A node exists from the first `set_taps` that names the channel until `drop`; a fresh bank
+    copies its input.  A channel's output is bit for bit what the reference's FIR node gives through all its history (the fill
+    phase of its VecDeque and the a / b split of the two sums included), however the frames are cut into runs.  `set_taps` on a
+    channel that carries a node is the reference's reload: new taps, the deque is kept.  `general_only` makes every wave take the
+    frames one at a time (for timing one body of the kernel against the other).  Asynchronous on `stream`."""
+
+    _C = "firs"
+    _DESC = _FirsDesc
+
+    def __init__(self, channels: int, max_taps: int = 64, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0,
+                 general_only: bool = False):
+        self.max_taps = int(max_taps)
+        super().__init__(channels, tile_channels, max_frames, device, self.max_taps & 0xFFFFFFFF, int(bool(general_only)))
+        p = C.c_void_p()
+        self._chk(self.L.dspfx_firs_deque(self.h, C.byref(p)))
+        self._deque = p.value
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every channel's node -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        n_frames = self._frames(block, n_frames)
+        if out is None:
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_firs_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
+        return out
+
+    def set_taps(self, impulse_response, first_channel: int = 0, count: Optional[int] = None, mode: Optional[int] = None):
+        """Give channels from first_channel a response, in time order as Fir takes it: a 1-d array [T] for `count` channels
+        (default: all from first_channel), or a 2-d array [n][T], one response per channel for n channels (`count`, when given,
+        must be n).  mode: FIR_BALANCED or FIR_AVERAGE; None keeps the mode of a channel that carries a node and is FIR_BALANCED
+        for a new one.  A channel without a node gets a new one (an empty deque); one that carries a node keeps its deque.  T of 0
+        or above max_taps, a range past the channels, an unknown mode or an array of another shape refuses the whole store.  Any
+        thread; applies to the runs submitted after it."""
+        h = np.ascontiguousarray(impulse_response, dtype=np.float64)
+        if h.ndim == 1:
+            rows, n = 0, self._n(first_channel, count)
+        elif h.ndim == 2 and (count is None or int(count) == h.shape[0]):
+            rows, n = 1, h.shape[0]
+        else:
+            raise DspfxError(-1, "firs set_taps: the response is [T], or [count][T] with one row per channel")
+        m = FIRS_NONE if mode is None else int(mode) & 0xFFFFFFFF
+        self._chk(self.L.dspfx_firs_set_taps(self.h, h.ctypes.data_as(C.POINTER(C.c_double)), h.shape[-1] & 0xFFFFFFFF, rows, m,
+                                             int(first_channel), n))
+
+    def set_mode(self, mode: int, first_channel: int = 0, count: Optional[int] = None):
+        """The mode (FIR_BALANCED, FIR_AVERAGE) of the nodes of `count` channels from first_channel (default: all from it); a
+        channel without a node stays without one; queued like a store."""
+        self._chk(self.L.dspfx_firs_set_mode(self.h, int(mode) & 0xFFFFFFFF, int(first_channel), self._n(first_channel, count)))
+
+    def drop(self, first_channel: int = 0, count: Optional[int] = None):
+        """Remove the node of `count` channels from first_channel (default: all from it): a copy again, and a later `set_taps`
+        makes a new node; queued like a store."""
+        self._span("drop", first_channel, count)
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None):
+        """Empty the deque of `count` channels from first_channel (default: all from it); taps and mode stay; queued like a store."""
+        self._span("reset", first_channel, count)
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
+        return self._table("present", first_channel, count)
+
+    def lengths(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the node's tap count T, 0 without a node."""
+        return self._table("lengths", first_channel, count)
+
+    def modes(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: FIR_BALANCED, FIR_AVERAGE, or FIRS_NONE without a node."""
+        return self._table("modes", first_channel, count)
+
+    def taps(self, channel: int) -> np.ndarray:
+        """float64[T]: the response of one channel as it was given (time order); empty without a node."""
+        v = np.zeros(max(self.max_taps, 1), np.float64)
+        n = C.c_uint32()
+        self._chk(self.L.dspfx_firs_taps(self.h, int(channel), v.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return v[:n.value].copy()
+
+    def deque(self):
+        """int32[3, channels] on the device: len, cap and head of every channel's VecDeque after the last run (valid after a run,
+        on its stream)."""
+        return self._view(self._deque, (3, self.channels), "<i4")
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

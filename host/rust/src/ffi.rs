@@ -304,6 +304,30 @@ pub struct dspfx_filters_desc {
 /// `dspfx_filters_kinds`: the slot is empty; `dspfx_filters_reset`: every stage.
 pub const DSPFX_FILTERS_NONE: u32 = 0xFFFF_FFFF;
 
+/// Opaque channel-FIR bank handle (`typedef struct dspfx_firs dspfx_firs`).
+#[repr(C)]
+pub struct dspfx_firs {
+    _private: [u8; 0],
+}
+
+/// The channel-FIR bank's descriptor (`dspfx_firs_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_firs_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub max_taps: u32,
+    pub general_only: u32,
+}
+
+/// The longest response a channel of a channel-FIR bank may carry.
+pub const DSPFX_FIRS_MAX_TAPS: u32 = 1024;
+/// `dspfx_firs_modes`: the channel carries no node; `dspfx_firs_set_taps`: keep the node's mode.
+pub const DSPFX_FIRS_NONE: u32 = 0xFFFF_FFFF;
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -691,6 +715,20 @@ extern "C" {
     pub fn dspfx_filters_kinds(f: *mut dspfx_filters, stage: u32, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_filters_sliders(f: *mut dspfx_filters, stage: u32, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_filters_state(f: *mut dspfx_filters, stage: u32, state_out: *mut *const f32) -> c_int;
+    pub fn dspfx_firs_plan(channels: u64, max_taps: u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_firs_create(desc: *const dspfx_firs_desc, out: *mut *mut dspfx_firs) -> c_int;
+    pub fn dspfx_firs_destroy(f: *mut dspfx_firs) -> c_int;
+    pub fn dspfx_firs_last_error(f: *const dspfx_firs) -> *const c_char;
+    pub fn dspfx_firs_run(f: *mut dspfx_firs, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_firs_set_taps(f: *mut dspfx_firs, host_taps: *const f64, n_taps: u32, per_channel: u32, mode: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_set_mode(f: *mut dspfx_firs, mode: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_drop(f: *mut dspfx_firs, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_reset(f: *mut dspfx_firs, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_present(f: *mut dspfx_firs, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_lengths(f: *mut dspfx_firs, host_lengths_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_modes(f: *mut dspfx_firs, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_firs_taps(f: *mut dspfx_firs, channel: u64, host_taps_out: *mut f64, n_taps_out: *mut u32) -> c_int;
+    pub fn dspfx_firs_deque(f: *mut dspfx_firs, deque_out: *mut *const i32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

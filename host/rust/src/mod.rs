@@ -14,4 +14,5 @@ pub mod channel_shapers;
 pub mod channel_generators;
 pub mod channel_blends;
 pub mod channel_filters;
+pub mod channel_firs;
 pub mod mix_matrix;

@@ -1583,6 +1583,95 @@ int dspfx_filters_sliders(dspfx_filters *f, uint32_t stage, float *host_sliders_
  * never changes; what it holds is valid after a run, on its stream. */
 int dspfx_filters_state(dspfx_filters *f, uint32_t stage, const float **state_out);
 
+/* ---- channel FIRs: a bank of per-channel FIR nodes, each with its own taps --------------------------------------------
+ * An engine runs one FIR node (nodes/fir.rs) with one tap table for all N channels, and the Convolver bank shares at most 256
+ * long responses.  This bank gives channel c ONE FIR node of its own: its own taps (f64), tap count T (1 .. max_taps), mode and
+ * VecDeque of past samples, over N channels in the desc's layout (tile_channels as dspfx_engine_desc).  A linear-phase EQ, a
+ * fractional delay for time alignment, a short cabinet or handset model, the taps of an adaptive echo canceller: short filters
+ * that are different numbers on every channel.
+ * A node EXISTS for a channel from the first dspfx_firs_set_taps that names it until dspfx_firs_drop; a fresh bank has no node
+ * anywhere: run copies in to out bit for bit.
+ * PER CHANNEL, per sample, what fir.rs:179-225 does: push; pop ONE sample when the deque is longer than T; then
+ *       a = (float) sum_{k < min(n_a, T)} state[k] * taps[k]                              sequential f64, nothing fused
+ *       b = (float) sum_{k < min(len - n_a, T - n_a)} state[n_a + k] * taps[n_a + k]     (+0.0 when n_a >= T)
+ *       out = (a + b) * divisor               divisor 1.0f (DSPFX_FIR_BALANCED) or 1.0f / (float)T (DSPFX_FIR_AVERAGE)
+ * with taps the response REVERSED (fir.rs:163,168) and n_a the length of the first physical slice of the reference's VecDeque
+ * (capacity 0, then 4, then doubling).  NaN, infinities and signed zeros go through the arithmetic as they are.  So out[f][c] is
+ * bit for bit what the reference's node gives through all its history, in either layout, in place or not, on any stream,
+ * whatever the channel's neighbours carry and however the frames are cut into runs.
+ * STORES.  dspfx_firs_set_taps on a channel without a node makes a NEW node: an empty deque, mode DSPFX_FIR_BALANCED unless the
+ * call names one.  On a channel that carries a node it is the reference's reload (fir.rs:153-171): the taps are replaced, the
+ * deque and (with mode DSPFX_FIRS_NONE) the mode are kept -- a deque longer than a shorter new response stays longer, a pure extra
+ * delay.  dspfx_firs_drop removes the node, so the next set_taps makes a new one; dspfx_firs_reset empties the deque and keeps
+ * taps and mode.  n_taps of 0 or above max_taps, a range past the channels, an unknown mode or no array refuses the WHOLE store:
+ * DSPFX_ERR_INVALID, the reason in dspfx_firs_last_error, nothing stored.
+ * ON THE DEVICE, per channel: the taps table, max_taps doubles laid out [tap][N] so the lanes of a wave (a lane is a channel)
+ * read one tap of 64 channels in one access; a ring of max_taps + 16 float samples in time, [row][N]; one word of T and mode; the
+ * three deque words len, cap, head, which the kernel steps itself per frame.  dspfx_firs_plan:
+ *       bytes = channels * (8 * max_taps + 4 * (max_taps + 16) + 4 + 12) = channels * (12 * max_taps + 80)
+ * Only the node words and the deque words are cleared at create.  On the host: 31 bytes per channel and one copy of every
+ * response a channel still carries.
+ * ONE RUN is one kernel behind the queued stores, one lane per channel.  A wave whose present lanes all stand at len == T < cap
+ * with the same T takes the next sixteen frames at once: the taps are read once per sixteen frames, the samples slide through a
+ * register window, and every frame keeps one running f64 sum that is rounded and restarted at +0.0 where its first slice ends.
+ * Otherwise the wave takes one frame with the two sums as written above (the fill phase, a deque longer than its taps, lanes of
+ * different T) and decides again, so a new node leaves that slower body at most sixteen frames after its deque is full.  A wave
+ * without a node copies.  No atomics, no LDS.
+ * Not here: link hops, control ports and graph wiring, which stay with the engine; T above DSPFX_FIRS_MAX_TAPS, the Convolver's. */
+#define DSPFX_FIRS_MAX_TAPS 1024u
+/* dspfx_firs_modes: the channel carries no node; dspfx_firs_set_taps: keep the node's mode (a new node: DSPFX_FIR_BALANCED) */
+#define DSPFX_FIRS_NONE 0xFFFFFFFFu
+typedef struct dspfx_firs dspfx_firs;
+typedef struct dspfx_firs_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t max_taps;        /* the longest response a channel may carry, 1 .. DSPFX_FIRS_MAX_TAPS */
+    uint32_t general_only;    /* 0; 1: every wave takes the frames one at a time (for timing one body against the other) */
+} dspfx_firs_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, channels * (12 * max_taps + 80).
+ * channels of 0 or above 2^32 - 256, max_taps outside 1 .. 1024: DSPFX_ERR_INVALID, the reason in dspfx_firs_last_error(NULL). */
+int dspfx_firs_plan(uint64_t channels, uint32_t max_taps, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0, max_taps outside 1 .. 1024) is DSPFX_ERR_INVALID with the reason in dspfx_firs_last_error of a NULL bank (kept
+ * per thread); all of that is checked before any device work. */
+int dspfx_firs_create(const dspfx_firs_desc *desc, dspfx_firs **out);
+int dspfx_firs_destroy(dspfx_firs *f);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_firs_last_error(const dspfx_firs *f);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out == in works in place (a
+ * thread rewrites the elements it read); any other overlap is the caller's error.  Asynchronous on `stream`; a run on another
+ * stream than the one before first waits (on the device) for that one, since the state is the bank's (the rules of
+ * dspfx_strips_run).  Queued stores go onto the stream ahead of the kernel, in the order they were made. */
+int dspfx_firs_run(dspfx_firs *f, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Gives channels [first_channel, first_channel + count) a response of n_taps taps in TIME order (h[0] meets the newest sample; the
+ * bank reverses them): per_channel 0: host_taps is [n_taps], one response for the range; 1: [count][n_taps], a response per
+ * channel.  mode: DSPFX_FIR_BALANCED, DSPFX_FIR_AVERAGE, or DSPFX_FIRS_NONE to keep the node's.  The contract of dspfx_dynamics_set:
+ * callable from any thread while runs are in flight, never waits for the device or for a run; the values are staged in page-locked
+ * memory and queued, each store is whole, and a run submitted after the call returns sees it, the runs submitted before it do not. */
+int dspfx_firs_set_taps(dspfx_firs *f, const double *host_taps, uint32_t n_taps, uint32_t per_channel, uint32_t mode, uint64_t first_channel,
+                        uint64_t count);
+/* The mode of the nodes on the range (a channel without a node stays without one).  Queued like a store. */
+int dspfx_firs_set_mode(dspfx_firs *f, uint32_t mode, uint64_t first_channel, uint64_t count);
+/* Removes the node of the channels of the range: a copy again, and a later set_taps makes a new node.  Queued like a store. */
+int dspfx_firs_drop(dspfx_firs *f, uint64_t first_channel, uint64_t count);
+/* Empties the deque of the channels of the range (what dspfx_reset does for the engine's FIR node); taps and mode stay.  Queued
+ * like a store. */
+int dspfx_firs_reset(dspfx_firs *f, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: present 1 / 0; lengths T, 0
+ * without a node; modes DSPFX_FIR_BALANCED, DSPFX_FIR_AVERAGE, or DSPFX_FIRS_NONE without a node. */
+int dspfx_firs_present(dspfx_firs *f, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_firs_lengths(dspfx_firs *f, uint32_t *host_lengths_out, uint64_t first_channel, uint64_t count);
+int dspfx_firs_modes(dspfx_firs *f, uint32_t *host_modes_out, uint64_t first_channel, uint64_t count);
+/* The response of ONE channel as it was given (time order): *n_taps_out = T (0 without a node), host_taps_out[0 .. T); the array
+ * has room for max_taps doubles. */
+int dspfx_firs_taps(dspfx_firs *f, uint64_t channel, double *host_taps_out, uint32_t *n_taps_out);
+/* The device pointer of the deque words, int32 [3][N]: len, cap, head of every channel's VecDeque after the last run (0, 0, 0
+ * without a node or before the first sample).  The pointer never changes; what it holds is valid after a run, on its stream. */
+int dspfx_firs_deque(dspfx_firs *f, const int32_t **deque_out);
+
 /* ---- channel generators: a bank of per-channel Signal Generators -------------------------------------------------------
  * An engine runs one Signal Generator (nodes/signal_gen.rs) with one amplitude, frequency and mode for all N channels.  This bank
  * gives channel c ONE generator of its own, with its own sliders, mode and clock, over N channels in the desc's layout

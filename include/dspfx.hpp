@@ -922,6 +922,87 @@ inline std::uint64_t filters_plan(std::uint64_t channels, std::uint32_t stages) 
     return bytes;
 }
 
+// Per-channel FIR nodes (include/dspfx.h, dspfx_firs_*): channel c may carry one FIR node of its own -- its own taps (f64), tap
+// count T (1 .. max_taps), mode and deque of past samples -- over a device block in the layout of tile_channels; its output is bit
+// for bit what the reference's node gives through all its history.  A node exists from the first set_taps() that names the channel
+// until drop(); set_taps() on a channel that carries a node is the reference's reload: new taps, the deque is kept.  A fresh bank
+// copies its input.
+class ChannelFirs {
+  public:
+    ChannelFirs(std::uint32_t channels, std::uint32_t max_taps = 64, std::uint32_t tile_channels = 0, std::uint32_t max_frames = DSPFX_BUF_SIZE,
+                int device = 0, bool general_only = false) : max_taps_(max_taps) {
+        const dspfx_firs_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, max_taps, general_only ? 1u : 0u};
+        const int rc = dspfx_firs_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_firs_last_error(nullptr) ? dspfx_firs_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelFirs() { dspfx_firs_destroy(p_); }
+    ChannelFirs(const ChannelFirs &) = delete;
+    ChannelFirs &operator=(const ChannelFirs &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_firs_run(p_, in, out, n_frames, stream)); }
+    // one response (time order) for channels [first_channel, first_channel + count); mode DSPFX_FIR_BALANCED, DSPFX_FIR_AVERAGE, or
+    // DSPFX_FIRS_NONE to keep the node's.  Any thread; never waits
+    void set_taps(const std::vector<double> &response, std::uint64_t first_channel, std::uint64_t count, std::uint32_t mode = DSPFX_FIRS_NONE) {
+        chk(dspfx_firs_set_taps(p_, response.data(), (std::uint32_t)response.size(), 0, mode, first_channel, count));
+    }
+    // a response per channel: host_rows is [count][n_taps]
+    void set_taps_rows(const double *host_rows, std::uint32_t n_taps, std::uint64_t first_channel, std::uint64_t count,
+                       std::uint32_t mode = DSPFX_FIRS_NONE) {
+        chk(dspfx_firs_set_taps(p_, host_rows, n_taps, 1, mode, first_channel, count));
+    }
+    void set_mode(std::uint32_t mode, std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_firs_set_mode(p_, mode, first_channel, count)); }
+    // the node removed: a copy again, a later set_taps() makes a new node; queued like a store
+    void drop(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_firs_drop(p_, first_channel, count)); }
+    // the deque emptied; taps and mode stay; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_firs_reset(p_, first_channel, count)); }
+    // the host tables, as all stores so far left them: 1 / 0; T (0 without a node); the mode or DSPFX_FIRS_NONE
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_firs_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> lengths(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_firs_lengths(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> modes(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_firs_modes(p_, m.data(), first_channel, count));
+        return m;
+    }
+    // the response of one channel as it was given (time order); empty without a node
+    std::vector<double> taps(std::uint64_t channel) {
+        std::vector<double> v(max_taps_ ? max_taps_ : 1);
+        std::uint32_t n = 0;
+        chk(dspfx_firs_taps(p_, channel, v.data(), &n));
+        v.resize(n);
+        return v;
+    }
+    // int32 [3][channels] on the device: len, cap, head of every channel's deque after the last run, on its stream
+    const std::int32_t *deque() {
+        const std::int32_t *d = nullptr;
+        chk(dspfx_firs_deque(p_, &d));
+        return d;
+    }
+    dspfx_firs *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_firs_last_error(p_) ? dspfx_firs_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_firs *p_ = nullptr;
+    std::uint32_t max_taps_;
+};
+
+// The device bytes of a ChannelFirs bank's tables (dspfx_firs_plan: a pure host function, no GPU).
+inline std::uint64_t firs_plan(std::uint64_t channels, std::uint32_t max_taps) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_firs_plan(channels, max_taps, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_firs_last_error(nullptr));
+    return bytes;
+}
+
 // Per-channel Signal Generators (include/dspfx.h, dspfx_gens_*), a source that lives on the device: channel c may carry one
 // generator of its own -- amplitude, frequency, mode (DSPFX_SIG_*) and clock -- over device blocks in the layout of tile_channels; its
 // sample is bit for bit what an engine whose chain is that one Signal Generator writes for it over the same block lengths.  A node
