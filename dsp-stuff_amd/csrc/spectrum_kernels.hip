@@ -10,7 +10,10 @@
 // A channel's n real samples are ONE complex signal of m = n/2 points, z[j] = x[2j] + i x[2j + 1] (the real-input FFT):
 // Z = FFT_m(z); with Zc = conj Z[(m - k) mod m] and w = exp(-2 pi i k / n),
 //       X[k] = ((Z[k] + Zc) - i w (Z[k] - Zc)) / 2          k in [0, n/2)
-// Every channel is transformed on its own: its rounding error is relative to its own level.  (Packing two CHANNELS into one
+// Every channel is transformed on its own: its rounding error is relative to its own level, for every finite window whose
+// peak window product is a normal float and whose 2 n max|x| is below FLT_MAX (the sums of the transform stay finite, and
+// bin_norm takes the magnitude without squaring out of range); a window with a NaN, or an infinity under a window entry of
+// 0, gives a column of NaN, any other infinity a column of NaN and +inf.  (Packing two CHANNELS into one
 // complex FFT costs the same, but each channel then carries the other's rounding error, which fails a quiet channel beside
 // a loud one.)  The Q transforms are done in place in ONE LDS buffer A[point][q]: fft_core.hip.h.
 //   n       128   256   512  1024  2048  4096  8192
@@ -49,12 +52,22 @@ struct ColArgs {
 };
 
 // |((z + conj zm) - i w (z - conj zm)) / 2|.  Not convolve_kernels.hip's bin_of: there the 0.5 is applied per component, here
-// once after the square root, and the two round differently
+// once after the square root, and the two round differently.
+// re, im hold 2 X[k].  Their squares leave f32's range long before the magnitude does (from 2^64 up and 2^-63 down), so both
+// are first scaled by ONE exact power of two, 2^-E with 2^(E-1) <= max(|re|, |im|) < 2^E (the hardware's frexp exponent, which
+// counts a subnormal's leading zeros too; ldexpf is exact here): the larger square lies in [1/4, 1), the smaller one can only
+// vanish below half an ulp of it, and the root is scaled back by 2^(E-1), the 0.5 folded in -- exact unless the magnitude
+// itself overflows (+inf) or is subnormal (rounded once).  Wherever the plain form 0.5f * sqrtf(re * re + im * im) rounds no
+// subnormal square the two give the same bits.  Zero arguments give +0.0 (E = 0, nothing divides); an infinity gives +inf
+// or, with a NaN beside it, NaN, whatever E is; fmaxf returns the other argument when one is a NaN, and the NaN then enters
+// through its own square
 __device__ __forceinline__ float bin_norm(float2 z, float2 zm, float2 w) {
     const float ar = z.x + zm.x, ai = z.y - zm.y;
     const float2 t = cmul(w, make_float2(z.x - zm.x, z.y + zm.y));
     const float re = ar + t.y, im = ai - t.x;
-    return 0.5f * sqrtf(re * re + im * im);
+    const int ex = __builtin_amdgcn_frexp_expf(fmaxf(fabsf(re), fabsf(im)));
+    const float sr = ldexpf(re, -ex), si = ldexpf(im, -ex);
+    return ldexpf(sqrtf(sr * sr + si * si), ex - 1);
 }
 
 template <int LOGN, int Q>

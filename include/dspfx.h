@@ -758,9 +758,22 @@ int dspfx_resample_plan(uint32_t target_hz, double *value, uint32_t *idx, uint32
  * |FFT(window * x)[k]|, k in [0, n/2); everything else is a factor or a label that depends on the bin index alone.  So the
  * GPU computes
  *       vol[k] = |FFT(window * x)[k]| * gain[k]        k in [0, n/2)
- * in f32 (window product rounded once, magnitude sqrtf(re * re + im * im), then the gain product), and window[n] and
+ * in f32 (window product rounded once; magnitude sqrtf(re * re + im * im) of the two components scaled by one exact power of
+ * two, so that the squares stay inside f32's range; then the gain product), and window[n] and
  * gain[n/2] are TABLES THE HOST SUPPLIES: what is not pinned is confined to them, and a maintainer who has the crates can
- * replace them without a new kernel.  The defaults:
+ * replace them without a new kernel.
+ * Independence: a channel's column depends on its own window alone, whatever any other channel carries -- non-finite
+ * samples, or a level 2^200 away from its own.  (Every channel has a transform of its own.)
+ * Level: the column is the restatement's (within the f32 accuracy the tests state, relative to the channel's own level) for
+ * every finite window whose peak window product max |window[i] * x[i]| is a normal float, >= 2^-126, and whose samples keep
+ * 2 n max |x| below FLT_MAX, so that no sum of the transform overflows; at ordinary levels the scale changes no bit.
+ * Outside that range: a window product that is NaN -- a NaN sample, or an infinity under a window entry of 0, as the default
+ * window's first and last -- makes every bin of the column NaN; any other infinity makes every bin NaN or +inf; no bin is
+ * ever negative or -inf; a finite window above the range gives +inf or NaN in some bins; a window whose products are all
+ * subnormal is transformed as it is, nothing flushed (a constant k * 2^-149 under a window of ones gives n k 2^-149 in
+ * bin 0 exactly), but its accuracy relative to its own level is not stated; an all-zero window, of either sign, gives +0.0
+ * in every bin.
+ * The defaults:
  *   window = NULL   the symmetric Hann window 0.5 - 0.5 cos(2 pi i / (n - 1)), f64 rounded once to f32 (apodize's
  *                   hanning_iter as recalled); entries n - 1 - i repeat entries i < n/2, so it is symmetric bit for bit
  *   gain = NULL     1.0 for every bin.  audioviz's VolumeNormalisation::Mixture curve is not restated here: a caller

@@ -53,8 +53,10 @@ def got_bytes(torch, out):
 class Pair:
     """a bank and its restatement, fed alike"""
 
-    def __init__(self, dspfx, torch, n, hz, tile=0, fmt=F32, ch=1, slots=4):
+    def __init__(self, dspfx, torch, n, hz, tile=0, fmt=F32, ch=1, slots=4, compare=None):
+        """compare(pair, got bytes, want [n_out][N] f32), when given, takes the place of the byte comparison in pull"""
         self.dspfx, self.torch, self.n, self.tile, self.fmt, self.ch = dspfx, torch, n, tile, fmt, ch
+        self.compare = compare
         self.bank = dspfx.Resampler(n, hz, tile_channels=tile, slots=slots, out_format=fmt, out_channels=ch)
         self.ref = R.Resampler(n, hz)
         self.fifo = np.zeros((0, n), np.float32)
@@ -85,7 +87,9 @@ class Pair:
         got = got_bytes(self.torch, out)
         exp = expected_bytes(self.dspfx, want, self.tile, self.fmt, self.ch)
         assert got.shape == exp.shape
-        if not np.array_equal(got, exp):
+        if self.compare is not None:
+            self.compare(self, got, want)
+        elif not np.array_equal(got, exp):
             bad = np.nonzero(got != exp)[0]
             raise AssertionError(f"pull {self.pulls} (n_out {n_out}): {len(bad)} bytes differ, first at {bad[0]}")
         self.pulls += 1
