@@ -63,6 +63,8 @@ SHAPERS_NONE = 0xFFFFFFFF       # DSPFX_SHAPERS_NONE: ChannelShapers.kinds() wit
 GENS_NONE = 0xFFFFFFFF          # DSPFX_GENS_NONE: ChannelGenerators.modes() without a node
 BLENDS_NONE = 0xFFFFFFFF        # DSPFX_BLENDS_NONE: ChannelBlends.kinds() without a node
 FILTERS_NONE = 0xFFFFFFFF       # DSPFX_FILTERS_NONE: ChannelFilters.kinds() of an empty slot; reset(stage=None), every stage
+RACKS_NONE = 0xFFFFFFFF         # DSPFX_RACKS_NONE: ChannelRacks.kinds() of an empty slot, .modes() without a Distort node
+RACKS_MAX_SLOTS = 4             # DSPFX_RACKS_MAX_SLOTS: the slots one ChannelRacks channel owns at most
 FIRS_NONE = 0xFFFFFFFF          # DSPFX_FIRS_NONE: ChannelFirs.modes() without a node; set_taps(mode=None), keep the node's mode
 FIRS_MAX_TAPS = 1024            # DSPFX_FIRS_MAX_TAPS: the longest response a ChannelFirs channel may carry
 BLENDS_NO_BUS = 0xFFFFFFFF      # DSPFX_BLENDS_NO_BUS: ChannelBlends.assign, the channel reads no bus (the same value as NO_ROOM)
@@ -123,6 +125,9 @@ EXPORTS = [
     "dspfx_firs_plan", "dspfx_firs_create", "dspfx_firs_destroy", "dspfx_firs_last_error", "dspfx_firs_run", "dspfx_firs_set_taps",
     "dspfx_firs_set_mode", "dspfx_firs_drop", "dspfx_firs_reset", "dspfx_firs_present", "dspfx_firs_lengths", "dspfx_firs_modes",
     "dspfx_firs_taps", "dspfx_firs_deque",
+    "dspfx_racks_plan", "dspfx_racks_create", "dspfx_racks_destroy", "dspfx_racks_last_error", "dspfx_racks_run", "dspfx_racks_set",
+    "dspfx_racks_drop", "dspfx_racks_reset", "dspfx_racks_present", "dspfx_racks_kinds", "dspfx_racks_modes", "dspfx_racks_sliders",
+    "dspfx_racks_state",
 ]
 COMM_ID_BYTES = 128
 
@@ -234,6 +239,11 @@ class _FiltersDesc(C.Structure):
 class _FirsDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("max_taps", C.c_uint32), ("general_only", C.c_uint32)]
+
+
+class _RacksDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("slots", C.c_uint32)]
 
 
 class _Ctl(C.Structure):
@@ -537,6 +547,20 @@ def lib():
         getattr(L, f"dspfx_firs_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_firs_taps.argtypes = [vp, C.c_uint64, C.POINTER(C.c_double), u32p]
     L.dspfx_firs_deque.argtypes = [vp, C.POINTER(vp)]
+    L.dspfx_racks_plan.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.dspfx_racks_create.argtypes = [C.POINTER(_RacksDesc), C.POINTER(vp)]
+    L.dspfx_racks_destroy.argtypes = [vp]
+    L.dspfx_racks_last_error.restype = C.c_char_p
+    L.dspfx_racks_last_error.argtypes = [vp]
+    L.dspfx_racks_run.argtypes = [vp, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_racks_set.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(fp), u32p, C.c_uint64, C.c_uint64]
+    for name in ("drop", "reset"):
+        getattr(L, f"dspfx_racks_{name}").argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64]
+    L.dspfx_racks_present.argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    for name in ("kinds", "modes"):
+        getattr(L, f"dspfx_racks_{name}").argtypes = [vp, C.c_uint32, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_racks_sliders.argtypes = [vp, C.c_uint32, fp, C.c_uint64, C.c_uint64]
+    L.dspfx_racks_state.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2478,6 +2502,121 @@ class ChannelFilters(_ChannelBank):
         p = C.c_void_p()
         self._chk(self.L.dspfx_filters_state(self.h, int(stage) & 0xFFFFFFFF, C.byref(p)))
         return self._view(p.value, (self.channels,))
+
+
+def racks_plan(channels: int, slots: int = 4) -> int:
+    """dspfx_racks_plan, a pure host function (no GPU): the device bytes of a ChannelRacks bank's tables, 37 per channel and slot
+    (five slider fields, four state floats, the kind byte)."""
+    return _plan_bytes("racks", channels, slots)
+
+
+# the kinds a rack slot may carry and their slider counts; every other kind is refused by the library with a reason
+_RACK_SLIDERS = {GAIN: 1, BIQUAD: 6, LOW_PASS: 1, HIGH_PASS: 1, ENVELOPE: 2, DISTORT: 1, OVERDRIVE: 3, CHEBYSHEV: 2}
+
+
+class ChannelRacks(_ChannelBank):
+    """A per-channel chain of mixed nodes in one pass (include/dspfx.h, dspfx_racks_*): channel c owns `slots` slots (1 .. 4), run
+    in slot order, each empty or any one of Gain, BiQuad, LowPass, HighPass, Envelope, Distort (every mode but FUZZ), Overdrive and
+    Chebyshev with its own sliders and state, over a device block in the layout of `tile_channels` (as Engine's).  All slots run
+    between one load and one store of the block.  An empty slot copies; a fresh bank copies its input.  A channel's output and
+    state are bit for bit what ChannelFilters(stages=1), ChannelStrips(bands=1) and ChannelShapers give when they are run slot
+    after slot with the slot's node on that channel; without a BiQuad that is Engine([its present nodes in slot order],
+    link_flags=0).  A `set` of a kind the slot does not carry makes a new node (state +0.0, the reference's defaults for what is
+    None); a `set` of the kind it carries keeps what is None, keeps the state of LowPass, HighPass and Envelope and zeroes a
+    BiQuad's.  Asynchronous on `stream`."""
+
+    _C = "racks"
+    _DESC = _RacksDesc
+
+    def __init__(self, channels: int, slots: int = 4, tile_channels: int = 0, max_frames: int = BUF_SIZE, device: int = 0):
+        self.slots = int(slots)
+        super().__init__(channels, tile_channels, max_frames, device, self.slots & 0xFFFFFFFF)
+
+    def run(self, block, n_frames: Optional[int] = None, out=None, stream: int = 0):
+        """One device block through every channel's slots -> `out`, a device block in the same layout (made when not given;
+        out=block works in place)."""
+        n_frames = self._frames(block, n_frames)
+        if out is None:
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_racks_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
+        return out
+
+    def set(self, slot: int, node: NodeSpec, first_channel: int = 0, count: Optional[int] = None):
+        """Give slot `slot` of channels from first_channel the node `node`, a NodeSpec of the engine's own constructors (Gain,
+        BiQuad, LowPass, HighPass, Envelope, Distort, Overdrive, Chebyshev): every slider, and a Distort's mode, is an array (one
+        value per channel, all arrays of one store the same length) or a scalar for `count` channels (default: all from
+        first_channel).  A slider given as None keeps its value where the slot carries the kind and is the reference's default
+        where it carries another or none.  Values are taken as given (no clamp).  A slot the bank does not have, a range past the
+        channels, a kind that is not a rack node, an unknown Distort mode or FUZZ refuse the whole store.  Any thread; applies to
+        the runs submitted after it."""
+        if not isinstance(node, NodeSpec):
+            raise DspfxError(-1, "racks set: the node is a NodeSpec (Gain(..), BiQuad(..), LowPass(..), ..)")
+        kind = int(node.kind)
+        params = list(node.params)
+        if kind in _RACK_SLIDERS and len(params) > _RACK_SLIDERS[kind]:
+            raise DspfxError(-1, f"racks set: kind {kind} has {_RACK_SLIDERS[kind]} sliders and {len(params)} are given")
+        modes = node.mode if kind == DISTORT else None
+        n = self._range(first_channel, count, tuple(params) + (modes,), "racks set: the arrays name different numbers of channels")
+        keep, ptrs = self._f32s(params, n)
+        six = (C.POINTER(C.c_float) * 6)(*[p if p is not None else C.POINTER(C.c_float)() for p in ptrs])
+        m, mp = self._u32s(modes, n, "set", "DSPFX_DIST_*")
+        self._chk(self.L.dspfx_racks_set(self.h, int(slot) & 0xFFFFFFFF, kind & 0xFFFFFFFF, six, mp, int(first_channel), n))
+
+    def set_chain(self, nodes: Sequence[NodeSpec], first_channel: int = 0, count: Optional[int] = None):
+        """Slots 0 .. len(nodes) - 1 of the range from `nodes`, in order (rules as `set`); the slots behind them are dropped."""
+        nodes = list(nodes)
+        if len(nodes) > self.slots:
+            raise DspfxError(-1, f"racks set_chain: {len(nodes)} nodes, and the bank has {self.slots} slots")
+        for node in nodes:
+            if not isinstance(node, NodeSpec):
+                raise DspfxError(-1, "racks set_chain: every node is a NodeSpec (Gain(..), BiQuad(..), LowPass(..), ..)")
+        for t, node in enumerate(nodes):
+            self.set(t, node, first_channel, count)
+        for t in range(len(nodes), self.slots):
+            self.drop(t, first_channel, count)
+
+    def drop(self, slot: int, first_channel: int = 0, count: Optional[int] = None):
+        """Empty slot `slot` of `count` channels from first_channel (default: all from it) and zero its state: that slot copies
+        again; queued like a store."""
+        self._chk(self.L.dspfx_racks_drop(self.h, int(slot) & 0xFFFFFFFF, int(first_channel), self._n(first_channel, count)))
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None, slot: Optional[int] = None):
+        """The state of slot `slot` (None: of every slot) back to +0.0 on `count` channels from first_channel (default: all from
+        it); the nodes and the sliders stay; queued like a store.  The way out for a slot whose state became NaN."""
+        s = RACKS_NONE if slot is None else int(slot) & 0xFFFFFFFF
+        self._chk(self.L.dspfx_racks_reset(self.h, s, int(first_channel), self._n(first_channel, count)))
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: bit t set where slot t of the channel carries a node, as every store made so far left it."""
+        return self._table("present", first_channel, count)
+
+    def _slot_table(self, name, slot, first_channel, count, dtype, per):
+        n = self._n(first_channel, count)
+        v = np.zeros((max(n, 0), per) if per > 1 else max(n, 0), dtype)
+        ct = C.c_float if dtype == np.float32 else C.c_uint32
+        self._chk(getattr(self.L, f"dspfx_racks_{name}")(self.h, int(slot) & 0xFFFFFFFF, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
+        return v
+
+    def kinds(self, slot: int, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: slot `slot`'s kind (GAIN, BIQUAD, LOW_PASS, HIGH_PASS, ENVELOPE, DISTORT, OVERDRIVE, CHEBYSHEV), or
+        RACKS_NONE when empty."""
+        return self._slot_table("kinds", slot, first_channel, count, np.uint32, 1)
+
+    def modes(self, slot: int, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the mode of slot `slot`'s Distort node, RACKS_NONE for every other channel."""
+        return self._slot_table("modes", slot, first_channel, count, np.uint32, 1)
+
+    def sliders(self, slot: int, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """float32[count, 6]: slot `slot`'s sliders as they were given, in the order of the node's constructor; 0 where the kind
+        has fewer and when empty."""
+        return self._slot_table("sliders", slot, first_channel, count, np.float32, 6)
+
+    def state(self, slot: int):
+        """float32[4, channels] on the device: slot `slot`'s state after the last run -- row 0 the z of a one-pole or the envelope,
+        rows 0 .. 3 a BiQuad's x1, x2, y1, y2, +0.0 everywhere else (valid after a run, on its stream)."""
+        p = C.c_void_p()
+        self._chk(self.L.dspfx_racks_state(self.h, int(slot) & 0xFFFFFFFF, C.byref(p)))
+        return self._view(p.value, (4, self.channels))
 
 
 def firs_plan(channels: int, max_taps: int = 64) -> int:

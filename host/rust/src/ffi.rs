@@ -328,6 +328,29 @@ pub const DSPFX_FIRS_MAX_TAPS: u32 = 1024;
 /// `dspfx_firs_modes`: the channel carries no node; `dspfx_firs_set_taps`: keep the node's mode.
 pub const DSPFX_FIRS_NONE: u32 = 0xFFFF_FFFF;
 
+/// Opaque channel-rack bank handle (`typedef struct dspfx_racks dspfx_racks`).
+#[repr(C)]
+pub struct dspfx_racks {
+    _private: [u8; 0],
+}
+
+/// The channel-rack bank's descriptor (`dspfx_racks_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_racks_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub slots: u32,
+}
+
+/// The slots one channel of a channel-rack bank owns at most.
+pub const DSPFX_RACKS_MAX_SLOTS: u32 = 4;
+/// `dspfx_racks_kinds`: the slot is empty; `dspfx_racks_modes`: it carries no Distort node; `dspfx_racks_reset`: every slot.
+pub const DSPFX_RACKS_NONE: u32 = 0xFFFF_FFFF;
+
 /// Opaque mix-group bank handle (`typedef struct dspfx_mixgroups dspfx_mixgroups`).
 #[repr(C)]
 pub struct dspfx_mixgroups {
@@ -715,6 +738,19 @@ extern "C" {
     pub fn dspfx_filters_kinds(f: *mut dspfx_filters, stage: u32, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_filters_sliders(f: *mut dspfx_filters, stage: u32, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_filters_state(f: *mut dspfx_filters, stage: u32, state_out: *mut *const f32) -> c_int;
+    pub fn dspfx_racks_plan(channels: u64, slots: u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_racks_create(desc: *const dspfx_racks_desc, out: *mut *mut dspfx_racks) -> c_int;
+    pub fn dspfx_racks_destroy(r: *mut dspfx_racks) -> c_int;
+    pub fn dspfx_racks_last_error(r: *const dspfx_racks) -> *const c_char;
+    pub fn dspfx_racks_run(r: *mut dspfx_racks, input: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_racks_set(r: *mut dspfx_racks, slot: u32, kind: u32, host_sliders: *const *const f32, host_mode: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_drop(r: *mut dspfx_racks, slot: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_reset(r: *mut dspfx_racks, slot: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_present(r: *mut dspfx_racks, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_kinds(r: *mut dspfx_racks, slot: u32, host_kinds_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_modes(r: *mut dspfx_racks, slot: u32, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_sliders(r: *mut dspfx_racks, slot: u32, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_racks_state(r: *mut dspfx_racks, slot: u32, state_out: *mut *const f32) -> c_int;
     pub fn dspfx_firs_plan(channels: u64, max_taps: u32, bytes_out: *mut u64) -> c_int;
     pub fn dspfx_firs_create(desc: *const dspfx_firs_desc, out: *mut *mut dspfx_firs) -> c_int;
     pub fn dspfx_firs_destroy(f: *mut dspfx_firs) -> c_int;

@@ -1685,6 +1685,107 @@ int dspfx_firs_taps(dspfx_firs *f, uint64_t channel, double *host_taps_out, uint
  * without a node or before the first sample).  The pointer never changes; what it holds is valid after a run, on its stream. */
 int dspfx_firs_deque(dspfx_firs *f, const int32_t **deque_out);
 
+/* ---- channel racks: a per-channel chain of mixed nodes in one pass ----------------------------------------------------
+ * The strips, filters and shapers banks give every channel its own sliders, but the ORDER of the nodes is the order of the host's
+ * run calls, the same for all N channels, and every bank is a launch with one read and one write of the block.  A rack gives
+ * channel c a chain of its own: `slots` SLOTS (1 .. 4), run in slot order 0 .. slots - 1, each empty or carrying ANY ONE of the
+ * small-state chain nodes with its own sliders and state, all slots between one load and one store of the block.  Over N channels
+ * in the desc's layout (tile_channels as dspfx_engine_desc).  A fresh bank has every slot empty: run copies in to out bit for bit.
+ * PER SLOT AND CHANNEL.  A kind (a dspfx_kind, or none), a mode (Distort only) and up to six sliders in the order of
+ * dspfx_node_desc.params, four floats of state:
+ *       kind               sliders                          state            arithmetic
+ *       DSPFX_GAIN         level                            -                x * level                      (gain.rs:33-37)
+ *       DSPFX_BIQUAD       raw a0, a1, a2, b0, b1, b2       x1, x2, y1, y2   normalised by dspfx_strips_coeffs; the strips bank's row,
+ *                                                                            b0 * x + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2 in that order
+ *       DSPFX_LOW_PASS     ratio                            z                the filters bank's bodies, every operation one IEEE f32
+ *       DSPFX_HIGH_PASS    ratio                            z                round-to-nearest
+ *       DSPFX_ENVELOPE     attack, release (frames)         env              the filters bank's; the gains by dspfx_envelope_gain
+ *       DSPFX_DISTORT      level; mode: the eight DSPFX_DIST_* other than Fuzz    -    the engine's distort1, the shapers bank's bypass
+ *                                                                            (level < 0.001, which a NaN level is not)
+ *       DSPFX_OVERDRIVE    boost, drive, level              -                the engine's overdrive1, the shapers bank's bypass
+ *       DSPFX_CHEBYSHEV    level_pos, level_neg             -                the engine's chebyshev1; the two tanh denominators once per run
+ *   An empty slot keeps the sample's own bits.  Values are taken as given: no clamp, NaN and out-of-range values included.
+ *   NOT HERE, refused as kinds with a reason that names the bank that has them: DSPFX_REVERB (delays), DSPFX_FIR (firs), DSPFX_ADD
+ *   and DSPFX_MIX (blends), DSPFX_SIGNAL_GEN (gens); Fuzz, which is block-global, stays with the shapers bank.  Link hops, control
+ *   ports and graph wiring stay with the engine.  More than four slots are two racks in a row.
+ * THE CONTRACT.  For any table of kinds and sliders and any sequence of stores and run lengths a channel's output is BIT FOR BIT
+ * what the existing banks give when they are run slot after slot on the same stream -- for slot t a dspfx_filters bank of one
+ * stage, then a dspfx_strips bank of one band with link_flags 0, then a dspfx_shapers bank, each persistent across runs and each
+ * carrying slot t's node on exactly the channels whose slot t holds a kind of its family -- and the slot's state is theirs.  So a
+ * channel without a BiQuad equals an engine whose chain is its present nodes in slot order with link_flags = 0 bit for bit, and a
+ * BiQuad slot is within 1 ulp of the engine's BiQuad, as the strips bank is.  A channel's bits are the same in either layout, in
+ * place or not, on any stream, however the frames are cut into runs and whatever its neighbours carry.
+ * STORES.  dspfx_racks_set of a kind the slot does not carry makes a NEW node: state +0.0, and the values of dspfx_node_defaults
+ * for what the call leaves NULL.  A set of the kind the slot carries keeps what is NULL; it KEEPS THE STATE for LowPass, HighPass
+ * and Envelope (none has an after_settings_change) and ZEROES it for BiQuad on the stored channels (biquad.rs:62-76, as
+ * dspfx_strips_set_band).  dspfx_racks_drop empties a slot and zeroes its state; dspfx_racks_reset zeroes state and keeps nodes and
+ * sliders.  A slot the bank does not have, a range past the channels, a kind outside the table, an unknown Distort mode or Fuzz
+ * refuse the WHOLE store: DSPFX_ERR_INVALID, the reason in dspfx_racks_last_error, nothing stored.  All stores go through the
+ * staged-store queue: from any thread, never waiting for the device, governing the runs submitted after they return.
+ * ONE RUN is one kernel behind the drained stores: a lane owns its channels for the whole run (four adjacent channels per 16-byte
+ * access at one or two slots, two at four slots, one when the layout or the alignment forbids vectors), frames go in chunks with
+ * the next chunk's loads issued ahead of the arithmetic, stores are nontemporal, `slots` is a template parameter (a bank of three
+ * runs the kernel of four) and every slot lives in registers.  The kinds differ per lane and slot: a wave ballots once per run
+ * and slot, and per chunk and slot runs each present kind's body wave-uniformly under a per-channel select; a wave whose lanes
+ * carry nothing in a slot does no arithmetic for it and reads neither its sliders nor its state.  A bank whose drained tables hold
+ * no kind that evaluates in f64 (Tanh, Sin, Atan, Overdrive, Chebyshev) runs an instantiation without those bodies.  No atomics,
+ * no LDS.
+ * Memory: 37 bytes per channel and slot of tables on the device (five slider fields, four state floats and a kind byte;
+ * dspfx_racks_plan), 26 on the host. */
+/* dspfx_racks_kinds: the slot is empty; dspfx_racks_modes: it carries no Distort node; dspfx_racks_reset: every slot */
+#define DSPFX_RACKS_NONE 0xFFFFFFFFu
+#define DSPFX_RACKS_MAX_SLOTS 4
+typedef struct dspfx_racks dspfx_racks;
+typedef struct dspfx_racks_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t slots;           /* slots per channel, 1 .. DSPFX_RACKS_MAX_SLOTS */
+} dspfx_racks_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, 37 * slots * channels.  channels of 0 or
+ * above 2^32 - 256, slots outside 1 .. 4: DSPFX_ERR_INVALID, the reason in dspfx_racks_last_error(NULL). */
+int dspfx_racks_plan(uint64_t channels, uint32_t slots, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0, slots outside 1 .. 4) is DSPFX_ERR_INVALID with the reason in dspfx_racks_last_error of a NULL bank (kept per
+ * thread); all of that is checked before any device work. */
+int dspfx_racks_create(const dspfx_racks_desc *desc, dspfx_racks **out);
+int dspfx_racks_destroy(dspfx_racks *r);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_racks_last_error(const dspfx_racks *r);
+/* in, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out == in works in place (a
+ * thread rewrites the elements it read); any other overlap is the caller's error.  Asynchronous on `stream`; a run on another
+ * stream than the one before first waits (on the device) for that one, since the state is the bank's (the rules of
+ * dspfx_strips_run).  Queued stores go onto the stream ahead of the kernel, in the order they were made. */
+int dspfx_racks_run(dspfx_racks *r, const float *in, float *out, uint32_t n_frames, void *stream);
+/* Gives slot `slot` of channels [first_channel, first_channel + count) a node of `kind` (a dspfx_kind of the table above).
+ * host_sliders: NULL or six pointers in the order of dspfx_node_desc.params, each NULL or a host array of `count` values; those
+ * behind the kind's slider count are not read.  host_mode: NULL or `count` DSPFX_DIST_* values, read for DSPFX_DISTORT only.  What
+ * is NULL is kept where the slot carries the kind and is the default of dspfx_node_defaults where it carries another or none.  The
+ * contract of dspfx_dynamics_set: callable from any thread while runs are in flight, never waits for the device or for a run; the
+ * values are staged in page-locked memory and queued, each store is whole, and a run submitted after the call returns sees it,
+ * the runs submitted before it do not. */
+int dspfx_racks_set(dspfx_racks *r, uint32_t slot, uint32_t kind, const float *const *host_sliders, const uint32_t *host_mode, uint64_t first_channel,
+                    uint64_t count);
+/* Empties slot `slot` of channels [first_channel, first_channel + count) and zeroes its state: that slot copies again, and a
+ * later store starts from the defaults.  Queued like a store. */
+int dspfx_racks_drop(dspfx_racks *r, uint32_t slot, uint64_t first_channel, uint64_t count);
+/* The state of slot `slot` (DSPFX_RACKS_NONE: of every slot) back to +0.0 on the range; the nodes and the sliders stay.  Queued
+ * like a store.  Also the way out for a slot whose state became NaN. */
+int dspfx_racks_reset(dspfx_racks *r, uint32_t slot, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: present, bit t set where slot
+ * t carries a node; kinds of slot `slot`, a dspfx_kind or DSPFX_RACKS_NONE; modes of slot `slot`, the DSPFX_DIST_* value of a
+ * Distort node, DSPFX_RACKS_NONE otherwise; sliders of slot `slot` [count][6] raw, as they were given, 0 behind the kind's slider
+ * count and for an empty slot. */
+int dspfx_racks_present(dspfx_racks *r, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_racks_kinds(dspfx_racks *r, uint32_t slot, uint32_t *host_kinds_out, uint64_t first_channel, uint64_t count);
+int dspfx_racks_modes(dspfx_racks *r, uint32_t slot, uint32_t *host_modes_out, uint64_t first_channel, uint64_t count);
+int dspfx_racks_sliders(dspfx_racks *r, uint32_t slot, float *host_sliders_out, uint64_t first_channel, uint64_t count);
+/* The device pointer of slot `slot`'s state, float [4][N]: row 0 is z of a one-pole or the envelope, rows 0 .. 3 are x1, x2, y1, y2
+ * of a BiQuad, +0.0 everywhere else.  The pointer never changes; what it holds is valid after a run, on its stream. */
+int dspfx_racks_state(dspfx_racks *r, uint32_t slot, const float **state_out);
+
 /* ---- channel generators: a bank of per-channel Signal Generators -------------------------------------------------------
  * An engine runs one Signal Generator (nodes/signal_gen.rs) with one amplitude, frequency and mode for all N channels.  This bank
  * gives channel c ONE generator of its own, with its own sliders, mode and clock, over N channels in the desc's layout

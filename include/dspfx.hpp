@@ -922,6 +922,86 @@ inline std::uint64_t filters_plan(std::uint64_t channels, std::uint32_t stages) 
     return bytes;
 }
 
+// A per-channel chain of mixed nodes in one pass (include/dspfx.h, dspfx_racks_*): channel c owns `slots` slots (1 .. 4), run in slot
+// order, each empty or any one of Gain, BiQuad, LowPass, HighPass, Envelope, Distort (every mode but Fuzz), Overdrive and Chebyshev
+// with its own sliders and state, over a device block in the layout of tile_channels; all slots run between one load and one store
+// of the block.  Its output and state are bit for bit what ChannelFilters(1 stage), ChannelStrips(1 band) and ChannelShapers give
+// when they are run slot after slot with the slot's node on that channel.  A set() of a kind the slot does not carry makes a new
+// node (state +0.0, dspfx_node_defaults for a slider passed as nullptr); a set() of the kind it carries keeps what is nullptr,
+// keeps the state of LowPass, HighPass and Envelope and zeroes a BiQuad's.  A fresh bank copies its input.
+class ChannelRacks {
+  public:
+    ChannelRacks(std::uint32_t channels, std::uint32_t slots = DSPFX_RACKS_MAX_SLOTS, std::uint32_t tile_channels = 0,
+                 std::uint32_t max_frames = DSPFX_BUF_SIZE, int device = 0) {
+        const dspfx_racks_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, slots};
+        const int rc = dspfx_racks_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_racks_last_error(nullptr) ? dspfx_racks_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelRacks() { dspfx_racks_destroy(p_); }
+    ChannelRacks(const ChannelRacks &) = delete;
+    ChannelRacks &operator=(const ChannelRacks &) = delete;
+    // device block of n_frames -> device block in the same layout (out == in: in place); asynchronous on `stream`
+    void run(const float *in, float *out, std::uint32_t n_frames, void *stream = nullptr) { chk(dspfx_racks_run(p_, in, out, n_frames, stream)); }
+    // a node of `kind` (a dspfx_kind) in slot `slot` of channels [first_channel, first_channel + count): host_sliders is nullptr or six
+    // pointers in the order of dspfx_node_desc.params, each nullptr or `count` values; host_mode is nullptr or `count` DSPFX_DIST_*
+    // values (Distort).  A slot that is not one of the bank's, a kind that is no rack node, an unknown mode or Fuzz refuses the
+    // whole store.  Any thread; never waits
+    void set(std::uint32_t slot, std::uint32_t kind, const float *const *host_sliders, const std::uint32_t *host_mode, std::uint64_t first_channel,
+             std::uint64_t count) {
+        chk(dspfx_racks_set(p_, slot, kind, host_sliders, host_mode, first_channel, count));
+    }
+    // the slot emptied and its state zeroed: that slot copies again; queued like a store
+    void drop(std::uint32_t slot, std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_racks_drop(p_, slot, first_channel, count)); }
+    // the state of slot `slot` (DSPFX_RACKS_NONE: of every slot) back to +0.0; nodes and sliders stay; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count, std::uint32_t slot = DSPFX_RACKS_NONE) {
+        chk(dspfx_racks_reset(p_, slot, first_channel, count));
+    }
+    // the host tables, as all stores so far left them: a bit per slot that carries a node; slot `slot`'s dspfx_kind or
+    // DSPFX_RACKS_NONE; its Distort mode or DSPFX_RACKS_NONE; its [count][6] raw sliders as given
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_racks_present(p_, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> kinds(std::uint32_t slot, std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_racks_kinds(p_, slot, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<std::uint32_t> modes(std::uint32_t slot, std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(dspfx_racks_modes(p_, slot, m.data(), first_channel, count));
+        return m;
+    }
+    std::vector<float> sliders(std::uint32_t slot, std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<float> m(6 * count);
+        chk(dspfx_racks_sliders(p_, slot, m.data(), first_channel, count));
+        return m;
+    }
+    // slot `slot`'s state[4][channels] on the device after the last run, on its stream: row 0 z or the envelope, rows 0 .. 3 a
+    // BiQuad's x1, x2, y1, y2
+    const float *state(std::uint32_t slot) {
+        const float *z = nullptr;
+        chk(dspfx_racks_state(p_, slot, &z));
+        return z;
+    }
+    dspfx_racks *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_racks_last_error(p_) ? dspfx_racks_last_error(p_) : dspfx_strerror(rc));
+    }
+    dspfx_racks *p_ = nullptr;
+};
+
+// The device bytes of a ChannelRacks bank's tables (dspfx_racks_plan: a pure host function, no GPU).
+inline std::uint64_t racks_plan(std::uint64_t channels, std::uint32_t slots) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_racks_plan(channels, slots, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_racks_last_error(nullptr));
+    return bytes;
+}
+
 // Per-channel FIR nodes (include/dspfx.h, dspfx_firs_*): channel c may carry one FIR node of its own -- its own taps (f64), tap
 // count T (1 .. max_taps), mode and deque of past samples -- over a device block in the layout of tile_channels; its output is bit
 // for bit what the reference's node gives through all its history.  A node exists from the first set_taps() that names the channel
