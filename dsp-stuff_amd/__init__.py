@@ -67,6 +67,8 @@ RACKS_NONE = 0xFFFFFFFF         # DSPFX_RACKS_NONE: ChannelRacks.kinds() of an e
 RACKS_MAX_SLOTS = 4             # DSPFX_RACKS_MAX_SLOTS: the slots one ChannelRacks channel owns at most
 FIRS_NONE = 0xFFFFFFFF          # DSPFX_FIRS_NONE: ChannelFirs.modes() without a node; set_taps(mode=None), keep the node's mode
 FIRS_MAX_TAPS = 1024            # DSPFX_FIRS_MAX_TAPS: the longest response a ChannelFirs channel may carry
+CANCEL_MAX_TAPS = 1024          # DSPFX_CANCEL_MAX_TAPS: the longest filter a ChannelCancellers channel may carry
+CANCEL_MAX_DELAY = 65535        # DSPFX_CANCEL_MAX_DELAY: the longest bulk delay, in frames
 BLENDS_NO_BUS = 0xFFFFFFFF      # DSPFX_BLENDS_NO_BUS: ChannelBlends.assign, the channel reads no bus (the same value as NO_ROOM)
 RESAMPLE_MAX_FRAMES = 4096      # DSPFX_RESAMPLE_MAX_FRAMES: the most device frames one pull makes, the most frames a FIFO slot holds
 
@@ -128,6 +130,9 @@ EXPORTS = [
     "dspfx_racks_plan", "dspfx_racks_create", "dspfx_racks_destroy", "dspfx_racks_last_error", "dspfx_racks_run", "dspfx_racks_set",
     "dspfx_racks_drop", "dspfx_racks_reset", "dspfx_racks_present", "dspfx_racks_kinds", "dspfx_racks_modes", "dspfx_racks_sliders",
     "dspfx_racks_state",
+    "dspfx_cancel_plan", "dspfx_cancel_create", "dspfx_cancel_destroy", "dspfx_cancel_last_error", "dspfx_cancel_run", "dspfx_cancel_set",
+    "dspfx_cancel_load", "dspfx_cancel_drop", "dspfx_cancel_reset", "dspfx_cancel_present", "dspfx_cancel_lengths", "dspfx_cancel_sliders",
+    "dspfx_cancel_delays", "dspfx_cancel_adapting", "dspfx_cancel_weights_view", "dspfx_cancel_levels_view",
 ]
 COMM_ID_BYTES = 128
 
@@ -239,6 +244,11 @@ class _FiltersDesc(C.Structure):
 class _FirsDesc(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
                 ("tile_channels", C.c_uint32), ("max_taps", C.c_uint32), ("general_only", C.c_uint32)]
+
+
+class _CancelDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("n_channels", C.c_uint32), ("max_frames", C.c_uint32),
+                ("tile_channels", C.c_uint32), ("max_taps", C.c_uint32), ("max_delay", C.c_uint32), ("general_only", C.c_uint32)]
 
 
 class _RacksDesc(C.Structure):
@@ -561,6 +571,21 @@ def lib():
         getattr(L, f"dspfx_racks_{name}").argtypes = [vp, C.c_uint32, u32p, C.c_uint64, C.c_uint64]
     L.dspfx_racks_sliders.argtypes = [vp, C.c_uint32, fp, C.c_uint64, C.c_uint64]
     L.dspfx_racks_state.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.dspfx_cancel_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.dspfx_cancel_create.argtypes = [C.POINTER(_CancelDesc), C.POINTER(vp)]
+    L.dspfx_cancel_destroy.argtypes = [vp]
+    L.dspfx_cancel_last_error.restype = C.c_char_p
+    L.dspfx_cancel_last_error.argtypes = [vp]
+    L.dspfx_cancel_run.argtypes = [vp, f32p, f32p, f32p, C.c_uint32, vp]
+    L.dspfx_cancel_set.argtypes = [vp, u32p, fp, fp, u32p, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_cancel_load.argtypes = [vp, fp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]
+    for name in ("drop", "reset"):
+        getattr(L, f"dspfx_cancel_{name}").argtypes = [vp, C.c_uint64, C.c_uint64]
+    for name in ("present", "lengths", "delays", "adapting"):
+        getattr(L, f"dspfx_cancel_{name}").argtypes = [vp, u32p, C.c_uint64, C.c_uint64]
+    L.dspfx_cancel_sliders.argtypes = [vp, fp, C.c_uint64, C.c_uint64]
+    for name in ("weights_view", "levels_view"):
+        getattr(L, f"dspfx_cancel_{name}").argtypes = [vp, C.POINTER(vp)]
     L.dspfx_mixmatrix_run_sparse.argtypes = [vp, f32p, C.c_uint32, f32p, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
@@ -2710,6 +2735,128 @@ class ChannelFirs(_ChannelBank):
         """int32[3, channels] on the device: len, cap and head of every channel's VecDeque after the last run (valid after a run,
         on its stream)."""
         return self._view(self._deque, (3, self.channels), "<i4")
+
+
+def cancel_plan(channels: int, max_taps: int = 64, max_delay: int = 0) -> int:
+    """dspfx_cancel_plan, a pure host function (no GPU): the device bytes of a ChannelCancellers bank's tables,
+    channels * (4 * max_taps + 4 * R + 24), R = max_delay + max_taps + 16 rounded up to a multiple of 8: max_taps f32 weights, a
+    ring of R f32 reference samples, the node word, the delay, mu, eps and the two levels per channel."""
+    return _plan_bytes("cancel", channels, max_taps, max_delay)
+
+
+class ChannelCancellers(_ChannelBank):
+    """Per-channel adaptive (NLMS) FIR filters (include/dspfx.h, dspfx_cancel_*): channel c may carry one canceller of its own --
+    T taps (1 .. max_taps) that the device updates every frame, a step size mu, a regulariser eps, a bulk delay (0 .. max_delay
+    frames) and the switch adapt -- over two device blocks in the layout of `tile_channels` (as Engine's): `mic`, the primary
+    input, and `ref`, the block the channel was sent.  out = mic minus the filter's estimate of ref's path into mic.  A node
+    exists from the first `set` that names the channel until `drop`; a fresh bank copies mic and reads no ref.  All arithmetic is
+    f32 with every operation rounded once (the rule is in include/dspfx.h), so a channel's output, weights and levels are the
+    same bits in either layout, in place or not, on any stream, whatever its neighbours carry and however the frames are cut into
+    runs.  1024 taps are 21 ms at 48 kHz: line and handset echo behind a bulk delay, not a room's tail.  `general_only` makes
+    every wave take the frames one at a time (for showing that both bodies of the kernel give the same bits).  Asynchronous on
+    `stream`."""
+
+    _C = "cancel"
+    _DESC = _CancelDesc
+
+    def __init__(self, channels: int, max_taps: int = 64, max_delay: int = 0, tile_channels: int = 0, max_frames: int = BUF_SIZE,
+                 device: int = 0, general_only: bool = False):
+        self.max_taps, self.max_delay = int(max_taps), int(max_delay)
+        super().__init__(channels, tile_channels, max_frames, device, self.max_taps & 0xFFFFFFFF, self.max_delay & 0xFFFFFFFF,
+                         int(bool(general_only)))
+        w, l = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.dspfx_cancel_weights_view(self.h, C.byref(w)))
+        self._chk(self.L.dspfx_cancel_levels_view(self.h, C.byref(l)))
+        self._weights, self._levels = w.value, l.value
+
+    def run(self, mic, n_frames: Optional[int] = None, ref=None, out=None, stream: int = 0):
+        """One device block `mic` against the block `ref` the channels were sent -> `out`, a device block in the same layout
+        (made when not given; out=mic works in place).  No ref, or an out that overlaps ref, refuses the run."""
+        n_frames = self._frames(mic, n_frames)
+        if out is None:
+            out = self._out(n_frames)
+        self._chk(self.L.dspfx_cancel_run(self.h, _ptr(mic), _ptr(ref), _ptr(out), int(n_frames), _stream(stream)))
+        return out
+
+    def set(self, taps=None, mu=None, eps=None, delay=None, adapt=None, first_channel: int = 0, count: Optional[int] = None):
+        """The node of channels from first_channel: every argument is None (keep), a scalar for `count` channels (default: all
+        from first_channel) or an array with one value per channel (all arrays of one store the same length).  A channel without a
+        node gets a new one -- weights and history +0.0 and, for what is None, max_taps taps, mu 0.5, eps 1e-6, delay 0,
+        adapting; one that carries a node keeps what is None and keeps its weights and history (a smaller `taps` zeroes the rows
+        it leaves, a larger one starts the new rows at +0.0).  adapt=False freezes: the node filters and does not update.  Values
+        are taken as given (NaN included).  A `taps` of 0 or above max_taps, a `delay` above max_delay, a range past the channels
+        or arrays of different lengths refuse the whole store.  Any thread; applies to the runs submitted after it."""
+        if adapt is not None:
+            adapt = np.asarray(adapt).astype(bool).astype(np.uint32)
+        n = self._range(first_channel, count, (taps, mu, eps, delay, adapt), "cancel set: the arrays name different numbers of channels")
+        keep, (pm, pe) = self._f32s((mu, eps), n)
+        t, pt = self._counts(taps, n, "taps")
+        d, pd = self._counts(delay, n, "delay")
+        a, pa = self._counts(adapt, n, "adapt")
+        self._chk(self.L.dspfx_cancel_set(self.h, pt, pm, pe, pd, pa, int(first_channel), n))
+
+    @staticmethod
+    def _counts(v, n, what):
+        """`v` (None, a scalar or an array of non-negative integers) as uint32[n] -> (the array, its pointer)."""
+        if v is None:
+            return None, None
+        m = np.asarray(v)
+        if m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF)):
+            raise DspfxError(-1, f"cancel set: {what} is a count of frames, or an array of them")
+        m = np.ascontiguousarray(np.broadcast_to(m.reshape(-1), (max(n, 0),)), np.uint32)
+        return m, m.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def load(self, rows, first_channel: int = 0, count: Optional[int] = None):
+        """A warm start: the weights of channels from first_channel, a 1-d float32 array [T] for `count` channels (default: all
+        from first_channel) or a 2-d array [n][T], one row per channel (`count`, when given, must be n); row[k] is w[k].  Every
+        channel of the range carries a node of exactly T taps, else the whole store is refused.  Queued like a store."""
+        h = np.ascontiguousarray(rows, dtype=np.float32)
+        if h.ndim == 1:
+            per, n = 0, self._n(first_channel, count)
+        elif h.ndim == 2 and (count is None or int(count) == h.shape[0]):
+            per, n = 1, h.shape[0]
+        else:
+            raise DspfxError(-1, "cancel load: the rows are [T], or [count][T] with one row per channel")
+        self._chk(self.L.dspfx_cancel_load(self.h, h.ctypes.data_as(C.POINTER(C.c_float)), h.shape[-1] & 0xFFFFFFFF, per, int(first_channel), n))
+
+    def drop(self, first_channel: int = 0, count: Optional[int] = None):
+        """Remove the node of `count` channels from first_channel (default: all from it): a copy again, and a later `set` makes a
+        new node; queued like a store."""
+        self._span("drop", first_channel, count)
+
+    def reset(self, first_channel: int = 0, count: Optional[int] = None):
+        """Weights and history of `count` channels from first_channel (default: all from it) back to +0.0; taps, mu, eps, delay
+        and adapt stay; queued like a store.  The way out for a channel whose weights became NaN."""
+        self._span("reset", first_channel, count)
+
+    def weights(self):
+        """float32[max_taps, channels] on the device, row k = w[k] of every channel, +0.0 in the rows k >= a channel's taps: a
+        view of the bank's table, no copy (valid after a run, on its stream)."""
+        return self._view(self._weights, (self.max_taps, self.channels))
+
+    def levels(self):
+        """float32[2, channels] on the device: sum d^2 and sum e^2 of the last run, +0.0 without a node (a view)."""
+        return self._view(self._levels, (2, self.channels))
+
+    def present(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the channel carries a node, as every store made so far left it."""
+        return self._table("present", first_channel, count)
+
+    def lengths(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the node's tap count T, 0 without a node."""
+        return self._table("lengths", first_channel, count)
+
+    def sliders(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """float32[count, 2]: mu and eps as they were given; 0, 0 without a node."""
+        return self._table("sliders", first_channel, count, np.float32, 2)
+
+    def delays(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: the node's bulk delay in frames, 0 without a node."""
+        return self._table("delays", first_channel, count)
+
+    def adapting(self, first_channel: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """uint32[count]: 1 where the node updates its weights, 0 frozen or without a node."""
+        return self._table("adapting", first_channel, count)
 
 
 def _seat_counts(seats, groups: int) -> np.ndarray:

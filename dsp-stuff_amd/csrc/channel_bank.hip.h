@@ -1,5 +1,5 @@
 // channel_bank.hip.h -- the scaffold of the per-channel banks (strips, delays, talkers, dynamics, shapers, gens, blends, filters,
-// firs, racks _kernels.hip): the members they all have, and the host glue around BankError (bank_common.hip.h) and StoreQueue
+// firs, racks, cancel _kernels.hip): the members they all have, and the host glue around BankError (bank_common.hip.h) and StoreQueue
 // (store_queue.hip.h) that is the same in each -- the range check, create's checks and its tail, the device tables' bytes,
 // allocation, clearing and freeing from the bank's one list of them, a run's first lines, a staged store's first lines, a store
 // without values, a host table read back.  A bank keeps what its stores mean (apply_store, its host tables, its validation), its

@@ -1,4 +1,4 @@
-// lane_io.hip.h -- how a lane of the per-channel banks (strips, talkers, dynamics, shapers, gens, blends, filters, firs, racks _kernels.hip) reads and writes the
+// lane_io.hip.h -- how a lane of the per-channel banks (strips, talkers, dynamics, shapers, gens, blends, filters, firs, racks, cancel _kernels.hip) reads and writes the
 // channels it owns for a whole block: CPL adjacent channels in one load and one store per frame, which channels those are
 // (lane_channel), and the host's decision whether CPL may be 4.  Device, and one small host part.  hipcc only.
 #pragma once

@@ -1,5 +1,5 @@
 // store_queue.hip.h -- the staged-store queue of the banks that take live stores (mixgroups, mixmatrix and the per-channel banks
-// strips, delays, talkers, dynamics, shapers, gens, blends, filters, firs, racks _kernels.hip; the latter through channel_bank.hip.h).
+// strips, delays, talkers, dynamics, shapers, gens, blends, filters, firs, racks, cancel _kernels.hip; the latter through channel_bank.hip.h).
 // A store is made on any thread at any time: its values are copied into a page-locked staging buffer and it joins the queue.  The
 // next run drains the queue onto its own stream ahead of its kernel, in the order the stores were made, so a store between two runs
 // changes exactly the second.  A staging buffer is reused once the event recorded behind its copy has passed.  Host only.

@@ -328,6 +328,31 @@ pub const DSPFX_FIRS_MAX_TAPS: u32 = 1024;
 /// `dspfx_firs_modes`: the channel carries no node; `dspfx_firs_set_taps`: keep the node's mode.
 pub const DSPFX_FIRS_NONE: u32 = 0xFFFF_FFFF;
 
+/// Opaque channel-canceller bank handle (`typedef struct dspfx_cancel dspfx_cancel`).
+#[repr(C)]
+pub struct dspfx_cancel {
+    _private: [u8; 0],
+}
+
+/// The channel-canceller bank's descriptor (`dspfx_cancel_create`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct dspfx_cancel_desc {
+    pub abi_version: u32,
+    pub device: i32,
+    pub n_channels: u32,
+    pub max_frames: u32,
+    pub tile_channels: u32,
+    pub max_taps: u32,
+    pub max_delay: u32,
+    pub general_only: u32,
+}
+
+/// The longest filter a channel of a channel-canceller bank may carry.
+pub const DSPFX_CANCEL_MAX_TAPS: u32 = 1024;
+/// The longest bulk delay, in frames, a channel of a channel-canceller bank may carry.
+pub const DSPFX_CANCEL_MAX_DELAY: u32 = 65535;
+
 /// Opaque channel-rack bank handle (`typedef struct dspfx_racks dspfx_racks`).
 #[repr(C)]
 pub struct dspfx_racks {
@@ -765,6 +790,22 @@ extern "C" {
     pub fn dspfx_firs_modes(f: *mut dspfx_firs, host_modes_out: *mut u32, first_channel: u64, count: u64) -> c_int;
     pub fn dspfx_firs_taps(f: *mut dspfx_firs, channel: u64, host_taps_out: *mut f64, n_taps_out: *mut u32) -> c_int;
     pub fn dspfx_firs_deque(f: *mut dspfx_firs, deque_out: *mut *const i32) -> c_int;
+    pub fn dspfx_cancel_plan(channels: u64, max_taps: u32, max_delay: u32, bytes_out: *mut u64) -> c_int;
+    pub fn dspfx_cancel_create(desc: *const dspfx_cancel_desc, out: *mut *mut dspfx_cancel) -> c_int;
+    pub fn dspfx_cancel_destroy(a: *mut dspfx_cancel) -> c_int;
+    pub fn dspfx_cancel_last_error(a: *const dspfx_cancel) -> *const c_char;
+    pub fn dspfx_cancel_run(a: *mut dspfx_cancel, mic: *const f32, reference: *const f32, out: *mut f32, n_frames: u32, stream: *mut c_void) -> c_int;
+    pub fn dspfx_cancel_set(a: *mut dspfx_cancel, host_taps: *const u32, host_mu: *const f32, host_eps: *const f32, host_delay: *const u32, host_adapt: *const u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_load(a: *mut dspfx_cancel, host_rows: *const f32, n_taps: u32, per_channel: u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_drop(a: *mut dspfx_cancel, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_reset(a: *mut dspfx_cancel, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_present(a: *mut dspfx_cancel, host_present_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_lengths(a: *mut dspfx_cancel, host_lengths_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_sliders(a: *mut dspfx_cancel, host_sliders_out: *mut f32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_delays(a: *mut dspfx_cancel, host_delays_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_adapting(a: *mut dspfx_cancel, host_adapting_out: *mut u32, first_channel: u64, count: u64) -> c_int;
+    pub fn dspfx_cancel_weights_view(a: *mut dspfx_cancel, weights_out: *mut *const f32) -> c_int;
+    pub fn dspfx_cancel_levels_view(a: *mut dspfx_cancel, levels_out: *mut *const f32) -> c_int;
     pub fn dspfx_mixmatrix_plan(group_start: *const u64, n_groups: u32, n_channels: u64, tile_channels: u32, count_out: *mut u32, edge_out: *mut u32, offset_out: *mut u64, total_bytes_out: *mut u64) -> c_int;
     pub fn dspfx_mixmatrix_create(desc: *const dspfx_mixmatrix_desc, out: *mut *mut dspfx_mixmatrix) -> c_int;
     pub fn dspfx_mixmatrix_destroy(m: *mut dspfx_mixmatrix) -> c_int;

@@ -1786,6 +1786,102 @@ int dspfx_racks_sliders(dspfx_racks *r, uint32_t slot, float *host_sliders_out, 
  * of a BiQuad, +0.0 everywhere else.  The pointer never changes; what it holds is valid after a run, on its stream. */
 int dspfx_racks_state(dspfx_racks *r, uint32_t slot, const float **state_out);
 
+/* ---- channel cancellers: a bank of per-channel adaptive (NLMS) FIR filters ---------------------------------------------
+ * The FIR bank's taps come from the host.  This bank gives channel c ONE adaptive filter of its own whose taps the DEVICE updates
+ * every frame: the stage that removes a participant's own return from their microphone (an echo canceller), adaptive noise
+ * cancelling against a reference pick-up, feedback suppression, live identification of a channel's path.  Two blocks come in, in
+ * the desc's layout (tile_channels as dspfx_engine_desc): mic, the primary input d, and ref, the block the channel was sent.
+ * A node EXISTS for a channel from the first dspfx_cancel_set that names it until dspfx_cancel_drop; a fresh bank has no node
+ * anywhere: run copies mic to out bit for bit and reads no ref.
+ * PER CHANNEL: T taps (1 .. max_taps), weights w[0 .. T), a step size mu, a regulariser eps, a bulk delay D (0 .. max_delay), the
+ * switch adapt.  All arithmetic is f32, every operation rounded once, as written, nothing fused or reassociated.  For frame n of
+ * the bank's own frame count:
+ *       u[k] = ref[n - D - k], k < T            +0.0 where that frame lies before the node's first frame (its creation or its
+ *                                               last reset); the history runs across runs
+ *       dot(a, b) = (s_0 + s_1) + (s_2 + s_3)   four chains from +0.0; chain j takes the k = j (mod 4) in ascending k,
+ *                                               s_j = s_j + (a[k] * b[k]); every k < T is a product as written, no term k >= T exists
+ *       y = dot(w, u);  e = d[n] - y;  out[n] = e
+ *       adapt only:  p = dot(u, u);  g = (mu * e) / (p + eps), one IEEE division;  w[k] = w[k] + (g * u[k]) for every k < T
+ *       levels: sum d * d and sum e * e over the run, in frame order, from +0.0
+ * Values are taken as given, NaN included: a NaN or an infinity that reaches a channel's weights stays in that channel until
+ * dspfx_cancel_reset and never reaches a neighbour.  So a channel's out, weights and levels are the same bits in either layout, in
+ * place or not, on any stream, whatever its neighbours carry and however the frames are cut into runs (the levels are per run).
+ * STORES.  dspfx_cancel_set on a channel without a node makes a NEW node: weights and history +0.0, and for what the call leaves
+ * NULL: max_taps taps, mu 0.5, eps 1e-6, delay 0, adapting.  On a channel that carries a node it keeps what it leaves NULL and
+ * keeps the weights and the history: a smaller T zeroes the rows k >= T, a larger T starts the new rows at +0.0 (the weights
+ * table holds +0.0 in every row k >= the node's T, always); a new delay only moves the window.  dspfx_cancel_load replaces the
+ * weights (a warm start).  dspfx_cancel_drop removes the node; dspfx_cancel_reset puts weights and history back to +0.0 and
+ * keeps T, mu, eps, delay and adapt.  A T of 0 or above max_taps, a delay above max_delay, a range past the channels, a load on a
+ * channel without a node or with another T refuses the WHOLE store: DSPFX_ERR_INVALID, the reason in dspfx_cancel_last_error,
+ * nothing stored.
+ * ON THE DEVICE, per channel: max_taps float weights laid out [tap][N], so the lanes of a wave (a lane is a channel) read one tap
+ * of 64 channels in one access; a ring in time of R float reference samples, R = max_delay + max_taps + 16 rounded up to a multiple
+ * of 8, the rows in groups of eight, [row / 8][N][8], so the eight rows a lane writes and reads per block are 32 bytes of its own
+ * whatever its delay; the node word (T and adapt), the delay, mu, eps; two levels.  dspfx_cancel_plan:
+ *       bytes = channels * (4 * max_taps + 4 * R + 16 + 8)
+ * ONE RUN is one kernel behind the queued stores, one lane per channel.  A wave whose present lanes share one T <= 64 keeps the
+ * weights in registers for the whole run and the window in a sliding register window, eight frames per block; otherwise (lanes
+ * of different T, T above 64, the frames behind a run's last whole block) a lane takes one frame at a time from the tables under
+ * its own bounds.  Both do the same operations in the same order.  A wave without a node copies.  No atomics, no LDS.
+ * 1024 taps are 21 ms at 48 kHz: line and handset echo behind a bulk delay, not a room's tail.
+ * Not here: a frequency-domain form for long tails, a double-talk detector (adapt is the host's), leakage, step-size control, a
+ * residual suppressor, link hops and graph wiring. */
+#define DSPFX_CANCEL_MAX_TAPS 1024u
+#define DSPFX_CANCEL_MAX_DELAY 65535u
+typedef struct dspfx_cancel dspfx_cancel;
+typedef struct dspfx_cancel_desc {
+    uint32_t abi_version;     /* DSPFX_ABI_VERSION */
+    int32_t device;           /* HIP device ordinal */
+    uint32_t n_channels;      /* N */
+    uint32_t max_frames;      /* largest n_frames a run will pass (>= 1) */
+    uint32_t tile_channels;   /* 0 = frame-major; W = channel-tiled, as dspfx_engine_desc */
+    uint32_t max_taps;        /* the longest filter a channel may carry, 1 .. DSPFX_CANCEL_MAX_TAPS */
+    uint32_t max_delay;       /* the longest bulk delay a channel may carry, 0 .. DSPFX_CANCEL_MAX_DELAY frames */
+    uint32_t general_only;    /* 0; 1: every wave takes the frames one at a time (for showing that both bodies give the same bits) */
+} dspfx_cancel_desc;
+/* PURE HOST function (no GPU, no bank): *bytes_out = the device bytes of a bank's tables, channels * (4 * max_taps + 4 * R + 24), R =
+ * max_delay + max_taps + 16 rounded up to a multiple of 8.  channels of 0 or above 2^32 - 256, max_taps outside 1 .. 1024, max_delay above 65535: DSPFX_ERR_INVALID, the reason in
+ * dspfx_cancel_last_error(NULL). */
+int dspfx_cancel_plan(uint64_t channels, uint32_t max_taps, uint32_t max_delay, uint64_t *bytes_out);
+/* A bad descriptor (channels of 0 or above 2^32 - 256, a tile that is not a power of two dividing n_channels, another ABI version,
+ * max_frames of 0, max_taps outside 1 .. 1024, max_delay above 65535) is DSPFX_ERR_INVALID with the reason in
+ * dspfx_cancel_last_error of a NULL bank (kept per thread); all of that is checked before any device work. */
+int dspfx_cancel_create(const dspfx_cancel_desc *desc, dspfx_cancel **out);
+int dspfx_cancel_destroy(dspfx_cancel *a);
+/* The reason of the bank's last failed call; of a NULL bank: of this thread's last failed create or plan. */
+const char *dspfx_cancel_last_error(const dspfx_cancel *a);
+/* mic, ref, out: device blocks of n_frames frames in the desc's layout (1 <= n_frames <= max_frames).  out == mic works in place (a
+ * thread rewrites the elements it read).  No ref, or an out that overlaps ref, refuses the run: DSPFX_ERR_INVALID.  Asynchronous
+ * on `stream`; a run on another stream than the one before first waits (on the device) for that one, since the state is the
+ * bank's (the rules of dspfx_strips_run).  Queued stores go onto the stream ahead of the kernel, in the order they were made. */
+int dspfx_cancel_run(dspfx_cancel *a, const float *mic, const float *ref, float *out, uint32_t n_frames, void *stream);
+/* The node of channels [first_channel, first_channel + count): each array is NULL (keep; a new node: the default) or `count`
+ * values -- host_taps T, host_mu, host_eps, host_delay D, host_adapt 0 / not 0.  The contract of dspfx_dynamics_set: callable from
+ * any thread while runs are in flight, never waits for the device or for a run; the values are staged in page-locked memory and
+ * queued, each store is whole, and a run submitted after the call returns sees it, the runs submitted before it do not. */
+int dspfx_cancel_set(dspfx_cancel *a, const uint32_t *host_taps, const float *host_mu, const float *host_eps, const uint32_t *host_delay,
+                     const uint32_t *host_adapt, uint64_t first_channel, uint64_t count);
+/* Replaces the weights of the channels of the range, every one of which carries a node of n_taps taps: per_channel 0: host_rows is
+ * [n_taps], one row for the range; 1: [count][n_taps], a row per channel; row[k] is w[k].  Queued like a store. */
+int dspfx_cancel_load(dspfx_cancel *a, const float *host_rows, uint32_t n_taps, uint32_t per_channel, uint64_t first_channel, uint64_t count);
+/* Removes the node of the channels of the range: a copy again, and a later set makes a new node.  Queued like a store. */
+int dspfx_cancel_drop(dspfx_cancel *a, uint64_t first_channel, uint64_t count);
+/* Weights and history of the channels of the range back to +0.0; T, mu, eps, delay and adapt stay.  Queued like a store.  Also the
+ * way out for a channel whose weights became NaN. */
+int dspfx_cancel_reset(dspfx_cancel *a, uint64_t first_channel, uint64_t count);
+/* The host tables over [first_channel, first_channel + count), as all stores made so far left them: present 1 / 0; lengths T, 0
+ * without a node; sliders [count][2], mu and eps (0, 0 without a node); delays D; adapting 1 / 0. */
+int dspfx_cancel_present(dspfx_cancel *a, uint32_t *host_present_out, uint64_t first_channel, uint64_t count);
+int dspfx_cancel_lengths(dspfx_cancel *a, uint32_t *host_lengths_out, uint64_t first_channel, uint64_t count);
+int dspfx_cancel_sliders(dspfx_cancel *a, float *host_sliders_out, uint64_t first_channel, uint64_t count);
+int dspfx_cancel_delays(dspfx_cancel *a, uint32_t *host_delays_out, uint64_t first_channel, uint64_t count);
+int dspfx_cancel_adapting(dspfx_cancel *a, uint32_t *host_adapting_out, uint64_t first_channel, uint64_t count);
+/* The device pointer of the weights, float [max_taps][N], row k = w[k] of every channel, +0.0 in the rows k >= a channel's T.  The
+ * pointer never changes; what it holds is valid after a run, on its stream. */
+int dspfx_cancel_weights_view(dspfx_cancel *a, const float **weights_out);
+/* The device pointer of the levels, float [2][N]: sum d * d and sum e * e of the last run, +0.0 without a node. */
+int dspfx_cancel_levels_view(dspfx_cancel *a, const float **levels_out);
+
 /* ---- channel generators: a bank of per-channel Signal Generators -------------------------------------------------------
  * An engine runs one Signal Generator (nodes/signal_gen.rs) with one amplitude, frequency and mode for all N channels.  This bank
  * gives channel c ONE generator of its own, with its own sliders, mode and clock, over N channels in the desc's layout

@@ -1083,6 +1083,94 @@ inline std::uint64_t firs_plan(std::uint64_t channels, std::uint32_t max_taps) {
     return bytes;
 }
 
+// Per-channel adaptive (NLMS) FIR filters (include/dspfx.h, dspfx_cancel_*): channel c may carry one canceller of its own -- T taps
+// (1 .. max_taps) that the device updates every frame, mu, eps, a bulk delay and the switch adapt -- over two device blocks in the
+// layout of tile_channels: mic, the primary input, and ref, the block the channel was sent; out = mic minus the filter's estimate
+// of ref's path into mic.  A node exists from the first set() that names the channel until drop(); a fresh bank copies mic.  In
+// set() a null pointer keeps the node's value (a new node: max_taps taps, mu 0.5, eps 1e-6, delay 0, adapting).
+class ChannelCancellers {
+  public:
+    ChannelCancellers(std::uint32_t channels, std::uint32_t max_taps = 64, std::uint32_t max_delay = 0, std::uint32_t tile_channels = 0,
+                      std::uint32_t max_frames = DSPFX_BUF_SIZE, int device = 0, bool general_only = false) {
+        const dspfx_cancel_desc d{DSPFX_ABI_VERSION, device, channels, max_frames, tile_channels, max_taps, max_delay, general_only ? 1u : 0u};
+        const int rc = dspfx_cancel_create(&d, &p_);
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_cancel_last_error(nullptr) ? dspfx_cancel_last_error(nullptr) : dspfx_strerror(rc));
+    }
+    ~ChannelCancellers() { dspfx_cancel_destroy(p_); }
+    ChannelCancellers(const ChannelCancellers &) = delete;
+    ChannelCancellers &operator=(const ChannelCancellers &) = delete;
+    // device blocks of n_frames -> device block in the same layout (out == mic: in place; out may not overlap ref); asynchronous on `stream`
+    void run(const float *mic, const float *ref, float *out, std::uint32_t n_frames, void *stream = nullptr) {
+        chk(dspfx_cancel_run(p_, mic, ref, out, n_frames, stream));
+    }
+    // the node of channels [first_channel, first_channel + count): each array null (keep) or `count` values.  Any thread; never waits
+    void set(const std::uint32_t *taps, const float *mu, const float *eps, const std::uint32_t *delay, const std::uint32_t *adapt,
+             std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_cancel_set(p_, taps, mu, eps, delay, adapt, first_channel, count));
+    }
+    // the host's double-talk decision for a range: false freezes (the node filters and does not update)
+    void set_adapt(bool adapt, std::uint64_t first_channel, std::uint64_t count) {
+        const std::vector<std::uint32_t> a(count, adapt ? 1u : 0u);
+        chk(dspfx_cancel_set(p_, nullptr, nullptr, nullptr, nullptr, a.data(), first_channel, count));
+    }
+    // a warm start: one row of weights for the range, every channel of which carries a node of row.size() taps
+    void load(const std::vector<float> &row, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_cancel_load(p_, row.data(), (std::uint32_t)row.size(), 0, first_channel, count));
+    }
+    // a row per channel: host_rows is [count][n_taps]
+    void load_rows(const float *host_rows, std::uint32_t n_taps, std::uint64_t first_channel, std::uint64_t count) {
+        chk(dspfx_cancel_load(p_, host_rows, n_taps, 1, first_channel, count));
+    }
+    // the node removed: a copy again, a later set() makes a new node; queued like a store
+    void drop(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_cancel_drop(p_, first_channel, count)); }
+    // weights and history back to +0.0; taps, mu, eps, delay and adapt stay; queued like a store
+    void reset(std::uint64_t first_channel, std::uint64_t count) { chk(dspfx_cancel_reset(p_, first_channel, count)); }
+    // the host tables, as all stores so far left them: 1 / 0; T (0 without a node); the delay; 1 / 0
+    std::vector<std::uint32_t> present(std::uint64_t first_channel, std::uint64_t count) { return table(dspfx_cancel_present, first_channel, count); }
+    std::vector<std::uint32_t> lengths(std::uint64_t first_channel, std::uint64_t count) { return table(dspfx_cancel_lengths, first_channel, count); }
+    std::vector<std::uint32_t> delays(std::uint64_t first_channel, std::uint64_t count) { return table(dspfx_cancel_delays, first_channel, count); }
+    std::vector<std::uint32_t> adapting(std::uint64_t first_channel, std::uint64_t count) { return table(dspfx_cancel_adapting, first_channel, count); }
+    // [count][2]: mu and eps as they were given
+    std::vector<float> sliders(std::uint64_t first_channel, std::uint64_t count) {
+        std::vector<float> v(2 * count);
+        chk(dspfx_cancel_sliders(p_, v.data(), first_channel, count));
+        return v;
+    }
+    // float [max_taps][channels] on the device, row k = w[k], +0.0 in the rows k >= a channel's T; valid after a run, on its stream
+    const float *weights() {
+        const float *w = nullptr;
+        chk(dspfx_cancel_weights_view(p_, &w));
+        return w;
+    }
+    // float [2][channels] on the device: sum d * d and sum e * e of the last run
+    const float *levels() {
+        const float *l = nullptr;
+        chk(dspfx_cancel_levels_view(p_, &l));
+        return l;
+    }
+    dspfx_cancel *raw() { return p_; }
+
+  private:
+    void chk(int rc) {
+        if (rc != DSPFX_OK) throw Error(rc, *dspfx_cancel_last_error(p_) ? dspfx_cancel_last_error(p_) : dspfx_strerror(rc));
+    }
+    std::vector<std::uint32_t> table(int (*get)(dspfx_cancel *, std::uint32_t *, std::uint64_t, std::uint64_t), std::uint64_t first_channel,
+                                     std::uint64_t count) {
+        std::vector<std::uint32_t> m(count);
+        chk(get(p_, m.data(), first_channel, count));
+        return m;
+    }
+    dspfx_cancel *p_ = nullptr;
+};
+
+// The device bytes of a ChannelCancellers bank's tables (dspfx_cancel_plan: a pure host function, no GPU).
+inline std::uint64_t cancel_plan(std::uint64_t channels, std::uint32_t max_taps, std::uint32_t max_delay) {
+    std::uint64_t bytes = 0;
+    const int rc = dspfx_cancel_plan(channels, max_taps, max_delay, &bytes);
+    if (rc != DSPFX_OK) throw Error(rc, dspfx_cancel_last_error(nullptr));
+    return bytes;
+}
+
 // Per-channel Signal Generators (include/dspfx.h, dspfx_gens_*), a source that lives on the device: channel c may carry one
 // generator of its own -- amplitude, frequency, mode (DSPFX_SIG_*) and clock -- over device blocks in the layout of tile_channels; its
 // sample is bit for bit what an engine whose chain is that one Signal Generator writes for it over the same block lengths.  A node
