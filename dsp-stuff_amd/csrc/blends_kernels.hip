@@ -149,7 +149,7 @@ __global__ __launch_bounds__(BWG) void blends_run(BlendArgs g) {
     l.b = SRC == S_BLOCK && node ? g.b + lane0 : nullptr;
     l.bus = SRC == S_BUS && node ? g.bus : nullptr;
     l.ctl = CTL && mixes ? g.ctl + lane0 : nullptr;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
+    // lane_io's each_chunk over the bank's own Rows (up to three streams in) and a separate row of results: its own loop
     const uint32_t nfull = g.nf / F;
     Rows<CPL, F, SRC, CTL> cur, nxt;
     if (nfull) load_chunk<CPL, F, SRC, CTL>(l, s, 0, cur);

@@ -25,6 +25,7 @@
 #include "../../include/dspfx.h"
 #include "channel_bank.hip.h"
 #include "lane_io.hip.h"
+#include "node_steps.hip.h"
 
 namespace {
 
@@ -47,7 +48,7 @@ struct Chan {
     bool on[CPL];
 };
 
-// R rows: envelope.rs:34-52 (Detector::next over full_wave) per detector sample k, then the gain computer on the sample x.
+// R rows: node_steps.hip.h's envelope_step per detector sample k, then the gain computer on the sample x.
 // v holds x and takes the output; k is v itself when there is no key
 template <int CPL, int R>
 __device__ __forceinline__ void dyn_rows(float (&v)[R][CPL], const float (&k)[R][CPL], Chan<CPL> &s) {
@@ -55,11 +56,8 @@ __device__ __forceinline__ void dyn_rows(float (&v)[R][CPL], const float (&k)[R]
     for (int i = 0; i < R; ++i) {
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
-            const float x = v[i][j], kk = k[i][j];
-            const float d = kk < 0.0f ? -kk : kk;
-            const float l = s.env[j];
-            const float gain = l < d ? s.ga[j] : s.gr[j];
-            const float e = __fadd_rn(d, __fmul_rn(__fadd_rn(l, -d), gain));
+            const float x = v[i][j];
+            const float e = envelope_step(k[i][j], s.env[j], s.ga[j], s.gr[j]);
             const float q = e > s.thr[j] ? s.thr[j] / e : 1.0f;      // (a NaN envelope compares false)
             const float y = __fmul_rn(x, __fmul_rn(s.mk[j], q));
             if (s.on[j]) {
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(WG) void dynamics_run(DynArgs a) {
     const size_t lane0 = lay(0, c, a.nf, a.N, a.W), rs = a.W ? a.W : a.N;
     const float *lin = a.in + lane0, *lkey = KEYED ? a.key + lane0 : nullptr;
     float *lout = a.out + lane0;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
+    // lane_io's each_chunk with a second prefetched stream, the key, which the helper does not carry
     const uint32_t nfull = a.nf / F;
     float cur[F][CPL], nxt[F][CPL], kcur[KEYED ? F : 1][CPL], knxt[KEYED ? F : 1][CPL];
     if (nfull) {

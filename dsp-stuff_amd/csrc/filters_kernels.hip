@@ -7,7 +7,7 @@
 // per channel, so a lane owns its channels for the whole run -- four adjacent channels with one 16-byte load and one nontemporal
 // 16-byte store per frame when the layout allows it (lane_io.hip.h), one channel otherwise.  Frames are taken in chunks of F rows
 // and the next chunk's loads are issued ahead of this one's arithmetic.  `stages` is a template parameter: every slot's kind, two
-// slider floats and state float are registers.  The three recurrences are restated here with explicit round-to-nearest operations
+// slider floats and state float are registers.  The three recurrences are node_steps.hip.h's, explicit round-to-nearest operations
 // in the engine's order (chain_kernels.hip.h, K_LOW_PASS, K_HIGH_PASS, K_ENVELOPE), so a channel's bits are those of an Engine that
 // runs its present nodes in slot order.  The kinds differ per lane: before the frame loop the wave ballots once per stage and kind
 // (shapers_kernels.hip's scheme), and per chunk and stage it takes one wave-uniform branch.  One kind in the wave (beside empty
@@ -32,6 +32,7 @@
 #include "../../include/dspfx.h"
 #include "channel_bank.hip.h"
 #include "lane_io.hip.h"
+#include "node_steps.hip.h"
 
 namespace {
 
@@ -58,10 +59,10 @@ struct Lane {
 };
 
 // kind K on R rows of one stage: every value is computed, a channel of kind K keeps the result and the new state; every other
-// channel keeps its sample's own bits.  Nothing is contracted:
-//   LowPass   y = x * (1 - r) + r * z; z = y              (low_pass.rs:36-39)
-//   HighPass  z = x * (1 - r) + r * z; y = x - z          (high_pass.rs:36-39)
-//   Envelope  d = x < 0 ? -x : x; g = z < d ? ga : gr; z = d + (z + (-d)) * g; y = z      (envelope.rs:34-52)
+// channel keeps its sample's own bits.  The steps are node_steps.hip.h's:
+//   LowPass   z = one_pole_step; y = z
+//   HighPass  z = one_pole_step; y = x - z
+//   Envelope  z = envelope_step; y = z
 template <int K, int CPL, int R>
 __device__ __forceinline__ void filt_rows(float (&v)[R][CPL], float (&z)[CPL], const float (&a)[CPL], const float (&b)[CPL], const uint32_t (&kind)[CPL]) {
 #pragma unroll
@@ -71,12 +72,10 @@ __device__ __forceinline__ void filt_rows(float (&v)[R][CPL], float (&z)[CPL], c
             const float x = v[i][j], l = z[j];
             float nz, y;
             if constexpr (K == C_ENV) {
-                const float d = x < 0.0f ? -x : x;
-                const float gain = l < d ? a[j] : b[j];
-                nz = __fadd_rn(d, __fmul_rn(__fadd_rn(l, -d), gain));
+                nz = envelope_step(x, l, a[j], b[j]);
                 y = nz;
             } else {
-                nz = __fadd_rn(__fmul_rn(x, b[j]), __fmul_rn(a[j], l));
+                nz = one_pole_step(x, l, a[j], b[j]);
                 y = K == C_HP ? __fsub_rn(x, nz) : nz;
             }
             const bool mine = kind[j] == (uint32_t)K;
@@ -95,10 +94,8 @@ __device__ __forceinline__ void filt_rows_any(float (&v)[R][CPL], float (&z)[CPL
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             const float x = v[i][j], l = z[j];
-            const float d = x < 0.0f ? -x : x;
-            const float gain = l < d ? a[j] : b[j];
-            const float e = __fadd_rn(d, __fmul_rn(__fadd_rn(l, -d), gain));
-            const float zl = __fadd_rn(__fmul_rn(x, b[j]), __fmul_rn(a[j], l));
+            const float e = envelope_step(x, l, a[j], b[j]);
+            const float zl = one_pole_step(x, l, a[j], b[j]);
             const float hp = __fsub_rn(x, zl);
             const uint32_t k = kind[j];
             z[j] = k == C_ENV ? e : k == C_NONE ? l : zl;
@@ -121,8 +118,8 @@ __device__ __forceinline__ void filt_stages(uint32_t kinds, float (&v)[R][CPL], 
     }
 }
 
-// F, the frame rows per chunk (two chunks are in registers): 4 with four channels per lane -- 80 / 101 / 123 / 152 VGPRs at
-// 1 .. 4 stages, where 8 rows took 138 / 151 / 173 / 202 and ran no faster -- and 8 with one (42 / 58 / 70 / 86 VGPRs).  Scratch is 0 in all eight
+// F, the frame rows per chunk (two chunks are in registers): 4 with four channels per lane -- 78 / 97 / 117 / 144 VGPRs at
+// 1 .. 4 stages, where 8 rows took 138 / 151 / 173 / 202 and ran no faster -- and 8 with one (42 / 54 / 64 / 78 VGPRs).  Scratch is 0 in all eight
 template <int S, int CPL>
 __global__ __launch_bounds__(FWG) void filters_run(FiltArgs a) {
     constexpr int F = CPL == 4 ? 4 : 8;
@@ -155,7 +152,8 @@ __global__ __launch_bounds__(FWG) void filters_run(FiltArgs a) {
     const size_t lane0 = lay(0, c, a.nf, a.N, a.W), rs = a.W ? a.W : a.N;
     const float *lin = a.in + lane0;
     float *lout = a.out + lane0;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
+    // lane_io's each_chunk, written out: with the helper filters_run<4, 4> kept its 152 registers and measured slower than the
+    // spread of five parent runs at 65 536 channels (an empty bank 0.0266 ms for 0.0241, LowPass everywhere 0.0413 for 0.0397)
     const uint32_t nfull = a.nf / F;
     float cur[F][CPL], nxt[F][CPL];
     if (nfull) load_rows<CPL, F>(lin, rs, 0, cur);

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(GWG) void gens_run(GenArgs a) {
     l.cam = CTL && a.cam && node ? a.cam + lane0 : nullptr;
     l.cfr = CTL && a.cfr && node ? a.cfr + lane0 : nullptr;
     l.out = a.out + lane0;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
+    // lane_io's each_chunk over the bank's own Rows (up to three streams in) and with close_block inside the loop: its own loop
     const uint32_t nfull = a.nf / F;
     Rows<CPL, F, CTL> cur, nxt;
     if (nfull) load_chunk<CPL, F, CTL>(l, 0, cur);

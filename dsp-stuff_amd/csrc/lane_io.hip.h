@@ -1,6 +1,8 @@
-// lane_io.hip.h -- how a lane of the per-channel banks (strips, talkers, dynamics, shapers, gens, blends, filters, firs, racks, cancel _kernels.hip) reads and writes the
-// channels it owns for a whole block: CPL adjacent channels in one load and one store per frame, which channels those are
-// (lane_channel), and the host's decision whether CPL may be 4.  Device, and one small host part.  hipcc only.
+// lane_io.hip.h -- how a lane of the per-channel banks (strips, delays, talkers, dynamics, shapers, gens, blends, filters, firs,
+// racks, cancel _kernels.hip) reads and writes the channels it owns for a whole block: CPL adjacent channels in one load and one
+// store per frame, the frame loop of a bank with one stream in and one out (each_chunk: shapers and talkers), which
+// channels a lane's are (lane_channel), and the host's decision whether CPL may be 4.  Device, and one small host part.  hipcc only.
+// What the nodes compute per sample is in node_steps.hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +52,35 @@ template <int CPL, int R>
 __device__ __forceinline__ void store_rows(float *lane, size_t rs, uint32_t f0, const float (&v)[R][CPL]) {
 #pragma unroll
     for (int i = 0; i < R; ++i) storev<CPL, true>(lane + (size_t)(f0 + i) * rs, v[i]);
+}
+
+// the frame loop of a lane over a block of nf frames: whole chunks of F rows, the next one's loads issued ahead of this one's
+// arithmetic; then the rows left, one at a time.  body(v, f0) works on v in place -- float[F][CPL], or float[1][CPL] for a row left --
+// whose first frame is f0; it is a generic lambda marked LANE_BODY, so it is inlined into both loops.  STORE = false: the rows are
+// loaded and run and no block is written (lout is not used)
+#define LANE_BODY __attribute__((always_inline))
+template <int CPL, int F, bool STORE = true, class Body>
+__device__ __forceinline__ void each_chunk(const float *lin, float *lout, size_t rs, uint32_t nf, Body &&body) {
+    const uint32_t nfull = nf / F;
+    float cur[F][CPL], nxt[F][CPL];
+    if (nfull) load_rows<CPL, F>(lin, rs, 0, cur);
+#pragma unroll 1
+    for (uint32_t ch = 0; ch < nfull; ++ch) {
+        if (ch + 1 < nfull) load_rows<CPL, F>(lin, rs, (ch + 1) * F, nxt);
+        body(cur, ch * F);
+        if constexpr (STORE) store_rows<CPL, F>(lout, rs, ch * F, cur);
+#pragma unroll
+        for (int i = 0; i < F; ++i)
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) cur[i][j] = nxt[i][j];
+    }
+#pragma unroll 1
+    for (uint32_t f = nfull * F; f < nf; ++f) {
+        float one[1][CPL];
+        load_rows<CPL, 1>(lin, rs, f, one);
+        body(one, f);
+        if constexpr (STORE) store_rows<CPL, 1>(lout, rs, f, one);
+    }
 }
 
 // the lane's first channel c in a launch of `wg` lanes per workgroup; false past N: the lane has none (CPL > 1 only with

@@ -8,8 +8,8 @@
 // run -- four adjacent channels with one 16-byte load and one nontemporal 16-byte store per frame when the layout allows it and the
 // slot count leaves the registers (lane_io.hip.h; CPL below), two or one otherwise.  Frames are taken in chunks of F rows and the
 // next chunk's loads are issued ahead of this one's arithmetic.  `slots` is a template parameter: every slot's kind, five slider
-// floats and four state floats are registers.  The arithmetic is the merged banks': the one-pole and envelope bodies of
-// filters_kernels.hip and the biquad row of strips_kernels.hip restated, the waveshapers called in chain_kernels.hip.h as
+// floats and four state floats are registers.  The arithmetic is the merged banks': the one-pole, envelope and biquad steps
+// that filters_kernels.hip and strips_kernels.hip call too (node_steps.hip.h), the waveshapers called in chain_kernels.hip.h as
 // shapers_kernels.hip calls them, so a channel's bits are those of the existing banks run slot after slot.  The kinds differ per
 // lane and per slot: before the frame loop the wave ballots once per slot for the kinds its lanes carry (a Distort or Overdrive
 // whose level is below 0.001 is folded into "empty" first, as in shapers), and per chunk and slot it walks the set bits with a
@@ -35,6 +35,7 @@
 #include "chain_kernels.hip.h"
 #include "channel_bank.hip.h"
 #include "lane_io.hip.h"
+#include "node_steps.hip.h"
 
 namespace {
 
@@ -74,18 +75,13 @@ struct Slot {
     uint32_t kind[CPL];          // with the bypasses folded in: C_NONE is a copy
 };
 
-// a where the mask is all ones, b where it is zero (strips_kernels.hip's pick)
-__device__ __forceinline__ float pick(uint32_t mask, float a, float b) {
-    return __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, a) & mask) | (__builtin_bit_cast(uint32_t, b) & ~mask));
-}
-
 // kind K on R rows of one slot: every value is computed, a channel of kind K keeps the result and the new state; every other
 // channel keeps its sample's own bits and its state.  Nothing is contracted:
 //   Gain      y = x * level                                                  (gain.rs:33-37)
-//   BiQuad    y = b0 * x + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2             (strips_kernels.hip band_rows, in that order)
-//   LowPass   y = x * (1 - r) + r * z; z = y                                 (filters_kernels.hip filt_rows)
-//   HighPass  z = x * (1 - r) + r * z; y = x - z
-//   Envelope  d = x < 0 ? -x : x; g = z < d ? ga : gr; z = d + (z + (-d)) * g; y = z
+//   BiQuad    y = biquad_step                                                (node_steps.hip.h, as strips_kernels.hip band_rows)
+//   LowPass   z = one_pole_step; y = z                                       (node_steps.hip.h, as filters_kernels.hip filt_rows)
+//   HighPass  z = one_pole_step; y = x - z
+//   Envelope  z = envelope_step; y = z
 //   the waveshapers: chain_kernels.hip.h, as shapers_kernels.hip shape_rows calls them
 template <int K, int CPL, int R>
 __device__ __forceinline__ void rack_rows(float (&v)[R][CPL], Slot<CPL> &s) {
@@ -99,7 +95,7 @@ __device__ __forceinline__ void rack_rows(float (&v)[R][CPL], Slot<CPL> &s) {
                 v[i][j] = pick(0u - (uint32_t)mine, x * s.p[0][j], x);
             } else if constexpr (K == C_BIQUAD) {
                 const float a1 = s.p[0][j], a2 = s.p[1][j], b0 = s.p[2][j], b1 = s.p[3][j], b2 = s.p[4][j];
-                const float y = b0 * x + b1 * s.st[0][j] + b2 * s.st[1][j] - a1 * s.st[2][j] - a2 * s.st[3][j];
+                const float y = biquad_step(x, a1, a2, b0, b1, b2, s.st[0][j], s.st[1][j], s.st[2][j], s.st[3][j]);
                 const uint32_t m = 0u - (uint32_t)mine;
                 s.st[1][j] = pick(m, s.st[0][j], s.st[1][j]);
                 s.st[0][j] = pick(m, x, s.st[0][j]);
@@ -110,12 +106,10 @@ __device__ __forceinline__ void rack_rows(float (&v)[R][CPL], Slot<CPL> &s) {
                 const float l = s.st[0][j];
                 float nz, y;
                 if constexpr (K == C_ENV) {
-                    const float d = x < 0.0f ? -x : x;
-                    const float gain = l < d ? s.p[0][j] : s.p[1][j];
-                    nz = __fadd_rn(d, __fmul_rn(__fadd_rn(l, -d), gain));
+                    nz = envelope_step(x, l, s.p[0][j], s.p[1][j]);
                     y = nz;
                 } else {
-                    nz = __fadd_rn(__fmul_rn(x, s.p[1][j]), __fmul_rn(s.p[0][j], l));
+                    nz = one_pole_step(x, l, s.p[0][j], s.p[1][j]);
                     y = K == C_HP ? __fsub_rn(x, nz) : nz;
                 }
                 s.st[0][j] = mine ? nz : l;
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(RWG) void racks_run(RackArgs a) {
     const size_t lane0 = lay(0, c, a.nf, a.N, a.W), rs = a.W ? a.W : a.N;
     const float *lin = a.in + lane0;
     float *lout = a.out + lane0;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
+    // lane_io's each_chunk, written out: with the helper racks_run<4, 2, true> takes 261 registers for 253, one wave per SIMD for two
     const uint32_t nfull = a.nf / F;
     float cur[F][CPL], nxt[F][CPL];
     if (nfull) load_rows<CPL, F>(lin, rs, 0, cur);

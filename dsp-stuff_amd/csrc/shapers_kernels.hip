@@ -78,7 +78,7 @@ __device__ __forceinline__ void shape_rows(float (&v)[R][CPL], const Lane<CPL> &
 
 // the kinds in `kinds` (a bit per code, the same in every lane of the wave), one after the other.  HEAVY: the kernel holds the
 // bodies that evaluate in f64 (Tanh, Sin, Atan, Overdrive, Chebyshev) too
-template <int CPL, int R, bool HEAVY>
+template <bool HEAVY, int CPL, int R>
 __device__ __forceinline__ void shape_kinds(uint32_t kinds, float (&v)[R][CPL], const Lane<CPL> &s) {
     while (kinds) {
         const int k = __builtin_ctz(kinds);
@@ -144,27 +144,7 @@ __global__ __launch_bounds__(SWG) void shapers_run(ShapeArgs a) {
     const size_t lane0 = lay(0, c, a.nf, a.N, a.W), rs = a.W ? a.W : a.N;
     const float *lin = a.in + lane0;
     float *lout = a.out + lane0;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
-    const uint32_t nfull = a.nf / F;
-    float cur[F][CPL], nxt[F][CPL];
-    if (nfull) load_rows<CPL, F>(lin, rs, 0, cur);
-#pragma unroll 1
-    for (uint32_t ch = 0; ch < nfull; ++ch) {
-        if (ch + 1 < nfull) load_rows<CPL, F>(lin, rs, (ch + 1) * F, nxt);
-        shape_kinds<CPL, F, HEAVY>(kinds, cur, s);
-        store_rows<CPL, F>(lout, rs, ch * F, cur);
-#pragma unroll
-        for (int i = 0; i < F; ++i)
-#pragma unroll
-            for (int j = 0; j < CPL; ++j) cur[i][j] = nxt[i][j];
-    }
-#pragma unroll 1
-    for (uint32_t f = nfull * F; f < a.nf; ++f) {
-        float one[1][CPL];
-        load_rows<CPL, 1>(lin, rs, f, one);
-        shape_kinds<CPL, 1, HEAVY>(kinds, one, s);
-        store_rows<CPL, 1>(lout, rs, f, one);
-    }
+    each_chunk<CPL, F>(lin, lout, rs, a.nf, [&](auto &v, uint32_t) LANE_BODY { shape_kinds<HEAVY>(kinds, v, s); });
 }
 
 // ---- Fuzz ------------------------------------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@
 #include "../../include/dspfx.h"
 #include "channel_bank.hip.h"
 #include "lane_io.hip.h"
+#include "node_steps.hip.h"
 
 namespace {
 
@@ -62,8 +63,8 @@ struct Chan {
     float g0[CPL], dg[CPL];      // the gated form: the gate, and target - gate
 };
 
-// R rows from frame f0: envelope.rs:34-52 (Detector::next over full_wave) per sample, the block's largest envelope, the gate
-template <int CPL, int R, bool GATED>
+// R rows from frame f0: node_steps.hip.h's envelope_step per sample, the block's largest envelope, the gate
+template <bool GATED, int CPL, int R>
 __device__ __forceinline__ void talk_rows(float (&v)[R][CPL], Chan<CPL> &s, uint32_t f0, float fn) {
 #pragma unroll
     for (int i = 0; i < R; ++i) {
@@ -72,10 +73,7 @@ __device__ __forceinline__ void talk_rows(float (&v)[R][CPL], Chan<CPL> &s, uint
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             const float x = v[i][j];
-            const float d = x < 0.0f ? -x : x;
-            const float l = s.env[j];
-            const float gain = l < d ? s.ga[j] : s.gr[j];
-            const float e = __fadd_rn(d, __fmul_rn(__fadd_rn(l, -d), gain));
+            const float e = envelope_step(x, s.env[j], s.ga[j], s.gr[j]);
             s.env[j] = e;
             if (e > s.lvl[j]) s.lvl[j] = e;      // a NaN or a -0.0 never raises it
             if (GATED) v[i][j] = __fmul_rn(x, __fadd_rn(s.g0[j], __fmul_rn(s.dg[j], r)));
@@ -106,27 +104,7 @@ __global__ __launch_bounds__(WG) void talkers_run(TalkArgs a) {
     const float *lin = a.in + lane0;
     float *lout = GATED ? a.out + lane0 : nullptr;
     const float fn = (float)a.nf;
-    // whole chunks of F rows, the next one's loads issued ahead of this one's arithmetic; then the rows left, one at a time
-    const uint32_t nfull = a.nf / F;
-    float cur[F][CPL], nxt[F][CPL];
-    if (nfull) load_rows<CPL, F>(lin, rs, 0, cur);
-#pragma unroll 1
-    for (uint32_t ch = 0; ch < nfull; ++ch) {
-        if (ch + 1 < nfull) load_rows<CPL, F>(lin, rs, (ch + 1) * F, nxt);
-        talk_rows<CPL, F, GATED>(cur, s, ch * F, fn);
-        if (GATED) store_rows<CPL, F>(lout, rs, ch * F, cur);
-#pragma unroll
-        for (int i = 0; i < F; ++i)
-#pragma unroll
-            for (int j = 0; j < CPL; ++j) cur[i][j] = nxt[i][j];
-    }
-#pragma unroll 1
-    for (uint32_t f = nfull * F; f < a.nf; ++f) {
-        float one[1][CPL];
-        load_rows<CPL, 1>(lin, rs, f, one);
-        talk_rows<CPL, 1, GATED>(one, s, f, fn);
-        if (GATED) store_rows<CPL, 1>(lout, rs, f, one);
-    }
+    each_chunk<CPL, F, GATED>(lin, lout, rs, a.nf, [&](auto &v, uint32_t f0) LANE_BODY { talk_rows<GATED>(v, s, f0, fn); });
     storev<CPL, false>(a.env + c, s.env);
     storev<CPL, false>(a.level + c, s.lvl);
     if (GATED) storev<CPL, false>(a.gate + c, tgt);        // after the block, gate = target

@@ -24,6 +24,7 @@ SHAPES = [(64, 0), (256, 64), (70, 0), (1, 0)]                   # vector lanes;
 THREE = [(64, 0), (256, 64), (70, 0)]
 TWO = [(256, 64), (70, 0)]
 FRAMES = [1, 37, 128]
+EDGES = FRAMES + [4, 8, 9]                                       # the frame loop's boundaries with 4 or 8 rows a chunk: one chunk, two, chunks and a row
 CUTS = (37, 128, 91)
 NX = 256                                                         # the channels of the shared input and of the engines that give the expectations
 RATIOS = (0.0, 0.5, 0.93, 1.0)                                                   # test_one_pole's
@@ -201,7 +202,7 @@ def states(torch, bank):
 
 
 # ---- 1. a fresh bank -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nf", FRAMES)
+@pytest.mark.parametrize("nf", EDGES)
 @pytest.mark.parametrize("n,tile", SHAPES)
 def test_a_fresh_bank_copies(dspfx, torch_cuda, n, tile, nf):
     stages = 1 + (n + nf) % 4
@@ -315,7 +316,7 @@ def test_a_channels_bits_do_not_depend_on_its_neighbours(dspfx, torch_cuda, n, t
 
 
 # ---- 5. in place, layouts, pointers, streams -----------------------------------------------------------------------------
-@pytest.mark.parametrize("nf", FRAMES)
+@pytest.mark.parametrize("nf", EDGES)
 @pytest.mark.parametrize("n,tile", SHAPES)
 def test_in_place_equals_out_of_place(dspfx, torch_cuda, n, tile, nf):
     torch = torch_cuda

@@ -29,6 +29,7 @@ F = np.float32
 SHAPES = [(64, 0), (256, 64), (70, 0), (1, 0)]                   # vector lanes; tiled; scalar lanes with a ragged tail; one channel
 WAVES = [(1028, 256), (261, 64)]                                 # (channels, the channels of one wave): test_wave_kinds_gpu's two shapes
 FRAMES = [1, 37, 128]
+EDGES = FRAMES + [4, 8, 9]                                       # the frame loop's boundaries with 4 or 8 rows a chunk: one chunk, two, chunks and a row
 CUTS = (37, 128, 91)
 NX = TF.NX
 ENGINE_CHANNELS = 24                                             # the channels of a table that are also held to the engine of their chain
@@ -253,7 +254,7 @@ def engine_columns(dspfx, torch, got, table, cols, nf, what, channels=ENGINE_CHA
 
 
 # ---- 1. a fresh bank -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nf", FRAMES)
+@pytest.mark.parametrize("nf", EDGES)
 @pytest.mark.parametrize("n,tile", SHAPES)
 def test_a_fresh_bank_copies(dspfx, torch_cuda, n, tile, nf):
     slots = 1 + (n + nf) % 4
@@ -419,7 +420,7 @@ def test_a_nan_and_an_infinity_in_one_channel_change_no_other_channels_bits(dspf
 
 
 # ---- 6. the run's forms ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nf", FRAMES)
+@pytest.mark.parametrize("nf", EDGES)
 @pytest.mark.parametrize("n,tile", SHAPES)
 def test_in_place_equals_out_of_place(dspfx, torch_cuda, n, tile, nf):
     torch = torch_cuda

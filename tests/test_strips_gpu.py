@@ -130,10 +130,11 @@ def test_same_bits_across_forms(dspfx, torch_cuda):
     assert np.array_equal(bits(o), bits(base[:, :m])), "one channel a lane"
 
 
-@pytest.mark.parametrize("nf", [1, 37])
+@pytest.mark.parametrize("nf", [1, 37, 4, 8, 9])
 @pytest.mark.parametrize("n,tile", [(256, 64), (70, 0)])
 def test_odd_frame_counts(dspfx, torch_cuda, n, tile, nf):
-    """n_frames = 1 and 37: whole chunks and the rows left over; three calls, the state carried between them"""
+    """n_frames = 1 and 37: whole chunks and the rows left over; 4, 8 and 9: the chunk loop's boundaries with 4 or 8 rows a chunk (one
+    chunk and no row left, two chunks, chunks and one row); three calls, the state carried between them"""
     K, flags = 3, 3
     su = Setup(n, K, 31)
     x = S.noise(np.random.default_rng(32), 3 * nf, n)

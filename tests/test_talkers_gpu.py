@@ -135,7 +135,7 @@ def test_selection_over_the_room_shapes(dspfx, torch_cuda, top):
 
 # ---- 3. the gate across a talker change ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("inplace", [False, True])
-@pytest.mark.parametrize("nf", [1, 37, 128])
+@pytest.mark.parametrize("nf", [1, 37, 128, 4, 8, 9])
 @pytest.mark.parametrize("n,tile", TWO)
 def test_gate_across_a_talker_change(dspfx, torch_cuda, n, tile, nf, inplace):
     """loud channels move from one set to another: open stays open, shut stays shut, a ramp up, a ramp down"""
