@@ -930,7 +930,7 @@ class Engine:
             n_frames = x.shape[0]
         if out is None:
             out = x
-        st = C.c_void_p(stream) if stream else None
+        st = _stream(stream)
         if ctl:
             arr = (_Ctl * len(ctl))()
             for i, ((node, param), sig) in enumerate(ctl.items()):
@@ -945,7 +945,7 @@ class Engine:
         """One block with the Output node complete (dspfx_process_bus): `mix` = this block's bus, summed inside the chain
         launch and divided by link_divisor(n_connected) when n_connected != 0."""
         self._chk(self.L.dspfx_process_bus(self.h, _ptr(x), _ptr(side), _ptr(out), _ptr(mix), int(n_frames),
-                                           int(n_connected), C.c_void_p(stream) if stream else None))
+                                           int(n_connected), _stream(stream)))
 
     def process_io(self, ins, outs, n_frames: int, mix=None, stream: int = 0):
         """A graph engine with several input / output blocks (dspfx_process_io): ins[k] = input block k, outs[m] = output
@@ -953,7 +953,7 @@ class Engine:
         ia = (C.c_void_p * max(1, len(ins)))(*[(_ptr(t).value if t is not None else None) for t in ins])
         oa = (C.c_void_p * max(1, len(outs)))(*[(_ptr(t).value if t is not None else None) for t in outs])
         self._chk(self.L.dspfx_process_io(self.h, ia, len(ins), oa, len(outs), _ptr(mix), int(n_frames),
-                                          C.c_void_p(stream) if stream else None))
+                                          _stream(stream)))
         return outs[0]
 
     def process_partials(self, x, out=None, side=None, n_frames: Optional[int] = None, stream: int = 0):
@@ -963,12 +963,12 @@ class Engine:
         if out is None:
             out = x
         self._chk(self.L.dspfx_process_partials(self.h, _ptr(x), _ptr(side), _ptr(out), int(n_frames),
-                                                C.c_void_p(stream) if stream else None))
+                                                _stream(stream)))
         return out
 
     def mix_collect(self, mix, n_frames: int, stream: int = 0):
         """Pipelined mix bus, part 2 (stream B): wait for the chain kernel, reduce partials -> mix[n_frames]."""
-        self._chk(self.L.dspfx_mix_collect(self.h, _ptr(mix), int(n_frames), C.c_void_p(stream) if stream else None))
+        self._chk(self.L.dspfx_mix_collect(self.h, _ptr(mix), int(n_frames), _stream(stream)))
 
     def process_host(self, x: np.ndarray, side: Optional[np.ndarray] = None, want_mix: bool = False, out=None):
         """Host path (numpy in / numpy out): H2D, process, D2H.  `out` may be a caller-provided (e.g. pinned) array."""
@@ -992,7 +992,7 @@ class Engine:
         if n_frames is None:
             n_frames = x.shape[0]
         self._chk(self.L.dspfx_process_pcm(self.h, C.byref(io), _ptr(x), _ptr(side), _ptr(out), _ptr(mix), int(n_frames),
-                                           C.c_void_p(stream) if stream else None))
+                                           _stream(stream)))
         return out
 
     def process_host_pcm(self, x: np.ndarray, out=None, side: Optional[np.ndarray] = None, want_mix: bool = False,
@@ -1015,34 +1015,34 @@ class Engine:
 
     def mix_finish(self, mix, n_frames: int, n_connected: int, stream: int = 0):
         self._chk(self.L.dspfx_mix_finish(self.h, _ptr(mix), int(n_frames), int(n_connected),
-                                          C.c_void_p(stream) if stream else None))
+                                          _stream(stream)))
 
     def mix_allreduce(self, comm: "Comm", mix, n_frames: int, n_connected: int = 0, stream: int = 0):
         """Sum this rank's un-normalised bus over the communicator's ranks (ONE RCCL all-reduce of n_frames floats, in
         place, asynchronous on `stream`), then the Output hop with the global channel count when n_connected != 0."""
         self._chk(self.L.dspfx_mix_allreduce(self.h, comm.h, _ptr(mix), int(n_frames), int(n_connected),
-                                             C.c_void_p(stream) if stream else None))
+                                             _stream(stream)))
 
     def tune_placement(self, x, out, n_frames: int, side=None, stream: int = 0):
         """Re-tune the delay rings' placement with the real chain kernels on the caller's buffers (DSP state is kept)."""
         self._chk(self.L.dspfx_tune_placement(self.h, _ptr(x), _ptr(side), _ptr(out), int(n_frames),
-                                              C.c_void_p(stream) if stream else None))
+                                              _stream(stream)))
 
     def process_mixpipe(self, x, out, mix, n_frames: int, n_connected: int = 0, side=None, stream: int = 0):
         """One block with the mix bus pipelined inside the chain kernel: `mix` receives the bus of the block
         submitted two calls earlier (divided by link_divisor(n_connected) when n_connected != 0)."""
         self._chk(self.L.dspfx_process_mixpipe(self.h, _ptr(x), _ptr(side), _ptr(out), _ptr(mix), int(n_frames),
-                                               int(n_connected), C.c_void_p(stream) if stream else None))
+                                               int(n_connected), _stream(stream)))
 
     def mixpipe_flush(self, mix_older, mix_newer, n_connected: int = 0, stream: int = 0):
         self._chk(self.L.dspfx_mixpipe_flush(self.h, _ptr(mix_older), _ptr(mix_newer), int(n_connected),
-                                             C.c_void_p(stream) if stream else None))
+                                             _stream(stream)))
 
     def link_average(self, srcs, dst, n_frames: int, stream: int = 0):
         """collect_and_average (node.rs:162-194) of `srcs` (device buffers, link order) into `dst`."""
         arr = (C.c_void_p * max(1, len(srcs)))(*[_ptr(t).value for t in srcs])
         self._chk(self.L.dspfx_link_average(self.h, arr, len(srcs), _ptr(dst), int(n_frames),
-                                            C.c_void_p(stream) if stream else None))
+                                            _stream(stream)))
 
     def state_export(self, node: int) -> np.ndarray:
         n = int(self.L.dspfx_state_size(self.h, node))
@@ -1059,10 +1059,10 @@ class Engine:
 
     def fill_noise(self, dst, n_frames: int, n_abs0: int, seed: int = 0x5EED0001, stream: int = 0):
         self._chk(self.L.dspfx_fill_noise(self.h, _ptr(dst), int(n_frames), int(n_abs0) & 0xFFFFFFFF, seed,
-                                          C.c_void_p(stream) if stream else None))
+                                          _stream(stream)))
 
     def sync(self, stream: int = 0):
-        self._chk(self.L.dspfx_sync(self.h, C.c_void_p(stream) if stream else None))
+        self._chk(self.L.dspfx_sync(self.h, _stream(stream)))
 
     def describe(self) -> str:
         buf = C.create_string_buffer(1 << 16)
@@ -1170,6 +1170,39 @@ class _Bank:
         except Exception:
             pass
 
+    def _view(self, addr, shape, typestr="<f4"):
+        """Device memory of the bank's as a torch tensor that shares it."""
+        import torch
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (addr, False), "version": 2}
+        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
+
+
+class _InputBank(_Bank):
+    """What the banks that take blocks in share (pitch, spectrum, resample): blocks pushed into a ring of slots of `_slot_frames`
+    frames each, and the next slot handed out so that an Engine can write its block there."""
+
+    _slot_frames = BUF_SIZE
+
+    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
+        """Append a device block [n_frames][N] (or the tiled form for n_frames); runs what falls due with it (windows, columns).
+        slot_tensor() itself: nothing is copied.  A Resampler's full FIFO raises DspfxError(ERR_STATE) and changes nothing."""
+        if n_frames is None:
+            n_frames = block.numel() // self.channels
+        self._chk(getattr(self.L, f"dspfx_{self._C}_push")(self.h, _ptr(block), int(n_frames), _stream(stream)))
+
+    def slot(self) -> Optional[int]:
+        """Device address of the next slot (None unless the frames pushed are a multiple of the slot's frames -- 128, a Resampler's
+        block_frames -- and, in a Resampler, a slot is free)."""
+        return getattr(self.L, f"dspfx_{self._C}_slot")(self.h)
+
+    def slot_tensor(self):
+        """The next slot as a float32 device tensor of slot frames * N elements over the bank's own memory (valid while the bank
+        lives; None when there is no slot): an Engine writes its block there, then push(slot, frames) copies nothing."""
+        addr = self.slot()
+        return None if addr is None else self._view(addr, (self._slot_frames * self.channels,))
+
 
 class _ChannelBank(_Bank):
     """What the per-channel banks share beyond _Bank: the fields every one of them has, how a store's arguments become a channel
@@ -1238,14 +1271,6 @@ class _ChannelBank(_Bank):
         self._chk(getattr(self.L, f"dspfx_{self._C}_{name}")(self.h, v.ctypes.data_as(C.POINTER(ct)), int(first_channel), n))
         return v
 
-    def _view(self, addr, shape, typestr="<f4"):
-        """A device table of the bank's as a torch tensor that shares its memory."""
-        import torch
-
-        class _Mem:
-            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (addr, False), "version": 2}
-        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
-
     def _frames(self, block, n_frames):
         return block.numel() // self.channels if n_frames is None else n_frames
 
@@ -1267,7 +1292,7 @@ def _plan_bytes(bank, channels, *more) -> int:
     return int(n.value)
 
 
-class PitchBank(_Bank):
+class PitchBank(_InputBank):
     """The Pitch Detector node (nodes/pitch.rs) for N channels (include/dspfx.h, dspfx_pitch_*): blocks pushed in the layout
     of `tile_channels` (as Engine's), a McLeod pitch and clarity per channel for every 1024 frames, held until the next
     window that gives one.  Device tensors in, device tensors out; asynchronous on `stream` like Engine.process."""
@@ -1281,29 +1306,6 @@ class PitchBank(_Bank):
         d = _PitchDesc(ABI_VERSION, self.device, self.channels, self.tile_channels, power_thresh, clarity_thresh, pick_thresh)
         self._create(d)
 
-    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
-        """Append a device block [n_frames][N] (or the tiled form); runs the windows that fall due."""
-        if n_frames is None:
-            n_frames = block.numel() // self.channels if hasattr(block, "numel") else None
-        self._chk(self.L.dspfx_pitch_push(self.h, _ptr(block), int(n_frames), C.c_void_p(stream) if stream else None))
-
-    def slot(self) -> Optional[int]:
-        """Device address of the next 128-frame slot (None unless the frames pushed are a multiple of 128)."""
-        return self.L.dspfx_pitch_slot(self.h)
-
-    def slot_tensor(self):
-        """The next slot as a float32 device tensor of 128 * N elements over the bank's own memory (valid while the bank
-        lives; None when there is no slot): an Engine writes its block there, then push(slot, 128) copies nothing."""
-        import torch
-        addr = self.slot()
-        if addr is None:
-            return None
-
-        class _Slot:
-            __cuda_array_interface__ = {"shape": (BUF_SIZE * self.channels,), "typestr": "<f4", "data": (addr, False),
-                                        "version": 2}
-        return torch.as_tensor(_Slot(), device=torch.device("cuda", self.device))
-
     def set_param(self, which: int, value: float):
         self._chk(self.L.dspfx_pitch_set_param(self.h, int(which), float(value)))
 
@@ -1315,7 +1317,7 @@ class PitchBank(_Bank):
             freq = torch.empty(self.channels, dtype=torch.float32, device=dev)
         if clarity is None:
             clarity = torch.empty(self.channels, dtype=torch.float32, device=dev)
-        self._chk(self.L.dspfx_pitch_read(self.h, _ptr(freq), _ptr(clarity), C.c_void_p(stream) if stream else None))
+        self._chk(self.L.dspfx_pitch_read(self.h, _ptr(freq), _ptr(clarity), _stream(stream)))
         return freq, clarity
 
     def reset(self):
@@ -1348,7 +1350,7 @@ def resample_plan(target_hz: int, value: float, idx: int, n_out: int):
 _PCM_TORCH = {SAMPLE_F32: "float32", SAMPLE_I16: "int16", SAMPLE_U16: "int16", SAMPLE_I32: "int32"}
 
 
-class Resampler(_Bank):
+class Resampler(_InputBank):
     """The output resampler bank (include/dspfx.h, dspfx_resample_*): the reference's output callback (devices.rs:394-498) for
     N channels whose device runs at `target_hz`.  Blocks of engine output (48 kHz, the layout of `tile_channels`, as Engine's)
     are pushed into a FIFO of `slots` slots of `block_frames` frames; pull(n_out) is one callback: n_out device frames of
@@ -1367,29 +1369,9 @@ class Resampler(_Bank):
                           self.target_hz, self.out_format, self.out_channels)
         self._create(d)
 
-    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
-        """Append a device block [n_frames][N] (or the tiled form for n_frames).  slot_tensor() itself: nothing is copied.
-        A full FIFO raises DspfxError(ERR_STATE) and changes nothing."""
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
-        self._chk(self.L.dspfx_resample_push(self.h, _ptr(block), int(n_frames), C.c_void_p(stream) if stream else None))
-
-    def slot(self) -> Optional[int]:
-        """Device address of the next slot (None unless the frames pushed are a multiple of block_frames and a slot is free)."""
-        return self.L.dspfx_resample_slot(self.h)
-
-    def slot_tensor(self):
-        """The next slot as a float32 device tensor of block_frames * N elements over the bank's own memory (valid while the
-        bank lives; None when there is no slot): an Engine writes its block there, then push(slot) copies nothing."""
-        import torch
-        addr = self.slot()
-        if addr is None:
-            return None
-
-        class _Slot:
-            __cuda_array_interface__ = {"shape": (self.block_frames * self.channels,), "typestr": "<f4", "data": (addr, False),
-                                        "version": 2}
-        return torch.as_tensor(_Slot(), device=torch.device("cuda", self.device))
+    @property
+    def _slot_frames(self):
+        return self.block_frames
 
     def pull(self, n_out: int, out=None, stream: int = 0):
         """One output callback -> (out, consumed, underrun).  `out` (made when not given) holds n_out * N device frames of
@@ -1400,7 +1382,7 @@ class Resampler(_Bank):
                               device=torch.device("cuda", self.device))
         used, under = C.c_uint32(0), C.c_int32(0)
         self._chk(self.L.dspfx_resample_pull(self.h, _ptr(out), int(n_out), C.byref(used), C.byref(under),
-                                             C.c_void_p(stream) if stream else None))
+                                             _stream(stream)))
         return out, int(used.value), bool(under.value)
 
     @property
@@ -1454,7 +1436,7 @@ def spectrum_bins(fft_size: int, lower_hz: float, upper_hz: float):
     return k_lo, k_hi, hz[k_lo:k_hi]
 
 
-class SpectrumBank(_Bank):
+class SpectrumBank(_InputBank):
     """The Spectrogram node (nodes/spectrogram.rs) for N channels (include/dspfx.h, dspfx_spectrum_*): blocks pushed in the
     layout of `tile_channels` (as Engine's); every `fft_size` frames one column vol[k] = |FFT(window * x)[k]| * gain[k],
     k in [0, fft_size/2), per channel, the newest `columns` of them kept on the device.  `window` (float32[fft_size]) and
@@ -1480,29 +1462,6 @@ class SpectrumBank(_Bank):
                           self.columns & 0xFFFFFFFF, *(fp() if tab is None else tab.ctypes.data_as(fp) for tab in tables))
         self._create(d)  # the tables are copied before this returns
 
-    def _view(self, addr, elems):
-        import torch
-
-        class _Mem:
-            __cuda_array_interface__ = {"shape": (elems,), "typestr": "<f4", "data": (addr, False), "version": 2}
-        return torch.as_tensor(_Mem(), device=torch.device("cuda", self.device))
-
-    def push(self, block, n_frames: Optional[int] = None, stream: int = 0):
-        """Append a device block [n_frames][N] (or the tiled form); computes the columns that fall due."""
-        if n_frames is None:
-            n_frames = block.numel() // self.channels
-        self._chk(self.L.dspfx_spectrum_push(self.h, _ptr(block), int(n_frames), C.c_void_p(stream) if stream else None))
-
-    def slot(self) -> Optional[int]:
-        """Device address of the next 128-frame slot (None unless the frames pushed are a multiple of 128)."""
-        return self.L.dspfx_spectrum_slot(self.h)
-
-    def slot_tensor(self):
-        """The next slot as a float32 device tensor of 128 * N elements over the bank's own memory (valid while the bank
-        lives; None when there is no slot): an Engine writes its block there, then push(slot, 128) copies nothing."""
-        addr = self.slot()
-        return None if addr is None else self._view(addr, BUF_SIZE * self.channels)
-
     def column(self, age: int = 0):
         """The column `age` windows back (0 = the newest): a float32 device tensor of fft_size/2 * N elements over the bank's
         own memory, no copy -- element (k, c) where frame k of channel c is in a block of fft_size/2 frames (frame-major:
@@ -1511,7 +1470,7 @@ class SpectrumBank(_Bank):
         if age < 0:
             return None
         addr = self.L.dspfx_spectrum_column(self.h, int(age))
-        return None if addr is None else self._view(addr, self.fft_size // 2 * self.channels)
+        return None if addr is None else self._view(addr, (self.fft_size // 2 * self.channels,))
 
     def bins(self, lower_hz: float = 20.0, upper_hz: float = 20000.0):
         """spectrum_bins for this bank's fft_size (the defaults are the node's, spectrogram.rs:200-201)."""
@@ -1606,7 +1565,7 @@ class MixGroups(_Bank):
             n_frames = block.numel() // self.channels
         if out is None:
             out = torch.empty((int(n_frames), self.groups), dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_mixgroups_run(self.h, _ptr(block), int(n_frames), _ptr(out), C.c_void_p(stream) if stream else None))
+        self._chk(self.L.dspfx_mixgroups_run(self.h, _ptr(block), int(n_frames), _ptr(out), _stream(stream)))
         return out
 
     def returns(self, block, n_frames: Optional[int] = None, out=None, buses=None, stream: int = 0):
@@ -1619,7 +1578,7 @@ class MixGroups(_Bank):
         if out is None:
             out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
         self._chk(self.L.dspfx_mixgroups_returns(self.h, _ptr(block), int(n_frames), _ptr(buses) if buses is not None else None,
-                                                 _ptr(out), C.c_void_p(stream) if stream else None))
+                                                 _ptr(out), _stream(stream)))
         return out
 
     def set_gains(self, values, first_channel: int = 0, count: Optional[int] = None):
@@ -1734,7 +1693,7 @@ class Convolver(_Bank):
         import torch
         if out is None:
             out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        self._chk(self.L.dspfx_convolve_run(self.h, _ptr(block), _ptr(out), int(n_frames), C.c_void_p(stream) if stream else None))
+        self._chk(self.L.dspfx_convolve_run(self.h, _ptr(block), _ptr(out), int(n_frames), _stream(stream)))
         return out
 
     def set_taps(self, impulse_response, mode: Optional[int] = None):
@@ -3061,7 +3020,7 @@ class MixMatrix(_Bank):
             n_frames = block.numel() // self.channels
         if out is None:
             out = torch.empty(int(n_frames) * self.channels, dtype=torch.float32, device=torch.device("cuda", self.device))
-        s = C.c_void_p(stream) if stream else None
+        s = _stream(stream)
         if sources is None:
             self._chk(self.L.dspfx_mixmatrix_run(self.h, _ptr(block), int(n_frames), _ptr(out), s))
             return out

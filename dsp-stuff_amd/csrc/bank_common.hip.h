@@ -1,10 +1,11 @@
 // bank_common.hip.h -- what the banks share (pitch, resample, spectrum, convolve, mixgroups, mixmatrix and the per-channel banks
 // strips, delays, talkers, dynamics, shapers, gens, blends, filters _kernels.hip): the desc's layout, 4-channel loads and stores in it, the slot copy,
-// and small host helpers -- all stateless -- and the scaffold of the banks that take live stores: the error holder, the shape /
-// range / table checks of their arguments, open_device, close_bank, release_bank and destroy_bank.  Host and device, hipcc only.
+// and small host helpers -- all stateless --, BankCore, the members a bank's struct starts from, and the scaffold around it: the
+// error holder of the banks that take live stores, the shape / range / table checks of their arguments, create_checks_plain,
+// open_device, close_bank, release_plain / release_bank and destroy_bank.  Host and device, hipcc only.
 // The FFT is in fft_core.hip.h, the staged stores in store_queue.hip.h, a lane's loads and stores of its own channels in
-// lane_io.hip.h, what the per-channel banks share beyond this in channel_bank.hip.h.  A bank's struct, its ring and the rest of
-// create / reset are its own.
+// lane_io.hip.h, what the per-channel banks share beyond this in channel_bank.hip.h, the ring of block slots of the banks that take
+// blocks in (pitch, spectrum, resample) in slot_ring.hip.h.  The rest of a bank's struct and of create / reset are its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -111,7 +112,17 @@ void twiddles(uint32_t n, float2 *out) {
     }
 }
 
-// a call on a stream other than the last one the bank used waits (on the device) for that one; Bank has ev, last, used
+// what every bank has: its desc, the lock of its calls, and the stream order's event and state
+template <class Desc>
+struct BankCore {
+    Desc desc{};
+    std::mutex mu;               // the bank's calls are serialised
+    hipEvent_t ev = nullptr;     // order()
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+
+// a call on a stream other than the last one the bank used waits (on the device) for that one
 template <class Bank>
 hipError_t order(Bank *p, hipStream_t s) {
     hipError_t err = hipSuccess;
@@ -217,7 +228,20 @@ int open_device(const char *name, int device, std::string *err) {
     return DSPFX_OK;
 }
 
-// destroy: no run is inside the bank, its work on the device is done, then `release` frees it.  Bank has mu, desc, last, used
+// create's first lines in the banks that keep no reason (pitch, spectrum, resample, convolve): the arguments, abi_version, the
+// shape, more() -- the bank's own checks of its desc -- and the device.  *out is cleared
+template <class Desc, class Bank, class More>
+int create_checks_plain(const Desc *desc, Bank **out, More more) {
+    if (!desc || !out) return DSPFX_ERR_INVALID;
+    *out = nullptr;
+    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
+    const uint32_t N = desc->channels, W = desc->tile_channels;
+    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
+    const int rc = more();
+    return rc != DSPFX_OK ? rc : open_device(nullptr, desc->device, nullptr);
+}
+
+// destroy: no run is inside the bank, its work on the device is done, then `release` frees it
 template <class Bank>
 void close_bank(Bank *p, void (*release)(Bank *)) {
     {
@@ -228,24 +252,40 @@ void close_bank(Bank *p, void (*release)(Bank *)) {
     release(p);
 }
 
-// a bank's `release`, where there is no more to it: free_tables() frees its device memory (the device is set), then the staged
-// stores' buffers and events, the bank's event, the bank.  Bank has desc, stores (store_queue.hip.h) and ev
+// a bank's `release`, where there is no more to it: free_tables() frees its device memory (the device is set), then the bank's
+// event, the bank
 template <class Bank, class FreeTables>
-void release_bank_by(Bank *p, FreeTables free_tables) {
+void release_plain_by(Bank *p, FreeTables free_tables) {
     (void)hipSetDevice(p->desc.device);
     free_tables();
-    p->stores.free_all();
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
 }
 
-// ... the device pointers in `dev` (nullptr: never allocated)
+// ... of a bank with staged stores (store_queue.hip.h): their buffers and events go behind the tables
+template <class Bank, class FreeTables>
+void release_bank_by(Bank *p, FreeTables free_tables) {
+    release_plain_by(p, [&] {
+        free_tables();
+        p->stores.free_all();
+    });
+}
+
+// the device pointers in `dev` (nullptr: never allocated)
+inline void free_device(std::initializer_list<void *> dev) {
+    for (void *d : dev)
+        if (d) (void)hipFree(d);
+}
+
+// ... the tables being the device pointers in `dev`
+template <class Bank>
+void release_plain(Bank *p, std::initializer_list<void *> dev) {
+    release_plain_by(p, [&] { free_device(dev); });
+}
+
 template <class Bank>
 void release_bank(Bank *p, std::initializer_list<void *> dev) {
-    release_bank_by(p, [&] {
-        for (void *d : dev)
-            if (d) (void)hipFree(d);
-    });
+    release_bank_by(p, [&] { free_device(dev); });
 }
 
 // the body of dspfx_<bank>_destroy

@@ -27,16 +27,11 @@ namespace {
 
 // Desc: the bank's dspfx_<bank>_desc (abi_version, device, n_channels, max_frames, tile_channels, ..); Fields: what a store of its holds
 template <class Desc, class Fields>
-struct ChannelBank : BankError {
+struct ChannelBank : BankError, BankCore<Desc> {      // mu: run / reset / destroy
     typedef StoreQueue<Fields> Stores;
     typedef typename Stores::Store Store;
-    Desc desc{};
-    std::mutex mu;               // run / reset / destroy
     std::mutex smu;              // one store at a time, where a store reads the host tables before it queues (strips': never taken)
     Stores stores;               // its qmu guards the host tables' writes and their readers
-    hipEvent_t ev = nullptr;     // order()
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 // channels [first, first + count) of `call` lie inside the bank; the reason is kept

@@ -448,10 +448,8 @@ struct Extra {
     float divisor = 1.0f;
 };
 
-struct dspfx_convolve {
-    dspfx_convolve_desc desc{};
-    std::mutex mu;                              // run / set_taps / response_* / assign / reset / destroy are serialised
-    uint32_t slots = 0;                         // P_max = partitions of max_taps
+struct dspfx_convolve : BankCore<dspfx_convolve_desc> {     // mu: run / set_taps / response_* / assign / reset / destroy are serialised
+    uint32_t slots = 0;                        // P_max = partitions of max_taps
     uint32_t P = 0;                             // partitions of the response in use
     float divisor = 1.0f;
     float2 *ring = nullptr;                     // [slots][128][N]
@@ -459,11 +457,8 @@ struct dspfx_convolve {
     float2 *acc = nullptr;                      // [128][N]
     float2 *table = nullptr;                    // room for [128][slots]; in use: [128][P]
     float2 *tw = nullptr;                       // [256]
-    hipEvent_t ev = nullptr;
     uint64_t blocks = 0;                        // blocks run since create / reset
     bool silence = false;                       // the next run clears the history first
-    hipStream_t last = nullptr;
-    bool used = false;
     // more than one response (dspfx_convolve_response_add): made by the first add, absent before it
     std::vector<Extra> extra;                   // responses 1, 2, ...
     std::vector<uint16_t> ids_host;             // [N]: the map as the device has it
@@ -475,18 +470,10 @@ struct dspfx_convolve {
 namespace {
 
 void release(dspfx_convolve *p) {
-    (void)hipSetDevice(p->desc.device);
-    if (p->ring) (void)hipFree(p->ring);
-    if (p->prev) (void)hipFree(p->prev);
-    if (p->acc) (void)hipFree(p->acc);
-    if (p->table) (void)hipFree(p->table);
-    if (p->tw) (void)hipFree(p->tw);
-    for (Extra &e : p->extra)
-        if (e.table) (void)hipFree(e.table);
-    if (p->ids) (void)hipFree(p->ids);
-    if (p->resp) (void)hipFree(p->resp);
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
+    release_plain_by(p, [p] {
+        free_device({p->ring, p->prev, p->acc, p->table, p->tw, p->ids, p->resp});
+        for (Extra &e : p->extra) free_device({e.table});
+    });
 }
 
 size_t ring_bytes(const dspfx_convolve *p) { return (size_t)p->slots * M * p->desc.channels * sizeof(float2); }
@@ -563,18 +550,16 @@ extern "C" int dspfx_convolve_plan(const double *taps_reversed, uint32_t n_taps,
 }
 
 extern "C" int dspfx_convolve_create(const dspfx_convolve_desc *desc, dspfx_convolve **out) {
-    if (!desc || !out) return DSPFX_ERR_INVALID;
-    *out = nullptr;
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
-    const uint32_t N = desc->channels, W = desc->tile_channels;
-    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
-    if (desc->mode != DSPFX_FIR_BALANCED && desc->mode != DSPFX_FIR_AVERAGE) return DSPFX_ERR_INVALID;
-    const int rc = check_taps(desc->taps_reversed, desc->n_taps);
+    uint32_t max_taps = 0;
+    const int rc = create_checks_plain(desc, out, [&]() -> int {
+        if (desc->mode != DSPFX_FIR_BALANCED && desc->mode != DSPFX_FIR_AVERAGE) return DSPFX_ERR_INVALID;
+        const int taps_rc = check_taps(desc->taps_reversed, desc->n_taps);
+        if (taps_rc != DSPFX_OK) return taps_rc;
+        max_taps = desc->max_taps ? desc->max_taps : desc->n_taps;
+        return max_taps < desc->n_taps || max_taps > DSPFX_CONVOLVE_MAX_TAPS ? DSPFX_ERR_INVALID : DSPFX_OK;
+    });
     if (rc != DSPFX_OK) return rc;
-    const uint32_t max_taps = desc->max_taps ? desc->max_taps : desc->n_taps;
-    if (max_taps < desc->n_taps || max_taps > DSPFX_CONVOLVE_MAX_TAPS) return DSPFX_ERR_INVALID;
-    const int dev_rc = open_device(nullptr, desc->device, nullptr);
-    if (dev_rc != DSPFX_OK) return dev_rc;
+    const uint32_t N = desc->channels;
     dspfx_convolve *p = new (std::nothrow) dspfx_convolve;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
@@ -611,16 +596,7 @@ extern "C" int dspfx_convolve_create(const dspfx_convolve_desc *desc, dspfx_conv
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_convolve_destroy(dspfx_convolve *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        (void)hipSetDevice(p->desc.device);
-        if (p->used) (void)hipStreamSynchronize(p->last);   // the bank's work is ordered on the last stream it used
-    }
-    release(p);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_convolve_destroy(dspfx_convolve *p) { return destroy_bank(p, release); }
 
 extern "C" int dspfx_convolve_reset(dspfx_convolve *p) {
     if (!p) return DSPFX_ERR_INVALID;

@@ -2,8 +2,7 @@
 //   slot copy     a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store (bank_common.hip.h)
 //   pitch_detect  one window of every channel: McLeod pitch and clarity, 8 bytes of result per channel that has one
 //   pitch_read    the held results into the caller's freq[N] / clarity[N]
-// The window store is a ring of 9 slots of 128 frames, each slot in the desc's layout for a 128-frame block, so an engine
-// can write its output straight into the next slot (dspfx_pitch_slot).  A window is 8 consecutive slots; the ninth is the
+// The window store is a slot ring (slot_ring.hip.h) of 9 slots of 128 frames.  A window is 8 consecutive slots; the ninth is the
 // one being filled while the window before it has not been detected yet (it falls due only with its next frame).
 //
 // pitch_detect, one workgroup of 256 threads per PAIR of channels (c0, c0 + 1): the pair is one complex signal
@@ -30,6 +29,7 @@
 #include "../../include/dspfx.h"
 #include "bank_common.hip.h"
 #include "fft_core.hip.h"
+#include "slot_ring.hip.h"
 
 namespace {
 
@@ -355,44 +355,25 @@ __global__ void pitch_read(const float2 *__restrict__ res, float *__restrict__ f
 
 }  // namespace
 
-struct dspfx_pitch {
-    dspfx_pitch_desc desc{};
-    std::mutex mu;                              // push / read / reset / destroy are serialised
-    float *ring = nullptr;                      // RING slots of 128 x N floats
+struct dspfx_pitch : BankCore<dspfx_pitch_desc> {     // mu: push / read / reset / destroy are serialised
+    SlotRing ring;                              // RING slots of 128 x N floats
     float2 *res = nullptr;                      // [N]
     float2 *tw = nullptr;                       // [FFT_N]
-    hipEvent_t ev = nullptr;
     uint64_t frames = 0;                        // frames pushed since create / reset
     std::atomic<int64_t> windows{0};
     std::atomic<float> th[3];                   // dspfx_pitch_param
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_pitch *p) {
-    (void)hipSetDevice(p->desc.device);
-    if (p->ring) (void)hipFree(p->ring);
-    if (p->res) (void)hipFree(p->res);
-    if (p->tw) (void)hipFree(p->tw);
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_pitch *p) { release_plain(p, {p->ring.base, p->res, p->tw}); }
 
-// frames [f, f + nf) of `block` (n_frames long, starting at stream frame f0) into the ring; nf stays within one slot
-hipError_t copy_in(dspfx_pitch *p, const float *block, uint32_t n_frames, uint64_t f0, uint64_t f, uint32_t nf, hipStream_t s) {
-    const uint32_t N = p->desc.channels, W = p->desc.tile_channels;
-    const uint32_t fa = (uint32_t)(f - f0), g0 = (uint32_t)(f % SLOT);
-    float *slot = p->ring + (size_t)((f / SLOT) % RING) * SLOT * N;
-    if (!W) return launch_copy(block + (size_t)fa * N, slot + (size_t)g0 * N, 1, (size_t)nf * N, 0, 0, s);
-    return launch_copy(block + (size_t)fa * W, slot + (size_t)g0 * W, N / W, (size_t)nf * W, (size_t)n_frames * W,
-                       (size_t)SLOT * W, s);
-}
+// one piece of a push through the slot copy kernel
+hipError_t copy_in(const SlotPiece &c, hipStream_t s) { return launch_copy(c.src, c.dst, c.rows, c.len, c.src_pitch, c.dst_pitch, s); }
 
 hipError_t detect(dspfx_pitch *p, uint64_t w, hipStream_t s) {
     DetArgs a;
-    a.ring = p->ring;
+    a.ring = p->ring.base;
     a.res = p->res;
     a.tw = p->tw;
     a.N = p->desc.channels;
@@ -408,22 +389,19 @@ hipError_t detect(dspfx_pitch *p, uint64_t w, hipStream_t s) {
 }  // namespace
 
 extern "C" int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **out) {
-    if (!desc || !out) return DSPFX_ERR_INVALID;
-    *out = nullptr;
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
-    const uint32_t N = desc->channels, W = desc->tile_channels;
-    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
-    const int dev_rc = open_device(nullptr, desc->device, nullptr);
-    if (dev_rc != DSPFX_OK) return dev_rc;
+    const int rc = create_checks_plain(desc, out, [] { return DSPFX_OK; });
+    if (rc != DSPFX_OK) return rc;
+    const uint32_t N = desc->channels;
     dspfx_pitch *p = new (std::nothrow) dspfx_pitch;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
+    p->ring = {nullptr, RING, SLOT, N, desc->tile_channels};
     p->th[DSPFX_PITCH_POWER] = desc->power_thresh;
     p->th[DSPFX_PITCH_CLARITY] = desc->clarity_thresh;
     p->th[DSPFX_PITCH_PICK] = desc->pick_thresh;
     std::vector<float2> tw(FFT_N);
     twiddles(FFT_N, tw.data());
-    if (hipMalloc((void **)&p->ring, (size_t)RING * SLOT * N * sizeof(float)) != hipSuccess ||
+    if (hipMalloc((void **)&p->ring.base, (size_t)RING * SLOT * N * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->res, (size_t)N * sizeof(float2)) != hipSuccess ||
         hipMalloc((void **)&p->tw, FFT_N * sizeof(float2)) != hipSuccess) {
         (void)hipGetLastError();
@@ -440,22 +418,12 @@ extern "C" int dspfx_pitch_create(const dspfx_pitch_desc *desc, dspfx_pitch **ou
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_pitch_destroy(dspfx_pitch *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        (void)hipSetDevice(p->desc.device);
-        if (p->used) (void)hipStreamSynchronize(p->last);   // the bank's work is ordered on the last stream it used
-    }
-    release(p);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_pitch_destroy(dspfx_pitch *p) { return destroy_bank(p, release); }
 
 extern "C" float *dspfx_pitch_slot(dspfx_pitch *p) {
     if (!p) return nullptr;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->frames % SLOT) return nullptr;
-    return p->ring + (size_t)((p->frames / SLOT) % RING) * SLOT * p->desc.channels;
+    return next_slot(p->ring, p->frames);
 }
 
 // pitch.rs:120-146 per frame position: window w runs once frame 1024 (w + 1) has been pushed too, and before the ring
@@ -463,29 +431,19 @@ extern "C" float *dspfx_pitch_slot(dspfx_pitch *p) {
 extern "C" int dspfx_pitch_push(dspfx_pitch *p, const float *block, uint32_t n_frames, void *stream) {
     if (!p || !block || n_frames == 0) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    const uint32_t N = p->desc.channels;
-    const float *slot = p->frames % SLOT ? nullptr : p->ring + (size_t)((p->frames / SLOT) % RING) * SLOT * N;
-    const bool in_place = block == slot;
+    const bool in_place = block == next_slot(p->ring, p->frames);
     if (in_place && n_frames != SLOT) return DSPFX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP(hipSetDevice(p->desc.device));
-    BANK_HIP(order(p, s));
-    const uint64_t f0 = p->frames, f1 = f0 + n_frames;
-    uint64_t f = f0;
-    for (;;) {
+    return push_pieces(p, p->ring, p->frames, n_frames, s, [&](uint64_t f, uint32_t fa, uint32_t nf) -> int {
         // window w falls due with frame 1024 (w + 1): F >= 1024 (w + 1) + 1.  It is launched before that frame is copied:
         // the copy goes to the ring's ninth slot, never into the window.
-        if (f > 0 && f % WIN == 0 && f1 > f) {
+        if (f > 0 && f % WIN == 0) {
             BANK_HIP(detect(p, f / WIN - 1, s));
             p->windows.fetch_add(1);
         }
-        if (f == f1) break;
-        const uint64_t end = std::min<uint64_t>(f1, (f / SLOT + 1) * SLOT);
-        if (!in_place) BANK_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
-        f = end;
-        p->frames = f;                   // what has been launched so far: a failure part-way leaves a consistent state
-    }
-    return DSPFX_OK;
+        if (!in_place) BANK_HIP(copy_in(piece_of(p->ring, block, n_frames, fa, f, nf), s));
+        return DSPFX_OK;
+    });
 }
 
 extern "C" int dspfx_pitch_set_param(dspfx_pitch *p, int which, float value) {

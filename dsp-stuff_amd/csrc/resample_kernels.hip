@@ -28,6 +28,7 @@
 
 #include "../../include/dspfx.h"
 #include "bank_common.hip.h"
+#include "slot_ring.hip.h"
 #include "pcm_kernels.h"
 #include "pcm_rules.h"
 
@@ -286,10 +287,8 @@ hipError_t launch_silence(int32_t fmt, void *out, size_t n, hipStream_t s) {
 
 }  // namespace
 
-struct dspfx_resample {
-    dspfx_resample_desc desc{};
-    std::mutex mu;                               // every call but plan is serialised
-    float *fifo = nullptr;                       // slots x block_frames x N
+struct dspfx_resample : BankCore<dspfx_resample_desc> {      // mu: every call but plan is serialised
+    SlotRing fifo;                               // slots x block_frames x N
     float *state = nullptr;                      // [16][N]
     PlanRow *dplan = nullptr;                    // [MAX_FRAMES], the table the kernels read
     PlanRow *hplan[PLAN_RING] = {};              // page-locked tables, one per pull in flight
@@ -298,28 +297,22 @@ struct dspfx_resample {
     uint32_t hnext = 0;
     std::vector<uint32_t> adv, depth;            // dspfx_resample_plan's output, before it is packed into rows
     std::vector<double> coeff;
-    hipEvent_t ev = nullptr;
     uint64_t head = 0, tail = 0;                 // frames released / pushed since create or reset
     double value = 0.0;                          // the converter's interpolation_value
     uint32_t idx = 0;                            // the interpolator's idx
     int vec = -1;                                // DSPFX_RESAMPLE_VEC at create: 0 / 1 force the lane width, -1 picks
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
 void release(dspfx_resample *r) {
-    (void)hipSetDevice(r->desc.device);
-    if (r->fifo) (void)hipFree(r->fifo);
-    if (r->state) (void)hipFree(r->state);
-    if (r->dplan) (void)hipFree(r->dplan);
-    for (int i = 0; i < PLAN_RING; ++i) {
-        if (r->hplan[i]) (void)hipHostFree(r->hplan[i]);
-        if (r->hev[i]) (void)hipEventDestroy(r->hev[i]);
-    }
-    if (r->ev) (void)hipEventDestroy(r->ev);
-    delete r;
+    release_plain_by(r, [r] {
+        free_device({r->fifo.base, r->state, r->dplan});
+        for (int i = 0; i < PLAN_RING; ++i) {
+            if (r->hplan[i]) (void)hipHostFree(r->hplan[i]);
+            if (r->hev[i]) (void)hipEventDestroy(r->hev[i]);
+        }
+    });
 }
 
 uint64_t capacity(const dspfx_resample *r) { return (uint64_t)r->desc.slots * r->desc.block_frames; }
@@ -330,14 +323,11 @@ uint32_t input_len_of(uint32_t n_out, uint32_t target_hz) {
     return f >= 4294967040.0f ? 0xFFFFFFFFu : (uint32_t)f;
 }
 
-// frames [f, f + nf) of the FIFO (within one slot) <- frames [fa, fa + nf) of `block`, a block of n_frames in the layout
-hipError_t copy_in(dspfx_resample *r, const float *block, uint32_t n_frames, uint32_t fa, uint64_t f, uint32_t nf, hipStream_t s) {
-    const uint32_t N = r->desc.channels, W = r->desc.tile_channels, BF = r->desc.block_frames;
-    const uint32_t g0 = (uint32_t)(f % BF);
-    float *slot = r->fifo + (size_t)((f / BF) % r->desc.slots) * BF * N;
-    if (!W) return hipMemcpyAsync(slot + (size_t)g0 * N, block + (size_t)fa * N, (size_t)nf * N * sizeof(float), hipMemcpyDeviceToDevice, s);
-    return hipMemcpy2DAsync(slot + (size_t)g0 * W, (size_t)BF * W * sizeof(float), block + (size_t)fa * W,
-                            (size_t)n_frames * W * sizeof(float), (size_t)nf * W * sizeof(float), N / W, hipMemcpyDeviceToDevice, s);
+// one piece of a push through the copy engine
+hipError_t copy_in(const SlotPiece &c, hipStream_t s) {
+    if (!c.dst_pitch) return hipMemcpyAsync(c.dst, c.src, c.len * sizeof(float), hipMemcpyDeviceToDevice, s);
+    return hipMemcpy2DAsync(c.dst, c.dst_pitch * sizeof(float), c.src, c.src_pitch * sizeof(float), c.len * sizeof(float), c.rows,
+                            hipMemcpyDeviceToDevice, s);
 }
 
 }  // namespace
@@ -388,23 +378,22 @@ extern "C" int dspfx_resample_plan(uint32_t target_hz, double *value, uint32_t *
 }
 
 extern "C" int dspfx_resample_create(const dspfx_resample_desc *desc, dspfx_resample **out) {
-    if (!desc || !out) return DSPFX_ERR_INVALID;
-    *out = nullptr;
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0) return DSPFX_ERR_INVALID;
-    const uint32_t N = desc->channels, W = desc->tile_channels;
-    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
-    if (desc->block_frames == 0 || desc->block_frames > MAX_FRAMES || desc->slots < 3 || desc->target_hz == 0) return DSPFX_ERR_INVALID;
-    if (!dspfx::pcm_format_ok(desc->out_format) || !dspfx::pcm_channels_ok(desc->out_channels)) return DSPFX_ERR_INVALID;
-    const int dev_rc = open_device(nullptr, desc->device, nullptr);
-    if (dev_rc != DSPFX_OK) return dev_rc;
+    const int rc = create_checks_plain(desc, out, [desc] {
+        if (desc->block_frames == 0 || desc->block_frames > MAX_FRAMES || desc->slots < 3 || desc->target_hz == 0) return DSPFX_ERR_INVALID;
+        if (!dspfx::pcm_format_ok(desc->out_format) || !dspfx::pcm_channels_ok(desc->out_channels)) return DSPFX_ERR_INVALID;
+        return DSPFX_OK;
+    });
+    if (rc != DSPFX_OK) return rc;
+    const uint32_t N = desc->channels;
     dspfx_resample *r = new (std::nothrow) dspfx_resample;
     if (!r) return DSPFX_ERR_OOM;
     r->desc = *desc;
+    r->fifo = {nullptr, desc->slots, desc->block_frames, N, desc->tile_channels};
     if (const char *e = std::getenv("DSPFX_RESAMPLE_VEC")) r->vec = std::atoi(e) ? 1 : 0;      // experiments: the lane width
     r->adv.resize(MAX_FRAMES);
     r->depth.resize(MAX_FRAMES);
     r->coeff.resize((size_t)MAX_FRAMES * TAPS);
-    if (hipMalloc((void **)&r->fifo, (size_t)capacity(r) * N * sizeof(float)) != hipSuccess ||
+    if (hipMalloc((void **)&r->fifo.base, (size_t)capacity(r) * N * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&r->state, (size_t)TAPS * N * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&r->dplan, (size_t)MAX_FRAMES * sizeof(PlanRow)) != hipSuccess) {
         (void)hipGetLastError();
@@ -431,48 +420,30 @@ extern "C" int dspfx_resample_create(const dspfx_resample_desc *desc, dspfx_resa
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_resample_destroy(dspfx_resample *r) {
-    if (!r) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        (void)hipSetDevice(r->desc.device);
-        if (r->used) (void)hipStreamSynchronize(r->last);    // the bank's work is ordered on the last stream it used
-    }
-    release(r);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_resample_destroy(dspfx_resample *r) { return destroy_bank(r, release); }
 
 extern "C" float *dspfx_resample_slot(dspfx_resample *r) {
     if (!r) return nullptr;
     std::lock_guard<std::mutex> lk(r->mu);
-    const uint32_t BF = r->desc.block_frames;
-    if (r->tail % BF || r->tail - r->head + BF > capacity(r)) return nullptr;
-    return r->fifo + (size_t)((r->tail / BF) % r->desc.slots) * BF * r->desc.channels;
+    if (r->tail - r->head + r->fifo.frames > capacity(r)) return nullptr;       // no slot is free
+    return next_slot(r->fifo, r->tail);
 }
 
 extern "C" int dspfx_resample_push(dspfx_resample *r, const float *block, uint32_t n_frames, void *stream) {
     if (!r || !block || n_frames == 0) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(r->mu);
-    const uint32_t BF = r->desc.block_frames, N = r->desc.channels;
-    const float *slot = r->tail % BF ? nullptr : r->fifo + (size_t)((r->tail / BF) % r->desc.slots) * BF * N;
-    const bool in_place = block == slot;
-    if (in_place && n_frames != BF) return DSPFX_ERR_INVALID;
+    const bool in_place = block == next_slot(r->fifo, r->tail);
+    if (in_place && n_frames != r->fifo.frames) return DSPFX_ERR_INVALID;
     if (r->tail - r->head + n_frames > capacity(r)) return DSPFX_ERR_STATE;
     if (in_place) {                      // nothing to launch: the writer and the pulls are stream-ordered by the caller
         r->tail += n_frames;
         return DSPFX_OK;
     }
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP(hipSetDevice(r->desc.device));
-    BANK_HIP(order(r, s));
-    const uint64_t f0 = r->tail, f1 = f0 + n_frames;
-    for (uint64_t f = f0; f < f1;) {
-        const uint64_t end = std::min<uint64_t>(f1, (f / BF + 1) * BF);
-        BANK_HIP(copy_in(r, block, n_frames, (uint32_t)(f - f0), f, (uint32_t)(end - f), s));
-        f = end;
-        r->tail = f;                     // what has been launched so far: a failure part-way leaves a consistent state
-    }
-    return DSPFX_OK;
+    return push_pieces(r, r->fifo, r->tail, n_frames, s, [&](uint64_t f, uint32_t fa, uint32_t nf) -> int {
+        BANK_HIP(copy_in(piece_of(r->fifo, block, n_frames, fa, f, nf), s));
+        return DSPFX_OK;
+    });
 }
 
 extern "C" int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out, uint32_t *consumed, int32_t *underrun,
@@ -516,7 +487,7 @@ extern "C" int dspfx_resample_pull(dspfx_resample *r, void *out, uint32_t n_out,
     r->hnext = (h + 1) % PLAN_RING;
 
     PullArgs a;
-    a.fifo = r->fifo;
+    a.fifo = r->fifo.base;
     a.state = r->state;
     a.plan = r->dplan;
     a.out = out;

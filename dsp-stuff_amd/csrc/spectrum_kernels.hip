@@ -1,8 +1,7 @@
 // spectrum_kernels.hip -- the Spectrogram bank (include/dspfx.h, dspfx_spectrum_*): nodes/spectrogram.rs:225-268 for N channels.
 //   slot copy        a pushed block (any frame range of it, either layout) into the 128-frame slots of the window store (bank_common.hip.h)
 //   spectrum_column  one window of every channel: vol[k] = |FFT(window * x)[k]| * gain[k], k in [0, n/2), into the history
-// The window store is a ring of n/128 + 1 slots of 128 frames, each slot in the desc's layout for a 128-frame block, so an
-// engine can write its output straight into the next slot (dspfx_spectrum_slot).  A window is n/128 consecutive slots and is
+// The window store is a slot ring (slot_ring.hip.h) of n/128 + 1 slots of 128 frames.  A window is n/128 consecutive slots and is
 // launched with its last frame; the spare slot is the one an engine may already fill while that launch is queued.
 //
 // spectrum_column, one workgroup of 512 threads per RUN of Q adjacent channels: in both layouts the Q samples of a frame are
@@ -32,6 +31,7 @@
 #include "../../include/dspfx.h"
 #include "bank_common.hip.h"
 #include "fft_core.hip.h"
+#include "slot_ring.hip.h"
 
 namespace {
 
@@ -157,58 +157,36 @@ void default_window(uint32_t n, float *w) {
 
 }  // namespace
 
-struct dspfx_spectrum {
-    dspfx_spectrum_desc desc{};
-    std::mutex mu;                              // push / slot / column / reset / destroy are serialised
-    uint32_t ring_slots = 0;                    // n/128 + 1
-    float *ring = nullptr;                      // ring_slots slots of 128 x N floats
+struct dspfx_spectrum : BankCore<dspfx_spectrum_desc> {     // mu: push / slot / column / reset / destroy are serialised
+    SlotRing ring;                              // n/128 + 1 slots of 128 x N floats
     float *cols = nullptr;                      // `columns` columns of n/2 x N floats
     float *win = nullptr;                       // [n]
     float *gain = nullptr;                      // [n/2]
     float2 *tw = nullptr;                       // [n]
-    hipEvent_t ev = nullptr;
     uint64_t frames = 0;                        // frames pushed since create / reset
     std::atomic<int64_t> windows{0};
-    hipStream_t last = nullptr;
-    bool used = false;
 };
 
 namespace {
 
-void release(dspfx_spectrum *p) {
-    (void)hipSetDevice(p->desc.device);
-    if (p->ring) (void)hipFree(p->ring);
-    if (p->cols) (void)hipFree(p->cols);
-    if (p->win) (void)hipFree(p->win);
-    if (p->gain) (void)hipFree(p->gain);
-    if (p->tw) (void)hipFree(p->tw);
-    if (p->ev) (void)hipEventDestroy(p->ev);
-    delete p;
-}
+void release(dspfx_spectrum *p) { release_plain(p, {p->ring.base, p->cols, p->win, p->gain, p->tw}); }
 
 size_t column_elems(const dspfx_spectrum *p) { return (size_t)(p->desc.fft_size / 2) * p->desc.channels; }
 
-// frames [f, f + nf) of `block` (n_frames long, starting at stream frame f0) into the ring; nf stays within one slot
-hipError_t copy_in(dspfx_spectrum *p, const float *block, uint32_t n_frames, uint64_t f0, uint64_t f, uint32_t nf, hipStream_t s) {
-    const uint32_t N = p->desc.channels, W = p->desc.tile_channels;
-    const uint32_t fa = (uint32_t)(f - f0), g0 = (uint32_t)(f % SLOT);
-    float *slot = p->ring + (size_t)((f / SLOT) % p->ring_slots) * SLOT * N;
-    if (!W) return launch_copy(block + (size_t)fa * N, slot + (size_t)g0 * N, 1, (size_t)nf * N, 0, 0, s);
-    return launch_copy(block + (size_t)fa * W, slot + (size_t)g0 * W, N / W, (size_t)nf * W, (size_t)n_frames * W,
-                       (size_t)SLOT * W, s);
-}
+// one piece of a push through the slot copy kernel
+hipError_t copy_in(const SlotPiece &c, hipStream_t s) { return launch_copy(c.src, c.dst, c.rows, c.len, c.src_pitch, c.dst_pitch, s); }
 
 hipError_t column(dspfx_spectrum *p, uint64_t w, hipStream_t s) {
     const uint32_t n = p->desc.fft_size;
     ColArgs a;
-    a.ring = p->ring;
+    a.ring = p->ring.base;
     a.col = p->cols + (size_t)(w % p->desc.columns) * column_elems(p);
     a.win = p->win;
     a.gain = p->gain;
     a.tw = p->tw;
     a.N = p->desc.channels;
     a.W = p->desc.tile_channels;
-    a.slot0 = (uint32_t)((w * (n / SLOT)) % p->ring_slots);
+    a.slot0 = (uint32_t)((w * (n / SLOT)) % p->ring.slots);
     a.vec = (a.W ? a.W : a.N) % 4 == 0;        // the tile divides N; hipMalloc and every slot / column offset are 16-byte aligned then
     switch (n) {
     case 128: return launch_column<7, 128>(a, s);
@@ -234,21 +212,15 @@ extern "C" int dspfx_spectrum_plan(uint32_t fft_size, float *window_out, float *
 }
 
 extern "C" int dspfx_spectrum_create(const dspfx_spectrum_desc *desc, dspfx_spectrum **out) {
-    if (!desc || !out) return DSPFX_ERR_INVALID;
-    *out = nullptr;
-    if (desc->abi_version != DSPFX_ABI_VERSION || desc->channels == 0 || desc->columns == 0) return DSPFX_ERR_INVALID;
-    const uint32_t N = desc->channels, W = desc->tile_channels, n = desc->fft_size;
-    if (W && (!pow2(W) || N % W)) return DSPFX_ERR_INVALID;
-    const int rc = check_size(n);
+    const int rc = create_checks_plain(desc, out, [desc] { return desc->columns == 0 ? DSPFX_ERR_INVALID : check_size(desc->fft_size); });
     if (rc != DSPFX_OK) return rc;
-    const int dev_rc = open_device(nullptr, desc->device, nullptr);
-    if (dev_rc != DSPFX_OK) return dev_rc;
+    const uint32_t N = desc->channels, n = desc->fft_size;
     dspfx_spectrum *p = new (std::nothrow) dspfx_spectrum;
     if (!p) return DSPFX_ERR_OOM;
     p->desc = *desc;
     p->desc.window = nullptr;                   // copied below: the caller's tables are not kept
     p->desc.gain = nullptr;
-    p->ring_slots = n / SLOT + 1;
+    p->ring = {nullptr, n / SLOT + 1, SLOT, N, desc->tile_channels};
     std::vector<float> win(n), gain(n / 2, 1.0f);
     std::vector<float2> tw(n);
     if (desc->window)
@@ -257,7 +229,7 @@ extern "C" int dspfx_spectrum_create(const dspfx_spectrum_desc *desc, dspfx_spec
         default_window(n, win.data());
     if (desc->gain) std::memcpy(gain.data(), desc->gain, (n / 2) * sizeof(float));
     twiddles(n, tw.data());
-    if (hipMalloc((void **)&p->ring, (size_t)p->ring_slots * SLOT * N * sizeof(float)) != hipSuccess ||
+    if (hipMalloc((void **)&p->ring.base, (size_t)p->ring.slots * SLOT * N * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->cols, (size_t)desc->columns * column_elems(p) * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->win, n * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&p->gain, (n / 2) * sizeof(float)) != hipSuccess ||
@@ -277,47 +249,31 @@ extern "C" int dspfx_spectrum_create(const dspfx_spectrum_desc *desc, dspfx_spec
     return DSPFX_OK;
 }
 
-extern "C" int dspfx_spectrum_destroy(dspfx_spectrum *p) {
-    if (!p) return DSPFX_ERR_INVALID;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        (void)hipSetDevice(p->desc.device);
-        if (p->used) (void)hipStreamSynchronize(p->last);   // the bank's work is ordered on the last stream it used
-    }
-    release(p);
-    return DSPFX_OK;
-}
+extern "C" int dspfx_spectrum_destroy(dspfx_spectrum *p) { return destroy_bank(p, release); }
 
 extern "C" float *dspfx_spectrum_slot(dspfx_spectrum *p) {
     if (!p) return nullptr;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->frames % SLOT) return nullptr;
-    return p->ring + (size_t)((p->frames / SLOT) % p->ring_slots) * SLOT * p->desc.channels;
+    return next_slot(p->ring, p->frames);
 }
 
 // spectrogram.rs:225-268 per frame position: window w is frames [n w, n (w + 1)) and runs as soon as the last of them is in
 extern "C" int dspfx_spectrum_push(dspfx_spectrum *p, const float *block, uint32_t n_frames, void *stream) {
     if (!p || !block || n_frames == 0) return DSPFX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    const uint32_t N = p->desc.channels, n = p->desc.fft_size;
-    const float *slot = p->frames % SLOT ? nullptr : p->ring + (size_t)((p->frames / SLOT) % p->ring_slots) * SLOT * N;
-    const bool in_place = block == slot;
+    const uint32_t n = p->desc.fft_size;
+    const bool in_place = block == next_slot(p->ring, p->frames);
     if (in_place && n_frames != SLOT) return DSPFX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    BANK_HIP(hipSetDevice(p->desc.device));
-    BANK_HIP(order(p, s));
-    const uint64_t f0 = p->frames, f1 = f0 + n_frames;
-    for (uint64_t f = f0; f < f1;) {
-        const uint64_t end = std::min<uint64_t>(f1, (f / SLOT + 1) * SLOT);
-        if (!in_place) BANK_HIP(copy_in(p, block, n_frames, f0, f, (uint32_t)(end - f), s));
-        f = end;
-        p->frames = f;                   // what has been launched so far: a failure part-way leaves a consistent state
-        if (f % n == 0) {                // a window ends on a slot boundary (n is a multiple of 128)
-            BANK_HIP(column(p, f / n - 1, s));
+    return push_pieces(p, p->ring, p->frames, n_frames, s, [&](uint64_t f, uint32_t fa, uint32_t nf) -> int {
+        if (!in_place) BANK_HIP(copy_in(piece_of(p->ring, block, n_frames, fa, f, nf), s));
+        p->frames = f + nf;              // the piece is in, whatever becomes of its window
+        if (p->frames % n == 0) {        // a window ends on a slot boundary (n is a multiple of 128)
+            BANK_HIP(column(p, p->frames / n - 1, s));
             p->windows.fetch_add(1);
         }
-    }
-    return DSPFX_OK;
+        return DSPFX_OK;
+    });
 }
 
 extern "C" const float *dspfx_spectrum_column(dspfx_spectrum *p, uint32_t age) {

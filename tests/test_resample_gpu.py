@@ -216,6 +216,46 @@ def test_slot_and_copy_paths_agree(dspfx, torch_cuda):
         assert a[1:] == b[1:] and np.array_equal(a[0], b[0])
 
 
+@pytest.mark.parametrize("n,tile", [(96, 32), (77, 0)])
+def test_pushes_that_straddle_slots_are_bit_identical(dspfx, torch_cuda, n, tile):
+    """pushes of 1, 127, 128, 129, 5 and 250 frames: pieces that end inside a slot, start inside one, cross one and two slot
+    boundaries and wrap the FIFO (tiled: rows of the block at a pitch of its own length into rows of the slot).  Every pull
+    equals the restatement, and the pulls equal those of a second bank fed the same frames in whole 128-frame blocks"""
+    lengths = (1, 127, 128, 129, 5, 250)
+    x = signal(sum(lengths), n, seed=13 + n)
+    cap = 4 * B
+
+    def keep(pair, got, want):
+        assert np.array_equal(got, expected_bytes(dspfx, want, pair.tile, pair.fmt, pair.ch)), pair.pulls
+        pair.last = got.copy()
+
+    def feed(pieces):
+        p = Pair(dspfx, torch_cuda, n, 44100, tile, compare=keep)
+        outs, f = [], 0
+
+        def pull():
+            used, under = p.pull(118)
+            if not under:
+                outs.append((p.last, used))
+            return under
+
+        for m in pieces:
+            while p.bank.available + m > cap:
+                assert not pull()
+            p.push(x[f:f + m])
+            f += m
+        while not pull():
+            pass
+        assert f == len(x) and p.bank.available == len(p.fifo) < B
+        return outs
+
+    ragged = feed(lengths)
+    whole = feed([B] * (len(x) // B))
+    assert len(ragged) == len(whole) >= 4
+    for k, (a, b) in enumerate(zip(ragged, whole)):
+        assert a[1] == b[1] and np.array_equal(a[0], b[0]), k
+
+
 def test_engine_chain5_into_the_slot(dspfx, torch_cuda):
     """an engine writes chain5 output straight into the slot; the pulls equal dspfx_process output fed to the restatement"""
     torch = torch_cuda
